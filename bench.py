@@ -4,7 +4,7 @@ BASELINE.json's north_star; workload = configs[3]: synthetic 10M x 768 fp16
 corpus, batch-64 queries, top-1000, row-sharded over N GPUs with one RCCL
 all-gather + merge per batch).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 A "step" = one batch of 64 queries searched against the whole corpus: local
 shard scan + exact top-k on every rank, all-gather of the partial lists, merge.
@@ -89,7 +89,30 @@ def parse_args():
                          "auto = live when rocprofv3 is on PATH and N=1, else static")
     ap.add_argument("--encoder", default=None,
                     help="bi-encoder of the secondary leg (default: random:bert with hidden = --dim)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's result (scores.npy, ids.npy) to DIR: the inputs "
+                         "are seeded, so two builds run with the same arguments can be compared output for output")
     return ap.parse_args()
+
+
+DUMP_BYTES_MAX = 64_000_000
+
+
+def dump_outputs(out_dir, D, I):
+    """--dump-outputs: the (D, I) a caller of the search receives — scores.npy float32 [B, k] and ids.npy, the int64
+    row ids as float64 (exact below 2**53).  Beyond DUMP_BYTES_MAX in all, a fixed seeded sample of the query rows is
+    kept and named in query_rows.npy; a single row still too large keeps its leading (best-scoring) columns."""
+    import numpy as np
+    B, k = D.shape
+    cols = max(1, min(k, (DUMP_BYTES_MAX - 8) // 12))
+    n_rows = max(1, DUMP_BYTES_MAX // (12 * cols + 8))
+    rows = np.arange(B)
+    os.makedirs(out_dir, exist_ok=True)
+    if n_rows < B:
+        rows = np.sort(np.random.default_rng(0).choice(B, n_rows, replace=False))
+        np.save(os.path.join(out_dir, "query_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "scores.npy"), np.ascontiguousarray(D[rows, :cols], dtype=np.float32))
+    np.save(os.path.join(out_dir, "ids.npy"), np.ascontiguousarray(I[rows, :cols], dtype=np.float64))
 
 
 def visible_gpus():
@@ -388,6 +411,9 @@ def main():
     if args.gpus < 1:
         sys.stderr.write("bench.py: --gpus must be >= 1\n")
         return 2
+    if args.steps < 1 or args.warmup < 0:
+        sys.stderr.write("bench.py: --steps must be >= 1 and --warmup >= 0\n")
+        return 2
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_self(args)      # N fresh ranks (RCCL), rank 0's JSON line relayed; non-zero if any rank fails
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -516,6 +542,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=device if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:   # the merged result is the same on every rank
+        dump_outputs(args.dump_outputs, D.cpu().numpy(), I.cpu().numpy())
 
     # ---- roofline of the dominant kernel (this rank's shard)
     esize = 4 if args.dtype == "f32" else 2

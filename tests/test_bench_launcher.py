@@ -75,6 +75,66 @@ def test_refuses_more_gpus_than_visible():
     assert r.returncode != 0 and r.stdout.strip() == "" and "visible" in r.stderr
 
 
+def test_refuses_zero_steps():
+    r = subprocess.run([sys.executable, BENCH, "--steps", "0"], capture_output=True, text=True)
+    assert r.returncode == 2 and r.stdout.strip() == "" and "--steps" in r.stderr
+
+
+def test_dump_outputs_dtypes_and_size_cap(tmp_path):
+    import numpy as np
+    b = _bench_module()
+    rng = np.random.default_rng(3)
+    D = rng.standard_normal((8, 5)).astype(np.float32)
+    I = rng.integers(0, 10_000_000, size=(8, 5))
+    b.dump_outputs(str(tmp_path / "small"), D, I)
+    assert sorted(os.listdir(tmp_path / "small")) == ["ids.npy", "scores.npy"]
+    s, i = np.load(tmp_path / "small" / "scores.npy"), np.load(tmp_path / "small" / "ids.npy")
+    assert s.dtype == np.float32 and i.dtype == np.float64
+    assert np.array_equal(s, D) and np.array_equal(i, I.astype(np.float64))
+    # beyond the cap: the same seeded sample of query rows every time, named in query_rows.npy, within the cap
+    b.DUMP_BYTES_MAX = 3 * (12 * 5 + 8)
+    for name in ("a", "b"):
+        b.dump_outputs(str(tmp_path / name), D, I)
+    rows = np.load(tmp_path / "a" / "query_rows.npy").astype(np.int64)
+    assert len(rows) == 3 and np.array_equal(rows, np.load(tmp_path / "b" / "query_rows.npy"))
+    assert np.array_equal(np.load(tmp_path / "a" / "scores.npy"), D[rows])
+    assert np.array_equal(np.load(tmp_path / "a" / "ids.npy"), I[rows].astype(np.float64))
+    # one row larger than the cap keeps its leading (best-scoring) columns
+    b.DUMP_BYTES_MAX = 12 * 2 + 8
+    b.dump_outputs(str(tmp_path / "c"), D, I)
+    assert np.array_equal(np.load(tmp_path / "c" / "scores.npy"), D[np.load(tmp_path / "c" / "query_rows.npy").astype(np.int64), :2])
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_is_the_last_step_and_repeats(tmp_path):
+    """`--dump-outputs DIR`: the result of the last timed step (queries[(steps - 1) % 4] of bench.py's seeded set)
+    against the float64 oracle on the same seeded corpus, and the same arrays bit for bit from a second run."""
+    import numpy as np
+    import torch
+    from helpers import check_topk
+    b = _bench_module()
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    rows, dim, k, steps = 100_000, 128, 100, 7
+    dumps = []
+    for name in ("a", "b"):
+        out_dir = str(tmp_path / name)
+        r = subprocess.run([sys.executable, BENCH, "--steps", str(steps), "--warmup", "1", "--rows", str(rows), "--dim",
+                            str(dim), "--k", str(k), "--no-cpu-baseline", "--no-encode-leg", "--no-pipeline-leg",
+                            "--no-read-probe", "--traffic", "off", "--dump-outputs", out_dir],
+                           env=env, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == steps and line["ms_per_step"] > 0
+        dumps.append((np.load(os.path.join(out_dir, "scores.npy")), np.load(os.path.join(out_dir, "ids.npy"))))
+    (D, I), (D2, I2) = dumps
+    assert D.dtype == np.float32 and I.dtype == np.float64 and D.shape == I.shape == (64, k)
+    assert np.array_equal(D, D2) and np.array_equal(I, I2)
+    dev = torch.device("cuda", 0)
+    corpus = b.gen_rows(torch, rows, dim, 1234, torch.float16, dev).float().cpu().numpy()
+    q = b.gen_rows(torch, 64, dim, 4321 + (steps - 1) % 4, torch.float16, dev).float().cpu().numpy()
+    check_topk(D, I.astype(np.int64), corpus, q, k)
+
+
 @pytest.mark.gpu
 def test_bench_gpus_2_starts_two_ranks_by_itself():
     """`python bench.py --gpus 2` as the driver types it, TS_BENCH_BACKEND=gloo because the test box has one GPU
