@@ -45,8 +45,9 @@ extern "C" {
  * (a caller built against version N may load any library whose ts_abi_version() == N; nothing older, nothing
  * newer).  1 = round 1 (24 entry points).  2 = round 2 changed ts_attention_varlen (offsets, window, rotary
  * tables) and added 15 entry points.  3 = round 3 added ts_index_read_probe, ts_index_filter_path and
- * ts_linear_add_layernorm, ts_mlp_add_layernorm.                                                            */
-#define TS_ABI_VERSION 3
+ * ts_linear_add_layernorm, ts_mlp_add_layernorm.  4 = filtered search: ts_index_search_filtered,
+ * ts_index_last_filter_info and ts_bm25_search_batch_filtered (no existing signature changed).             */
+#define TS_ABI_VERSION 4
 
 typedef struct ts_index ts_index; /* opaque */
 
@@ -116,6 +117,35 @@ int ts_index_add(ts_index* h, const void* rows, int64_t n, int32_t rows_dtype,
 int ts_index_search(ts_index* h, const void* queries, int32_t nq,
                     int32_t q_dtype, int32_t k, float* out_scores,
                     int64_t* out_ids, uint32_t flags, void* stream);
+
+/* ---- filtered search -------------------------------------------------------
+ * ts_index_search restricted per query to an allowed set of rows: the result is exactly what
+ * ts_index_search would return on an index holding only the allowed rows, with their original ids
+ * (scores descending, ties by ascending id, padded with id -1 / -FLT_MAX when a query has fewer than k
+ * allowed rows), and every allowed row's score is bit-identical to its score in an unfiltered search.
+ *   allow_bits     n_masks masks of allow_words uint32 words each (device memory; host memory with
+ *                  TS_FLAG_HOST_PTR).  Bit r % 32 of word r / 32 set = local row r allowed (local rows
+ *                  are numbered before ts_index_set_id_offset).  Bits at or beyond ntotal are ignored;
+ *                  allow_words >= ceil(ntotal / 32).
+ *   mask_of_query  HOST array of nq entries in [-1, n_masks); -1 = the query is not filtered.  Queries of
+ *                  one pass may share a mask.
+ * Flags as for ts_index_search: TS_FLAG_HOST_PTR, TS_FLAG_NO_FILTER, TS_FLAG_ASYNC (the masks are read in
+ * stream order; ts_index_finish verifies the search and reports it for a redo like any other).
+ * TS_FLAG_PIPELINE and TS_FLAG_ONE_LAUNCH are ignored for passes with a mask: they take the five-launch
+ * path (the one-launch kernel has no masked form).  Per pass of <= 64 queries the GPU builds the list of
+ * row blocks (32 rows) whose OR over the pass's masks is non-zero, and the scan reads only those.  fp32
+ * storage takes the exact dense path with the masks applied at selection.  Invalid arguments return
+ * TS_ERR_INVALID before any HIP call.                                                                   */
+int ts_index_search_filtered(ts_index* h, const void* queries, int32_t nq, int32_t q_dtype, int32_t k,
+                             const uint32_t* allow_bits, int64_t allow_words, int32_t n_masks,
+                             const int32_t* mask_of_query, float* out_scores, int64_t* out_ids,
+                             uint32_t flags, void* stream);
+/* the last ts_index_search_filtered call on this handle, summed over its passes that had a mask:
+ * [0] row blocks the scans read (live blocks; a pass on the dense path reads them all), [1] row blocks
+ * of the index, [2] passes on the masked filter path, [3] passes on the dense path.  For an asynchronous
+ * call [0] is complete after ts_index_finish.  The redo of a ticket that ts_index_finish reports is a new
+ * ts_index_search_filtered call: read the counters of the submitted searches before it.                */
+int ts_index_last_filter_info(const ts_index* h, int64_t info[4]);
 
 /* ---- all scores, no selection -----------------------------------------------
  * replaces the numpy product in EmbeddingService.similarity (reference
@@ -264,6 +294,16 @@ int ts_bm25_search(ts_bm25* h, const int32_t* term_ids, int32_t n_terms, int32_t
 int ts_bm25_search_batch(ts_bm25* h, const int32_t* term_ids, const int64_t* term_off, int32_t nq,
                          int32_t k, double* out_scores, int64_t* out_ids, int32_t* n_out,
                          void* stream);
+/* ts_bm25_search_batch restricted per query to an allowed set of documents (the masks of
+ * ts_index_search_filtered: n_masks masks of allow_words >= ceil(N / 32) words, bit d % 32 of word d / 32 =
+ * document d allowed; mask_of_query a HOST array, -1 = not filtered).  allow_bits is device memory, host memory
+ * with TS_FLAG_HOST_PTR.  A document outside its query's mask is never scored: the output holds the allowed
+ * documents with a non-zero score only (*n_out < k: all of them), so a caller's zero-score padding must take
+ * allowed documents too.  Allowed documents score exactly as in ts_bm25_search_batch.                      */
+int ts_bm25_search_batch_filtered(ts_bm25* h, const int32_t* term_ids, const int64_t* term_off, int32_t nq,
+                                  int32_t k, const uint32_t* allow_bits, int64_t allow_words, int32_t n_masks,
+                                  const int32_t* mask_of_query, uint32_t flags, double* out_scores,
+                                  int64_t* out_ids, int32_t* n_out, void* stream);
 
 /* ---- fused residual add + LayerNorm (between the GEMMs of the encoder forwards) ---
  * The cross-encoder forward the reference reaches through CrossEncoder.predict

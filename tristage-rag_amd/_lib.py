@@ -42,6 +42,9 @@ SIGNATURES = {
     "ts_index_add": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_uint32, c_void_p]),
     "ts_index_search": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p,
                                   c_void_p, c_uint32, c_void_p]),
+    "ts_index_search_filtered": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int64, c_int32,
+                                           c_void_p, c_void_p, c_void_p, c_uint32, c_void_p]),
+    "ts_index_last_filter_info": (c_int32, [c_void_p, POINTER(c_int64)]),
     "ts_index_scores": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int64, c_void_p]),
     "ts_index_ntotal": (c_int64, [c_void_p]),
     "ts_index_dim": (c_int32, [c_void_p]),
@@ -74,6 +77,8 @@ SIGNATURES = {
                                  POINTER(c_int32), c_void_p]),
     "ts_bm25_search_batch": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p,
                                        c_void_p, c_void_p]),
+    "ts_bm25_search_batch_filtered": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int64, c_int32,
+                                                c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ts_add_layernorm": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_float, c_int64, c_int32, c_void_p,
                                    c_void_p, c_int32, c_int32, c_void_p]),
     "ts_embed_layernorm": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float,

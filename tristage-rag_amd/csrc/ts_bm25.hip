@@ -54,6 +54,10 @@ struct ts_bm25 {
   uint64_t* tau = nullptr;     // [lanes]
   void* steps = nullptr;       // device copy of a batch's per-(token position, lane) posting ranges
   size_t steps_bytes = 0;
+  int64_t* lane_mask = nullptr;  // filtered batches: per chunk and lane, the word offset of the lane's allow mask (-1: none)
+  size_t lane_mask_bytes = 0;
+  uint32_t* mstage = nullptr;    // filtered batches with host masks: their device copy
+  size_t mstage_bytes = 0;
   double* out_s = nullptr;     // [BM_MAX_K]
   int32_t* out_i = nullptr;    // [BM_MAX_K]
   int64_t* term_off = nullptr;  // host copy [V+1]
@@ -100,6 +104,32 @@ __global__ void bm25_accumulate(const int32_t* __restrict__ post_doc, const floa
   const double old = acc[d];
   acc[d] = old + c;
   if (old == 0.0) touched[atomicAdd(n_touched, 1u)] = d;  // contributions are > 0: first touch
+}
+
+// bm25_accumulate for a filtered batch: a document outside the lane's allow mask (word offset moff[y] into
+// bits; -1 = no mask) is skipped, so it is never touched and gets no key in the pre-filter or the select.  The
+// allowed documents receive the same additions in the same order as in an unfiltered search.
+__global__ void bm25_accumulate_masked(const int32_t* __restrict__ post_doc, const float* __restrict__ post_tf,
+                                       const BmStep* __restrict__ st, double k1p1, int64_t N,
+                                       const double* __restrict__ len_norm, double* __restrict__ acc,
+                                       int32_t* __restrict__ touched, uint32_t* __restrict__ counters,
+                                       const uint32_t* __restrict__ bits, const int64_t* __restrict__ moff) {
+#pragma clang fp contract(off)
+  const int y = blockIdx.y;
+  const int64_t off = st[y].off, df = st[y].df;
+  const double idf = st[y].idf;
+  acc += (size_t)y * N; touched += (size_t)y * N;
+  uint32_t* n_touched = counters + 4 * y;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= df) return;
+  const int32_t d = post_doc[off + i];
+  const int64_t mo = moff[y];
+  if (mo >= 0 && !((bits[mo + (d >> 5)] >> (d & 31)) & 1u)) return;
+  const double tf = (double)post_tf[off + i];
+  const double c = idf * ((tf * k1p1) / (tf + len_norm[d]));
+  const double old = acc[d];
+  acc[d] = old + c;
+  if (old == 0.0) touched[atomicAdd(n_touched, 1u)] = d;
 }
 
 __global__ void bm25_reset(const int32_t* __restrict__ touched, const uint32_t* __restrict__ counters,
@@ -333,11 +363,12 @@ extern "C" int ts_bm25_create(int32_t device, ts_bm25** out) {
 
 static void bm25_free(ts_bm25* h) {
   void* bufs[] = {h->post_doc, h->post_tf, h->idf, h->len_norm, h->acc, h->touched, h->counters, h->out_s, h->out_i,
-                  h->keys, h->cand, h->tau, h->batch_buf, h->steps};
+                  h->keys, h->cand, h->tau, h->batch_buf, h->steps, h->lane_mask, h->mstage};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   h->batch_buf = nullptr; h->batch_bytes = 0;
   h->steps = nullptr; h->steps_bytes = 0; h->lanes = 0;
+  h->lane_mask = nullptr; h->lane_mask_bytes = 0; h->mstage = nullptr; h->mstage_bytes = 0;
   h->post_doc = nullptr; h->post_tf = nullptr; h->idf = nullptr; h->len_norm = nullptr; h->acc = nullptr;
   h->touched = nullptr; h->counters = nullptr; h->out_s = nullptr; h->out_i = nullptr;
   h->keys = nullptr; h->cand = nullptr; h->tau = nullptr;
@@ -415,8 +446,10 @@ extern "C" int ts_bm25_set_index(ts_bm25* h, int64_t N, int64_t V, int64_t nnz, 
 // pre-filter (if some lane's postings are long enough to need it) and the two select launches, all with blockIdx.y = lane;
 // results land in rows q0 .. of bs / bi / bc (device).  Accumulators, touched lists and counters are back to zero afterwards.
 // Everything is stream-ordered; `st_host` / `st_dev` hold this chunk's [positions][lanes] posting ranges.
+// Filtered batches: `bits` (device) and `moff` (device, [lanes]: the word offset of each lane's mask, -1 = none).
 static int bm25_enqueue_chunk(ts_bm25* h, const int32_t* term_ids, const int64_t* term_off, int q0, int nl, int32_t k,
-                              double* bs, int32_t* bi, uint32_t* bc, BmStep* st_host, BmStep* st_dev, hipStream_t s) {
+                              double* bs, int32_t* bi, uint32_t* bc, BmStep* st_host, BmStep* st_dev, hipStream_t s,
+                              const uint32_t* bits = nullptr, const int64_t* moff = nullptr) {
   const int L = h->lanes;
   int64_t max_terms = 0, max_total = 0;
   for (int y = 0; y < nl; ++y) max_terms = std::max<int64_t>(max_terms, term_off[q0 + y + 1] - term_off[q0 + y]);
@@ -446,6 +479,11 @@ static int bm25_enqueue_chunk(ts_bm25* h, const int32_t* term_ids, const int64_t
   for (int64_t i = 0; i < max_terms; ++i) {
     if (max_df[(size_t)i] <= 0) continue;
     const int64_t blocks = (max_df[(size_t)i] + 255) / 256;
+    if (moff)
+      hipLaunchKernelGGL(bm25_accumulate_masked, dim3((unsigned)blocks, (unsigned)nl), dim3(256), 0, s, h->post_doc,
+                         h->post_tf, st_dev + (size_t)i * L, h->k1p1, h->N, h->len_norm, h->acc, h->touched, h->counters,
+                         bits, moff);
+    else
     hipLaunchKernelGGL(bm25_accumulate, dim3((unsigned)blocks, (unsigned)nl), dim3(256), 0, s, h->post_doc, h->post_tf,
                        st_dev + (size_t)i * L, h->k1p1, h->N, h->len_norm, h->acc, h->touched, h->counters);
   }
@@ -468,12 +506,65 @@ static int bm25_enqueue_chunk(ts_bm25* h, const int32_t* term_ids, const int64_t
   return TS_OK;
 }
 
+struct BmMasks {
+  const uint32_t* bits;        // device
+  int64_t words;
+  const int32_t* mask_of_query;  // host
+};
+
+static int bm25_batch(ts_bm25* h, const int32_t* term_ids, const int64_t* term_off, int32_t nq, int32_t k,
+                      double* out_scores, int64_t* out_ids, int32_t* n_out, hipStream_t s, const BmMasks* mk);
+
 extern "C" int ts_bm25_search_batch(ts_bm25* h, const int32_t* term_ids, const int64_t* term_off, int32_t nq, int32_t k,
                                     double* out_scores, int64_t* out_ids, int32_t* n_out, void* stream) {
   if (!h || !out_scores || !out_ids || !n_out || !term_off || nq < 0 || k <= 0) {
     ts_set_error("bad arguments to bm25_search_batch");
     return TS_ERR_INVALID;
   }
+  return bm25_batch(h, term_ids, term_off, nq, k, out_scores, out_ids, n_out, (hipStream_t)stream, nullptr);
+}
+
+extern "C" int ts_bm25_search_batch_filtered(ts_bm25* h, const int32_t* term_ids, const int64_t* term_off, int32_t nq,
+                                             int32_t k, const uint32_t* allow_bits, int64_t allow_words, int32_t n_masks,
+                                             const int32_t* mask_of_query, uint32_t flags, double* out_scores,
+                                             int64_t* out_ids, int32_t* n_out, void* stream) {
+  if (!out_scores || !out_ids || !n_out || !term_off || nq < 0 || k <= 0 || n_masks < 0 || allow_words < 0 ||
+      (n_masks > 0 && !allow_bits) || (nq > 0 && !mask_of_query)) {
+    ts_set_error("bad arguments to bm25_search_batch_filtered");
+    return TS_ERR_INVALID;
+  }
+  for (int32_t q = 0; q < nq; ++q) {
+    if (mask_of_query[q] < -1 || mask_of_query[q] >= n_masks) {
+      ts_set_error("bm25_search_batch_filtered: mask_of_query[%d] = %d is outside [-1, %d)", q, mask_of_query[q], n_masks);
+      return TS_ERR_INVALID;
+    }
+  }
+  if (!h) { ts_set_error("null handle"); return TS_ERR_INVALID; }
+  if (n_masks > 0 && allow_words < (h->N + 31) / 32) {
+    ts_set_error("bm25_search_batch_filtered: allow_words = %lld < ceil(N / 32) = %lld", (long long)allow_words,
+                 (long long)((h->N + 31) / 32));
+    return TS_ERR_INVALID;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  BmMasks mk{allow_bits, allow_words, mask_of_query};
+  if ((flags & TS_FLAG_HOST_PTR) && n_masks > 0 && h->N > 0) {
+    Guard g(h->device);
+    const size_t bytes = (size_t)n_masks * (size_t)allow_words * 4;
+    if (bytes > h->mstage_bytes) {
+      TS_HIP(hipStreamSynchronize(s));
+      if (h->mstage) (void)hipFree(h->mstage);
+      h->mstage = nullptr; h->mstage_bytes = 0;
+      TS_HIP(hipMalloc((void**)&h->mstage, bytes));
+      h->mstage_bytes = bytes;
+    }
+    TS_HIP(hipMemcpyAsync(h->mstage, allow_bits, bytes, hipMemcpyHostToDevice, s));
+    mk.bits = h->mstage;
+  }
+  return bm25_batch(h, term_ids, term_off, nq, k, out_scores, out_ids, n_out, s, n_masks > 0 ? &mk : nullptr);
+}
+
+static int bm25_batch(ts_bm25* h, const int32_t* term_ids, const int64_t* term_off, int32_t nq, int32_t k,
+                      double* out_scores, int64_t* out_ids, int32_t* n_out, hipStream_t s, const BmMasks* mk) {
   if (k > BM_MAX_K) { ts_set_error("bm25 top_k %d exceeds %d", k, BM_MAX_K); return TS_ERR_UNSUPPORTED; }
   int64_t max_terms = 0;
   for (int q = 0; q < nq; ++q) {
@@ -486,7 +577,6 @@ extern "C" int ts_bm25_search_batch(ts_bm25* h, const int32_t* term_ids, const i
   }
   if (nq == 0 || h->N == 0) return TS_OK;
   Guard g(h->device);
-  hipStream_t s = (hipStream_t)stream;
   // lanes: as many as the batch has queries, within the workspace budget (64 at most)
   {
     const size_t per_lane = (size_t)h->N * 20 + (size_t)BM_CAND_CAP * 4 + 32;
@@ -514,6 +604,22 @@ extern "C" int ts_bm25_search_batch(ts_bm25* h, const int32_t* term_ids, const i
     h->steps_bytes = (size_t)nchunks * st_count * sizeof(BmStep);
   }
   std::vector<BmStep> st_host((size_t)nchunks * st_count);   // (alive until the synchronisation below: source of async copies)
+  std::vector<int64_t> moff_host(mk ? (size_t)nchunks * L : 0);
+  if (mk) {
+    if ((size_t)nchunks * L * 8 > h->lane_mask_bytes) {
+      if (h->lane_mask) (void)hipFree(h->lane_mask);
+      h->lane_mask = nullptr; h->lane_mask_bytes = 0;
+      TS_HIP(hipMalloc((void**)&h->lane_mask, (size_t)nchunks * L * 8));
+      h->lane_mask_bytes = (size_t)nchunks * L * 8;
+    }
+    for (int c = 0; c < nchunks; ++c)
+      for (int y = 0; y < L; ++y) {
+        const int q = c * L + y;
+        const int32_t m = q < nq ? mk->mask_of_query[q] : -1;
+        moff_host[(size_t)c * L + y] = m < 0 ? -1 : (int64_t)m * mk->words;
+      }
+    TS_HIP(hipMemcpyAsync(h->lane_mask, moff_host.data(), (size_t)nchunks * L * 8, hipMemcpyHostToDevice, s));
+  }
   double* bs = reinterpret_cast<double*>(h->batch_buf);
   int32_t* bi = reinterpret_cast<int32_t*>(bs + (size_t)nq * k);
   uint32_t* bc = reinterpret_cast<uint32_t*>(bi + (size_t)nq * k);
@@ -522,7 +628,8 @@ extern "C" int ts_bm25_search_batch(ts_bm25* h, const int32_t* term_ids, const i
   for (int c = 0; c < nchunks && st == TS_OK; ++c) {
     const int q0 = c * L, nl = std::min(L, nq - q0);
     st = bm25_enqueue_chunk(h, term_ids, term_off, q0, nl, k, bs, bi, bc, st_host.data() + (size_t)c * st_count,
-                            reinterpret_cast<BmStep*>(h->steps) + (size_t)c * st_count, s);
+                            reinterpret_cast<BmStep*>(h->steps) + (size_t)c * st_count, s,
+                            mk ? mk->bits : nullptr, mk ? h->lane_mask + (size_t)c * L : nullptr);
   }
   if (st != TS_OK) {   // a bad term id part-way: leave the handle clean (accumulators / counters) before reporting it
     hipLaunchKernelGGL(bm25_reset, dim3(256, L), dim3(256), 0, s, h->touched, h->counters, h->acc, h->N);

@@ -137,8 +137,52 @@ struct ScanParams {
 
 enum { SCAN_DENSE = 0, SCAN_FILTER = 1 };
 
+// The masked filter scan of filtered searches (scan_masked_kernel, a kernel of its own, so that ScanParams
+// and the kernels that take it stay as they are): work item w is row block live[w], w < *nlive (nwork is
+// then only the grid's upper bound), and a survivor of query q also needs bit (row % 32) of word
+// allow_bits[qmask[q] * allow_words + row / 32]; qmask[q] < 0 allows every row.
+struct MaskedScanParams : ScanParams {
+  const int32_t* live;
+  const uint32_t* nlive;
+  const uint32_t* allow_bits;
+  int64_t allow_words;
+  const int32_t* qmask;   // [64]
+};
+int ts_launch_scan_masked(const TsLayout& L, int qh, const MaskedScanParams& p, int num_cus, hipStream_t stream);
+
 int ts_launch_scan(const TsLayout& L, int mode, int qh, const ScanParams& p,
                    int num_cus, hipStream_t stream);
+
+// ---------------------------------------------------------------- filtered search (masks)
+// One pass of a filtered search: the distinct masks its queries use and each query's mask.
+struct TsMaskPass {
+  int32_t nd;              // distinct masks of the pass
+  int32_t all_live;        // a query of the pass has no mask: every row block is live
+  int32_t dist[TS_MAX_Q];  // mask index of distinct mask d
+  int32_t qmask[TS_MAX_Q]; // mask index of query q (-1: no mask, also for q >= nq)
+  int32_t qd[TS_MAX_Q];    // distinct-mask slot of query q (-1: no mask)
+};
+// Device tables of a filtered pass (ts_index.hip keeps one per workspace set).
+struct TsMaskDev {
+  int32_t qmask[TS_MAX_Q];
+  int32_t qd[TS_MAX_Q];
+  uint32_t popc[TS_MAX_Q];   // allowed rows (< ntotal) of distinct mask d
+  uint32_t need[TS_MAX_Q];   // min(k, allowed rows) of query q: the exactness check (need_check_kernel)
+  uint32_t nlive;            // live row blocks
+  uint32_t pad[63];
+  // followed by int32_t live[nblk]
+};
+// live[] = row blocks whose OR over the pass's masks is non-zero (every block if mp.all_live), *nlive their
+// number, popc[d] = allowed rows of each distinct mask; also writes qmask[] / qd[].  nlive and popc must be
+// zero on entry.
+int ts_launch_live_blocks(const uint32_t* bits, int64_t words, const TsMaskPass& mp, int64_t nblk,
+                          int64_t ntotal, TsMaskDev* md, hipStream_t stream);
+// Thresholds of a filtered pass from the (unfiltered, strided) sample: per query the m_q-th best ALLOWED
+// sample score, m_q = max(min_rank, ceil(over * k * S_q / N_q)), or -FLT_MAX when S_q < m_q; need[q] =
+// min(k, N_q); +FLT_MAX for nq <= q < 64.  Block 0 copies *nlive to *report when report is non-null.
+int ts_launch_tau_masked(const float* sample, int64_t S, int64_t sstride, int64_t ntotal, const uint32_t* bits,
+                         int64_t words, TsMaskDev* md, int nq, int k, uint32_t over, uint32_t min_rank,
+                         float* tau, uint32_t* report, hipStream_t stream);
 // LDS bytes the scan kernel needs for qh*32 queries (Q image + candidate staging)
 size_t ts_scan_lds_bytes(const TsLayout& L, int qh);
 // fp32 storage, 32-query passes, 512 < d <= 768: the bf16x3 split scan (ts_scan_f32s.hip) instead of the exact-f32 MFMA
@@ -222,6 +266,12 @@ struct SelParams {
   uint32_t* clear_counts;  // optional: n_per_q is given back as zeros (the one-launch search has no
                            // preparation kernel that would clear it)
 };
+// filtered searches: the dense path's per-chunk ids (row, or -1 outside the query's mask) for SEL_PAIRS32 over
+// the dense scores, and the exactness check of a masked pass (TS_STATUS_SHORT if cand_cnt[q] < need[q])
+int ts_launch_mask_ids(const uint32_t* bits, int64_t words, const TsMaskPass& mp, int nq, int64_t row0,
+                       uint32_t rows, int64_t ld, int32_t* ids, hipStream_t stream);
+int ts_launch_need_check(const uint32_t* cand_cnt, const uint32_t* need, int nq, uint32_t* status,
+                         uint32_t* host_report, hipStream_t stream);
 
 int ts_launch_select(const SelParams& p, int nq, hipStream_t stream);
 

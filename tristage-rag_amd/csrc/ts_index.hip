@@ -104,12 +104,18 @@ struct ts_index {
   uint4* corpus = nullptr;
   int64_t id_offset = 0;
   int64_t info[4] = {0, 0, 0, 0};
+  // the last filtered search (ts_index_last_filter_info): live row blocks read, row blocks, masked passes,
+  // passes on the dense path; fseq numbers filtered calls, so that ts_index_finish adds the live counts of
+  // the last one only
+  int64_t finfo[4] = {0, 0, 0, 0};
+  int64_t fseq = 0;
   // Per-search workspace, double-buffered so that consecutive pipelined searches never
   // share a buffer that is still being read (see search_pass).
   struct WSet {
     DevBuf qimg, small, cand_score, cand_id, sample;
     DevBuf dense, list_score, list_id;   // the dense path's score chunk and per-chunk lists
     DevBuf hist, spill;                  // one-launch search (ts_fused.hip): threshold histogram, parked score tiles
+    DevBuf mask, mids;                   // filtered searches: TsMaskDev + live-block list; the dense path's masked ids
     uint32_t gen = 0;                    // generation tag of the last one-launch search on this set
     uint32_t arrive_total = 0;           // running goal of the set's arrival hint counter
     bool hist_dirty = false;             // a launch may have left entries behind: cleared before the next one
@@ -136,12 +142,12 @@ struct ts_index {
   bool slot_busy[TS_ASYNC_SLOTS] = {};
   hipStream_t s_pro = nullptr, s_scan = nullptr, s_sel = nullptr;  // TS_FLAG_PIPELINE only
   // staging of host-pointer calls (add / reconstruct need exclusive access anyway; searches: host_mu)
-  DevBuf stage, den, qstage, out_s, out_i;
+  DevBuf stage, den, qstage, out_s, out_i, mstage;
   uint32_t* host_status = nullptr;  // pinned + mapped: written by the select kernel
   uint32_t* host_status_dev = nullptr;  // device view of host_status
   // asynchronous searches (TS_FLAG_ASYNC): each pass reports into its own slot of
   // the mapped host ring; ts_index_finish() syncs once and inspects them all
-  struct Pending { int64_t ticket; int slot; int nq; uint32_t S; uint32_t m; hipEvent_t e0, e1; int set; };
+  struct Pending { int64_t ticket; int slot; int nq; uint32_t S; uint32_t m; hipEvent_t e0, e1; int set; int64_t fseq; };
   Pending pending[TS_ASYNC_SLOTS];
   int npending = 0;
   uint64_t slot_next = 0;
@@ -281,11 +287,11 @@ extern "C" int ts_index_destroy(ts_index* h) {
   DeviceGuard g(h->device);
   (void)hipDeviceSynchronize();
   if (h->corpus) (void)hipFree(h->corpus);
-  DevBuf* bufs[] = {&h->stage, &h->den, &h->qstage, &h->out_s, &h->out_i};
+  DevBuf* bufs[] = {&h->stage, &h->den, &h->qstage, &h->out_s, &h->out_i, &h->mstage};
   for (DevBuf* b : bufs) release(*b);
   for (ts_index::WSet& w : h->ws) {
     DevBuf* wb[] = {&w.qimg, &w.small, &w.cand_score, &w.cand_id, &w.sample, &w.dense, &w.list_score, &w.list_id,
-                    &w.hist, &w.spill};
+                    &w.hist, &w.spill, &w.mask, &w.mids};
     for (DevBuf* b : wb) release(*b);
     hipEvent_t evs[] = {w.ev_pro, w.ev_scan, w.ev_sel, w.ev_in};
     for (hipEvent_t e : evs)
@@ -402,13 +408,21 @@ extern "C" int ts_index_reconstruct(ts_index* h, int64_t row0, int64_t n, float*
 }
 
 // ------------------------------------------------------------------ search
+// One pass of a filtered search (ts_index_search_filtered): the masks (device) and the pass's tables.
+struct MaskCtx {
+  const uint32_t* bits;
+  int64_t words;
+  TsMaskPass mp;
+};
+
 static int dense_path(ts_index* h, ts_index::WSet& W, int nq, int qh, int k, float* out_s,
-                      int64_t* out_i, hipStream_t s) {
+                      int64_t* out_i, hipStream_t s, const MaskCtx* mc = nullptr) {
   const int64_t N = h->ntotal;
   const int64_t nblk = (N + TS_ROWS_PER_BLOCK - 1) / TS_ROWS_PER_BLOCK;
   const int64_t chunk_rows = std::min<int64_t>(kDenseChunkRows, nblk * TS_ROWS_PER_BLOCK);
   const int64_t nch = (nblk * TS_ROWS_PER_BLOCK + chunk_rows - 1) / chunk_rows;
   TS_CHECK(ensure(W.dense, (size_t)nq * chunk_rows * 4));
+  if (mc) TS_CHECK(ensure(W.mids, (size_t)nq * chunk_rows * 4));
   if (nch > 1) {
     TS_CHECK(ensure(W.list_score, (size_t)nq * nch * k * 4));
     TS_CHECK(ensure(W.list_id, (size_t)nq * nch * k * 4));
@@ -435,6 +449,14 @@ static int dense_path(ts_index* h, ts_index::WSet& W, int nq, int qh, int k, flo
     p.n = (uint32_t)rows;
     p.id_base = (int32_t)row0;
     p.k = k;
+    if (mc) {
+      // filtered: the rows outside a query's mask get id -1 and with it no rank (SEL_PAIRS32 skips them),
+      // so the result is padded with -1 / -FLT_MAX, never with disallowed rows
+      TS_CHECK(ts_launch_mask_ids(mc->bits, mc->words, mc->mp, nq, row0, (uint32_t)rows, chunk_rows,
+                                  (int32_t*)W.mids.p, s));
+      p.mode = SEL_PAIRS32;
+      p.ids32 = (const int32_t*)W.mids.p;
+    }
     if (nch == 1) {
       p.out_scores = out_s;
       p.out_ids64 = out_i;
@@ -610,26 +632,47 @@ static void set_info(ts_index* h, int64_t a, int64_t b, int64_t c, int64_t d) {
 }
 
 static int search_pass_on(ts_index* h, ts_index::WSet& W, const void* dq, int nq, int q_dtype, int k,
-                          float* out_s, int64_t* out_i, uint32_t flags, hipStream_t s);
+                          float* out_s, int64_t* out_i, uint32_t flags, hipStream_t s, const MaskCtx* mc);
 
 static int search_pass(ts_index* h, const void* dq, int nq, int q_dtype, int k, float* out_s,
-                       int64_t* out_i, uint32_t flags, hipStream_t s) {
+                       int64_t* out_i, uint32_t flags, hipStream_t s, const MaskCtx* mc = nullptr) {
   // per-phase timing shares one set of events per handle: profiled searches run one at a time
   std::unique_lock<std::mutex> plk(h->prof_mu, std::defer_lock);
   if (h->profiling) plk.lock();
   ts_index::WSet* W = acquire_set(h);
-  const int st = search_pass_on(h, *W, dq, nq, q_dtype, k, out_s, out_i, flags, s);
+  const int st = search_pass_on(h, *W, dq, nq, q_dtype, k, out_s, out_i, flags, s, mc);
   release_set(h, W);
   return st;
 }
 
+// ts_index_last_filter_info: one pass of the filtered call `fseq` (a later call has reset the counters)
+static void add_filter_info(ts_index* h, int64_t fseq, int64_t live, int64_t blocks, bool dense) {
+  std::lock_guard<std::mutex> lk(h->mu);
+  if (fseq != h->fseq) return;
+  h->finfo[0] += live;
+  h->finfo[1] += blocks;
+  h->finfo[dense ? 3 : 2] += 1;
+}
+
+// Filtered passes (mc != null) take the five-launch path with the live-block list and the masked scan
+// (f16 / bf16 storage), or the dense path with masked selection (fp32 storage, small corpora, large k,
+// TS_FLAG_NO_FILTER, fallback).
+
 static int search_pass_on(ts_index* h, ts_index::WSet& W, const void* dq, int nq, int q_dtype, int k,
-                          float* out_s, int64_t* out_i, uint32_t flags, hipStream_t s) {
+                          float* out_s, int64_t* out_i, uint32_t flags, hipStream_t s, const MaskCtx* mc) {
   const int64_t N = h->ntotal;
   const int64_t nblk = (N + TS_ROWS_PER_BLOCK - 1) / TS_ROWS_PER_BLOCK;
   const int qh = nq > 32 ? 2 : 1;
+  int64_t fseq = 0;
+  if (mc) {
+    // the one-launch kernel has no masked form, and the pipelined schedule is not worth a second copy of it
+    flags &= ~(uint32_t)(TS_FLAG_ONE_LAUNCH | TS_FLAG_PIPELINE);
+    flags |= TS_FLAG_CLASSIC;
+    std::lock_guard<std::mutex> lk(h->mu);
+    fseq = h->fseq;
+  }
   const bool filter = !(flags & TS_FLAG_NO_FILTER) && k <= kMaxFilterK && N >= kMinFilterRows &&
-                      N >= 32 * (int64_t)k;
+                      N >= 32 * (int64_t)k && !(mc && h->L.dtype == TS_F32);
   const bool async = (flags & TS_FLAG_ASYNC) != 0;
   const bool pipe = filter && async && (flags & TS_FLAG_PIPELINE) != 0;
   if (pipe) TS_CHECK(ensure_streams(h));
@@ -662,8 +705,9 @@ static int search_pass_on(ts_index* h, ts_index::WSet& W, const void* dq, int nq
   if (!fused) TS_CHECK(ts_launch_qprep(h->L, dq, q_dtype, nq, qh, (uint4*)W.qimg.p, W.cand_cnt(), W.status(), sP));
   if (!filter) {
     set_info(h, 0, 0, 0, 0);
+    if (mc) add_filter_info(h, fseq, nblk, nblk, true);
     prof_mark(h, pc, 5, s);
-    TS_CHECK(dense_path(h, W, nq, qh, k, out_s, out_i, s));
+    TS_CHECK(dense_path(h, W, nq, qh, k, out_s, out_i, s, mc));
     prof_mark(h, pc, -1, s);
     TS_HIP(hipEventRecord(W.ev_sel, s));
     W.used = true;
@@ -674,6 +718,14 @@ static int search_pass_on(ts_index* h, ts_index::WSet& W, const void* dq, int nq
   }
   int64_t S = 0;
   uint32_t m = 0;
+  // the report slot: the select kernel writes the candidate counts and the status word into it, a filtered
+  // pass's threshold kernel also the live-block count (word 65)
+  SlotGuard slot_guard(h, -1);   // every early return below gives the slot back
+  if (mc) {
+    slot_guard.slot = alloc_slot(h);
+    if (slot_guard.slot < 0) { ts_set_error("no free report slot"); return TS_ERR_INVALID; }
+    for (int i = 0; i < 66; ++i) h->host_status[(size_t)slot_guard.slot * TS_SLOT_WORDS + i] = 0;
+  }
   TS_CHECK(ensure(W.cand_score, (size_t)TS_MAX_Q * kCandCap * 4));
   TS_CHECK(ensure(W.cand_id, (size_t)TS_MAX_Q * kCandCap * 4));
   if (fused) {
@@ -759,8 +811,20 @@ static int search_pass_on(ts_index* h, ts_index::WSet& W, const void* dq, int nq
 #else
   constexpr bool dbg_tau_inf = false;
 #endif
+  TsMaskDev* md = nullptr;
+  if (mc) {
+    // (2') the live-block list of the pass, then per query the m_q-th best ALLOWED sample score
+    TS_CHECK(ensure(W.mask, sizeof(TsMaskDev) + (size_t)nblk * 4));
+    md = (TsMaskDev*)W.mask.p;
+    TS_HIP(hipMemsetAsync(md, 0, sizeof(TsMaskDev), sP));
+    TS_CHECK(ts_launch_live_blocks(mc->bits, mc->words, mc->mp, nblk, N, md, sP));
+    TS_CHECK(ts_launch_tau_masked((const float*)W.sample.p, S, sstride, N, mc->bits, mc->words, md, nq, k,
+                                  (uint32_t)oversample, kMinSampleRank, W.tau(),
+                                  h->host_status_dev + (size_t)slot_guard.slot * TS_SLOT_WORDS + 65, sP));
+  } else {
   TS_CHECK(ts_launch_tau((const float*)W.sample.p, S, dbg_tau_inf ? 0xFFFFFFFFu : (uint32_t)S, m, nq,
                          W.tau(), sP));
+  }
   if (pipe) {
     TS_HIP(hipEventRecord(W.ev_pro, sP));
     TS_HIP(hipStreamWaitEvent(sS, W.ev_pro, 0));
@@ -782,7 +846,18 @@ static int search_pass_on(ts_index* h, ts_index::WSet& W, const void* dq, int nq
   if (dbg_cus > 0) scan_cus = dbg_cus;
 #endif
   prof_mark(h, pc, 3, sS);
+  if (mc) {
+    MaskedScanParams mp{};
+    static_cast<ScanParams&>(mp) = sp;
+    mp.live = reinterpret_cast<const int32_t*>(md + 1);
+    mp.nlive = &md->nlive;
+    mp.allow_bits = mc->bits;
+    mp.allow_words = mc->words;
+    mp.qmask = md->qmask;
+    TS_CHECK(ts_launch_scan_masked(h->L, qh, mp, scan_cus, sS));
+  } else {
   TS_CHECK(ts_launch_scan(h->L, SCAN_FILTER, qh, sp, scan_cus, sS));
+  }
   prof_mark(h, pc, 4, sS);
   }  // five launches
   if (pipe) {
@@ -812,7 +887,7 @@ static int search_pass_on(ts_index* h, ts_index::WSet& W, const void* dq, int nq
   p.stride = kCandCap;
   p.n_per_q = W.cand_cnt();
   p.n_cap = kCandCap;
-  p.need = (uint32_t)std::min<int64_t>(k, N);
+  p.need = mc ? 0u : (uint32_t)std::min<int64_t>(k, N);   // (filtered: need_check_kernel, min(k, N_q))
   p.k = k;
   p.out_scores = out_s;
   p.out_ids64 = out_i;
@@ -823,12 +898,18 @@ static int search_pass_on(ts_index* h, ts_index::WSet& W, const void* dq, int nq
   // the select kernel reports the candidate counts and the status word straight
   // into mapped host memory: no copy kernel between it and the sync; every search in flight
   // has its own slot of the ring
-  const int slot = alloc_slot(h);
-  if (slot < 0) { ts_set_error("no free report slot"); return TS_ERR_INVALID; }
-  SlotGuard slot_guard(h, slot);   // every early return below gives the slot back
+  if (!mc) {
+    slot_guard.slot = alloc_slot(h);
+    if (slot_guard.slot < 0) { ts_set_error("no free report slot"); return TS_ERR_INVALID; }
+  }
+  const int slot = slot_guard.slot;
   uint32_t* rep = h->host_status + (size_t)slot * TS_SLOT_WORDS;
   p.host_report = h->host_status_dev + (size_t)slot * TS_SLOT_WORDS;
-  for (int i = 0; i < 65; ++i) rep[i] = 0;
+  if (mc) {
+    TS_CHECK(ts_launch_need_check(W.cand_cnt(), ((TsMaskDev*)W.mask.p)->need, nq, W.status(), p.host_report, sL));
+  } else {
+    for (int i = 0; i < 65; ++i) rep[i] = 0;
+  }
   TS_CHECK(ts_launch_select(p, nq, sL));
   TS_HIP(hipEventRecord(W.ev_sel, sL));
   W.used = true;
@@ -840,6 +921,8 @@ static int search_pass_on(ts_index* h, ts_index::WSet& W, const void* dq, int nq
     pe.ticket = h->next_ticket; pe.slot = slot; pe.nq = nq; pe.S = (uint32_t)S; pe.m = m;
     pe.e0 = pe.e1 = nullptr;
     pe.set = fused ? (int)(&W - h->ws) : -1;
+    pe.fseq = mc ? fseq : -1;
+    if (mc) { h->finfo[1] += (fseq == h->fseq) ? nblk : 0; h->finfo[2] += (fseq == h->fseq) ? 1 : 0; }
     if (pc.now && pc.nev == 2) {  // the scan+filter interval of this pass (prof_mu is held: h->ev is ours)
       pe.e0 = h->ev[0]; pe.e1 = h->ev[1];
       // hand the two events over and give the handle fresh ones
@@ -858,6 +941,7 @@ static int search_pass_on(ts_index* h, ts_index::WSet& W, const void* dq, int nq
   for (int i = 0; i < nq; ++i) maxc = std::max(maxc, rep[i]);
   const bool redo = rep[64] != 0;
   set_info(h, (redo ? 2 : 1) | (fused ? 16 : 0), maxc, S, m);
+  if (mc) add_filter_info(h, fseq, rep[65], nblk, false);
   if (redo) {
     // a threshold was too high (fewer than k survivors) or too low (candidate
     // list overflowed, e.g. massive score ties): redo this pass exactly.
@@ -866,7 +950,7 @@ static int search_pass_on(ts_index* h, ts_index::WSet& W, const void* dq, int nq
       TS_CHECK(ts_launch_qprep(h->L, dq, q_dtype, nq, qh, (uint4*)W.qimg.p, W.cand_cnt(), W.status(), s));
     }
     prof_mark(h, pc, 5, s);
-    TS_CHECK(dense_path(h, W, nq, qh, k, out_s, out_i, s));
+    TS_CHECK(dense_path(h, W, nq, qh, k, out_s, out_i, s, mc));
     prof_mark(h, pc, -1, s);
     TS_HIP(hipStreamSynchronize(s));
     prof_collect(h, pc);
@@ -934,6 +1018,127 @@ extern "C" int ts_index_search(ts_index* h, const void* queries, int32_t nq, int
     TS_HIP(hipMemcpyAsync(out_ids, di, (size_t)nq * k * 8, hipMemcpyDeviceToHost, s));
     TS_HIP(hipStreamSynchronize(s));
   }
+  return TS_OK;
+}
+
+// Filtered search (include/tristage.h): ts_index_search restricted, per query, to the rows of one of
+// n_masks bitmaps.  A pass whose queries have no mask is an ordinary ts_index_search pass.
+extern "C" int ts_index_search_filtered(ts_index* h, const void* queries, int32_t nq, int32_t q_dtype, int32_t k,
+                                        const uint32_t* allow_bits, int64_t allow_words, int32_t n_masks,
+                                        const int32_t* mask_of_query, float* out_scores, int64_t* out_ids,
+                                        uint32_t flags, void* stream) {
+  // the checks that need no handle come first (and none of them touches the GPU)
+  if (nq < 0 || k <= 0 || !dtype_ok(q_dtype) || (nq > 0 && (!queries || !out_scores || !out_ids))) {
+    ts_set_error("bad arguments to search_filtered");
+    return TS_ERR_INVALID;
+  }
+  if (n_masks < 0 || allow_words < 0) { ts_set_error("search_filtered: negative n_masks / allow_words"); return TS_ERR_INVALID; }
+  if (n_masks > 0 && !allow_bits) { ts_set_error("search_filtered: n_masks > 0 but allow_bits is null"); return TS_ERR_INVALID; }
+  if (nq > 0 && !mask_of_query) { ts_set_error("search_filtered: mask_of_query is null"); return TS_ERR_INVALID; }
+  for (int32_t q = 0; q < nq; ++q) {
+    if (mask_of_query[q] < -1 || mask_of_query[q] >= n_masks) {
+      ts_set_error("search_filtered: mask_of_query[%d] = %d is outside [-1, %d)", q, mask_of_query[q], n_masks);
+      return TS_ERR_INVALID;
+    }
+  }
+  if (!h) { ts_set_error("null handle"); return TS_ERR_INVALID; }
+  const int64_t N = h->ntotal;
+  const int64_t need_words = (N + 31) / 32;
+  if (n_masks > 0 && allow_words < need_words) {
+    ts_set_error("search_filtered: allow_words = %lld < ceil(ntotal / 32) = %lld", (long long)allow_words,
+                 (long long)need_words);
+    return TS_ERR_INVALID;
+  }
+  if ((flags & TS_FLAG_PIPELINE) && !(flags & TS_FLAG_ASYNC)) {
+    ts_set_error("TS_FLAG_PIPELINE needs TS_FLAG_ASYNC");
+    return TS_ERR_INVALID;
+  }
+  if ((flags & TS_FLAG_ASYNC) && (flags & TS_FLAG_HOST_PTR)) {
+    ts_set_error("TS_FLAG_ASYNC needs device pointers");
+    return TS_ERR_INVALID;
+  }
+  if (nq == 0) return TS_OK;
+  if (N == 0) {
+    ts_set_error("No documents indexed. Call add_documents() first.");
+    return TS_ERR_EMPTY;
+  }
+  {
+    std::lock_guard<std::mutex> lk(h->mu);
+    ++h->fseq;
+    for (int i = 0; i < 4; ++i) h->finfo[i] = 0;
+  }
+  bool any = false;
+  for (int32_t q = 0; q < nq && !any; ++q) any = mask_of_query[q] >= 0;
+  if (!any) return ts_index_search(h, queries, nq, q_dtype, k, out_scores, out_ids, flags, stream);
+  DeviceGuard g(h->device);
+  hipStream_t s = (hipStream_t)stream;
+  const int qp = (ts_scan_lds_bytes(h->L, 2) <= 160 * 1024) ? 64 : 32;  // queries per pass
+  if (flags & TS_FLAG_ASYNC) {
+    const int passes = (nq + qp - 1) / qp;
+    if (passes > 4) { ts_set_error("TS_FLAG_ASYNC: at most %d queries per call", 4 * qp); return TS_ERR_INVALID; }
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (h->npending + passes > TS_ASYNC_SLOTS / 4) {
+      ts_set_error("too many unfinished asynchronous searches; call ts_index_finish()");
+      return TS_ERR_INVALID;
+    }
+  }
+  const size_t qrow = (size_t)h->L.dim * dtype_size(q_dtype);
+  const void* dq = queries;
+  float* ds = out_scores;
+  int64_t* di = out_ids;
+  const uint32_t* bits = allow_bits;
+  const bool host = (flags & TS_FLAG_HOST_PTR) != 0;
+  std::unique_lock<std::mutex> hlk(h->host_mu, std::defer_lock);
+  if (host) {
+    hlk.lock();   // one staging area per handle
+    const size_t mbytes = (size_t)n_masks * (size_t)allow_words * 4;
+    TS_CHECK(ensure(h->qstage, (size_t)nq * qrow));
+    TS_CHECK(ensure(h->out_s, (size_t)nq * k * 4));
+    TS_CHECK(ensure(h->out_i, (size_t)nq * k * 8));
+    TS_CHECK(ensure(h->mstage, mbytes));
+    TS_HIP(hipMemcpyAsync(h->qstage.p, queries, (size_t)nq * qrow, hipMemcpyHostToDevice, s));
+    TS_HIP(hipMemcpyAsync(h->mstage.p, allow_bits, mbytes, hipMemcpyHostToDevice, s));
+    dq = h->qstage.p;
+    ds = (float*)h->out_s.p;
+    di = (int64_t*)h->out_i.p;
+    bits = (const uint32_t*)h->mstage.p;
+  }
+  for (int q0 = 0; q0 < nq; q0 += qp) {
+    const int c = std::min(qp, nq - q0);
+    MaskCtx mc{};
+    mc.bits = bits;
+    mc.words = allow_words;
+    bool masked = false;
+    for (int j = 0; j < TS_MAX_Q; ++j) { mc.mp.qmask[j] = -1; mc.mp.qd[j] = -1; }
+    for (int j = 0; j < c; ++j) {
+      const int32_t m = mask_of_query[q0 + j];
+      mc.mp.qmask[j] = m;
+      if (m < 0) { mc.mp.all_live = 1; continue; }
+      masked = true;
+      int d = 0;
+      while (d < mc.mp.nd && mc.mp.dist[d] != m) ++d;
+      if (d == mc.mp.nd) mc.mp.dist[mc.mp.nd++] = m;
+      mc.mp.qd[j] = d;
+    }
+    TS_CHECK(search_pass(h, (const char*)dq + (size_t)q0 * qrow, c, q_dtype, k, ds + (size_t)q0 * k,
+                         di + (size_t)q0 * k, flags, s, masked ? &mc : nullptr));
+  }
+  if (flags & TS_FLAG_ASYNC) {
+    std::lock_guard<std::mutex> lk(h->mu);
+    ++h->next_ticket;
+  }
+  if (host) {
+    TS_HIP(hipMemcpyAsync(out_scores, ds, (size_t)nq * k * 4, hipMemcpyDeviceToHost, s));
+    TS_HIP(hipMemcpyAsync(out_ids, di, (size_t)nq * k * 8, hipMemcpyDeviceToHost, s));
+    TS_HIP(hipStreamSynchronize(s));
+  }
+  return TS_OK;
+}
+
+extern "C" int ts_index_last_filter_info(const ts_index* h, int64_t info[4]) {
+  if (!h || !info) { ts_set_error("bad arguments"); return TS_ERR_INVALID; }
+  std::lock_guard<std::mutex> lk(const_cast<ts_index*>(h)->mu);
+  for (int i = 0; i < 4; ++i) info[i] = h->finfo[i];
   return TS_OK;
 }
 
@@ -1033,6 +1238,7 @@ extern "C" int ts_index_finish(ts_index* h, void* stream, int64_t* failed_ticket
       (void)hipEventDestroy(pe.e1);
     }
     h->info[0] = 1 | (pe.set >= 0 ? 16 : 0); h->info[2] = pe.S; h->info[3] = pe.m;
+    if (pe.fseq >= 0 && pe.fseq == h->fseq) h->finfo[0] += rep[65];
     h->slot_busy[pe.slot] = false;
   }
   if (h->npending) h->info[1] = maxc;

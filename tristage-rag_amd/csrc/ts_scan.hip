@@ -147,6 +147,135 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_kernel(ScanParams p) {
   if constexpr (MODE == SCAN_FILTER) flush_stage(p, st, tid);
 }
 
+// Masked filter mode (filtered searches): scan_kernel's SCAN_FILTER loop, walking the live-block list
+// instead of blk0 + w * blk_stride.  Work item w is row block p.live[w], w < *p.nlive.  Both are read
+// with scalar loads (constant address space, wave-uniform index): they count against lgkmcnt, not
+// vmcnt, so fetching the next block's index never waits for the corpus ring.  Each lane's allow word
+// of the NEXT block is requested just before that block's first ring loads, unpredicated (an unmasked
+// query reads word 0 of mask 0 and ORs in all ones), and is complete by the time the block's epilogue
+// reads it: vmcnt retires in order, and the ring loads issued after it have been consumed by then.
+// (A kernel of its own rather than a third MODE of scan_kernel, so that ScanParams and the code of every
+// existing instantiation stay exactly as they were.)
+typedef const uint32_t __attribute__((address_space(4)))* ts_sgpr_u32p;
+typedef const int32_t __attribute__((address_space(4)))* ts_sgpr_i32p;
+
+template <int DT, int QH>
+__global__ __launch_bounds__(SCAN_THREADS) void scan_masked_kernel(MaskedScanParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  u32x4* qlds = reinterpret_cast<u32x4*>(smem);
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int kg = p.kg;
+
+  const int64_t nwaves = (int64_t)gridDim.x * SCAN_WAVES;
+  int64_t w = (int64_t)blockIdx.x * SCAN_WAVES + wave;
+  const int64_t nwork = (int64_t)*(ts_sgpr_u32p)p.nlive;
+  const bool active = w < nwork;  // (waves without work still join the final flush)
+  const u32x4* base = reinterpret_cast<const u32x4*>(p.corpus) + lane;
+  const size_t blk_units = (size_t)kg * 64;
+  int64_t blk = active ? (int64_t)((ts_sgpr_i32p)p.live)[w] : 0;
+  const u32x4* cur = base + (size_t)blk * blk_units;
+  u32x4 ring[TS_RING];
+  if (active) {
+#pragma unroll
+    for (int i = 0; i < TS_RING; ++i) ring[i] = stream_load(cur + (size_t)i * 64);
+  }
+
+  // ---- prologue: Q image global(L2) -> LDS, once per workgroup
+  {
+    const u32x4* src = reinterpret_cast<const u32x4*>(p.qimg);
+    const int units = kg * QH * 64;
+    for (int i0 = tid; i0 < units; i0 += 8 * SCAN_THREADS) {
+      u32x4 t[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int i = i0 + j * SCAN_THREADS;
+        t[j] = (i < units) ? src[i] : u32x4{0, 0, 0, 0};
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int i = i0 + j * SCAN_THREADS;
+        if (i < units) qlds[i] = t[j];
+      }
+    }
+  }
+  StageLds* st = reinterpret_cast<StageLds*>(smem + (size_t)kg * QH * 1024);
+  if (tid == 0) st->cnt = 0;
+  __syncthreads();
+
+  if (active) {
+
+  float tau[QH];
+  const uint32_t* mrow[QH];   // the lane's allow-word row
+  int64_t mstep[QH];          // 0 for an unmasked query: it keeps reading word 0
+  uint32_t mor[QH], mw[QH];   // all ones for an unmasked query; the current block's word
+#pragma unroll
+  for (int hq = 0; hq < QH; ++hq) {
+    tau[hq] = p.tau[hq * 32 + (lane & 31)];
+    const int32_t qm = p.qmask[hq * 32 + (lane & 31)];
+    mrow[hq] = p.allow_bits + (qm < 0 ? 0 : (int64_t)qm * p.allow_words);
+    mstep[hq] = qm < 0 ? 0 : 1;
+    mor[hq] = qm < 0 ? ~0u : 0u;
+    mw[hq] = mrow[hq][blk * mstep[hq]] | mor[hq];
+  }
+
+  const u32x4* ql = qlds + lane;
+
+  while (true) {
+    const int64_t wn = w + nwaves;
+    const bool has_next = wn < nwork;
+    const int64_t blkn = has_next ? (int64_t)((ts_sgpr_i32p)p.live)[wn] : blk;
+    const u32x4* nxt = base + (size_t)blkn * blk_units;
+
+    f32x16 acc[QH];
+#pragma unroll
+    for (int hq = 0; hq < QH; ++hq)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[hq][r] = 0.f;
+
+    // main part: prefetch stays inside the current row block
+    int g0 = 0;
+    for (; g0 < kg - TS_RING; g0 += TS_RING) {
+#pragma unroll
+      for (int i = 0; i < TS_RING; ++i) {
+#pragma unroll
+        for (int hq = 0; hq < QH; ++hq) {
+          const u32x4 b = ql[(size_t)((g0 + i) * QH + hq) * 64];
+          mma_group<DT>(acc[hq], ring[i], b);
+        }
+        ring[i] = stream_load(cur + (size_t)(g0 + i + TS_RING) * 64);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+    // tail: the next block's allow words, then the ring is refilled from the start of that block
+    uint32_t mwn[QH];
+#pragma unroll
+    for (int hq = 0; hq < QH; ++hq) mwn[hq] = mrow[hq][blkn * mstep[hq]];
+#pragma unroll
+    for (int i = 0; i < TS_RING; ++i) {
+#pragma unroll
+      for (int hq = 0; hq < QH; ++hq) {
+        const u32x4 b = ql[(size_t)((g0 + i) * QH + hq) * 64];
+        mma_group<DT>(acc[hq], ring[i], b);
+      }
+      ring[i] = stream_load(nxt + (size_t)i * 64);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+
+    epilogue_filter<QH, StageLds, true>(p, st, acc, tau, blk, lane, mw);
+
+    if (!has_next) break;
+    w = wn;
+    blk = blkn;
+    cur = nxt;
+#pragma unroll
+    for (int hq = 0; hq < QH; ++hq) mw[hq] = mwn[hq] | mor[hq];
+  }
+  }  // active
+  flush_stage(p, st, tid);
+}
+
 bool ts_use_f32_split(const TsLayout& L, int qh) {
   if (L.dtype != TS_F32 || qh != 1) return false;
 #ifdef TS_TUNING   // A/B: TS_NO_F32_SPLIT=1 keeps the exact-f32 MFMA kernel
@@ -185,6 +314,37 @@ static int launch_scan_t(const TsLayout& L, const ScanParams& p, int num_cus,
   return TS_OK;
 }
 
+template <int DT, int QH>
+static int launch_scan_masked_t(const TsLayout& L, const MaskedScanParams& p, int num_cus, hipStream_t stream) {
+  const size_t lds = (size_t)L.kg * QH * 1024 + sizeof(StageLds);
+  auto kern = scan_masked_kernel<DT, QH>;
+  static TsDeviceOnce lds_attr;
+  TS_CHECK(ts_allow_max_lds(lds_attr, reinterpret_cast<const void*>(kern)));
+  // p.nwork: every row block (the live count is only known on the device; waves past it leave at once)
+  int64_t want = (p.nwork + SCAN_WAVES - 1) / SCAN_WAVES;
+  int grid = (int)(want < num_cus ? want : num_cus);
+  if (grid < 1) grid = 1;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(SCAN_THREADS), lds, stream, p);
+  TS_HIP(hipGetLastError());
+  return TS_OK;
+}
+
+int ts_launch_scan_masked(const TsLayout& L, int qh, const MaskedScanParams& p, int num_cus, hipStream_t stream) {
+  if (p.nwork <= 0) return TS_OK;
+  if (ts_scan_lds_bytes(L, qh) > 160 * 1024) {
+    ts_set_error("dimension %d too large for the LDS-resident query image", L.dim);
+    return TS_ERR_UNSUPPORTED;
+  }
+  switch (L.dtype) {   // (fp32 storage: filtered searches take the dense path)
+    case TS_F16: return qh == 1 ? launch_scan_masked_t<TS_F16, 1>(L, p, num_cus, stream)
+                                : launch_scan_masked_t<TS_F16, 2>(L, p, num_cus, stream);
+    case TS_BF16: return qh == 1 ? launch_scan_masked_t<TS_BF16, 1>(L, p, num_cus, stream)
+                                 : launch_scan_masked_t<TS_BF16, 2>(L, p, num_cus, stream);
+  }
+  ts_set_error("the masked scan takes f16 / bf16 storage only");
+  return TS_ERR_UNSUPPORTED;
+}
+
 template <int DT>
 static int launch_scan_dt(const TsLayout& L, int mode, int qh,
                           const ScanParams& p, int num_cus, hipStream_t s) {
@@ -211,6 +371,55 @@ int ts_launch_scan(const TsLayout& L, int mode, int qh, const ScanParams& p,
   }
   ts_set_error("bad dtype %d", L.dtype);
   return TS_ERR_INVALID;
+}
+
+// ------------------------------------------------------------------ live-block list (filtered searches)
+// Thread per row block b: OR of the pass's distinct masks at word b (bits at or beyond ntotal cleared),
+// compacted into live[] with one atomic per wave (block order is kept inside a wave); per distinct mask
+// the allowed rows are summed with one atomic per wave.  Thread t < 64 of workgroup 0 also publishes
+// the pass's query -> mask tables for the scan and the threshold kernel.
+__global__ __launch_bounds__(256) void live_blocks_kernel(const uint32_t* bits, int64_t words, TsMaskPass mp,
+                                                          int64_t nblk, int64_t ntotal, TsMaskDev* md) {
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  if (blockIdx.x == 0 && tid < TS_MAX_Q) {
+    md->qmask[tid] = mp.qmask[tid];
+    md->qd[tid] = mp.qd[tid];
+  }
+  const int64_t b = (int64_t)blockIdx.x * blockDim.x + tid;
+  const bool in = b < nblk;
+  // rows of block b below ntotal (only the last block is partial)
+  const int64_t rows = in ? ntotal - b * TS_ROWS_PER_BLOCK : 0;
+  const uint32_t valid = rows >= 32 ? ~0u : (rows > 0 ? ((1u << rows) - 1u) : 0u);
+  uint32_t any = 0;
+  for (int d = 0; d < mp.nd; ++d) {
+    const uint32_t wd = in ? (bits[(int64_t)mp.dist[d] * words + b] & valid) : 0u;
+    any |= wd;
+    uint32_t c = (uint32_t)__builtin_popcount(wd);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) c += (uint32_t)__shfl_xor((int)c, off, 64);
+    if (lane == 0 && c) atomicAdd(&md->popc[d], c);
+  }
+  if (mp.all_live) any = valid;
+  const bool live = any != 0u;
+  const unsigned long long bal = __builtin_amdgcn_ballot_w64(live);
+  if (bal == 0ull) return;
+  uint32_t base = 0;
+  if (lane == 0) base = atomicAdd(&md->nlive, (uint32_t)__builtin_popcountll(bal));
+  base = (uint32_t)__shfl((int)base, 0, 64);
+  if (live) {
+    const uint32_t below = (uint32_t)__builtin_popcountll(bal & ((1ull << lane) - 1ull));
+    reinterpret_cast<int32_t*>(md + 1)[base + below] = (int32_t)b;
+  }
+}
+
+int ts_launch_live_blocks(const uint32_t* bits, int64_t words, const TsMaskPass& mp, int64_t nblk,
+                          int64_t ntotal, TsMaskDev* md, hipStream_t stream) {
+  const int64_t blocks = (nblk + 255) / 256;
+  if (blocks < 1 || blocks > 0x7fffffffLL) { ts_set_error("live blocks: bad row block count"); return TS_ERR_INVALID; }
+  hipLaunchKernelGGL(live_blocks_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, bits, words, mp, nblk, ntotal, md);
+  TS_HIP(hipGetLastError());
+  return TS_OK;
 }
 
 // ------------------------------------------------------------------ layout

@@ -111,11 +111,14 @@ struct StageLdsT {
 };
 typedef StageLdsT<STAGE_CAP> StageLds;
 
-template <int QH, class SL>
+// MASKED (scan_masked_kernel, filtered searches): on the rare path a survivor of query hq*32 + (lane & 31)
+// also needs its bit in mw[hq], that query's allow word of this row block (bit i = row 32*blk + i).  The
+// common path is the same ballot: the mask costs nothing there.
+template <int QH, class SL, bool MASKED = false>
 __device__ __forceinline__ void epilogue_filter(const ScanParams& p, SL* st,
                                                 const f32x16 (&acc)[QH],
                                                 const float (&tau)[QH],
-                                                int64_t blk, int lane) {
+                                                int64_t blk, int lane, const uint32_t* mw = nullptr) {
   bool hit = false;
 #pragma unroll
   for (int hq = 0; hq < QH; ++hq) hit |= (acc_max(acc[hq]) >= tau[hq]);
@@ -128,8 +131,9 @@ __device__ __forceinline__ void epilogue_filter(const ScanParams& p, SL* st,
     uint32_t mask = 0;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      const bool ok = (acc[hq][r] >= tau[hq]) &&
-                      (row_base + acc_row(r, lane) < p.ntotal);
+      bool ok = (acc[hq][r] >= tau[hq]) &&
+                (row_base + acc_row(r, lane) < p.ntotal);
+      if constexpr (MASKED) ok = ok && ((mw[hq] >> acc_row(r, lane)) & 1u);
       mask |= ok ? (1u << r) : 0u;
     }
     if (mask) {

@@ -560,3 +560,130 @@ int ts_launch_tau(const float* sample, int64_t ld, uint32_t n, uint32_t m, int n
   TS_HIP(hipGetLastError());
   return TS_OK;
 }
+
+// ------------------------------------------------------------------ filtered searches
+// The dense path of a filtered search: ids[q][i] = row0 + i where row0 + i is allowed for query q, else -1.
+// SEL_PAIRS32 over (dense scores, these ids) then ranks exactly the allowed rows (an entry with id < 0 is
+// the padding of a short list: no key), and pads the tail with -1 / -FLT_MAX.
+__global__ void mask_ids_kernel(const uint32_t* bits, int64_t words, TsMaskPass mp, int64_t row0,
+                                uint32_t rows, int64_t ld, int32_t* ids) {
+  const int q = blockIdx.y;
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= rows) return;
+  const int32_t qm = mp.qmask[q];
+  const int64_t row = row0 + i;
+  const bool ok = qm < 0 || ((bits[(int64_t)qm * words + (row >> 5)] >> (row & 31)) & 1u);
+  ids[(int64_t)q * ld + i] = ok ? (int32_t)row : -1;
+}
+
+int ts_launch_mask_ids(const uint32_t* bits, int64_t words, const TsMaskPass& mp, int nq, int64_t row0,
+                       uint32_t rows, int64_t ld, int32_t* ids, hipStream_t stream) {
+  if (nq <= 0 || rows == 0) return TS_OK;
+  hipLaunchKernelGGL(mask_ids_kernel, dim3((rows + 255) / 256, nq), dim3(256), 0, stream, bits, words, mp, row0,
+                     rows, ld, ids);
+  TS_HIP(hipGetLastError());
+  return TS_OK;
+}
+
+// The exactness check of a filtered pass, between its scan and its select: a query with fewer candidates
+// than need[q] = min(k, allowed rows) sets TS_STATUS_SHORT (the select itself is run with need = 0).
+__global__ void need_check_kernel(const uint32_t* cand_cnt, const uint32_t* need, int nq, uint32_t* status,
+                                  uint32_t* host_report) {
+  const int q = threadIdx.x;
+  if (q >= nq) return;
+  if (cand_cnt[q] < need[q]) {
+    if (status) atomicOr(status, TS_STATUS_SHORT);
+    if (host_report) atomicOr(&host_report[64], TS_STATUS_SHORT);
+  }
+}
+
+int ts_launch_need_check(const uint32_t* cand_cnt, const uint32_t* need, int nq, uint32_t* status,
+                         uint32_t* host_report, hipStream_t stream) {
+  hipLaunchKernelGGL(need_check_kernel, dim3(1), dim3(TS_MAX_Q), 0, stream, cand_cnt, need, nq, status, host_report);
+  TS_HIP(hipGetLastError());
+  return TS_OK;
+}
+
+// Thresholds of a filtered pass.  Per query: the allowed rows of the strided sample (S_q of them;
+// sample entry i is row 32 * (i / 32) * sstride + i % 32) and its allowed rows overall (N_q, from the
+// live-block kernel) give the rank m_q = max(min_rank, ceil(over * k * S_q / N_q)); tau = the m_q-th best
+// allowed sample score (a lower bound of it, as in tau_kernel), or -FLT_MAX when S_q < m_q: every allowed
+// row is then a candidate, which for small allowed sets is both exact and cheap.  Unmasked queries:
+// N_q = ntotal.  need[q] = min(k, N_q) feeds need_check_kernel.
+__global__ __launch_bounds__(SEL_THREADS) void tau_masked_kernel(const float* sample, int64_t S, int64_t sstride,
+                                                                 int64_t ntotal, const uint32_t* bits, int64_t words,
+                                                                 TsMaskDev* md, int nq, int k, uint32_t over,
+                                                                 uint32_t min_rank, float* tau, uint32_t* report) {
+  constexpr int KEEP = 4;
+  __shared__ __attribute__((aligned(16))) uint32_t keys[KEEP * SEL_THREADS];
+  __shared__ uint32_t cnt;
+  const int q = blockIdx.x;
+  const int tid = threadIdx.x;
+  if (q == 0 && tid == 0 && report) report[0] = md->nlive;
+  if (q >= nq) {
+    if (tid == 0) { tau[q] = 3.402823466e38f; md->need[q] = 0u; }
+    return;
+  }
+  const int32_t qm = md->qmask[q];
+  const uint32_t* mrow = qm >= 0 ? bits + (int64_t)qm * words : nullptr;
+  const float* s = sample + (int64_t)q * S;
+  if (tid == 0) cnt = 0;
+  __syncthreads();
+  uint32_t a0 = 0, a1 = 0, a2 = 0, a3 = 0, mine = 0;
+  for (int64_t i = tid; i < S; i += SEL_THREADS) {
+    const int64_t row = (i >> 5) * sstride * TS_ROWS_PER_BLOCK + (i & 31);
+    if (row >= ntotal) continue;
+    if (mrow && !((mrow[row >> 5] >> (row & 31)) & 1u)) continue;
+    ++mine;
+    const uint32_t kk = f2key(s[i]);
+    if (kk > a3) {
+      if (kk > a0) { a3 = a2; a2 = a1; a1 = a0; a0 = kk; }
+      else if (kk > a1) { a3 = a2; a2 = a1; a1 = kk; }
+      else if (kk > a2) { a3 = a2; a2 = kk; }
+      else a3 = kk;
+    }
+  }
+  if (mine) atomicAdd(&cnt, mine);
+  keys[tid] = a0;
+  keys[SEL_THREADS + tid] = a1;
+  keys[2 * SEL_THREADS + tid] = a2;
+  keys[3 * SEL_THREADS + tid] = a3;
+  __syncthreads();
+  constexpr uint32_t P = KEEP * SEL_THREADS;
+  for (uint32_t size = 2; size <= P; size <<= 1) {
+    for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
+      for (uint32_t t = tid; t < (P >> 1); t += SEL_THREADS) {
+        const uint32_t i = 2 * t - (t & (stride - 1));
+        const uint32_t j = i + stride;
+        const bool desc = (i & size) == 0;
+        const uint32_t a = keys[i], b = keys[j];
+        if (desc ? (b > a) : (a > b)) { keys[i] = b; keys[j] = a; }
+      }
+      __syncthreads();
+    }
+  }
+  if (tid == 0) {
+    const uint64_t Nq = qm >= 0 ? (uint64_t)md->popc[md->qd[q]] : (uint64_t)ntotal;
+    const uint64_t Sq = cnt;
+    uint64_t m = Nq ? ((uint64_t)over * (uint64_t)k * Sq + Nq - 1) / Nq : 0;
+    if (m < min_rank) m = min_rank;
+    float t = NEG_MAX;
+    if (Sq >= m) {
+      uint32_t idx = (uint32_t)(m - 1);
+      if (idx >= P) idx = P - 1;
+      const uint32_t kx = keys[idx];
+      t = (kx == 0u) ? NEG_MAX : key2f(kx);
+    }
+    tau[q] = t;
+    md->need[q] = (uint32_t)((uint64_t)k < Nq ? (uint64_t)k : Nq);
+  }
+}
+
+int ts_launch_tau_masked(const float* sample, int64_t S, int64_t sstride, int64_t ntotal, const uint32_t* bits,
+                         int64_t words, TsMaskDev* md, int nq, int k, uint32_t over, uint32_t min_rank,
+                         float* tau, uint32_t* report, hipStream_t stream) {
+  hipLaunchKernelGGL(tau_masked_kernel, dim3(TS_MAX_Q), dim3(SEL_THREADS), 0, stream, sample, S, sstride, ntotal, bits,
+                     words, md, nq, k, over, min_rank, tau, report);
+  TS_HIP(hipGetLastError());
+  return TS_OK;
+}

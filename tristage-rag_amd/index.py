@@ -48,6 +48,31 @@ def _tensor_dtype(t) -> int:
     raise TypeError(f"unsupported tensor dtype {t.dtype}")
 
 
+def pack_allowed(mask, n: int) -> np.ndarray:
+    """An allow mask over ``n`` rows -> packed uint32 words (host): bit ``r % 32`` of word ``r // 32`` set
+    means row ``r`` is allowed (the layout of ``ts_index_search_filtered``).  ``mask`` is a bool array /
+    tensor of length ``n``, or an already packed uint32 array of at least ``ceil(n / 32)`` words."""
+    if _is_tensor(mask):
+        mask = mask.detach().cpu().numpy()
+    m = np.asarray(mask)
+    words = (int(n) + 31) // 32
+    if m.dtype == np.bool_:
+        if m.ndim != 1 or m.shape[0] != n:
+            raise ValueError(f"a bool allow mask must have one entry per row ({n}), got shape {m.shape}")
+        b = np.packbits(m, bitorder="little")
+        out = np.zeros(words * 4, dtype=np.uint8)
+        out[: b.shape[0]] = b
+        return out.view("<u4").astype(np.uint32)
+    if m.dtype in (np.uint32, np.int32):
+        if m.ndim != 1 or m.shape[0] < words:
+            raise ValueError(f"a packed allow mask needs >= {words} uint32 words, got shape {m.shape}")
+        w = np.ascontiguousarray(m[:words]).view(np.uint32).copy()
+        if n % 32:   # bits at or beyond n are ignored by the library; cleared here too for a canonical form
+            w[-1] &= np.uint32((1 << (n % 32)) - 1)
+        return w
+    raise TypeError(f"allow mask: expected a bool array or packed uint32 words, got dtype {m.dtype}")
+
+
 def _stream_ptr(device_index: int) -> int:
     torch = _torch()
     return int(torch.cuda.current_stream(device_index).cuda_stream)
@@ -79,6 +104,7 @@ class FlatIPIndex:
         self.auto_finish = True  # False: the owner (ShardedFlatIPIndex) calls finish() itself, collectively
         self.classic_filter = False  # True: every search takes the five-launch filter path (A/B measurements)
         self.one_launch_filter = False  # True: the one-launch scan wherever it is valid (also pipelined / large corpora)
+        self._filter_info = None  # set by finish() when it redid a filtered search: the counters of what was submitted
 
     # -- lifetime ---------------------------------------------------------
     def close(self) -> None:
@@ -136,7 +162,7 @@ class FlatIPIndex:
         return None
 
     def search(self, q, k: int, exact_dense: bool = False, async_: bool = False, out=None,
-               inputs_ready: bool = False, classic: bool = False, one_launch: bool = False):
+               inputs_ready: bool = False, classic: bool = False, one_launch: bool = False, allowed=None):
         """Top-``k`` inner products.  numpy in -> ``(D float32[B,k], I int64[B,k])``
         numpy out (FAISS convention, -1 padded); CUDA tensor in -> tensors out.
 
@@ -148,10 +174,17 @@ class FlatIPIndex:
         ``inputs_ready=True`` (with ``async_``): the caller guarantees ``q`` is already
         complete in memory (not the result of work still pending on the stream); the
         library then pipelines this search's small kernels beside its neighbours' scans
-        (TS_FLAG_PIPELINE)."""
+        (TS_FLAG_PIPELINE).
+        ``allowed``: restrict the search to a subset of the rows (FAISS ``IDSelector``): a bool array /
+        tensor over the rows, packed uint32 words (:func:`pack_allowed`), a list with one of these (or
+        ``None``: unfiltered) per query, or ``None``.  The result is what an index holding only the
+        allowed rows would return, with the original ids; fewer than ``k`` allowed rows pad with
+        -1 / -FLT_MAX.  The scan reads only the 32-row blocks some query of a pass may see."""
         k = int(k)
         if k <= 0:
             raise ValueError("k must be positive")
+        if allowed is not None:
+            return self._search_filtered(q, k, allowed, exact_dense=exact_dense, async_=async_, out=out)
         if k > self.MAX_KERNEL_K and self.ntotal > self.MAX_KERNEL_K:
             return self._search_large_k(q, k, out)
         if async_ and _is_tensor(q) and q.is_cuda and q.shape[0] > self.MAX_ASYNC_QUERIES:
@@ -199,7 +232,7 @@ class FlatIPIndex:
             self._search_raw(q.data_ptr(), B, _tensor_dtype(q), k, D.data_ptr(), I.data_ptr(),
                              flags, _stream_ptr(self.device))
             if async_:
-                self._pending[int(self._lib.ts_index_last_ticket(self._h))] = (q, k, D, I)
+                self._pending[int(self._lib.ts_index_last_ticket(self._h))] = (q, k, D, I, None)
                 self._pending_passes += (B + 31) // 32
             return D, I
         if _is_tensor(q):
@@ -216,7 +249,7 @@ class FlatIPIndex:
                          flags | _lib.TS_FLAG_HOST_PTR, 0)
         return D, I
 
-    def _search_large_k(self, q, k: int, out=None):
+    def _search_large_k(self, q, k: int, out=None, masks=None):
         """k > 16384 on a corpus of more than 16384 rows (the select kernels keep 16384 keys in LDS; FAISS itself takes
         any k on the CPU, reference src/stage1_retriever.py:380): every inner product from the HIP dense scan
         (ts_index_scores), then ONE stable descending device sort per slice of queries — equal scores keep ascending
@@ -241,14 +274,172 @@ class FlatIPIndex:
         I[:, kk:] = -1
         step = max(1, int(2e9 // (4 * max(n, 1))))          # <= 2 GB of scores per slice
         off = int(self._id_offset_value())
+        if masks is not None:   # filtered: rows outside a query's mask sort behind every allowed row (-inf) and are cut
+            bits, moq = masks
+            allow = np.unpackbits(bits.view(np.uint8), bitorder="little").reshape(bits.shape[0], -1)[:, :n].astype(bool)
+            allow_t = torch.from_numpy(allow).to(dev)
         for s in range(0, B, step):
             sc = self.scores(qt[s: s + step])
+            if masks is not None:
+                m = torch.from_numpy(moq[s: s + step].astype(np.int64)).to(dev)
+                rows_ok = torch.where((m >= 0)[:, None], allow_t[m.clamp(min=0)], torch.ones_like(allow_t[:1]))
+                sc = sc.masked_fill(~rows_ok, float("-inf"))
             srt, idx = torch.sort(sc, dim=1, descending=True, stable=True)
             D[s: s + step, :kk] = srt[:, :kk]
             I[s: s + step, :kk] = idx[:, :kk] + off
+            if masks is not None:
+                cut = torch.isneginf(D[s: s + step])
+                D[s: s + step][cut] = -3.4028234663852886e38
+                I[s: s + step][cut] = -1
         if was_np:
             return D.cpu().numpy(), I.cpu().numpy()
         return D, I
+
+    # -- filtered search ----------------------------------------------------
+    def _masks(self, allowed, B: int):
+        """``allowed`` -> (packed masks uint32 [n_masks, words] on the host, mask_of_query int32 [B]).
+        Identical mask objects of a list share one packed mask."""
+        n = self.ntotal
+        per_query = isinstance(allowed, (list, tuple))
+        if not per_query and _is_tensor(allowed) and allowed.dim() == 2:
+            allowed = list(allowed)
+            per_query = True
+        elif not per_query and isinstance(allowed, np.ndarray) and allowed.ndim == 2:
+            allowed = list(allowed)
+            per_query = True
+        if per_query and len(allowed) != B:
+            raise ValueError(f"allowed: {len(allowed)} masks for {B} queries")
+        items = allowed if per_query else [allowed] * B
+        packed, seen = [], {}
+        moq = np.full(B, -1, dtype=np.int32)
+        for qi, a in enumerate(items):
+            if a is None:
+                continue
+            key = id(a)
+            if key not in seen:
+                seen[key] = len(packed)
+                packed.append(pack_allowed(a, n))
+            moq[qi] = seen[key]
+        words = (n + 31) // 32
+        bits = np.stack(packed) if packed else np.zeros((1, max(words, 1)), dtype=np.uint32)
+        return np.ascontiguousarray(bits), words, moq
+
+    def _filtered_raw(self, q_ptr: int, B: int, q_dtype: int, k: int, bits_ptr: int, words: int, moq: np.ndarray,
+                      d_ptr: int, i_ptr: int, flags: int, stream: int) -> None:
+        n_masks = int(moq.max()) + 1 if moq.size else 0
+        code = self._lib.ts_index_search_filtered(
+            self._h, ctypes.c_void_p(q_ptr), B, q_dtype, k, ctypes.c_void_p(bits_ptr), int(words), n_masks,
+            moq.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(d_ptr), ctypes.c_void_p(i_ptr), flags,
+            ctypes.c_void_p(stream) if stream else None)
+        if code == _lib.TS_ERR_EMPTY:
+            raise ValueError("No documents indexed. Call add_documents() first.")
+        _lib.check(code)
+
+    @staticmethod
+    def _device_masks(allowed, B: int, words: int, device):
+        """``allowed`` made only of packed int32 CUDA tensors (>= words each) or None -> (bits [n, words] on the
+        device, mask_of_query), else None."""
+        items = list(allowed) if isinstance(allowed, (list, tuple)) else [allowed] * B
+        if len(items) != B or not any(a is not None for a in items):
+            return None
+        for a in items:
+            if a is not None and not (_is_tensor(a) and a.is_cuda and a.dtype == _torch().int32 and a.dim() == 1
+                                      and a.shape[0] >= words and a.device == device):
+                return None
+        uniq, seen = [], {}
+        moq = np.full(B, -1, dtype=np.int32)
+        for qi, a in enumerate(items):
+            if a is not None:
+                if id(a) not in seen:
+                    seen[id(a)] = len(uniq)
+                    uniq.append(a[:words])
+                moq[qi] = seen[id(a)]
+        if len(uniq) == 1 and uniq[0].is_contiguous():   # one mask for the call: used in place, no copy
+            return uniq[0].view(1, -1), moq
+        return _torch().stack(uniq).contiguous(), moq
+
+    def _search_filtered(self, q, k: int, allowed, exact_dense: bool = False, async_: bool = False, out=None):
+        if self.ntotal == 0:
+            raise ValueError("No documents indexed. Call add_documents() first.")
+        B = int(q.shape[0])
+        self._filter_info = None   # last_filter_info() reads the library's counters of this call again
+        if getattr(allowed, "ndim", 1) == 2:   # one row per query: the list form (sliced with the queries below)
+            allowed = list(allowed)
+        words = (self.ntotal + 31) // 32
+        dev_bits = None
+        if (_is_tensor(q) and q.is_cuda and not (k > self.MAX_KERNEL_K and self.ntotal > self.MAX_KERNEL_K)
+                and not (async_ and B > self.MAX_ASYNC_QUERIES)):
+            dev_bits = self._device_masks(allowed, B, words, q.device)   # packed on the device already: no host copy
+        if dev_bits is None:
+            bits, words, moq = self._masks(allowed, B)
+        if k > self.MAX_KERNEL_K and self.ntotal > self.MAX_KERNEL_K:
+            return self._search_large_k(q, k, out, masks=(bits, moq))
+        flags = _lib.TS_FLAG_NO_FILTER if exact_dense else 0
+        if _is_tensor(q) and q.is_cuda:
+            torch = _torch()
+            if q.dim() != 2 or q.shape[1] != self.d:
+                raise ValueError(f"expected [B, {self.d}] queries, got {tuple(q.shape)}")
+            if async_ and B > self.MAX_ASYNC_QUERIES:
+                D, I = out if out is not None else (torch.empty((B, k), dtype=torch.float32, device=q.device),
+                                                    torch.empty((B, k), dtype=torch.int64, device=q.device))
+                for s in range(0, B, self.MAX_ASYNC_QUERIES):
+                    e = min(B, s + self.MAX_ASYNC_QUERIES)
+                    sub = [allowed[i] for i in range(s, e)] if isinstance(allowed, (list, tuple)) else allowed
+                    self._search_filtered(q[s:e], k, sub, exact_dense=exact_dense, async_=True, out=(D[s:e], I[s:e]))
+                return D, I
+            q = q.contiguous()
+            if out is not None:
+                D, I = out
+                if (D.shape != (B, k) or I.shape != (B, k) or D.dtype != torch.float32 or
+                        I.dtype != torch.int64 or not D.is_contiguous() or not I.is_contiguous()):
+                    raise ValueError("out must be contiguous (float32[B,k], int64[B,k]) CUDA tensors")
+            else:
+                D = torch.empty((B, k), dtype=torch.float32, device=q.device)
+                I = torch.empty((B, k), dtype=torch.int64, device=q.device)
+            if dev_bits is not None:   # (Stage1Retriever's filter cache, tools/filter_probe.py)
+                dbits, moq = dev_bits
+            else:
+                dbits = torch.from_numpy(bits.view(np.int32)).to(q.device)   # device copy, kept alive with the search
+            if async_:
+                if self.pending_room(B) < 0:
+                    if not self.auto_finish:
+                        raise RuntimeError("too many unfinished asynchronous searches: the owner of this index "
+                                           "must call finish() (see pending_room())")
+                    self._auto_redone = self.finish()
+                flags |= _lib.TS_FLAG_ASYNC
+            self._filtered_raw(q.data_ptr(), B, _tensor_dtype(q), k, dbits.data_ptr(), words, moq,
+                               D.data_ptr(), I.data_ptr(), flags, _stream_ptr(self.device))
+            if async_:
+                self._pending[int(self._lib.ts_index_last_ticket(self._h))] = (q, k, D, I, (dbits, words, moq))
+                self._pending_passes += (B + 31) // 32
+            return D, I
+        if async_:
+            raise ValueError("async_ search needs a CUDA tensor")
+        if _is_tensor(q):
+            q = q.detach().float().numpy()
+        q = np.ascontiguousarray(q)
+        if q.dtype not in _NP_DTYPES:
+            q = q.astype(np.float32)
+        if q.ndim != 2 or q.shape[1] != self.d:
+            raise ValueError(f"expected [B, {self.d}] queries, got {q.shape}")
+        D = np.empty((B, k), dtype=np.float32)
+        I = np.empty((B, k), dtype=np.int64)
+        self._filtered_raw(q.ctypes.data, B, _NP_DTYPES[q.dtype], k, bits.ctypes.data, words, moq,
+                           D.ctypes.data, I.ctypes.data, flags | _lib.TS_FLAG_HOST_PTR, 0)
+        return D, I
+
+    def last_filter_info(self) -> dict:
+        """The last filtered search: row blocks (32 rows) its scans read, row blocks of the index, passes on the
+        masked filter path and on the dense path (asynchronous searches: complete after :meth:`finish`)."""
+        if getattr(self, "_filter_info", None) is not None:
+            return dict(self._filter_info)
+        return self._read_filter_info()
+
+    def _read_filter_info(self) -> dict:
+        arr = (ctypes.c_int64 * 4)()
+        _lib.check(self._lib.ts_index_last_filter_info(self._h, arr))
+        return {"live_blocks": int(arr[0]), "total_blocks": int(arr[1]), "filter_passes": int(arr[2]),
+                "dense_passes": int(arr[3])}
 
     def _id_offset_value(self) -> int:
         return getattr(self, "_id_offset", 0)
@@ -310,10 +501,19 @@ class FlatIPIndex:
         _lib.check(self._lib.ts_index_finish(self._h, ctypes.c_void_p(_stream_ptr(self.device)) if
                                              _stream_ptr(self.device) else None, failed, 256, ctypes.byref(nf)))
         redone = []
+        if any(self._pending[int(failed[i])][4] is not None for i in range(nf.value)):
+            # a redo is a new library call that resets the filter counters: last_filter_info() keeps describing the
+            # searches that were submitted (complete now that ts_index_finish has run)
+            self._filter_info = self._read_filter_info()
         for i in range(nf.value):
-            q, k, D, I = self._pending[int(failed[i])]
-            self._search_raw(q.data_ptr(), q.shape[0], _tensor_dtype(q), k, D.data_ptr(), I.data_ptr(),
-                             _lib.TS_FLAG_NO_FILTER, _stream_ptr(self.device))
+            q, k, D, I, masks = self._pending[int(failed[i])]
+            if masks is None:
+                self._search_raw(q.data_ptr(), q.shape[0], _tensor_dtype(q), k, D.data_ptr(), I.data_ptr(),
+                                 _lib.TS_FLAG_NO_FILTER, _stream_ptr(self.device))
+            else:   # a filtered search: redone on the exact dense path with the masks it kept alive
+                bits, words, moq = masks
+                self._filtered_raw(q.data_ptr(), q.shape[0], _tensor_dtype(q), k, bits.data_ptr(), words,
+                                   moq, D.data_ptr(), I.data_ptr(), _lib.TS_FLAG_NO_FILTER, _stream_ptr(self.device))
             redone.append(int(failed[i]))
         self._pending.clear()
         self._pending_passes = 0

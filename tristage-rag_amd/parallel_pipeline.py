@@ -61,6 +61,9 @@ def _world(group):
     return dist, dist.get_world_size(group), dist.get_rank(group)
 
 
+FILTER_UNSUPPORTED = ("filtered search is not supported on the sharded path (ShardedFlatIPIndex / ShardedBM25 / ShardedRetrievalPipeline); use a single-rank RetrievalPipeline")
+
+
 class ShardedList:
     """List-shaped view of a row-sharded sequence: ``len()`` is the GLOBAL length, item i is the real item on the
     rank that owns row i and ``missing`` elsewhere.  Stands where the reference keeps ``Stage1Retriever.documents``
@@ -153,7 +156,9 @@ class ShardedBM25:
             out.append((i[order], s_[order]))
         return out
 
-    def search_many_arrays(self, queries: Sequence[str], top_k: int = 10):
+    def search_many_arrays(self, queries: Sequence[str], top_k: int = 10, allowed=None):
+        if allowed is not None:
+            raise NotImplementedError(FILTER_UNSUPPORTED)
         k = int(top_k)
         kl = min(k, max(self.local.corpus_size, 0))
         got = self.local.search_many_arrays(list(queries), kl) if kl > 0 else [(np.zeros(0, np.int64), np.zeros(0))] * len(queries)
@@ -164,10 +169,14 @@ class ShardedBM25:
             sc[q, : len(i)] = s_
         return self._merge(ids, sc, k)
 
-    def search_many(self, queries: Sequence[str], top_k: int = 10):
+    def search_many(self, queries: Sequence[str], top_k: int = 10, allowed=None):
+        if allowed is not None:
+            raise NotImplementedError(FILTER_UNSUPPORTED)
         return [list(zip(i.tolist(), s_.tolist())) for i, s_ in self.search_many_arrays(queries, top_k)]
 
-    def search(self, query: str, top_k: int = 10):
+    def search(self, query: str, top_k: int = 10, allowed=None):
+        if allowed is not None:
+            raise NotImplementedError(FILTER_UNSUPPORTED)
         return self.search_many([query], top_k)[0]
 
 
@@ -324,7 +333,9 @@ class ShardedRetrievalPipeline(RetrievalPipeline):
                     if isinstance(r, dict) and r.get("document") is None and int(r["doc_id"]) in have:
                         r["document"], r["metadata"] = have[int(r["doc_id"])]
 
-    def search(self, query: str, top_k: Optional[int] = None) -> Dict[str, Any]:
+    def search(self, query: str, top_k: Optional[int] = None, filter=None) -> Dict[str, Any]:
+        if filter is not None:
+            raise NotImplementedError(FILTER_UNSUPPORTED)
         if self.world_size == 1:
             return super().search(query, top_k)
         if self.config.search_on_arrays and self._arrays_agreed():
@@ -396,10 +407,12 @@ class ShardedRetrievalPipeline(RetrievalPipeline):
         out = (pos2.cpu().numpy(), sc2.cpu().numpy(), pos3.cpu().numpy(), sc3.cpu().numpy())
         return out + (self._span(ma, mb), self._span(mb, mc))
 
-    def search_many(self, queries: List[str], top_k: Optional[int] = None) -> List[Dict[str, Any]]:
+    def search_many(self, queries: List[str], top_k: Optional[int] = None, filter=None) -> List[Dict[str, Any]]:
         """Batched search over R ranks; every rank returns every query's records.  Array path (token store + id
         cache on the shards): three collectives per call besides stage 1's — two all-reduces of small score matrices
         and one gather of the returned texts.  Otherwise the per-record path, query by query."""
+        if filter is not None:
+            raise NotImplementedError(FILTER_UNSUPPORTED)
         if self.world_size == 1:
             return super().search_many(queries, top_k)
         if not self.stage1 or not self.stage2 or not self.stage3:

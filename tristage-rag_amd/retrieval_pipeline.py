@@ -261,11 +261,14 @@ class RetrievalPipeline:
             self._cleanup_memory()
         return result
 
-    def search(self, query: str, top_k: Optional[int] = None) -> Dict[str, Any]:
+    def search(self, query: str, top_k: Optional[int] = None, filter=None) -> Dict[str, Any]:
+        """``filter``: search only the documents it allows (Stage1Retriever.filter_mask: a metadata dict, a
+        callable, document indices or a bool array).  Stages 2 and 3 rescore stage 1's candidates, so fewer
+        than ``top_k`` results come back when fewer documents are allowed, and none when none are."""
         if not self.stage1 or not self.stage2 or not self.stage3:
             self.initialize_stages()
         top_k = top_k or self.config.stage3_top_k
-        if self.config.search_on_arrays:
+        if self.config.search_on_arrays and filter is None:
             # one query through the array path of search_many (resident token store + stage-3 id cache): no candidate
             # text is tokenised or re-encoded, one cross-encoder forward for the query's pairs; same records (tests)
             fast = self._search_many_arrays([query], top_k)
@@ -274,23 +277,33 @@ class RetrievalPipeline:
         total_start = self._now()
         try:
             t = self._now()
-            stage1_results = self.stage1.search(query, self.config.stage1_top_k)
+            if filter is None:
+                stage1_results = self.stage1.search(query, self.config.stage1_top_k)
+            else:
+                stage1_results = self.stage1.search(query, self.config.stage1_top_k, filter=filter)
             stage1_time = time.time() - t if t else None
             return self._run_later_stages(query, top_k, stage1_results, total_start, stage1_time)
         except Exception as e:
             self.logger.error(f"Error during search: {e}")
             raise
 
-    def batch_search(self, queries: List[str], top_k: Optional[int] = None) -> List[Dict[str, Any]]:
-        """Sequential, like the reference (:444-448); see search_many for the batched form."""
-        return [self.search(q, top_k) for q in queries]
+    def batch_search(self, queries: List[str], top_k: Optional[int] = None, filter=None) -> List[Dict[str, Any]]:
+        """Sequential, like the reference (:444-448); see search_many for the batched form.  ``filter``: one
+        filter for every query or a list with one per query."""
+        if filter is None:
+            return [self.search(q, top_k) for q in queries]
+        if not self.stage1:
+            self.initialize_stages()
+        specs = self.stage1._per_query_filters(filter, len(queries))
+        return [self.search(q, top_k, filter=f) for q, f in zip(queries, specs)]
 
-    def search_many(self, queries: List[str], top_k: Optional[int] = None) -> List[Dict[str, Any]]:
+    def search_many(self, queries: List[str], top_k: Optional[int] = None, filter=None) -> List[Dict[str, Any]]:
         """Same result records as batch_search, every stage batched over the queries: one
         bi-encoder pass and one sweep of the corpus per 64 queries (stage 1), one query forward
         and one MaxSim launch (stage 2, with the resident token store), one length-sorted pass
         of the cross-encoder over all (query, candidate) pairs (stage 3).  Stage times are
-        reported as equal shares of the batch's stage times."""
+        reported as equal shares of the batch's stage times.  ``filter``: one filter for every query or a list
+        with one per query (see :meth:`search`); a filtered batch takes the record path."""
         if not self.stage1 or not self.stage2 or not self.stage3:
             self.initialize_stages()
         top_k = top_k or self.config.stage3_top_k
@@ -304,12 +317,16 @@ class RetrievalPipeline:
         gc_was_on = gc.isenabled()
         gc.disable()
         try:
-            fast = self._search_many_arrays(queries, top_k)
-            if fast is not None:
-                return fast
+            if filter is None:
+                fast = self._search_many_arrays(queries, top_k)
+                if fast is not None:
+                    return fast
             total_start = self._now()
             t = self._now()
-            s1 = self.stage1.search_many(queries, self.config.stage1_top_k)
+            if filter is None:
+                s1 = self.stage1.search_many(queries, self.config.stage1_top_k)
+            else:
+                s1 = self.stage1.search_many(queries, self.config.stage1_top_k, filter=filter)
             t1 = (time.time() - t) / n if t else None
             s2, s3, t2, t3 = self._later_stages_many(queries, s1)
             total = (time.time() - total_start) / n if total_start else None

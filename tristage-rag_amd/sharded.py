@@ -90,12 +90,16 @@ class ShardedFlatIPIndex:
             raise ValueError(f"expected {self.n_total} rows, got {rows.shape[0]}")
         self.local_index.add(rows[self.lo:self.hi])
 
-    def search(self, q, k: int, async_: bool = False, inputs_ready: bool = False):
+    def search(self, q, k: int, async_: bool = False, inputs_ready: bool = False, allowed=None):
         """Global top-k for the replicated query batch `q` (tensor).  Returns
         tensors (D float32 [B,k], I int64 [B,k]) identical on every rank.
 
         ``async_=True``: local search, all-gather and merge are only enqueued (all
-        three are stream-ordered); call :meth:`finish` before reading the result."""
+        three are stream-ordered); call :meth:`finish` before reading the result.
+        ``allowed`` (filtered search) is not supported on the sharded index."""
+        if allowed is not None:
+            raise NotImplementedError("filtered search (allowed=) is not supported by ShardedFlatIPIndex; "
+                                      "use a single FlatIPIndex")
         import torch
         if not torch.is_tensor(q):  # FAISS-style numpy call: same path, numpy back
             D, I = self.search(torch.from_numpy(np.ascontiguousarray(q, dtype=np.float32)), k)

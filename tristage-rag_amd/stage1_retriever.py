@@ -26,7 +26,7 @@ import logging
 import math
 import os
 import re
-from collections import defaultdict
+from collections import OrderedDict, defaultdict
 from dataclasses import dataclass
 from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple
 
@@ -75,6 +75,9 @@ def amp_torch_dtype(name: str):
     if key in ("fp16", "f16", "float16", "half"):
         return torch.float16
     raise ValueError(f"amp_dtype must be 'bf16' or 'fp16', not {name!r}")
+
+
+_MISSING = object()   # a metadata key a document does not have: equal to no filter value
 
 
 class BM25Index:
@@ -183,8 +186,9 @@ class BM25Index:
     def _search_gpu(self, query: str, top_k: int) -> List[Tuple[int, float]]:
         return self._search_gpu_many([query], top_k)[0]
 
-    def _search_gpu_many(self, queries: Sequence[str], top_k: int, arrays: bool = False):
-        """All queries through ts_bm25_search_batch: one call and one synchronisation for the batch."""
+    def _search_gpu_many(self, queries: Sequence[str], top_k: int, arrays: bool = False, allowed=None):
+        """All queries through ts_bm25_search_batch (ts_bm25_search_batch_filtered with ``allowed``: one bool
+        array over the documents, or None, per query): one call and one synchronisation for the batch."""
         from . import _lib
         lib = _lib.load()
         terms = [np.array([self._term_id[t] for t in self.tokenize(q) if t in self._term_id], dtype=np.int32) for q in queries]
@@ -198,32 +202,63 @@ class BM25Index:
         n_out = np.zeros(max(nq, 1), dtype=np.int32)
         if k > 0 and nq and off[-1]:
             with self._gpu_lock:      # one accumulator per handle, and ctypes drops the GIL for the call
-                _lib.check(lib.ts_bm25_search_batch(self._gpu, flat.ctypes.data, off.ctypes.data, nq, k, out_s.ctypes.data,
-                                                    out_i.ctypes.data, n_out.ctypes.data, None))
+                if allowed is None:
+                    _lib.check(lib.ts_bm25_search_batch(self._gpu, flat.ctypes.data, off.ctypes.data, nq, k,
+                                                        out_s.ctypes.data, out_i.ctypes.data, n_out.ctypes.data, None))
+                else:
+                    from .index import pack_allowed
+                    packed, seen = [], {}
+                    moq = np.full(nq, -1, dtype=np.int32)
+                    for qi, a in enumerate(allowed):
+                        if a is not None:
+                            if id(a) not in seen:
+                                seen[id(a)] = len(packed)
+                                packed.append(pack_allowed(a, self.corpus_size))
+                            moq[qi] = seen[id(a)]
+                    bits = np.ascontiguousarray(np.stack(packed)) if packed else np.zeros((1, 1), np.uint32)
+                    _lib.check(lib.ts_bm25_search_batch_filtered(
+                        self._gpu, flat.ctypes.data, off.ctypes.data, nq, k, bits.ctypes.data, bits.shape[1],
+                        len(packed), moq.ctypes.data, _lib.TS_FLAG_HOST_PTR, out_s.ctypes.data, out_i.ctypes.data,
+                        n_out.ctypes.data, None))
+        allow_of = (lambda q: None) if allowed is None else (lambda q: allowed[q])
         if arrays:      # (ids, scores) per query, no tuples: the array path of Stage1Retriever fuses them as they are
-            want = min(int(top_k), self.corpus_size)
             out = []
             for q in range(nq):
                 n = int(n_out[q])
+                a = allow_of(q)
+                want = min(int(top_k), self.corpus_size if a is None else int(np.count_nonzero(a)))
                 if n < want:    # documents without a query term score exactly 0.0 and follow in ascending id order
-                    pad = self._pad_with_zero_scores(list(zip(out_i[q, :n].tolist(), out_s[q, :n].tolist())), top_k)
+                    pad = self._pad_with_zero_scores(list(zip(out_i[q, :n].tolist(), out_s[q, :n].tolist())), top_k, a)
                     out.append((np.array([i for i, _ in pad], dtype=np.int64), np.array([v for _, v in pad], dtype=np.float64)))
                 else:
                     out.append((out_i[q, :n], out_s[q, :n]))
             return out
-        return [self._pad_with_zero_scores(list(zip(out_i[q, : n_out[q]].tolist(), out_s[q, : n_out[q]].tolist())), top_k)
+        return [self._pad_with_zero_scores(list(zip(out_i[q, : n_out[q]].tolist(), out_s[q, : n_out[q]].tolist())), top_k,
+                                           allow_of(q))
                 for q in range(nq)]
 
-    def _pad_with_zero_scores(self, res: List[Tuple[int, float]], top_k: int) -> List[Tuple[int, float]]:
-        if len(res) < min(top_k, self.corpus_size):
-            # every document with a non-zero score is listed; the rest score exactly 0.0 and
-            # follow in ascending id order (the reference's stable sort)
+    def _pad_with_zero_scores(self, res: List[Tuple[int, float]], top_k: int, allowed=None) -> List[Tuple[int, float]]:
+        """``allowed`` (bool array over the documents, or None): a filtered search pads with allowed documents only."""
+        if allowed is None:
+            if len(res) < min(top_k, self.corpus_size):
+                # every document with a non-zero score is listed; the rest score exactly 0.0 and
+                # follow in ascending id order (the reference's stable sort)
+                seen = {i for i, _ in res}
+                d = 0
+                while len(res) < min(top_k, self.corpus_size):
+                    if d not in seen:
+                        res.append((d, 0.0))
+                    d += 1
+            return res
+        cand = np.flatnonzero(np.asarray(allowed, dtype=bool))
+        want = min(int(top_k), int(cand.size))
+        if len(res) < want:
             seen = {i for i, _ in res}
-            d = 0
-            while len(res) < min(top_k, self.corpus_size):
+            for d in cand.tolist():
+                if len(res) >= want:
+                    break
                 if d not in seen:
                     res.append((d, 0.0))
-                d += 1
         return res
 
     def close(self) -> None:
@@ -261,27 +296,35 @@ class BM25Index:
             acc[ds] += self.idf[tok] * ((tf * (self.k1 + 1)) / (tf + self._len_norm[ds]))
         return acc
 
-    def search_many(self, queries: Sequence[str], top_k: int = 10) -> List[List[Tuple[int, float]]]:
-        """search() for several queries (the GPU index takes them in one call)."""
+    def search_many(self, queries: Sequence[str], top_k: int = 10, allowed=None) -> List[List[Tuple[int, float]]]:
+        """search() for several queries (the GPU index takes them in one call).  ``allowed``: None, or one bool
+        array over the documents (or None) per query."""
         if self._gpu is not None:
-            return self._search_gpu_many(list(queries), top_k)
-        return [self.search(q, top_k) for q in queries]
+            return self._search_gpu_many(list(queries), top_k, allowed=allowed)
+        return [self.search(q, top_k, allowed=None if allowed is None else allowed[i]) for i, q in enumerate(queries)]
 
-    def search_many_arrays(self, queries: Sequence[str], top_k: int = 10):
+    def search_many_arrays(self, queries: Sequence[str], top_k: int = 10, allowed=None):
         """search_many() as (ids int64 [n], scores float64 [n]) per query."""
         if self._gpu is not None:
-            return self._search_gpu_many(list(queries), top_k, arrays=True)
+            return self._search_gpu_many(list(queries), top_k, arrays=True, allowed=allowed)
         out = []
-        for q in queries:
-            r = self.search(q, top_k)
+        for qi, q in enumerate(queries):
+            r = self.search(q, top_k, allowed=None if allowed is None else allowed[qi])
             out.append((np.fromiter((i for i, _ in r), dtype=np.int64, count=len(r)),
                         np.fromiter((v for _, v in r), dtype=np.float64, count=len(r))))
         return out
 
-    def search(self, query: str, top_k: int = 10) -> List[Tuple[int, float]]:
+    def search(self, query: str, top_k: int = 10, allowed=None) -> List[Tuple[int, float]]:
+        """``allowed``: a bool array over the documents — only those are ranked (zero scores included)."""
         if self._gpu is not None:
-            return self._search_gpu(query, top_k)
+            if allowed is None:
+                return self._search_gpu(query, top_k)
+            return self._search_gpu_many([query], top_k, allowed=[allowed])[0]
         s = self.scores(query)
+        if allowed is not None:
+            cand = np.flatnonzero(np.asarray(allowed, dtype=bool))
+            order = cand[np.argsort(-s[cand], kind="stable")[:top_k]]
+            return [(int(i), float(s[i])) for i in order]
         order = np.argsort(-s, kind="stable")[:top_k]  # ties keep ascending doc order
         return [(int(i), float(s[i])) for i in order]
 
@@ -299,6 +342,14 @@ class Stage1Retriever:
         self.bm25_index: Optional[BM25Index] = None
         self.documents: List[str] = []
         self.doc_metadata: List[Dict[str, Any]] = []
+        # filtered search: host bitmaps of the dict filters' (key, value) pairs, extended as documents arrive, and a
+        # small LRU of packed device masks of whole dict filters.  Neither is persisted, and both belong to ONE
+        # metadata list (_filter_cache_meta): when doc_metadata is replaced (load_index, the sharded pipeline) they
+        # are dropped and rebuilt on first use.  Metadata is append-only in between (add_documents).
+        self._kv_bitmaps: Dict[Any, np.ndarray] = {}
+        self._mask_lru: "OrderedDict[Any, Any]" = OrderedDict()
+        self._filter_cache_meta = self.doc_metadata
+        self.filter_cache_size = 8
         self._index_factory = index_factory
         os.makedirs(self.config.cache_dir, exist_ok=True)
         os.makedirs(self.config.index_dir, exist_ok=True)
@@ -409,6 +460,135 @@ class Stage1Retriever:
             self.bm25_index.fit(self.documents)
         self.logger.info(f"Documents added successfully. Total documents: {len(self.documents)}")
 
+    # -- filters -----------------------------------------------------------
+    def _reset_filter_caches(self) -> None:
+        self._kv_bitmaps.clear()
+        self._mask_lru.clear()
+        self._filter_cache_meta = self.doc_metadata
+
+    def _check_filter_caches(self) -> None:
+        """Drop the filter caches if they were built from another metadata list than the current one."""
+        if self._filter_cache_meta is not self.doc_metadata:
+            self._reset_filter_caches()
+
+    def _kv_bitmap(self, key, value) -> np.ndarray:
+        """Documents whose metadata has ``key`` equal to ``value`` (bool [n_docs]); built once per (key, value)
+        and extended by the documents added since."""
+        n = len(self.doc_metadata)
+        try:
+            ck = (key, value)
+            hash(ck)
+        except TypeError:   # an unhashable value: evaluated per call
+            return np.fromiter((md.get(key, _MISSING) == value for md in self.doc_metadata), dtype=bool, count=n)
+        bm = self._kv_bitmaps.get(ck)
+        if bm is not None and bm.shape[0] > n:   # (a shorter corpus than the bitmap: not the corpus it was built on)
+            bm = None
+        have = 0 if bm is None else bm.shape[0]
+        if have < n:
+            ext = np.fromiter((md.get(key, _MISSING) == value for md in self.doc_metadata[have:]), dtype=bool,
+                              count=n - have)
+            bm = ext if bm is None else np.concatenate([bm, ext])
+            self._kv_bitmaps[ck] = bm
+        return bm
+
+    def filter_mask(self, filter) -> Optional[np.ndarray]:
+        """A filter spec -> bool array over the documents (None: no filter).  Specs: a dict ``{key: value}``
+        (every key equal; a list / tuple / set value means membership), a callable ``metadata -> bool``, a
+        sequence of document indices, or a bool array over the documents."""
+        n = len(self.documents)
+        if filter is None:
+            return None
+        self._check_filter_caches()
+        if isinstance(filter, dict):
+            m = np.ones(n, dtype=bool)
+            for key, value in filter.items():
+                if isinstance(value, (list, tuple, set, frozenset)):
+                    any_ = np.zeros(n, dtype=bool)
+                    for v in value:
+                        any_ |= self._kv_bitmap(key, v)
+                    m &= any_
+                else:
+                    m &= self._kv_bitmap(key, value)
+            return m
+        if callable(filter):
+            return np.fromiter((bool(filter(md)) for md in self.doc_metadata), dtype=bool, count=n)
+        if hasattr(filter, "detach"):
+            filter = filter.detach().cpu().numpy()
+        arr = np.asarray(filter)
+        if arr.dtype == np.bool_:
+            if arr.shape != (n,):
+                raise ValueError(f"a bool filter needs one entry per document ({n}), got shape {arr.shape}")
+            return arr
+        if arr.size == 0:
+            return np.zeros(n, dtype=bool)
+        if arr.ndim != 1 or not np.issubdtype(arr.dtype, np.integer):
+            raise TypeError("filter: expected a dict, a callable, document indices or a bool array")
+        if arr.min() < 0 or arr.max() >= n:
+            raise ValueError(f"filter: document index out of range [0, {n})")
+        m = np.zeros(n, dtype=bool)
+        m[arr] = True
+        return m
+
+    @staticmethod
+    def _is_spec(f) -> bool:
+        return f is None or isinstance(f, (dict, list, tuple, np.ndarray)) or callable(f) or hasattr(f, "detach")
+
+    def _per_query_filters(self, filter, nq: int) -> Optional[list]:
+        """One filter for every query, or a list with one filter per query -> one filter per query (None: no
+        filter at all).  A list of integers is one filter (document indices), not one per query."""
+        if filter is None:
+            return None
+        per_query = (isinstance(filter, (list, tuple)) and len(filter) == nq and len(filter) > 0 and
+                     all(self._is_spec(f) for f in filter) and not all(isinstance(f, (int, np.integer)) for f in filter))
+        return list(filter) if per_query else [filter] * nq
+
+    def _filter_masks(self, filter, nq: int) -> Optional[List[Optional[np.ndarray]]]:
+        """-> one mask (or None) per query, None when no query is filtered."""
+        specs = self._per_query_filters(filter, nq)
+        if specs is None:
+            return None
+        cache: Dict[int, Optional[np.ndarray]] = {}
+        masks = []
+        for f in specs:   # (one filter shared by the queries: resolved once)
+            if id(f) not in cache:
+                cache[id(f)] = self.filter_mask(f)
+            masks.append(cache[id(f)])
+        return None if all(m is None for m in masks) else masks
+
+    def _index_mask(self, filter, mask: np.ndarray):
+        """What FlatIPIndex.search(allowed=) gets for one query: for a dict filter on a device index, packed words
+        on the device from the LRU (a repeated tenant filter is neither re-packed nor re-uploaded)."""
+        if mask is None or not isinstance(filter, dict) or not self._device_path():
+            return mask
+        self._check_filter_caches()
+        try:
+            key = (tuple(sorted((k, tuple(sorted(map(repr, v))) if isinstance(v, (list, tuple, set, frozenset)) else v)
+                                for k, v in filter.items())), len(self.documents))
+            hash(key)
+        except TypeError:
+            return mask
+        hit = self._mask_lru.get(key)
+        if hit is None:
+            import torch
+            from .index import pack_allowed
+            words = pack_allowed(mask, len(self.documents))
+            hit = torch.from_numpy(words.view(np.int32)).to(torch.device("cuda", self.config.gpu_index_device))
+            self._mask_lru[key] = hit
+            while len(self._mask_lru) > self.filter_cache_size:
+                self._mask_lru.popitem(last=False)
+        else:
+            self._mask_lru.move_to_end(key)
+        return hit
+
+    def _dense_search(self, q, top_k: int, masks, filters):
+        """faiss_index.search, with ``allowed=`` when a filter is given."""
+        if masks is None:
+            return self.faiss_index.search(q, top_k)
+        per_q = self._per_query_filters(filters, len(masks))
+        allowed = [self._index_mask(f, m) for f, m in zip(per_q, masks)]
+        same = all(a is allowed[0] for a in allowed)
+        return self.faiss_index.search(q, top_k, allowed=allowed[0] if same else allowed)
+
     # -- fusion ------------------------------------------------------------
     def _reciprocal_rank_fusion(self, dense_results, bm25_results):
         """reference :326-343"""
@@ -437,10 +617,14 @@ class Stage1Retriever:
         return fused
 
     # -- search ------------------------------------------------------------
-    def _finish(self, query: str, dense_results: List[Tuple[int, float]], top_k: int) -> List[Dict[str, Any]]:
+    def _finish(self, query: str, dense_results: List[Tuple[int, float]], top_k: int,
+                allowed: Optional[np.ndarray] = None) -> List[Dict[str, Any]]:
         bm25_results: List[Tuple[int, float]] = []
         if self.config.enable_bm25 and self.bm25_index is not None:
-            bm25_results = self.bm25_index.search(query, self.config.bm25_top_k)
+            if allowed is None:
+                bm25_results = self.bm25_index.search(query, self.config.bm25_top_k)
+            else:   # the lexical half is filtered too: no disallowed document may come back through it
+                bm25_results = self.bm25_index.search(query, self.config.bm25_top_k, allowed=allowed)
         if self.config.enable_bm25 and bm25_results:
             if self.config.fusion_method == "rrf":
                 fused = self._reciprocal_rank_fusion(dense_results, bm25_results)
@@ -457,47 +641,59 @@ class Stage1Retriever:
                                 "stage": "stage1"})
         return results
 
-    def search(self, query: str, top_k: Optional[int] = None) -> List[Dict[str, Any]]:
+    def search(self, query: str, top_k: Optional[int] = None, filter=None) -> List[Dict[str, Any]]:
+        """``filter``: restrict the candidates to some documents (see :meth:`filter_mask`); fewer than
+        ``top_k`` results when fewer documents are allowed, none when none are."""
         if self.faiss_index is None:
             raise ValueError("No documents indexed. Call add_documents() first.")
         top_k = top_k or self.config.top_k_candidates
+        masks = self._filter_masks(filter, 1)
+        if masks is not None and not masks[0].any():
+            return []
         if self._device_path():
-            D, I = self.faiss_index.search(self._normalized_query_tensor([query]), top_k)
+            D, I = self._dense_search(self._normalized_query_tensor([query]), top_k, masks, filter)
             scores, ids = D.cpu().numpy(), I.cpu().numpy()
         else:
             q = self._normalize_embeddings(self._encode_batch([query]))
-            scores, ids = self.faiss_index.search(q, top_k)
+            scores, ids = self._dense_search(q, top_k, masks, filter)
         dense = [(int(i), float(s)) for i, s in zip(ids[0], scores[0]) if i >= 0]
-        results = self._finish(query, dense, top_k)
+        results = self._finish(query, dense, top_k, None if masks is None else masks[0])
         self.logger.info(f"Stage 1 search completed. Found {len(results)} candidates")
         return results
 
-    def search_many(self, queries: Sequence[str], top_k: Optional[int] = None) -> List[List[Dict[str, Any]]]:
+    def search_many(self, queries: Sequence[str], top_k: Optional[int] = None, filter=None) -> List[List[Dict[str, Any]]]:
         """All queries through ONE encoder pass and ONE index call (64 queries share a
-        single sweep over the corpus on the GPU)."""
+        single sweep over the corpus on the GPU).  ``filter``: one filter for every query, or a list with one
+        per query (None: unfiltered)."""
         if self.faiss_index is None:
             raise ValueError("No documents indexed. Call add_documents() first.")
         top_k = top_k or self.config.top_k_candidates
         if not queries:
             return []
+        masks = self._filter_masks(filter, len(queries))
         if self._device_path():
-            D, I = self.faiss_index.search(self._normalized_query_tensor(list(queries)), top_k)
+            D, I = self._dense_search(self._normalized_query_tensor(list(queries)), top_k, masks, filter)
             scores, ids = D.cpu().numpy(), I.cpu().numpy()
         else:
             q = self._normalize_embeddings(self._encode_batch(list(queries)))
-            scores, ids = self.faiss_index.search(q, top_k)
+            scores, ids = self._dense_search(q, top_k, masks, filter)
         out = []
         for qi, query in enumerate(queries):
+            m = None if masks is None else masks[qi]
+            if m is not None and not m.any():
+                out.append([])
+                continue
             dense = [(int(i), float(s)) for i, s in zip(ids[qi], scores[qi]) if i >= 0]
-            out.append(self._finish(query, dense, top_k))
+            out.append(self._finish(query, dense, top_k, m))
         return out
 
-    def search_many_arrays(self, queries: Sequence[str], top_k: Optional[int] = None):
+    def search_many_arrays(self, queries: Sequence[str], top_k: Optional[int] = None, filter=None):
         """Stage 1 for a query batch WITHOUT building result records: (ids int64 [B, k'], scores [B, k'])
         as torch tensors on the index's device for the pure dense search, numpy arrays (float64 fused
         scores) when BM25 fusion is on.  Row q, in order, is exactly what ``search_many`` would list for
         query q.  None when the corpus holds fewer than top_k rows (the caller then uses ``search_many``,
-        which deals with padded results)."""
+        which deals with padded results).  ``filter`` as for :meth:`search_many`: None also when some query has
+        fewer than top_k allowed documents."""
         import torch
         if self.faiss_index is None:
             raise ValueError("No documents indexed. Call add_documents() first.")
@@ -505,6 +701,11 @@ class Stage1Retriever:
         n = int(self.faiss_index.ntotal)
         if top_k > n or n != len(self.documents):
             return None
+        masks = self._filter_masks(filter, len(queries))
+        if masks is not None:
+            if any(m is not None and int(np.count_nonzero(m)) < top_k for m in masks):
+                return None
+            return self._search_many_arrays_filtered(list(queries), top_k, masks, filter)
         fuse = self.config.enable_bm25 and self.bm25_index is not None
         if self._device_path():
             qt = self._normalized_query_tensor(list(queries))
@@ -529,6 +730,30 @@ class Stage1Retriever:
         out_s = np.empty((len(queries), top_k), dtype=np.float64)
         bms = (bm25.search_many_arrays(list(queries), self.config.bm25_top_k) if hasattr(bm25, "search_many_arrays")
                else [bm25.search(q, self.config.bm25_top_k) for q in queries])
+        for qi, bm in enumerate(bms):
+            fi, fs = self._fuse_arrays(ids[qi], scores[qi], bm)
+            if len(fi) < top_k:
+                return None
+            out_i[qi], out_s[qi] = fi[:top_k], fs[:top_k]
+        return out_i, out_s
+
+    def _search_many_arrays_filtered(self, queries: List[str], top_k: int, masks, filter):
+        """search_many_arrays with a filter (every query has >= top_k allowed documents), same return types as without
+        one: torch tensors (ids, scores) for the pure dense search — on the index's device on the device path —,
+        numpy arrays with float64 fused scores when BM25 fusion is on (through the host arrays code, _fuse_arrays,
+        with the BM25 lists filtered alike)."""
+        import torch
+        if self._device_path():
+            D, I = self._dense_search(self._normalized_query_tensor(queries), top_k, masks, filter)
+        else:
+            D, I = self._dense_search(self._normalize_embeddings(self._encode_batch(queries)), top_k, masks, filter)
+            D, I = torch.as_tensor(D), torch.as_tensor(I)
+        if not (self.config.enable_bm25 and self.bm25_index is not None):
+            return I, D
+        ids, scores = I.cpu().numpy(), D.cpu().numpy()
+        bms = self.bm25_index.search_many_arrays(queries, self.config.bm25_top_k, allowed=masks)
+        out_i = np.empty((len(queries), top_k), dtype=np.int64)
+        out_s = np.empty((len(queries), top_k), dtype=np.float64)
         for qi, bm in enumerate(bms):
             fi, fs = self._fuse_arrays(ids[qi], scores[qi], bm)
             if len(fi) < top_k:
@@ -629,6 +854,7 @@ class Stage1Retriever:
         manifest = json.load(open(index_path))
         self.documents = manifest["documents"]
         self.doc_metadata = manifest["doc_metadata"]
+        self._reset_filter_caches()   # the cached filter bitmaps describe the corpus that was here before
         self.faiss_index = None
         if manifest.get("matrix"):
             mat = np.load(os.path.join(os.path.dirname(os.path.abspath(index_path)), manifest["matrix"]),
