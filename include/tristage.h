@@ -46,7 +46,9 @@ extern "C" {
  * newer).  1 = round 1 (24 entry points).  2 = round 2 changed ts_attention_varlen (offsets, window, rotary
  * tables) and added 15 entry points.  3 = round 3 added ts_index_read_probe, ts_index_filter_path and
  * ts_linear_add_layernorm, ts_mlp_add_layernorm.  4 = filtered search: ts_index_search_filtered,
- * ts_index_last_filter_info and ts_bm25_search_batch_filtered (no existing signature changed).             */
+ * ts_index_last_filter_info and ts_bm25_search_batch_filtered (no existing signature changed).  Coalesced passes
+ * (TS_FLAG_COALESCE, ts_index_flush, ts_coalesce_groups) were added within version 4: no signature changed, and a
+ * caller that never sets the flag sees the library it was built against.                                     */
 #define TS_ABI_VERSION 4
 
 typedef struct ts_index ts_index; /* opaque */
@@ -84,6 +86,11 @@ enum ts_metric { TS_METRIC_INNER_PRODUCT = 0 };
 #define TS_FLAG_ONE_LAUNCH 64u  /* search: take the one-launch scan wherever its threshold estimate is
                                    valid, also where the five-launch path is the default (pipelined
                                    submission, corpora above 4 M rows); results are identical      */
+#define TS_FLAG_COALESCE 128u   /* with TS_FLAG_ASYNC: the search's filter scan may be held until other
+                                   batches arrive, so that one corpus pass serves up to
+                                   ts_coalesce_groups() 32-query groups (see "coalesced passes"
+                                   below).  Results are identical; they are complete after
+                                   ts_index_finish() (or ts_index_flush() and stream order).    */
 #define TS_FLAG_NORMALIZE 4u    /* add: L2-normalise rows x/(|x|+1e-8) on device first
                                    (reference src/stage1_retriever.py:285-288) */
 
@@ -176,6 +183,25 @@ int64_t ts_index_last_ticket(const ts_index* h);
 int ts_index_filter_path(const ts_index* h, int32_t k);
 int ts_index_finish(ts_index* h, void* stream, int64_t* failed_tickets, int32_t max_failed,
                     int32_t* n_failed);
+
+/* ---- coalesced passes (TS_FLAG_COALESCE | TS_FLAG_ASYNC) ------------------------
+ * An unfiltered, unpipelined asynchronous search on the five-launch filter path (corpora above 4 M rows, or
+ * TS_FLAG_CLASSIC) enqueues its query preparation, sample scan and thresholds on `stream` at once (the queries
+ * are read in stream order, as without the flag) and puts its 32-query groups in a pending-pass queue on the
+ * handle.  When the queue holds ts_coalesce_groups() groups, one filter scan over the corpus serves them all,
+ * and the select of every batch whose last group was in it follows on the same stream.  Groups of different
+ * batches, sizes and k share a pass; a batch of 64 may straddle two passes.  A search that cannot join
+ * (other flags, a filtered search, another stream, the one-launch or dense path, fewer than 3 groups per pass)
+ * joins nothing and is ordered behind the held work.  The queue is flushed — a partial pass is launched — by
+ * ts_index_finish, ts_index_flush, any search that cannot join, ts_index_add / reset / reserve /
+ * set_id_offset / reconstruct / scores / destroy (a held batch searches the corpus it was submitted against),
+ * and the unfinished-pass limit.  Tickets, verification and redo are those of any asynchronous search.
+ * Not for callers that consume results in stream order before ts_index_finish without ts_index_flush.       */
+/* enqueue every held pass on the queue's stream; `stream`'s later work is ordered behind it.  No host sync. */
+int ts_index_flush(ts_index* h, void* stream);
+/* 32-query groups per coalesced pass for this dimension and storage type: 4 up to a padded dimension of 512,
+ * 3 at 640 and 768, 2 from 896 (no coalescing below 3), 0 for fp32 storage.  Needs no GPU.                   */
+int32_t ts_coalesce_groups(int32_t dim, int32_t storage_dtype);
 
 /* ---- introspection -------------------------------------------------------
  * faiss_index.ntotal / .d                                                    */

@@ -32,6 +32,7 @@ def header_abi_version() -> int:
 
 
 TS_FLAG_HOST_PTR, TS_FLAG_NO_FILTER, TS_FLAG_NORMALIZE, TS_FLAG_ASYNC, TS_FLAG_PIPELINE, TS_FLAG_CLASSIC, TS_FLAG_ONE_LAUNCH = 1, 2, 4, 8, 16, 32, 64
+TS_FLAG_COALESCE = 128
 
 # name -> (restype, argtypes); mirrors include/tristage.h one to one
 SIGNATURES = {
@@ -55,6 +56,8 @@ SIGNATURES = {
     "ts_index_last_ticket": (c_int64, [c_void_p]),
     "ts_index_filter_path": (c_int32, [c_void_p, c_int32]),
     "ts_index_finish": (c_int32, [c_void_p, c_void_p, POINTER(c_int64), c_int32, POINTER(c_int32)]),
+    "ts_index_flush": (c_int32, [c_void_p, c_void_p]),
+    "ts_coalesce_groups": (c_int32, [c_int32, c_int32]),
     "ts_index_set_profiling": (c_int32, [c_void_p, c_int32]),
     "ts_index_get_timings": (c_int32, [c_void_p, POINTER(ctypes.c_double), POINTER(c_int64), c_int32]),
     "ts_index_read_probe": (c_int32, [c_void_p, c_int32, POINTER(ctypes.c_double), POINTER(ctypes.c_double),

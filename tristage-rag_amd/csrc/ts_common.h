@@ -150,6 +150,32 @@ struct MaskedScanParams : ScanParams {
 };
 int ts_launch_scan_masked(const TsLayout& L, int qh, const MaskedScanParams& p, int num_cus, hipStream_t stream);
 
+// Coalesced passes (TS_FLAG_COALESCE, scan_multi_kernel): one filter scan over every row block for G 32-query
+// groups that may come from different batches.  Group g is the query columns 32*ghalf[g] .. +32 of the Q image
+// gimg[g] (laid out with gqh[g] halves per k group), with its batch's thresholds and candidate lists at the same
+// query offset: gtau[g][j], gcnt[g][j], gscore[g][j*cand_cap + slot], gid[g][j*cand_cap + slot] for query j of
+// the group.  The base's qimg / nq / tau / cand_cnt / cand_score / cand_id are unused; blk0 / blk_stride /
+// nwork / ntotal / cand_cap mean what they mean for scan_kernel.  stage_cap: LDS staging entries (8 B each).
+#define TS_MAX_GROUPS 4
+struct MultiScanParams : ScanParams {
+  const uint4* gimg[TS_MAX_GROUPS];
+  int gqh[TS_MAX_GROUPS];
+  int ghalf[TS_MAX_GROUPS];
+  const float* gtau[TS_MAX_GROUPS];
+  uint32_t* gcnt[TS_MAX_GROUPS];
+  float* gscore[TS_MAX_GROUPS];
+  int32_t* gid[TS_MAX_GROUPS];
+  uint32_t stage_cap;
+};
+// The largest group count (<= TS_MAX_GROUPS) whose query images and a minimal staging area fit the LDS; 0 for fp32
+// storage (no multi-group kernel).  Host-only arithmetic.
+int ts_scan_multi_groups(const TsLayout& L);
+// staging entries the kernel gets for G groups (0: G groups do not fit)
+uint32_t ts_scan_multi_stage_cap(const TsLayout& L, int G);
+// false where a workgroup's survivor keys could not encode a wave's iteration count (the grid is too small for nblk)
+bool ts_scan_multi_fits(int64_t nblk, int num_cus);
+int ts_launch_scan_multi(const TsLayout& L, int G, const MultiScanParams& p, int num_cus, hipStream_t stream);
+
 int ts_launch_scan(const TsLayout& L, int mode, int qh, const ScanParams& p,
                    int num_cus, hipStream_t stream);
 

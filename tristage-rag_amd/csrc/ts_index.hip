@@ -92,6 +92,9 @@ constexpr uint32_t kOversample = 4;         // expected candidates ~ 4k per quer
 constexpr int64_t kDenseChunkRows = 1 << 20;
 constexpr int64_t kOneLaunchMaxRows = 4 << 20;   // default use of the one-launch search (search_pass_on)
 constexpr int kHeadStartUs = 12;           // pipelined mode: delay of the select behind the next scan (search_pass)
+// coalesced passes (co_submit): expected survivors ~ 3k per query instead of 4k, so that three groups' survivors
+// fit the staging area the query images leave at d = 768 (about 1.3 k per workgroup and pass against 1.9 k slots)
+constexpr int64_t kCoalesceOversample = 3;
 
 }  // namespace
 
@@ -153,6 +156,22 @@ struct ts_index {
   uint64_t slot_next = 0;
   int64_t next_ticket = 0;
   hipEvent_t async_ev[2 * TS_ASYNC_SLOTS] = {};
+  // coalesced passes (TS_FLAG_COALESCE): batches whose query prep, sample scan and thresholds are
+  // enqueued but whose filter scan and select wait for co_gmax 32-query groups to share one scan.  A held batch
+  // keeps its workspace set busy until its select is enqueued.  co_mu serialises coalesced submissions and
+  // flushes; it is taken before `mu`, never while `mu` is held.
+  struct CoBatch { WSet* W; int nq, qh, k, slot, groups_left; float* out_s; int64_t* out_i; };
+  struct CoGroup { int batch, half; };
+  std::mutex co_mu;
+  int co_gmax = 0;                       // groups per pass (ts_coalesce_groups); < 3: no coalescing
+  hipStream_t co_stream = nullptr;       // the stream of the held batches
+  CoBatch co_batch[TS_MAX_GROUPS] = {};  // held batches in submission order
+  int co_nbatch = 0;
+  CoGroup co_group[TS_MAX_GROUPS] = {};  // pending groups of the next pass
+  int co_ngroup = 0;
+  uint64_t co_pass_seq = 0;              // timed passes: every prof_every-th
+  hipEvent_t co_ev = nullptr;            // recorded on co_stream after every pass and its selects (co_launch_pass)
+  bool co_ev_live = false;               // co_ev may still be pending: work on another stream must wait for it
   // optional per-phase timing with HIP events on the caller's stream
   // `profiling` / `prof_every` change only under exclusive access (ts_index_set_profiling); a profiled search holds
   // prof_mu for its whole duration, which is what makes the ONE set of events `ev` safe; everything that varies
@@ -164,6 +183,8 @@ struct ts_index {
   double phase_ms[TS_NPHASE] = {};
   int64_t phase_cnt[TS_NPHASE] = {};
 };
+
+static int co_flush(ts_index* h, hipStream_t s);
 
 // Per-search profiling state (round 2 kept these three in the handle, written by every search: a data race
 // between concurrent callers of one handle even with profiling off).
@@ -252,6 +273,7 @@ extern "C" int ts_index_create(int32_t dim, int32_t storage_dtype, int32_t metri
   if (!h) { ts_set_error("out of host memory"); return TS_ERR_OOM; }
   h->device = device;
   h->L = L;
+  h->co_gmax = ts_coalesce_groups(dim, storage_dtype);
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
     h->num_cus = prop.multiProcessorCount;
@@ -267,6 +289,10 @@ extern "C" int ts_index_create(int32_t dim, int32_t storage_dtype, int32_t metri
       ts_set_error("hipEventCreate failed");
       st = TS_ERR_HIP;
     }
+  }
+  if (st == TS_OK && hipEventCreateWithFlags(&h->co_ev, hipEventDisableTiming) != hipSuccess) {
+    ts_set_error("hipEventCreate failed");
+    st = TS_ERR_HIP;
   }
   if (st == TS_OK &&
       (hipHostMalloc((void**)&h->host_status, (size_t)(TS_ASYNC_SLOTS + 1) * TS_SLOT_WORDS * 4, hipHostMallocMapped) != hipSuccess ||
@@ -285,6 +311,7 @@ extern "C" int ts_index_create(int32_t dim, int32_t storage_dtype, int32_t metri
 extern "C" int ts_index_destroy(ts_index* h) {
   if (!h) return TS_OK;
   DeviceGuard g(h->device);
+  (void)co_flush(h, nullptr);
   (void)hipDeviceSynchronize();
   if (h->corpus) (void)hipFree(h->corpus);
   DevBuf* bufs[] = {&h->stage, &h->den, &h->qstage, &h->out_s, &h->out_i, &h->mstage};
@@ -305,12 +332,14 @@ extern "C" int ts_index_destroy(ts_index* h) {
     if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : h->async_ev)
     if (e) (void)hipEventDestroy(e);
+  if (h->co_ev) (void)hipEventDestroy(h->co_ev);
   delete h;
   return TS_OK;
 }
 
 extern "C" int ts_index_reset(ts_index* h) {
   if (!h) { ts_set_error("null handle"); return TS_ERR_INVALID; }
+  { DeviceGuard g(h->device); TS_CHECK(co_flush(h, nullptr)); }   // held passes search the corpus they were submitted against
   h->ntotal = 0;
   return TS_OK;
 }
@@ -319,6 +348,7 @@ extern "C" int ts_index_reserve(ts_index* h, int64_t nrows) {
   if (!h || nrows < 0) { ts_set_error("bad arguments"); return TS_ERR_INVALID; }
   if (nrows >= (1LL << 31)) { ts_set_error("at most 2^31-1 rows per index"); return TS_ERR_UNSUPPORTED; }
   DeviceGuard g(h->device);
+  TS_CHECK(co_flush(h, nullptr));   // (grow_corpus frees the old corpus after a sync of the null stream)
   return grow_corpus(h, (nrows + TS_ROWS_PER_BLOCK - 1) / TS_ROWS_PER_BLOCK, true, nullptr);
 }
 
@@ -328,6 +358,7 @@ extern "C" int32_t ts_index_dtype(const ts_index* h) { return h ? h->L.dtype : -
 
 extern "C" int ts_index_set_id_offset(ts_index* h, int64_t offset) {
   if (!h) { ts_set_error("null handle"); return TS_ERR_INVALID; }
+  { DeviceGuard g(h->device); TS_CHECK(co_flush(h, nullptr)); }   // a held batch's ids carry the offset of its submission
   h->id_offset = offset;
   return TS_OK;
 }
@@ -350,6 +381,7 @@ extern "C" int ts_index_add(ts_index* h, const void* rows, int64_t n, int32_t ro
   if (h->ntotal + n >= (1LL << 31)) { ts_set_error("at most 2^31-1 rows per index"); return TS_ERR_UNSUPPORTED; }
   DeviceGuard g(h->device);
   hipStream_t s = (hipStream_t)stream;
+  TS_CHECK(co_flush(h, s));   // held passes search the corpus they were submitted against
   const int64_t need_blocks = (h->ntotal + n + TS_ROWS_PER_BLOCK - 1) / TS_ROWS_PER_BLOCK;
   TS_CHECK(grow_corpus(h, need_blocks, false, s));
   const bool norm = (flags & TS_FLAG_NORMALIZE) != 0;
@@ -388,6 +420,7 @@ extern "C" int ts_index_reconstruct(ts_index* h, int64_t row0, int64_t n, float*
   if (n == 0) return TS_OK;
   DeviceGuard g(h->device);
   hipStream_t s = (hipStream_t)stream;
+  TS_CHECK(co_flush(h, s));
   if (flags & TS_FLAG_HOST_PTR) {
     const size_t row_bytes = (size_t)h->L.dim * 4;
     int64_t chunk = std::max<int64_t>(1, (int64_t)((64u << 20) / row_bytes));
@@ -958,6 +991,218 @@ static int search_pass_on(ts_index* h, ts_index::WSet& W, const void* dq, int nq
   return TS_OK;
 }
 
+// ---- coalesced passes (TS_FLAG_COALESCE)
+extern "C" int32_t ts_coalesce_groups(int32_t dim, int32_t storage_dtype) {
+  if (dim <= 0 || (storage_dtype != TS_F16 && storage_dtype != TS_BF16)) return 0;
+  return ts_scan_multi_groups(ts_make_layout(dim, storage_dtype));
+}
+
+// Whether an unfiltered pass of a search with these flags joins the pending-pass queue: asynchronous, not
+// pipelined, on the five-launch filter path (the one-launch kernel has no multi-group form), and at least three
+// groups per pass (at two, one pass per 64-query batch is what the plain scan already does).
+static bool co_eligible(const ts_index* h, int k, uint32_t flags) {
+  const int64_t N = h->ntotal;
+  const int64_t nblk = (N + TS_ROWS_PER_BLOCK - 1) / TS_ROWS_PER_BLOCK;
+  const uint32_t need = TS_FLAG_ASYNC | TS_FLAG_COALESCE;
+  if ((flags & need) != need || (flags & (TS_FLAG_PIPELINE | TS_FLAG_NO_FILTER | TS_FLAG_HOST_PTR | TS_FLAG_ONE_LAUNCH)))
+    return false;
+  if (h->co_gmax < 3 || k > kMaxFilterK || N < kMinFilterRows || N < 32 * (int64_t)k) return false;
+  if (!(flags & TS_FLAG_CLASSIC) && N <= kOneLaunchMaxRows) return false;   // the one-launch search's regime
+  return ts_scan_multi_fits(nblk, h->num_cus - h->num_cus / 8);
+}
+
+// One filter scan over the pending groups; then the select of every batch whose last group was in it.
+// Caller holds co_mu.
+static int co_launch_pass(ts_index* h) {
+  if (h->co_ngroup == 0) return TS_OK;
+  const int G = h->co_ngroup;
+  const int64_t N = h->ntotal;
+  const int64_t nblk = (N + TS_ROWS_PER_BLOCK - 1) / TS_ROWS_PER_BLOCK;
+  hipStream_t s = h->co_stream;
+  MultiScanParams mp{};
+  mp.corpus = h->corpus;
+  mp.kg = h->L.kg;
+  mp.nwork = nblk;
+  mp.blk0 = 0;
+  mp.blk_stride = 1;
+  mp.ntotal = N;
+  mp.cand_cap = kCandCap;
+  mp.stage_cap = ts_scan_multi_stage_cap(h->L, G);
+  for (int g = 0; g < G; ++g) {
+    const ts_index::CoBatch& b = h->co_batch[h->co_group[g].batch];
+    const int half = h->co_group[g].half;
+    mp.gimg[g] = (const uint4*)b.W->qimg.p;
+    mp.gqh[g] = b.qh;
+    mp.ghalf[g] = half;
+    mp.gtau[g] = b.W->tau() + 32 * half;
+    mp.gcnt[g] = b.W->cand_cnt() + 32 * half;
+    mp.gscore[g] = (float*)b.W->cand_score.p + (size_t)32 * half * kCandCap;
+    mp.gid[g] = (int32_t*)b.W->cand_id.p + (size_t)32 * half * kCandCap;
+  }
+  // per-launch timing of the scan (ts_index_get_timings "filter_scan"), handed to a batch that ends in this pass
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (h->profiling && h->co_pass_seq++ % (uint64_t)h->prof_every == 0) {
+    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess || hipEventRecord(e0, s) != hipSuccess) {
+      if (e0) (void)hipEventDestroy(e0);
+      if (e1) (void)hipEventDestroy(e1);
+      e0 = e1 = nullptr;
+    }
+  }
+  int st = ts_launch_scan_multi(h->L, G, mp, h->num_cus - h->num_cus / 8, s);
+  if (e0 && (st != TS_OK || hipEventRecord(e1, s) != hipSuccess)) {
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    e0 = e1 = nullptr;
+  }
+  for (int g = 0; g < G; ++g) --h->co_batch[h->co_group[g].batch].groups_left;
+  h->co_ngroup = 0;
+  // the selects of the finished batches, in submission order; unfinished ones move to the front
+  int keep = 0;
+  const int nb = h->co_nbatch;
+  for (int i = 0; i < nb; ++i) {
+    ts_index::CoBatch b = h->co_batch[i];
+    if (b.groups_left > 0) { h->co_batch[keep++] = b; continue; }
+    if (st == TS_OK) {
+      SelParams p{};
+      p.mode = SEL_PAIRS32;
+      p.scores = (const float*)b.W->cand_score.p;
+      p.ids32 = (const int32_t*)b.W->cand_id.p;
+      p.stride = kCandCap;
+      p.n_per_q = b.W->cand_cnt();
+      p.n_cap = kCandCap;
+      p.need = (uint32_t)std::min<int64_t>(b.k, N);
+      p.k = b.k;
+      p.out_scores = b.out_s;
+      p.out_ids64 = b.out_i;
+      p.out_stride = b.k;
+      p.id_offset = h->id_offset;
+      p.status = b.W->status();
+      p.clear_counts = b.W->cand_cnt();
+      p.host_report = h->host_status_dev + (size_t)b.slot * TS_SLOT_WORDS;
+      st = ts_launch_select(p, b.nq, s);
+      if (st == TS_OK) {
+        if (hipEventRecord(b.W->ev_sel, s) == hipSuccess) b.W->used = true;   // (the set's next user waits for it)
+        else { ts_set_error("hipEventRecord failed"); st = TS_ERR_HIP; }
+      }
+    }
+    if (st != TS_OK) {
+      // nothing verifies a batch whose select is missing: finish() must report it for a redo
+      h->host_status[(size_t)b.slot * TS_SLOT_WORDS + 64] = TS_STATUS_OVERFLOW;
+    }
+    if (e0) {
+      std::lock_guard<std::mutex> lk(h->mu);
+      for (int j = 0; j < h->npending; ++j)
+        if (h->pending[j].slot == b.slot) { h->pending[j].e0 = e0; h->pending[j].e1 = e1; e0 = e1 = nullptr; break; }
+    }
+    release_set(h, b.W);
+  }
+  if (e0) { (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); }
+  h->co_nbatch = keep;
+  // the end of this pass and its selects, for work that later arrives on another stream (co_flush_locked)
+  if (hipEventRecord(h->co_ev, s) != hipSuccess) {
+    (void)hipStreamSynchronize(s);   // no event: nothing of this pass may be left running behind a later wait
+    h->co_ev_live = false;
+    if (st == TS_OK) { ts_set_error("hipEventRecord failed"); st = TS_ERR_HIP; }
+  } else {
+    h->co_ev_live = true;
+  }
+  return st;
+}
+
+// Enqueue every held batch: the pending groups make a (partial) pass, which holds the last group of every held
+// batch (co_submit queues all groups of a batch before it returns).  Then `s` is ordered behind every pass and
+// select enqueued so far on the queue's stream, so that work the caller puts on `s` next — a search, an add, the
+// sync of ts_index_finish — sees them, as it saw an unheld search that was enqueued before it.  Caller holds co_mu.
+static int co_flush_locked(ts_index* h, hipStream_t s) {
+  const int st = co_launch_pass(h);
+  if (h->co_ev_live && s != h->co_stream) {
+    // (asked first: a wait on another stream's event, even a satisfied one, costs the waiting stream 10-20 us)
+    if (hipEventQuery(h->co_ev) == hipSuccess) h->co_ev_live = false;
+    else TS_HIP(hipStreamWaitEvent(s, h->co_ev, 0));
+  }
+  return st;
+}
+
+static int co_flush(ts_index* h, hipStream_t s) {
+  std::lock_guard<std::mutex> lk(h->co_mu);
+  return co_flush_locked(h, s);
+}
+
+// One coalesced batch of <= 64 queries: query prep, sample scan and thresholds on the caller's stream now (they
+// read the caller's queries), its groups into the pending-pass queue.  Caller holds co_mu; the stream is the queue's.
+static int co_submit(ts_index* h, const void* dq, int nq, int q_dtype, int k, float* out_s, int64_t* out_i,
+                     hipStream_t s) {
+  const int64_t N = h->ntotal;
+  const int64_t nblk = (N + TS_ROWS_PER_BLOCK - 1) / TS_ROWS_PER_BLOCK;
+  const int qh = nq > 32 ? 2 : 1;
+  ts_index::WSet* W = acquire_set(h);   // (at most co_gmax - 1 < TS_NSETS sets are held by the queue here)
+  struct SetGuard {
+    ts_index* h; ts_index::WSet* W;
+    ~SetGuard() { if (W) release_set(h, W); }
+  } set_guard{h, W};
+  SlotGuard slot_guard(h, alloc_slot(h));
+  if (slot_guard.slot < 0) { ts_set_error("no free report slot"); return TS_ERR_INVALID; }
+  if (W->used && hipEventQuery(W->ev_sel) != hipSuccess) TS_HIP(hipStreamWaitEvent(s, W->ev_sel, 0));
+  TS_CHECK(ts_launch_qprep(h->L, dq, q_dtype, nq, qh, (uint4*)W->qimg.p, W->cand_cnt(), W->status(), s));
+  TS_CHECK(ensure(W->cand_score, (size_t)TS_MAX_Q * kCandCap * 4));
+  TS_CHECK(ensure(W->cand_id, (size_t)TS_MAX_Q * kCandCap * 4));
+  // the five-launch geometry of search_pass_on, with a lower survivor target: three groups share the staging area
+  // that two have in scan_kernel (ts_scan.hip, scan_multi_kernel)
+  int64_t nsb = std::max(kMinSampleRows, N / kSampleDiv) / TS_ROWS_PER_BLOCK;
+  const int64_t round = (int64_t)h->num_cus * 8;
+  if (nsb > round) nsb -= nsb % round;
+  nsb = std::min(nsb, nblk);
+  const int64_t sstride = nblk / nsb;
+  const int64_t S = nsb * TS_ROWS_PER_BLOCK;
+  const int64_t oversample = kCoalesceOversample;
+  uint32_t m = (uint32_t)((oversample * (int64_t)k * S + N - 1) / N);
+  m = std::max(m, kMinSampleRank);
+  TS_CHECK(ensure(W->sample, (size_t)nq * S * 4));
+  ScanParams sp{};
+  sp.corpus = h->corpus;
+  sp.qimg = (const uint4*)W->qimg.p;
+  sp.kg = h->L.kg;
+  sp.nq = nq;
+  sp.ntotal = N;
+  sp.nwork = nsb;
+  sp.blk0 = 0;
+  sp.blk_stride = sstride;
+  sp.dense = (float*)W->sample.p;
+  sp.dense_ld = S;
+  TS_CHECK(ts_launch_scan(h->L, SCAN_DENSE, qh, sp, h->num_cus, s));
+  TS_CHECK(ts_launch_tau((const float*)W->sample.p, S, (uint32_t)S, m, nq, W->tau(), s));
+  uint32_t* rep = h->host_status + (size_t)slot_guard.slot * TS_SLOT_WORDS;
+  for (int i = 0; i < 65; ++i) rep[i] = 0;
+  {
+    std::lock_guard<std::mutex> lk(h->mu);
+    ts_index::Pending& pe = h->pending[h->npending];
+    pe.ticket = h->next_ticket; pe.slot = slot_guard.slot; pe.nq = nq; pe.S = (uint32_t)S; pe.m = m;
+    pe.e0 = pe.e1 = nullptr;
+    pe.set = -1;
+    pe.fseq = -1;
+    ++h->npending;
+  }
+  h->co_batch[h->co_nbatch++] = ts_index::CoBatch{W, nq, qh, k, slot_guard.slot, qh, out_s, out_i};
+  slot_guard.handed_over();
+  set_guard.W = nullptr;   // released by co_launch_pass once its select is enqueued
+  int st = TS_OK;
+  for (int half = 0; half < qh; ++half) {
+    h->co_group[h->co_ngroup++] = ts_index::CoGroup{h->co_nbatch - 1, half};
+    if (h->co_ngroup == h->co_gmax) {
+      const int s1 = co_launch_pass(h);
+      if (st == TS_OK) st = s1;
+    }
+  }
+  return st;
+}
+
+extern "C" int ts_index_flush(ts_index* h, void* stream) {
+  if (!h) { ts_set_error("null handle"); return TS_ERR_INVALID; }
+  DeviceGuard g(h->device);
+  std::lock_guard<std::mutex> lk(h->co_mu);
+  return co_flush_locked(h, (hipStream_t)stream);   // later work on `stream` is ordered behind the flushed passes
+}
+
 extern "C" int ts_index_search(ts_index* h, const void* queries, int32_t nq, int32_t q_dtype,
                                int32_t k, float* out_scores, int64_t* out_ids, uint32_t flags,
                                void* stream) {
@@ -982,13 +1227,33 @@ extern "C" int ts_index_search(ts_index* h, const void* queries, int32_t nq, int
     if (flags & TS_FLAG_HOST_PTR) { ts_set_error("TS_FLAG_ASYNC needs device pointers"); return TS_ERR_INVALID; }
     const int passes = (nq + qp - 1) / qp;
     if (passes > 4) { ts_set_error("TS_FLAG_ASYNC: at most %d queries per call", 4 * qp); return TS_ERR_INVALID; }
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (h->npending + passes > TS_ASYNC_SLOTS / 4) {
+    bool full = false;
+    {
+      std::lock_guard<std::mutex> lk(h->mu);
+      full = h->npending + passes > TS_ASYNC_SLOTS / 4;
+    }
+    if (full) {
+      (void)co_flush(h, s);   // the unfinished-pass limit: nothing stays held behind the error
       ts_set_error("too many unfinished asynchronous searches; call ts_index_finish()");
       return TS_ERR_INVALID;
     }
   }
   const size_t qrow = (size_t)h->L.dim * dtype_size(q_dtype);
+  if (co_eligible(h, k, flags)) {
+    std::lock_guard<std::mutex> lk(h->co_mu);
+    // the queue holds one stream's batches: moving it to `s` flushes it and orders `s` behind the old stream's passes
+    if (h->co_stream != s) TS_CHECK(co_flush_locked(h, s));
+    h->co_stream = s;
+    for (int q0 = 0; q0 < nq; q0 += qp) {
+      const int c = std::min(qp, nq - q0);
+      TS_CHECK(co_submit(h, (const char*)queries + (size_t)q0 * qrow, c, q_dtype, k, out_scores + (size_t)q0 * k,
+                         out_ids + (size_t)q0 * k, s));
+    }
+    std::lock_guard<std::mutex> lk2(h->mu);
+    ++h->next_ticket;
+    return TS_OK;
+  }
+  TS_CHECK(co_flush(h, s));   // a search that cannot join the queue runs after the held ones
   const void* dq = queries;
   float* ds = out_scores;
   int64_t* di = out_ids;
@@ -1072,6 +1337,7 @@ extern "C" int ts_index_search_filtered(ts_index* h, const void* queries, int32_
   if (!any) return ts_index_search(h, queries, nq, q_dtype, k, out_scores, out_ids, flags, stream);
   DeviceGuard g(h->device);
   hipStream_t s = (hipStream_t)stream;
+  TS_CHECK(co_flush(h, s));   // a filtered search never joins a coalesced pass
   const int qp = (ts_scan_lds_bytes(h->L, 2) <= 160 * 1024) ? 64 : 32;  // queries per pass
   if (flags & TS_FLAG_ASYNC) {
     const int passes = (nq + qp - 1) / qp;
@@ -1157,6 +1423,7 @@ extern "C" int ts_index_scores(ts_index* h, const void* queries, int32_t nq, int
   if (N == 0) { ts_set_error("No documents indexed. Call add_documents() first."); return TS_ERR_EMPTY; }
   DeviceGuard g(h->device);
   hipStream_t s = (hipStream_t)stream;
+  TS_CHECK(co_flush(h, s));
   const int qp = (ts_scan_lds_bytes(h->L, 2) <= 160 * 1024) ? 64 : 32;
   const size_t qrow = (size_t)h->L.dim * dtype_size(q_dtype);
   for (int q0 = 0; q0 < nq; q0 += qp) {
@@ -1216,6 +1483,10 @@ extern "C" int ts_index_finish(ts_index* h, void* stream, int64_t* failed_ticket
     return TS_ERR_INVALID;
   }
   DeviceGuard g(h->device);
+  {
+    std::lock_guard<std::mutex> clk(h->co_mu);
+    TS_CHECK(co_flush_locked(h, (hipStream_t)stream));   // the sync below then covers every held pass
+  }
   TS_HIP(hipStreamSynchronize((hipStream_t)stream));
   std::lock_guard<std::mutex> lk(h->mu);
   int nf = 0;

@@ -276,6 +276,269 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_masked_kernel(MaskedScanPar
   flush_stage(p, st, tid);
 }
 
+// Multi-group filter mode (coalesced passes, TS_FLAG_COALESCE): scan_kernel's SCAN_FILTER loop for G 32-query
+// groups that may belong to different batches (MultiScanParams, ts_common.h).  The prologue gathers each group's
+// columns from its batch's Q image into one G-group image laid out like scan_kernel's (unit (kg*G + g)*64 + lane);
+// the hot loop is scan_kernel's ring with G reads and G MFMAs per k group.  Every group's pointers are indexed by
+// a compile-time group number where it matters (the epilogue), so they stay scalar.
+//
+// Staging: with 3 groups at d = 768 the image leaves 16 KiB of LDS, so a survivor takes 8 bytes instead of
+// StageLds's 9: its score and one key word, (iteration << 15) | (wave << 12) | (row in block << 7) | query of
+// the pass.  The row id is rebuilt in the flush from the workgroup's fixed walk: work item
+// w = blockIdx.x * SCAN_WAVES + wave + iteration * (waves in the grid).  ts_scan_multi_fits() keeps the
+// iteration count below 2^17.
+struct StageMultiHdr {
+  uint32_t cnt;
+  uint32_t pad[3];
+  uint32_t qcnt[TS_MAX_GROUPS * 32];
+  uint32_t qbase[TS_MAX_GROUPS * 32];
+  uint32_t qoff[TS_MAX_GROUPS * 32];
+  // followed by float score[stage_cap], uint32_t key[stage_cap]
+};
+static_assert(SCAN_WAVES <= 8 && TS_MAX_GROUPS * 32 <= 128, "survivor key fields");
+#define TS_MULTI_MAX_ITERS (1 << 17)
+#define TS_MULTI_MIN_STAGE 1024u     // entries: below this a group count is not offered (ts_scan_multi_groups)
+#define TS_MULTI_MAX_STAGE 4096u     // entries: more LDS than this buys nothing (about 1.3 k survivors per pass)
+
+// a[g] for a run-time g < G, without a dynamically indexed kernel argument (that would go through scratch)
+template <int G, class T>
+__device__ __forceinline__ T pick_group(const T (&a)[TS_MAX_GROUPS], int g) {
+  T r = a[0];
+#pragma unroll
+  for (int i = 1; i < G; ++i) r = (g == i) ? a[i] : r;
+  return r;
+}
+
+template <int G>
+__device__ __forceinline__ void epilogue_multi(const MultiScanParams& p, StageMultiHdr* st, float* sscore,
+                                               uint32_t* skey, const f32x16 (&acc)[G], const float (&tau)[G],
+                                               int64_t blk, uint32_t keyhi, int lane) {
+  bool hit = false;
+#pragma unroll
+  for (int hq = 0; hq < G; ++hq) hit |= (acc_max(acc[hq]) >= tau[hq]);
+  if (__builtin_amdgcn_ballot_w64(hit) == 0ull) return;  // the common case
+  const int64_t row_base = blk * TS_ROWS_PER_BLOCK;
+  const int j = lane & 31;
+#pragma unroll
+  for (int hq = 0; hq < G; ++hq) {
+    uint32_t mask = 0;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const bool ok = (acc[hq][r] >= tau[hq]) && (row_base + acc_row(r, lane) < p.ntotal);
+      mask |= ok ? (1u << r) : 0u;
+    }
+    if (mask) {
+      uint32_t slot = atomicAdd(&st->cnt, (uint32_t)__builtin_popcount(mask));  // LDS
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        if (mask & (1u << r)) {
+          if (slot < p.stage_cap) {
+            sscore[slot] = acc[hq][r];
+            skey[slot] = keyhi | ((uint32_t)acc_row(r, lane) << 7) | (uint32_t)(hq * 32 + j);
+          } else {
+            // staging area full: append directly
+            const uint32_t g = atomicAdd(&p.gcnt[hq][j], 1u);
+            if (g < p.cand_cap) {
+              p.gscore[hq][(size_t)j * p.cand_cap + g] = acc[hq][r];
+              p.gid[hq][(size_t)j * p.cand_cap + g] = (int32_t)(row_base + acc_row(r, lane));
+            }
+          }
+          ++slot;
+        }
+      }
+    }
+  }
+}
+
+template <int DT, int G>
+__global__ __launch_bounds__(SCAN_THREADS) void scan_multi_kernel(MultiScanParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  u32x4* qlds = reinterpret_cast<u32x4*>(smem);
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int kg = p.kg;
+
+  const int64_t nwaves = (int64_t)gridDim.x * SCAN_WAVES;
+  int64_t w = (int64_t)blockIdx.x * SCAN_WAVES + wave;
+  const bool active = w < p.nwork;  // (waves without work still join the final flush)
+  const u32x4* base = reinterpret_cast<const u32x4*>(p.corpus) + lane;
+  const size_t blk_units = (size_t)kg * 64;
+  int64_t blk = active ? p.blk0 + w * p.blk_stride : p.blk0;
+  const u32x4* cur = base + (size_t)blk * blk_units;
+  u32x4 ring[TS_RING];
+  if (active) {
+#pragma unroll
+    for (int i = 0; i < TS_RING; ++i) ring[i] = stream_load(cur + (size_t)i * 64);
+  }
+
+  // ---- prologue: gather the groups' columns (global/L2) into one G-group image in LDS, once per workgroup
+  {
+    const int units = kg * G * 64;
+    for (int i0 = tid; i0 < units; i0 += 8 * SCAN_THREADS) {
+      u32x4 t[8];
+#pragma unroll
+      for (int jj = 0; jj < 8; ++jj) {
+        const int i = i0 + jj * SCAN_THREADS;
+        t[jj] = u32x4{0, 0, 0, 0};
+        if (i < units) {
+          const int u = i >> 6, gk = u / G, g = u - gk * G;
+          const u32x4* src = reinterpret_cast<const u32x4*>(pick_group<G>(p.gimg, g));
+          t[jj] = src[(size_t)(gk * pick_group<G>(p.gqh, g) + pick_group<G>(p.ghalf, g)) * 64 + (i & 63)];
+        }
+      }
+#pragma unroll
+      for (int jj = 0; jj < 8; ++jj) {
+        const int i = i0 + jj * SCAN_THREADS;
+        if (i < units) qlds[i] = t[jj];
+      }
+    }
+  }
+  StageMultiHdr* st = reinterpret_cast<StageMultiHdr*>(smem + (size_t)kg * G * 1024);
+  float* sscore = reinterpret_cast<float*>(st + 1);
+  uint32_t* skey = reinterpret_cast<uint32_t*>(sscore + p.stage_cap);
+  if (tid == 0) st->cnt = 0;
+  __syncthreads();
+
+  if (active) {
+
+  float tau[G];
+#pragma unroll
+  for (int hq = 0; hq < G; ++hq) tau[hq] = p.gtau[hq][lane & 31];
+
+  const u32x4* ql = qlds + lane;
+  uint32_t keyhi = (uint32_t)wave << 12;   // + (iteration << 15)
+
+  while (true) {
+    const int64_t wn = w + nwaves;
+    const bool has_next = wn < p.nwork;
+    const int64_t blkn = has_next ? (p.blk0 + wn * p.blk_stride) : blk;
+    const u32x4* nxt = base + (size_t)blkn * blk_units;
+
+    f32x16 acc[G];
+#pragma unroll
+    for (int hq = 0; hq < G; ++hq)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[hq][r] = 0.f;
+
+    // main part: prefetch stays inside the current row block
+    int g0 = 0;
+    for (; g0 < kg - TS_RING; g0 += TS_RING) {
+#pragma unroll
+      for (int i = 0; i < TS_RING; ++i) {
+#pragma unroll
+        for (int hq = 0; hq < G; ++hq) {
+          const u32x4 b = ql[(size_t)((g0 + i) * G + hq) * 64];
+          mma_group<DT>(acc[hq], ring[i], b);
+        }
+        ring[i] = stream_load(cur + (size_t)(g0 + i + TS_RING) * 64);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+    // tail: the ring is refilled from the start of the wave's next row block
+#pragma unroll
+    for (int i = 0; i < TS_RING; ++i) {
+#pragma unroll
+      for (int hq = 0; hq < G; ++hq) {
+        const u32x4 b = ql[(size_t)((g0 + i) * G + hq) * 64];
+        mma_group<DT>(acc[hq], ring[i], b);
+      }
+      ring[i] = stream_load(nxt + (size_t)i * 64);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+
+    epilogue_multi<G>(p, st, sscore, skey, acc, tau, blk, keyhi, lane);
+
+    if (!has_next) break;
+    w = wn;
+    blk = blkn;
+    cur = nxt;
+    keyhi += 1u << 15;
+  }
+  }  // active
+
+  // ---- flush: one global atomic per (workgroup, query) reserves the slots
+  __syncthreads();
+  const uint32_t n = st->cnt < p.stage_cap ? st->cnt : p.stage_cap;
+  if (n == 0) return;  // uniform: cnt is final after the barrier
+  if (tid < G * 32) { st->qcnt[tid] = 0; st->qoff[tid] = 0; }
+  __syncthreads();
+  for (uint32_t e = tid; e < n; e += SCAN_THREADS) atomicAdd(&st->qcnt[skey[e] & 127u], 1u);
+  __syncthreads();
+  if (tid < G * 32 && st->qcnt[tid] > 0)
+    st->qbase[tid] = atomicAdd(pick_group<G>(p.gcnt, tid >> 5) + (tid & 31), st->qcnt[tid]);
+  __syncthreads();
+  for (uint32_t e = tid; e < n; e += SCAN_THREADS) {
+    const uint32_t key = skey[e];
+    const uint32_t q = key & 127u;
+    const uint32_t slot = st->qbase[q] + atomicAdd(&st->qoff[q], 1u);
+    if (slot < p.cand_cap) {
+      const int g = (int)(q >> 5);
+      const size_t at = (size_t)(q & 31u) * p.cand_cap + slot;
+      const int64_t wi = (int64_t)blockIdx.x * SCAN_WAVES + ((key >> 12) & 7u) + (int64_t)(key >> 15) * nwaves;
+      pick_group<G>(p.gscore, g)[at] = sscore[e];
+      pick_group<G>(p.gid, g)[at] = (int32_t)((p.blk0 + wi * p.blk_stride) * TS_ROWS_PER_BLOCK + ((key >> 7) & 31u));
+    }
+  }
+}
+
+int ts_scan_multi_groups(const TsLayout& L) {
+  if (L.dtype != TS_F16 && L.dtype != TS_BF16) return 0;
+  for (int G = TS_MAX_GROUPS; G >= 1; --G)
+    if (ts_scan_multi_stage_cap(L, G) > 0) return G;
+  return 0;
+}
+
+uint32_t ts_scan_multi_stage_cap(const TsLayout& L, int G) {
+  const size_t fixed = (size_t)L.kg * G * 1024 + sizeof(StageMultiHdr);
+  if (G < 1 || G > TS_MAX_GROUPS || fixed + 8 * (size_t)TS_MULTI_MIN_STAGE > 160 * 1024) return 0;
+  return (uint32_t)std::min<size_t>(TS_MULTI_MAX_STAGE, (160 * 1024 - fixed) / 8);
+}
+
+// the grid of ts_launch_scan_multi: at most num_cus workgroups of SCAN_WAVES waves
+bool ts_scan_multi_fits(int64_t nblk, int num_cus) {
+  const int64_t want = (nblk + SCAN_WAVES - 1) / SCAN_WAVES;
+  const int64_t grid = std::max<int64_t>(1, std::min<int64_t>(want, num_cus));
+  const int64_t nwaves = grid * SCAN_WAVES;
+  return (nblk + nwaves - 1) / nwaves <= TS_MULTI_MAX_ITERS;
+}
+
+template <int DT, int G>
+static int launch_scan_multi_t(const TsLayout& L, const MultiScanParams& p, int num_cus, hipStream_t stream) {
+  const size_t lds = (size_t)L.kg * G * 1024 + sizeof(StageMultiHdr) + 8 * (size_t)p.stage_cap;
+  auto kern = scan_multi_kernel<DT, G>;
+  static TsDeviceOnce lds_attr;
+  TS_CHECK(ts_allow_max_lds(lds_attr, reinterpret_cast<const void*>(kern)));
+  const int64_t want = (p.nwork + SCAN_WAVES - 1) / SCAN_WAVES;
+  int grid = (int)(want < num_cus ? want : num_cus);
+  if (grid < 1) grid = 1;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(SCAN_THREADS), lds, stream, p);
+  TS_HIP(hipGetLastError());
+  return TS_OK;
+}
+
+int ts_launch_scan_multi(const TsLayout& L, int G, const MultiScanParams& p, int num_cus, hipStream_t stream) {
+  if (p.nwork <= 0) return TS_OK;
+  if (p.stage_cap == 0 || p.stage_cap > ts_scan_multi_stage_cap(L, G) || !ts_scan_multi_fits(p.nwork, num_cus)) {
+    ts_set_error("multi-group scan: %d groups do not fit at dimension %d", G, L.dim);
+    return TS_ERR_UNSUPPORTED;
+  }
+#define TS_MULTI_G(DT)                                                      \
+  switch (G) {                                                              \
+    case 1: return launch_scan_multi_t<DT, 1>(L, p, num_cus, stream);       \
+    case 2: return launch_scan_multi_t<DT, 2>(L, p, num_cus, stream);       \
+    case 3: return launch_scan_multi_t<DT, 3>(L, p, num_cus, stream);       \
+    case 4: return launch_scan_multi_t<DT, 4>(L, p, num_cus, stream);       \
+  }
+  switch (L.dtype) {
+    case TS_F16: TS_MULTI_G(TS_F16); break;
+    case TS_BF16: TS_MULTI_G(TS_BF16); break;
+  }
+#undef TS_MULTI_G
+  ts_set_error("multi-group scan: bad dtype %d or group count %d", L.dtype, G);
+  return TS_ERR_UNSUPPORTED;
+}
+
 bool ts_use_f32_split(const TsLayout& L, int qh) {
   if (L.dtype != TS_F32 || qh != 1) return false;
 #ifdef TS_TUNING   // A/B: TS_NO_F32_SPLIT=1 keeps the exact-f32 MFMA kernel

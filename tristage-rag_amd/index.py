@@ -104,6 +104,9 @@ class FlatIPIndex:
         self.auto_finish = True  # False: the owner (ShardedFlatIPIndex) calls finish() itself, collectively
         self.classic_filter = False  # True: every search takes the five-launch filter path (A/B measurements)
         self.one_launch_filter = False  # True: the one-launch scan wherever it is valid (also pipelined / large corpora)
+        # async_ searches may share one corpus pass with the batches that follow them (TS_FLAG_COALESCE); results are
+        # identical.  False: one pass per batch, as before (A/B runs, owners that read results in stream order)
+        self.coalesce = True
         self._filter_info = None  # set by finish() when it redid a filtered search: the counters of what was submitted
 
     # -- lifetime ---------------------------------------------------------
@@ -171,6 +174,8 @@ class FlatIPIndex:
         verified after :meth:`finish`.  Batches issued this way run back to back on
         the GPU without a host round trip between them.
         ``out=(D, I)``: CUDA tensors [B,k] float32 / int64 to write into.
+        With ``coalesce`` (the default) the scan of an ``async_`` batch may wait for the next ones, so that one
+        corpus pass serves up to four 32-query groups; :meth:`finish` (or :meth:`flush`) enqueues what is held.
         ``inputs_ready=True`` (with ``async_``): the caller guarantees ``q`` is already
         complete in memory (not the result of work still pending on the stream); the
         library then pipelines this search's small kernels beside its neighbours' scans
@@ -215,6 +220,8 @@ class FlatIPIndex:
             flags |= _lib.TS_FLAG_ASYNC
             if inputs_ready:
                 flags |= _lib.TS_FLAG_PIPELINE
+            elif self.coalesce:
+                flags |= _lib.TS_FLAG_COALESCE
         if _is_tensor(q) and q.is_cuda:
             torch = _torch()
             if q.dim() != 2 or q.shape[1] != self.d:
@@ -489,6 +496,12 @@ class FlatIPIndex:
     def pending_room(self, n_queries: int) -> int:
         """>= 0 while another asynchronous search of `n_queries` queries fits before a finish()."""
         return self.PENDING_PASSES - self._pending_passes - (int(n_queries) + 31) // 32
+
+    def flush(self) -> None:
+        """Enqueue the scans that coalesced ``async_`` searches are holding, without a host sync: their results
+        are then ordered on the current stream (still verified only by :meth:`finish`)."""
+        _lib.check(self._lib.ts_index_flush(self._h, ctypes.c_void_p(_stream_ptr(self.device)) if
+                                            _stream_ptr(self.device) else None))
 
     def finish(self):
         """Complete every asynchronous search: one stream sync, then the (rare)

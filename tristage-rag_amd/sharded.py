@@ -63,6 +63,10 @@ class ShardedFlatIPIndex:
             # this wrapper owns the finish() cadence: a finish that repairs a batch must be followed
             # by a repeat of that batch's exchange on EVERY rank, so it has to be the collective one
             self.local_index.auto_finish = False
+        if hasattr(self.local_index, "coalesce"):
+            # the local result is all-gathered in stream order before finish(): a held scan would feed the exchange
+            # buffers that are not written yet (TS_FLAG_COALESCE is never set here)
+            self.local_index.coalesce = False
         self.merge_packed_fn = None
         if merge_fn is None:
             from .index import merge_topk, merge_topk_packed
