@@ -48,7 +48,8 @@ extern "C" {
  * ts_linear_add_layernorm, ts_mlp_add_layernorm.  4 = filtered search: ts_index_search_filtered,
  * ts_index_last_filter_info and ts_bm25_search_batch_filtered (no existing signature changed).  Coalesced passes
  * (TS_FLAG_COALESCE, ts_index_flush, ts_coalesce_groups) were added within version 4: no signature changed, and a
- * caller that never sets the flag sees the library it was built against.                                     */
+ * caller that never sets the flag sees the library it was built against.  The IVF-Flat entry points (ts_ivf_*) were
+ * added within version 4 as well: no existing signature changed.                                             */
 #define TS_ABI_VERSION 4
 
 typedef struct ts_index ts_index; /* opaque */
@@ -451,6 +452,44 @@ int ts_mlp_add_layernorm(const void* w1_tiled, const void* b1, const void* w2_ti
 /* Frees the internal MaxSim scratch buffers kept per (device, stream) (all devices
  * if device < 0).  No MaxSim launch may be pending on that device.               */
 int ts_maxsim_release_scratch(int32_t device);
+
+/* ---- IVF-Flat -----------------------------------------------------------------
+ * replaces faiss.IndexIVFFlat(quantizer, d, nlist, METRIC_INNER_PRODUCT) with nprobe (reference
+ * src/stage1_retriever.py:256-283).  Inner product only; f16 / bf16 storage in 32-row blocks that each hold rows of
+ * one inverted list; an fp32 flat index of the centroids is the coarse quantizer.  Every pointer except
+ * ts_ivf_list_sizes's and ts_ivf_train's `objective` (host) is device memory on the handle's device.  A handle serves
+ * one caller at a time.  Added within ABI version 4: no existing signature changed.
+ *   train     spherical k-means on <= 256 * nlist points sampled with `seed` (initial centroids: the first nlist of
+ *             them), `iters` iterations, centroids L2-normalised after each update, an empty cluster re-seeded by
+ *             splitting the largest; deterministic (no float atomics).  n < nlist: TS_ERR_INVALID.  objective
+ *             (NULL or host double[iters]) receives the sum of each point's best centroid score per iteration.
+ *   add       each row (after the flat index's rounding and optional normalisation) goes to the list of its highest
+ *             fp32 centroid score, ties to the lower list; ids are insertion order plus the id offset.  Before
+ *             train / set_centroids: TS_ERR_INVALID.
+ *   probe     the nprobe lists of highest fp32 centroid score, descending, ties to the lower list id.
+ *   search    the exact top-k over the rows of the query's probed lists (scores bit-identical to ts_index_search on
+ *             the same rows, ties by ascending id), -1 / -FLT_MAX padded; synchronous with respect to `stream`.
+ *   reconstruct  rows [id0, id0 + n) in id order as float32.
+ *   last_search_info  {passes, passes on the filter path, of them redone densely, live blocks of the last pass}. */
+typedef struct ts_ivf ts_ivf; /* opaque */
+int ts_ivf_create(int32_t dim, int32_t nlist, int32_t storage_dtype, int32_t device, ts_ivf** out);
+int ts_ivf_destroy(ts_ivf* h);
+int ts_ivf_reset(ts_ivf* h);   /* drop all rows, keep the centroids */
+int ts_ivf_train(ts_ivf* h, const void* x, int64_t n, int32_t x_dtype, int64_t seed, int32_t iters,
+                 double* objective, void* stream);
+int ts_ivf_set_centroids(ts_ivf* h, const float* centroids, void* stream);   /* [nlist, dim] fp32, empty index */
+int ts_ivf_get_centroids(ts_ivf* h, float* out, void* stream);
+int32_t ts_ivf_is_trained(const ts_ivf* h);
+int ts_ivf_add(ts_ivf* h, const void* rows, int64_t n, int32_t rows_dtype, uint32_t flags, void* stream);
+int ts_ivf_search(ts_ivf* h, const void* queries, int32_t nq, int32_t q_dtype, int32_t k, int32_t nprobe,
+                  float* out_scores, int64_t* out_ids, void* stream);
+int ts_ivf_probe(ts_ivf* h, const void* queries, int32_t nq, int32_t q_dtype, int32_t nprobe, float* out_scores,
+                 int64_t* out_lists, void* stream);
+int ts_ivf_list_sizes(const ts_ivf* h, int64_t* out);   /* host int64[nlist] */
+int ts_ivf_reconstruct(ts_ivf* h, int64_t id0, int64_t n, float* out, void* stream);
+int64_t ts_ivf_ntotal(const ts_ivf* h);
+int ts_ivf_set_id_offset(ts_ivf* h, int64_t offset);
+int ts_ivf_last_search_info(const ts_ivf* h, int64_t info[4]);
 
 /* ---- diagnostics (no GPU needed) -------------------------------------------
  * Exercises the per-device one-time table that guards hipFuncSetAttribute with

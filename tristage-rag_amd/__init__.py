@@ -13,6 +13,7 @@ __version__ = "0.1.0"
 
 _LAZY = {
     "FlatIPIndex": ("index", "FlatIPIndex"),
+    "IVFFlatIndex": ("index", "IVFFlatIndex"),
     "merge_topk": ("index", "merge_topk"),
     "maxsim": ("index", "maxsim"),
     "ShardedFlatIPIndex": ("sharded", "ShardedFlatIPIndex"),

@@ -62,6 +62,21 @@ SIGNATURES = {
     "ts_index_get_timings": (c_int32, [c_void_p, POINTER(ctypes.c_double), POINTER(c_int64), c_int32]),
     "ts_index_read_probe": (c_int32, [c_void_p, c_int32, POINTER(ctypes.c_double), POINTER(ctypes.c_double),
                                       POINTER(c_int64), c_void_p]),
+    "ts_ivf_create": (c_int32, [c_int32, c_int32, c_int32, c_int32, POINTER(c_void_p)]),
+    "ts_ivf_destroy": (c_int32, [c_void_p]),
+    "ts_ivf_reset": (c_int32, [c_void_p]),
+    "ts_ivf_train": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int64, c_int32, c_void_p, c_void_p]),
+    "ts_ivf_set_centroids": (c_int32, [c_void_p, c_void_p, c_void_p]),
+    "ts_ivf_get_centroids": (c_int32, [c_void_p, c_void_p, c_void_p]),
+    "ts_ivf_is_trained": (c_int32, [c_void_p]),
+    "ts_ivf_add": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_uint32, c_void_p]),
+    "ts_ivf_search": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "ts_ivf_probe": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "ts_ivf_list_sizes": (c_int32, [c_void_p, c_void_p]),
+    "ts_ivf_reconstruct": (c_int32, [c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+    "ts_ivf_ntotal": (c_int64, [c_void_p]),
+    "ts_ivf_set_id_offset": (c_int32, [c_void_p, c_int64]),
+    "ts_ivf_last_search_info": (c_int32, [c_void_p, POINTER(c_int64)]),
     "ts_merge_topk": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p,
                                 c_int32, c_void_p]),
     "ts_merge_topk_strided": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int64, c_int64,

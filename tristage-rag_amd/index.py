@@ -961,3 +961,195 @@ class TiledLinear:
                                                        1 if gelu_input else 0, ptr(out32), ptr(outlp), dev,
                                                        ctypes.c_void_p(_stream_ptr(dev))))
         return out32, outlp
+
+
+class IVFFlatIndex:
+    """Inverted-file index over f16 / bf16 rows resident in MI355X HBM: FAISS ``IndexIVFFlat`` with inner product
+    (reference src/stage1_retriever.py:256-283, ``nlist`` lists, ``nprobe`` probed per query).
+
+    ``train`` runs spherical k-means on the device; ``search`` returns the exact top-k over the rows of the query's
+    ``nprobe`` probed lists, with scores bit-identical to :class:`FlatIPIndex` on the same rows and ties by ascending id.
+    Inputs may be numpy arrays or torch tensors; host inputs are copied to the index's GPU first."""
+
+    MAX_KERNEL_K = 16384
+
+    def __init__(self, d: int, nlist: int, dtype: str = "f16", device: int = 0, nprobe: int = 10):
+        if dtype not in _NAME_TO_DTYPE or _NAME_TO_DTYPE[dtype] == _lib.TS_F32:
+            raise ValueError(f"IVF storage dtype must be f16 or bf16, got {dtype!r}")
+        self._lib = _lib.load()
+        self.d = int(d)
+        self.nlist = int(nlist)
+        self.nprobe = int(nprobe)
+        self.device = int(device)
+        self.storage_dtype = _DTYPE_NAME[_NAME_TO_DTYPE[dtype]]
+        self.seed = 1234
+        self.niter = 25
+        self.objective = []   # per k-means iteration: sum over the training points of their best centroid score
+        self._id_offset = 0
+        self._h = ctypes.c_void_p()
+        _lib.check(self._lib.ts_ivf_create(self.d, self.nlist, _NAME_TO_DTYPE[dtype], self.device,
+                                           ctypes.byref(self._h)))
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._lib.ts_ivf_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    # -- helpers -------------------------------------------------------------
+    def _dev(self, x, what: str):
+        """x -> a contiguous [n, d] tensor on the index's GPU (f32 / f16 / bf16)."""
+        torch = _torch()
+        if not _is_tensor(x):
+            a = np.ascontiguousarray(x)
+            if a.dtype not in _NP_DTYPES:
+                a = a.astype(np.float32)
+            x = torch.from_numpy(a)
+        if x.dim() != 2 or x.shape[1] != self.d:
+            raise ValueError(f"expected [n, {self.d}] {what}, got {tuple(x.shape)}")
+        if x.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            x = x.float()
+        if not x.is_cuda or x.device.index != self.device:
+            x = x.to(torch.device("cuda", self.device))
+        return x.contiguous()
+
+    def _stream(self) -> ctypes.c_void_p:
+        return ctypes.c_void_p(_stream_ptr(self.device))
+
+    # -- FAISS duck type -----------------------------------------------------
+    @property
+    def ntotal(self) -> int:
+        return int(self._lib.ts_ivf_ntotal(self._h))
+
+    @property
+    def is_trained(self) -> bool:
+        return int(self._lib.ts_ivf_is_trained(self._h)) == 1
+
+    def train(self, x, seed: Optional[int] = None, niter: Optional[int] = None) -> None:
+        x = self._dev(x, "training points")
+        if x.shape[0] < self.nlist:
+            raise ValueError(f"{x.shape[0]} training points for nlist={self.nlist}: need at least nlist")
+        it = self.niter if niter is None else int(niter)
+        obj = (ctypes.c_double * max(it, 1))()
+        _lib.check(self._lib.ts_ivf_train(self._h, ctypes.c_void_p(x.data_ptr()), x.shape[0], _tensor_dtype(x),
+                                          int(self.seed if seed is None else seed), it, obj, self._stream()))
+        self.objective = [float(obj[i]) for i in range(it)]
+
+    def add(self, x, normalize: bool = False) -> None:
+        if not self.is_trained:
+            raise RuntimeError("IVFFlatIndex.add before train(): the index has no centroids")
+        x = self._dev(x, "rows")
+        flags = _lib.TS_FLAG_NORMALIZE if normalize else 0
+        _lib.check(self._lib.ts_ivf_add(self._h, ctypes.c_void_p(x.data_ptr()), x.shape[0], _tensor_dtype(x),
+                                        flags, self._stream()))
+
+    def reset(self) -> None:
+        _lib.check(self._lib.ts_ivf_reset(self._h))
+
+    def set_id_offset(self, offset: int) -> None:
+        _lib.check(self._lib.ts_ivf_set_id_offset(self._h, int(offset)))
+        self._id_offset = int(offset)
+
+    @property
+    def centroids(self) -> np.ndarray:
+        """[nlist, d] float32 (host)."""
+        torch = _torch()
+        out = torch.empty((self.nlist, self.d), dtype=torch.float32, device=torch.device("cuda", self.device))
+        _lib.check(self._lib.ts_ivf_get_centroids(self._h, ctypes.c_void_p(out.data_ptr()), self._stream()))
+        return out.cpu().numpy()
+
+    def set_centroids(self, c) -> None:
+        """Load trained centroids [nlist, d] (no training); the index must be empty."""
+        torch = _torch()
+        c = self._dev(c, "centroids").float().contiguous()
+        if c.shape[0] != self.nlist:
+            raise ValueError(f"expected {self.nlist} centroids, got {c.shape[0]}")
+        _lib.check(self._lib.ts_ivf_set_centroids(self._h, ctypes.c_void_p(c.data_ptr()), self._stream()))
+        torch.cuda.current_stream(self.device).synchronize()
+
+    def list_sizes(self) -> np.ndarray:
+        out = np.zeros(self.nlist, dtype=np.int64)
+        _lib.check(self._lib.ts_ivf_list_sizes(self._h, out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def probe(self, q, nprobe: Optional[int] = None):
+        """``(scores float32 [B, nprobe], lists int64 [B, nprobe])``: the lists a search probes, best first."""
+        torch = _torch()
+        was_np = not (_is_tensor(q) and q.is_cuda)
+        q = self._dev(q, "queries")
+        p = min(self.nprobe if nprobe is None else int(nprobe), self.nlist)
+        if p <= 0:
+            raise ValueError("nprobe must be positive")
+        B = q.shape[0]
+        S = torch.empty((B, p), dtype=torch.float32, device=q.device)
+        L = torch.empty((B, p), dtype=torch.int64, device=q.device)
+        _lib.check(self._lib.ts_ivf_probe(self._h, ctypes.c_void_p(q.data_ptr()), B, _tensor_dtype(q), p,
+                                          ctypes.c_void_p(S.data_ptr()), ctypes.c_void_p(L.data_ptr()),
+                                          self._stream()))
+        return (S.cpu().numpy(), L.cpu().numpy()) if was_np else (S, L)
+
+    def search(self, q, k: int, async_: bool = False, out=None, allowed=None, nprobe: Optional[int] = None):
+        """Top-``k`` over the rows of each query's probed lists (FAISS convention, -1 / -FLT_MAX padded).  numpy in
+        -> numpy out, CUDA tensor in -> tensors out.  ``async_`` is accepted and completes synchronously (:meth:`finish`
+        then has nothing to report)."""
+        if allowed is not None:
+            raise NotImplementedError("filtered search (allowed=) is not supported by IVFFlatIndex")
+        k = int(k)
+        if k <= 0:
+            raise ValueError("k must be positive")
+        if k > self.MAX_KERNEL_K:
+            raise NotImplementedError(f"IVFFlatIndex.search: k={k} exceeds the select limit {self.MAX_KERNEL_K}")
+        if not self.is_trained:
+            raise RuntimeError("IVFFlatIndex.search before train()")
+        if self.ntotal == 0:
+            raise ValueError("No documents indexed. Call add_documents() first.")
+        torch = _torch()
+        was_np = not (_is_tensor(q) and q.is_cuda)
+        q = self._dev(q, "queries")
+        B = q.shape[0]
+        if out is not None:
+            D, I = out
+            if (D.shape != (B, k) or I.shape != (B, k) or D.dtype != torch.float32 or I.dtype != torch.int64
+                    or not D.is_contiguous() or not I.is_contiguous()):
+                raise ValueError("out must be contiguous (float32[B,k], int64[B,k]) CUDA tensors")
+        else:
+            D = torch.empty((B, k), dtype=torch.float32, device=q.device)
+            I = torch.empty((B, k), dtype=torch.int64, device=q.device)
+        p = self.nprobe if nprobe is None else int(nprobe)
+        if p <= 0:
+            raise ValueError("nprobe must be positive")
+        _lib.check(self._lib.ts_ivf_search(self._h, ctypes.c_void_p(q.data_ptr()), B, _tensor_dtype(q), k,
+                                           min(p, self.nlist), ctypes.c_void_p(D.data_ptr()),
+                                           ctypes.c_void_p(I.data_ptr()), self._stream()))
+        if was_np:
+            return D.cpu().numpy(), I.cpu().numpy()
+        return D, I
+
+    def finish(self):
+        """Asynchronous searches complete synchronously here: nothing is pending, no ticket failed."""
+        return []
+
+    def flush(self) -> None:
+        return None
+
+    def reconstruct_n(self, i0: int = 0, n: Optional[int] = None) -> np.ndarray:
+        """Rows [i0, i0+n) in id order as float32 (after storage rounding)."""
+        torch = _torch()
+        if n is None:
+            n = self.ntotal - i0
+        out = torch.empty((max(n, 0), self.d), dtype=torch.float32, device=torch.device("cuda", self.device))
+        if n:
+            _lib.check(self._lib.ts_ivf_reconstruct(self._h, int(i0), int(n), ctypes.c_void_p(out.data_ptr()),
+                                                    self._stream()))
+        return out.cpu().numpy()
+
+    def last_search_info(self) -> dict:
+        info = (ctypes.c_int64 * 4)()
+        _lib.check(self._lib.ts_ivf_last_search_info(self._h, info))
+        return {"passes": int(info[0]), "filter_passes": int(info[1]), "redone": int(info[2]),
+                "live_blocks": int(info[3])}

@@ -8,7 +8,9 @@ What differs underneath:
 * ``faiss_index`` is a tristage_rag_amd.index.FlatIPIndex (HIP, exact inner
   product).  The reference switches to IndexIVFFlat(nlist=100, nprobe=10) when the
   first add has >1000 rows (:262-273), an approximation of the exact result this
-  index returns; exact search is kept for every size.
+  index returns; exact search is kept for every size by default.
+  ``Stage1Config.index_type`` = "ivf" / "auto" selects tristage_rag_amd.index.IVFFlatIndex
+  (nlist / nprobe; "auto" follows the reference's 1000-row rule).
 * row normalisation ``x / (|x| + 1e-8)`` (:285-288) runs on the GPU inside
   ``add`` when the embeddings are already on the device.
 * ``search_many`` batches queries through one index call (the reference loops one
@@ -54,8 +56,11 @@ class Stage1Config:
     dense_weight: float = 0.7
     bm25_weight: float = 0.3
     use_fp16: bool = True
-    nlist: int = 100  # kept for config compatibility; the index is exact
-    nprobe: int = 10
+    nlist: int = 100  # inverted lists of the IVF index (index_type "ivf", or "auto" above 1000 documents)
+    nprobe: int = 10  # lists each query of the IVF index scans
+    # "flat": exact search (default); "ivf": IVFFlatIndex(nlist, nprobe) trained on the first add_documents;
+    # "auto": the reference's rule (:256-283) — IVF when the first add_documents brings more than 1000 documents
+    index_type: str = "flat"
     # additive knobs (not in the reference)
     index_dtype: str = "f32"   # storage dtype of the corpus matrix: f32 | f16 | bf16
     gpu_index_device: int = 0
@@ -339,6 +344,7 @@ class Stage1Retriever:
         self.model = model
         self.embedding_dim: Optional[int] = None
         self.faiss_index = None
+        self.index_type_used = "flat"   # the kind of faiss_index once it exists: "flat" or "ivf"
         self.bm25_index: Optional[BM25Index] = None
         self.documents: List[str] = []
         self.doc_metadata: List[Dict[str, Any]] = []
@@ -421,14 +427,36 @@ class Stage1Retriever:
         return q / (q.norm(dim=1, keepdim=True) + 1e-8)
 
     # -- index -------------------------------------------------------------
+    def _index_kind(self, n_first: int) -> str:
+        """"flat" or "ivf" for an index whose first add brings ``n_first`` rows (Stage1Config.index_type)."""
+        kind = getattr(self.config, "index_type", "flat")
+        if kind not in ("flat", "ivf", "auto"):
+            raise ValueError(f"index_type must be 'flat', 'ivf' or 'auto', not {kind!r}")
+        if kind == "auto":
+            return "ivf" if n_first > 1000 else "flat"   # reference :256-283
+        return kind
+
+    def _new_device_index(self, d: int, kind: str):
+        if kind == "ivf":
+            from .index import IVFFlatIndex
+            # (the IVF index stores f16 / bf16 rows; an f32 index_dtype stores f16)
+            dt = self.config.index_dtype if self.config.index_dtype in ("f16", "bf16") else "f16"
+            idx = IVFFlatIndex(d, int(self.config.nlist), dtype=dt, device=self.config.gpu_index_device,
+                               nprobe=int(self.config.nprobe))
+        else:
+            from .index import FlatIPIndex  # raises without libtristage.so / a GPU: no CPU fallback
+            idx = FlatIPIndex(d, dtype=self.config.index_dtype, device=self.config.gpu_index_device)
+        self.index_type_used = kind
+        return idx
+
     def _create_faiss_index(self, embeddings: np.ndarray) -> None:
         d = int(embeddings.shape[1])
         if self._index_factory is not None:
             self.faiss_index = self._index_factory(d)
         else:
-            from .index import FlatIPIndex  # raises without libtristage.so / a GPU: no CPU fallback
-            self.faiss_index = FlatIPIndex(d, dtype=self.config.index_dtype,
-                                           device=self.config.gpu_index_device)
+            self.faiss_index = self._new_device_index(d, self._index_kind(len(embeddings)))
+            if self.index_type_used == "ivf":
+                self.faiss_index.train(embeddings)
         self.faiss_index.add(embeddings)
         self.logger.info(f"Index created with {len(embeddings)} vectors (exact inner product)")
 
@@ -443,9 +471,9 @@ class Stage1Retriever:
         if self._device_path():
             emb = self._encode_batch_tensor(list(documents), bulk=True)
             if self.faiss_index is None:
-                from .index import FlatIPIndex
-                self.faiss_index = FlatIPIndex(int(emb.shape[1]), dtype=self.config.index_dtype,
-                                               device=self.config.gpu_index_device)
+                self.faiss_index = self._new_device_index(int(emb.shape[1]), self._index_kind(int(emb.shape[0])))
+                if self.index_type_used == "ivf":
+                    self.faiss_index.train(emb / (emb.norm(dim=1, keepdim=True) + 1e-8))
             self.faiss_index.add(emb, normalize=True)
         else:
             embeddings = self._normalize_embeddings(self._encode_batch(list(documents)))
@@ -544,6 +572,8 @@ class Stage1Retriever:
 
     def _filter_masks(self, filter, nq: int) -> Optional[List[Optional[np.ndarray]]]:
         """-> one mask (or None) per query, None when no query is filtered."""
+        if filter is not None and getattr(self, "index_type_used", "flat") == "ivf":
+            raise NotImplementedError("filtered search is not supported on an IVF index (index_type='ivf')")
         specs = self._per_query_filters(filter, nq)
         if specs is None:
             return None
@@ -830,12 +860,17 @@ class Stage1Retriever:
         os.makedirs(os.path.dirname(os.path.abspath(index_path)), exist_ok=True)
         manifest = {"format": "tristage-rag_amd/1", "documents": self.documents,
                     "doc_metadata": self.doc_metadata, "config": dict(self.config.__dict__),
-                    "ntotal": 0, "dim": self.embedding_dim, "matrix": None}
+                    "ntotal": 0, "dim": self.embedding_dim, "matrix": None,
+                    "index_type": getattr(self, "index_type_used", "flat"), "centroids": None}
         if self.faiss_index is not None:
             mat = self.faiss_index.reconstruct_n(0, self.faiss_index.ntotal)
             np.save(base + ".matrix.npy", mat)
             manifest.update(ntotal=int(mat.shape[0]), dim=int(mat.shape[1]),
                             matrix=os.path.basename(base + ".matrix.npy"))
+            if manifest["index_type"] == "ivf":   # the trained centroids: a reload neither retrains nor reassigns
+                np.save(base + ".centroids.npy", self.faiss_index.centroids)
+                manifest.update(centroids=os.path.basename(base + ".centroids.npy"),
+                                nlist=int(self.faiss_index.nlist), ivf_dtype=self.faiss_index.storage_dtype)
         with open(index_path, "w") as f:  # JSON under the reference's file name
             json.dump(manifest, f)
         self.logger.info(f"Stage 1 index saved to {index_path}")
@@ -856,10 +891,23 @@ class Stage1Retriever:
         self.doc_metadata = manifest["doc_metadata"]
         self._reset_filter_caches()   # the cached filter bitmaps describe the corpus that was here before
         self.faiss_index = None
+        self.index_type_used = "flat"
         if manifest.get("matrix"):
-            mat = np.load(os.path.join(os.path.dirname(os.path.abspath(index_path)), manifest["matrix"]),
-                          allow_pickle=False)
-            self._create_faiss_index(mat.astype(np.float32))
+            here = os.path.dirname(os.path.abspath(index_path))
+            mat = np.load(os.path.join(here, manifest["matrix"]), allow_pickle=False)
+            if manifest.get("index_type", "flat") == "ivf" and self._index_factory is None:
+                from .index import IVFFlatIndex
+                cent = np.load(os.path.join(here, manifest["centroids"]), allow_pickle=False)
+                self.faiss_index = IVFFlatIndex(int(mat.shape[1]), int(manifest["nlist"]), dtype=manifest["ivf_dtype"],
+                                                device=self.config.gpu_index_device, nprobe=int(self.config.nprobe))
+                self.faiss_index.set_centroids(cent.astype(np.float32))
+                self.faiss_index.add(mat.astype(np.float32))
+                self.index_type_used = "ivf"
+            elif self._index_factory is not None:
+                self._create_faiss_index(mat.astype(np.float32))
+            else:
+                self.faiss_index = self._new_device_index(int(mat.shape[1]), "flat")
+                self.faiss_index.add(mat.astype(np.float32))
         if self.config.enable_bm25 and self.documents:
             self.bm25_index = BM25Index(gpu_device=self._bm25_device())
             self.bm25_index.fit(self.documents)
@@ -868,6 +916,7 @@ class Stage1Retriever:
     def get_stats(self) -> Dict[str, Any]:
         return {"total_documents": len(self.documents), "embedding_dimension": self.embedding_dim,
                 "faiss_index_type": type(self.faiss_index).__name__ if self.faiss_index else None,
+                "index_type": getattr(self, "index_type_used", None) if self.faiss_index else None,
                 "bm25_enabled": self.config.enable_bm25,
                 "bm25_vocabulary_size": len(self.bm25_index.vocabulary) if self.bm25_index else 0,
                 "config": self.config.__dict__}
