@@ -49,7 +49,8 @@ extern "C" {
  * ts_index_last_filter_info and ts_bm25_search_batch_filtered (no existing signature changed).  Coalesced passes
  * (TS_FLAG_COALESCE, ts_index_flush, ts_coalesce_groups) were added within version 4: no signature changed, and a
  * caller that never sets the flag sees the library it was built against.  The IVF-Flat entry points (ts_ivf_*) were
- * added within version 4 as well: no existing signature changed.                                             */
+ * added within version 4 as well: no existing signature changed.  So were wide coalesced passes
+ * (TS_FLAG_WIDE_PASSES, TS_FLAG_NO_WIDE_PASSES, ts_coalesce_groups_wide, ts_coalesce_wide_min_bytes).                                             */
 #define TS_ABI_VERSION 4
 
 typedef struct ts_index ts_index; /* opaque */
@@ -92,6 +93,9 @@ enum ts_metric { TS_METRIC_INNER_PRODUCT = 0 };
                                    ts_coalesce_groups() 32-query groups (see "coalesced passes"
                                    below).  Results are identical; they are complete after
                                    ts_index_finish() (or ts_index_flush() and stream order).    */
+#define TS_FLAG_WIDE_PASSES 256u     /* with TS_FLAG_COALESCE: wide passes (ts_coalesce_groups_wide() groups)
+                                        whatever the corpus size; results are identical              */
+#define TS_FLAG_NO_WIDE_PASSES 512u  /* with TS_FLAG_COALESCE: never wide passes (ts_coalesce_groups())  */
 #define TS_FLAG_NORMALIZE 4u    /* add: L2-normalise rows x/(|x|+1e-8) on device first
                                    (reference src/stage1_retriever.py:285-288) */
 
@@ -203,6 +207,14 @@ int ts_index_flush(ts_index* h, void* stream);
 /* 32-query groups per coalesced pass for this dimension and storage type: 4 up to a padded dimension of 512,
  * 3 at 640 and 768, 2 from 896 (no coalescing below 3), 0 for fp32 storage.  Needs no GPU.                   */
 int32_t ts_coalesce_groups(int32_t dim, int32_t storage_dtype);
+/* Wide passes: LDS holds a double-buffered window of the groups' query images instead of the whole images, so a
+ * pass takes ts_coalesce_groups_wide() groups at any dimension (6 for f16 / bf16 storage, 0 for fp32).  The queue
+ * uses them where the corpus (rows rounded up to 32 x padded dimension x element size) is larger than
+ * ts_coalesce_wide_min_bytes() and ts_coalesce_groups() is at most 3 (a padded dimension above 512), unless
+ * TS_FLAG_WIDE_PASSES / TS_FLAG_NO_WIDE_PASSES decide.  A queue holds groups
+ * of one width: a search that asks for the other flushes it first.  Added within version 4.  Need no GPU.     */
+int32_t ts_coalesce_groups_wide(int32_t dim, int32_t storage_dtype);
+int64_t ts_coalesce_wide_min_bytes(void);
 
 /* ---- introspection -------------------------------------------------------
  * faiss_index.ntotal / .d                                                    */

@@ -1,10 +1,12 @@
 """A/B of coalesced passes (TS_FLAG_COALESCE): batches of 64 queries, k = 1000, submitted back to back with
 async_=True and completed by one finish(), with `coalesce` on and off on the same index.  Prints one JSON object.
 
-    python tools/coalesce_probe.py [--rows 1250000] [--dim 768] [--steps 20] [--reps 3]
+    python tools/coalesce_probe.py [--rows 1250000] [--dim 768] [--steps 20] [--reps 3] [--modes classic]
+                                   [--wide auto True False]
 
 Modes per shape: the default path (one-launch at <= 4 M rows, five-launch above), the five-launch path
-(classic) and the pipelined path (inputs_ready=True, which never coalesces)."""
+(classic) and the pipelined path (inputs_ready=True, which never coalesces).  --wide: the FlatIPIndex.wide_passes
+settings the coalesced runs take, one run each (wide passes)."""
 import argparse
 import json
 import os
@@ -23,6 +25,9 @@ def main():
     ap.add_argument("--k", type=int, default=1000)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--modes", nargs="+", default=["default", "classic", "pipelined"],
+                    choices=["default", "classic", "pipelined"])
+    ap.add_argument("--wide", nargs="+", default=["auto"], choices=["auto", "True", "False"])
     args = ap.parse_args()
     import torch
     from tristage_rag_amd.index import FlatIPIndex
@@ -37,10 +42,11 @@ def main():
         qs = [torch.nn.functional.normalize(torch.randn((args.batch, args.dim), generator=g, device="cuda"), dim=1)
               .half() for _ in range(4)]
         torch.cuda.synchronize()
-        for mode in ("default", "classic", "pipelined"):
+        for mode in args.modes:
             idx.classic_filter = mode == "classic"
-            for co in (False, True):
+            for co, wide in [(False, "auto")] + [(True, w) for w in args.wide]:
                 idx.coalesce = co
+                idx.wide_passes = {"auto": "auto", "True": True, "False": False}[wide]
                 ms = []
                 for rep in range(args.reps + 1):
                     torch.cuda.synchronize()
@@ -52,7 +58,7 @@ def main():
                     if rep:   # the first repetition warms up
                         ms.append((time.perf_counter() - t0) * 1e3 / args.steps)
                     assert redone == [], redone
-                out["results"].append({"rows": rows, "mode": mode, "coalesce": co,
+                out["results"].append({"rows": rows, "mode": mode, "coalesce": co, "wide_passes": wide,
                                        "ms_per_batch": [round(x, 4) for x in ms],
                                        "qps_best": round(args.batch / (min(ms) * 1e-3), 1)})
                 print(json.dumps(out["results"][-1]), file=sys.stderr, flush=True)

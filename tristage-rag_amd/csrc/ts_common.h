@@ -176,6 +176,28 @@ uint32_t ts_scan_multi_stage_cap(const TsLayout& L, int G);
 bool ts_scan_multi_fits(int64_t nblk, int num_cus);
 int ts_launch_scan_multi(const TsLayout& L, int G, const MultiScanParams& p, int num_cus, hipStream_t stream);
 
+// Wide coalesced passes (scan_wide_kernel): the groups of MultiScanParams, up to TS_MAX_WIDE_GROUPS of them.  The
+// query image is not kept resident: LDS holds a double-buffered window of TS_RING k groups for all G groups
+// (2 * G * TS_RING KiB), gathered from the batches' images one window ahead, so G does not depend on the dimension.
+#define TS_MAX_WIDE_GROUPS 8
+struct WideScanParams : ScanParams {
+  const uint4* gimg[TS_MAX_WIDE_GROUPS];
+  int gqh[TS_MAX_WIDE_GROUPS];
+  int ghalf[TS_MAX_WIDE_GROUPS];
+  const float* gtau[TS_MAX_WIDE_GROUPS];
+  uint32_t* gcnt[TS_MAX_WIDE_GROUPS];
+  float* gscore[TS_MAX_WIDE_GROUPS];
+  int32_t* gid[TS_MAX_WIDE_GROUPS];
+  uint32_t stage_cap;
+};
+// groups per wide pass (0 for fp32 storage: no wide kernel); host-only arithmetic
+int ts_scan_wide_groups(const TsLayout& L);
+// staging entries the wide kernel gets for G groups (0: G is not a wide group count)
+uint32_t ts_scan_wide_stage_cap(const TsLayout& L, int G);
+// as ts_scan_multi_fits, for the wide kernel's survivor keys (one query bit more, one iteration bit less)
+bool ts_scan_wide_fits(int64_t nblk, int num_cus);
+int ts_launch_scan_wide(const TsLayout& L, int G, const WideScanParams& p, int num_cus, hipStream_t stream);
+
 int ts_launch_scan(const TsLayout& L, int mode, int qh, const ScanParams& p,
                    int num_cus, hipStream_t stream);
 

@@ -77,7 +77,8 @@ void release(DevBuf& b) {
 
 }  // namespace
 #define TS_NPHASE 8
-#define TS_NSETS 4         // workspace sets = synchronous searches that may run at once on one handle
+#define TS_NSETS 8         // workspace sets = synchronous searches that may run at once on one handle; also the
+                           // coalesced queue's held batches (at most TS_MAX_WIDE_GROUPS - 1) plus the one it acquires
 #define TS_ASYNC_SLOTS 1024   // report slots; at most a quarter of them (256 passes) may belong to unfinished asynchronous searches
 #define TS_SLOT_WORDS 80   // 64 counts + status word, padded
 namespace {
@@ -95,6 +96,12 @@ constexpr int kHeadStartUs = 12;           // pipelined mode: delay of the selec
 // coalesced passes (co_submit): expected survivors ~ 3k per query instead of 4k, so that three groups' survivors
 // fit the staging area the query images leave at d = 768 (about 1.3 k per workgroup and pass against 1.9 k slots)
 constexpr int64_t kCoalesceOversample = 3;
+// wide coalesced passes (scan_wide_kernel) by default only where the corpus is larger than the 256 MiB Infinity Cache
+// (only there does a pass saved save HBM bytes) and the LDS-resident passes take at most 3 groups: a wide pass of 6
+// costs 0.62 ms per group at 10 M x 768, a resident pass of 3 0.74, and one of 4 (padded d <= 512) runs at the read
+// ceiling too
+constexpr int64_t kWideMinCorpusBytes = 256ll << 20;
+constexpr int kWideMaxResidentGroups = 3;
 
 }  // namespace
 
@@ -157,17 +164,19 @@ struct ts_index {
   int64_t next_ticket = 0;
   hipEvent_t async_ev[2 * TS_ASYNC_SLOTS] = {};
   // coalesced passes (TS_FLAG_COALESCE): batches whose query prep, sample scan and thresholds are
-  // enqueued but whose filter scan and select wait for co_gmax 32-query groups to share one scan.  A held batch
+  // enqueued but whose filter scan and select wait for co_width 32-query groups to share one scan.  A held batch
   // keeps its workspace set busy until its select is enqueued.  co_mu serialises coalesced submissions and
   // flushes; it is taken before `mu`, never while `mu` is held.
   struct CoBatch { WSet* W; int nq, qh, k, slot, groups_left; float* out_s; int64_t* out_i; };
   struct CoGroup { int batch, half; };
   std::mutex co_mu;
-  int co_gmax = 0;                       // groups per pass (ts_coalesce_groups); < 3: no coalescing
+  int co_gmax = 0;                       // groups per LDS-resident pass (ts_coalesce_groups)
+  int co_gwide = 0;                      // groups per wide pass (ts_coalesce_groups_wide)
+  int co_width = 0;                      // groups per pass of the queue's pending groups (co_pass_width)
   hipStream_t co_stream = nullptr;       // the stream of the held batches
-  CoBatch co_batch[TS_MAX_GROUPS] = {};  // held batches in submission order
+  CoBatch co_batch[TS_MAX_WIDE_GROUPS] = {};  // held batches in submission order
   int co_nbatch = 0;
-  CoGroup co_group[TS_MAX_GROUPS] = {};  // pending groups of the next pass
+  CoGroup co_group[TS_MAX_WIDE_GROUPS] = {};  // pending groups of the next pass
   int co_ngroup = 0;
   uint64_t co_pass_seq = 0;              // timed passes: every prof_every-th
   hipEvent_t co_ev = nullptr;            // recorded on co_stream after every pass and its selects (co_launch_pass)
@@ -274,6 +283,7 @@ extern "C" int ts_index_create(int32_t dim, int32_t storage_dtype, int32_t metri
   h->device = device;
   h->L = L;
   h->co_gmax = ts_coalesce_groups(dim, storage_dtype);
+  h->co_gwide = ts_coalesce_groups_wide(dim, storage_dtype);
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
     h->num_cus = prop.multiProcessorCount;
@@ -997,37 +1007,48 @@ extern "C" int32_t ts_coalesce_groups(int32_t dim, int32_t storage_dtype) {
   return ts_scan_multi_groups(ts_make_layout(dim, storage_dtype));
 }
 
-// Whether an unfiltered pass of a search with these flags joins the pending-pass queue: asynchronous, not
-// pipelined, on the five-launch filter path (the one-launch kernel has no multi-group form), and at least three
-// groups per pass (at two, one pass per 64-query batch is what the plain scan already does).
-static bool co_eligible(const ts_index* h, int k, uint32_t flags) {
+extern "C" int32_t ts_coalesce_groups_wide(int32_t dim, int32_t storage_dtype) {
+  if (dim <= 0 || (storage_dtype != TS_F16 && storage_dtype != TS_BF16)) return 0;
+  return ts_scan_wide_groups(ts_make_layout(dim, storage_dtype));
+}
+
+extern "C" int64_t ts_coalesce_wide_min_bytes() { return kWideMinCorpusBytes; }
+
+// Groups per pass of an unfiltered pass of a search with these flags, or 0 where it does not join the pending-pass
+// queue: asynchronous, not pipelined, on the five-launch filter path (the one-launch kernel has no multi-group form),
+// and at least three groups per pass (at two, one pass per 64-query batch is what the plain scan already does).
+// Wide passes where the corpus (padded rows x padded dimension) is larger than kWideMinCorpusBytes and the resident
+// passes take at most kWideMaxResidentGroups groups, or where TS_FLAG_WIDE_PASSES asks for them;
+// TS_FLAG_NO_WIDE_PASSES keeps the LDS-resident ones.
+static int co_pass_width(const ts_index* h, int k, uint32_t flags) {
   const int64_t N = h->ntotal;
   const int64_t nblk = (N + TS_ROWS_PER_BLOCK - 1) / TS_ROWS_PER_BLOCK;
   const uint32_t need = TS_FLAG_ASYNC | TS_FLAG_COALESCE;
   if ((flags & need) != need || (flags & (TS_FLAG_PIPELINE | TS_FLAG_NO_FILTER | TS_FLAG_HOST_PTR | TS_FLAG_ONE_LAUNCH)))
-    return false;
-  if (h->co_gmax < 3 || k > kMaxFilterK || N < kMinFilterRows || N < 32 * (int64_t)k) return false;
-  if (!(flags & TS_FLAG_CLASSIC) && N <= kOneLaunchMaxRows) return false;   // the one-launch search's regime
-  return ts_scan_multi_fits(nblk, h->num_cus - h->num_cus / 8);
+    return 0;
+  if (k > kMaxFilterK || N < kMinFilterRows || N < 32 * (int64_t)k) return 0;
+  if (!(flags & TS_FLAG_CLASSIC) && N <= kOneLaunchMaxRows) return 0;   // the one-launch search's regime
+  const int grid = h->num_cus - h->num_cus / 8;
+  bool wide = (int64_t)nblk * (int64_t)ts_block_bytes(h->L) > kWideMinCorpusBytes &&
+              h->co_gmax <= kWideMaxResidentGroups;
+  if (flags & TS_FLAG_WIDE_PASSES) wide = true;
+  if (flags & TS_FLAG_NO_WIDE_PASSES) wide = false;
+  if (wide && h->co_gwide >= 3 && ts_scan_wide_fits(nblk, grid)) return h->co_gwide;
+  if (h->co_gmax >= 3 && ts_scan_multi_fits(nblk, grid)) return h->co_gmax;
+  return 0;
 }
 
-// One filter scan over the pending groups; then the select of every batch whose last group was in it.
-// Caller holds co_mu.
-static int co_launch_pass(ts_index* h) {
-  if (h->co_ngroup == 0) return TS_OK;
-  const int G = h->co_ngroup;
+// the pass's geometry and groups, for MultiScanParams / WideScanParams
+template <class P>
+static void co_fill_params(const ts_index* h, int G, P& mp) {
   const int64_t N = h->ntotal;
-  const int64_t nblk = (N + TS_ROWS_PER_BLOCK - 1) / TS_ROWS_PER_BLOCK;
-  hipStream_t s = h->co_stream;
-  MultiScanParams mp{};
   mp.corpus = h->corpus;
   mp.kg = h->L.kg;
-  mp.nwork = nblk;
+  mp.nwork = (N + TS_ROWS_PER_BLOCK - 1) / TS_ROWS_PER_BLOCK;
   mp.blk0 = 0;
   mp.blk_stride = 1;
   mp.ntotal = N;
   mp.cand_cap = kCandCap;
-  mp.stage_cap = ts_scan_multi_stage_cap(h->L, G);
   for (int g = 0; g < G; ++g) {
     const ts_index::CoBatch& b = h->co_batch[h->co_group[g].batch];
     const int half = h->co_group[g].half;
@@ -1039,6 +1060,15 @@ static int co_launch_pass(ts_index* h) {
     mp.gscore[g] = (float*)b.W->cand_score.p + (size_t)32 * half * kCandCap;
     mp.gid[g] = (int32_t*)b.W->cand_id.p + (size_t)32 * half * kCandCap;
   }
+}
+
+// One filter scan over the pending groups; then the select of every batch whose last group was in it.  Groups whose
+// images all fit the LDS take scan_multi_kernel, more take scan_wide_kernel.  Caller holds co_mu.
+static int co_launch_pass(ts_index* h) {
+  if (h->co_ngroup == 0) return TS_OK;
+  const int G = h->co_ngroup;
+  const int64_t N = h->ntotal;
+  hipStream_t s = h->co_stream;
   // per-launch timing of the scan (ts_index_get_timings "filter_scan"), handed to a batch that ends in this pass
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if (h->profiling && h->co_pass_seq++ % (uint64_t)h->prof_every == 0) {
@@ -1048,7 +1078,18 @@ static int co_launch_pass(ts_index* h) {
       e0 = e1 = nullptr;
     }
   }
-  int st = ts_launch_scan_multi(h->L, G, mp, h->num_cus - h->num_cus / 8, s);
+  int st;
+  if (G <= h->co_gmax) {
+    MultiScanParams mp{};
+    co_fill_params(h, G, mp);
+    mp.stage_cap = ts_scan_multi_stage_cap(h->L, G);
+    st = ts_launch_scan_multi(h->L, G, mp, h->num_cus - h->num_cus / 8, s);
+  } else {
+    WideScanParams wp{};
+    co_fill_params(h, G, wp);
+    wp.stage_cap = ts_scan_wide_stage_cap(h->L, G);
+    st = ts_launch_scan_wide(h->L, G, wp, h->num_cus - h->num_cus / 8, s);
+  }
   if (e0 && (st != TS_OK || hipEventRecord(e1, s) != hipSuccess)) {
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
@@ -1135,7 +1176,7 @@ static int co_submit(ts_index* h, const void* dq, int nq, int q_dtype, int k, fl
   const int64_t N = h->ntotal;
   const int64_t nblk = (N + TS_ROWS_PER_BLOCK - 1) / TS_ROWS_PER_BLOCK;
   const int qh = nq > 32 ? 2 : 1;
-  ts_index::WSet* W = acquire_set(h);   // (at most co_gmax - 1 < TS_NSETS sets are held by the queue here)
+  ts_index::WSet* W = acquire_set(h);   // (at most co_width - 1 < TS_NSETS sets are held by the queue here)
   struct SetGuard {
     ts_index* h; ts_index::WSet* W;
     ~SetGuard() { if (W) release_set(h, W); }
@@ -1188,7 +1229,7 @@ static int co_submit(ts_index* h, const void* dq, int nq, int q_dtype, int k, fl
   int st = TS_OK;
   for (int half = 0; half < qh; ++half) {
     h->co_group[h->co_ngroup++] = ts_index::CoGroup{h->co_nbatch - 1, half};
-    if (h->co_ngroup == h->co_gmax) {
+    if (h->co_ngroup == h->co_width) {
       const int s1 = co_launch_pass(h);
       if (st == TS_OK) st = s1;
     }
@@ -1239,11 +1280,14 @@ extern "C" int ts_index_search(ts_index* h, const void* queries, int32_t nq, int
     }
   }
   const size_t qrow = (size_t)h->L.dim * dtype_size(q_dtype);
-  if (co_eligible(h, k, flags)) {
+  if (const int width = co_pass_width(h, k, flags)) {
     std::lock_guard<std::mutex> lk(h->co_mu);
     // the queue holds one stream's batches: moving it to `s` flushes it and orders `s` behind the old stream's passes
     if (h->co_stream != s) TS_CHECK(co_flush_locked(h, s));
+    // and passes of one width: a search that asks for another one flushes the pending groups first
+    if (h->co_ngroup > 0 && h->co_width != width) TS_CHECK(co_flush_locked(h, s));
     h->co_stream = s;
+    h->co_width = width;
     for (int q0 = 0; q0 < nq; q0 += qp) {
       const int c = std::min(qp, nq - q0);
       TS_CHECK(co_submit(h, (const char*)queries + (size_t)q0 * qrow, c, q_dtype, k, out_scores + (size_t)q0 * k,

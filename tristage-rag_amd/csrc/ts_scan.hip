@@ -21,6 +21,7 @@
 //     query out of millions) are appended to per-query candidate lists, so the
 //     B x N score matrix is never materialised.
 #include "ts_scan_dev.h"
+#include "ts_linear_dev.h"   // fs_barrier: the wide scan's window barrier
 #include <stdlib.h>
 
 // One persistent wave streams row blocks gw, gw+W, gw+2W, ... (W = waves in
@@ -301,16 +302,18 @@ static_assert(SCAN_WAVES <= 8 && TS_MAX_GROUPS * 32 <= 128, "survivor key fields
 #define TS_MULTI_MAX_STAGE 4096u     // entries: more LDS than this buys nothing (about 1.3 k survivors per pass)
 
 // a[g] for a run-time g < G, without a dynamically indexed kernel argument (that would go through scratch)
-template <int G, class T>
-__device__ __forceinline__ T pick_group(const T (&a)[TS_MAX_GROUPS], int g) {
+template <int G, class T, int N>
+__device__ __forceinline__ T pick_group(const T (&a)[N], int g) {
   T r = a[0];
 #pragma unroll
   for (int i = 1; i < G; ++i) r = (g == i) ? a[i] : r;
   return r;
 }
 
-template <int G>
-__device__ __forceinline__ void epilogue_multi(const MultiScanParams& p, StageMultiHdr* st, float* sscore,
+// QB: bits of the query field of the survivor key (7 for scan_multi_kernel, 8 for scan_wide_kernel); the row in the
+// block sits right above it
+template <int G, int QB, class P, class H>
+__device__ __forceinline__ void epilogue_multi(const P& p, H* st, float* sscore,
                                                uint32_t* skey, const f32x16 (&acc)[G], const float (&tau)[G],
                                                int64_t blk, uint32_t keyhi, int lane) {
   bool hit = false;
@@ -334,7 +337,7 @@ __device__ __forceinline__ void epilogue_multi(const MultiScanParams& p, StageMu
         if (mask & (1u << r)) {
           if (slot < p.stage_cap) {
             sscore[slot] = acc[hq][r];
-            skey[slot] = keyhi | ((uint32_t)acc_row(r, lane) << 7) | (uint32_t)(hq * 32 + j);
+            skey[slot] = keyhi | ((uint32_t)acc_row(r, lane) << QB) | (uint32_t)(hq * 32 + j);
           } else {
             // staging area full: append directly
             const uint32_t g = atomicAdd(&p.gcnt[hq][j], 1u);
@@ -447,7 +450,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_multi_kernel(MultiScanParam
       __builtin_amdgcn_sched_barrier(0);
     }
 
-    epilogue_multi<G>(p, st, sscore, skey, acc, tau, blk, keyhi, lane);
+    epilogue_multi<G, 7>(p, st, sscore, skey, acc, tau, blk, keyhi, lane);
 
     if (!has_next) break;
     w = wn;
@@ -536,6 +539,248 @@ int ts_launch_scan_multi(const TsLayout& L, int G, const MultiScanParams& p, int
   }
 #undef TS_MULTI_G
   ts_set_error("multi-group scan: bad dtype %d or group count %d", L.dtype, G);
+  return TS_ERR_UNSUPPORTED;
+}
+
+// Wide coalesced passes (scan_wide_kernel<DT, G>, WideScanParams): scan_multi_kernel for more groups than their
+// query images can keep resident in LDS.  The corpus path is scan_kernel's: the same persistent waves, row blocks,
+// order and TS_RING-deep register ring of non-temporal loads.  The query side is a double-buffered window in LDS:
+// TS_RING k groups of all G groups (G * TS_RING KiB; unit (i*G + g)*64 + lane for k group g0 + i of group g, the
+// resident image's order), so G no longer depends on the dimension.  The k groups of a row block are walked in
+// windows of TS_RING — the g0 += TS_RING steps of scan_kernel — and every row block walks the same windows, so the
+// workgroup's waves meet at one barrier per window:
+//   * at the start of a window each thread requests its G units of the NEXT window from the batches' Q images (L2:
+//     a pass reads at most a few hundred KiB of images, and FETCH_SIZE stays one corpus read);
+//   * it runs the window's TS_RING x G MFMAs out of the current buffer and refills its corpus ring;
+//   * it writes the requested units to the other buffer (their vmcnt wait is behind the ring loads issued in this
+//     window, which it leaves in flight) and meets the others at lgkmcnt(0) + s_barrier.
+// The other buffer was last read in the previous window, before the previous barrier.  Waves whose walk is shorter
+// than the workgroup's longest (one iteration less, or no work at all) keep copying and meeting the barrier until
+// that walk ends.  Each group's MFMA chain is scan_kernel's for it (same operands, k order, zeroed start), so a
+// query's score bits do not depend on G or on which groups share its pass.
+//
+// Survivor keys need 8 query bits at G > 4: (iteration << 16) | (wave << 13) | (row in block << 8) | query of the
+// pass; ts_scan_wide_fits() keeps the iteration count below 2^16.  Staging gets the LDS the two windows leave.
+struct StageWideHdr {
+  uint32_t cnt;
+  uint32_t pad[3];
+  uint32_t qcnt[TS_MAX_WIDE_GROUPS * 32];
+  uint32_t qbase[TS_MAX_WIDE_GROUPS * 32];
+  uint32_t qoff[TS_MAX_WIDE_GROUPS * 32];
+  // followed by float score[stage_cap], uint32_t key[stage_cap]
+};
+static_assert(SCAN_WAVES <= 8 && TS_MAX_WIDE_GROUPS * 32 <= 256, "wide survivor key fields");
+static_assert(SCAN_THREADS == TS_RING * 64, "a window is G units per thread");
+#define TS_WIDE_GROUPS 6             // groups per wide pass: three 64-query batches
+#define TS_WIDE_MAX_ITERS (1 << 16)
+#define TS_WIDE_MIN_STAGE 4096u      // entries
+#define TS_WIDE_MAX_STAGE 8192u      // entries: about 2.6 k survivors per workgroup and pass at G = 6
+
+template <int DT, int G>
+__global__ __launch_bounds__(SCAN_THREADS) void scan_wide_kernel(WideScanParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr int WU = G * TS_RING * 64;   // 16-byte units per window buffer
+  u32x4* win = reinterpret_cast<u32x4*>(smem);
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int kg = p.kg;
+  const int nwin = kg / TS_RING;   // (ts_make_layout: kg is a multiple of TS_RING)
+
+  const int64_t nwaves = (int64_t)gridDim.x * SCAN_WAVES;
+  const int64_t w0 = (int64_t)blockIdx.x * SCAN_WAVES;
+  int64_t w = w0 + wave;
+  const bool active = w < p.nwork;
+  const u32x4* base = reinterpret_cast<const u32x4*>(p.corpus) + lane;
+  const size_t blk_units = (size_t)kg * 64;
+  int64_t blk = active ? p.blk0 + w * p.blk_stride : p.blk0;
+  const u32x4* cur = base + (size_t)blk * blk_units;
+  u32x4 ring[TS_RING];
+  if (active) {
+#pragma unroll
+    for (int i = 0; i < TS_RING; ++i) ring[i] = stream_load(cur + (size_t)i * 64);
+  }
+
+  // this thread's share of every window: units tid + j*SCAN_THREADS (j < G) = k group v / G of the window, group
+  // v % G, v = wave + SCAN_WAVES*j (wave-uniform); source offsets of window 0 and the step between windows
+  const u32x4* qsrc[G];
+  int qstep[G];
+#pragma unroll
+  for (int j = 0; j < G; ++j) {
+    const int v = wave + SCAN_WAVES * j, i = v / G, g = v - i * G;
+    const int gqh = pick_group<G>(p.gqh, g);
+    qsrc[j] = reinterpret_cast<const u32x4*>(pick_group<G>(p.gimg, g)) +
+              (size_t)(i * gqh + pick_group<G>(p.ghalf, g)) * 64 + lane;
+    qstep[j] = gqh * TS_RING * 64;
+  }
+  u32x4 qt[G];
+  auto gather = [&](int wi) {
+#pragma unroll
+    for (int j = 0; j < G; ++j) qt[j] = qsrc[j][(size_t)wi * qstep[j]];
+  };
+  auto put = [&](int b) {
+#pragma unroll
+    for (int j = 0; j < G; ++j) win[b * WU + tid + j * SCAN_THREADS] = qt[j];
+  };
+
+  StageWideHdr* st = reinterpret_cast<StageWideHdr*>(smem + (size_t)2 * WU * 16);
+  float* sscore = reinterpret_cast<float*>(st + 1);
+  uint32_t* skey = reinterpret_cast<uint32_t*>(sscore + p.stage_cap);
+  gather(0);
+  put(0);
+  if (tid == 0) st->cnt = 0;
+  fs_barrier();
+  int buf = 0;   // the buffer holding the current window
+
+  // walks: this wave's row blocks, and the workgroup's longest walk (its wave 0's)
+  const int64_t my_iters = active ? (p.nwork - 1 - w) / nwaves + 1 : 0;
+  const int64_t wg_iters = w0 < p.nwork ? (p.nwork - 1 - w0) / nwaves + 1 : 0;
+
+  if (active) {
+
+  float tau[G];
+#pragma unroll
+  for (int hq = 0; hq < G; ++hq) tau[hq] = p.gtau[hq][lane & 31];
+
+  uint32_t keyhi = (uint32_t)wave << 13;   // + (iteration << 16)
+
+  while (true) {
+    const int64_t wn = w + nwaves;
+    const bool has_next = wn < p.nwork;
+    const int64_t blkn = has_next ? (p.blk0 + wn * p.blk_stride) : blk;
+    const u32x4* nxt = base + (size_t)blkn * blk_units;
+
+    f32x16 acc[G];
+#pragma unroll
+    for (int hq = 0; hq < G; ++hq)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[hq][r] = 0.f;
+
+    // one window: k groups [g0, g0 + TS_RING) from buffer `buf`, the ring refilled from `refill`, window `wnext`
+    // requested now and written to the other buffer at the end
+    auto window = [&](const u32x4* refill, int wnext) {
+      gather(wnext);
+      const u32x4* ql = win + buf * WU + lane;
+#pragma unroll
+      for (int i = 0; i < TS_RING; ++i) {
+#pragma unroll
+        for (int hq = 0; hq < G; ++hq) {
+          const u32x4 b = ql[(i * G + hq) * 64];
+          mma_group<DT>(acc[hq], ring[i], b);
+        }
+        ring[i] = stream_load(refill + (size_t)i * 64);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      put(buf ^ 1);
+      fs_barrier();
+      buf ^= 1;
+    };
+    // main part: prefetch stays inside the current row block
+    int g0 = 0, wi = 0;
+    for (; g0 < kg - TS_RING; g0 += TS_RING, ++wi) window(cur + (size_t)(g0 + TS_RING) * 64, wi + 1);
+    // tail: the ring is refilled from the start of the wave's next row block; the next window is window 0
+    window(nxt, 0);
+
+    epilogue_multi<G, 8>(p, st, sscore, skey, acc, tau, blk, keyhi, lane);
+
+    if (!has_next) break;
+    w = wn;
+    blk = blkn;
+    cur = nxt;
+    keyhi += 1u << 16;
+  }
+  }  // active
+
+  // the workgroup's other waves are still walking: keep filling windows with them
+  for (int64_t it = my_iters; it < wg_iters; ++it) {
+    for (int wi = 0; wi < nwin; ++wi) {
+      gather(wi + 1 < nwin ? wi + 1 : 0);
+      put(buf ^ 1);
+      fs_barrier();
+      buf ^= 1;
+    }
+  }
+
+  // ---- flush: one global atomic per (workgroup, query) reserves the slots
+  __syncthreads();
+  const uint32_t n = st->cnt < p.stage_cap ? st->cnt : p.stage_cap;
+  if (n == 0) return;  // uniform: cnt is final after the barrier
+  for (int t = tid; t < G * 32; t += SCAN_THREADS) { st->qcnt[t] = 0; st->qoff[t] = 0; }
+  __syncthreads();
+  for (uint32_t e = tid; e < n; e += SCAN_THREADS) atomicAdd(&st->qcnt[skey[e] & 255u], 1u);
+  __syncthreads();
+  for (int t = tid; t < G * 32; t += SCAN_THREADS)
+    if (st->qcnt[t] > 0) st->qbase[t] = atomicAdd(pick_group<G>(p.gcnt, t >> 5) + (t & 31), st->qcnt[t]);
+  __syncthreads();
+  for (uint32_t e = tid; e < n; e += SCAN_THREADS) {
+    const uint32_t key = skey[e];
+    const uint32_t q = key & 255u;
+    const uint32_t slot = st->qbase[q] + atomicAdd(&st->qoff[q], 1u);
+    if (slot < p.cand_cap) {
+      const int g = (int)(q >> 5);
+      const size_t at = (size_t)(q & 31u) * p.cand_cap + slot;
+      const int64_t wi = (int64_t)blockIdx.x * SCAN_WAVES + ((key >> 13) & 7u) + (int64_t)(key >> 16) * nwaves;
+      pick_group<G>(p.gscore, g)[at] = sscore[e];
+      pick_group<G>(p.gid, g)[at] = (int32_t)((p.blk0 + wi * p.blk_stride) * TS_ROWS_PER_BLOCK + ((key >> 8) & 31u));
+    }
+  }
+}
+
+int ts_scan_wide_groups(const TsLayout& L) {
+  if (L.dtype != TS_F16 && L.dtype != TS_BF16) return 0;
+  return ts_scan_wide_stage_cap(L, TS_WIDE_GROUPS) > 0 ? TS_WIDE_GROUPS : 0;
+}
+
+uint32_t ts_scan_wide_stage_cap(const TsLayout& L, int G) {
+  (void)L;   // the windows do not depend on the dimension
+  const size_t fixed = (size_t)2 * G * TS_RING * 1024 + sizeof(StageWideHdr);
+  if (G < 2 || G > TS_WIDE_GROUPS || fixed + 8 * (size_t)TS_WIDE_MIN_STAGE > 160 * 1024) return 0;
+  return (uint32_t)std::min<size_t>(TS_WIDE_MAX_STAGE, (160 * 1024 - fixed) / 8);
+}
+
+bool ts_scan_wide_fits(int64_t nblk, int num_cus) {
+  const int64_t want = (nblk + SCAN_WAVES - 1) / SCAN_WAVES;
+  const int64_t grid = std::max<int64_t>(1, std::min<int64_t>(want, num_cus));
+  const int64_t nwaves = grid * SCAN_WAVES;
+  return (nblk + nwaves - 1) / nwaves <= TS_WIDE_MAX_ITERS;
+}
+
+template <int DT, int G>
+static int launch_scan_wide_t(const WideScanParams& p, int num_cus, hipStream_t stream) {
+  const size_t lds = (size_t)2 * G * TS_RING * 1024 + sizeof(StageWideHdr) + 8 * (size_t)p.stage_cap;
+  auto kern = scan_wide_kernel<DT, G>;
+  static TsDeviceOnce lds_attr;
+  TS_CHECK(ts_allow_max_lds(lds_attr, reinterpret_cast<const void*>(kern)));
+  const int64_t want = (p.nwork + SCAN_WAVES - 1) / SCAN_WAVES;
+  int grid = (int)(want < num_cus ? want : num_cus);
+  if (grid < 1) grid = 1;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(SCAN_THREADS), lds, stream, p);
+  TS_HIP(hipGetLastError());
+  return TS_OK;
+}
+
+int ts_launch_scan_wide(const TsLayout& L, int G, const WideScanParams& p, int num_cus, hipStream_t stream) {
+  if (p.nwork <= 0) return TS_OK;
+  if (p.stage_cap == 0 || p.stage_cap > ts_scan_wide_stage_cap(L, G) || !ts_scan_wide_fits(p.nwork, num_cus) ||
+      L.kg % TS_RING != 0) {
+    ts_set_error("wide scan: %d groups do not fit at dimension %d", G, L.dim);
+    return TS_ERR_UNSUPPORTED;
+  }
+  // (G = 2..4: partial passes that the LDS-resident kernel cannot take at this dimension)
+#define TS_WIDE_G(DT)                                                   \
+  switch (G) {                                                          \
+    case 2: return launch_scan_wide_t<DT, 2>(p, num_cus, stream);       \
+    case 3: return launch_scan_wide_t<DT, 3>(p, num_cus, stream);       \
+    case 4: return launch_scan_wide_t<DT, 4>(p, num_cus, stream);       \
+    case 5: return launch_scan_wide_t<DT, 5>(p, num_cus, stream);       \
+    case 6: return launch_scan_wide_t<DT, 6>(p, num_cus, stream);       \
+  }
+  switch (L.dtype) {
+    case TS_F16: TS_WIDE_G(TS_F16); break;
+    case TS_BF16: TS_WIDE_G(TS_BF16); break;
+  }
+#undef TS_WIDE_G
+  ts_set_error("wide scan: bad dtype %d or group count %d", L.dtype, G);
   return TS_ERR_UNSUPPORTED;
 }
 

@@ -78,6 +78,17 @@ def _stream_ptr(device_index: int) -> int:
     return int(torch.cuda.current_stream(device_index).cuda_stream)
 
 
+def wide_pass_flags(wide_passes) -> int:
+    """Search flags of FlatIPIndex.wide_passes: "auto" (the library's policy), True / False (forced on / off)."""
+    if wide_passes is True:
+        return _lib.TS_FLAG_WIDE_PASSES
+    if wide_passes is False:
+        return _lib.TS_FLAG_NO_WIDE_PASSES
+    if isinstance(wide_passes, str) and wide_passes == "auto":
+        return 0
+    raise ValueError(f"wide_passes must be 'auto', True or False, not {wide_passes!r}")
+
+
 class FlatIPIndex:
     """Exact inner-product index resident in MI355X HBM."""
 
@@ -107,6 +118,9 @@ class FlatIPIndex:
         # async_ searches may share one corpus pass with the batches that follow them (TS_FLAG_COALESCE); results are
         # identical.  False: one pass per batch, as before (A/B runs, owners that read results in stream order)
         self.coalesce = True
+        # coalesced passes of ts_coalesce_groups_wide() groups: "auto" where the corpus is larger than the Infinity
+        # Cache (ts_coalesce_wide_min_bytes()), True / False to force them on / off (tests, A/B runs)
+        self.wide_passes = "auto"
         self._filter_info = None  # set by finish() when it redid a filtered search: the counters of what was submitted
 
     # -- lifetime ---------------------------------------------------------
@@ -222,6 +236,7 @@ class FlatIPIndex:
                 flags |= _lib.TS_FLAG_PIPELINE
             elif self.coalesce:
                 flags |= _lib.TS_FLAG_COALESCE
+                flags |= wide_pass_flags(self.wide_passes)
         if _is_tensor(q) and q.is_cuda:
             torch = _torch()
             if q.dim() != 2 or q.shape[1] != self.d:
