@@ -1033,7 +1033,7 @@ static int co_pass_width(const ts_index* h, int k, uint32_t flags) {
               h->co_gmax <= kWideMaxResidentGroups;
   if (flags & TS_FLAG_WIDE_PASSES) wide = true;
   if (flags & TS_FLAG_NO_WIDE_PASSES) wide = false;
-  if (wide && h->co_gwide >= 3 && ts_scan_wide_fits(nblk, grid)) return h->co_gwide;
+  if (wide && h->co_gwide >= 3 && ts_scan_wide_fits(nblk, h->num_cus)) return h->co_gwide;   // (co_launch_pass: every CU)
   if (h->co_gmax >= 3 && ts_scan_multi_fits(nblk, grid)) return h->co_gmax;
   return 0;
 }
@@ -1088,7 +1088,16 @@ static int co_launch_pass(ts_index* h) {
     WideScanParams wp{};
     co_fill_params(h, G, wp);
     wp.stage_cap = ts_scan_wide_stage_cap(h->L, G);
-    st = ts_launch_scan_wide(h->L, G, wp, h->num_cus - h->num_cus / 8, s);
+    // every CU: the wide pass is co-bound by the matrix pipe, so the 7/8 of scan_kernel (HBM-bound) gives up 1/8
+    // of its MFMA throughput (3.53-3.54 against 3.72-3.79 ms per 6-group pass at 10 M x 768).  The
+    // free eighth serves the one-launch search's threshold workgroups and pipelined neighbours; a coalesced pass has
+    // neither (co_pass_width), and its selects follow it on this stream.
+    int wide_cus = h->num_cus;
+#ifdef TS_TUNING   // A/B only: how many CUs the wide pass may occupy
+    static const int dbg_wide_cus = getenv("TS_WIDE_CUS") ? atoi(getenv("TS_WIDE_CUS")) : 0;
+    if (dbg_wide_cus > 0) wide_cus = dbg_wide_cus;
+#endif
+    st = ts_launch_scan_wide(h->L, G, wp, wide_cus, s);
   }
   if (e0 && (st != TS_OK || hipEventRecord(e1, s) != hipSuccess)) {
     (void)hipEventDestroy(e0);

@@ -543,21 +543,25 @@ int ts_launch_scan_multi(const TsLayout& L, int G, const MultiScanParams& p, int
 }
 
 // Wide coalesced passes (scan_wide_kernel<DT, G>, WideScanParams): scan_multi_kernel for more groups than their
-// query images can keep resident in LDS.  The corpus path is scan_kernel's: the same persistent waves, row blocks,
-// order and TS_RING-deep register ring of non-temporal loads.  The query side is a double-buffered window in LDS:
-// TS_RING k groups of all G groups (G * TS_RING KiB; unit (i*G + g)*64 + lane for k group g0 + i of group g, the
-// resident image's order), so G no longer depends on the dimension.  The k groups of a row block are walked in
-// windows of TS_RING — the g0 += TS_RING steps of scan_kernel — and every row block walks the same windows, so the
-// workgroup's waves meet at one barrier per window:
-//   * at the start of a window each thread requests its G units of the NEXT window from the batches' Q images (L2:
-//     a pass reads at most a few hundred KiB of images, and FETCH_SIZE stays one corpus read);
-//   * it runs the window's TS_RING x G MFMAs out of the current buffer and refills its corpus ring;
-//   * it writes the requested units to the other buffer (their vmcnt wait is behind the ring loads issued in this
-//     window, which it leaves in flight) and meets the others at lgkmcnt(0) + s_barrier.
-// The other buffer was last read in the previous window, before the previous barrier.  Waves whose walk is shorter
-// than the workgroup's longest (one iteration less, or no work at all) keep copying and meeting the barrier until
-// that walk ends.  Each group's MFMA chain is scan_kernel's for it (same operands, k order, zeroed start), so a
-// query's score bits do not depend on G or on which groups share its pass.
+// query images can keep resident in LDS.  The corpus path is scan_kernel's persistent waves, row blocks and order of
+// non-temporal loads, with a register ring two windows (2 * TS_RING units) deep.  The query side is a double-buffered
+// window in LDS: TS_RING k groups of all G groups (G * TS_RING KiB; unit (i*G + g)*64 + lane for k group g0 + i of
+// group g, the resident image's order), so G no longer depends on the dimension.  The k groups of a row block are
+// walked in windows of TS_RING — the g0 += TS_RING steps of scan_kernel — and every row block walks the same
+// windows, so the workgroup's waves meet at one barrier per window:
+//   * at the start of window t each wave requests its G units of window t + 1 from the batches' Q images (L2: a pass
+//     reads at most a few hundred KiB of images, and FETCH_SIZE stays one corpus read) by LDS-DMA into the other
+//     buffer;
+//   * it runs the window's TS_RING x G MFMAs out of the current buffer and refills that ring half with window t + 2;
+//   * it waits for the units (vmcnt(TS_RING): the ring loads issued in this window stay in flight) and meets the
+//     others at lgkmcnt(0) + s_barrier.
+// The other buffer was last read in window t - 1, before the previous barrier.  A window's corpus units are thus
+// requested a full window before it starts, where a one-window ring requested them during the window before: with
+// 48 MFMAs per window the loads then arrived late and the workgroup waited at the barrier for its slowest wave
+// (DESIGN.md 4.2c).  Waves whose walk is shorter than the workgroup's longest (one iteration less, or no work at
+// all) keep requesting windows and meeting the barrier until that walk ends.  Each group's MFMA chain is
+// scan_kernel's for it (same operands, k order, zeroed start), so a query's score bits do not depend on G or on which
+// groups share its pass.
 //
 // Survivor keys need 8 query bits at G > 4: (iteration << 16) | (wave << 13) | (row in block << 8) | query of the
 // pass; ts_scan_wide_fits() keeps the iteration count below 2^16.  Staging gets the LDS the two windows leave.
@@ -576,6 +580,34 @@ static_assert(SCAN_THREADS == TS_RING * 64, "a window is G units per thread");
 #define TS_WIDE_MIN_STAGE 4096u      // entries
 #define TS_WIDE_MAX_STAGE 8192u      // entries: about 2.6 k survivors per workgroup and pass at G = 6
 
+// f(std::integral_constant<int, i>) for i = 0 .. N-1: unrolled with i usable as an inline-asm immediate
+template <int N, int I = 0, class F>
+__device__ __forceinline__ void ts_static_for(F&& f) {
+  if constexpr (I < N) {
+    f(std::integral_constant<int, I>{});
+    ts_static_for<N, I + 1>(f);
+  }
+}
+
+// ring slot I of the wide scan: fill (wave-uniform) + the lane's 16-byte offset + I KiB, as the lane offset and an
+// immediate of (I % 4) KiB from fill or fill + 4 KiB (no offset registers); non-temporal like stream_load.
+// (s_nop 4: a VMEM instruction may read an SGPR only 5 wait states after a VALU wrote it (v_readfirstlane), and
+// the compiler pads nothing inside an asm statement; the base is SALU arithmetic today, which needs none, but that is
+// the compiler's choice.  Issue cost only: the MFMAs in flight keep running.)
+// The destination is written when the load lands, up to two windows after the statement, while the compiler takes it
+// as written at once: the kernel is correct only if the compiler neither copies nor spills a ring register in between.
+// It does neither while the kernel uses no scratch (every instantiation, tests/test_wide_ring_build.py).  A
+// TS_TUNING build without MFMAs spills, so there the loads are plain ones the compiler waits for.
+template <int I>
+__device__ __forceinline__ void wide_ring_load(u32x4& r, uint32_t loff, const unsigned char* fill) {
+#if defined(TS_TUNING) && defined(DBG_NO_MFMA)
+  r = stream_load(reinterpret_cast<const u32x4*>(fill + loff + I * 1024));
+#else
+  __asm__ volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2 offset:%3 nt"
+                   : "=v"(r) : "v"(loff), "s"(fill + (I / 4) * 4096), "i"((I % 4) * 1024) : "memory");
+#endif
+}
+
 template <int DT, int G>
 __global__ __launch_bounds__(SCAN_THREADS) void scan_wide_kernel(WideScanParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -591,114 +623,193 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_wide_kernel(WideScanParams 
   const int64_t w0 = (int64_t)blockIdx.x * SCAN_WAVES;
   int64_t w = w0 + wave;
   const bool active = w < p.nwork;
-  const u32x4* base = reinterpret_cast<const u32x4*>(p.corpus) + lane;
   const size_t blk_units = (size_t)kg * 64;
   int64_t blk = active ? p.blk0 + w * p.blk_stride : p.blk0;
-  const u32x4* cur = base + (size_t)blk * blk_units;
-  u32x4 ring[TS_RING];
-  if (active) {
-#pragma unroll
-    for (int i = 0; i < TS_RING; ++i) ring[i] = stream_load(cur + (size_t)i * 64);
-  }
+
+  // walks, in windows: this wave's (its row blocks x nwin) and the workgroup's longest (its wave 0's)
+  const int64_t my_iters = active ? (p.nwork - 1 - w) / nwaves + 1 : 0;
+  const int64_t wg_iters = w0 < p.nwork ? (p.nwork - 1 - w0) / nwaves + 1 : 0;
+  const int64_t tw_mine = my_iters * nwin, tw_all = wg_iters * nwin;
+
+  // The ring is two windows deep: window t of the walk computes from slots (t & 1) * TS_RING + i and refills them
+  // with window t + 2, so every corpus unit is requested a full window before the window that needs it starts.
+  // `fill` (wave-uniform, scalar) is the first byte of the window the next refill requests, `fwin` its window in the
+  // row block.  A lane adds its 16 bytes as a 32-bit offset.
+  const unsigned char* corpus = reinterpret_cast<const unsigned char*>(p.corpus);
+  const uint32_t loff = (uint32_t)lane * 16;
+  int64_t fw = w;
+  const unsigned char* fill = corpus + (size_t)blk * blk_units * 16;
+  // past the end of the walk the refills (two windows per wave, never consumed) read the first 8 KiB of group 0's
+  // query image instead: in bounds (an image holds kg >= TS_RING KiB per 32 queries), L2-resident (every window's
+  // requests read it), so no corpus bytes are fetched twice, and every window still issues TS_RING ring loads
+  const unsigned char* const fill_dead = reinterpret_cast<const unsigned char*>(p.gimg[0]);
+  bool fill_done = false;
+  int fwin = 0;
+  auto advance_fill = [&]() {
+    if (fill_done) return;
+    if (++fwin < nwin) {
+      fill += TS_RING * 1024;
+    } else if (fw + nwaves < p.nwork) {
+      fwin = 0;
+      fw += nwaves;
+      fill = corpus + (size_t)(p.blk0 + fw * p.blk_stride) * blk_units * 16;
+    } else {
+      fill_done = true;
+      fill = fill_dead;
+    }
+  };
+#if defined(TS_TUNING) && defined(DBG_WIDE_L2_RING)   // ablation builds only (wrong results): the ring reads one L2-resident 8 KiB
+  fill = fill_dead;
+  fill_done = true;
+#endif
+  // The ring's loads are inline asm too, and the walk waits for them itself (ring_wait): the compiler's waitcnt pass
+  // does not count the units' LDS-DMA, and for loads it counts it waits as if the ring were one window deep.
+  // Requests per wave, oldest first: the units of window t + 1 (G), then the ring loads of window t + 2 (TS_RING)
+  // at window t; so a slot's load is followed by (TS_RING - 1) + 2 * G + TS_RING younger ones when it is consumed.
+  auto refill = [&](u32x4& r, auto slot) { wide_ring_load<decltype(slot)::value>(r, loff, fill); };
+  auto ring_wait = [&](u32x4& r) {
+    __asm__ volatile("s_waitcnt vmcnt(%1)" : "+v"(r) : "i"(2 * TS_RING - 1 + 2 * G));
+  };
 
   // this thread's share of every window: units tid + j*SCAN_THREADS (j < G) = k group v / G of the window, group
-  // v % G, v = wave + SCAN_WAVES*j (wave-uniform); source offsets of window 0 and the step between windows
-  const u32x4* qsrc[G];
-  int qstep[G];
+  // v % G, v = wave + SCAN_WAVES*j (wave-uniform).  A wave's 64 lanes fill 64 consecutive units, so each share is
+  // one LDS-DMA (global_load_lds_dwordx4: per-lane source, LDS destination = wave-uniform base + lane * 16) from a
+  // wave-uniform source base plus the lane's 16 bytes: no registers hold the units, no ds_write copies them.
+  // (Inline asm, not the builtin: DESIGN.md §8.  The requests are invisible to the compiler's waitcnt pass, so its
+  // waits for the ring can only come out stricter; their own completion is the explicit vmcnt before each barrier.)
+  const unsigned char* qsrc[G];
+  int64_t qstep[G];   // bytes between windows
 #pragma unroll
   for (int j = 0; j < G; ++j) {
     const int v = wave + SCAN_WAVES * j, i = v / G, g = v - i * G;
     const int gqh = pick_group<G>(p.gqh, g);
-    qsrc[j] = reinterpret_cast<const u32x4*>(pick_group<G>(p.gimg, g)) +
-              (size_t)(i * gqh + pick_group<G>(p.ghalf, g)) * 64 + lane;
-    qstep[j] = gqh * TS_RING * 64;
+    qsrc[j] = reinterpret_cast<const unsigned char*>(pick_group<G>(p.gimg, g)) +
+              (size_t)(i * gqh + pick_group<G>(p.ghalf, g)) * 1024;
+    qstep[j] = (int64_t)gqh * TS_RING * 1024;
   }
-  u32x4 qt[G];
-  auto gather = [&](int wi) {
+  const uint32_t win_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)(win + wave * 64);
+  // request window wi's units into buffer b
+  auto gather = [&](int wi, int b) {
 #pragma unroll
-    for (int j = 0; j < G; ++j) qt[j] = qsrc[j][(size_t)wi * qstep[j]];
-  };
-  auto put = [&](int b) {
-#pragma unroll
-    for (int j = 0; j < G; ++j) win[b * WU + tid + j * SCAN_THREADS] = qt[j];
+    for (int j = 0; j < G; ++j) {
+      const unsigned char* src = qsrc[j] + wi * qstep[j];
+      const uint32_t dst = win_lds + (uint32_t)(b * WU + j * SCAN_THREADS) * 16;
+      // s_nop 4: the SGPR-base hazard of wide_ring_load.  s_nop 0: an LDS-DMA may read M0 one wait state after an
+      // SALU wrote it.  M0 is saved and restored: the compiler reserves it, and a clobber would not make it do so.
+      uint32_t keep;
+      __asm__ volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
+                       "global_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+                       : "=&s"(keep) : "v"(loff), "s"(src), "s"(dst) : "memory");
+    }
   };
 
   StageWideHdr* st = reinterpret_cast<StageWideHdr*>(smem + (size_t)2 * WU * 16);
   float* sscore = reinterpret_cast<float*>(st + 1);
   uint32_t* skey = reinterpret_cast<uint32_t*>(sscore + p.stage_cap);
-  gather(0);
-  put(0);
   if (tid == 0) st->cnt = 0;
-  fs_barrier();
-  int buf = 0;   // the buffer holding the current window
 
-  // walks: this wave's row blocks, and the workgroup's longest walk (its wave 0's)
-  const int64_t my_iters = active ? (p.nwork - 1 - w) / nwaves + 1 : 0;
-  const int64_t wg_iters = w0 < p.nwork ? (p.nwork - 1 - w0) / nwaves + 1 : 0;
-
-  if (active) {
-
+  // (the thresholds are loaded before the ring: no load issued ahead of the walk is still pending inside it)
   float tau[G];
 #pragma unroll
   for (int hq = 0; hq < G; ++hq) tau[hq] = p.gtau[hq][lane & 31];
+#pragma unroll
+  for (int hq = 0; hq < G; ++hq) __asm__ volatile("" : "+v"(tau[hq]));   // (loaded here, not sunk into the walk)
+  // the ring's first window, window 0's query units, the ring's second window: the same order of requests as
+  // every later window's
+  u32x4 ring[2 * TS_RING];
+  if (active) {
+    ts_static_for<TS_RING>([&](auto i) { refill(ring[i], i); });
+    advance_fill();
+  }
+  gather(0, 0);
+  if (active) {
+    ts_static_for<TS_RING>([&](auto i) { refill(ring[TS_RING + i], i); });
+    advance_fill();
+    __builtin_amdgcn_s_waitcnt(0x3F70 | TS_RING);   // vmcnt(TS_RING)
+  } else {
+    __builtin_amdgcn_s_waitcnt(0x3F70);   // vmcnt(0)
+  }
+  fs_barrier();
 
   uint32_t keyhi = (uint32_t)wave << 13;   // + (iteration << 16)
 
-  while (true) {
-    const int64_t wn = w + nwaves;
-    const bool has_next = wn < p.nwork;
-    const int64_t blkn = has_next ? (p.blk0 + wn * p.blk_stride) : blk;
-    const u32x4* nxt = base + (size_t)blkn * blk_units;
+  f32x16 acc[G];
+#pragma unroll
+  for (int hq = 0; hq < G; ++hq)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[hq][r] = 0.f;
 
-    f32x16 acc[G];
+  // the walk's window barrier (fs_barrier: vmcnt untouched)
+  auto walk_barrier = [&]() {
+#if defined(TS_TUNING) && defined(DBG_WIDE_NO_BARRIER)   // ablation builds only (wrong results; with TS_DEBUG_TAU_INF=1)
+    __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0)
+#else
+    fs_barrier();
+#endif
+  };
+  // Window t of the wave's walk (k window qw of a row block), ring half and LDS buffer P = t & 1: request the next
+  // window's query units into the other buffer, run the window's TS_RING x G MFMAs and refill the ring half with
+  // window t + 2, wait for the units (vmcnt(TS_RING): this window's ring loads stay in flight) and meet the others
+  // at lgkmcnt(0) + s_barrier.  The other buffer was last read in window t - 1, before the previous barrier.
+  int qw = 0;
+  auto window = [&](auto half) {
+    constexpr int P = decltype(half)::value;
+    const int qn = qw + 1 < nwin ? qw + 1 : 0;
+    gather(qn, P ^ 1);
+    const u32x4* ql = win + P * WU + lane;
+    ts_static_for<TS_RING>([&](auto i) {
+      ring_wait(ring[P * TS_RING + i]);
+#if defined(TS_TUNING) && defined(DBG_WIDE_B2)   // A/B only: the next MFMA's B operand is read before this one issues
+      u32x4 bq = ql[(i * G) * 64];
 #pragma unroll
-    for (int hq = 0; hq < G; ++hq)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[hq][r] = 0.f;
-
-    // one window: k groups [g0, g0 + TS_RING) from buffer `buf`, the ring refilled from `refill`, window `wnext`
-    // requested now and written to the other buffer at the end
-    auto window = [&](const u32x4* refill, int wnext) {
-      gather(wnext);
-      const u32x4* ql = win + buf * WU + lane;
-#pragma unroll
-      for (int i = 0; i < TS_RING; ++i) {
-#pragma unroll
-        for (int hq = 0; hq < G; ++hq) {
-          const u32x4 b = ql[(i * G + hq) * 64];
-          mma_group<DT>(acc[hq], ring[i], b);
-        }
-        ring[i] = stream_load(refill + (size_t)i * 64);
-        __builtin_amdgcn_sched_barrier(0);
+      for (int hq = 0; hq < G; ++hq) {
+        const u32x4 bn = hq + 1 < G ? ql[(i * G + hq + 1) * 64] : bq;
+        mma_group<DT>(acc[hq], ring[P * TS_RING + i], bq);
+        bq = bn;
       }
-      put(buf ^ 1);
-      fs_barrier();
-      buf ^= 1;
-    };
-    // main part: prefetch stays inside the current row block
-    int g0 = 0, wi = 0;
-    for (; g0 < kg - TS_RING; g0 += TS_RING, ++wi) window(cur + (size_t)(g0 + TS_RING) * 64, wi + 1);
-    // tail: the ring is refilled from the start of the wave's next row block; the next window is window 0
-    window(nxt, 0);
-
-    epilogue_multi<G, 8>(p, st, sscore, skey, acc, tau, blk, keyhi, lane);
-
-    if (!has_next) break;
-    w = wn;
-    blk = blkn;
-    cur = nxt;
-    keyhi += 1u << 16;
-  }
-  }  // active
-
-  // the workgroup's other waves are still walking: keep filling windows with them
-  for (int64_t it = my_iters; it < wg_iters; ++it) {
-    for (int wi = 0; wi < nwin; ++wi) {
-      gather(wi + 1 < nwin ? wi + 1 : 0);
-      put(buf ^ 1);
-      fs_barrier();
-      buf ^= 1;
+#else
+#pragma unroll
+      for (int hq = 0; hq < G; ++hq) {
+        const u32x4 b = ql[(i * G + hq) * 64];
+        mma_group<DT>(acc[hq], ring[P * TS_RING + i], b);
+      }
+#endif
+      refill(ring[P * TS_RING + i], i);
+      __builtin_amdgcn_sched_barrier(0);
+    });
+    advance_fill();
+    if (qw == nwin - 1) {   // the row block's last window
+      epilogue_multi<G, 8>(p, st, sscore, skey, acc, tau, blk, keyhi, lane);
+#pragma unroll
+      for (int hq = 0; hq < G; ++hq)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[hq][r] = 0.f;
+      w += nwaves;
+      blk = p.blk0 + w * p.blk_stride;
+      keyhi += 1u << 16;
     }
+    __builtin_amdgcn_s_waitcnt(0x3F70 | TS_RING);   // vmcnt(TS_RING)
+    walk_barrier();
+    qw = qn;
+  };
+  // Ring slots and buffers are compile-time, so the walk goes in pairs of windows (nwin may be odd).  The walk has
+  // no branch between a wave's computing windows: every window's waits see the same two windows of ring loads.
+  int64_t t = 0;
+  for (; t < tw_mine; t += 2) {
+    window(std::integral_constant<int, 0>{});
+    if (t + 1 == tw_mine) { ++t; break; }
+    window(std::integral_constant<int, 1>{});
+  }
+  // The last window's ring loads are still in flight, into registers the compiler now takes as free: nothing that
+  // follows may be written before they land.
+  __builtin_amdgcn_s_waitcnt(0x3F70);   // vmcnt(0)
+  // the workgroup's other waves are still walking: keep filling windows with them
+  for (; t < tw_all; ++t) {
+    const int qn = qw + 1 < nwin ? qw + 1 : 0;
+    gather(qn, (int)(t & 1) ^ 1);
+    __builtin_amdgcn_s_waitcnt(0x3F70);   // vmcnt(0)
+    walk_barrier();
+    qw = qn;
   }
 
   // ---- flush: one global atomic per (workgroup, query) reserves the slots
