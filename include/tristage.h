@@ -66,7 +66,8 @@ enum ts_status {
   TS_ERR_UNSUPPORTED = -5
 };
 
-enum ts_dtype { TS_F32 = 0, TS_F16 = 1, TS_BF16 = 2 };
+enum ts_dtype { TS_F32 = 0, TS_F16 = 1, TS_BF16 = 2,
+               TS_FP8_E4M3 = 3 /* OCP e4m3fn: only the e4m3 token-store entry points below take it */ };
 
 enum ts_metric { TS_METRIC_INNER_PRODUCT = 0 };
 
@@ -303,6 +304,31 @@ int ts_maxsim_indexed_batch(const void* q, const int32_t* q_off, int32_t nq, con
                             const int64_t* starts, const int32_t* lens, const int32_t* cand_off,
                             int32_t H, int32_t dtype, int32_t mode, float* out, int32_t device,
                             void* stream);
+
+/* ---- stage-2 MaxSim over an e4m3 token store (added within ABI version 4: no existing signature changed) ----
+ * The resident token store kept at one byte per element.  Stored format: a document token row x
+ * (H elements) is the H bytes of OCP e4m3fn  e4m3_rne(x * 2^k),  k the largest integer with max|x_i| * 2^k <= 448
+ * (max|x_i| * 2^k in (224, 448]); round to nearest even, e4m3 subnormals kept; a zero row stores zeros; a row with a
+ * NaN or an Inf stores 0x7F in every byte.  k is not stored: the scores are cosines, which a positive per-row
+ * factor does not change.
+ *   ts_quantize_rows_fp8   x [rows, H] of x_dtype (TS_F32 / TS_F16 / TS_BF16) -> out [rows, H] bytes, in that
+ *                          format bit for bit.  H % 16 == 0 and 16-byte aligned x / out, else TS_ERR_UNSUPPORTED.
+ *   ts_maxsim_indexed_fp8, ts_maxsim_indexed_batch_fp8
+ *                          ts_maxsim_indexed / _batch over such a store: the query stays q_dtype (TS_F16 /
+ *                          TS_BF16), the store's bytes are converted in registers (exactly: every e4m3 value is a
+ *                          bf16 and an f16 value), so the scores are the exact cosines of the decoded rows against
+ *                          the query.  H % 16 != 0, or a query image over the kernel's LDS budget (H > 2048 at
+ *                          the time of writing): TS_ERR_UNSUPPORTED — there is no general kernel behind these.
+ *                          Lq >= 1 (q_off strictly increasing where a query has candidates).  Existing entry
+ *                          points keep rejecting dtype TS_FP8_E4M3.                                           */
+int ts_quantize_rows_fp8(const void* x, int32_t x_dtype, int64_t rows, int32_t H, void* out, int32_t device,
+                         void* stream);
+int ts_maxsim_indexed_fp8(const void* q, int32_t q_dtype, int32_t Lq, const void* store, const int64_t* starts,
+                          const int32_t* lens, int32_t n_docs, int32_t H, int32_t mode, float* out, int32_t device,
+                          void* stream);
+int ts_maxsim_indexed_batch_fp8(const void* q, int32_t q_dtype, const int32_t* q_off, int32_t nq, const void* store,
+                                const int64_t* starts, const int32_t* lens, const int32_t* cand_off, int32_t H,
+                                int32_t mode, float* out, int32_t device, void* stream);
 
 /* ---- BM25 (the lexical half of stage 1) ---------------------------------------
  * replaces BM25Index.search (reference src/stage1_retriever.py:103-112, called at

@@ -4,7 +4,8 @@
     python tools/bench_maxsim.py [--docs 1000] [--lq 32] [--hidden 768] [--dtype bf16] [--len-lo 64 --len-hi 192]
 
 Algorithmic bytes per query = (sum(Ld) + Lq) * H * esize: every candidate's
-token rows read once.  Timed with events on the stream the kernels are launched on (torch's
+token rows read once.  --dtype fp8: an e4m3 store (index.quantize_rows_fp8) against a bf16 query,
+sum(Ld) * H * 1 + Lq * H * 2 bytes.  Timed with events on the stream the kernels are launched on (torch's
 current stream is what index.maxsim_indexed passes to the C ABI)."""
 import argparse
 import json
@@ -19,7 +20,7 @@ def main():
     ap.add_argument("--docs", type=int, default=1000)
     ap.add_argument("--lq", type=int, default=32)
     ap.add_argument("--hidden", type=int, default=768)
-    ap.add_argument("--dtype", default="bf16", choices=["bf16", "f16", "f32"])
+    ap.add_argument("--dtype", default="bf16", choices=["bf16", "f16", "f32", "fp8"])
     ap.add_argument("--len-lo", type=int, default=64)
     ap.add_argument("--len-hi", type=int, default=192)
     ap.add_argument("--store-docs", type=int, default=200_000, help="documents in the resident store")
@@ -32,15 +33,24 @@ def main():
                     help="diagnostic: candidates are neighbours in the store (no scattered 2 MiB pages)")
     args = ap.parse_args()
     import torch
-    from tristage_rag_amd.index import maxsim_indexed, maxsim_indexed_batch
-    tdt = {"bf16": torch.bfloat16, "f16": torch.float16, "f32": torch.float32}[args.dtype]
-    esize = 4 if args.dtype == "f32" else 2
+    from tristage_rag_amd.index import maxsim_indexed, maxsim_indexed_batch, quantize_rows_fp8
+    fp8 = args.dtype == "fp8"
+    tdt = {"bf16": torch.bfloat16, "f16": torch.float16, "f32": torch.float32, "fp8": torch.bfloat16}[args.dtype]
+    esize = {"f32": 4, "fp8": 1}.get(args.dtype, 2)   # store bytes per element
+    qsize = 2 if fp8 else esize                        # query bytes per element
     dev = torch.device("cuda", 0)
     g = torch.Generator(device=dev).manual_seed(7)
     lens_all = torch.randint(args.len_lo, args.len_hi + 1, (args.store_docs,), generator=g, device=dev, dtype=torch.int64)
     starts_all = torch.cumsum(lens_all, 0) - lens_all
     rows = int(lens_all.sum().item())
-    store = torch.randn((rows, args.hidden), generator=g, device=dev, dtype=torch.float32).to(tdt)
+    if fp8:   # quantised in slices: no f32 copy of the whole store
+        store = torch.empty((rows, args.hidden), dtype=torch.float8_e4m3fn, device=dev)
+        for r0 in range(0, rows, 1 << 20):
+            r1 = min(rows, r0 + (1 << 20))
+            store[r0:r1].view(torch.uint8).copy_(quantize_rows_fp8(torch.randn(
+                (r1 - r0, args.hidden), generator=g, device=dev, dtype=torch.float32)).view(torch.uint8))
+    else:
+        store = torch.randn((rows, args.hidden), generator=g, device=dev, dtype=torch.float32).to(tdt)
     q = torch.randn((args.lq, args.hidden), generator=g, device=dev, dtype=torch.float32).to(tdt)
     # a different random candidate set per repetition: nothing is cache-resident between queries
     if args.contiguous:
@@ -71,7 +81,7 @@ def main():
             e1.record()
         torch.cuda.synchronize()
         ms = sorted(e0.elapsed_time(e1) for e0, e1 in evs)
-        byts = [(int(l.sum().item()) + nq * args.lq) * args.hidden * esize for _, l in bsets[1:]]
+        byts = [(int(l.sum().item()) * esize + nq * args.lq * qsize) * args.hidden for _, l in bsets[1:]]
         mean_ms, mean_bytes = sum(ms) / len(ms), sum(byts) / len(byts)
         print(json.dumps({"what": "ts_maxsim_indexed_batch, one launch", "queries": nq, "docs_per_query": args.docs,
                           "lq": args.lq, "hidden": args.hidden, "dtype": args.dtype,
@@ -90,7 +100,7 @@ def main():
         e1.record()
     torch.cuda.synchronize()
     ms = sorted(e0.elapsed_time(e1) for e0, e1 in evs)
-    byts = [(int(l.sum().item()) + args.lq) * args.hidden * esize for _, l in sets[3:]]
+    byts = [(int(l.sum().item()) * esize + args.lq * qsize) * args.hidden for _, l in sets[3:]]
     mean_ms = sum(ms) / len(ms)
     mean_bytes = sum(byts) / len(byts)
     print(json.dumps({"what": "ts_maxsim_indexed, all launches of one query", "docs": args.docs, "lq": args.lq,

@@ -17,7 +17,7 @@ CSRC_DIR = os.path.join(_HERE, "csrc")
 
 TS_OK = 0
 TS_ERR_INVALID, TS_ERR_HIP, TS_ERR_OOM, TS_ERR_EMPTY, TS_ERR_UNSUPPORTED = -1, -2, -3, -4, -5
-TS_F32, TS_F16, TS_BF16 = 0, 1, 2
+TS_F32, TS_F16, TS_BF16, TS_FP8_E4M3 = 0, 1, 2, 3
 TS_METRIC_INNER_PRODUCT = 0
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "tristage.h")
 
@@ -90,6 +90,11 @@ SIGNATURES = {
                                     c_int32, c_int32, c_void_p, c_int32, c_void_p]),
     "ts_maxsim_indexed_batch": (c_int32, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                           c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p]),
+    "ts_quantize_rows_fp8": (c_int32, [c_void_p, c_int32, c_int64, c_int32, c_void_p, c_int32, c_void_p]),
+    "ts_maxsim_indexed_fp8": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
+                                        c_int32, c_void_p, c_int32, c_void_p]),
+    "ts_maxsim_indexed_batch_fp8": (c_int32, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
+                                              c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p]),
     "ts_bm25_create": (c_int32, [c_int32, POINTER(c_void_p)]),
     "ts_bm25_destroy": (c_int32, [c_void_p]),
     "ts_bm25_set_index": (c_int32, [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p,

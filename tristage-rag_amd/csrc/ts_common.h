@@ -332,11 +332,16 @@ int ts_launch_tau(const float* sample, int64_t ld, uint32_t n, uint32_t m,
 int ts_launch_maxsim(const void* q, int Lq, const void* docs,
                      const int32_t* doc_off, const int64_t* starts, const int32_t* lens,
                      int n_docs, int H, int dtype, int mode, float* out, hipStream_t stream);
-// HBM-bound streaming form for f16/bf16 token matrices (ts_maxsim16.hip).  Returns
-// TS_ERR_UNSUPPORTED without an error string for shapes it does not take.
+// HBM-bound streaming form for f16/bf16/f32 token matrices and e4m3 token stores (ts_maxsim16.hip).  Returns
+// TS_ERR_UNSUPPORTED without an error string for shapes it does not take.  dtype is the store's element type;
+// q_dtype the query's (< 0: the store's; an e4m3 store takes a TS_F16 / TS_BF16 query).
 int ts_launch_maxsim16(const void* q, int Lq, const void* docs, const int32_t* doc_off,
                        const int64_t* starts, const int32_t* lens, int n_docs, int H, int dtype,
-                       int mode, float* out, int device, hipStream_t stream);
+                       int mode, float* out, int device, hipStream_t stream, int q_dtype = -1);
 int ts_launch_maxsim16_batch(const void* q, const int32_t* q_off, int nq, const void* store,
                              const int64_t* starts, const int32_t* lens, const int32_t* cand_off,
-                             int H, int dtype, int mode, float* out, int device, hipStream_t stream);
+                             int H, int dtype, int mode, float* out, int device, hipStream_t stream,
+                             int q_dtype = -1);
+// rows x H elements of x (x_dtype TS_F32 / TS_F16 / TS_BF16, H % 16 == 0, 16-byte aligned) -> the e4m3 token-store
+// rows of include/tristage.h (ts_fp8.hip)
+int ts_launch_quantize_rows_fp8(const void* x, int x_dtype, int64_t rows, int H, void* out, hipStream_t stream);

@@ -1868,3 +1868,79 @@ extern "C" int ts_maxsim_indexed_batch(const void* q, const int32_t* q_off, int3
   }
   return TS_OK;
 }
+
+// ---- e4m3 token store (include/tristage.h "stage-2 MaxSim over an e4m3 token store")
+static bool fp8_query_dtype_ok(int dt) { return dt == TS_F16 || dt == TS_BF16; }
+
+extern "C" int ts_maxsim_indexed_fp8(const void* q, int32_t q_dtype, int32_t Lq, const void* store,
+                                     const int64_t* starts, const int32_t* lens, int32_t n_docs, int32_t H,
+                                     int32_t mode, float* out, int32_t device, void* stream) {
+  if (!q || !store || !starts || !lens || !out || Lq <= 0 || n_docs < 0 || H <= 0 || !fp8_query_dtype_ok(q_dtype) ||
+      (mode != 0 && mode != 1)) {
+    ts_set_error("bad arguments to maxsim_indexed_fp8");
+    return TS_ERR_INVALID;
+  }
+  if (H % 16 != 0) {
+    ts_set_error("maxsim_indexed_fp8: H = %d is not a multiple of 16", H);
+    return TS_ERR_UNSUPPORTED;
+  }
+  if (n_docs == 0) return TS_OK;
+  DeviceGuard g(device);
+  if (!g.ok) { ts_set_error("hipSetDevice(%d) failed", device); return TS_ERR_HIP; }
+  const int st = ts_launch_maxsim16(q, Lq, store, nullptr, starts, lens, n_docs, H, TS_FP8_E4M3, mode, out,
+                                    device, (hipStream_t)stream, q_dtype);
+  if (st == TS_ERR_UNSUPPORTED)   // (no general kernel behind this one)
+    ts_set_error("maxsim_indexed_fp8: H = %d, Lq = %d is not a shape the streaming kernel takes", H, Lq);
+  return st;
+}
+
+extern "C" int ts_maxsim_indexed_batch_fp8(const void* q, int32_t q_dtype, const int32_t* q_off, int32_t nq,
+                                           const void* store, const int64_t* starts, const int32_t* lens,
+                                           const int32_t* cand_off, int32_t H, int32_t mode, float* out,
+                                           int32_t device, void* stream) {
+  if (!q || !q_off || !store || !starts || !lens || !cand_off || !out || nq < 0 || H <= 0 ||
+      !fp8_query_dtype_ok(q_dtype) || (mode != 0 && mode != 1)) {
+    ts_set_error("bad arguments to maxsim_indexed_batch_fp8");
+    return TS_ERR_INVALID;
+  }
+  for (int j = 0; j < nq; ++j)
+    if (q_off[j + 1] < q_off[j] || cand_off[j + 1] < cand_off[j]) {
+      ts_set_error("maxsim_indexed_batch_fp8: offsets must be non-decreasing");
+      return TS_ERR_INVALID;
+    }
+  if (H % 16 != 0) {
+    ts_set_error("maxsim_indexed_batch_fp8: H = %d is not a multiple of 16", H);
+    return TS_ERR_UNSUPPORTED;
+  }
+  if (nq == 0) return TS_OK;
+  DeviceGuard g(device);
+  if (!g.ok) { ts_set_error("hipSetDevice(%d) failed", device); return TS_ERR_HIP; }
+  const int st = ts_launch_maxsim16_batch(q, q_off, nq, store, starts, lens, cand_off, H, TS_FP8_E4M3, mode, out,
+                                          device, (hipStream_t)stream, q_dtype);
+  if (st != TS_ERR_UNSUPPORTED) return st;
+  // shapes the one-launch form does not take (a query of > 4096 candidates): query by query
+  for (int j = 0; j < nq; ++j) {
+    const int nc = cand_off[j + 1] - cand_off[j];
+    if (nc == 0) continue;
+    TS_CHECK(ts_maxsim_indexed_fp8((const char*)q + (size_t)q_off[j] * H * 2, q_dtype, q_off[j + 1] - q_off[j],
+                                   store, starts + cand_off[j], lens + cand_off[j], nc, H, mode, out + cand_off[j],
+                                   device, stream));
+  }
+  return TS_OK;
+}
+
+extern "C" int ts_quantize_rows_fp8(const void* x, int32_t x_dtype, int64_t rows, int32_t H, void* out,
+                                    int32_t device, void* stream) {
+  if (!x || !out || rows < 0 || H <= 0 || !dtype_ok(x_dtype)) {
+    ts_set_error("bad arguments to quantize_rows_fp8");
+    return TS_ERR_INVALID;
+  }
+  if (H % 16 != 0 || ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) & 15)) {
+    ts_set_error("quantize_rows_fp8: needs H %% 16 == 0 (H = %d) and 16-byte aligned rows", H);
+    return TS_ERR_UNSUPPORTED;
+  }
+  if (rows == 0) return TS_OK;
+  DeviceGuard g(device);
+  if (!g.ok) { ts_set_error("hipSetDevice(%d) failed", device); return TS_ERR_HIP; }
+  return ts_launch_quantize_rows_fp8(x, x_dtype, rows, H, out, (hipStream_t)stream);
+}

@@ -1,6 +1,6 @@
-// Stage-2 MaxSim on gfx950: the HBM-bound streaming form (f16 / bf16 token matrices, and f32
-// ones on the exact-f32 MFMA; rows are addressed in bytes, a k step is 32 bytes of a row — the
-// "16" in the names is the 16-byte operand unit every lane loads).
+// Stage-2 MaxSim on gfx950: the HBM-bound streaming form (f16 / bf16 token matrices, f32 ones on
+// the exact-f32 MFMA, and e4m3 token stores against a bf16 / f16 query; rows are addressed in bytes,
+// a k step is 32 bytes of a row — the "16" in the names is the 16-byte operand unit every lane loads).
 //
 // Same scores as ts_maxsim.hip (reference src/stage2_rescorer.py:167-201 applied to
 // every candidate, loop at :268-276):  for query tokens Q[Lq,H], document tokens D[Ld,H]
@@ -43,6 +43,7 @@ typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 #ifndef M16_THREADS
@@ -52,7 +53,9 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 #define M16_WAVES (M16_THREADS / 64)
 #ifndef M16_RING
 #define M16_RING 16     // k steps (1 KiB each) in the register ring of a wave
-#endif
+#endif                  // (an e4m3 store whose rows are 24 k steps long, H = 768, takes a 24-deep ring: see
+                        // M16_RING_E4M3)
+#define M16_RING_E4M3 24
 #ifndef M16_GROUP
 #define M16_GROUP 8     // ring slots refilled together.  Issuing the loads that share a 128-byte line
                         // set back to back matters: refilling one slot per step (GROUP 1) re-misses
@@ -70,7 +73,7 @@ struct Ms16Params {
   const unsigned char* q;  // [Lq, H] (row_bytes per row)
   int Lq, H;               // H is carried as row_bytes = H * element size: a k step is 32 bytes of a row
                            // (2 x 16-byte operand units) for every element type
-  int s_pad;               // k steps per tile (16 elements each), multiple of M16_RING
+  int s_pad;               // k steps per tile (32 bytes of a row each), multiple of the ring depth
   int lq_pad;              // row stride of `best` (= passes * NQT * 32)
   int passes;              // gridDim.y: query tokens are taken NQT*32 per pass
   const unsigned char* docs;  // [rows, H] row-major
@@ -173,6 +176,31 @@ __device__ __forceinline__ void m16_mma(f32x16& acc, const u32x4& a, const u32x4
     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf8, a), __builtin_bit_cast(bf8, b), acc, 0, 0, 0);
 }
 
+// e4m3 store (DT = TS_FP8_E4M3) against a QT = TS_BF16 / TS_F16 query: a lane's 16-byte unit holds 16 e4m3
+// values, converted in registers into two 8-wide QT operands (every e4m3 value is exact in bf16 and in f16), each
+// the A operand of one 32x32x16 MFMA.  The query image holds M16_UPS<DT> units per k step: unit m of lane (r, h)
+// at k step g is the 16 bytes at byte 64g + 32h + 16m of the query row, i.e. the query's elements
+// 32g + 16h + 8m .. +8 — the same elements the document's operand m carries.
+template <int DT> constexpr int M16_UPS = DT == TS_FP8_E4M3 ? 2 : 1;         // query-image units per k step
+template <int DT, int QT> constexpr int M16_MT = DT == TS_FP8_E4M3 ? QT : DT;  // MFMA operand element type
+template <int QT, bool HI> __device__ __forceinline__ uint32_t m16_cvt_e4m3(uint32_t w) {   // bytes 2HI, 2HI+1 of w
+  if constexpr (QT == TS_F16)
+    return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, 1.0f, HI));
+  else
+    return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, HI));
+}
+template <int DT, int QT>
+__device__ __forceinline__ void m16_decode(const u32x4& a, u32x4 (&o)[M16_UPS<DT>]) {
+  if constexpr (DT == TS_FP8_E4M3) {
+    o[0] = u32x4{m16_cvt_e4m3<QT, false>(a.x), m16_cvt_e4m3<QT, true>(a.x),
+                 m16_cvt_e4m3<QT, false>(a.y), m16_cvt_e4m3<QT, true>(a.y)};
+    o[1] = u32x4{m16_cvt_e4m3<QT, false>(a.z), m16_cvt_e4m3<QT, true>(a.z),
+                 m16_cvt_e4m3<QT, false>(a.w), m16_cvt_e4m3<QT, true>(a.w)};
+  } else {
+    o[0] = a;
+  }
+}
+
 // ---------------------------------------------------------------------------------
 // 16 bytes of this lane's row for k step g (k = 16g + 8h .. +8).  The load is ALWAYS issued
 // (a load under a lane predicate becomes a branch with s_waitcnt vmcnt(0) behind it, which
@@ -273,9 +301,12 @@ extern "C" int ts_debug_m16_trace(unsigned long long* out) {
 #else
 #define M16_STEP(a, g)                                                                          \
   do {                                                                                          \
-    dsq = m16_sumsq<DT>((a), dsq);                                                              \
-    _Pragma("unroll") for (int t = 0; t < NQT; ++t)                                             \
-        m16_mma<DT>(acc[t], (a), ql[(size_t)((g) * NQT + t) * 64]);                             \
+    u32x4 op_[UPS];                                                                             \
+    m16_decode<DT, QT>((a), op_);                                                               \
+    _Pragma("unroll") for (int m = 0; m < UPS; ++m) dsq = m16_sumsq<MT>(op_[m], dsq);          \
+    _Pragma("unroll") for (int m = 0; m < UPS; ++m)                                             \
+      _Pragma("unroll") for (int t = 0; t < NQT; ++t)                                           \
+        m16_mma<MT>(acc[t], op_[m], ql[(size_t)(((g) * NQT + t) * UPS + m) * 64]);              \
   } while (0)
 #endif
 
@@ -283,15 +314,20 @@ extern "C" int ts_debug_m16_trace(unsigned long long* out) {
 // the ring's first loads, the slices are equal); otherwise many queries share the launch, a workgroup's prologue runs
 // beside its neighbours' streaming, and the ring's loads go out first (measured both ways: the single-query order costs
 // the 64-query launch 3-4 %, the batch order costs the single query ~2 us).
-template <int DT, int NQT, bool FULL, bool SINGLE>
+//
+// QT: the query's element type (= DT except for an e4m3 store); RING: k steps in the register ring.
+template <int DT, int NQT, bool FULL, bool SINGLE, int QT = DT, int RING = M16_RING>
 __global__ __launch_bounds__(M16_THREADS) void maxsim16_kernel(Ms16Params pin) {
+  constexpr int UPS = M16_UPS<DT>;
+  constexpr int MT = M16_MT<DT, QT>;
+  static_assert(RING % M16_GROUP == 0, "the ring is refilled M16_GROUP slots at a time");
   Ms16Params p = pin;
   if (pin.nq) {  // one of several queries: narrow every array to this query's part
     const int qj = blockIdx.z;
     const int qa = pin.q_off[qj], ca = pin.cand_off[qj];
     p.Lq = pin.q_off[qj + 1] - qa;
     p.n_docs = pin.cand_off[qj + 1] - ca;
-    p.q = pin.q + (size_t)qa * pin.H;   // (H = row bytes)
+    p.q = pin.q + (size_t)qa * UPS * pin.H;   // (H = row bytes of the store; a query row is UPS times as long)
     p.starts += ca; p.lens += ca; p.out += ca;
     p.cnt += ca;
     p.best += (size_t)ca * pin.lq_pad;
@@ -299,8 +335,8 @@ __global__ __launch_bounds__(M16_THREADS) void maxsim16_kernel(Ms16Params pin) {
     if ((int)blockIdx.y >= p.passes || p.n_docs <= 0) return;  // (uniform for the workgroup)
   }
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  u32x4* qlds = reinterpret_cast<u32x4*>(smem);                                  // [s_pad][NQT][64]
-  float* invl = reinterpret_cast<float*>(smem + (size_t)p.s_pad * NQT * 1024);    // [waves][32]
+  u32x4* qlds = reinterpret_cast<u32x4*>(smem);                                  // [s_pad][NQT][UPS][64]
+  float* invl = reinterpret_cast<float*>(smem + (size_t)p.s_pad * NQT * UPS * 1024);  // [waves][32]
   int32_t* wsum = reinterpret_cast<int32_t*>(invl + M16_WAVES * 32);              // [waves] (+pad to 64 B)
   int32_t* prefix = wsum + 16;                                                    // [n_docs+1]
   const int tid = threadIdx.x;
@@ -309,6 +345,7 @@ __global__ __launch_bounds__(M16_THREADS) void maxsim16_kernel(Ms16Params pin) {
   const int r = lane & 31, h = lane >> 5;
   const int q0 = blockIdx.y * (NQT * 32);  // first query token of this pass
   const int H = p.H;
+  const int QH = UPS * H;   // query row bytes
   const int S = p.s_pad;
 #if defined(TS_TUNING) && defined(M16_TRACE)
   const int gwt = (tid >> 6) * gridDim.x + blockIdx.x;
@@ -387,15 +424,16 @@ __global__ __launch_bounds__(M16_THREADS) void maxsim16_kernel(Ms16Params pin) {
   // first 16 MB of ring loads.  (Round 2 requested it after the ring — complete at 8.3 us, every wave idle on a full
   // ring for ~2 us; through registers before the ring it cost the ring 3 us; parked in registers across the search it
   // made the compiler re-order the ring's refills.  tools/trace_maxsim.py.)  Lanes outside the image's valid part
-  // (query tokens >= Lq, bytes >= H) read 16 zero bytes.
+  // (query tokens >= Lq, bytes >= H) read 16 zero bytes.  (UPS = 2, e4m3 store: unit ((g*NQT + t)*2 + m)*64 + l is the
+  // 16 bytes at byte 64g + 32(l>>5) + 16m of the query row.)
   if constexpr (SINGLE) {
-    const int units = S * NQT * 64;
+    const int units = S * NQT * UPS * 64;
     for (int u0 = wave * 64; u0 < units; u0 += M16_THREADS) {     // (uniform per wave: units is a multiple of 64)
       const int u = u0 + lane;
-      const int l = u & 63, t = (u >> 6) % NQT, g = (u >> 6) / NQT;
-      const int qi = q0 + 32 * t + (l & 31), k = 32 * g + 16 * (l >> 5);   // k: byte offset in the row
-      const bool ok = qi < p.Lq && k < H;
-      const unsigned char* src = ok ? p.q + (size_t)qi * H + k : reinterpret_cast<const unsigned char*>(&m16_zero16);
+      const int l = u & 63, m = (u >> 6) % UPS, t = (u >> 6) / UPS % NQT, g = (u >> 6) / UPS / NQT;
+      const int qi = q0 + 32 * t + (l & 31), k = UPS * (32 * g + 16 * (l >> 5)) + 16 * m;   // k: byte offset in the row
+      const bool ok = qi < p.Lq && k < QH;
+      const unsigned char* src = ok ? p.q + (size_t)qi * QH + k : reinterpret_cast<const unsigned char*>(&m16_zero16);
       // (inline asm, not __builtin_amdgcn_global_load_lds: the compiler's waitcnt pass books the builtin as a pending
       // "flat" access that only a vmcnt(0) it can see clears, and until then turns EVERY vector-memory wait into
       // vmcnt(0) — with the partial wait below that is the tile loop's vmcnt(15..9) ladder, i.e. the ring drained once
@@ -431,20 +469,21 @@ __global__ __launch_bounds__(M16_THREADS) void maxsim16_kernel(Ms16Params pin) {
     start = m16_start_s(p, doc);
   }
   const unsigned char* cur = p.docs;
-  u32x4 ring[M16_RING];
+  u32x4 ring[RING];
   if (has_work) {
     const int rows = min(32, len - tile * 32);
     cur = p.docs + ((size_t)(start + tile * 32 + min(r, rows - 1)) * H + 16 * h);
 #pragma unroll
-    for (int i = 0; i < M16_RING; ++i) ring[i] = m16_load<FULL>(cur, i, h, H);
+    for (int i = 0; i < RING; ++i) ring[i] = m16_load<FULL>(cur, i, h, H);
   }
   M16_STAMP(2);
   if constexpr (SINGLE) {
     // the query image requested above (LDS-DMA) has to be complete, for every wave of the workgroup, before the first
-    // tile is multiplied.  Its requests are OLDER than the ring's M16_RING loads and vmcnt retires in order, so
-    // vmcnt(M16_RING) is exactly "the image has landed" and the ring stays in flight across the barrier.
-    static_assert(M16_RING == 16, "the wait below is vmcnt(16)");
-    if (has_work) __builtin_amdgcn_s_waitcnt(0x4F70);  // vmcnt(16): [3:0] = 0, [15:14] = 1; expcnt/lgkmcnt untouched
+    // tile is multiplied.  Its requests are OLDER than the ring's RING loads and vmcnt retires in order, so
+    // vmcnt(RING) is exactly "the image has landed" and the ring stays in flight across the barrier.
+    static_assert(RING < 64, "vmcnt is 6 bits");
+    constexpr int vm_ring = 0x0F70 | (RING & 15) | ((RING >> 4) << 14);   // vmcnt(RING): [3:0] low bits, [15:14] high
+    if (has_work) __builtin_amdgcn_s_waitcnt(vm_ring);  // (vmcnt(16) = 0x4F70); expcnt/lgkmcnt untouched
     else __builtin_amdgcn_s_waitcnt(0x0F70);           // vmcnt(0): no ring behind the image
     // A bare s_barrier: __syncthreads() (and a workgroup fence, even an LDS-only one) put vmcnt(0) in front of the
     // barrier = the ring drained.  What the barrier orders here is only the image's LDS-DMA writes (complete: the
@@ -457,17 +496,17 @@ __global__ __launch_bounds__(M16_THREADS) void maxsim16_kernel(Ms16Params pin) {
   if constexpr (!SINGLE) {
     // ---- Q image through registers, AFTER the ring's first loads (a launch of many queries: other workgroups stream
     // meanwhile): 8 independent L2 reads in flight per thread (one at a time costs ~1 us each)
-    const int units = S * NQT * 64;
+    const int units = S * NQT * UPS * 64;
     for (int u0 = tid; u0 < units; u0 += 8 * M16_THREADS) {
       u32x4 v[8];
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const int u = u0 + j * M16_THREADS;
-        const int l = u & 63, t = (u >> 6) % NQT, g = (u >> 6) / NQT;
-        const int qi = q0 + 32 * t + (l & 31), k = 32 * g + 16 * (l >> 5);   // k: byte offset in the row
-        const bool ok = u < units && qi < p.Lq && k < H;
+        const int l = u & 63, m = (u >> 6) % UPS, t = (u >> 6) / UPS % NQT, g = (u >> 6) / UPS / NQT;
+        const int qi = q0 + 32 * t + (l & 31), k = UPS * (32 * g + 16 * (l >> 5)) + 16 * m;   // k: byte offset in the row
+        const bool ok = u < units && qi < p.Lq && k < QH;
         // always-issued load from a valid address, zeroed afterwards (no branch around the load)
-        const u32x4 x = *reinterpret_cast<const u32x4*>(p.q + (ok ? (size_t)qi * H + k : 0));
+        const u32x4 x = *reinterpret_cast<const u32x4*>(p.q + (ok ? (size_t)qi * QH + k : 0));
         v[j] = u32x4{ok ? x[0] : 0u, ok ? x[1] : 0u, ok ? x[2] : 0u, ok ? x[3] : 0u};
       }
 #pragma unroll
@@ -496,7 +535,9 @@ __global__ __launch_bounds__(M16_THREADS) void maxsim16_kernel(Ms16Params pin) {
     for (int t = 0; t < NQT; ++t) qsq[t] = 0.f;
     for (int g = 0; g < S; ++g)
 #pragma unroll
-      for (int t = 0; t < NQT; ++t) qsq[t] = m16_sumsq<DT>(ql[(size_t)(g * NQT + t) * 64], qsq[t]);
+      for (int t = 0; t < NQT; ++t)
+#pragma unroll
+        for (int m = 0; m < UPS; ++m) qsq[t] = m16_sumsq<MT>(ql[(size_t)((g * NQT + t) * UPS + m) * 64], qsq[t]);
 #pragma unroll
     for (int t = 0; t < NQT; ++t) {
       qsq[t] += __shfl_xor(qsq[t], 32, 64);
@@ -540,20 +581,20 @@ __global__ __launch_bounds__(M16_THREADS) void maxsim16_kernel(Ms16Params pin) {
     float dsq = 0.f;
 
     int g0 = 0;
-    for (; g0 < S - M16_RING; g0 += M16_RING) {
+    for (; g0 < S - RING; g0 += RING) {
 #pragma unroll
-      for (int i = 0; i < M16_RING; ++i) {
+      for (int i = 0; i < RING; ++i) {
         const u32x4 a = m16_use<FULL>(ring[i], g0 + i, h, H);
         M16_STEP(a, g0 + i);
         if ((i + 1) % M16_GROUP == 0) {  // refill the group of slots just consumed
 #pragma unroll
-          for (int j = i + 1 - M16_GROUP; j <= i; ++j) ring[j] = m16_load<FULL>(cur, g0 + j + M16_RING, h, H);
+          for (int j = i + 1 - M16_GROUP; j <= i; ++j) ring[j] = m16_load<FULL>(cur, g0 + j + RING, h, H);
         }
         __builtin_amdgcn_sched_barrier(0);
       }
     }
 #pragma unroll
-    for (int i = 0; i < M16_RING; ++i) {  // tail: refill from the next tile
+    for (int i = 0; i < RING; ++i) {  // tail: refill from the next tile
       const u32x4 a = m16_use<FULL>(ring[i], g0 + i, h, H);
       M16_STEP(a, g0 + i);
       if ((i + 1) % M16_GROUP == 0 && has_next) {  // (wave-uniform: nothing is read past the slice)
@@ -706,38 +747,98 @@ extern "C" int ts_maxsim_release_scratch(int32_t device) {
   return TS_OK;
 }
 
-template <int DT, int NQT, bool FULL, bool SINGLE>
+template <int DT, int NQT, bool FULL, bool SINGLE, int QT, int RING>
 static int launch_main_s(const Ms16Params& p, int grid, size_t lds, hipStream_t s, int nq) {
-  auto kern = maxsim16_kernel<DT, NQT, FULL, SINGLE>;
+  auto kern = maxsim16_kernel<DT, NQT, FULL, SINGLE, QT, RING>;
   static TsDeviceOnce lds_attr;  // per instantiation, per device (ts_common.h)
   TS_CHECK(ts_allow_max_lds(lds_attr, reinterpret_cast<const void*>(kern)));
   hipLaunchKernelGGL(kern, dim3(grid, p.passes, nq), dim3(M16_THREADS), lds, s, p);
   TS_HIP(hipGetLastError());
   return TS_OK;
 }
-template <int DT, int NQT, bool FULL>
-static int launch_main(const Ms16Params& p, int grid, size_t lds, hipStream_t s, int nq = 1) {
-  return nq <= 1 ? launch_main_s<DT, NQT, FULL, true>(p, grid, lds, s, nq) : launch_main_s<DT, NQT, FULL, false>(p, grid, lds, s, nq);
+template <int DT, int NQT, bool FULL, int QT, int RING>
+static int launch_main(const Ms16Params& p, int grid, size_t lds, hipStream_t s, int nq) {
+  return nq <= 1 ? launch_main_s<DT, NQT, FULL, true, QT, RING>(p, grid, lds, s, nq)
+                 : launch_main_s<DT, NQT, FULL, false, QT, RING>(p, grid, lds, s, nq);
+}
+
+// What a launch looks like for a store of element type `dtype` and rows of H elements, with queries of up to
+// max_lq tokens.  TS_ERR_UNSUPPORTED for shapes the kernel does not take.
+struct M16Shape {
+  int row_bytes;   // bytes of a store row (= Ms16Params::H)
+  int q_row_bytes; // bytes of a query row
+  int ring;        // k steps in the register ring
+  int s_pad, nqt, passes, lq_pad;
+  size_t lds;
+  bool full;       // no k step past the row: unpredicated loads
+};
+static int m16_shape(int H, int dtype, int max_lq, M16Shape& sh) {
+  const int ups = dtype == TS_FP8_E4M3 ? 2 : 1;
+  sh.row_bytes = H * (dtype == TS_F32 ? 4 : dtype == TS_FP8_E4M3 ? 1 : 2);
+  sh.q_row_bytes = ups * sh.row_bytes;
+  if ((sh.row_bytes % 16) != 0) return TS_ERR_UNSUPPORTED;
+  const int s_real = (sh.row_bytes + 31) / 32;
+  // an e4m3 row of 24 k steps (H = 768) would stream 8 padding steps per tile in a 16-deep ring, a third of the
+  // ring's slots re-reading unit 0 instead of bytes that matter: such rows get a 24-deep ring (96 VGPRs)
+  sh.ring = (dtype == TS_FP8_E4M3 && sh.row_bytes % (32 * M16_RING_E4M3) == 0 &&
+             sh.row_bytes % (32 * M16_RING) != 0) ? M16_RING_E4M3 : M16_RING;
+  sh.s_pad = ((s_real + sh.ring - 1) / sh.ring) * sh.ring;
+  const size_t lds_cap = 156 * 1024;
+  const size_t extra = M16_WAVES * 32 * sizeof(float) + 64 + ((size_t)M16_MAX_DOCS + 1) * 4 + 12;
+  const size_t image = (size_t)sh.s_pad * ups * 1024;   // query image bytes per 32 query tokens
+  sh.nqt = (max_lq > 32 && image * 2 + extra <= lds_cap) ? 2 : 1;
+  sh.lds = image * sh.nqt + extra;
+  if (sh.lds > lds_cap) return TS_ERR_UNSUPPORTED;
+  sh.passes = (max_lq + sh.nqt * 32 - 1) / (sh.nqt * 32);
+  sh.lq_pad = sh.passes * sh.nqt * 32;
+  sh.full = (sh.row_bytes % (32 * sh.ring)) == 0;
+  return TS_OK;
+}
+
+template <int DT, int QT, int RING>
+static int m16_go_t(const M16Shape& sh, const Ms16Params& p, int grid, hipStream_t s, int nq) {
+  if constexpr (RING != M16_RING) {   // (chosen only for rows that are whole multiples of the ring)
+    return sh.nqt == 2 ? launch_main<DT, 2, true, QT, RING>(p, grid, sh.lds, s, nq)
+                       : launch_main<DT, 1, true, QT, RING>(p, grid, sh.lds, s, nq);
+  } else if (sh.full) {
+    return sh.nqt == 2 ? launch_main<DT, 2, true, QT, RING>(p, grid, sh.lds, s, nq)
+                       : launch_main<DT, 1, true, QT, RING>(p, grid, sh.lds, s, nq);
+  } else {
+    return sh.nqt == 2 ? launch_main<DT, 2, false, QT, RING>(p, grid, sh.lds, s, nq)
+                       : launch_main<DT, 1, false, QT, RING>(p, grid, sh.lds, s, nq);
+  }
+}
+static int m16_go(const M16Shape& sh, int dtype, int q_dtype, const Ms16Params& p, int grid, hipStream_t s, int nq) {
+  switch (dtype) {
+    case TS_F16: return m16_go_t<TS_F16, TS_F16, M16_RING>(sh, p, grid, s, nq);
+    case TS_BF16: return m16_go_t<TS_BF16, TS_BF16, M16_RING>(sh, p, grid, s, nq);
+    case TS_F32: return m16_go_t<TS_F32, TS_F32, M16_RING>(sh, p, grid, s, nq);
+    default: break;
+  }
+  if (q_dtype == TS_F16)
+    return sh.ring == M16_RING ? m16_go_t<TS_FP8_E4M3, TS_F16, M16_RING>(sh, p, grid, s, nq)
+                               : m16_go_t<TS_FP8_E4M3, TS_F16, M16_RING_E4M3>(sh, p, grid, s, nq);
+  return sh.ring == M16_RING ? m16_go_t<TS_FP8_E4M3, TS_BF16, M16_RING>(sh, p, grid, s, nq)
+                             : m16_go_t<TS_FP8_E4M3, TS_BF16, M16_RING_E4M3>(sh, p, grid, s, nq);
+}
+// the (store, query) element types this kernel takes: a 16-bit or f32 store with a query of its own type, or an
+// e4m3 store with a bf16 / f16 query
+static bool m16_types_ok(int dtype, int q_dtype) {
+  if (dtype == TS_F16 || dtype == TS_BF16 || dtype == TS_F32) return q_dtype == dtype;
+  return dtype == TS_FP8_E4M3 && (q_dtype == TS_F16 || q_dtype == TS_BF16);
 }
 
 // returns TS_ERR_UNSUPPORTED (without setting an error) when the shape is not one this
-// kernel takes; the caller then uses the general kernel of ts_maxsim.hip
+// kernel takes; the caller then uses the general kernel of ts_maxsim.hip (there is none for an e4m3 store)
 int ts_launch_maxsim16(const void* q, int Lq, const void* docs, const int32_t* doc_off,
                        const int64_t* starts, const int32_t* lens, int n_docs, int H, int dtype,
-                       int mode, float* out, int device, hipStream_t stream) {
-  if (dtype != TS_F16 && dtype != TS_BF16 && dtype != TS_F32) return TS_ERR_UNSUPPORTED;
-  const int row_bytes = H * (dtype == TS_F32 ? 4 : 2);
-  if (Lq <= 0 || n_docs <= 0 || (row_bytes % 16) != 0) return TS_ERR_UNSUPPORTED;
+                       int mode, float* out, int device, hipStream_t stream, int q_dtype) {
+  if (q_dtype < 0) q_dtype = dtype;
+  if (!m16_types_ok(dtype, q_dtype)) return TS_ERR_UNSUPPORTED;
+  if (Lq <= 0 || n_docs <= 0) return TS_ERR_UNSUPPORTED;
+  M16Shape sh;
+  if (m16_shape(H, dtype, Lq, sh) != TS_OK) return TS_ERR_UNSUPPORTED;
   if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(docs)) & 15) return TS_ERR_UNSUPPORTED;
-  const int s_real = (row_bytes + 31) / 32;
-  const int s_pad = ((s_real + M16_RING - 1) / M16_RING) * M16_RING;
-  const size_t lds_cap = 156 * 1024;
-  const size_t extra = M16_WAVES * 32 * sizeof(float) + 64 + ((size_t)M16_MAX_DOCS + 1) * 4 + 12;
-  const int nqt = (Lq > 32 && (size_t)s_pad * 2 * 1024 + extra <= lds_cap) ? 2 : 1;
-  const size_t lds = (size_t)s_pad * nqt * 1024 + extra;
-  if (lds > lds_cap) return TS_ERR_UNSUPPORTED;
-  const int passes = (Lq + nqt * 32 - 1) / (nqt * 32);
-  const int lq_pad = passes * nqt * 32;
 
   if (device < 0 || device >= 64) return TS_ERR_UNSUPPORTED;
   if (g_cus[device] == 0) {
@@ -751,18 +852,18 @@ int ts_launch_maxsim16(const void* q, int Lq, const void* docs, const int32_t* d
 #endif
 
   Ms16Params p;
-  p.q = (const unsigned char*)q; p.Lq = Lq; p.H = row_bytes; p.s_pad = s_pad; p.lq_pad = lq_pad; p.passes = passes;
+  p.q = (const unsigned char*)q; p.Lq = Lq; p.H = sh.row_bytes; p.s_pad = sh.s_pad; p.lq_pad = sh.lq_pad;
+  p.passes = sh.passes;
   p.docs = (const unsigned char*)docs; p.mode = mode; p.nq = 0;
   p.eq_slices = 1;
 #ifdef TS_TUNING
   if (getenv("TS_M16_NO_EQ")) p.eq_slices = 0;
 #endif
   const int chunk_max = M16_MAX_DOCS;
-  const size_t cells = (size_t)std::min(n_docs, chunk_max) * (1 + (size_t)lq_pad);
+  const size_t cells = (size_t)std::min(n_docs, chunk_max) * (1 + (size_t)sh.lq_pad);
   std::lock_guard<std::mutex> lk(g_mu);
   void* ws = nullptr;
   TS_CHECK(scratch_get(device, stream, cells * 4, &ws));
-  const bool full = (row_bytes % (32 * M16_RING)) == 0;  // no k step past the row: unpredicated loads
   for (int c0 = 0; c0 < n_docs; c0 += chunk_max) {   // (one launch unless > 4096 candidates)
     const int n = std::min(chunk_max, n_docs - c0);
     p.n_docs = n;
@@ -772,17 +873,7 @@ int ts_launch_maxsim16(const void* q, int Lq, const void* docs, const int32_t* d
     p.out = out + c0;
     p.cnt = (uint32_t*)ws;
     p.best = p.cnt + n;
-#define M16_GO(DT_, NQT_)                                                       \
-  (full ? launch_main<DT_, NQT_, true>(p, grid, lds, stream)                    \
-        : launch_main<DT_, NQT_, false>(p, grid, lds, stream))
-    if (dtype == TS_F16) {
-      if (nqt == 2) TS_CHECK(M16_GO(TS_F16, 2)); else TS_CHECK(M16_GO(TS_F16, 1));
-    } else if (dtype == TS_BF16) {
-      if (nqt == 2) TS_CHECK(M16_GO(TS_BF16, 2)); else TS_CHECK(M16_GO(TS_BF16, 1));
-    } else {
-      if (nqt == 2) TS_CHECK(M16_GO(TS_F32, 2)); else TS_CHECK(M16_GO(TS_F32, 1));
-    }
-#undef M16_GO
+    TS_CHECK(m16_go(sh, dtype, q_dtype, p, grid, stream, 1));
   }
   return TS_OK;
 }
@@ -793,10 +884,14 @@ int ts_launch_maxsim16(const void* q, int Lq, const void* docs, const int32_t* d
 // inside its arguments, 64 queries per launch.
 int ts_launch_maxsim16_batch(const void* q, const int32_t* q_off, int nq, const void* store,
                              const int64_t* starts, const int32_t* lens, const int32_t* cand_off,
-                             int H, int dtype, int mode, float* out, int device, hipStream_t stream) {
-  if (dtype != TS_F16 && dtype != TS_BF16 && dtype != TS_F32) return TS_ERR_UNSUPPORTED;
-  const int row_bytes = H * (dtype == TS_F32 ? 4 : 2);
-  if (nq <= 0 || (row_bytes % 16) != 0) return TS_ERR_UNSUPPORTED;
+                             int H, int dtype, int mode, float* out, int device, hipStream_t stream, int q_dtype) {
+  if (q_dtype < 0) q_dtype = dtype;
+  if (!m16_types_ok(dtype, q_dtype)) return TS_ERR_UNSUPPORTED;
+  if (nq <= 0) return TS_ERR_UNSUPPORTED;
+  {
+    M16Shape sh0;   // (the row-size rule, before the offsets are read)
+    if (m16_shape(H, dtype, 1, sh0) != TS_OK) return TS_ERR_UNSUPPORTED;
+  }
   if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(store)) & 15) return TS_ERR_UNSUPPORTED;
   int max_lq = 0, max_cand = 0;
   for (int j = 0; j < nq; ++j) {
@@ -808,15 +903,8 @@ int ts_launch_maxsim16_batch(const void* q, const int32_t* q_off, int nq, const 
   const int64_t n_pairs = (int64_t)cand_off[nq] - cand_off[0];
   if (n_pairs <= 0) return TS_OK;
   if (q_off[0] != 0 || cand_off[0] != 0) return TS_ERR_UNSUPPORTED;
-  const int s_real = (row_bytes + 31) / 32;
-  const int s_pad = ((s_real + M16_RING - 1) / M16_RING) * M16_RING;
-  const size_t lds_cap = 156 * 1024;
-  const size_t extra = M16_WAVES * 32 * sizeof(float) + 64 + ((size_t)M16_MAX_DOCS + 1) * 4 + 12;
-  const int nqt = (max_lq > 32 && (size_t)s_pad * 2 * 1024 + extra <= lds_cap) ? 2 : 1;
-  const size_t lds = (size_t)s_pad * nqt * 1024 + extra;
-  if (lds > lds_cap) return TS_ERR_UNSUPPORTED;
-  const int passes = (max_lq + nqt * 32 - 1) / (nqt * 32);
-  const int lq_pad = passes * nqt * 32;
+  M16Shape sh;
+  if (m16_shape(H, dtype, max_lq, sh) != TS_OK) return TS_ERR_UNSUPPORTED;
   if (device < 0 || device >= 64) return TS_ERR_UNSUPPORTED;
   if (g_cus[device] == 0) {
     int n = 0;
@@ -830,14 +918,13 @@ int ts_launch_maxsim16_batch(const void* q, const int32_t* q_off, int nq, const 
 #endif
 
   Ms16Params p;
-  p.H = row_bytes; p.s_pad = s_pad; p.lq_pad = lq_pad; p.passes = passes;
+  p.H = sh.row_bytes; p.s_pad = sh.s_pad; p.lq_pad = sh.lq_pad; p.passes = sh.passes;
   p.docs = (const unsigned char*)store; p.doc_off = nullptr; p.mode = mode;
   p.Lq = max_lq; p.n_docs = max_cand;
   p.eq_slices = (nq == 1 && grid == g_cus[device]) ? 1 : 0;   // ONE query in the batch form (RetrievalPipeline.search)
 #ifdef TS_TUNING
   if (getenv("TS_M16_NO_EQ")) p.eq_slices = 0;
 #endif
-  const bool full = (row_bytes % (32 * M16_RING)) == 0;
   std::lock_guard<std::mutex> lk(g_mu);
   for (int j0 = 0; j0 < nq; j0 += M16_MAX_BATCH) {   // (one launch unless > 64 queries)
     const int nb = std::min(M16_MAX_BATCH, nq - j0);
@@ -849,23 +936,13 @@ int ts_launch_maxsim16_batch(const void* q, const int32_t* q_off, int nq, const 
       p.cand_off[j] = cand_off[j0 + j] - ca;
     }
     p.nq = nb;
-    p.q = (const unsigned char*)q + (size_t)qa * row_bytes;
+    p.q = (const unsigned char*)q + (size_t)qa * sh.q_row_bytes;
     p.starts = starts + ca; p.lens = lens + ca; p.out = out + ca;
     void* ws = nullptr;
-    TS_CHECK(scratch_get(device, stream, (size_t)pairs * (1 + (size_t)lq_pad) * 4, &ws));
+    TS_CHECK(scratch_get(device, stream, (size_t)pairs * (1 + (size_t)sh.lq_pad) * 4, &ws));
     p.cnt = (uint32_t*)ws;
     p.best = p.cnt + pairs;
-#define M16_GO(DT_, NQT_)                                                       \
-  (full ? launch_main<DT_, NQT_, true>(p, grid, lds, stream, nb)                \
-        : launch_main<DT_, NQT_, false>(p, grid, lds, stream, nb))
-    if (dtype == TS_F16) {
-      if (nqt == 2) TS_CHECK(M16_GO(TS_F16, 2)); else TS_CHECK(M16_GO(TS_F16, 1));
-    } else if (dtype == TS_BF16) {
-      if (nqt == 2) TS_CHECK(M16_GO(TS_BF16, 2)); else TS_CHECK(M16_GO(TS_BF16, 1));
-    } else {
-      if (nqt == 2) TS_CHECK(M16_GO(TS_F32, 2)); else TS_CHECK(M16_GO(TS_F32, 1));
-    }
-#undef M16_GO
+    TS_CHECK(m16_go(sh, dtype, q_dtype, p, grid, stream, nb));
   }
   return TS_OK;
 }

@@ -671,14 +671,17 @@ def maxsim(q, docs, doc_offsets, mode: str = "maxsim"):
 def maxsim_indexed(q, store, starts, lens, mode: str = "maxsim"):
     """Stage-2 scores for candidates that live in a resident token store: document i
     is rows [starts[i], starts[i]+lens[i]) of ``store`` [rows, H] (CUDA tensors; starts
-    int64, lens int32).  The kernel reads the store in place."""
+    int64, lens int32).  The kernel reads the store in place.  A float8_e4m3fn store (quantize_rows_fp8) is
+    scored against the query in bf16 / f16 (an f32 query goes to bf16)."""
     torch = _torch()
     lib = _lib.load()
+    if not store.is_contiguous():
+        raise ValueError("token store must be contiguous")
+    if _is_fp8(store):   # an e4m3 store: the query stays bf16 / f16
+        return _maxsim_indexed_fp8(q, store, starts, lens, mode)
     if q.dtype != store.dtype:
         q = q.to(store.dtype)
     q = q.contiguous()
-    if not store.is_contiguous():
-        raise ValueError("token store must be contiguous")
     starts = starts.to(device=q.device, dtype=torch.int64).contiguous()
     lens = lens.to(device=q.device, dtype=torch.int32).contiguous()
     n = starts.numel()
@@ -697,12 +700,15 @@ def maxsim_indexed(q, store, starts, lens, mode: str = "maxsim"):
 def maxsim_indexed_batch(q_packed, q_offsets, store, starts, lens, cand_offsets, mode: str = "maxsim"):
     """Stage-2 scores for SEVERAL queries in one launch: query j has tokens
     q_packed[q_offsets[j]:q_offsets[j+1]] and candidates starts/lens[cand_offsets[j]:cand_offsets[j+1]]
-    (rows of the resident token ``store``).  q_offsets / cand_offsets: host int sequences of
-    nq+1 values starting at 0.  Returns float32 [cand_offsets[-1]] on the GPU."""
+    (rows of the resident token ``store``; a float8_e4m3fn store as in maxsim_indexed).  q_offsets / cand_offsets:
+    host int sequences of nq+1 values starting at 0.  Returns float32 [cand_offsets[-1]] on the GPU."""
     import numpy as np
     torch = _torch()
     lib = _lib.load()
-    if q_packed.dtype != store.dtype:
+    fp8 = _is_fp8(store)
+    if fp8:   # an e4m3 store: the query stays bf16 / f16
+        q_packed = q_packed.to(fp8_query_dtype(q_packed.dtype))
+    elif q_packed.dtype != store.dtype:
         q_packed = q_packed.to(store.dtype)
     q_packed = q_packed.contiguous()
     if not store.is_contiguous():
@@ -723,11 +729,104 @@ def maxsim_indexed_batch(q_packed, q_offsets, store, starts, lens, cand_offsets,
     if n == 0 or nq == 0:
         return out
     dev = q_packed.device.index
+    if fp8:
+        _lib.check(lib.ts_maxsim_indexed_batch_fp8(ctypes.c_void_p(q_packed.data_ptr()), _tensor_dtype(q_packed),
+                                                   qo.ctypes.data_as(ctypes.c_void_p), nq,
+                                                   ctypes.c_void_p(store.data_ptr()), ctypes.c_void_p(starts.data_ptr()),
+                                                   ctypes.c_void_p(lens.data_ptr()), co.ctypes.data_as(ctypes.c_void_p),
+                                                   q_packed.shape[1], 0 if mode == "maxsim" else 1,
+                                                   ctypes.c_void_p(out.data_ptr()), dev, ctypes.c_void_p(_stream_ptr(dev))))
+        return out
     _lib.check(lib.ts_maxsim_indexed_batch(ctypes.c_void_p(q_packed.data_ptr()), qo.ctypes.data_as(ctypes.c_void_p), nq,
                                            ctypes.c_void_p(store.data_ptr()), ctypes.c_void_p(starts.data_ptr()),
                                            ctypes.c_void_p(lens.data_ptr()), co.ctypes.data_as(ctypes.c_void_p),
                                            q_packed.shape[1], _tensor_dtype(q_packed), 0 if mode == "maxsim" else 1,
                                            ctypes.c_void_p(out.data_ptr()), dev, ctypes.c_void_p(_stream_ptr(dev))))
+    return out
+
+
+# ---- e4m3 token store (include/tristage.h) --------------------------------------------------
+FP8_STORE_MAX_H = 2048   # the largest H whose query image fits the streaming kernel's LDS budget (at H % 16 == 0)
+
+
+def fp8_store_supported(H: int) -> bool:
+    """Whether the e4m3-store MaxSim kernel takes rows of H elements (there is no general kernel behind it)."""
+    return H > 0 and H % 16 == 0 and H <= FP8_STORE_MAX_H
+
+
+def _is_fp8(t) -> bool:
+    return t.dtype == _torch().float8_e4m3fn
+
+
+def quantize_rows_fp8_reference(x):
+    """The stored format of an e4m3 token store, in plain torch on the CPU: row x -> e4m3_rne(x * 2^k), k the largest
+    integer with max|x_i| * 2^k <= 448 (taken from the exponent of max|x_i|, exact at powers of two), e4m3 subnormals
+    kept; a zero row stores zeros, a row with a NaN or an Inf stores NaN (0x7F) in every element.  k is not kept: the
+    stage-2 scores are cosines, which no positive per-row factor changes.  x [rows, H] of f32 / f16 / bf16 ->
+    float8_e4m3fn [rows, H] on the CPU."""
+    torch = _torch()
+    x = x.detach().to("cpu", torch.float32)
+    if x.dim() != 2:
+        raise ValueError("quantize_rows_fp8: x must be [rows, H]")
+    bad = ~torch.isfinite(x).all(dim=1)
+    m = x.abs().amax(dim=1) if x.shape[1] else torch.zeros(x.shape[0])
+    mant, e = torch.frexp(m)                      # m = mant * 2^e, mant in [0.5, 1); 448 = 0.875 * 2^9
+    k = torch.where(mant <= 0.875, 9 - e, 8 - e)
+    k = torch.where((m == 0) | bad, torch.zeros_like(k), k)
+    # x * 2^k is exact in float64 (|k| <= 158) and, wherever it can round to a non-zero e4m3 value, in float32 too
+    y = (x.double() * torch.pow(2.0, k.double()).unsqueeze(1)).float()
+    y[bad] = 0.0
+    q = y.to(torch.float8_e4m3fn)
+    q.view(torch.uint8)[bad] = 0x7F
+    return q
+
+
+def quantize_rows_fp8(x):
+    """Rows -> the e4m3 token-store format (see quantize_rows_fp8_reference, which it equals bit for bit): the
+    ts_quantize_rows_fp8 kernel for a GPU tensor, the torch reference for a CPU one.  x [rows, H] f32 / f16 / bf16."""
+    torch = _torch()
+    if x.dim() != 2:
+        raise ValueError("quantize_rows_fp8: x must be [rows, H]")
+    if not x.is_cuda:
+        return quantize_rows_fp8_reference(x)
+    lib = _lib.load()
+    rows, H = int(x.shape[0]), int(x.shape[1])
+    if H % 16 != 0:
+        raise ValueError(f"quantize_rows_fp8: H = {H} is not a multiple of 16")
+    x = x.contiguous()
+    if x.data_ptr() % 16:
+        x = x.clone()
+    out = torch.empty((rows, H), dtype=torch.float8_e4m3fn, device=x.device)
+    if rows == 0:
+        return out
+    dev = x.device.index
+    _lib.check(lib.ts_quantize_rows_fp8(ctypes.c_void_p(x.data_ptr()), _tensor_dtype(x), rows, H,
+                                        ctypes.c_void_p(out.data_ptr()), dev, ctypes.c_void_p(_stream_ptr(dev))))
+    return out
+
+
+def fp8_query_dtype(q_dtype):
+    """The type a query keeps against an e4m3 store: its own if bf16 / f16, else bf16 (it is never quantised)."""
+    torch = _torch()
+    return q_dtype if q_dtype in (torch.float16, torch.bfloat16) else torch.bfloat16
+
+
+def _maxsim_indexed_fp8(q, store, starts, lens, mode):
+    torch = _torch()
+    lib = _lib.load()
+    q = q.to(fp8_query_dtype(q.dtype)).contiguous()
+    starts = starts.to(device=q.device, dtype=torch.int64).contiguous()
+    lens = lens.to(device=q.device, dtype=torch.int32).contiguous()
+    n = starts.numel()
+    out = torch.empty((n,), dtype=torch.float32, device=q.device)
+    if n == 0:
+        return out
+    dev = q.device.index
+    _lib.check(lib.ts_maxsim_indexed_fp8(ctypes.c_void_p(q.data_ptr()), _tensor_dtype(q), q.shape[0],
+                                         ctypes.c_void_p(store.data_ptr()), ctypes.c_void_p(starts.data_ptr()),
+                                         ctypes.c_void_p(lens.data_ptr()), n, q.shape[1],
+                                         0 if mode == "maxsim" else 1, ctypes.c_void_p(out.data_ptr()), dev,
+                                         ctypes.c_void_p(_stream_ptr(dev))))
     return out
 
 

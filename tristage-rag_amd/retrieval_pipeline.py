@@ -70,7 +70,7 @@ class PipelineConfig:
     stage2_cache_document_embeddings: bool = False
     stage2_precompute_document_embeddings: bool = False  # token store filled by add_documents
     use_hip_graphs: bool = False             # query forwards of stages 1/2 and a query's stage-3 pairs replayed from HIP graphs
-    stage2_token_store_dtype: str = "auto"   # "auto": bf16 under AMP, else the encoder's output type; or bf16 | f16 | f32
+    stage2_token_store_dtype: str = "auto"   # "auto": bf16 under AMP, else the encoder's output type; or bf16 | f16 | f32 | fp8
     amp_dtype: str = "bf16"                     # what stage*_use_fp16 means on the GPU: "bf16" (BASELINE configs[2]) or "fp16"
                                                 # (what torch.cuda.amp.autocast() gives the reference on a GPU)
     stage1_index_batch_size: int = 256          # documents per encoder forward at add_documents time (stage 1, device path)
@@ -539,6 +539,7 @@ class RetrievalPipeline:
             info["stage1_stats"] = self.stage1.get_stats()
         if self.stage2:
             info["stage2_info"] = self.stage2.get_model_info()
+            info["stage2_token_store_dtype"] = info["stage2_info"].get("token_store_dtype")
         if self.stage3:
             info["stage3_info"] = self.stage3.get_model_info()
         return info

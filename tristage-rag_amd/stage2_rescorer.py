@@ -42,12 +42,24 @@ class Stage2Config:
     precompute_document_embeddings: bool = False  # resident token store filled at add time
     token_store_dtype: str = "auto"               # storage type of the resident token store: "auto" = bf16 when the
                                                   # encoder runs under AMP (its last LayerNorm hands back fp32 even
-                                                  # then), else the encoder's own output type; or "bf16" | "f16" | "f32"
+                                                  # then), else the encoder's own output type; or "bf16" | "f16" | "f32",
+                                                  # or "fp8": OCP e4m3 rows, one byte per element,
+                                                  # scored against the bf16 / f16 query
     use_hip_graph: bool = False                   # replay the batch-1 query forward from a HIP graph
     amp_dtype: str = "bf16"                       # what use_fp16 means on the GPU: "bf16" or "fp16" (the reference's autocast)
     index_batch_size: int = 256                   # documents per forward wherever MANY documents are encoded: filling the
                                                   # token store at add time, re-encoding a query's candidates without one
                                                   # (batch_size, the reference's 16, keeps both launch-bound)
+
+
+TOKEN_STORE_FORMAT = "tristage-rag_amd/token-store/1"          # rows of bf16 / f16 / f32
+TOKEN_STORE_FORMAT_FP8 = "tristage-rag_amd/token-store-fp8/1"  # rows of e4m3 (index.quantize_rows_fp8)
+
+
+def _as_bytes(t: torch.Tensor) -> torch.Tensor:
+    """An e4m3 tensor as its bytes (copies of float8 tensors go through uint8 views: nothing depends on a float8
+    kernel of the backend)."""
+    return t.view(torch.uint8) if t.dtype == torch.float8_e4m3fn else t
 
 
 class TokenStore:
@@ -76,11 +88,11 @@ class TokenStore:
             cap = max(self.rows + add, int(1.5 * (self.data.shape[0] if self.data is not None else 0)), 1024)
             new = torch.empty((cap, H), dtype=mats[0].dtype, device=mats[0].device)
             if self.data is not None and self.rows:
-                new[: self.rows].copy_(self.data[: self.rows])
+                _as_bytes(new[: self.rows]).copy_(_as_bytes(self.data[: self.rows]))
             self.data = new
         for m in mats:
             n = int(m.shape[0])
-            self.data[self.rows: self.rows + n].copy_(m)
+            _as_bytes(self.data[self.rows: self.rows + n]).copy_(_as_bytes(m))
             self.starts.append(self.rows)
             self.lens.append(n)
             self.rows += n
@@ -95,9 +107,9 @@ class TokenStore:
             cap = max(self.rows + add, int(1.5 * (self.data.shape[0] if self.data is not None else 0)), 1024)
             new = torch.empty((cap, int(rows.shape[1])), dtype=rows.dtype, device=rows.device)
             if self.data is not None and self.rows:
-                new[: self.rows].copy_(self.data[: self.rows])
+                _as_bytes(new[: self.rows]).copy_(_as_bytes(self.data[: self.rows]))
             self.data = new
-        self.data[self.rows: self.rows + add].copy_(rows)
+        _as_bytes(self.data[self.rows: self.rows + add]).copy_(_as_bytes(rows))
         at = self.rows
         for n in lens:
             self.starts.append(at)
@@ -290,7 +302,16 @@ class ColBERTScorer:
         name = self.config.token_store_dtype
         if name == "auto":
             return self._amp_dtype() if self.use_amp else None
-        return {"bf16": torch.bfloat16, "f16": torch.float16, "f32": torch.float32}[name]
+        return {"bf16": torch.bfloat16, "f16": torch.float16, "f32": torch.float32, "fp8": torch.float8_e4m3fn}[name]
+
+    def _query_dtype(self, q_dtype: torch.dtype) -> torch.dtype:
+        """What a query is scored in against the resident store: the store's type, except that an e4m3 store keeps the
+        query in bf16 / f16 (an f32 query goes to bf16) — the query is never quantised."""
+        dt = self.token_store.data.dtype
+        if dt == torch.float8_e4m3fn:
+            from .index import fp8_query_dtype
+            return fp8_query_dtype(q_dtype)
+        return dt
 
     def index_documents(self, documents: List[str], first_doc_id: int) -> None:
         """Encode `documents` once and keep their token matrices on the GPU; document j
@@ -308,7 +329,14 @@ class ColBERTScorer:
             hidden = self._forward(enc)
             mask = enc["attention_mask"].bool()
             rows = hidden[mask]                                  # [sum(lens), H]
-            if dt is not None and rows.dtype != dt:
+            if dt == torch.float8_e4m3fn:
+                # the encoder's rows as they come (fp32 from its last LayerNorm), quantised once: no bf16 rounding first
+                from .index import fp8_store_supported, quantize_rows_fp8
+                if not fp8_store_supported(int(rows.shape[1])):
+                    raise ValueError(f"token_store_dtype='fp8' needs H % 16 == 0 and H <= 2048; this encoder has "
+                                     f"H = {int(rows.shape[1])}")
+                rows = quantize_rows_fp8(rows)
+            elif dt is not None and rows.dtype != dt:
                 rows = rows.to(dt)
             base = len(self.token_store)
             self.token_store.append_packed(rows, mask.sum(dim=1).tolist())
@@ -324,24 +352,30 @@ class ColBERTScorer:
         from safetensors.torch import save_file
         st = self.token_store
         ids = sorted(self._store_slot, key=self._store_slot.get)
+        fp8 = st.data.dtype == torch.float8_e4m3fn
         save_file({"tokens": st.data[: st.rows].contiguous().cpu(),
                    "starts": torch.tensor(st.starts, dtype=torch.int64),
                    "lens": torch.tensor(st.lens, dtype=torch.int32),
                    "doc_ids": torch.tensor(ids, dtype=torch.int64)}, path,
-                  metadata={"format": "tristage-rag_amd/token-store/1", "model": str(self.config.model_name),
+                  metadata={"format": TOKEN_STORE_FORMAT_FP8 if fp8 else TOKEN_STORE_FORMAT,
+                            "model": str(self.config.model_name),
                             "max_seq_length": str(self.config.max_seq_length)})
         return True
 
     def load_token_store(self, path: str, expected_docs: Optional[int] = None) -> bool:
         """Restore what save_token_store wrote.  False (store left empty) when the file is absent,
-        was produced by another model / sequence length, or does not cover `expected_docs`."""
+        was produced by another model / sequence length, or does not cover `expected_docs`.  An e4m3 file
+        (TOKEN_STORE_FORMAT_FP8) loads only into an fp8-configured scorer; an fp8-configured scorer given a
+        16/32-bit file quantises its rows on load (the migration path: no re-encode)."""
         import os
         if not os.path.exists(path):
             return False
         from safetensors import safe_open
         with safe_open(path, framework="pt", device="cpu") as f:
             meta = f.metadata() or {}
-            if (meta.get("format") != "tristage-rag_amd/token-store/1" or meta.get("model") != str(self.config.model_name)
+            want_fp8 = self.config.token_store_dtype == "fp8"
+            ok_formats = (TOKEN_STORE_FORMAT, TOKEN_STORE_FORMAT_FP8) if want_fp8 else (TOKEN_STORE_FORMAT,)
+            if (meta.get("format") not in ok_formats or meta.get("model") != str(self.config.model_name)
                     or meta.get("max_seq_length") != str(self.config.max_seq_length)):
                 return False
             lens = f.get_tensor("lens")
@@ -350,6 +384,11 @@ class ColBERTScorer:
             tokens, starts, ids = f.get_tensor("tokens"), f.get_tensor("starts"), f.get_tensor("doc_ids")
         st = TokenStore()
         st.data = tokens.to(self.device)
+        if want_fp8 and st.data.dtype != torch.float8_e4m3fn:
+            from .index import fp8_store_supported, quantize_rows_fp8
+            if not fp8_store_supported(int(st.data.shape[1])):
+                return False
+            st.data = quantize_rows_fp8(st.data)
         st.rows = int(tokens.shape[0])
         st.starts, st.lens = [int(x) for x in starts.tolist()], [int(x) for x in lens.tolist()]
         self.token_store = st
@@ -366,7 +405,8 @@ class ColBERTScorer:
             return None
         starts_all, lens_all = self.token_store.device_tables()
         sel = torch.tensor(slots, dtype=torch.int64, device=starts_all.device)
-        q = query_embeddings.squeeze(0).to(self.token_store.data.dtype).contiguous()
+        q = query_embeddings.squeeze(0)
+        q = q.to(self._query_dtype(q.dtype)).contiguous()
         fn = self._maxsim_indexed_fn
         if fn is None:
             from .index import maxsim_indexed  # HIP kernel; raises without the library or a GPU
@@ -440,7 +480,7 @@ class ColBERTScorer:
         q_embs = self.encode_queries_batch(list(queries))
         store = self.token_store
         starts_all, lens_all = store.device_tables()
-        dt = store.data.dtype
+        dt = self._query_dtype(q_embs[0].dtype)
         q_off, c_off = [0], [0]
         for e, sl in zip(q_embs, slots_list):
             q_off.append(q_off[-1] + int(e.shape[0]))
@@ -519,7 +559,7 @@ class ColBERTScorer:
             sel = slots.clamp(min=0).reshape(-1)
         q_embs = self._query_embeddings(queries)
         starts_all, lens_all = store.device_tables()
-        dt = store.data.dtype
+        dt = self._query_dtype(q_embs[0].dtype)
         q_off, c_off = [0], [0]
         for e, c in zip(q_embs, counts):
             q_off.append(q_off[-1] + int(e.shape[0]))
@@ -602,7 +642,16 @@ class ColBERTScorer:
                 "max_seq_length": self.config.max_seq_length, "use_fp16": self.use_amp,
                 "pooling_method": self.config.pooling_method, "scoring_method": self.config.scoring_method,
                 "batch_size": self.config.batch_size,
-                "embedding_dim": self.model.config.hidden_size if self.model else None}
+                "embedding_dim": self.model.config.hidden_size if self.model else None,
+                "token_store_dtype": self._token_store_dtype_name()}
+
+    def _token_store_dtype_name(self) -> Optional[str]:
+        """The resident store's element type ("bf16" | "f16" | "f32" | "fp8"), or what it will be (None: the
+        encoder's own output type) while it is empty."""
+        names = {torch.bfloat16: "bf16", torch.float16: "f16", torch.float32: "f32", torch.float8_e4m3fn: "fp8"}
+        st = self.token_store
+        dt = st.data.dtype if st.data is not None else self.store_dtype()
+        return names.get(dt, str(dt)) if dt is not None else None
 
     def clear_gpu_memory(self):
         """The reference calls torch.cuda.empty_cache() after every query
