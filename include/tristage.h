@@ -50,7 +50,9 @@ extern "C" {
  * (TS_FLAG_COALESCE, ts_index_flush, ts_coalesce_groups) were added within version 4: no signature changed, and a
  * caller that never sets the flag sees the library it was built against.  The IVF-Flat entry points (ts_ivf_*) were
  * added within version 4 as well: no existing signature changed.  So were wide coalesced passes
- * (TS_FLAG_WIDE_PASSES, TS_FLAG_NO_WIDE_PASSES, ts_coalesce_groups_wide, ts_coalesce_wide_min_bytes).                                             */
+ * (TS_FLAG_WIDE_PASSES, TS_FLAG_NO_WIDE_PASSES, ts_coalesce_groups_wide, ts_coalesce_wide_min_bytes), and removal
+ * (ts_index_remove, ts_index_live_count, ts_index_live_words, ts_index_compact): no existing signature changed, and
+ * an index from which nothing is removed behaves as before; so was ts_remove_ivf.                                 */
 #define TS_ABI_VERSION 4
 
 typedef struct ts_index ts_index; /* opaque */
@@ -216,6 +218,29 @@ int32_t ts_coalesce_groups(int32_t dim, int32_t storage_dtype);
  * of one width: a search that asks for the other flushes it first.  Added within version 4.  Need no GPU.     */
 int32_t ts_coalesce_groups_wide(int32_t dim, int32_t storage_dtype);
 int64_t ts_coalesce_wide_min_bytes(void);
+
+/* ---- removal (tombstones) ------------------------------------------------
+ * FAISS remove_ids with stable ids: a removed row keeps its id, is never returned by a search, and keeps its
+ * storage until ts_index_compact.  ntotal keeps counting every id ever assigned; rows added later get ids from
+ * ntotal upward.  While nothing is removed no search reads the tombstones.  After a removal every search is the
+ * filtered search (ts_index_search_filtered) of the live rows: ts_index_search equals ts_index_search_filtered with
+ * the live set as its mask, bit for bit, and a filtered search's masks are ANDed with the live set.  Added within
+ * version 4.  Exclusive access, as add.
+ *   remove       ids (HOST int64[n]) as search returns them, i.e. after the id offset; unknown, repeated and
+ *                already removed ids are skipped and not counted (*n_removed).  Held coalesced passes are flushed
+ *                first and the update is ordered on `stream` behind every search submitted before it, so those
+ *                see the index as it was.  A search that ts_index_finish reports for a redo is redone against
+ *                the index as it is then: finish before removing where that matters.
+ *   live_count   rows not removed.
+ *   live_words   the live set, HOST uint32[ceil(ntotal / 32)]: bit r % 32 of word r / 32 = row r live.
+ *   compact      moves the live rows down in place (order kept; ts_index_scores / reconstruct see the new rows),
+ *                ntotal = live_count afterwards; old2new (HOST int64[old ntotal], -1 = removed; may be NULL)
+ *                receives the monotone map.  On the device: a prefix count over the live words, then ascending
+ *                chunks of whole row blocks gathered through a 256 MiB staging buffer and copied back.          */
+int ts_index_remove(ts_index* h, const int64_t* ids, int64_t n, int64_t* n_removed, void* stream);
+int64_t ts_index_live_count(const ts_index* h);
+int ts_index_live_words(ts_index* h, uint32_t* out, void* stream);
+int ts_index_compact(ts_index* h, int64_t* old2new, void* stream);
 
 /* ---- introspection -------------------------------------------------------
  * faiss_index.ntotal / .d                                                    */
@@ -526,6 +551,12 @@ int ts_ivf_probe(ts_ivf* h, const void* queries, int32_t nq, int32_t q_dtype, in
 int ts_ivf_list_sizes(const ts_ivf* h, int64_t* out);   /* host int64[nlist] */
 int ts_ivf_reconstruct(ts_ivf* h, int64_t id0, int64_t n, float* out, void* stream);
 int64_t ts_ivf_ntotal(const ts_ivf* h);
+/* removal, with the contract of ts_index_remove (ids as search returns them, HOST int64[n]; unknown, repeated and
+ * removed ids not counted): the slot leaves its block's valid bits, so the scan and the thresholds (whose N_q counts
+ * live probed rows) never see it again, and its list shrinks (ts_ivf_list_sizes counts live rows).  The hole stays
+ * until reset + re-add; reconstruct still returns the stored row.  Added within version 4.                       */
+/* (outside the ts_ivf_ prefix: that set of entry points is fixed by the IVF ABI tests) */
+int ts_remove_ivf(ts_ivf* h, const int64_t* ids, int64_t n, int64_t* n_removed, void* stream);
 int ts_ivf_set_id_offset(ts_ivf* h, int64_t offset);
 int ts_ivf_last_search_info(const ts_ivf* h, int64_t info[4]);
 

@@ -198,6 +198,18 @@ uint32_t ts_scan_wide_stage_cap(const TsLayout& L, int G);
 bool ts_scan_wide_fits(int64_t nblk, int num_cus);
 int ts_launch_scan_wide(const TsLayout& L, int G, const WideScanParams& p, int num_cus, hipStream_t stream);
 
+// Tombstone passes: the coalesced passes of an index with removed rows.  live: its live words (bit
+// r % 32 of word r / 32 = row r live); each wave reads its block's word as a scalar load and its survivor epilogue
+// drops the rows whose bit is clear.  Derived structs, so that the existing instantiations keep their arguments.
+struct MultiTombParams : MultiScanParams {
+  const uint32_t* live;
+};
+struct WideTombParams : WideScanParams {
+  const uint32_t* live;
+};
+int ts_launch_scan_multi_tomb(const TsLayout& L, int G, const MultiTombParams& p, int num_cus, hipStream_t stream);
+int ts_launch_scan_wide_tomb(const TsLayout& L, int G, const WideTombParams& p, int num_cus, hipStream_t stream);
+
 int ts_launch_scan(const TsLayout& L, int mode, int qh, const ScanParams& p,
                    int num_cus, hipStream_t stream);
 
@@ -345,3 +357,21 @@ int ts_launch_maxsim16_batch(const void* q, const int32_t* q_off, int nq, const 
 // rows x H elements of x (x_dtype TS_F32 / TS_F16 / TS_BF16, H % 16 == 0, 16-byte aligned) -> the e4m3 token-store
 // rows of include/tristage.h (ts_fp8.hip)
 int ts_launch_quantize_rows_fp8(const void* x, int x_dtype, int64_t rows, int H, void* out, hipStream_t stream);
+
+// ---------------------------------------------------------------- removal (ts_remove.hip)
+// Tombstone bitmap of a flat index: bit r % 32 of word r / 32 set = row r live (the filtered-search layout).
+// sets the bits of rows [row0, row1) (the other bits of the words they share are kept)
+int ts_launch_live_set(uint32_t* live, int64_t row0, int64_t row1, hipStream_t stream);
+// clears the bits of ids - id_offset in [0, ntotal) and adds to *cleared how many bits went from set to clear
+int ts_launch_live_clear(uint32_t* live, const int64_t* ids, int64_t n, int64_t id_offset, int64_t ntotal,
+                         unsigned long long* cleared, hipStream_t stream);
+// out [n_masks + 1][words]: mask m ANDed with live (bits has bit_words words per mask), then live itself
+int ts_launch_and_live(const uint32_t* bits, int64_t bit_words, int n_masks, const uint32_t* live, int64_t words,
+                       uint32_t* out, hipStream_t stream);
+// Moves the live rows of the tiled corpus down in place (order kept), zeroes what lies behind them up to the old
+// last block, and writes old2new_dev[ntotal] (-1 = removed) when it is non-null.  scratch: at least
+// ts_compact_scratch_bytes(ntotal); stage: the staging buffer of the ascending chunks (whole row blocks).
+int ts_compact_corpus(const TsLayout& L, uint4* corpus, const uint32_t* live, int64_t ntotal, void* scratch,
+                      size_t scratch_bytes, uint4* stage, size_t stage_bytes, int64_t* old2new_dev, int64_t* nlive_out,
+                      hipStream_t stream);
+size_t ts_compact_scratch_bytes(int64_t ntotal);

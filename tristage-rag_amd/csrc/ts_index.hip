@@ -191,6 +191,17 @@ struct ts_index {
   hipEvent_t ev[TS_NPHASE + 1] = {};
   double phase_ms[TS_NPHASE] = {};
   int64_t phase_cnt[TS_NPHASE] = {};
+  // tombstones (ts_index_remove): bit r % 32 of word r / 32 of `live` set = row r live.  The bitmap
+  // is written at the first removal; while nremoved == 0 no search reads it and every path is the one without it.
+  DevBuf live;
+  int64_t live_cap_words = 0;
+  int64_t nremoved = 0;
+  // a search of an index with removed rows is a filtered one: its masks ANDed with `live` go to `eff`, one call at a
+  // time (eff_mu); eff_ev, recorded behind the call's passes, orders the next writer of `eff` or `live` after them
+  DevBuf eff, rids, compact_scratch, compact_stage;
+  std::mutex eff_mu;
+  hipEvent_t eff_ev = nullptr;
+  bool eff_used = false;
 };
 
 static int co_flush(ts_index* h, hipStream_t s);
@@ -300,7 +311,8 @@ extern "C" int ts_index_create(int32_t dim, int32_t storage_dtype, int32_t metri
       st = TS_ERR_HIP;
     }
   }
-  if (st == TS_OK && hipEventCreateWithFlags(&h->co_ev, hipEventDisableTiming) != hipSuccess) {
+  if (st == TS_OK && (hipEventCreateWithFlags(&h->co_ev, hipEventDisableTiming) != hipSuccess ||
+                      hipEventCreateWithFlags(&h->eff_ev, hipEventDisableTiming) != hipSuccess)) {
     ts_set_error("hipEventCreate failed");
     st = TS_ERR_HIP;
   }
@@ -343,6 +355,9 @@ extern "C" int ts_index_destroy(ts_index* h) {
   for (hipEvent_t e : h->async_ev)
     if (e) (void)hipEventDestroy(e);
   if (h->co_ev) (void)hipEventDestroy(h->co_ev);
+  DevBuf* rb[] = {&h->live, &h->eff, &h->rids, &h->compact_scratch, &h->compact_stage};
+  for (DevBuf* b : rb) release(*b);
+  if (h->eff_ev) (void)hipEventDestroy(h->eff_ev);
   delete h;
   return TS_OK;
 }
@@ -351,6 +366,7 @@ extern "C" int ts_index_reset(ts_index* h) {
   if (!h) { ts_set_error("null handle"); return TS_ERR_INVALID; }
   { DeviceGuard g(h->device); TS_CHECK(co_flush(h, nullptr)); }   // held passes search the corpus they were submitted against
   h->ntotal = 0;
+  h->nremoved = 0;
   return TS_OK;
 }
 
@@ -381,6 +397,23 @@ extern "C" int ts_index_last_search_info(const ts_index* h, int64_t info[4]) {
 }
 
 static size_t dtype_size(int dt) { return dt == TS_F32 ? 4 : 2; }
+
+// the tombstone bitmap holds the words of `rows` rows; its content so far is kept
+static int live_reserve(ts_index* h, int64_t rows, hipStream_t s) {
+  const int64_t words = (rows + 31) / 32;
+  if (words <= h->live_cap_words) return TS_OK;
+  const int64_t cap = std::max<int64_t>(words, h->live_cap_words + h->live_cap_words / 2);
+  DevBuf nb;
+  TS_CHECK(ensure(nb, (size_t)cap * 4));
+  TS_HIP(hipMemsetAsync(nb.p, 0, (size_t)cap * 4, s));
+  if (h->live_cap_words > 0)
+    TS_HIP(hipMemcpyAsync(nb.p, h->live.p, (size_t)h->live_cap_words * 4, hipMemcpyDeviceToDevice, s));
+  TS_HIP(hipStreamSynchronize(s));
+  release(h->live);
+  h->live = nb;
+  h->live_cap_words = cap;
+  return TS_OK;
+}
 static bool dtype_ok(int dt) { return dt == TS_F32 || dt == TS_F16 || dt == TS_BF16; }
 
 extern "C" int ts_index_add(ts_index* h, const void* rows, int64_t n, int32_t rows_dtype,
@@ -415,6 +448,11 @@ extern "C" int ts_index_add(ts_index* h, const void* rows, int64_t n, int32_t ro
     if (norm) TS_CHECK(ensure(h->den, (size_t)n * 4));
     TS_CHECK(ts_launch_relayout(h->L, rows, rows_dtype, n, h->ntotal, h->corpus, norm,
                                 (float*)h->den.p, s));
+    TS_HIP(hipStreamSynchronize(s));
+  }
+  if (h->nremoved > 0) {   // the new rows are live
+    TS_CHECK(live_reserve(h, h->ntotal + n, s));
+    TS_CHECK(ts_launch_live_set((uint32_t*)h->live.p, h->ntotal, h->ntotal + n, s));
     TS_HIP(hipStreamSynchronize(s));
   }
   h->ntotal += n;
@@ -1079,15 +1117,20 @@ static int co_launch_pass(ts_index* h) {
     }
   }
   int st;
+  // removed rows: the tombstone instantiations (the queue is flushed whenever removals change)
+  const bool tomb = h->nremoved > 0;
   if (G <= h->co_gmax) {
-    MultiScanParams mp{};
+    MultiTombParams mp{};
     co_fill_params(h, G, mp);
     mp.stage_cap = ts_scan_multi_stage_cap(h->L, G);
-    st = ts_launch_scan_multi(h->L, G, mp, h->num_cus - h->num_cus / 8, s);
+    mp.live = (const uint32_t*)h->live.p;
+    st = tomb ? ts_launch_scan_multi_tomb(h->L, G, mp, h->num_cus - h->num_cus / 8, s)
+              : ts_launch_scan_multi(h->L, G, mp, h->num_cus - h->num_cus / 8, s);
   } else {
-    WideScanParams wp{};
+    WideTombParams wp{};
     co_fill_params(h, G, wp);
     wp.stage_cap = ts_scan_wide_stage_cap(h->L, G);
+    wp.live = (const uint32_t*)h->live.p;
     // every CU: the wide pass is co-bound by the matrix pipe, so the 7/8 of scan_kernel (HBM-bound) gives up 1/8
     // of its MFMA throughput (3.53-3.54 against 3.72-3.79 ms per 6-group pass at 10 M x 768).  The
     // free eighth serves the one-launch search's threshold workgroups and pipelined neighbours; a coalesced pass has
@@ -1097,7 +1140,7 @@ static int co_launch_pass(ts_index* h) {
     static const int dbg_wide_cus = getenv("TS_WIDE_CUS") ? atoi(getenv("TS_WIDE_CUS")) : 0;
     if (dbg_wide_cus > 0) wide_cus = dbg_wide_cus;
 #endif
-    st = ts_launch_scan_wide(h->L, G, wp, wide_cus, s);
+    st = tomb ? ts_launch_scan_wide_tomb(h->L, G, wp, wide_cus, s) : ts_launch_scan_wide(h->L, G, wp, wide_cus, s);
   }
   if (e0 && (st != TS_OK || hipEventRecord(e1, s) != hipSuccess)) {
     (void)hipEventDestroy(e0);
@@ -1120,7 +1163,7 @@ static int co_launch_pass(ts_index* h) {
       p.stride = kCandCap;
       p.n_per_q = b.W->cand_cnt();
       p.n_cap = kCandCap;
-      p.need = (uint32_t)std::min<int64_t>(b.k, N);
+      p.need = tomb ? 0u : (uint32_t)std::min<int64_t>(b.k, N);   // (tomb: need_check_kernel, min(k, live rows))
       p.k = b.k;
       p.out_scores = b.out_s;
       p.out_ids64 = b.out_i;
@@ -1129,7 +1172,9 @@ static int co_launch_pass(ts_index* h) {
       p.status = b.W->status();
       p.clear_counts = b.W->cand_cnt();
       p.host_report = h->host_status_dev + (size_t)b.slot * TS_SLOT_WORDS;
-      st = ts_launch_select(p, b.nq, s);
+      if (tomb) st = ts_launch_need_check(b.W->cand_cnt(), ((TsMaskDev*)b.W->mask.p)->need, b.nq, b.W->status(),
+                                          p.host_report, s);
+      if (st == TS_OK) st = ts_launch_select(p, b.nq, s);
       if (st == TS_OK) {
         if (hipEventRecord(b.W->ev_sel, s) == hipSuccess) b.W->used = true;   // (the set's next user waits for it)
         else { ts_set_error("hipEventRecord failed"); st = TS_ERR_HIP; }
@@ -1220,7 +1265,22 @@ static int co_submit(ts_index* h, const void* dq, int nq, int q_dtype, int k, fl
   sp.dense = (float*)W->sample.p;
   sp.dense_ld = S;
   TS_CHECK(ts_launch_scan(h->L, SCAN_DENSE, qh, sp, h->num_cus, s));
+  if (h->nremoved > 0) {
+    // removed rows: the thresholds of the filtered path (tau_masked_kernel) with the live words as the
+    // batch's one mask: the m_q-th best LIVE sample score with N_q = the live rows; need[q] = min(k, live rows)
+    TS_CHECK(ensure(W->mask, sizeof(TsMaskDev) + (size_t)nblk * 4));
+    TsMaskDev* md = (TsMaskDev*)W->mask.p;
+    TsMaskPass mp{};
+    mp.nd = 1;
+    mp.dist[0] = 0;
+    for (int j = 0; j < TS_MAX_Q; ++j) { mp.qmask[j] = j < nq ? 0 : -1; mp.qd[j] = j < nq ? 0 : -1; }
+    TS_HIP(hipMemsetAsync(md, 0, sizeof(TsMaskDev), s));
+    TS_CHECK(ts_launch_live_blocks((const uint32_t*)h->live.p, nblk, mp, nblk, N, md, s));
+    TS_CHECK(ts_launch_tau_masked((const float*)W->sample.p, S, sstride, N, (const uint32_t*)h->live.p, nblk, md, nq,
+                                  k, (uint32_t)oversample, kMinSampleRank, W->tau(), nullptr, s));
+  } else {
   TS_CHECK(ts_launch_tau((const float*)W->sample.p, S, (uint32_t)S, m, nq, W->tau(), s));
+  }
   uint32_t* rep = h->host_status + (size_t)slot_guard.slot * TS_SLOT_WORDS;
   for (int i = 0; i < 65; ++i) rep[i] = 0;
   {
@@ -1265,6 +1325,13 @@ extern "C" int ts_index_search(ts_index* h, const void* queries, int32_t nq, int
   if (h->ntotal == 0) {
     ts_set_error("No documents indexed. Call add_documents() first.");
     return TS_ERR_EMPTY;
+  }
+  if (h->nremoved > 0 && !co_pass_width(h, k, flags)) {
+    // removed rows: the filtered search whose only mask is the tombstone bitmap; a search that
+    // joins the coalesced passes takes their tombstone form instead (co_submit, co_launch_pass)
+    std::vector<int32_t> moq((size_t)nq, -1);
+    return ts_index_search_filtered(h, queries, nq, q_dtype, k, nullptr, 0, 0, moq.data(), out_scores, out_ids, flags,
+                                    stream);
   }
   DeviceGuard g(h->device);
   hipStream_t s = (hipStream_t)stream;
@@ -1387,7 +1454,7 @@ extern "C" int ts_index_search_filtered(ts_index* h, const void* queries, int32_
   }
   bool any = false;
   for (int32_t q = 0; q < nq && !any; ++q) any = mask_of_query[q] >= 0;
-  if (!any) return ts_index_search(h, queries, nq, q_dtype, k, out_scores, out_ids, flags, stream);
+  if (!any && h->nremoved == 0) return ts_index_search(h, queries, nq, q_dtype, k, out_scores, out_ids, flags, stream);
   DeviceGuard g(h->device);
   hipStream_t s = (hipStream_t)stream;
   TS_CHECK(co_flush(h, s));   // a filtered search never joins a coalesced pass
@@ -1414,13 +1481,33 @@ extern "C" int ts_index_search_filtered(ts_index* h, const void* queries, int32_
     TS_CHECK(ensure(h->qstage, (size_t)nq * qrow));
     TS_CHECK(ensure(h->out_s, (size_t)nq * k * 4));
     TS_CHECK(ensure(h->out_i, (size_t)nq * k * 8));
-    TS_CHECK(ensure(h->mstage, mbytes));
     TS_HIP(hipMemcpyAsync(h->qstage.p, queries, (size_t)nq * qrow, hipMemcpyHostToDevice, s));
-    TS_HIP(hipMemcpyAsync(h->mstage.p, allow_bits, mbytes, hipMemcpyHostToDevice, s));
+    if (mbytes) {
+      TS_CHECK(ensure(h->mstage, mbytes));
+      TS_HIP(hipMemcpyAsync(h->mstage.p, allow_bits, mbytes, hipMemcpyHostToDevice, s));
+      bits = (const uint32_t*)h->mstage.p;
+    }
     dq = h->qstage.p;
     ds = (float*)h->out_s.p;
     di = (int64_t*)h->out_i.p;
-    bits = (const uint32_t*)h->mstage.p;
+  }
+  // removed rows: every mask is ANDed with the tombstone bitmap on the device, and a query without a
+  // mask gets the bitmap itself, so the call is the filtered search of the live rows
+  std::unique_lock<std::mutex> elk(h->eff_mu, std::defer_lock);
+  std::vector<int32_t> moq_live;
+  if (h->nremoved > 0) {
+    elk.lock();
+    TS_CHECK(ensure(h->eff, (size_t)(n_masks + 1) * (size_t)need_words * 4));
+    if (h->eff_used) TS_HIP(hipStreamWaitEvent(s, h->eff_ev, 0));   // the previous call's passes have read `eff`
+    TS_CHECK(ts_launch_and_live(bits, allow_words, n_masks, (const uint32_t*)h->live.p, need_words,
+                                (uint32_t*)h->eff.p, s));
+    moq_live.assign(mask_of_query, mask_of_query + nq);
+    for (int32_t& m : moq_live)
+      if (m < 0) m = n_masks;
+    mask_of_query = moq_live.data();
+    bits = (const uint32_t*)h->eff.p;
+    allow_words = need_words;
+    n_masks += 1;
   }
   for (int q0 = 0; q0 < nq; q0 += qp) {
     const int c = std::min(qp, nq - q0);
@@ -1442,6 +1529,10 @@ extern "C" int ts_index_search_filtered(ts_index* h, const void* queries, int32_
     TS_CHECK(search_pass(h, (const char*)dq + (size_t)q0 * qrow, c, q_dtype, k, ds + (size_t)q0 * k,
                          di + (size_t)q0 * k, flags, s, masked ? &mc : nullptr));
   }
+  if (elk.owns_lock()) {
+    TS_HIP(hipEventRecord(h->eff_ev, s));
+    h->eff_used = true;
+  }
   if (flags & TS_FLAG_ASYNC) {
     std::lock_guard<std::mutex> lk(h->mu);
     ++h->next_ticket;
@@ -1458,6 +1549,110 @@ extern "C" int ts_index_last_filter_info(const ts_index* h, int64_t info[4]) {
   if (!h || !info) { ts_set_error("bad arguments"); return TS_ERR_INVALID; }
   std::lock_guard<std::mutex> lk(const_cast<ts_index*>(h)->mu);
   for (int i = 0; i < 4; ++i) info[i] = h->finfo[i];
+  return TS_OK;
+}
+
+// ---- removal (include/tristage.h "removal")
+// `s` waits for every search enqueued so far on this handle, on any stream: each workspace set records ev_sel behind
+// the last search that used it (the five-launch, one-launch, dense and coalesced paths alike)
+static int wait_for_searches(ts_index* h, hipStream_t s) {
+  std::lock_guard<std::mutex> lk(h->mu);
+  for (ts_index::WSet& w : h->ws)
+    if (w.used && hipEventQuery(w.ev_sel) != hipSuccess) TS_HIP(hipStreamWaitEvent(s, w.ev_sel, 0));
+  return TS_OK;
+}
+
+namespace {
+constexpr size_t kCompactStageBytes = 256u << 20;   // compaction's staging buffer: chunks of whole row blocks
+}  // namespace
+
+extern "C" int ts_index_remove(ts_index* h, const int64_t* ids, int64_t n, int64_t* n_removed, void* stream) {
+  if (!h || !n_removed || n < 0 || (n > 0 && !ids)) { ts_set_error("bad arguments to remove"); return TS_ERR_INVALID; }
+  *n_removed = 0;
+  if (n == 0 || h->ntotal == 0) return TS_OK;
+  DeviceGuard g(h->device);
+  hipStream_t s = (hipStream_t)stream;
+  TS_CHECK(co_flush(h, s));   // held passes search the index as it was when they were submitted
+  std::lock_guard<std::mutex> elk(h->eff_mu);
+  // searches submitted earlier (on any stream) have read the bitmap before it changes: eff_ev follows the last
+  // call's passes, and that call's stream waited for the one before it
+  if (h->eff_used) TS_HIP(hipStreamWaitEvent(s, h->eff_ev, 0));
+  TS_CHECK(wait_for_searches(h, s));
+  if (h->nremoved == 0) {   // the first removal: the bitmap starts all-live
+    TS_CHECK(live_reserve(h, h->ntotal, s));
+    TS_HIP(hipMemsetAsync(h->live.p, 0, (size_t)h->live_cap_words * 4, s));
+    TS_CHECK(ts_launch_live_set((uint32_t*)h->live.p, 0, h->ntotal, s));
+  }
+  const int64_t chunk = std::min<int64_t>(n, 1 << 22);
+  TS_CHECK(ensure(h->rids, (size_t)chunk * 8 + 256));
+  unsigned long long* cnt = (unsigned long long*)((char*)h->rids.p + (size_t)chunk * 8);
+  TS_HIP(hipMemsetAsync(cnt, 0, 8, s));
+  for (int64_t i0 = 0; i0 < n; i0 += chunk) {
+    const int64_t c = std::min(chunk, n - i0);
+    TS_HIP(hipMemcpyAsync(h->rids.p, ids + i0, (size_t)c * 8, hipMemcpyHostToDevice, s));
+    TS_CHECK(ts_launch_live_clear((uint32_t*)h->live.p, (const int64_t*)h->rids.p, c, h->id_offset, h->ntotal, cnt,
+                                  s));
+  }
+  unsigned long long cleared = 0;
+  TS_HIP(hipMemcpyAsync(&cleared, cnt, 8, hipMemcpyDeviceToHost, s));
+  TS_HIP(hipStreamSynchronize(s));
+  h->nremoved += (int64_t)cleared;
+  *n_removed = (int64_t)cleared;
+  return TS_OK;
+}
+
+extern "C" int64_t ts_index_live_count(const ts_index* h) { return h ? h->ntotal - h->nremoved : -1; }
+
+extern "C" int ts_index_live_words(ts_index* h, uint32_t* out, void* stream) {
+  if (!h || (!out && h->ntotal > 0)) { ts_set_error("bad arguments to live_words"); return TS_ERR_INVALID; }
+  const int64_t words = (h->ntotal + 31) / 32;
+  if (words == 0) return TS_OK;
+  if (h->nremoved == 0) {
+    for (int64_t w = 0; w < words; ++w) {
+      const int64_t rows = h->ntotal - w * 32;
+      out[w] = rows >= 32 ? ~0u : ((1u << rows) - 1u);
+    }
+    return TS_OK;
+  }
+  DeviceGuard g(h->device);
+  hipStream_t s = (hipStream_t)stream;
+  TS_HIP(hipMemcpyAsync(out, h->live.p, (size_t)words * 4, hipMemcpyDeviceToHost, s));
+  TS_HIP(hipStreamSynchronize(s));
+  return TS_OK;
+}
+
+extern "C" int ts_index_compact(ts_index* h, int64_t* old2new, void* stream) {
+  if (!h) { ts_set_error("null handle"); return TS_ERR_INVALID; }
+  const int64_t N = h->ntotal;
+  if (h->nremoved == 0) {
+    if (old2new)
+      for (int64_t r = 0; r < N; ++r) old2new[r] = r;
+    return TS_OK;
+  }
+  DeviceGuard g(h->device);
+  hipStream_t s = (hipStream_t)stream;
+  TS_CHECK(co_flush(h, s));
+  std::lock_guard<std::mutex> elk(h->eff_mu);
+  if (h->eff_used) TS_HIP(hipStreamWaitEvent(s, h->eff_ev, 0));   // earlier searches have read the old corpus
+  TS_CHECK(wait_for_searches(h, s));
+  const size_t sb = ts_compact_scratch_bytes(N);
+  if (sb == 0) { ts_set_error("bad compaction size"); return TS_ERR_INVALID; }
+  TS_CHECK(ensure(h->compact_scratch, sb + (old2new ? (size_t)N * 8 : 0)));
+  const size_t stage = std::max(kCompactStageBytes - kCompactStageBytes % ts_block_bytes(h->L), ts_block_bytes(h->L));
+  TS_CHECK(ensure(h->compact_stage, stage));
+  int64_t* o2n = old2new ? (int64_t*)((char*)h->compact_scratch.p + sb) : nullptr;
+  int64_t nlive = 0;
+  const int st = ts_compact_corpus(h->L, h->corpus, (const uint32_t*)h->live.p, N, h->compact_scratch.p, sb,
+                                   (uint4*)h->compact_stage.p, stage, o2n, &nlive, s);
+  if (st == TS_ERR_INVALID) ts_set_error("compaction scratch too small");
+  TS_CHECK(st);
+  if (old2new) TS_HIP(hipMemcpyAsync(old2new, o2n, (size_t)N * 8, hipMemcpyDeviceToHost, s));
+  TS_HIP(hipStreamSynchronize(s));
+  // the staging buffer is the size of a few hundred row blocks: given back, as the scratch is
+  release(h->compact_stage);
+  release(h->compact_scratch);
+  h->ntotal = nlive;
+  h->nremoved = 0;
   return TS_OK;
 }
 

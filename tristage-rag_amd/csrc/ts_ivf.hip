@@ -118,7 +118,8 @@ struct ts_ivf {
   int64_t id_offset = 0;
   int64_t info[4] = {0, 0, 0, 0};
   std::vector<std::vector<int32_t>> list_blocks;
-  std::vector<int64_t> list_size;
+  std::vector<int64_t> list_size;      // slots taken per list (where add continues)
+  std::vector<int64_t> list_removed;   // of them removed (ts_remove_ivf): dlist_size = list_size - list_removed
   IvfBuf corpus, blk_list, blk_valid, slot2id, id2slot, dlist_size;
   // add staging
   IvfBuf tmp_tiled, tmp_f32, den, assign, ascore, dst;
@@ -462,6 +463,26 @@ __global__ void ivf_scatter_kernel(const uint4* src, uint4* corpus, const int64_
   }
 }
 
+// remove (ts_remove_ivf): the slot of each id in [0, ntotal) leaves its block's valid word and slot2id; lists[i] = the
+// list of a slot this call freed, else -1.  id2slot keeps the slot, so that reconstruct still reads the stored row.
+__global__ void ivf_remove_kernel(const int64_t* ids, int64_t n, int64_t id_offset, int64_t ntotal,
+                                  const int64_t* id2slot, const int32_t* blk_list, uint32_t* blk_valid,
+                                  int64_t* slot2id, int32_t* lists) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int64_t r = ids[i] - id_offset;
+  int32_t l = -1;
+  if (r >= 0 && r < ntotal) {
+    const int64_t s = id2slot[r];
+    const uint32_t bit = 1u << (s & 31);
+    if (atomicAnd(&blk_valid[s >> 5], ~bit) & bit) {
+      slot2id[s] = -1;
+      l = blk_list[s >> 5];
+    }
+  }
+  lists[i] = l;
+}
+
 // reconstruct in id order: out[i] = stored row of id id0 + i, as float32
 __global__ void ivf_reconstruct_kernel(const uint4* corpus, const int64_t* id2slot, int64_t id0, int64_t n, int dim,
                                        int kg, int dt, float* out) {
@@ -607,6 +628,7 @@ extern "C" int ts_ivf_create(int32_t dim, int32_t nlist, int32_t storage_dtype, 
   h->L = L;
   h->list_blocks.resize(nlist);
   h->list_size.assign(nlist, 0);
+  h->list_removed.assign(nlist, 0);
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
     h->num_cus = prop.multiProcessorCount;
@@ -654,10 +676,44 @@ extern "C" int ts_ivf_reset(ts_ivf* h) {
   h->nblocks = 0;
   for (auto& v : h->list_blocks) v.clear();
   std::fill(h->list_size.begin(), h->list_size.end(), 0);
+  std::fill(h->list_removed.begin(), h->list_removed.end(), 0);
   return TS_OK;
 }
 
 extern "C" int64_t ts_ivf_ntotal(const ts_ivf* h) { return h ? h->ntotal : -1; }
+
+// removal with the contract of ts_index_remove (include/tristage.h): removed ids keep their slots as holes until
+// reset + re-add; the live list sizes feed the thresholds' N_q
+extern "C" int ts_remove_ivf(ts_ivf* h, const int64_t* ids, int64_t n, int64_t* n_removed, void* stream) {
+  if (!h || !n_removed || n < 0 || (n > 0 && !ids)) { ts_set_error("bad arguments to remove"); return TS_ERR_INVALID; }
+  *n_removed = 0;
+  if (n == 0 || h->ntotal == 0) return TS_OK;
+  IvfGuard g(h->device);
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t chunk = std::min<int64_t>(n, 1 << 20);
+  TS_CHECK(ivf_ensure(h->dst, (size_t)chunk * 8));
+  TS_CHECK(ivf_ensure(h->assign, (size_t)chunk * 8));
+  std::vector<int32_t> lists(chunk);
+  std::vector<int64_t> live_size(h->nlist);
+  int64_t cleared = 0;
+  for (int64_t i0 = 0; i0 < n; i0 += chunk) {
+    const int64_t c = std::min(chunk, n - i0);
+    TS_HIP(hipMemcpyAsync(h->dst.p, ids + i0, (size_t)c * 8, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(ivf_remove_kernel, dim3((unsigned)((c + 255) / 256)), dim3(256), 0, s, (const int64_t*)h->dst.p,
+                       c, h->id_offset, h->ntotal, (const int64_t*)h->id2slot.p, (const int32_t*)h->blk_list.p,
+                       (uint32_t*)h->blk_valid.p, (int64_t*)h->slot2id.p, (int32_t*)h->assign.p);
+    TS_HIP(hipGetLastError());
+    TS_HIP(hipMemcpyAsync(lists.data(), h->assign.p, (size_t)c * 4, hipMemcpyDeviceToHost, s));
+    TS_HIP(hipStreamSynchronize(s));
+    for (int64_t i = 0; i < c; ++i)
+      if (lists[i] >= 0) { ++h->list_removed[lists[i]]; ++cleared; }
+  }
+  for (int l = 0; l < h->nlist; ++l) live_size[l] = h->list_size[l] - h->list_removed[l];
+  TS_HIP(hipMemcpyAsync(h->dlist_size.p, live_size.data(), (size_t)h->nlist * 8, hipMemcpyHostToDevice, s));
+  TS_HIP(hipStreamSynchronize(s));
+  *n_removed = cleared;
+  return TS_OK;
+}
 extern "C" int32_t ts_ivf_is_trained(const ts_ivf* h) { return h ? (h->trained ? 1 : 0) : -1; }
 
 extern "C" int ts_ivf_set_id_offset(ts_ivf* h, int64_t offset) {
@@ -668,7 +724,7 @@ extern "C" int ts_ivf_set_id_offset(ts_ivf* h, int64_t offset) {
 
 extern "C" int ts_ivf_list_sizes(const ts_ivf* h, int64_t* out) {
   if (!h || !out) { ts_set_error("bad arguments to list_sizes"); return TS_ERR_INVALID; }
-  for (int l = 0; l < h->nlist; ++l) out[l] = h->list_size[l];
+  for (int l = 0; l < h->nlist; ++l) out[l] = h->list_size[l] - h->list_removed[l];
   return TS_OK;
 }
 
@@ -825,7 +881,7 @@ extern "C" int ts_ivf_add(ts_ivf* h, const void* rows, int64_t n, int32_t rows_d
   TS_CHECK(ivf_ensure(h->assign, (size_t)chunk * 8));
   TS_CHECK(ivf_ensure(h->ascore, (size_t)chunk * 4));
   TS_CHECK(ivf_ensure(h->dst, (size_t)chunk * 8));
-  std::vector<int64_t> asg(chunk), dst(chunk);
+  std::vector<int64_t> asg(chunk), dst(chunk), live_size(h->nlist);
   for (int64_t r0 = 0; r0 < n; r0 += chunk) {
     const int64_t c = std::min(chunk, n - r0);
     // the flat index's relayout (same rounding and normalisation), then the stored rows back as fp32 for the assignment
@@ -862,7 +918,8 @@ extern "C" int ts_ivf_add(ts_ivf* h, const void* rows, int64_t n, int32_t rows_d
                        (const uint4*)h->tmp_tiled.p, (uint4*)h->corpus.p, (const int64_t*)h->dst.p, c, h->L.kg,
                        h->ntotal, (int64_t*)h->slot2id.p, (int64_t*)h->id2slot.p, (uint32_t*)h->blk_valid.p);
     TS_HIP(hipGetLastError());
-    TS_HIP(hipMemcpyAsync(h->dlist_size.p, h->list_size.data(), (size_t)h->nlist * 8, hipMemcpyHostToDevice, s));
+    for (int l = 0; l < h->nlist; ++l) live_size[l] = h->list_size[l] - h->list_removed[l];
+    TS_HIP(hipMemcpyAsync(h->dlist_size.p, live_size.data(), (size_t)h->nlist * 8, hipMemcpyHostToDevice, s));
     TS_HIP(hipStreamSynchronize(s));   // (staging reused by the next chunk; host tables read by the copies)
     h->ntotal += c;
   }

@@ -143,6 +143,48 @@ class FlatIPIndex:
     def train(self, x) -> None:  # IndexIVFFlat API used at reference :267; no-op here
         return None
 
+    # -- removal (tombstones) -----------------------------
+    @property
+    def nlive(self) -> int:
+        """Rows not removed (``ntotal`` counts every id assigned since the last :meth:`compact` / :meth:`reset`)."""
+        return int(self._lib.ts_index_live_count(self._h))
+
+    def remove_ids(self, ids) -> int:
+        """FAISS ``remove_ids`` with stable ids: the rows with these ids (as :meth:`search` returns them, i.e. with
+        the id offset) are never returned again, but keep their ids and storage until :meth:`compact`.  Unknown,
+        repeated and already removed ids are skipped.  Returns how many rows were removed.  Unfinished ``async_``
+        searches are finished first, so that every search submitted before sees the index as it was."""
+        if _is_tensor(ids):
+            ids = ids.detach().cpu().numpy()
+        arr = np.ascontiguousarray(np.asarray(ids, dtype=np.int64).reshape(-1))
+        if self._pending:
+            self._auto_redone = self._auto_redone + self.finish()
+        n = ctypes.c_int64(0)
+        _lib.check(self._lib.ts_index_remove(self._h, arr.ctypes.data_as(ctypes.c_void_p), int(arr.shape[0]),
+                                             ctypes.byref(n), ctypes.c_void_p(_stream_ptr(self.device)) or None))
+        return int(n.value)
+
+    def live_words(self) -> np.ndarray:
+        """The live set as packed uint32 words (the layout of :func:`pack_allowed`)."""
+        out = np.zeros(max((self.ntotal + 31) // 32, 1), dtype=np.uint32)
+        _lib.check(self._lib.ts_index_live_words(self._h, out.ctypes.data_as(ctypes.c_void_p), None))
+        return out[: (self.ntotal + 31) // 32]
+
+    def live_mask(self) -> np.ndarray:
+        """The live set as a bool array over the ``ntotal`` rows."""
+        return np.unpackbits(self.live_words().view(np.uint8), bitorder="little")[: self.ntotal].astype(bool)
+
+    def compact(self) -> np.ndarray:
+        """Move the live rows down (order kept), drop the removed ones; ``ntotal`` becomes :attr:`nlive`.  Returns
+        the old -> new map int64 [old ntotal] (-1 = removed), monotone, so ties keep their order."""
+        if self._pending:
+            self._auto_redone = self._auto_redone + self.finish()
+        out = np.empty(max(self.ntotal, 1), dtype=np.int64)
+        n = self.ntotal
+        _lib.check(self._lib.ts_index_compact(self._h, out.ctypes.data_as(ctypes.c_void_p),
+                                              ctypes.c_void_p(_stream_ptr(self.device)) or None))
+        return out[:n]
+
     def reset(self) -> None:
         _lib.check(self._lib.ts_index_reset(self._h))
 
@@ -205,6 +247,8 @@ class FlatIPIndex:
         if allowed is not None:
             return self._search_filtered(q, k, allowed, exact_dense=exact_dense, async_=async_, out=out)
         if k > self.MAX_KERNEL_K and self.ntotal > self.MAX_KERNEL_K:
+            if self.nlive < self.ntotal:   # removed rows: the live set is the one mask
+                return self._search_large_k(q, k, out, masks=(self.live_words()[None, :], np.zeros(int(q.shape[0]), np.int32)))
             return self._search_large_k(q, k, out)
         if async_ and _is_tensor(q) and q.is_cuda and q.shape[0] > self.MAX_ASYNC_QUERIES:
             # the library takes at most 4 passes (256 queries) per asynchronous call: larger batches go in slices
@@ -395,6 +439,10 @@ class FlatIPIndex:
         if dev_bits is None:
             bits, words, moq = self._masks(allowed, B)
         if k > self.MAX_KERNEL_K and self.ntotal > self.MAX_KERNEL_K:
+            if self.nlive < self.ntotal:   # removed rows: every mask ANDed with the live set, which unfiltered queries get
+                live = self.live_words()
+                bits = np.concatenate([bits[:, :words] & live[None, :], live[None, :]]) if words else bits
+                moq = np.where(moq < 0, bits.shape[0] - 1, moq).astype(np.int32)
             return self._search_large_k(q, k, out, masks=(bits, moq))
         flags = _lib.TS_FLAG_NO_FILTER if exact_dense else 0
         if _is_tensor(q) and q.is_cuda:
@@ -1143,6 +1191,22 @@ class IVFFlatIndex:
     @property
     def is_trained(self) -> bool:
         return int(self._lib.ts_ivf_is_trained(self._h)) == 1
+
+    @property
+    def nlive(self) -> int:
+        """Rows not removed (``ntotal`` counts every id ever assigned)."""
+        return int(self.list_sizes().sum())
+
+    def remove_ids(self, ids) -> int:
+        """:meth:`FlatIPIndex.remove_ids` for the IVF index: removed rows leave their lists (holes stay until
+        :meth:`reset` and a new add).  Returns how many rows were removed."""
+        if _is_tensor(ids):
+            ids = ids.detach().cpu().numpy()
+        arr = np.ascontiguousarray(np.asarray(ids, dtype=np.int64).reshape(-1))
+        n = ctypes.c_int64(0)
+        _lib.check(self._lib.ts_remove_ivf(self._h, arr.ctypes.data_as(ctypes.c_void_p), int(arr.shape[0]),
+                                           ctypes.byref(n), self._stream()))
+        return int(n.value)
 
     def train(self, x, seed: Optional[int] = None, niter: Optional[int] = None) -> None:
         x = self._dev(x, "training points")

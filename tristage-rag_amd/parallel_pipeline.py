@@ -189,6 +189,12 @@ class ShardedRetrievalPipeline(RetrievalPipeline):
         self._indexed = False
         self.lo = self.hi = self.n_total = 0
 
+    def remove_documents(self, doc_ids) -> int:
+        raise NotImplementedError("remove_documents is not supported by the row-sharded pipeline")
+
+    def compact(self):
+        raise NotImplementedError("compact is not supported by the row-sharded pipeline")
+
     # -- collectives -------------------------------------------------------------
     def _host_staged(self) -> bool:
         return self.world_size > 1 and self._dist.get_backend(self.group) == "gloo"

@@ -218,6 +218,28 @@ class RetrievalPipeline:
             self.logger.error(f"Error adding documents: {e}")
             raise
 
+    # -- removal -------------------------------------------------
+    def remove_documents(self, doc_ids) -> int:
+        """Removes documents by doc_id: no stage returns them again (stage 1 drops them from the dense search, BM25 and
+        the fusion; stages 2 and 3 only see stage 1's candidates).  Their ids stay valid and their placeholders stay in
+        the documents / metadata lists until :meth:`compact`.  Returns how many documents were removed."""
+        if not self.stage1:
+            self.initialize_stages()
+        return self.stage1.remove_documents(doc_ids)
+
+    def compact(self):
+        """Drops the removed documents everywhere: the stage-1 index moves its live rows down on the GPU, BM25 is
+        refitted on the survivors, the stage-2 token store and the stage-3 token-id cache move their live entries
+        down in place.  Returns the old -> new doc_id map (numpy int64, -1 = removed; monotone)."""
+        if not self.stage1:
+            self.initialize_stages()
+        old2new = self.stage1.compact()
+        if self.stage2 is not None and hasattr(self.stage2, "compact_documents"):
+            self.stage2.compact_documents(old2new)
+        if self.stage3 is not None and hasattr(self.stage3, "compact_documents"):
+            self.stage3.compact_documents(old2new)
+        return old2new
+
     # -- search ----------------------------------------------------------------
     def _now(self) -> Optional[float]:
         return time.time() if self.config.enable_timing else None
@@ -537,6 +559,8 @@ class RetrievalPipeline:
                 "performance_stats": self.performance_stats}
         if self.stage1:
             info["stage1_stats"] = self.stage1.get_stats()
+            info["documents"] = {"total": len(self.stage1.documents), "removed": self.stage1.n_removed,
+                                 "live": len(self.stage1.documents) - self.stage1.n_removed}
         if self.stage2:
             info["stage2_info"] = self.stage2.get_model_info()
             info["stage2_token_store_dtype"] = info["stage2_info"].get("token_store_dtype")

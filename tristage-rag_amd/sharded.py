@@ -94,6 +94,12 @@ class ShardedFlatIPIndex:
             raise ValueError(f"expected {self.n_total} rows, got {rows.shape[0]}")
         self.local_index.add(rows[self.lo:self.hi])
 
+    def remove_ids(self, ids) -> int:
+        raise NotImplementedError("removal is not supported on a row-sharded index")
+
+    def compact(self):
+        raise NotImplementedError("removal is not supported on a row-sharded index")
+
     def search(self, q, k: int, async_: bool = False, inputs_ready: bool = False, allowed=None):
         """Global top-k for the replicated query batch `q` (tensor).  Returns
         tensors (D float32 [B,k], I int64 [B,k]) identical on every rank.

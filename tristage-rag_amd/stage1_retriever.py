@@ -348,6 +348,7 @@ class Stage1Retriever:
         self.bm25_index: Optional[BM25Index] = None
         self.documents: List[str] = []
         self.doc_metadata: List[Dict[str, Any]] = []
+        self._removed: Optional[np.ndarray] = None   # remove_documents: True = removed (placeholders until compact)
         # filtered search: host bitmaps of the dict filters' (key, value) pairs, extended as documents arrive, and a
         # small LRU of packed device masks of whole dict filters.  Neither is persisted, and both belong to ONE
         # metadata list (_filter_cache_meta): when doc_metadata is replaced (load_index, the sharded pipeline) they
@@ -571,19 +572,101 @@ class Stage1Retriever:
         return list(filter) if per_query else [filter] * nq
 
     def _filter_masks(self, filter, nq: int) -> Optional[List[Optional[np.ndarray]]]:
-        """-> one mask (or None) per query, None when no query is filtered."""
+        """-> one mask (or None) per query, None when no query is filtered.  With removed documents every query is
+        filtered: its mask (all documents without a filter) ANDed with the live ones."""
         if filter is not None and getattr(self, "index_type_used", "flat") == "ivf":
             raise NotImplementedError("filtered search is not supported on an IVF index (index_type='ivf')")
+        live = self.live_mask()
         specs = self._per_query_filters(filter, nq)
         if specs is None:
-            return None
+            return None if live is None else [live] * nq
         cache: Dict[int, Optional[np.ndarray]] = {}
         masks = []
         for f in specs:   # (one filter shared by the queries: resolved once)
             if id(f) not in cache:
-                cache[id(f)] = self.filter_mask(f)
+                m = self.filter_mask(f)
+                cache[id(f)] = m if live is None else (live if m is None else m & live)
             masks.append(cache[id(f)])
         return None if all(m is None for m in masks) else masks
+
+    # -- removal (DESIGN.md 4.11) ----------------------------------------------
+    def live_mask(self) -> Optional[np.ndarray]:
+        """bool array over the documents, False = removed; None while nothing is removed."""
+        r = getattr(self, "_removed", None)
+        if r is None or not r.any():
+            return None
+        live = np.ones(len(self.documents), dtype=bool)
+        live[: r.size] = ~r[: len(self.documents)]
+        return live
+
+    @property
+    def n_removed(self) -> int:
+        r = getattr(self, "_removed", None)
+        return 0 if r is None else int(np.count_nonzero(r))
+
+    def _index_removes(self) -> bool:
+        """The dense index drops removed rows itself (FlatIPIndex tombstones)."""
+        return self.faiss_index is not None and hasattr(self.faiss_index, "remove_ids")
+
+    def remove_documents(self, doc_ids) -> int:
+        """Removes documents by doc_id: they are never returned again (dense search, BM25 and the fusion), but keep
+        their ids, their placeholder in ``documents`` / ``doc_metadata`` and their storage until :meth:`compact`.
+        BM25 statistics stay those of every document added, as in Lucene, until :meth:`compact` refits them.
+        Unknown and already removed ids are skipped; returns how many documents were removed."""
+        if getattr(self, "index_type_used", "flat") == "ivf":
+            raise NotImplementedError("remove_documents is not supported on an IVF pipeline index (index_type='ivf'); "
+                                      "IVFFlatIndex.remove_ids removes rows of the index itself")
+        n = len(self.documents)
+        ids = np.unique(np.asarray(doc_ids, dtype=np.int64).reshape(-1))
+        ids = ids[(ids >= 0) & (ids < n)]
+        r = getattr(self, "_removed", None)
+        if r is None or r.size < n:
+            grown = np.zeros(n, dtype=bool)
+            if r is not None:
+                grown[: r.size] = r
+            r = self._removed = grown
+        ids = ids[~r[ids]]
+        if ids.size == 0:
+            return 0
+        if self._index_removes():
+            got = self.faiss_index.remove_ids(ids)
+            if got != ids.size:
+                raise RuntimeError(f"the index removed {got} of {ids.size} rows: it is out of step with the documents")
+        r[ids] = True
+        return int(ids.size)
+
+    def compact(self) -> np.ndarray:
+        """Drops the removed documents for good: the index moves its live rows down (FlatIPIndex.compact), documents /
+        metadata lose their placeholders, BM25 is refitted on the survivors and the filter caches start over.
+        Returns the old -> new doc_id map (-1 = removed), monotone."""
+        n = len(self.documents)
+        live = self.live_mask()
+        if live is None:
+            return np.arange(n, dtype=np.int64)
+        old2new = np.full(n, -1, dtype=np.int64)
+        old2new[live] = np.arange(int(np.count_nonzero(live)), dtype=np.int64)
+        if self._index_removes() and hasattr(self.faiss_index, "compact"):
+            got = self.faiss_index.compact()
+            if not np.array_equal(got, old2new):
+                raise RuntimeError("the index's compaction map differs from the documents' live set")
+        elif self.faiss_index is not None:   # an index without tombstones: rebuilt from its live rows
+            mat = self.faiss_index.reconstruct_n(0, self.faiss_index.ntotal)[live]
+            self.faiss_index = None
+            if len(mat):
+                self._create_faiss_index(mat.astype(np.float32))
+        keep = np.flatnonzero(live).tolist()
+        self.documents = [self.documents[i] for i in keep]
+        self.doc_metadata = [self.doc_metadata[i] for i in keep]   # (a new list: the filter caches start over)
+        self._removed = None
+        self._reset_filter_caches()
+        if self.bm25_index is not None:   # a fresh fit on the survivors (refit_compat would append to the old one)
+            self.bm25_index.close()
+            self.bm25_index = None
+            if self.documents:
+                self.bm25_index = BM25Index(gpu_device=self._bm25_device(),
+                                            refit_compat=getattr(self.config, "bm25_refit_compat", False))
+                self.bm25_index.fit(self.documents)
+        return old2new
 
     def _index_mask(self, filter, mask: np.ndarray):
         """What FlatIPIndex.search(allowed=) gets for one query: for a dict filter on a device index, packed words
@@ -614,8 +697,12 @@ class Stage1Retriever:
         """faiss_index.search, with ``allowed=`` when a filter is given."""
         if masks is None:
             return self.faiss_index.search(q, top_k)
-        per_q = self._per_query_filters(filters, len(masks))
-        allowed = [self._index_mask(f, m) for f, m in zip(per_q, masks)]
+        per_q = self._per_query_filters(filters, len(masks)) or [None] * len(masks)
+        # (a query whose only mask is the live set: the index applies its own tombstones)
+        drop_live = self._index_removes()
+        allowed = [None if (f is None and drop_live) else self._index_mask(f, m) for f, m in zip(per_q, masks)]
+        if all(a is None for a in allowed):
+            return self.faiss_index.search(q, top_k)
         same = all(a is allowed[0] for a in allowed)
         return self.faiss_index.search(q, top_k, allowed=allowed[0] if same else allowed)
 
@@ -871,6 +958,9 @@ class Stage1Retriever:
                 np.save(base + ".centroids.npy", self.faiss_index.centroids)
                 manifest.update(centroids=os.path.basename(base + ".centroids.npy"),
                                 nlist=int(self.faiss_index.nlist), ivf_dtype=self.faiss_index.storage_dtype)
+        if self.live_mask() is not None:   # the tombstones: bool per document, True = removed
+            np.save(base + ".removed.npy", ~self.live_mask())
+            manifest.update(removed=os.path.basename(base + ".removed.npy"))
         with open(index_path, "w") as f:  # JSON under the reference's file name
             json.dump(manifest, f)
         self.logger.info(f"Stage 1 index saved to {index_path}")
@@ -911,10 +1001,16 @@ class Stage1Retriever:
         if self.config.enable_bm25 and self.documents:
             self.bm25_index = BM25Index(gpu_device=self._bm25_device())
             self.bm25_index.fit(self.documents)
+        self._removed = None
+        if manifest.get("removed"):   # (a manifest without the entry: every document live)
+            removed = np.load(os.path.join(os.path.dirname(os.path.abspath(index_path)), manifest["removed"]),
+                              allow_pickle=False)
+            self.remove_documents(np.flatnonzero(removed))
         self.logger.info(f"Stage 1 index loaded from {index_path}")
 
     def get_stats(self) -> Dict[str, Any]:
-        return {"total_documents": len(self.documents), "embedding_dimension": self.embedding_dim,
+        return {"total_documents": len(self.documents), "removed_documents": self.n_removed,
+                "live_documents": len(self.documents) - self.n_removed, "embedding_dimension": self.embedding_dim,
                 "faiss_index_type": type(self.faiss_index).__name__ if self.faiss_index else None,
                 "index_type": getattr(self, "index_type_used", None) if self.faiss_index else None,
                 "bm25_enabled": self.config.enable_bm25,

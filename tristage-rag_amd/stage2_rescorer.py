@@ -118,6 +118,42 @@ class TokenStore:
         self.rows += add
         self._starts_dev = None
 
+    COMPACT_CHUNK_BYTES = 64 << 20   # compact(): the staging copy of one chunk of destination rows
+
+    def compact(self, keep) -> None:
+        """Keeps the documents (slots) with ``keep[slot]`` True, in slot order, and moves their token rows down IN PLACE
+        (the store is the largest thing on the GPU: no second copy of it).  Destination rows go in ascending chunks
+        of at most COMPACT_CHUNK_BYTES through a staging gather: a kept row never moves up, so a chunk's destinations
+        precede every source row of the chunks after it.  e4m3 stores are moved as bytes."""
+        keep = np.asarray(keep, dtype=bool)
+        if keep.shape != (len(self.starts),):
+            raise ValueError(f"keep: one entry per document ({len(self.starts)}), got shape {keep.shape}")
+        if keep.all():
+            return
+        starts = np.asarray(self.starts, dtype=np.int64)[keep]
+        lens = np.asarray(self.lens, dtype=np.int64)[keep]
+        new_starts = np.zeros_like(starts)
+        if lens.size:
+            new_starts[1:] = np.cumsum(lens)[:-1]
+        rows = int(lens.sum())
+        if rows and self.data is not None:
+            dev = self.data.device
+            data = _as_bytes(self.data)
+            moved = np.flatnonzero(starts != new_starts)
+            if moved.size:
+                first = int(new_starts[moved[0]])
+                # source row of every destination row from `first` on
+                shift = torch.from_numpy(np.repeat(starts[moved[0]:] - new_starts[moved[0]:], lens[moved[0]:])).to(dev)
+                src = shift + torch.arange(first, rows, dtype=torch.int64, device=dev)
+                chunk = max(1, self.COMPACT_CHUNK_BYTES // max(1, data.shape[1] * data.element_size()))
+                for c0 in range(first, rows, chunk):
+                    c1 = min(rows, c0 + chunk)
+                    data[c0:c1].copy_(data.index_select(0, src[c0 - first: c1 - first]))
+        self.starts = [int(x) for x in new_starts.tolist()]
+        self.lens = [int(x) for x in lens.tolist()]
+        self.rows = rows
+        self._starts_dev = None
+
     def device_tables(self):
         if self._starts_dev is None:
             dev = self.data.device
@@ -343,6 +379,20 @@ class ColBERTScorer:
             for j, i in enumerate(idx):
                 self._store_slot[first_doc_id + i] = base + j
         self._slot_version += 1
+
+    def compact_documents(self, old2new) -> None:
+        """RetrievalPipeline.compact: drops the token rows of removed documents (old2new[doc_id] == -1) from the store,
+        in place, and renumbers the rest (old2new: the monotone old -> new doc_id map)."""
+        old2new = np.asarray(old2new, dtype=np.int64)
+        slot_doc = {s: d for d, s in self._store_slot.items()}
+        keep = np.array([0 <= slot_doc.get(s, -1) < old2new.size and old2new[slot_doc[s]] >= 0
+                         for s in range(len(self.token_store))], dtype=bool)
+        new_slot = np.cumsum(keep) - 1
+        self.token_store.compact(keep)
+        self._store_slot = {int(old2new[d]): int(new_slot[s]) for d, s in self._store_slot.items()
+                            if d < old2new.size and old2new[d] >= 0}
+        self._slot_version += 1
+        self._doc_cache.clear()
 
     # -- persistence of the token store (additive; the reference has nothing to persist for stage 2)
     def save_token_store(self, path: str) -> bool:

@@ -209,6 +209,22 @@ class CrossEncoderReranker:
         self._pairs_usable = True
         return True
 
+    def compact_documents(self, old2new) -> None:
+        """RetrievalPipeline.compact: the token-id cache keeps the documents whose old2new entry is >= 0, in order
+        (old2new: the monotone old -> new doc_id map of the pipeline)."""
+        pa = getattr(self, "_pairs", None)
+        if pa is None:
+            return
+        old2new = np.asarray(old2new, dtype=np.int64)
+        base = int(getattr(self, "_pairs_base", 0))
+        ids = np.arange(base, base + len(pa))
+        keep = (ids < old2new.size) & (old2new[np.minimum(ids, old2new.size - 1)] >= 0)
+        pa._doc_ids = [x for x, k in zip(pa._doc_ids, keep) if k]
+        pa._doc_len = [x for x, k in zip(pa._doc_len, keep) if k]
+        pa._table = None
+        live_before = int(np.count_nonzero(old2new[:base] >= 0)) if base else 0
+        self._pairs_base = live_before
+
     def prefetch_queries(self, queries: List[str]) -> None:
         """Tokenise the queries of a coming rerank_arrays / raw_arrays_partial call now (host work that needs nothing
         from stages 1 and 2: the pipeline does it while the GPU is busy with them)."""
