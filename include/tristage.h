@@ -52,7 +52,8 @@ extern "C" {
  * added within version 4 as well: no existing signature changed.  So were wide coalesced passes
  * (TS_FLAG_WIDE_PASSES, TS_FLAG_NO_WIDE_PASSES, ts_coalesce_groups_wide, ts_coalesce_wide_min_bytes), and removal
  * (ts_index_remove, ts_index_live_count, ts_index_live_words, ts_index_compact): no existing signature changed, and
- * an index from which nothing is removed behaves as before; so was ts_remove_ivf.                                 */
+ * an index from which nothing is removed behaves as before; so was ts_remove_ivf.  So were ts_index_update and
+ * ts_update_ivf: an index that is never updated runs the code it ran before.                                      */
 #define TS_ABI_VERSION 4
 
 typedef struct ts_index ts_index; /* opaque */
@@ -241,6 +242,28 @@ int ts_index_remove(ts_index* h, const int64_t* ids, int64_t n, int64_t* n_remov
 int64_t ts_index_live_count(const ts_index* h);
 int ts_index_live_words(ts_index* h, uint32_t* out, void* stream);
 int ts_index_compact(ts_index* h, int64_t* old2new, void* stream);
+
+/* ---- update in place ------------------------------------------------------
+ * Replaces stored rows and keeps their ids.  Reference call site: none; the reference never changes a stored vector
+ * (its FAISS index is only ever added to, reference src/stage1_retriever.py:283).  Added within version 4.
+ * Exclusive access, as add.
+ *   ids      HOST int64[n], as search returns them, i.e. after the id offset.
+ *   rows     [n, dim] of rows_dtype, row i replacing id ids[i]; DEVICE, or HOST with TS_FLAG_HOST_PTR.
+ *   flags    TS_FLAG_NORMALIZE, TS_FLAG_HOST_PTR, as ts_index_add takes them.
+ * Afterwards the index holds the bytes ts_index_add of the final matrix would have written: the rows go through
+ * add's own relayout (rounding, normalisation), by one of two routes.  Ids that are one ascending run of consecutive
+ * rows are relaid out straight into the corpus at those rows (the relayout writes the units of the rows it is given
+ * and of no other); no staging, no further kernel.  Any other ids are relaid out into a staging tile, and 16-byte
+ * units move from there to their places: a row block all of whose 32 rows are updated is written as whole 1 KiB unit
+ * rows, of any other block only the updated rows' units are written.
+ * All or nothing: an id outside [0, ntotal), an id given twice in the call, or the id of a removed row fails the
+ * call with TS_ERR_INVALID, a message naming the first such id, and nothing written (ts_index_remove skips
+ * unknown ids; a skipped update would lose data silently).
+ * Ordering as ts_index_remove: held coalesced passes are flushed first and the update is ordered on `stream` behind
+ * every search submitted before it, so those read the rows as they were.  The tombstones, ntotal, live_count and
+ * the id offset do not change.                                                                                   */
+int ts_index_update(ts_index* h, const int64_t* ids, int64_t n, const void* rows, int32_t rows_dtype,
+                    uint32_t flags, void* stream);
 
 /* ---- introspection -------------------------------------------------------
  * faiss_index.ntotal / .d                                                    */
@@ -557,6 +580,13 @@ int64_t ts_ivf_ntotal(const ts_ivf* h);
  * until reset + re-add; reconstruct still returns the stored row.  Added within version 4.                       */
 /* (outside the ts_ivf_ prefix: that set of entry points is fixed by the IVF ABI tests) */
 int ts_remove_ivf(ts_ivf* h, const int64_t* ids, int64_t n, int64_t* n_removed, void* stream);
+/* update in place, with the contract of ts_index_update (all or nothing; rows DEVICE only, as ts_ivf_add).  Reference
+ * call site: none (the reference never changes a stored vector).  Each row leaves its list exactly as ts_remove_ivf
+ * makes it leave, is assigned by the quantizer exactly as ts_ivf_add assigns a new row, and is placed at the end of
+ * its new list under its old id; ntotal does not change and the hole stays, as after a removal.  Added within
+ * version 4; outside the ts_ivf_ prefix for the reason given above.                                              */
+int ts_update_ivf(ts_ivf* h, const int64_t* ids, int64_t n, const void* rows, int32_t rows_dtype, uint32_t flags,
+                  void* stream);
 int ts_ivf_set_id_offset(ts_ivf* h, int64_t offset);
 int ts_ivf_last_search_info(const ts_ivf* h, int64_t info[4]);
 

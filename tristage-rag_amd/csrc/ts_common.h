@@ -34,6 +34,7 @@ void ts_set_error(const char* fmt, ...);
 // mutex after the action succeeded (a failed action is retried by the next caller).
 #include <atomic>
 #include <mutex>
+#include <vector>
 #define TS_MAX_DEVICES 64
 struct TsDeviceOnce {
   std::mutex mu;
@@ -375,3 +376,34 @@ int ts_compact_corpus(const TsLayout& L, uint4* corpus, const uint32_t* live, in
                       size_t scratch_bytes, uint4* stage, size_t stage_bytes, int64_t* old2new_dev, int64_t* nlive_out,
                       hipStream_t stream);
 size_t ts_compact_scratch_bytes(int64_t ntotal);
+
+// ---------------------------------------------------------------- update in place (ts_update.hip)
+// rows[i] = ids[i] - id_offset (HOST arrays); TS_ERR_INVALID and a message naming the first id of the call that lies
+// outside [0, ntotal) or repeats an earlier one.  keys: rows[i] << 32 | i, ordered by row (ts_update_sort_rows); left
+// empty when the rows are strictly ascending as given (a bulk update need not pay for them).
+int ts_update_check_ids(const int64_t* ids, int64_t n, int64_t id_offset, int64_t ntotal, int64_t* rows,
+                        std::vector<uint64_t>* keys);
+// keys[i] = rows[i] << 32 | i ordered by row, positions of equal rows ascending (rows < 2^31, n < 2^31)
+void ts_update_sort_rows(const int64_t* rows, int64_t n, std::vector<uint64_t>* keys);
+// The row blocks a staging chunk touches: staging row j replaces row r for each key r << 32 | j of the chunk's n keys
+// (ordered by row, rows distinct; HOST).
+// A block all 32 of whose rows are replaced: full_blk[e], full_src[e * 32 + r] = staging row of its row r.  Any other
+// block: part_blk[e] with the items part_first[e] .. part_first[e + 1) of part_item, item = staging row * 32 + r.
+struct TsUpdateTables {
+  std::vector<int32_t> full_blk, full_src, part_blk, part_first, part_item;
+};
+void ts_update_group_blocks(const uint64_t* keys, int64_t n, TsUpdateTables* t);
+// out[0] += ids whose row is not live, out[1] = min(out[1], position of such an id); rows: DEVICE, after the offset
+int ts_launch_update_live_check(const uint32_t* live, const int64_t* rows, int64_t n, unsigned long long* out,
+                                hipStream_t stream);
+// moves the staging tile's rows to their places (DEVICE tables of ts_update_group_blocks): whole unit rows of the
+// fully replaced blocks / the 16-byte pieces of the replaced rows of the other blocks
+int ts_launch_update_blocks(const TsLayout& L, const uint4* stage, uint4* corpus, const int32_t* blk,
+                            const int32_t* src, int64_t n_entries, hipStream_t stream);
+int ts_launch_update_rows(const TsLayout& L, const uint4* stage, uint4* corpus, const int32_t* blk,
+                          const int32_t* first, const int32_t* item, int64_t n_entries, hipStream_t stream);
+int ts_launch_update_ivf_check(const int64_t* rows, int64_t n, const int64_t* id2slot, const int64_t* slot2id,
+                               const uint32_t* blk_valid, unsigned long long* out, hipStream_t stream);
+int ts_launch_update_ivf_place(const TsLayout& L, const uint4* src, uint4* corpus, const int64_t* dst,
+                               const int64_t* ids, int64_t n, int64_t* slot2id, int64_t* id2slot, uint32_t* blk_valid,
+                               hipStream_t stream);

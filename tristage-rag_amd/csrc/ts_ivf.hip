@@ -123,6 +123,7 @@ struct ts_ivf {
   IvfBuf corpus, blk_list, blk_valid, slot2id, id2slot, dlist_size;
   // add staging
   IvfBuf tmp_tiled, tmp_f32, den, assign, ascore, dst;
+  IvfBuf upd_ids;   // ts_update_ivf: the chunk's local ids
   // search workspace
   IvfBuf qimg, small, pid, pscore, bits, live, sample, cand_score, cand_id, dense, mids, list_score, list_id;
   // training
@@ -661,7 +662,8 @@ extern "C" int ts_ivf_destroy(ts_ivf* h) {
   IvfBuf* bufs[] = {&h->corpus, &h->blk_list, &h->blk_valid, &h->slot2id, &h->id2slot, &h->dlist_size,
                     &h->tmp_tiled, &h->tmp_f32, &h->den, &h->assign, &h->ascore, &h->dst, &h->qimg, &h->small,
                     &h->pid, &h->pscore, &h->bits, &h->live, &h->sample, &h->cand_score, &h->cand_id, &h->dense,
-                    &h->mids, &h->list_score, &h->list_id, &h->train_x, &h->cent, &h->perm, &h->offs};
+                    &h->mids, &h->list_score, &h->list_id, &h->train_x, &h->cent, &h->perm, &h->offs,
+                    &h->upd_ids};
   for (IvfBuf* b : bufs) ivf_release(*b);
   if (h->host_rep) (void)hipHostFree(h->host_rep);
   delete h;
@@ -922,6 +924,104 @@ extern "C" int ts_ivf_add(ts_ivf* h, const void* rows, int64_t n, int32_t rows_d
     TS_HIP(hipMemcpyAsync(h->dlist_size.p, live_size.data(), (size_t)h->nlist * 8, hipMemcpyHostToDevice, s));
     TS_HIP(hipStreamSynchronize(s));   // (staging reused by the next chunk; host tables read by the copies)
     h->ntotal += c;
+  }
+  return TS_OK;
+}
+
+// update in place, with the contract of ts_index_update (include/tristage.h): each row leaves its list as
+// ts_remove_ivf makes it leave, is staged, read back and assigned as ts_ivf_add assigns a new row, and is placed at the
+// end of its new list under its old id.  The hole stays, as after a removal.
+extern "C" int ts_update_ivf(ts_ivf* h, const int64_t* ids, int64_t n, const void* rows, int32_t rows_dtype,
+                             uint32_t flags, void* stream) {
+  if (!h || n < 0 || (n > 0 && (!ids || !rows)) ||
+      (rows_dtype != TS_F32 && rows_dtype != TS_F16 && rows_dtype != TS_BF16) || (flags & TS_FLAG_HOST_PTR)) {
+    ts_set_error("bad arguments to update (device rows of f32 / f16 / bf16)");
+    return TS_ERR_INVALID;
+  }
+  if (n == 0) return TS_OK;
+  std::vector<int64_t> loc((size_t)n);
+  std::vector<uint64_t> keys;
+  TS_CHECK(ts_update_check_ids(ids, n, h->id_offset, h->ntotal, loc.data(), &keys));
+  if (h->nblocks * 32 + n + 32LL * h->nlist >= (1LL << 31)) { ts_set_error("at most 2^31 slots per IVF index"); return TS_ERR_UNSUPPORTED; }
+  IvfGuard g(h->device);
+  hipStream_t s = (hipStream_t)stream;
+  const bool norm = (flags & TS_FLAG_NORMALIZE) != 0;
+  const size_t row_bytes = (size_t)h->L.dim * (rows_dtype == TS_F32 ? 4 : 2);
+  const int64_t chunk = std::min(n, kIvfAddChunkRows);
+  const int64_t cblk = (chunk + 31) / 32;
+  TS_CHECK(ivf_ensure(h->tmp_tiled, (size_t)cblk * ts_block_bytes(h->L)));
+  TS_CHECK(ivf_ensure(h->tmp_f32, (size_t)chunk * h->L.dim * 4));
+  TS_CHECK(ivf_ensure(h->den, (size_t)chunk * 4));
+  TS_CHECK(ivf_ensure(h->assign, (size_t)chunk * 8));
+  TS_CHECK(ivf_ensure(h->ascore, (size_t)chunk * 4));
+  TS_CHECK(ivf_ensure(h->dst, (size_t)chunk * 8));
+  TS_CHECK(ivf_ensure(h->upd_ids, (size_t)chunk * 8 + 256));
+  unsigned long long* cnt = (unsigned long long*)((char*)h->upd_ids.p + (size_t)chunk * 8);
+  // a removed id cannot be updated: every id is checked before the first row moves
+  for (int64_t i0 = 0; i0 < n; i0 += chunk) {
+    const int64_t c = std::min(chunk, n - i0);
+    unsigned long long dead[2] = {0ull, ~0ull};
+    TS_HIP(hipMemcpyAsync(cnt, dead, 16, hipMemcpyHostToDevice, s));
+    TS_HIP(hipMemcpyAsync(h->upd_ids.p, loc.data() + i0, (size_t)c * 8, hipMemcpyHostToDevice, s));
+    TS_CHECK(ts_launch_update_ivf_check((const int64_t*)h->upd_ids.p, c, (const int64_t*)h->id2slot.p,
+                                        (const int64_t*)h->slot2id.p, (const uint32_t*)h->blk_valid.p, cnt, s));
+    TS_HIP(hipMemcpyAsync(dead, cnt, 16, hipMemcpyDeviceToHost, s));
+    TS_HIP(hipStreamSynchronize(s));
+    if (dead[0] != 0ull) {
+      ts_set_error("update: id %lld was removed", (long long)ids[i0 + (int64_t)dead[1]]);
+      return TS_ERR_INVALID;
+    }
+  }
+  std::vector<int64_t> asg(chunk), dst(chunk), live_size(h->nlist);
+  std::vector<int32_t> lists(chunk);
+  for (int64_t r0 = 0; r0 < n; r0 += chunk) {
+    const int64_t c = std::min(chunk, n - r0);
+    // the new rows' lists, as ts_ivf_add finds them
+    TS_CHECK(ts_launch_relayout(h->L, (const char*)rows + (size_t)r0 * row_bytes, rows_dtype, c, 0,
+                                (uint4*)h->tmp_tiled.p, norm, (float*)h->den.p, s));
+    TS_CHECK(ts_launch_reconstruct(h->L, (const uint4*)h->tmp_tiled.p, 0, c, (float*)h->tmp_f32.p, s));
+    TS_CHECK(ivf_quant_topk(h, h->tmp_f32.p, c, TS_F32, 1, (float*)h->ascore.p, (int64_t*)h->assign.p, s));
+    TS_HIP(hipMemcpyAsync(asg.data(), h->assign.p, (size_t)c * 8, hipMemcpyDeviceToHost, s));
+    TS_HIP(hipStreamSynchronize(s));
+    for (int64_t r = 0; r < c; ++r)
+      if (asg[r] < 0 || asg[r] >= h->nlist) { ts_set_error("update: bad assignment %lld", (long long)asg[r]); return TS_ERR_HIP; }
+    // the old rows leave their lists (ts_remove_ivf's kernel; ids without the offset)
+    TS_HIP(hipMemcpyAsync(h->upd_ids.p, loc.data() + r0, (size_t)c * 8, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(ivf_remove_kernel, dim3((unsigned)((c + 255) / 256)), dim3(256), 0, s,
+                       (const int64_t*)h->upd_ids.p, c, (int64_t)0, h->ntotal, (const int64_t*)h->id2slot.p,
+                       (const int32_t*)h->blk_list.p, (uint32_t*)h->blk_valid.p, (int64_t*)h->slot2id.p,
+                       (int32_t*)h->assign.p);
+    TS_HIP(hipGetLastError());
+    TS_HIP(hipMemcpyAsync(lists.data(), h->assign.p, (size_t)c * 4, hipMemcpyDeviceToHost, s));
+    TS_HIP(hipStreamSynchronize(s));
+    for (int64_t i = 0; i < c; ++i)
+      if (lists[i] >= 0) ++h->list_removed[lists[i]];
+    // and take the next slots of their new ones
+    const int64_t old_blocks = h->nblocks;
+    int64_t nb = h->nblocks;
+    std::vector<int32_t> new_lists;
+    for (int64_t r = 0; r < c; ++r) {
+      const int64_t l = asg[r];
+      const int64_t pos = h->list_size[l];
+      if (pos % 32 == 0) {
+        h->list_blocks[l].push_back((int32_t)nb++);
+        new_lists.push_back((int32_t)l);
+      }
+      dst[r] = (int64_t)h->list_blocks[l][pos / 32] * 32 + pos % 32;
+      ++h->list_size[l];
+    }
+    if (nb > old_blocks) TS_CHECK(ivf_grow_blocks(h, nb, s));
+    h->nblocks = nb;
+    if (nb > old_blocks)
+      TS_HIP(hipMemcpyAsync((int32_t*)h->blk_list.p + old_blocks, new_lists.data(), (size_t)(nb - old_blocks) * 4,
+                            hipMemcpyHostToDevice, s));
+    TS_HIP(hipMemcpyAsync(h->dst.p, dst.data(), (size_t)c * 8, hipMemcpyHostToDevice, s));
+    TS_CHECK(ts_launch_update_ivf_place(h->L, (const uint4*)h->tmp_tiled.p, (uint4*)h->corpus.p,
+                                        (const int64_t*)h->dst.p, (const int64_t*)h->upd_ids.p, c,
+                                        (int64_t*)h->slot2id.p, (int64_t*)h->id2slot.p, (uint32_t*)h->blk_valid.p, s));
+    for (int l = 0; l < h->nlist; ++l) live_size[l] = h->list_size[l] - h->list_removed[l];
+    TS_HIP(hipMemcpyAsync(h->dlist_size.p, live_size.data(), (size_t)h->nlist * 8, hipMemcpyHostToDevice, s));
+    TS_HIP(hipStreamSynchronize(s));   // (staging reused by the next chunk; host tables read by the copies)
   }
   return TS_OK;
 }

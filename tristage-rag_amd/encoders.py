@@ -702,6 +702,14 @@ class PairAssembler:
             self._doc_ids.append(ids[: self.max_length])
         self._table = None
 
+    def replace_documents(self, slots: Sequence[int], texts: Sequence[str]) -> None:
+        """The documents in `slots` get the token ids and lengths of `texts`; the device table is rebuilt on next use."""
+        for s_, t in zip(slots, texts):
+            ids = self.ids_of(t)
+            self._doc_len[s_] = len(ids)
+            self._doc_ids[s_] = ids[: self.max_length]
+        self._table = None
+
     def __len__(self) -> int:
         return len(self._doc_ids)
 

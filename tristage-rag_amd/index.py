@@ -89,6 +89,14 @@ def wide_pass_flags(wide_passes) -> int:
     raise ValueError(f"wide_passes must be 'auto', True or False, not {wide_passes!r}")
 
 
+def _update_call(fn, handle, ids: np.ndarray, ptr, dtype: int, flags: int, stream) -> None:
+    """ts_index_update / ts_update_ivf: a refused id (TS_ERR_INVALID, nothing written) is a ``ValueError``."""
+    code = fn(handle, ids.ctypes.data_as(ctypes.c_void_p), int(ids.shape[0]), ptr, dtype, flags, stream)
+    if code == _lib.TS_ERR_INVALID:
+        raise ValueError(_lib.last_error())
+    _lib.check(code)
+
+
 class FlatIPIndex:
     """Exact inner-product index resident in MI355X HBM."""
 
@@ -163,6 +171,37 @@ class FlatIPIndex:
         _lib.check(self._lib.ts_index_remove(self._h, arr.ctypes.data_as(ctypes.c_void_p), int(arr.shape[0]),
                                              ctypes.byref(n), ctypes.c_void_p(_stream_ptr(self.device)) or None))
         return int(n.value)
+
+    def update_rows(self, ids, x, normalize: bool = False) -> None:
+        """Replace the stored rows ``ids`` (as :meth:`search` returns them, i.e. with the id offset) by the rows of ``x``
+        [len(ids), d] (numpy or a CUDA tensor, as :meth:`add` takes them); afterwards the index holds exactly what
+        :meth:`add` of the final matrix would have written.  All or nothing: an id out of range, given
+        twice or removed raises ``ValueError`` and nothing is written.  Unfinished ``async_`` searches are finished
+        first, as :meth:`remove_ids` does, so that every search submitted before reads the rows as they were."""
+        if _is_tensor(ids):
+            ids = ids.detach().cpu().numpy()
+        arr = np.ascontiguousarray(np.asarray(ids, dtype=np.int64).reshape(-1))
+        flags = _lib.TS_FLAG_NORMALIZE if normalize else 0
+        if _is_tensor(x):
+            if x.is_cuda and x.device.index != self.device:
+                raise ValueError("rows live on a different GPU than the index")
+            if not x.is_cuda:
+                x = x.detach().float().numpy()
+        if _is_tensor(x):
+            x = x.contiguous()
+            shape, ptr, dt = tuple(x.shape), ctypes.c_void_p(x.data_ptr()), _tensor_dtype(x)
+        else:
+            x = np.ascontiguousarray(x)
+            if x.dtype not in _NP_DTYPES:
+                x = x.astype(np.float32)
+            shape, ptr, dt = x.shape, x.ctypes.data_as(ctypes.c_void_p), _NP_DTYPES[x.dtype]
+            flags |= _lib.TS_FLAG_HOST_PTR
+        if len(shape) != 2 or shape[1] != self.d or shape[0] != arr.shape[0]:
+            raise ValueError(f"expected [{arr.shape[0]}, {self.d}] rows, got {tuple(shape)}")
+        if self._pending:
+            self._auto_redone = self._auto_redone + self.finish()
+        _update_call(self._lib.ts_index_update, self._h, arr, ptr, dt, flags,
+                     ctypes.c_void_p(_stream_ptr(self.device)) or None)
 
     def live_words(self) -> np.ndarray:
         """The live set as packed uint32 words (the layout of :func:`pack_allowed`)."""
@@ -1207,6 +1246,20 @@ class IVFFlatIndex:
         _lib.check(self._lib.ts_remove_ivf(self._h, arr.ctypes.data_as(ctypes.c_void_p), int(arr.shape[0]),
                                            ctypes.byref(n), self._stream()))
         return int(n.value)
+
+    def update_rows(self, ids, x, normalize: bool = False) -> None:
+        """:meth:`FlatIPIndex.update_rows` for the IVF index: each row leaves its list, is assigned by the quantizer as
+        :meth:`add` assigns a new row and joins the end of its new list under its old id (the hole stays, as after a
+        removal).  All or nothing: an id out of range, given twice or removed raises ``ValueError``."""
+        if _is_tensor(ids):
+            ids = ids.detach().cpu().numpy()
+        arr = np.ascontiguousarray(np.asarray(ids, dtype=np.int64).reshape(-1))
+        x = self._dev(x, "rows")
+        if x.shape[0] != arr.shape[0]:
+            raise ValueError(f"expected [{arr.shape[0]}, {self.d}] rows, got {tuple(x.shape)}")
+        flags = _lib.TS_FLAG_NORMALIZE if normalize else 0
+        _update_call(self._lib.ts_update_ivf, self._h, arr, ctypes.c_void_p(x.data_ptr()), _tensor_dtype(x), flags,
+                     self._stream())
 
     def train(self, x, seed: Optional[int] = None, niter: Optional[int] = None) -> None:
         x = self._dev(x, "training points")

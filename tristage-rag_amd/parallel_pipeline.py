@@ -195,6 +195,9 @@ class ShardedRetrievalPipeline(RetrievalPipeline):
     def compact(self):
         raise NotImplementedError("compact is not supported by the row-sharded pipeline")
 
+    def update_documents(self, doc_ids, documents, metadata=None) -> int:
+        raise NotImplementedError("update_documents is not supported by the row-sharded pipeline")
+
     # -- collectives -------------------------------------------------------------
     def _host_staged(self) -> bool:
         return self.world_size > 1 and self._dist.get_backend(self.group) == "gloo"

@@ -240,6 +240,26 @@ class RetrievalPipeline:
             self.stage3.compact_documents(old2new)
         return old2new
 
+    # -- update in place -------------------------------------------
+    def update_documents(self, doc_ids, documents: List[str], metadata: Optional[List[Dict[str, Any]]] = None) -> int:
+        """Replaces the documents ``doc_ids`` by ``documents`` (and, when given, their metadata) under the same
+        doc_ids, in every stage: the stage-1 index rows are rewritten in place, BM25 is refitted, the stage-2 token
+        rows are overwritten (or appended and repointed when the new text has more tokens) and the stage-3 token ids
+        replaced.  All or nothing: an id out of range, given twice or removed raises ``ValueError`` before any stage
+        is touched.  Returns how many documents were updated."""
+        if not self.stage1:
+            self.initialize_stages()
+        ids = self.stage1.check_update(doc_ids, documents, metadata)
+        if ids.size == 0:
+            return 0
+        documents = list(documents)
+        n = self.stage1.update_documents(ids, documents, metadata)
+        if self.stage2 is not None and self.stage2.config.precompute_document_embeddings:
+            self.stage2.update_documents(ids.tolist(), documents)
+        if self.stage3 is not None and self.config.stage3_cache_document_tokens:
+            self.stage3.update_documents(ids.tolist(), documents)
+        return n
+
     # -- search ----------------------------------------------------------------
     def _now(self) -> Optional[float]:
         return time.time() if self.config.enable_timing else None

@@ -668,6 +668,64 @@ class Stage1Retriever:
                 self.bm25_index.fit(self.documents)
         return old2new
 
+    # -- update in place --------------------------------------
+    def check_update(self, doc_ids, documents, metadata=None) -> np.ndarray:
+        """The ids of an update as int64, or ``ValueError``: one text (and, when given, one metadata dict) per id, every
+        id in range, given once and not removed.  All or nothing: called before any stage is touched."""
+        ids = np.asarray(doc_ids, dtype=np.int64).reshape(-1)
+        if len(documents) != ids.size or (metadata is not None and len(metadata) != ids.size):
+            raise ValueError(f"update_documents: {ids.size} ids, {len(documents)} documents"
+                             + ("" if metadata is None else f", {len(metadata)} metadata entries"))
+        n = len(self.documents)
+        seen = set()
+        r = getattr(self, "_removed", None)
+        for i in ids.tolist():
+            if i < 0 or i >= n:
+                raise ValueError(f"update_documents: doc_id {i} is not a document of this index ({n} documents)")
+            if i in seen:
+                raise ValueError(f"update_documents: doc_id {i} is given twice in one call")
+            if r is not None and i < r.size and r[i]:
+                raise ValueError(f"update_documents: doc_id {i} was removed")
+            seen.add(i)
+        return ids
+
+    def update_documents(self, doc_ids, documents: List[str], metadata: Optional[List[Dict[str, Any]]] = None) -> int:
+        """Replaces the documents ``doc_ids`` by ``documents`` under the same ids: the new texts are encoded on the path
+        :meth:`add_documents` uses and written over the index rows (``update_rows``; an index object without it is
+        rebuilt from its reconstructed rows with these replaced, the way :meth:`compact` falls back), the texts and,
+        when given, the metadata are replaced, the filter caches start over when metadata changed and BM25 is refitted
+        on the document list.  All or nothing (:meth:`check_update`).  Returns how many documents were updated."""
+        ids = self.check_update(doc_ids, documents, metadata)
+        if ids.size == 0:
+            return 0
+        documents = list(documents)
+        if self._device_path():
+            emb = self._encode_batch_tensor(documents, bulk=True)
+            self.faiss_index.update_rows(ids, emb, normalize=True)
+        else:
+            embeddings = self._normalize_embeddings(self._encode_batch(documents))
+            if hasattr(self.faiss_index, "update_rows"):
+                self.faiss_index.update_rows(ids, embeddings)
+            else:   # an index without update_rows (a custom index_factory): rebuilt with the rows replaced
+                mat = np.array(self.faiss_index.reconstruct_n(0, self.faiss_index.ntotal), dtype=np.float32)
+                mat[ids] = embeddings
+                self.faiss_index = None
+                self._create_faiss_index(mat)
+                if self.n_removed and self._index_removes():
+                    self.faiss_index.remove_ids(np.flatnonzero(self._removed))
+        for j, i in enumerate(ids.tolist()):
+            self.documents[i] = documents[j]
+            if metadata is not None:
+                self.doc_metadata[i] = metadata[j]
+        if metadata is not None:
+            self._reset_filter_caches()
+        if self.config.enable_bm25 and self.bm25_index is not None:
+            if self.bm25_index.refit_compat:   # (its fit() appends to the old entries: document i would keep the old
+                self.bm25_index.close()        # text's term frequencies; a fresh index, as compact() builds)
+                self.bm25_index = BM25Index(gpu_device=self._bm25_device(), refit_compat=True)
+            self.bm25_index.fit(self.documents)
+        return int(ids.size)
+
     def _index_mask(self, filter, mask: np.ndarray):
         """What FlatIPIndex.search(allowed=) gets for one query: for a dict filter on a device index, packed words
         on the device from the LRU (a repeated tenant filter is neither re-packed nor re-uploaded)."""

@@ -118,6 +118,19 @@ class TokenStore:
         self.rows += add
         self._starts_dev = None
 
+    def overwrite(self, slot: int, rows: torch.Tensor) -> None:
+        """The document in `slot` becomes `rows` [L, H], L <= its current length: written over the head of its rows,
+        its length shortened (the tail stays unused until :meth:`compact`).  :meth:`compact` moves rows down in
+        slot order and relies on slot order being start order: overwriting keeps a slot's start and appending takes
+        the end of the store, so both keep it.  Giving an abandoned slot's rows to another document would not."""
+        n = int(rows.shape[0])
+        if n > self.lens[slot]:
+            raise ValueError(f"{n} rows do not fit slot {slot} ({self.lens[slot]} rows)")
+        at = self.starts[slot]
+        _as_bytes(self.data[at: at + n]).copy_(_as_bytes(rows))
+        self.lens[slot] = n
+        self._starts_dev = None
+
     COMPACT_CHUNK_BYTES = 64 << 20   # compact(): the staging copy of one chunk of destination rows
 
     def compact(self, keep) -> None:
@@ -128,7 +141,7 @@ class TokenStore:
         keep = np.asarray(keep, dtype=bool)
         if keep.shape != (len(self.starts),):
             raise ValueError(f"keep: one entry per document ({len(self.starts)}), got shape {keep.shape}")
-        if keep.all():
+        if keep.all() and self.rows == sum(self.lens):   # (rows > sum(lens): documents shortened by overwrite())
             return
         starts = np.asarray(self.starts, dtype=np.int64)[keep]
         lens = np.asarray(self.lens, dtype=np.int64)[keep]
@@ -354,6 +367,16 @@ class ColBERTScorer:
         gets pipeline id first_doc_id + j (the doc_id stage 1 reports).  Same tokenisation, padding
         and forward as encode_documents_batch (reference :207-242); the valid rows of a batch go
         into the store with ONE masked copy (row-major mask order = document order)."""
+        for idx, rows, lens in self._store_batches(documents):
+            base = len(self.token_store)
+            self.token_store.append_packed(rows, lens)
+            for j, i in enumerate(idx):
+                self._store_slot[first_doc_id + i] = base + j
+        self._slot_version += 1
+
+    def _store_batches(self, documents: List[str]):
+        """The token rows of `documents` as the store keeps them, batch by batch: (idx, rows, lens) with rows
+        [sum(lens), H] in the store's type holding documents[idx[0]], documents[idx[1]], ... back to back."""
         bs = max(self.config.batch_size, getattr(self.config, "index_batch_size", 0) or 0, 1)
         dt = self.store_dtype()
         # length-sorted batches (little padding in the GEMMs); the slot table remembers where each document went
@@ -374,10 +397,33 @@ class ColBERTScorer:
                 rows = quantize_rows_fp8(rows)
             elif dt is not None and rows.dtype != dt:
                 rows = rows.to(dt)
-            base = len(self.token_store)
-            self.token_store.append_packed(rows, mask.sum(dim=1).tolist())
-            for j, i in enumerate(idx):
-                self._store_slot[first_doc_id + i] = base + j
+            yield idx, rows, mask.sum(dim=1).tolist()
+
+    def update_documents(self, doc_ids, documents: List[str]) -> None:
+        """RetrievalPipeline.update_documents: the token rows of the documents `doc_ids` become those of `documents`,
+        encoded as index_documents encodes them.  A document whose new token count fits its slot is overwritten in
+        place and its length shortened; a longer one is appended as a new slot and its doc_id repointed.  The rows
+        left behind (tails and abandoned slots) are reclaimed by compact_documents, which drops every slot no
+        document points to."""
+        doc_ids = [int(d) for d in doc_ids]
+        st = self.token_store
+        for idx, rows, lens in self._store_batches(list(documents)):
+            at = 0
+            grown, grown_lens = [], []   # the batch's documents that do not fit their slots: appended in one copy
+            for i, n in zip(idx, lens):
+                n = int(n)
+                r = rows[at: at + n]
+                at += n
+                slot = self._store_slot.get(doc_ids[i])
+                if slot is not None and n <= st.lens[slot]:
+                    st.overwrite(slot, r)
+                else:
+                    self._store_slot[doc_ids[i]] = len(st) + len(grown)
+                    grown.append(r)
+                    grown_lens.append(n)
+            if grown:
+                packed = grown[0] if len(grown) == 1 else torch.cat([_as_bytes(r) for r in grown]).view(rows.dtype)
+                st.append_packed(packed, grown_lens)
         self._slot_version += 1
 
     def compact_documents(self, old2new) -> None:
@@ -402,10 +448,13 @@ class ColBERTScorer:
         from safetensors.torch import save_file
         st = self.token_store
         ids = sorted(self._store_slot, key=self._store_slot.get)
+        # one entry per document: after update_documents some slots are referenced by no document (load_token_store
+        # numbers the entries 0, 1, ... in this order)
+        slots = [self._store_slot[d] for d in ids]
         fp8 = st.data.dtype == torch.float8_e4m3fn
         save_file({"tokens": st.data[: st.rows].contiguous().cpu(),
-                   "starts": torch.tensor(st.starts, dtype=torch.int64),
-                   "lens": torch.tensor(st.lens, dtype=torch.int32),
+                   "starts": torch.tensor([st.starts[j] for j in slots], dtype=torch.int64),
+                   "lens": torch.tensor([st.lens[j] for j in slots], dtype=torch.int32),
                    "doc_ids": torch.tensor(ids, dtype=torch.int64)}, path,
                   metadata={"format": TOKEN_STORE_FORMAT_FP8 if fp8 else TOKEN_STORE_FORMAT,
                             "model": str(self.config.model_name),

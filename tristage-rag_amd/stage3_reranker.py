@@ -209,6 +209,20 @@ class CrossEncoderReranker:
         self._pairs_usable = True
         return True
 
+    def update_documents(self, doc_ids, documents: List[str]) -> None:
+        """RetrievalPipeline.update_documents: the cached token ids and lengths of the documents `doc_ids` are replaced
+        by those of `documents` (the device table is rebuilt on next use).  A document the cache does not hold makes
+        the cache unusable, so that stage 3 tokenises pairs on the record path, as it does without the cache."""
+        pa = getattr(self, "_pairs", None)
+        if pa is None:
+            return
+        base = int(getattr(self, "_pairs_base", 0))
+        slots = [int(d) - base for d in doc_ids]
+        if any(s_ < 0 or s_ >= len(pa) for s_ in slots):
+            self._pairs_usable = False
+            return
+        pa.replace_documents(slots, documents)
+
     def compact_documents(self, old2new) -> None:
         """RetrievalPipeline.compact: the token-id cache keeps the documents whose old2new entry is >= 0, in order
         (old2new: the monotone old -> new doc_id map of the pipeline)."""
