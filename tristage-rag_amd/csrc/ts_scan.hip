@@ -770,6 +770,7 @@ int ts_launch_scan_multi_tomb(const TsLayout& L, int G, const MultiTombParams& p
 //     reads at most a few hundred KiB of images, and FETCH_SIZE stays one corpus read) by LDS-DMA into the other
 //     buffer;
 //   * it runs the window's TS_RING x G MFMAs out of the current buffer and refills that ring half with window t + 2;
+//     the B operands roll through G register sets, each re-read for the next slot right after its MFMA;
 //   * it waits for the units (vmcnt(TS_RING): the ring loads issued in this window stay in flight) and meets the
 //     others at lgkmcnt(0) + s_barrier.
 // The other buffer was last read in window t - 1, before the previous barrier.  A window's corpus units are thus
@@ -824,6 +825,53 @@ __device__ __forceinline__ void wide_ring_load(u32x4& r, uint32_t loff, const un
                    : "=v"(r) : "v"(loff), "s"(fill + (I / 4) * 4096), "i"((I % 4) * 1024) : "memory");
 #endif
 }
+
+#if defined(TS_TUNING) && defined(WIDE_TRACE)   // diagnostic builds only: per-wave phase sums of the wide walk, tools/trace_wide.py
+// Row (workgroup * SCAN_WAVES + wave) of the last wide launch: 100 MHz ticks summed over the wave's windows for
+// 0 gather requests, 1 the window's first-slot operand reads (issued and waited for: lgkmcnt(0), which the untraced
+// walk does not wait for in one piece), 2 the TS_RING slots (MFMAs, re-reads, refills), 3 fill pointer + epilogue,
+// 4 the vmcnt wait for the next window's units, 5 the barrier; then 6 the walk's ticks, 7 its s_memtime counts,
+// 8 the wave's windows.  A stamp is a scalar memory read, so it waits lgkmcnt(0) itself: none inside the slots.
+#define WIDE_TRACE_ROW 10
+__device__ uint32_t wide_trace_buf[256 * SCAN_WAVES * WIDE_TRACE_ROW];
+extern "C" int ts_debug_wide_trace(uint32_t* out) {
+  return hipMemcpyFromSymbol(out, HIP_SYMBOL(wide_trace_buf), sizeof(wide_trace_buf)) == hipSuccess ? 0 : -2;
+}
+#define WIDE_TRACE_BEGIN()                                              \
+  uint32_t wt_sum[6] = {0, 0, 0, 0, 0, 0};                              \
+  const uint32_t wt_c0 = (uint32_t)__builtin_readcyclecounter();        \
+  const uint32_t wt_t0 = (uint32_t)__builtin_amdgcn_s_memrealtime();    \
+  uint32_t wt_last = wt_t0
+#define WIDE_STAMP(k)                                                   \
+  do {                                                                  \
+    __builtin_amdgcn_sched_barrier(0);                                  \
+    const uint32_t now_ = (uint32_t)__builtin_amdgcn_s_memrealtime();   \
+    wt_sum[k] += now_ - wt_last;                                        \
+    wt_last = now_;                                                     \
+    __builtin_amdgcn_sched_barrier(0);                                  \
+  } while (0)
+#define WIDE_STAMP_READS(k)                                             \
+  do {                                                                  \
+    __builtin_amdgcn_sched_barrier(0);                                  \
+    __builtin_amdgcn_s_waitcnt(0xC07F); /* lgkmcnt(0) */                \
+    WIDE_STAMP(k);                                                      \
+  } while (0)
+#define WIDE_TRACE_END(nwindows)                                                                     \
+  do {                                                                                               \
+    if (lane == 0 && blockIdx.x < 256) {                                                             \
+      uint32_t* row_ = wide_trace_buf + ((size_t)blockIdx.x * SCAN_WAVES + wave) * WIDE_TRACE_ROW;   \
+      for (int k_ = 0; k_ < 6; ++k_) row_[k_] = wt_sum[k_];                                          \
+      row_[6] = (uint32_t)__builtin_amdgcn_s_memrealtime() - wt_t0;                                  \
+      row_[7] = (uint32_t)__builtin_readcyclecounter() - wt_c0;                                      \
+      row_[8] = (uint32_t)(nwindows);                                                                \
+    }                                                                                                \
+  } while (0)
+#else
+#define WIDE_TRACE_BEGIN() do { } while (0)
+#define WIDE_STAMP(k) do { } while (0)
+#define WIDE_STAMP_READS(k) do { } while (0)
+#define WIDE_TRACE_END(nwindows) do { } while (0)
+#endif
 
 // scan_wide_tomb_kernel (TOMB = true, PR = WideTombParams), a copy of scan_wide_kernel's walk: removed rows are
 // dropped from the staged survivors at the flush (tomb_live), after the ring, so no load enters the walk; only a
@@ -972,31 +1020,49 @@ __device__ __forceinline__ void scan_wide_body(const PR& p) {
   // window t + 2, wait for the units (vmcnt(TS_RING): this window's ring loads stay in flight) and meet the others
   // at lgkmcnt(0) + s_barrier.  The other buffer was last read in window t - 1, before the previous barrier.
   int qw = 0;
+  WIDE_TRACE_BEGIN();
   auto window = [&](auto half) {
     constexpr int P = decltype(half)::value;
     const int qn = qw + 1 < nwin ? qw + 1 : 0;
     gather(qn, P ^ 1);
+    WIDE_STAMP(0);
     const u32x4* ql = win + P * WU + lane;
-    ts_static_for<TS_RING>([&](auto i) {
-      ring_wait(ring[P * TS_RING + i]);
-#if defined(TS_TUNING) && defined(DBG_WIDE_B2)   // A/B only: the next MFMA's B operand is read before this one issues
-      u32x4 bq = ql[(i * G) * 64];
+#if !(defined(TS_TUNING) && defined(DBG_WIDE_SERIAL_B))
+    // slot 0's operands: the buffer is valid since the barrier that ended the window before
+    u32x4 bb[G];
 #pragma unroll
-      for (int hq = 0; hq < G; ++hq) {
-        const u32x4 bn = hq + 1 < G ? ql[(i * G + hq + 1) * 64] : bq;
-        mma_group<DT>(acc[hq], ring[P * TS_RING + i], bq);
-        bq = bn;
-      }
-#else
+    for (int hq = 0; hq < G; ++hq) bb[hq] = ql[hq * 64];
+#endif
+    WIDE_STAMP_READS(1);
+    ts_static_for<TS_RING>([&](auto i) {
+#if defined(TS_TUNING) && defined(DBG_WIDE_SERIAL_B)   // A/B only: one B register set, every MFMA waits for its own read
+      ring_wait(ring[P * TS_RING + i]);
 #pragma unroll
       for (int hq = 0; hq < G; ++hq) {
         const u32x4 b = ql[(i * G + hq) * 64];
         mma_group<DT>(acc[hq], ring[P * TS_RING + i], b);
       }
+#else
+      // rolling B operands: group hq's register set is re-read with the next slot's operand as soon as its MFMA has
+      // issued, so every read is G - 1 MFMAs ahead of its use (lgkmcnt(G - 1) before each MFMA, counted by the
+      // compiler; it counts down to 0 only in the window's last slot).  The sched_barriers pin that order: left
+      // alone the scheduler puts each read back in front of its MFMA.
+      __builtin_amdgcn_sched_barrier(0);
+      ring_wait(ring[P * TS_RING + i]);
+#pragma unroll
+      for (int hq = 0; hq < G; ++hq) {
+        mma_group<DT>(acc[hq], ring[P * TS_RING + i], bb[hq]);
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (decltype(i)::value + 1 < TS_RING) {
+          bb[hq] = ql[((i + 1) * G + hq) * 64];
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
 #endif
       refill(ring[P * TS_RING + i], i);
       __builtin_amdgcn_sched_barrier(0);
     });
+    WIDE_STAMP(2);
     advance_fill();
     if (qw == nwin - 1) {   // the row block's last window
       epilogue_multi_tomb<G, 8, PR, StageWideHdr, TOMB>(p, st, sscore, skey, acc, tau, blk, keyhi, lane);
@@ -1008,8 +1074,11 @@ __device__ __forceinline__ void scan_wide_body(const PR& p) {
       blk = p.blk0 + w * p.blk_stride;
       keyhi += 1u << 16;
     }
+    WIDE_STAMP(3);
     __builtin_amdgcn_s_waitcnt(0x3F70 | TS_RING);   // vmcnt(TS_RING)
+    WIDE_STAMP(4);
     walk_barrier();
+    WIDE_STAMP(5);
     qw = qn;
   };
   // Ring slots and buffers are compile-time, so the walk goes in pairs of windows (nwin may be odd).  The walk has
@@ -1031,6 +1100,7 @@ __device__ __forceinline__ void scan_wide_body(const PR& p) {
     walk_barrier();
     qw = qn;
   }
+  WIDE_TRACE_END(tw_mine);
 
   // ---- flush: one global atomic per (workgroup, query) reserves the slots
   __syncthreads();
@@ -1212,31 +1282,49 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_wide_kernel(WideScanParams 
   // window t + 2, wait for the units (vmcnt(TS_RING): this window's ring loads stay in flight) and meet the others
   // at lgkmcnt(0) + s_barrier.  The other buffer was last read in window t - 1, before the previous barrier.
   int qw = 0;
+  WIDE_TRACE_BEGIN();
   auto window = [&](auto half) {
     constexpr int P = decltype(half)::value;
     const int qn = qw + 1 < nwin ? qw + 1 : 0;
     gather(qn, P ^ 1);
+    WIDE_STAMP(0);
     const u32x4* ql = win + P * WU + lane;
-    ts_static_for<TS_RING>([&](auto i) {
-      ring_wait(ring[P * TS_RING + i]);
-#if defined(TS_TUNING) && defined(DBG_WIDE_B2)   // A/B only: the next MFMA's B operand is read before this one issues
-      u32x4 bq = ql[(i * G) * 64];
+#if !(defined(TS_TUNING) && defined(DBG_WIDE_SERIAL_B))
+    // slot 0's operands: the buffer is valid since the barrier that ended the window before
+    u32x4 bb[G];
 #pragma unroll
-      for (int hq = 0; hq < G; ++hq) {
-        const u32x4 bn = hq + 1 < G ? ql[(i * G + hq + 1) * 64] : bq;
-        mma_group<DT>(acc[hq], ring[P * TS_RING + i], bq);
-        bq = bn;
-      }
-#else
+    for (int hq = 0; hq < G; ++hq) bb[hq] = ql[hq * 64];
+#endif
+    WIDE_STAMP_READS(1);
+    ts_static_for<TS_RING>([&](auto i) {
+#if defined(TS_TUNING) && defined(DBG_WIDE_SERIAL_B)   // A/B only: one B register set, every MFMA waits for its own read
+      ring_wait(ring[P * TS_RING + i]);
 #pragma unroll
       for (int hq = 0; hq < G; ++hq) {
         const u32x4 b = ql[(i * G + hq) * 64];
         mma_group<DT>(acc[hq], ring[P * TS_RING + i], b);
       }
+#else
+      // rolling B operands: group hq's register set is re-read with the next slot's operand as soon as its MFMA has
+      // issued, so every read is G - 1 MFMAs ahead of its use (lgkmcnt(G - 1) before each MFMA, counted by the
+      // compiler; it counts down to 0 only in the window's last slot).  The sched_barriers pin that order: left
+      // alone the scheduler puts each read back in front of its MFMA.
+      __builtin_amdgcn_sched_barrier(0);
+      ring_wait(ring[P * TS_RING + i]);
+#pragma unroll
+      for (int hq = 0; hq < G; ++hq) {
+        mma_group<DT>(acc[hq], ring[P * TS_RING + i], bb[hq]);
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (decltype(i)::value + 1 < TS_RING) {
+          bb[hq] = ql[((i + 1) * G + hq) * 64];
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
 #endif
       refill(ring[P * TS_RING + i], i);
       __builtin_amdgcn_sched_barrier(0);
     });
+    WIDE_STAMP(2);
     advance_fill();
     if (qw == nwin - 1) {   // the row block's last window
       epilogue_multi<G, 8>(p, st, sscore, skey, acc, tau, blk, keyhi, lane);
@@ -1248,8 +1336,11 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_wide_kernel(WideScanParams 
       blk = p.blk0 + w * p.blk_stride;
       keyhi += 1u << 16;
     }
+    WIDE_STAMP(3);
     __builtin_amdgcn_s_waitcnt(0x3F70 | TS_RING);   // vmcnt(TS_RING)
+    WIDE_STAMP(4);
     walk_barrier();
+    WIDE_STAMP(5);
     qw = qn;
   };
   // Ring slots and buffers are compile-time, so the walk goes in pairs of windows (nwin may be odd).  The walk has
@@ -1271,6 +1362,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_wide_kernel(WideScanParams 
     walk_barrier();
     qw = qn;
   }
+  WIDE_TRACE_END(tw_mine);
 
   // ---- flush: one global atomic per (workgroup, query) reserves the slots
   __syncthreads();
