@@ -4,7 +4,7 @@ BASELINE.json's north_star; workload = configs[3]: synthetic 10M x 768 fp16
 corpus, batch-64 queries, top-1000, row-sharded over N GPUs with one RCCL
 all-gather + merge per batch).
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" = one batch of 64 queries searched against the whole corpus: local
 shard scan + exact top-k on every rank, all-gather of the partial lists, merge.
@@ -12,13 +12,25 @@ Corpus and queries are resident in HBM before the timed region.  The total
 corpus is fixed as N grows (strong scaling: the metric is quoted "@10Mx768
 corpus, 1/2/4/8 GPU").
 
-One JSON line on rank 0.  Besides the driver's contract it carries
+One JSON line on rank 0.  A plain run does what the headline needs and no more:
+set up, warm up, time the K steps, dump the outputs if asked, print the line.
+Besides the driver's contract the line carries
   roofline      the fused scan+filter kernel: algorithmic bytes per launch
                 (shard rows x padded dim x 2 B, the corpus read once) / its mean
-                duration measured with HIP events on the launch stream
+                duration measured with HIP events on the launch stream, inside
+                the timed steps; `traffic` is the number kept in
+                profiles/traffic.json for the shape
+
+--full adds everything that takes runs of its own (and the --no-* switches and
+--traffic choose among those):
+  roofline      `traffic` measured live (two rocprofv3 --pmc child runs) and
+                `measured_read_peak` (a read-only pass over the corpus)
+  secondary     the search fed by a bi-encoder forward, and the three-stage
+                pipeline on the configs[2] shape (N=1 only)
   cpu_baseline  the same search on the host cores (oracle.ip_topk_blas: blocked
                 SGEMM + partial sort, what faiss-cpu IndexFlatIP does) on a
                 bounded row sample, scaled to the full corpus.  N=1 only.
+Without --full, `secondary` and `cpu_baseline` are null.
 """
 from __future__ import annotations
 
@@ -37,7 +49,7 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: 8 TB/s spec (6.29 TB/s measured copy ceiling)
 
 
-def parse_args():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -47,7 +59,11 @@ def parse_args():
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--k", type=int, default=1000)
     ap.add_argument("--dtype", default="f16", choices=["f16", "bf16", "f32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beside the headline that takes runs of its own: cpu_baseline, the secondary legs "
+                         "(encoder + search, three-stage pipeline), the read probe and live PMC traffic of the roofline.  "
+                         "Off by default: a plain run sets up, warms up, times the steps and prints its line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
     ap.add_argument("--sync", action="store_true",
                     help="wait for every batch before issuing the next (default: batches are enqueued "
                          "back to back and completed + verified by finish() inside the timed region)")
@@ -77,22 +93,30 @@ def parse_args():
                     help="diagnostic: the per-step event intervals (ms) and the steps at which the collective finish() ran, "
                          "as config.step_ms / config.finish_at")
     ap.add_argument("--no-encode-leg", action="store_true",
-                    help="skip the secondary leg (bi-encoder forward of the 64 query texts + the same search)")
+                    help="with --full: skip the secondary leg (bi-encoder forward of the 64 query texts + the same search)")
     ap.add_argument("--no-pipeline-leg", action="store_true",
-                    help="skip the secondary legs that run the full three-stage pipeline (configs[2] shape, search_many of 64 "
+                    help="with --full: skip the secondary legs that run the full three-stage pipeline (configs[2] shape, search_many of 64 "
                          "queries, BM25 off and on); N=1 only")
     ap.add_argument("--no-read-probe", action="store_true",
-                    help="skip the read-only pass over the corpus that gives roofline.measured_read_peak")
+                    help="with --full: skip the read-only pass over the corpus that gives roofline.measured_read_peak")
     ap.add_argument("--traffic", choices=["auto", "live", "static", "off"], default="auto",
                     help="roofline.traffic: live = two rocprofv3 --pmc child runs of this script (FETCH_SIZE, WRITE_SIZE; "
                          "about half a minute each), static = the number kept in profiles/traffic.json for this shape, "
-                         "auto = live when rocprofv3 is on PATH and N=1, else static")
+                         "auto = live with --full when rocprofv3 is on PATH and N=1, else static; live needs --full")
     ap.add_argument("--encoder", default=None,
                     help="bi-encoder of the secondary leg (default: random:bert with hidden = --dim)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the last step's result (scores.npy, ids.npy) to DIR: the inputs "
                          "are seeded, so two builds run with the same arguments can be compared output for output")
-    return ap.parse_args()
+    args = ap.parse_args(argv)
+    if not args.full:
+        # a plain run: nothing but the headline's own set-up, warm-up and timed steps
+        if args.traffic == "live":
+            ap.error("--traffic live takes two profiler runs of its own: it needs --full")
+        args.no_cpu_baseline = args.no_encode_leg = args.no_pipeline_leg = args.no_read_probe = True
+        if args.traffic == "auto":
+            args.traffic = "static"
+    return args
 
 
 DUMP_BYTES_MAX = 64_000_000
@@ -505,6 +529,8 @@ def main():
     for i in range(args.warmup):
         step(i)
     finish()
+    # (stays in a plain run: five searches, some 10 ms at the default shape, and the timed steps below start from the
+    # clocks and caches these leave, as they always have)
     # per-batch latency with a host sync after every batch (reported, not the metric)
     torch.cuda.synchronize()
     tl = time.perf_counter()

@@ -80,6 +80,29 @@ def test_refuses_zero_steps():
     assert r.returncode == 2 and r.stdout.strip() == "" and "--steps" in r.stderr
 
 
+def test_plain_run_measures_the_headline_only_and_full_adds_the_rest():
+    """Without --full nothing that takes runs of its own is on (CPU baseline, encoder and pipeline legs, read probe,
+    live PMC traffic); --full turns all of it on, and the --no-* switches and --traffic choose among it."""
+    b = _bench_module()
+    plain = b.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "3"])
+    assert not plain.full
+    assert plain.no_cpu_baseline and plain.no_encode_leg and plain.no_pipeline_leg and plain.no_read_probe
+    assert plain.traffic == "static" and not plain.no_profile and plain.dump_outputs is None
+    assert (plain.steps, plain.warmup, plain.rows, plain.dim, plain.batch, plain.k, plain.dtype) == (20, 3, 10_000_000, 768, 64, 1000, "f16")
+    assert b.parse_args(["--traffic", "off"]).traffic == "off"
+    full = b.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "3", "--full"])
+    assert full.full and full.traffic == "auto"
+    assert not (full.no_cpu_baseline or full.no_encode_leg or full.no_pipeline_leg or full.no_read_probe)
+    assert (full.steps, full.warmup, full.rows, full.dim, full.batch, full.k, full.dtype) == (20, 3, 10_000_000, 768, 64, 1000, "f16")
+    some = b.parse_args(["--full", "--no-pipeline-leg", "--traffic", "live"])
+    assert some.no_pipeline_leg and not some.no_encode_leg and some.traffic == "live"
+
+
+def test_live_traffic_without_full_is_refused():
+    r = subprocess.run([sys.executable, BENCH, "--traffic", "live"], capture_output=True, text=True)
+    assert r.returncode == 2 and r.stdout.strip() == "" and "--full" in r.stderr
+
+
 def test_dump_outputs_dtypes_and_size_cap(tmp_path):
     import numpy as np
     b = _bench_module()
@@ -133,6 +156,32 @@ def test_bench_dump_outputs_is_the_last_step_and_repeats(tmp_path):
     corpus = b.gen_rows(torch, rows, dim, 1234, torch.float16, dev).float().cpu().numpy()
     q = b.gen_rows(torch, 64, dim, 4321 + (steps - 1) % 4, torch.float16, dev).float().cpu().numpy()
     check_topk(D, I.astype(np.int64), corpus, q, k)
+
+
+@pytest.mark.gpu
+def test_bench_plain_line_is_the_headline_and_full_adds_the_rest():
+    """A plain run prints the headline fields and the in-step roofline, with `secondary` and `cpu_baseline` null and no
+    read probe; the same command with --full carries all of them (live PMC traffic left to the full-size run:
+    `--traffic static`)."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    base = [sys.executable, BENCH, "--gpus", "1", "--steps", "8", "--warmup", "2", "--rows", "200000", "--k", "100"]
+    lines = []
+    for extra in ([], ["--full", "--traffic", "static", "--cpu-sample-rows", "50000"]):
+        r = subprocess.run(base + extra, env=env, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(out) == 1
+        lines.append(json.loads(out[0]))
+    plain, full = lines
+    for line in lines:
+        assert line["metric"].startswith("end-to-end queries/sec @200000x768 corpus") and line["unit"] == "queries/s"
+        assert line["value"] > 0 and line["ms_per_step"] > 0 and line["higher_is_better"] is True and line["dtype"] == "f16"
+        assert line["steps"] == 8 and line["warmup"] == 2 and line["roofline"]["avg_kernel_ms"] > 0
+        assert abs(line["value"] - 64 / (line["ms_per_step"] * 1e-3)) <= 1e-3 * line["value"]
+    assert plain["secondary"] is None and plain["cpu_baseline"] is None and "measured_read_peak" not in plain["roofline"]
+    assert full["cpu_baseline"]["value"] > 0 and full["roofline"]["measured_read_peak"] > 0
+    assert full["secondary"]["encode_plus_stage1_qps"] > 0 and full["secondary"]["pipeline_search_many_qps"] > 0
+    assert full["secondary"]["pipeline_search_many_bm25_rrf_qps"] > 0
 
 
 @pytest.mark.gpu

@@ -7,7 +7,7 @@ mkdir -p $O
 cd $R
 timeout -k 10 600 python -m pytest tests -m gpu -q --timeout 600 > $O/gputest.log 2>&1
 tail -2 $O/gputest.log
-timeout -k 10 400 python bench.py > $O/bench.json 2>$O/bench.err
+timeout -k 10 400 python bench.py --full > $O/bench.json 2>$O/bench.err
 tail -c 600 $O/bench.json
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 $R/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-encode-leg > $O/trace_bench.log 2>&1

@@ -26,7 +26,7 @@ b --rows 6250000 --dim 1024 --dtype bf16 --steps 40 --warmup 5 >> $O/shapes.json
 b --rows 10000000 --dtype f32 --steps 10 --warmup 2 >> $O/shapes.jsonl
 echo "shapes done" >> $O/progress.log
 echo "== headline" >> $O/progress.log
-timeout -k 10 400 python bench.py > $O/bench.json 2>>$O/err.log
+timeout -k 10 400 python bench.py --full > $O/bench.json 2>>$O/err.log
 TS_BENCH_CLASSIC=1 timeout -k 10 300 python bench.py --no-cpu-baseline --no-encode-leg > $O/bench_classic.json 2>>$O/err.log
 echo "headline done" >> $O/progress.log
 echo "== maxsim" >> $O/progress.log
