@@ -343,3 +343,45 @@ def test_async_coalesced_passes_keep_coalescing_after_removal(torch_mod, dtype, 
         _same(r, twin.search(q, k, allowed=live))
     idx.close()
     twin.close()
+
+
+# (d, groups, kernel family of the pass): every tombstone group count once, scan_multi_kernel 1..4, scan_wide_kernel 2..6
+PARTIAL = [(768, 3, "multi"), (768, 4, "wide"), (768, 5, "wide"), (1024, 3, "wide"), (1536, 1, "multi"),
+           (1536, 2, "wide"), (1536, 6, "wide"), (768, 2, "multi"), (384, 4, "multi")]
+
+
+@pytest.mark.parametrize("dtype", ["f16", "bf16"])
+@pytest.mark.parametrize("d,groups,family", PARTIAL)
+def test_partial_tombstone_passes(torch_mod, dtype, d, groups, family):
+    """Single-group batches on an index with removed rows, flushed at finish() as one tombstone pass: LDS-resident
+    where the images fit, wide otherwise (test_partial_wide_passes of test_coalesce_wide_gpu.py, after a removal)."""
+    from tristage_rag_amd import _lib
+    torch = torch_mod
+    n, k = 100_000, 100   # the floor below which the five-launch path does not coalesce
+    code = _lib.TS_F16 if dtype == "f16" else _lib.TS_BF16
+    assert (groups <= _lib.load().ts_coalesce_groups(d, code)) == (family == "multi")
+    corpus = make_corpus(n, d, seed=35, dtype=dtype)
+    idx, twin = _index(d, dtype, corpus), _index(d, dtype, corpus)
+    idx.classic_filter = True
+    idx.wide_passes = True
+    D = _removed_set(n, 0.05, np.random.default_rng(11))
+    assert idx.remove_ids(D) == D.size
+    live = np.ones(n, bool)
+    live[D] = False
+    tdt = torch.float16 if dtype == "f16" else torch.bfloat16
+    qs = [torch.from_numpy(make_corpus(32, d, seed=260 + i, dtype=dtype)).cuda().to(tdt) for i in range(groups)]
+    idx.set_profiling(True, every=1)
+    idx.timings(reset=True)
+    outs = [idx.search(q, k, async_=True) for q in qs]
+    redone = idx.finish()
+    torch.cuda.synchronize()
+    launches = idx.timings(reset=True)["filter_scan"][1]
+    idx.set_profiling(False)
+    assert redone == []
+    assert idx.last_filter_info()["filter_passes"] == 0   # nothing took the filtered path
+    assert launches == 1
+    for q, r in zip(qs, outs):
+        assert not np.isin(r[1].cpu().numpy(), D).any()
+        _same(r, twin.search(q, k, allowed=live))
+    idx.close()
+    twin.close()

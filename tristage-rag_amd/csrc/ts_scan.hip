@@ -311,53 +311,12 @@ __device__ __forceinline__ T pick_group(const T (&a)[N], int g) {
 }
 
 // QB: bits of the query field of the survivor key (7 for scan_multi_kernel, 8 for scan_wide_kernel); the row in the
-// block sits right above it
-template <int G, int QB, class P, class H>
-__device__ __forceinline__ void epilogue_multi(const P& p, H* st, float* sscore,
-                                               uint32_t* skey, const f32x16 (&acc)[G], const float (&tau)[G],
-                                               int64_t blk, uint32_t keyhi, int lane) {
-  bool hit = false;
-#pragma unroll
-  for (int hq = 0; hq < G; ++hq) hit |= (acc_max(acc[hq]) >= tau[hq]);
-  if (__builtin_amdgcn_ballot_w64(hit) == 0ull) return;  // the common case
-  const int64_t row_base = blk * TS_ROWS_PER_BLOCK;
-  const int j = lane & 31;
-#pragma unroll
-  for (int hq = 0; hq < G; ++hq) {
-    uint32_t mask = 0;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const bool ok = (acc[hq][r] >= tau[hq]) && (row_base + acc_row(r, lane) < p.ntotal);
-      mask |= ok ? (1u << r) : 0u;
-    }
-    if (mask) {
-      uint32_t slot = atomicAdd(&st->cnt, (uint32_t)__builtin_popcount(mask));  // LDS
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        if (mask & (1u << r)) {
-          if (slot < p.stage_cap) {
-            sscore[slot] = acc[hq][r];
-            skey[slot] = keyhi | ((uint32_t)acc_row(r, lane) << QB) | (uint32_t)(hq * 32 + j);
-          } else {
-            // staging area full: append directly
-            const uint32_t g = atomicAdd(&p.gcnt[hq][j], 1u);
-            if (g < p.cand_cap) {
-              p.gscore[hq][(size_t)j * p.cand_cap + g] = acc[hq][r];
-              p.gid[hq][(size_t)j * p.cand_cap + g] = (int32_t)(row_base + acc_row(r, lane));
-            }
-          }
-          ++slot;
-        }
-      }
-    }
-  }
-}
-
+// block sits right above it.
 // TOMB (the tombstone passes of an index with removed rows): staged survivors are checked against the
 // live words when the workgroup flushes them (tomb_live), after the walk; a survivor that finds the staging area full
 // is not appended but makes its batch overflow (redone exactly).
-template <int G, int QB, class P, class H, bool TOMB>
-__device__ __forceinline__ void epilogue_multi_tomb(const P& p, H* st, float* sscore,
+template <int G, int QB, bool TOMB, class P, class H>
+__device__ __forceinline__ void epilogue_multi(const P& p, H* st, float* sscore,
                                                uint32_t* skey, const f32x16 (&acc)[G], const float (&tau)[G],
                                                int64_t blk, uint32_t keyhi, int lane) {
   bool hit = false;
@@ -386,12 +345,14 @@ __device__ __forceinline__ void epilogue_multi_tomb(const P& p, H* st, float* ss
             // staging area full: append directly
             // (TOMB: nothing here knows whether the row is live, so the count is pushed past the list's capacity:
             // the select reports an overflow and the batch is redone exactly)
-            uint32_t g = p.cand_cap;
-            if constexpr (TOMB) atomicMax(&p.gcnt[hq][j], p.cand_cap + 1u);
-            else g = atomicAdd(&p.gcnt[hq][j], 1u);
-            if (g < p.cand_cap) {
-              p.gscore[hq][(size_t)j * p.cand_cap + g] = acc[hq][r];
-              p.gid[hq][(size_t)j * p.cand_cap + g] = (int32_t)(row_base + acc_row(r, lane));
+            if constexpr (TOMB) {
+              atomicMax(&p.gcnt[hq][j], p.cand_cap + 1u);
+            } else {
+              const uint32_t g = atomicAdd(&p.gcnt[hq][j], 1u);
+              if (g < p.cand_cap) {
+                p.gscore[hq][(size_t)j * p.cand_cap + g] = acc[hq][r];
+                p.gid[hq][(size_t)j * p.cand_cap + g] = (int32_t)(row_base + acc_row(r, lane));
+              }
             }
           }
           ++slot;
@@ -408,11 +369,13 @@ __device__ __forceinline__ bool tomb_live(const P& p, int64_t row) {
   return true;
 }
 
-// scan_multi_tomb_kernel (TOMB = true, P = MultiTombParams): scan_multi_kernel's walk with removed rows dropped at the
-// flush.  A copy, not a shared body: an inlined shared body changes the register allocation of the existing kernel
-// (DESIGN.md 4.8), whose instruction stream stays as it is.
-template <int DT, int G, bool TOMB, class P>
-__device__ __forceinline__ void scan_multi_body(const P& p) {
+// One kernel template for the plain passes (TOMB = false, MultiScanParams) and the tombstone passes of an index with
+// removed rows (TOMB = true, MultiTombParams): the same walk, with removed rows dropped at the flush.  The kernel itself
+// carries TOMB and takes its parameter block as the kernel argument; a __global__ wrapper around an inlined body that
+// receives the block by reference is what changes the plain instantiations' code, so there is none.
+template <int DT, int G, bool TOMB>
+__global__ __launch_bounds__(SCAN_THREADS) void scan_multi_kernel(
+    std::conditional_t<TOMB, MultiTombParams, MultiScanParams> p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   u32x4* qlds = reinterpret_cast<u32x4*>(smem);
   const int tid = threadIdx.x;
@@ -508,7 +471,7 @@ __device__ __forceinline__ void scan_multi_body(const P& p) {
       __builtin_amdgcn_sched_barrier(0);
     }
 
-    epilogue_multi_tomb<G, 7, P, StageMultiHdr, TOMB>(p, st, sscore, skey, acc, tau, blk, keyhi, lane);
+    epilogue_multi<G, 7, TOMB>(p, st, sscore, skey, acc, tau, blk, keyhi, lane);
 
     if (!has_next) break;
     w = wn;
@@ -554,143 +517,6 @@ __device__ __forceinline__ void scan_multi_body(const P& p) {
   }
 }
 
-template <int DT, int G>
-__global__ __launch_bounds__(SCAN_THREADS) void scan_multi_kernel(MultiScanParams p) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  u32x4* qlds = reinterpret_cast<u32x4*>(smem);
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int kg = p.kg;
-
-  const int64_t nwaves = (int64_t)gridDim.x * SCAN_WAVES;
-  int64_t w = (int64_t)blockIdx.x * SCAN_WAVES + wave;
-  const bool active = w < p.nwork;  // (waves without work still join the final flush)
-  const u32x4* base = reinterpret_cast<const u32x4*>(p.corpus) + lane;
-  const size_t blk_units = (size_t)kg * 64;
-  int64_t blk = active ? p.blk0 + w * p.blk_stride : p.blk0;
-  const u32x4* cur = base + (size_t)blk * blk_units;
-  u32x4 ring[TS_RING];
-  if (active) {
-#pragma unroll
-    for (int i = 0; i < TS_RING; ++i) ring[i] = stream_load(cur + (size_t)i * 64);
-  }
-
-  // ---- prologue: gather the groups' columns (global/L2) into one G-group image in LDS, once per workgroup
-  {
-    const int units = kg * G * 64;
-    for (int i0 = tid; i0 < units; i0 += 8 * SCAN_THREADS) {
-      u32x4 t[8];
-#pragma unroll
-      for (int jj = 0; jj < 8; ++jj) {
-        const int i = i0 + jj * SCAN_THREADS;
-        t[jj] = u32x4{0, 0, 0, 0};
-        if (i < units) {
-          const int u = i >> 6, gk = u / G, g = u - gk * G;
-          const u32x4* src = reinterpret_cast<const u32x4*>(pick_group<G>(p.gimg, g));
-          t[jj] = src[(size_t)(gk * pick_group<G>(p.gqh, g) + pick_group<G>(p.ghalf, g)) * 64 + (i & 63)];
-        }
-      }
-#pragma unroll
-      for (int jj = 0; jj < 8; ++jj) {
-        const int i = i0 + jj * SCAN_THREADS;
-        if (i < units) qlds[i] = t[jj];
-      }
-    }
-  }
-  StageMultiHdr* st = reinterpret_cast<StageMultiHdr*>(smem + (size_t)kg * G * 1024);
-  float* sscore = reinterpret_cast<float*>(st + 1);
-  uint32_t* skey = reinterpret_cast<uint32_t*>(sscore + p.stage_cap);
-  if (tid == 0) st->cnt = 0;
-  __syncthreads();
-
-  if (active) {
-
-  float tau[G];
-#pragma unroll
-  for (int hq = 0; hq < G; ++hq) tau[hq] = p.gtau[hq][lane & 31];
-
-  const u32x4* ql = qlds + lane;
-  uint32_t keyhi = (uint32_t)wave << 12;   // + (iteration << 15)
-
-  while (true) {
-    const int64_t wn = w + nwaves;
-    const bool has_next = wn < p.nwork;
-    const int64_t blkn = has_next ? (p.blk0 + wn * p.blk_stride) : blk;
-    const u32x4* nxt = base + (size_t)blkn * blk_units;
-
-    f32x16 acc[G];
-#pragma unroll
-    for (int hq = 0; hq < G; ++hq)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[hq][r] = 0.f;
-
-    // main part: prefetch stays inside the current row block
-    int g0 = 0;
-    for (; g0 < kg - TS_RING; g0 += TS_RING) {
-#pragma unroll
-      for (int i = 0; i < TS_RING; ++i) {
-#pragma unroll
-        for (int hq = 0; hq < G; ++hq) {
-          const u32x4 b = ql[(size_t)((g0 + i) * G + hq) * 64];
-          mma_group<DT>(acc[hq], ring[i], b);
-        }
-        ring[i] = stream_load(cur + (size_t)(g0 + i + TS_RING) * 64);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    // tail: the ring is refilled from the start of the wave's next row block
-#pragma unroll
-    for (int i = 0; i < TS_RING; ++i) {
-#pragma unroll
-      for (int hq = 0; hq < G; ++hq) {
-        const u32x4 b = ql[(size_t)((g0 + i) * G + hq) * 64];
-        mma_group<DT>(acc[hq], ring[i], b);
-      }
-      ring[i] = stream_load(nxt + (size_t)i * 64);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-
-    epilogue_multi<G, 7>(p, st, sscore, skey, acc, tau, blk, keyhi, lane);
-
-    if (!has_next) break;
-    w = wn;
-    blk = blkn;
-    cur = nxt;
-    keyhi += 1u << 15;
-  }
-  }  // active
-
-  // ---- flush: one global atomic per (workgroup, query) reserves the slots
-  __syncthreads();
-  const uint32_t n = st->cnt < p.stage_cap ? st->cnt : p.stage_cap;
-  if (n == 0) return;  // uniform: cnt is final after the barrier
-  if (tid < G * 32) { st->qcnt[tid] = 0; st->qoff[tid] = 0; }
-  __syncthreads();
-  for (uint32_t e = tid; e < n; e += SCAN_THREADS) atomicAdd(&st->qcnt[skey[e] & 127u], 1u);
-  __syncthreads();
-  if (tid < G * 32 && st->qcnt[tid] > 0)
-    st->qbase[tid] = atomicAdd(pick_group<G>(p.gcnt, tid >> 5) + (tid & 31), st->qcnt[tid]);
-  __syncthreads();
-  for (uint32_t e = tid; e < n; e += SCAN_THREADS) {
-    const uint32_t key = skey[e];
-    const uint32_t q = key & 127u;
-    const uint32_t slot = st->qbase[q] + atomicAdd(&st->qoff[q], 1u);
-    if (slot < p.cand_cap) {
-      const int g = (int)(q >> 5);
-      const size_t at = (size_t)(q & 31u) * p.cand_cap + slot;
-      const int64_t wi = (int64_t)blockIdx.x * SCAN_WAVES + ((key >> 12) & 7u) + (int64_t)(key >> 15) * nwaves;
-      pick_group<G>(p.gscore, g)[at] = sscore[e];
-      pick_group<G>(p.gid, g)[at] = (int32_t)((p.blk0 + wi * p.blk_stride) * TS_ROWS_PER_BLOCK + ((key >> 7) & 31u));
-    }
-  }
-}
-
-template <int DT, int G>
-__global__ __launch_bounds__(SCAN_THREADS) void scan_multi_tomb_kernel(MultiTombParams p) {
-  scan_multi_body<DT, G, true>(p);
-}
-
 int ts_scan_multi_groups(const TsLayout& L) {
   if (L.dtype != TS_F16 && L.dtype != TS_BF16) return 0;
   for (int G = TS_MAX_GROUPS; G >= 1; --G)
@@ -715,9 +541,7 @@ bool ts_scan_multi_fits(int64_t nblk, int num_cus) {
 template <int DT, int G, class P = MultiScanParams>
 static int launch_scan_multi_t(const TsLayout& L, const P& p, int num_cus, hipStream_t stream) {
   const size_t lds = (size_t)L.kg * G * 1024 + sizeof(StageMultiHdr) + 8 * (size_t)p.stage_cap;
-  void (*kern)(P);
-  if constexpr (std::is_same<P, MultiTombParams>::value) kern = scan_multi_tomb_kernel<DT, G>;
-  else kern = scan_multi_kernel<DT, G>;
+  void (*kern)(P) = scan_multi_kernel<DT, G, std::is_same<P, MultiTombParams>::value>;
   static TsDeviceOnce lds_attr;
   TS_CHECK(ts_allow_max_lds(lds_attr, reinterpret_cast<const void*>(kern)));
   const int64_t want = (p.nwork + SCAN_WAVES - 1) / SCAN_WAVES;
@@ -814,7 +638,7 @@ __device__ __forceinline__ void ts_static_for(F&& f) {
 // the compiler's choice.  Issue cost only: the MFMAs in flight keep running.)
 // The destination is written when the load lands, up to two windows after the statement, while the compiler takes it
 // as written at once: the kernel is correct only if the compiler neither copies nor spills a ring register in between.
-// It does neither while the kernel uses no scratch (every instantiation, tests/test_wide_ring_build.py).  A
+// It does neither while the kernel uses no scratch (every instantiation, tests/test_wide_prefetch_build.py).  A
 // TS_TUNING build without MFMAs spills, so there the loads are plain ones the compiler waits for.
 template <int I>
 __device__ __forceinline__ void wide_ring_load(u32x4& r, uint32_t loff, const unsigned char* fill) {
@@ -873,11 +697,12 @@ extern "C" int ts_debug_wide_trace(uint32_t* out) {
 #define WIDE_TRACE_END(nwindows) do { } while (0)
 #endif
 
-// scan_wide_tomb_kernel (TOMB = true, PR = WideTombParams), a copy of scan_wide_kernel's walk: removed rows are
-// dropped from the staged survivors at the flush (tomb_live), after the ring, so no load enters the walk; only a
-// survivor that finds the staging area full makes its batch overflow and be redone.
-template <int DT, int G, bool TOMB, class PR>
-__device__ __forceinline__ void scan_wide_body(const PR& p) {
+// One kernel template, like scan_multi_kernel: TOMB = false takes WideScanParams, TOMB = true WideTombParams.  In a
+// tombstone pass removed rows are dropped from the staged survivors at the flush (tomb_live), after the ring, so no
+// load enters the walk; only a survivor that finds the staging area full makes its batch overflow and be redone.
+template <int DT, int G, bool TOMB>
+__global__ __launch_bounds__(SCAN_THREADS) void scan_wide_kernel(
+    std::conditional_t<TOMB, WideTombParams, WideScanParams> p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   constexpr int WU = G * TS_RING * 64;   // 16-byte units per window buffer
   u32x4* win = reinterpret_cast<u32x4*>(smem);
@@ -1065,7 +890,7 @@ __device__ __forceinline__ void scan_wide_body(const PR& p) {
     WIDE_STAMP(2);
     advance_fill();
     if (qw == nwin - 1) {   // the row block's last window
-      epilogue_multi_tomb<G, 8, PR, StageWideHdr, TOMB>(p, st, sscore, skey, acc, tau, blk, keyhi, lane);
+      epilogue_multi<G, 8, TOMB>(p, st, sscore, skey, acc, tau, blk, keyhi, lane);
 #pragma unroll
       for (int hq = 0; hq < G; ++hq)
 #pragma unroll
@@ -1138,262 +963,6 @@ __device__ __forceinline__ void scan_wide_body(const PR& p) {
   }
 }
 
-template <int DT, int G>
-__global__ __launch_bounds__(SCAN_THREADS) void scan_wide_kernel(WideScanParams p) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  constexpr int WU = G * TS_RING * 64;   // 16-byte units per window buffer
-  u32x4* win = reinterpret_cast<u32x4*>(smem);
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int kg = p.kg;
-  const int nwin = kg / TS_RING;   // (ts_make_layout: kg is a multiple of TS_RING)
-
-  const int64_t nwaves = (int64_t)gridDim.x * SCAN_WAVES;
-  const int64_t w0 = (int64_t)blockIdx.x * SCAN_WAVES;
-  int64_t w = w0 + wave;
-  const bool active = w < p.nwork;
-  const size_t blk_units = (size_t)kg * 64;
-  int64_t blk = active ? p.blk0 + w * p.blk_stride : p.blk0;
-
-  // walks, in windows: this wave's (its row blocks x nwin) and the workgroup's longest (its wave 0's)
-  const int64_t my_iters = active ? (p.nwork - 1 - w) / nwaves + 1 : 0;
-  const int64_t wg_iters = w0 < p.nwork ? (p.nwork - 1 - w0) / nwaves + 1 : 0;
-  const int64_t tw_mine = my_iters * nwin, tw_all = wg_iters * nwin;
-
-  // The ring is two windows deep: window t of the walk computes from slots (t & 1) * TS_RING + i and refills them
-  // with window t + 2, so every corpus unit is requested a full window before the window that needs it starts.
-  // `fill` (wave-uniform, scalar) is the first byte of the window the next refill requests, `fwin` its window in the
-  // row block.  A lane adds its 16 bytes as a 32-bit offset.
-  const unsigned char* corpus = reinterpret_cast<const unsigned char*>(p.corpus);
-  const uint32_t loff = (uint32_t)lane * 16;
-  int64_t fw = w;
-  const unsigned char* fill = corpus + (size_t)blk * blk_units * 16;
-  // past the end of the walk the refills (two windows per wave, never consumed) read the first 8 KiB of group 0's
-  // query image instead: in bounds (an image holds kg >= TS_RING KiB per 32 queries), L2-resident (every window's
-  // requests read it), so no corpus bytes are fetched twice, and every window still issues TS_RING ring loads
-  const unsigned char* const fill_dead = reinterpret_cast<const unsigned char*>(p.gimg[0]);
-  bool fill_done = false;
-  int fwin = 0;
-  auto advance_fill = [&]() {
-    if (fill_done) return;
-    if (++fwin < nwin) {
-      fill += TS_RING * 1024;
-    } else if (fw + nwaves < p.nwork) {
-      fwin = 0;
-      fw += nwaves;
-      fill = corpus + (size_t)(p.blk0 + fw * p.blk_stride) * blk_units * 16;
-    } else {
-      fill_done = true;
-      fill = fill_dead;
-    }
-  };
-#if defined(TS_TUNING) && defined(DBG_WIDE_L2_RING)   // ablation builds only (wrong results): the ring reads one L2-resident 8 KiB
-  fill = fill_dead;
-  fill_done = true;
-#endif
-  // The ring's loads are inline asm too, and the walk waits for them itself (ring_wait): the compiler's waitcnt pass
-  // does not count the units' LDS-DMA, and for loads it counts it waits as if the ring were one window deep.
-  // Requests per wave, oldest first: the units of window t + 1 (G), then the ring loads of window t + 2 (TS_RING)
-  // at window t; so a slot's load is followed by (TS_RING - 1) + 2 * G + TS_RING younger ones when it is consumed.
-  auto refill = [&](u32x4& r, auto slot) { wide_ring_load<decltype(slot)::value>(r, loff, fill); };
-  auto ring_wait = [&](u32x4& r) {
-    __asm__ volatile("s_waitcnt vmcnt(%1)" : "+v"(r) : "i"(2 * TS_RING - 1 + 2 * G));
-  };
-
-  // this thread's share of every window: units tid + j*SCAN_THREADS (j < G) = k group v / G of the window, group
-  // v % G, v = wave + SCAN_WAVES*j (wave-uniform).  A wave's 64 lanes fill 64 consecutive units, so each share is
-  // one LDS-DMA (global_load_lds_dwordx4: per-lane source, LDS destination = wave-uniform base + lane * 16) from a
-  // wave-uniform source base plus the lane's 16 bytes: no registers hold the units, no ds_write copies them.
-  // (Inline asm, not the builtin: DESIGN.md §8.  The requests are invisible to the compiler's waitcnt pass, so its
-  // waits for the ring can only come out stricter; their own completion is the explicit vmcnt before each barrier.)
-  const unsigned char* qsrc[G];
-  int64_t qstep[G];   // bytes between windows
-#pragma unroll
-  for (int j = 0; j < G; ++j) {
-    const int v = wave + SCAN_WAVES * j, i = v / G, g = v - i * G;
-    const int gqh = pick_group<G>(p.gqh, g);
-    qsrc[j] = reinterpret_cast<const unsigned char*>(pick_group<G>(p.gimg, g)) +
-              (size_t)(i * gqh + pick_group<G>(p.ghalf, g)) * 1024;
-    qstep[j] = (int64_t)gqh * TS_RING * 1024;
-  }
-  const uint32_t win_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)(win + wave * 64);
-  // request window wi's units into buffer b
-  auto gather = [&](int wi, int b) {
-#pragma unroll
-    for (int j = 0; j < G; ++j) {
-      const unsigned char* src = qsrc[j] + wi * qstep[j];
-      const uint32_t dst = win_lds + (uint32_t)(b * WU + j * SCAN_THREADS) * 16;
-      // s_nop 4: the SGPR-base hazard of wide_ring_load.  s_nop 0: an LDS-DMA may read M0 one wait state after an
-      // SALU wrote it.  M0 is saved and restored: the compiler reserves it, and a clobber would not make it do so.
-      uint32_t keep;
-      __asm__ volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
-                       "global_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                       : "=&s"(keep) : "v"(loff), "s"(src), "s"(dst) : "memory");
-    }
-  };
-
-  StageWideHdr* st = reinterpret_cast<StageWideHdr*>(smem + (size_t)2 * WU * 16);
-  float* sscore = reinterpret_cast<float*>(st + 1);
-  uint32_t* skey = reinterpret_cast<uint32_t*>(sscore + p.stage_cap);
-  if (tid == 0) st->cnt = 0;
-
-  // (the thresholds are loaded before the ring: no load issued ahead of the walk is still pending inside it)
-  float tau[G];
-#pragma unroll
-  for (int hq = 0; hq < G; ++hq) tau[hq] = p.gtau[hq][lane & 31];
-#pragma unroll
-  for (int hq = 0; hq < G; ++hq) __asm__ volatile("" : "+v"(tau[hq]));   // (loaded here, not sunk into the walk)
-  // the ring's first window, window 0's query units, the ring's second window: the same order of requests as
-  // every later window's
-  u32x4 ring[2 * TS_RING];
-  if (active) {
-    ts_static_for<TS_RING>([&](auto i) { refill(ring[i], i); });
-    advance_fill();
-  }
-  gather(0, 0);
-  if (active) {
-    ts_static_for<TS_RING>([&](auto i) { refill(ring[TS_RING + i], i); });
-    advance_fill();
-    __builtin_amdgcn_s_waitcnt(0x3F70 | TS_RING);   // vmcnt(TS_RING)
-  } else {
-    __builtin_amdgcn_s_waitcnt(0x3F70);   // vmcnt(0)
-  }
-  fs_barrier();
-
-  uint32_t keyhi = (uint32_t)wave << 13;   // + (iteration << 16)
-
-  f32x16 acc[G];
-#pragma unroll
-  for (int hq = 0; hq < G; ++hq)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[hq][r] = 0.f;
-
-  // the walk's window barrier (fs_barrier: vmcnt untouched)
-  auto walk_barrier = [&]() {
-#if defined(TS_TUNING) && defined(DBG_WIDE_NO_BARRIER)   // ablation builds only (wrong results; with TS_DEBUG_TAU_INF=1)
-    __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0)
-#else
-    fs_barrier();
-#endif
-  };
-  // Window t of the wave's walk (k window qw of a row block), ring half and LDS buffer P = t & 1: request the next
-  // window's query units into the other buffer, run the window's TS_RING x G MFMAs and refill the ring half with
-  // window t + 2, wait for the units (vmcnt(TS_RING): this window's ring loads stay in flight) and meet the others
-  // at lgkmcnt(0) + s_barrier.  The other buffer was last read in window t - 1, before the previous barrier.
-  int qw = 0;
-  WIDE_TRACE_BEGIN();
-  auto window = [&](auto half) {
-    constexpr int P = decltype(half)::value;
-    const int qn = qw + 1 < nwin ? qw + 1 : 0;
-    gather(qn, P ^ 1);
-    WIDE_STAMP(0);
-    const u32x4* ql = win + P * WU + lane;
-#if !(defined(TS_TUNING) && defined(DBG_WIDE_SERIAL_B))
-    // slot 0's operands: the buffer is valid since the barrier that ended the window before
-    u32x4 bb[G];
-#pragma unroll
-    for (int hq = 0; hq < G; ++hq) bb[hq] = ql[hq * 64];
-#endif
-    WIDE_STAMP_READS(1);
-    ts_static_for<TS_RING>([&](auto i) {
-#if defined(TS_TUNING) && defined(DBG_WIDE_SERIAL_B)   // A/B only: one B register set, every MFMA waits for its own read
-      ring_wait(ring[P * TS_RING + i]);
-#pragma unroll
-      for (int hq = 0; hq < G; ++hq) {
-        const u32x4 b = ql[(i * G + hq) * 64];
-        mma_group<DT>(acc[hq], ring[P * TS_RING + i], b);
-      }
-#else
-      // rolling B operands: group hq's register set is re-read with the next slot's operand as soon as its MFMA has
-      // issued, so every read is G - 1 MFMAs ahead of its use (lgkmcnt(G - 1) before each MFMA, counted by the
-      // compiler; it counts down to 0 only in the window's last slot).  The sched_barriers pin that order: left
-      // alone the scheduler puts each read back in front of its MFMA.
-      __builtin_amdgcn_sched_barrier(0);
-      ring_wait(ring[P * TS_RING + i]);
-#pragma unroll
-      for (int hq = 0; hq < G; ++hq) {
-        mma_group<DT>(acc[hq], ring[P * TS_RING + i], bb[hq]);
-        __builtin_amdgcn_sched_barrier(0);
-        if constexpr (decltype(i)::value + 1 < TS_RING) {
-          bb[hq] = ql[((i + 1) * G + hq) * 64];
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-#endif
-      refill(ring[P * TS_RING + i], i);
-      __builtin_amdgcn_sched_barrier(0);
-    });
-    WIDE_STAMP(2);
-    advance_fill();
-    if (qw == nwin - 1) {   // the row block's last window
-      epilogue_multi<G, 8>(p, st, sscore, skey, acc, tau, blk, keyhi, lane);
-#pragma unroll
-      for (int hq = 0; hq < G; ++hq)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[hq][r] = 0.f;
-      w += nwaves;
-      blk = p.blk0 + w * p.blk_stride;
-      keyhi += 1u << 16;
-    }
-    WIDE_STAMP(3);
-    __builtin_amdgcn_s_waitcnt(0x3F70 | TS_RING);   // vmcnt(TS_RING)
-    WIDE_STAMP(4);
-    walk_barrier();
-    WIDE_STAMP(5);
-    qw = qn;
-  };
-  // Ring slots and buffers are compile-time, so the walk goes in pairs of windows (nwin may be odd).  The walk has
-  // no branch between a wave's computing windows: every window's waits see the same two windows of ring loads.
-  int64_t t = 0;
-  for (; t < tw_mine; t += 2) {
-    window(std::integral_constant<int, 0>{});
-    if (t + 1 == tw_mine) { ++t; break; }
-    window(std::integral_constant<int, 1>{});
-  }
-  // The last window's ring loads are still in flight, into registers the compiler now takes as free: nothing that
-  // follows may be written before they land.
-  __builtin_amdgcn_s_waitcnt(0x3F70);   // vmcnt(0)
-  // the workgroup's other waves are still walking: keep filling windows with them
-  for (; t < tw_all; ++t) {
-    const int qn = qw + 1 < nwin ? qw + 1 : 0;
-    gather(qn, (int)(t & 1) ^ 1);
-    __builtin_amdgcn_s_waitcnt(0x3F70);   // vmcnt(0)
-    walk_barrier();
-    qw = qn;
-  }
-  WIDE_TRACE_END(tw_mine);
-
-  // ---- flush: one global atomic per (workgroup, query) reserves the slots
-  __syncthreads();
-  const uint32_t n = st->cnt < p.stage_cap ? st->cnt : p.stage_cap;
-  if (n == 0) return;  // uniform: cnt is final after the barrier
-  for (int t = tid; t < G * 32; t += SCAN_THREADS) { st->qcnt[t] = 0; st->qoff[t] = 0; }
-  __syncthreads();
-  for (uint32_t e = tid; e < n; e += SCAN_THREADS) atomicAdd(&st->qcnt[skey[e] & 255u], 1u);
-  __syncthreads();
-  for (int t = tid; t < G * 32; t += SCAN_THREADS)
-    if (st->qcnt[t] > 0) st->qbase[t] = atomicAdd(pick_group<G>(p.gcnt, t >> 5) + (t & 31), st->qcnt[t]);
-  __syncthreads();
-  for (uint32_t e = tid; e < n; e += SCAN_THREADS) {
-    const uint32_t key = skey[e];
-    const uint32_t q = key & 255u;
-    const uint32_t slot = st->qbase[q] + atomicAdd(&st->qoff[q], 1u);
-    if (slot < p.cand_cap) {
-      const int g = (int)(q >> 5);
-      const size_t at = (size_t)(q & 31u) * p.cand_cap + slot;
-      const int64_t wi = (int64_t)blockIdx.x * SCAN_WAVES + ((key >> 13) & 7u) + (int64_t)(key >> 16) * nwaves;
-      pick_group<G>(p.gscore, g)[at] = sscore[e];
-      pick_group<G>(p.gid, g)[at] = (int32_t)((p.blk0 + wi * p.blk_stride) * TS_ROWS_PER_BLOCK + ((key >> 8) & 31u));
-    }
-  }
-}
-
-template <int DT, int G>
-__global__ __launch_bounds__(SCAN_THREADS) void scan_wide_tomb_kernel(WideTombParams p) {
-  scan_wide_body<DT, G, true>(p);
-}
-
 int ts_scan_wide_groups(const TsLayout& L) {
   if (L.dtype != TS_F16 && L.dtype != TS_BF16) return 0;
   return ts_scan_wide_stage_cap(L, TS_WIDE_GROUPS) > 0 ? TS_WIDE_GROUPS : 0;
@@ -1416,9 +985,7 @@ bool ts_scan_wide_fits(int64_t nblk, int num_cus) {
 template <int DT, int G, class P = WideScanParams>
 static int launch_scan_wide_t(const P& p, int num_cus, hipStream_t stream) {
   const size_t lds = (size_t)2 * G * TS_RING * 1024 + sizeof(StageWideHdr) + 8 * (size_t)p.stage_cap;
-  void (*kern)(P);
-  if constexpr (std::is_same<P, WideTombParams>::value) kern = scan_wide_tomb_kernel<DT, G>;
-  else kern = scan_wide_kernel<DT, G>;
+  void (*kern)(P) = scan_wide_kernel<DT, G, std::is_same<P, WideTombParams>::value>;
   static TsDeviceOnce lds_attr;
   TS_CHECK(ts_allow_max_lds(lds_attr, reinterpret_cast<const void*>(kern)));
   const int64_t want = (p.nwork + SCAN_WAVES - 1) / SCAN_WAVES;
