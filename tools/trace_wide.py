@@ -7,7 +7,8 @@ Submits `--batches` asynchronous batches of 64 queries (k = 1000) a few times, s
 pass of 2 x batches groups, and prints, per phase of scan_wide_kernel's window (ts_scan.hip, WIDE_TRACE), the mean
 time per window and its share of the walk, over the traced waves; plus the ratio of the s_memtime count to the
 100 MHz clock.  The stamps wait for the window's first-slot operand reads in one piece, which the untraced walk does not, so
-the traced pass is slightly slower than the untraced one."""
+the traced pass is slightly slower than the untraced one.  Each phase is also given for the first and the second half of
+a workgroup's waves: with staggered requests (TS_WIDE_STAGGER) the second half requests inside the slots phase."""
 import argparse
 import ctypes
 import json
@@ -51,6 +52,7 @@ def main():
     buf = (ctypes.c_uint32 * (WGS * WAVES * ROW))()
     assert lib.ts_debug_wide_trace(buf) == 0
     t = np.frombuffer(buf, dtype=np.uint32).reshape(WGS * WAVES, ROW).astype(np.float64)
+    half = (np.arange(WGS * WAVES) % WAVES >= WAVES // 2)[t[:, 8] > 0]   # the waves that request late when staggered
     t = t[t[:, 8] > 0]
     nwin = t[:, 8]
     walk_us = t[:, 6] / 100.0
@@ -67,9 +69,12 @@ def main():
         out["phases"][name] = {"ns_per_window_mean": round(float(per_win_ns.mean()), 1),
                                "ns_per_window_p5_p95": [round(float(np.percentile(per_win_ns, 5)), 1),
                                                         round(float(np.percentile(per_win_ns, 95)), 1)],
-                               "share_of_walk": round(float(share.mean()), 4)}
+                               "share_of_walk": round(float(share.mean()), 4),
+                               "ns_per_window_mean_waves_0_3_4_7": [round(float(per_win_ns[~half].mean()), 1),
+                                                                    round(float(per_win_ns[half].mean()), 1)]}
         print(f"  {k} {name:34s} {per_win_ns.mean():8.1f} ns per window (p5 {np.percentile(per_win_ns, 5):7.1f}, "
-              f"p95 {np.percentile(per_win_ns, 95):7.1f})  {100 * share.mean():5.1f} % of the walk")
+              f"p95 {np.percentile(per_win_ns, 95):7.1f})  {100 * share.mean():5.1f} % of the walk; "
+              f"waves 0-3 {per_win_ns[~half].mean():7.1f}, 4-7 {per_win_ns[half].mean():7.1f}")
     idx.close()
     if args.json:
         with open(args.json, "w") as f:

@@ -315,10 +315,18 @@ __device__ __forceinline__ T pick_group(const T (&a)[N], int g) {
 // TOMB (the tombstone passes of an index with removed rows): staged survivors are checked against the
 // live words when the workgroup flushes them (tomb_live), after the walk; a survivor that finds the staging area full
 // is not appended but makes its batch overflow (redone exactly).
+// The tests are wave-uniform: one ballot per group of the lanes whose largest score reaches the threshold (in a wide
+// pass of 192 queries about five row blocks in six have one), then in a group with a hit one ballot per accumulator
+// register, so the staging code runs with the execution mask of the lanes that hit.  The hit is marked unlikely: the
+// compiler then lays a group's 16 tests out as 16 x (v_cmp, s_cbranch_vccnz) in a row and the staging blocks behind
+// the loop, so a score that misses costs two instructions and no taken branch.  The row bound matters only in the
+// corpus's partial last row block (wave-uniform too).  The per-lane LDS atomicAdd of 1 compiles to one wave-aggregated
+// ds_add_rtn.  (-DTS_TUNING -DDBG_EPILOGUE_MASKS: the per-lane 16-bit masks this replaced, for A/B.)
 template <int G, int QB, bool TOMB, class P, class H>
 __device__ __forceinline__ void epilogue_multi(const P& p, H* st, float* sscore,
                                                uint32_t* skey, const f32x16 (&acc)[G], const float (&tau)[G],
                                                int64_t blk, uint32_t keyhi, int lane) {
+#if defined(TS_TUNING) && defined(DBG_EPILOGUE_MASKS)   // A/B only: per-lane masks, then 16 x G divergent blocks
   bool hit = false;
 #pragma unroll
   for (int hq = 0; hq < G; ++hq) hit |= (acc_max(acc[hq]) >= tau[hq]);
@@ -360,6 +368,53 @@ __device__ __forceinline__ void epilogue_multi(const P& p, H* st, float* sscore,
       }
     }
   }
+#else
+  uint64_t gm[G], any = 0;
+#pragma unroll
+  for (int hq = 0; hq < G; ++hq) {
+    gm[hq] = __builtin_amdgcn_ballot_w64(acc_max(acc[hq]) >= tau[hq]);
+    any |= gm[hq];
+  }
+  if (any == 0ull) return;
+  const int64_t row_base = blk * TS_ROWS_PER_BLOCK;
+  const bool partial = row_base + TS_ROWS_PER_BLOCK > p.ntotal;   // the corpus's last row block, wave-uniform
+  const int rows_left = (int)(p.ntotal - row_base);                // (its rows: read only if partial)
+#pragma unroll
+  for (int hq = 0; hq < G; ++hq) {
+    if (gm[hq] == 0ull) continue;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const bool ok = acc[hq][r] >= tau[hq];
+      if (__builtin_expect(__builtin_amdgcn_ballot_w64(ok) == 0ull, 1)) continue;
+      if (!ok) continue;
+      // (the lane as the staging code's own value: what is computed from it, rows and the lists' addresses, is then
+      // computed here and not kept in registers across the walk)
+      int ln = lane;
+      __asm__ volatile("" : "+v"(ln));
+      const int row = acc_row(r, ln), j = ln & 31;
+      if (!partial || row < rows_left) {
+        const uint32_t slot = atomicAdd(&st->cnt, 1u);  // LDS
+        if (slot < p.stage_cap) {
+          sscore[slot] = acc[hq][r];
+          skey[slot] = keyhi | ((uint32_t)row << QB) | (uint32_t)(hq * 32 + j);
+        } else {
+          // staging area full: append directly
+          // (TOMB: nothing here knows whether the row is live, so the count is pushed past the list's capacity:
+          // the select reports an overflow and the batch is redone exactly)
+          if constexpr (TOMB) {
+            atomicMax(&p.gcnt[hq][j], p.cand_cap + 1u);
+          } else {
+            const uint32_t g = atomicAdd(&p.gcnt[hq][j], 1u);
+            if (g < p.cand_cap) {
+              p.gscore[hq][(size_t)j * p.cand_cap + g] = acc[hq][r];
+              p.gid[hq][(size_t)j * p.cand_cap + g] = (int32_t)(row_base + row);
+            }
+          }
+        }
+      }
+    }
+  }
+#endif
 }
 
 // a staged survivor's row is live (after the walk: a plain load)
@@ -697,6 +752,17 @@ extern "C" int ts_debug_wide_trace(uint32_t* out) {
 #define WIDE_TRACE_END(nwindows) do { } while (0)
 #endif
 
+// Staggered requests: the slots whose MFMAs the second half of a workgroup's waves runs before it
+// requests the next window's units; -1: every wave requests right after the barrier.  Kept as an A/B switch only:
+// S = 1 .. 3 measured no gain at 10 M x 768 (the late waves are the window's critical path wherever their requests
+// stand), so the default build has none of it.
+#if defined(TS_TUNING) && defined(DBG_WIDE_STAGGER)   // A/B only
+#define TS_WIDE_STAGGER DBG_WIDE_STAGGER
+#else
+#define TS_WIDE_STAGGER (-1)
+#endif
+static_assert(TS_WIDE_STAGGER >= -1 && TS_WIDE_STAGGER < TS_RING - 1, "stagger slots");
+
 // One kernel template, like scan_multi_kernel: TOMB = false takes WideScanParams, TOMB = true WideTombParams.  In a
 // tombstone pass removed rows are dropped from the staged survivors at the flush (tomb_live), after the ring, so no
 // load enters the walk; only a survivor that finds the staging area full makes its batch overflow and be redone.
@@ -760,8 +826,14 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_wide_kernel(
   // Requests per wave, oldest first: the units of window t + 1 (G), then the ring loads of window t + 2 (TS_RING)
   // at window t; so a slot's load is followed by (TS_RING - 1) + 2 * G + TS_RING younger ones when it is consumed.
   auto refill = [&](u32x4& r, auto slot) { wide_ring_load<decltype(slot)::value>(r, loff, fill); };
-  auto ring_wait = [&](u32x4& r) {
-    __asm__ volatile("s_waitcnt vmcnt(%1)" : "+v"(r) : "i"(2 * TS_RING - 1 + 2 * G));
+  // (staggered requests, TS_WIDE_STAGGER = S >= 0: slots 0 .. S are consumed before the workgroup's late half of waves
+  // has requested anything in this window, so their loads have only 2 * TS_RING - 1 + G - slot younger ones there; the
+  // early half uses the same count, which makes it wait in addition only for ring loads two windows old and for units
+  // the last barrier already waited for)
+  auto ring_wait = [&](u32x4& r, auto slot) {
+    constexpr int I = decltype(slot)::value;
+    __asm__ volatile("s_waitcnt vmcnt(%1)" : "+v"(r)
+                     : "i"(I <= TS_WIDE_STAGGER ? 2 * TS_RING - 1 + G - I : 2 * TS_RING - 1 + 2 * G));
   };
 
   // this thread's share of every window: units tid + j*SCAN_THREADS (j < G) = k group v / G of the window, group
@@ -849,7 +921,16 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_wide_kernel(
   auto window = [&](auto half) {
     constexpr int P = decltype(half)::value;
     const int qn = qw + 1 < nwin ? qw + 1 : 0;
-    gather(qn, P ^ 1);
+    // Nothing is pending here after a window barrier; ahead of the first window the compiler may have started scalar
+    // loads of loop-invariant kernel arguments (the epilogue's) that it waits for only at their use.  With one of
+    // those counted as in flight it waits lgkmcnt(0) before slot 0's first MFMA in every window, for all G operand
+    // reads at once.
+    __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0)
+    // staggered requests: the waves of the workgroup's second half (w and w + SCAN_WAVES / 2 share a SIMD) run the
+    // MFMAs of slots 0 .. S before they request the units, while their SIMD partners request first.  Every wave defers
+    // the refills of slots 0 .. S until then, so a wave's requests keep their order: G units, then refills 0 .. 7.
+    const bool late = TS_WIDE_STAGGER >= 0 && wave >= SCAN_WAVES / 2;
+    if (!late) gather(qn, P ^ 1);
     WIDE_STAMP(0);
     const u32x4* ql = win + P * WU + lane;
 #if !(defined(TS_TUNING) && defined(DBG_WIDE_SERIAL_B))
@@ -861,7 +942,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_wide_kernel(
     WIDE_STAMP_READS(1);
     ts_static_for<TS_RING>([&](auto i) {
 #if defined(TS_TUNING) && defined(DBG_WIDE_SERIAL_B)   // A/B only: one B register set, every MFMA waits for its own read
-      ring_wait(ring[P * TS_RING + i]);
+      ring_wait(ring[P * TS_RING + i], i);
 #pragma unroll
       for (int hq = 0; hq < G; ++hq) {
         const u32x4 b = ql[(i * G + hq) * 64];
@@ -873,7 +954,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_wide_kernel(
       // compiler; it counts down to 0 only in the window's last slot).  The sched_barriers pin that order: left
       // alone the scheduler puts each read back in front of its MFMA.
       __builtin_amdgcn_sched_barrier(0);
-      ring_wait(ring[P * TS_RING + i]);
+      ring_wait(ring[P * TS_RING + i], i);
 #pragma unroll
       for (int hq = 0; hq < G; ++hq) {
         mma_group<DT>(acc[hq], ring[P * TS_RING + i], bb[hq]);
@@ -884,7 +965,12 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_wide_kernel(
         }
       }
 #endif
-      refill(ring[P * TS_RING + i], i);
+      if constexpr (decltype(i)::value == TS_WIDE_STAGGER) {
+        if (late) gather(qn, P ^ 1);
+        ts_static_for<TS_WIDE_STAGGER + 1>([&](auto k) { refill(ring[P * TS_RING + k], k); });
+      } else if constexpr (decltype(i)::value > TS_WIDE_STAGGER) {
+        refill(ring[P * TS_RING + i], i);
+      }
       __builtin_amdgcn_sched_barrier(0);
     });
     WIDE_STAMP(2);
