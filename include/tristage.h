@@ -53,7 +53,8 @@ extern "C" {
  * (TS_FLAG_WIDE_PASSES, TS_FLAG_NO_WIDE_PASSES, ts_coalesce_groups_wide, ts_coalesce_wide_min_bytes), and removal
  * (ts_index_remove, ts_index_live_count, ts_index_live_words, ts_index_compact): no existing signature changed, and
  * an index from which nothing is removed behaves as before; so was ts_remove_ivf.  So were ts_index_update and
- * ts_update_ivf: an index that is never updated runs the code it ran before.                                      */
+ * ts_update_ivf: an index that is never updated runs the code it ran before.  So was ts_compact_ivf: no existing
+ * signature changed, and an index that is never compacted runs the code it ran before.                            */
 #define TS_ABI_VERSION 4
 
 typedef struct ts_index ts_index; /* opaque */
@@ -577,16 +578,28 @@ int64_t ts_ivf_ntotal(const ts_ivf* h);
 /* removal, with the contract of ts_index_remove (ids as search returns them, HOST int64[n]; unknown, repeated and
  * removed ids not counted): the slot leaves its block's valid bits, so the scan and the thresholds (whose N_q counts
  * live probed rows) never see it again, and its list shrinks (ts_ivf_list_sizes counts live rows).  The hole stays
- * until reset + re-add; reconstruct still returns the stored row.  Added within version 4.                       */
+ * until ts_compact_ivf; reconstruct still returns the stored row.  Added within version 4.                        */
 /* (outside the ts_ivf_ prefix: that set of entry points is fixed by the IVF ABI tests) */
 int ts_remove_ivf(ts_ivf* h, const int64_t* ids, int64_t n, int64_t* n_removed, void* stream);
 /* update in place, with the contract of ts_index_update (all or nothing; rows DEVICE only, as ts_ivf_add).  Reference
  * call site: none (the reference never changes a stored vector).  Each row leaves its list exactly as ts_remove_ivf
  * makes it leave, is assigned by the quantizer exactly as ts_ivf_add assigns a new row, and is placed at the end of
- * its new list under its old id; ntotal does not change and the hole stays, as after a removal.  Added within
- * version 4; outside the ts_ivf_ prefix for the reason given above.                                              */
+ * its new list under its old id; ntotal does not change and the hole stays, as after a removal, until
+ * ts_compact_ivf.  Added within version 4; outside the ts_ivf_ prefix for the reason given above.                 */
 int ts_update_ivf(ts_ivf* h, const int64_t* ids, int64_t n, const void* rows, int32_t rows_dtype, uint32_t flags,
                   void* stream);
+/* compaction, with the contract of ts_index_compact: the live rows are renumbered densely in ascending id order,
+ * ntotal = live rows afterwards, and old2new (HOST int64[old ntotal] of ids before the id offset, -1 = removed; may be
+ * NULL) receives the monotone map.  The id offset and the centroids stay, and the quantizer is not run: a row stays in
+ * the list it is in.  The survivors are placed as ts_ivf_add places rows (in id order, each the next slot of its list,
+ * a list whose last block is full takes the next fresh block), so the index afterwards is the one a fresh handle with
+ * the same centroids holds after one add of the surviving rows: the same list sizes, blocks, reconstructed rows and
+ * search results bit for bit, now and after any later add / remove / update.  The holes of ts_update_ivf are closed
+ * too (the map is then the identity); an index without a hole is left untouched, one with no live row is left empty
+ * and trained.  All or nothing: the new corpus and tables are built beside the old ones (peak device memory: old +
+ * new corpus) and swapped in at the end; on an error the index is as it was.  Ordered on `stream`, synchronous.
+ * Added within version 4; outside the ts_ivf_ prefix for the reason given above.                                  */
+int ts_compact_ivf(ts_ivf* h, int64_t* old2new, void* stream);
 int ts_ivf_set_id_offset(ts_ivf* h, int64_t offset);
 int ts_ivf_last_search_info(const ts_ivf* h, int64_t info[4]);
 

@@ -85,6 +85,7 @@ SIGNATURES = {
     "ts_ivf_ntotal": (c_int64, [c_void_p]),
     "ts_remove_ivf": (c_int32, [c_void_p, c_void_p, c_int64, POINTER(c_int64), c_void_p]),
     "ts_update_ivf": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_uint32, c_void_p]),
+    "ts_compact_ivf": (c_int32, [c_void_p, c_void_p, c_void_p]),
     "ts_ivf_set_id_offset": (c_int32, [c_void_p, c_int64]),
     "ts_ivf_last_search_info": (c_int32, [c_void_p, POINTER(c_int64)]),
     "ts_merge_topk": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p,

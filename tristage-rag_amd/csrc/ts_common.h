@@ -407,3 +407,16 @@ int ts_launch_update_ivf_check(const int64_t* rows, int64_t n, const int64_t* id
 int ts_launch_update_ivf_place(const TsLayout& L, const uint4* src, uint4* corpus, const int64_t* dst,
                                const int64_t* ids, int64_t n, int64_t* slot2id, int64_t* id2slot, uint32_t* blk_valid,
                                hipStream_t stream);
+
+// ---------------------------------------------------------------- IVF compaction (ts_ivf_compact.hip)
+// lists[id] (DEVICE int32[ntotal]) = the list of id's row, or -1 when the id was removed
+int ts_launch_ivf_compact_classify(const int64_t* id2slot, const int64_t* slot2id, const int32_t* blk_list,
+                                   int64_t ntotal, int32_t* lists, hipStream_t stream);
+// Writes the new index beside the old one: new id j is old id new2old[j] and takes slot dst[j] (DEVICE int32[nlive],
+// the host's placement).  new_corpus (new_blocks row blocks, every byte written: padding slots are zero rows),
+// new_slot2id[32 * new_blocks] (-1 = padding), new_id2slot[nlive], new_valid[new_blocks]; src_slot: workspace,
+// int32[32 * new_blocks].
+int ts_launch_ivf_compact_move(const TsLayout& L, const uint4* old_corpus, const int64_t* old_id2slot,
+                               const int32_t* new2old, const int32_t* dst, int64_t nlive, int64_t new_blocks,
+                               uint4* new_corpus, int32_t* src_slot, int64_t* new_slot2id, int64_t* new_id2slot,
+                               uint32_t* new_valid, hipStream_t stream);

@@ -685,7 +685,7 @@ extern "C" int ts_ivf_reset(ts_ivf* h) {
 extern "C" int64_t ts_ivf_ntotal(const ts_ivf* h) { return h ? h->ntotal : -1; }
 
 // removal with the contract of ts_index_remove (include/tristage.h): removed ids keep their slots as holes until
-// reset + re-add; the live list sizes feed the thresholds' N_q
+// ts_compact_ivf; the live list sizes feed the thresholds' N_q
 extern "C" int ts_remove_ivf(ts_ivf* h, const int64_t* ids, int64_t n, int64_t* n_removed, void* stream) {
   if (!h || !n_removed || n < 0 || (n > 0 && !ids)) { ts_set_error("bad arguments to remove"); return TS_ERR_INVALID; }
   *n_removed = 0;
@@ -861,6 +861,28 @@ static int ivf_grow_blocks(ts_ivf* h, int64_t need, hipStream_t s) {
   return TS_OK;
 }
 
+// The placement rule of the index: rows take their slots in the order given, each the next slot of its list; a list
+// continues in its last block, and one whose last block is full (or that has none) takes the next fresh block at the
+// end.  asg[r] = list of row r (in [0, nlist); a negative entry is no row and gets dst -1).  Appends to list_blocks /
+// list_size and *nblocks; new_lists receives the list of every block taken, in block order.
+template <typename A, typename D>
+static void ivf_place(std::vector<std::vector<int32_t>>& list_blocks, std::vector<int64_t>& list_size, int64_t* nblocks,
+                      const A* asg, int64_t n, D* dst, std::vector<int32_t>* new_lists) {
+  int64_t nb = *nblocks;
+  for (int64_t r = 0; r < n; ++r) {
+    const int64_t l = (int64_t)asg[r];
+    if (l < 0) { dst[r] = (D)-1; continue; }
+    const int64_t pos = list_size[l];
+    if (pos % 32 == 0) {
+      list_blocks[l].push_back((int32_t)nb++);
+      new_lists->push_back((int32_t)l);
+    }
+    dst[r] = (D)((int64_t)list_blocks[l][pos / 32] * 32 + pos % 32);
+    ++list_size[l];
+  }
+  *nblocks = nb;
+}
+
 extern "C" int ts_ivf_add(ts_ivf* h, const void* rows, int64_t n, int32_t rows_dtype, uint32_t flags, void* stream) {
   if (!h) { ts_set_error("null handle"); return TS_ERR_INVALID; }
   if (n == 0) return TS_OK;
@@ -894,20 +916,12 @@ extern "C" int ts_ivf_add(ts_ivf* h, const void* rows, int64_t n, int32_t rows_d
     TS_HIP(hipMemcpyAsync(asg.data(), h->assign.p, (size_t)c * 8, hipMemcpyDeviceToHost, s));
     TS_HIP(hipStreamSynchronize(s));
     // slots: a list continues in its last block, then takes fresh blocks at the end; rows keep id order in a list
+    for (int64_t r = 0; r < c; ++r)
+      if (asg[r] < 0 || asg[r] >= h->nlist) { ts_set_error("add: bad assignment %lld", (long long)asg[r]); return TS_ERR_HIP; }
     const int64_t old_blocks = h->nblocks;
     int64_t nb = h->nblocks;
     std::vector<int32_t> new_lists;
-    for (int64_t r = 0; r < c; ++r) {
-      const int64_t l = asg[r];
-      if (l < 0 || l >= h->nlist) { ts_set_error("add: bad assignment %lld", (long long)l); return TS_ERR_HIP; }
-      const int64_t pos = h->list_size[l];
-      if (pos % 32 == 0) {
-        h->list_blocks[l].push_back((int32_t)nb++);
-        new_lists.push_back((int32_t)l);
-      }
-      dst[r] = (int64_t)h->list_blocks[l][pos / 32] * 32 + pos % 32;
-      ++h->list_size[l];
-    }
+    ivf_place(h->list_blocks, h->list_size, &nb, asg.data(), c, dst.data(), &new_lists);
     if (nb > old_blocks) TS_CHECK(ivf_grow_blocks(h, nb, s));
     h->nblocks = nb;
     TS_CHECK(ivf_grow(h->id2slot, (size_t)(h->ntotal + c) * 8, (size_t)h->ntotal * 8, s));
@@ -930,7 +944,7 @@ extern "C" int ts_ivf_add(ts_ivf* h, const void* rows, int64_t n, int32_t rows_d
 
 // update in place, with the contract of ts_index_update (include/tristage.h): each row leaves its list as
 // ts_remove_ivf makes it leave, is staged, read back and assigned as ts_ivf_add assigns a new row, and is placed at the
-// end of its new list under its old id.  The hole stays, as after a removal.
+// end of its new list under its old id.  The hole stays, as after a removal, until ts_compact_ivf.
 extern "C" int ts_update_ivf(ts_ivf* h, const int64_t* ids, int64_t n, const void* rows, int32_t rows_dtype,
                              uint32_t flags, void* stream) {
   if (!h || n < 0 || (n > 0 && (!ids || !rows)) ||
@@ -1000,16 +1014,7 @@ extern "C" int ts_update_ivf(ts_ivf* h, const int64_t* ids, int64_t n, const voi
     const int64_t old_blocks = h->nblocks;
     int64_t nb = h->nblocks;
     std::vector<int32_t> new_lists;
-    for (int64_t r = 0; r < c; ++r) {
-      const int64_t l = asg[r];
-      const int64_t pos = h->list_size[l];
-      if (pos % 32 == 0) {
-        h->list_blocks[l].push_back((int32_t)nb++);
-        new_lists.push_back((int32_t)l);
-      }
-      dst[r] = (int64_t)h->list_blocks[l][pos / 32] * 32 + pos % 32;
-      ++h->list_size[l];
-    }
+    ivf_place(h->list_blocks, h->list_size, &nb, asg.data(), c, dst.data(), &new_lists);
     if (nb > old_blocks) TS_CHECK(ivf_grow_blocks(h, nb, s));
     h->nblocks = nb;
     if (nb > old_blocks)
@@ -1022,6 +1027,111 @@ extern "C" int ts_update_ivf(ts_ivf* h, const int64_t* ids, int64_t n, const voi
     for (int l = 0; l < h->nlist; ++l) live_size[l] = h->list_size[l] - h->list_removed[l];
     TS_HIP(hipMemcpyAsync(h->dlist_size.p, live_size.data(), (size_t)h->nlist * 8, hipMemcpyHostToDevice, s));
     TS_HIP(hipStreamSynchronize(s));   // (staging reused by the next chunk; host tables read by the copies)
+  }
+  return TS_OK;
+}
+
+// Compaction (include/tristage.h): the index a fresh ts_ivf_add of the surviving rows, in id order and
+// into the lists they are in, would build.  Out of place and all or nothing: the new corpus and tables are written
+// beside the old ones (peak: old + new corpus) and take their place at the end; until then nothing of the index changes.
+namespace {
+struct IvfCompactBufs {   // the new index while it is built; after the swap, the old one
+  IvfBuf corpus, blk_list, blk_valid, slot2id, id2slot, dlist_size, src_slot;
+  ~IvfCompactBufs() {
+    IvfBuf* bufs[] = {&corpus, &blk_list, &blk_valid, &slot2id, &id2slot, &dlist_size, &src_slot};
+    for (IvfBuf* b : bufs) ivf_release(*b);
+  }
+};
+}  // namespace
+
+extern "C" int ts_compact_ivf(ts_ivf* h, int64_t* old2new, void* stream) {
+  if (!h) { ts_set_error("bad arguments to compact"); return TS_ERR_INVALID; }
+  const int64_t n = h->ntotal;
+  bool holes = false;
+  for (int l = 0; l < h->nlist; ++l) holes = holes || h->list_removed[l] != 0;
+  if (!holes) {   // (an empty index too) nothing to move
+    if (old2new)
+      for (int64_t i = 0; i < n; ++i) old2new[i] = i;
+    return TS_OK;
+  }
+  IvfGuard g(h->device);
+  hipStream_t s = (hipStream_t)stream;
+  // (1) the list of every id, -1 for a removed one
+  std::vector<int32_t> lists((size_t)n);
+  TS_CHECK(ivf_ensure(h->assign, (size_t)n * 4));
+  TS_CHECK(ts_launch_ivf_compact_classify((const int64_t*)h->id2slot.p, (const int64_t*)h->slot2id.p,
+                                          (const int32_t*)h->blk_list.p, n, (int32_t*)h->assign.p, s));
+  TS_HIP(hipMemcpyAsync(lists.data(), h->assign.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+  TS_HIP(hipStreamSynchronize(s));
+  // (2) the survivors in id order and their places, by the placement routine of add
+  std::vector<int64_t> live_size(h->nlist, 0);
+  int64_t nlive = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    const int32_t l = lists[i];
+    if (l >= h->nlist) { ts_set_error("compact: bad list %d of id %lld", (int)l, (long long)i); return TS_ERR_HIP; }
+    if (l >= 0) { ++live_size[l]; ++nlive; }
+  }
+  for (int l = 0; l < h->nlist; ++l)
+    if (live_size[l] != h->list_size[l] - h->list_removed[l]) {
+      ts_set_error("compact: list %d holds %lld live rows, its table says %lld", l, (long long)live_size[l],
+                   (long long)(h->list_size[l] - h->list_removed[l]));
+      return TS_ERR_HIP;
+    }
+  std::vector<int32_t> up((size_t)nlive * 2);   // new2old[nlive], then dst[nlive]
+  int32_t* new2old = up.data();
+  int32_t* dst = up.data() + nlive;
+  {
+    int64_t j = 0;
+    for (int64_t i = 0; i < n; ++i)
+      if (lists[i] >= 0) { new2old[j] = (int32_t)i; lists[j] = lists[i]; ++j; }   // (lists: now per new id)
+  }
+  std::vector<std::vector<int32_t>> new_blocks(h->nlist);
+  std::vector<int64_t> new_size(h->nlist, 0);
+  std::vector<int32_t> new_blk_list;
+  int64_t nb = 0;
+  for (int l = 0; l < h->nlist; ++l) new_blocks[l].reserve((size_t)((live_size[l] + 31) / 32));
+  ivf_place(new_blocks, new_size, &nb, lists.data(), nlive, dst, &new_blk_list);
+  // (3) the new corpus and tables beside the old ones
+  IvfCompactBufs nw;
+  TS_CHECK(ivf_ensure(nw.dlist_size, (size_t)h->nlist * 8));
+  TS_HIP(hipMemcpyAsync(nw.dlist_size.p, new_size.data(), (size_t)h->nlist * 8, hipMemcpyHostToDevice, s));
+  if (nlive > 0) {
+    TS_CHECK(ivf_ensure(nw.corpus, (size_t)nb * ts_block_bytes(h->L)));
+    TS_CHECK(ivf_ensure(nw.blk_list, (size_t)nb * 4));
+    TS_CHECK(ivf_ensure(nw.blk_valid, (size_t)nb * 4));
+    TS_CHECK(ivf_ensure(nw.slot2id, (size_t)nb * 32 * 8));
+    TS_CHECK(ivf_ensure(nw.id2slot, (size_t)nlive * 8));
+    TS_CHECK(ivf_ensure(nw.src_slot, (size_t)nb * 32 * 4));
+    TS_CHECK(ivf_ensure(h->dst, (size_t)nlive * 8));
+    TS_HIP(hipMemcpyAsync(h->dst.p, up.data(), (size_t)nlive * 8, hipMemcpyHostToDevice, s));
+    TS_HIP(hipMemcpyAsync(nw.blk_list.p, new_blk_list.data(), (size_t)nb * 4, hipMemcpyHostToDevice, s));
+    TS_CHECK(ts_launch_ivf_compact_move(h->L, (const uint4*)h->corpus.p, (const int64_t*)h->id2slot.p,
+                                        (const int32_t*)h->dst.p, (const int32_t*)h->dst.p + nlive, nlive, nb,
+                                        (uint4*)nw.corpus.p, (int32_t*)nw.src_slot.p, (int64_t*)nw.slot2id.p,
+                                        (int64_t*)nw.id2slot.p, (uint32_t*)nw.blk_valid.p, s));
+  }
+  TS_HIP(hipStreamSynchronize(s));
+  // (4) the swap: host state only from here on.  With no survivor the index keeps its (empty) buffers, as after reset.
+  std::swap(h->dlist_size, nw.dlist_size);
+  if (nlive > 0) {
+    std::swap(h->corpus, nw.corpus);
+    std::swap(h->blk_list, nw.blk_list);
+    std::swap(h->blk_valid, nw.blk_valid);
+    std::swap(h->slot2id, nw.slot2id);
+    std::swap(h->id2slot, nw.id2slot);
+  }
+  h->list_blocks.swap(new_blocks);
+  h->list_size.swap(new_size);
+  std::fill(h->list_removed.begin(), h->list_removed.end(), 0);
+  h->nblocks = nb;
+  h->ntotal = nlive;
+  if (old2new) {
+    int64_t j = 0, i = 0;
+    for (; j < nlive; ++j) {
+      for (; i < new2old[j]; ++i) old2new[i] = -1;
+      old2new[i++] = j;
+    }
+    for (; i < n; ++i) old2new[i] = -1;
   }
   return TS_OK;
 }

@@ -1233,12 +1233,12 @@ class IVFFlatIndex:
 
     @property
     def nlive(self) -> int:
-        """Rows not removed (``ntotal`` counts every id ever assigned)."""
+        """Rows not removed (``ntotal`` counts every id assigned since the last :meth:`compact` / :meth:`reset`)."""
         return int(self.list_sizes().sum())
 
     def remove_ids(self, ids) -> int:
         """:meth:`FlatIPIndex.remove_ids` for the IVF index: removed rows leave their lists (holes stay until
-        :meth:`reset` and a new add).  Returns how many rows were removed."""
+        :meth:`compact`).  Returns how many rows were removed."""
         if _is_tensor(ids):
             ids = ids.detach().cpu().numpy()
         arr = np.ascontiguousarray(np.asarray(ids, dtype=np.int64).reshape(-1))
@@ -1250,7 +1250,8 @@ class IVFFlatIndex:
     def update_rows(self, ids, x, normalize: bool = False) -> None:
         """:meth:`FlatIPIndex.update_rows` for the IVF index: each row leaves its list, is assigned by the quantizer as
         :meth:`add` assigns a new row and joins the end of its new list under its old id (the hole stays, as after a
-        removal).  All or nothing: an id out of range, given twice or removed raises ``ValueError``."""
+        removal, until :meth:`compact`).  All or nothing: an id out of range, given twice or removed raises
+        ``ValueError``."""
         if _is_tensor(ids):
             ids = ids.detach().cpu().numpy()
         arr = np.ascontiguousarray(np.asarray(ids, dtype=np.int64).reshape(-1))
@@ -1260,6 +1261,17 @@ class IVFFlatIndex:
         flags = _lib.TS_FLAG_NORMALIZE if normalize else 0
         _update_call(self._lib.ts_update_ivf, self._h, arr, ctypes.c_void_p(x.data_ptr()), _tensor_dtype(x), flags,
                      self._stream())
+
+    def compact(self) -> np.ndarray:
+        """:meth:`FlatIPIndex.compact` for the IVF index: the live rows are renumbered densely in id order, the holes of
+        removals and updates are closed and ``ntotal`` becomes :attr:`nlive`.  Rows stay in their lists and the
+        centroids and the id offset stay; afterwards the index is the one a fresh index with the same centroids holds
+        after ``add`` of the surviving rows.  Returns the old -> new map int64 [old ntotal] (-1 =
+        removed), monotone, so ties keep their order."""
+        n = self.ntotal
+        out = np.empty(max(n, 1), dtype=np.int64)
+        _lib.check(self._lib.ts_compact_ivf(self._h, out.ctypes.data_as(ctypes.c_void_p), self._stream()))
+        return out[:n]
 
     def train(self, x, seed: Optional[int] = None, niter: Optional[int] = None) -> None:
         x = self._dev(x, "training points")

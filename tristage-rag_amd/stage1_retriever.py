@@ -605,7 +605,7 @@ class Stage1Retriever:
         return 0 if r is None else int(np.count_nonzero(r))
 
     def _index_removes(self) -> bool:
-        """The dense index drops removed rows itself (FlatIPIndex tombstones)."""
+        """The dense index drops removed rows itself (FlatIPIndex tombstones, IVFFlatIndex list holes)."""
         return self.faiss_index is not None and hasattr(self.faiss_index, "remove_ids")
 
     def remove_documents(self, doc_ids) -> int:
@@ -613,9 +613,6 @@ class Stage1Retriever:
         their ids, their placeholder in ``documents`` / ``doc_metadata`` and their storage until :meth:`compact`.
         BM25 statistics stay those of every document added, as in Lucene, until :meth:`compact` refits them.
         Unknown and already removed ids are skipped; returns how many documents were removed."""
-        if getattr(self, "index_type_used", "flat") == "ivf":
-            raise NotImplementedError("remove_documents is not supported on an IVF pipeline index (index_type='ivf'); "
-                                      "IVFFlatIndex.remove_ids removes rows of the index itself")
         n = len(self.documents)
         ids = np.unique(np.asarray(doc_ids, dtype=np.int64).reshape(-1))
         ids = ids[(ids >= 0) & (ids < n)]
@@ -636,8 +633,10 @@ class Stage1Retriever:
         return int(ids.size)
 
     def compact(self) -> np.ndarray:
-        """Drops the removed documents for good: the index moves its live rows down (FlatIPIndex.compact), documents /
-        metadata lose their placeholders, BM25 is refitted on the survivors and the filter caches start over.
+        """Drops the removed documents for good: the index renumbers its live rows (FlatIPIndex.compact moves them
+        down; IVFFlatIndex.compact rewrites its lists without their holes and keeps the centroids), documents /
+        metadata lose their placeholders, BM25 is refitted on the survivors and the filter caches start over.  Only an
+        index object without ``compact`` (a custom index_factory) is rebuilt from its reconstructed rows.
         Returns the old -> new doc_id map (-1 = removed), monotone."""
         n = len(self.documents)
         live = self.live_mask()
