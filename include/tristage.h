@@ -130,6 +130,9 @@ int ts_index_add(ts_index* h, const void* rows, int64_t n, int32_t rows_dtype,
  * the row count the tail is padded with id -1 / score -FLT_MAX (FAISS's
  * convention, which the reference filters at src/stage1_retriever.py:383).
  * Ids are row numbers plus the offset set by ts_index_set_id_offset.
+ * The order in full ("selection order"): score descending with
+ * -0 equal to +0 (a zero comes back as +0); a NaN of either sign ranks below
+ * -inf; exactly equal scores by ascending id, whatever the size of the tie.
  * Synchronous with respect to `stream` on return.                            */
 int ts_index_search(ts_index* h, const void* queries, int32_t nq,
                     int32_t q_dtype, int32_t k, float* out_scores,
@@ -307,7 +310,15 @@ int ts_index_read_probe(ts_index* h, int32_t reps, double* ms_avg, double* ms_be
  * rank's ts_index_search result); writes the global top-k [nq, k] in the same
  * canonical order.  Entries with id < 0 are padding and ignored.  k <= 8192;
  * any number of lists (more than 16384 / k of them are merged in groups, then the
- * groups' results: the order is total, so the result is the same).            */
+ * groups' results: the order is total, so the result is the same).
+ * The order, as for ts_index_search: score descending with -0 equal to +0 (a
+ * zero comes back as +0); NaN of either sign or payload below -inf (it comes
+ * back as a NaN); exactly equal scores by ascending id, for any number of tied
+ * entries and wherever they sit in the lists (the lists need not be sorted);
+ * an id that occurs twice with one score occupies two places; the tail of a
+ * query with fewer than k valid entries is id -1 / score -FLT_MAX, also where
+ * the padding came in with another negative id.  The result does not depend
+ * on the run.                                                                */
 int ts_merge_topk(const float* scores, const int64_t* ids, int32_t nlists,
                   int32_t nq, int32_t k, float* out_scores, int64_t* out_ids,
                   int32_t device, void* stream);

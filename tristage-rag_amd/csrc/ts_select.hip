@@ -19,7 +19,7 @@
 
 #define SEL_THREADS 1024
 #define SEL_OUT_CAP 2048   // survivors kept by the in-LDS select (k <= 2048)
-#define SEL_TIE_CAP 1024   // MERGE64: entries whose score equals the k-th score
+#define SEL_TIE_CAP 1024   // MERGE64: entries whose score equals the k-th score (more: radix select on their ids)
 #define NEG_MAX (-3.402823466e38f)
 
 __device__ __forceinline__ uint32_t f2key(float f) {
@@ -80,6 +80,19 @@ __device__ __forceinline__ bool key_before(const SelParams& p, int64_t qbase, ui
   } else {
     return a > b;
   }
+}
+
+// SEL_MERGE64, more boundary ties than SEL_TIE_CAP: the rank of a tie entry's real id, larger = smaller id
+// (sign-biased, inverted), and the digits of it / of the key's low half that t radix passes have decided
+__device__ __forceinline__ uint64_t tie_id_rank(const SelParams& p, int64_t qbase, uint64_t key) {
+  const int64_t id = p.ids64[id_addr(p, qbase, 0xFFFFFFFFu - (uint32_t)key)];
+  return ~((uint64_t)id ^ 0x8000000000000000ull);
+}
+__device__ __forceinline__ uint64_t tie_prefix(uint64_t v, int t) {
+  return t >= 8 ? v : (t ? v >> (64 - 8 * t) : 0ull);
+}
+__device__ __forceinline__ uint32_t tie_prefix_lo(uint32_t lo, int t) {
+  return t <= 8 ? 0u : lo >> (96 - 8 * t);
 }
 
 // ---- shared pieces ----------------------------------------------------------
@@ -346,8 +359,56 @@ __global__ __launch_bounds__(SEL_THREADS) void select_kernel(SelParams p, uint32
       }
       __syncthreads();
       uint32_t c1 = sh[3], nt = sh[4];
-      if (nt > SEL_TIE_CAP) nt = SEL_TIE_CAP;  // > 1024 exact ties at the boundary: by position
-      if (nt > 0) {
+      if (nt > SEL_TIE_CAP) {
+        // More exact ties at the boundary than the tie list holds (what it caught is ignored).  The tie entries
+        // still sit in keys: a radix select over (id ascending, position ascending) — the 64 bits of the
+        // sign-biased id, then the 32 of the key's low half — finds the want-th of them, and every tie entry
+        // at or before it is a survivor.  It ends at the first bin that is wanted whole: with distinct ids
+        // within the eight id passes, and always by the twelfth (positions are unique).
+        // want >= nt (the k-th key is a padding key, the ties are NaN entries): no pass runs, every tie survives.
+        const uint32_t want = kk - c1;   // >= 1
+        uint64_t pid = 0ull;             // digits decided so far: of the id rank ...
+        uint32_t plo = 0u;               // ... and, from pass 8 on, of the position rank
+        uint32_t krem = want;
+        int t = 0;
+        while (want < nt && t < 12) {
+          if (tid < 256) hist[tid] = 0;
+          __syncthreads();
+          for (uint32_t base = 0; base < count; base += SEL_THREADS) {
+            const uint32_t i = base + tid;
+            const uint64_t key = (i < count) ? keys[i] : 0ull;
+            bool in = key != 0ull && (uint32_t)(key >> 32) == sT;
+            uint32_t digit = 0;
+            if (in) {
+              const uint64_t v = tie_id_rank(p, qbase, key);
+              const uint32_t lo = (uint32_t)key;
+              in = tie_prefix(v, t) == pid && tie_prefix_lo(lo, t) == plo;
+              digit = t < 8 ? (uint32_t)(v >> (56 - 8 * t)) & 0xFFu : (lo >> (88 - 8 * t)) & 0xFFu;
+            }
+            hist_vote(hist, in, digit, tid);
+          }
+          __syncthreads();
+          find_digit(hist, krem, sh, wtot, tid);
+          if (t < 8) pid = (pid << 8) | (uint64_t)sh[0];
+          else plo = (plo << 8) | sh[0];
+          krem = sh[1];
+          ++t;
+          const bool done = sh[2] != 0;
+          __syncthreads();
+          if (done) break;
+        }
+        for (uint32_t i = tid; i < count; i += SEL_THREADS) {
+          const uint64_t key = keys[i];
+          if (key == 0ull || (uint32_t)(key >> 32) != sT) continue;
+          const uint64_t vp = tie_prefix(tie_id_rank(p, qbase, key), t);
+          if (vp > pid || (vp == pid && tie_prefix_lo((uint32_t)key, t) >= plo)) {
+            const uint32_t pos = atomicAdd(&sh[3], 1u);
+            if (pos < SEL_OUT_CAP) outk[pos] = key;
+          }
+        }
+        __syncthreads();
+        c1 = sh[3];
+      } else if (nt > 0) {
         uint32_t pt = 2;
         while (pt < nt) pt <<= 1;
         for (uint32_t i = nt + tid; i < pt; i += SEL_THREADS) ties[i] = 0ull;
