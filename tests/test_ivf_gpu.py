@@ -6,20 +6,12 @@ import torch
 
 from oracle import oracle
 
+from ivf_train_model import mixture
 from tristage_rag_amd.index import FlatIPIndex, IVFFlatIndex
 
 pytestmark = pytest.mark.gpu
 
 TORCH_DT = {"f16": torch.float16, "bf16": torch.bfloat16}
-
-
-def mixture(n, d, centers=40, seed=0, spread=0.35):
-    """Seeded Gaussian mixture on the sphere (float32)."""
-    rng = np.random.default_rng(seed)
-    c = rng.standard_normal((centers, d)).astype(np.float32)
-    c /= np.linalg.norm(c, axis=1, keepdims=True)
-    x = c[rng.integers(0, centers, n)] + spread * rng.standard_normal((n, d)).astype(np.float32) / np.sqrt(d) * 4
-    return (x / np.linalg.norm(x, axis=1, keepdims=True)).astype(np.float32)
 
 
 def dev(x, dt):
