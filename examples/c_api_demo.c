@@ -5,7 +5,8 @@
  *   ./examples/c_api_demo <n> <d> <k> <nq> <out.bin>
  * Builds a deterministic corpus on the host, adds it (host pointers), searches,
  * and writes  [float scores nq*k][int64 ids nq*k]  so a test can compare with the
- * oracle computed from the same generator (tests/test_c_api_gpu.py).
+ * oracle computed from the same generator (tests/test_c_api_gpu.py).  Then a range search with each query's k-th
+ * score as its radius (ts_index_range_search, ts_index_range_fetch): at least k rows per query, ids ascending.
  */
 #include <math.h>
 #include <stdint.h>
@@ -61,6 +62,25 @@ int main(int argc, char** argv) {
   CHECK(ts_index_last_search_info(h, info));
   printf("abi %d  ntotal %lld  path %lld  best[0] id %lld score %.6f\n", ts_abi_version(),
          (long long)ts_index_ntotal(h), (long long)info[0], (long long)I[0], D[0]);
+  /* range search: every row scoring at least the query's k-th best (inclusive), CSR form, ids ascending */
+  float* radius = (float*)malloc(sizeof(float) * (size_t)nq);
+  int64_t* lims = (int64_t*)malloc(sizeof(int64_t) * ((size_t)nq + 1));
+  if (!radius || !lims) return 3;
+  for (int q = 0; q < nq; ++q) radius[q] = D[(size_t)q * k + (k - 1)];
+  CHECK(ts_index_range_search(h, queries, nq, TS_F32, radius, NULL, 0, 0, NULL, 0, lims, TS_FLAG_HOST_PTR, NULL));
+  const int64_t total = lims[nq];
+  float* RD = (float*)malloc(sizeof(float) * (size_t)(total + 1));
+  int64_t* RI = (int64_t*)malloc(sizeof(int64_t) * (size_t)(total + 1));
+  if (!RD || !RI) return 3;
+  if (ts_index_range_fetch(h, RD, RI, total - 1, TS_FLAG_HOST_PTR, NULL) != TS_ERR_INVALID) return 7; /* too small */
+  CHECK(ts_index_range_fetch(h, RD, RI, total, TS_FLAG_HOST_PTR, NULL));
+  for (int q = 0; q < nq; ++q) {
+    if (lims[q + 1] - lims[q] < (k < n ? k : n)) return 7;
+    for (int64_t e = lims[q]; e < lims[q + 1]; ++e)
+      if (RD[e] < radius[q] || (e > lims[q] && RI[e] <= RI[e - 1])) return 7;
+  }
+  printf("range results %lld (first query %lld)\n", (long long)total, (long long)(lims[1] - lims[0]));
+  free(radius); free(lims); free(RD); free(RI);
   FILE* f = fopen(argv[5], "wb");
   if (!f) return 6;
   fwrite(D, sizeof(float), (size_t)nq * k, f);

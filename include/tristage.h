@@ -54,7 +54,9 @@ extern "C" {
  * (ts_index_remove, ts_index_live_count, ts_index_live_words, ts_index_compact): no existing signature changed, and
  * an index from which nothing is removed behaves as before; so was ts_remove_ivf.  So were ts_index_update and
  * ts_update_ivf: an index that is never updated runs the code it ran before.  So was ts_compact_ivf: no existing
- * signature changed, and an index that is never compacted runs the code it ran before.                            */
+ * signature changed, and an index that is never compacted runs the code it ran before.  So were ts_index_range_search
+ * and ts_index_range_fetch: no existing signature changed, and a caller that never runs a range search sees the
+ * library it was built against (no existing kernel changed).                                                    */
 #define TS_ABI_VERSION 4
 
 typedef struct ts_index ts_index; /* opaque */
@@ -166,6 +168,44 @@ int ts_index_search_filtered(ts_index* h, const void* queries, int32_t nq, int32
  * call [0] is complete after ts_index_finish.  The redo of a ticket that ts_index_finish reports is a new
  * ts_index_search_filtered call: read the counters of the submitted searches before it.                */
 int ts_index_last_filter_info(const ts_index* h, int64_t info[4]);
+
+/* ---- range search ----------------------------------------------------------
+ * FAISS range_search: for query q with radius[q] (a float32 on the index's score scale) every live row with
+ * score(q, row) >= radius[q]; with masks, only the allowed rows count.  Added within version 4.
+ *   - The bound is inclusive; the comparison is the float >= of the filter scan.  A NaN score is never returned.
+ *     A NaN radius is TS_ERR_INVALID before any HIP call.  -inf returns every live (allowed) row.
+ *   - Scores are bit-identical to those of ts_index_search / ts_index_scores on the same rows (same query image,
+ *     same MFMA k-group order).
+ *   - The result is in FAISS's CSR form: lims (HOST int64[nq + 1]); query q owns entries [lims[q], lims[q + 1]) of
+ *     the packed scores and ids.  WITHIN A QUERY THE ROWS ARE IN ASCENDING ID ORDER, on every path (FAISS promises
+ *     no order).  Ids carry the id offset.  Removed rows are never returned; after ts_index_compact the ids are the
+ *     new ones.
+ *   - Every storage type, any nq (passes of <= 64 queries), tombstones, and masks with the semantics of
+ *     ts_index_search_filtered (allow_bits / allow_words / n_masks / mask_of_query as there, ANDed with the live
+ *     set); mask_of_query may be NULL: unfiltered.  radius is a HOST array of nq floats.
+ *   - Synchronous only; held coalesced passes are flushed first.  Flags: TS_FLAG_HOST_PTR (queries and masks are host
+ *     memory), TS_FLAG_NO_FILTER (force the dense path: tests, A/B runs).
+ *   - max_total bounds the number of entries of the call (<= 0: 1 << 26 entries, 12 bytes each).  Every pass's total
+ *     is known on the host before anything of it is written; if the running total would pass the limit the call
+ *     returns TS_ERR_UNSUPPORTED, lims hold the counts so far (flat behind them), ts_last_error() names the total and
+ *     the limit, nothing is stored and the index stays usable.
+ * Per pass: the query image; then, from 32768 rows, the filter scan of ts_index_search with the radii as its
+ * thresholds (its masked form with masks or tombstones), whose per-query counts are exact also past its 16384
+ * candidate slots; if no count exceeds them, one workgroup per query sorts its (id, score) pairs by id.  Otherwise,
+ * and for smaller corpora and fp32 storage with masks or tombstones, the whole pass takes the dense path: dense scores
+ * in chunks of 2^20 rows, counted per 1024-row tile, prefixed, and written in place by rank.
+ * The packed result stays in the handle: ts_index_range_fetch copies the lims[nq] entries of the last range search to
+ * out_scores (float) / out_ids (int64), device memory or host memory with TS_FLAG_HOST_PTR; a capacity (entries) that
+ * is too small is TS_ERR_INVALID.  The stored result is valid until the next range search, add, remove, update,
+ * compact, reset or destroy on the handle.  ts_index_last_search_info after a range call: [0] 32 + (0 every pass
+ * dense, 1 filter scans, 2 a filter pass was redone densely), [1] passes, [2] passes that ran the filter scan,
+ * [3] those of them that were redone densely.                                                                    */
+int ts_index_range_search(ts_index* h, const void* queries, int32_t nq, int32_t q_dtype, const float* radius,
+                          const uint32_t* allow_bits, int64_t allow_words, int32_t n_masks,
+                          const int32_t* mask_of_query, int64_t max_total, int64_t* lims, uint32_t flags,
+                          void* stream);
+int ts_index_range_fetch(ts_index* h, float* out_scores, int64_t* out_ids, int64_t capacity, uint32_t flags,
+                         void* stream);
 
 /* ---- all scores, no selection -----------------------------------------------
  * replaces the numpy product in EmbeddingService.similarity (reference
@@ -283,7 +323,7 @@ int ts_index_reconstruct(ts_index* h, int64_t row0, int64_t n, float* out,
 /* counters of the last search on this handle: [0] path taken (low 4 bits: 0 dense,
  * 1 filter, 2 filter-then-dense fallback; +16 when the filter ran as the
  * one-launch scan), [1] max candidates per query, [2] sample rows,
- * [3] sample rank m                                                          */
+ * [3] sample rank m.  After ts_index_range_search: see "range search".       */
 int ts_index_last_search_info(const ts_index* h, int64_t info[4]);
 
 /* Per-phase device timing of searches, measured with HIP events recorded on the

@@ -47,6 +47,9 @@ SIGNATURES = {
     "ts_index_search_filtered": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int64, c_int32,
                                            c_void_p, c_void_p, c_void_p, c_uint32, c_void_p]),
     "ts_index_last_filter_info": (c_int32, [c_void_p, POINTER(c_int64)]),
+    "ts_index_range_search": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_int32,
+                                        c_void_p, c_int64, c_void_p, c_uint32, c_void_p]),
+    "ts_index_range_fetch": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_uint32, c_void_p]),
     "ts_index_scores": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int64, c_void_p]),
     "ts_index_remove": (c_int32, [c_void_p, c_void_p, c_int64, POINTER(c_int64), c_void_p]),
     "ts_index_update": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_uint32, c_void_p]),

@@ -341,6 +341,49 @@ int ts_launch_select(const SelParams& p, int nq, hipStream_t stream);
 int ts_launch_tau(const float* sample, int64_t ld, uint32_t n, uint32_t m,
                   int nq, float* tau, hipStream_t stream);
 
+// ---------------------------------------------------------------- range search (ts_range.hip)
+// Results in CSR form: query q of the pass owns out[off[q] .. off[q + 1]) of the call's result buffers (`capacity`
+// entries), rows in ascending id order.  off[] comes from counts the host has read before the launch.
+#define TS_RANGE_TILE 1024   // rows per tile of the dense path
+// Small path: the filter scan's lists (cand_cap entries per query, cnt[q] <= cand_cap of them valid) sorted by id.
+struct TsRangeSortParams {
+  const float* cand_score;
+  const int32_t* cand_id;
+  uint32_t cand_cap;
+  uint32_t cnt[TS_MAX_Q];
+  int64_t off[TS_MAX_Q + 1];
+  float* out_scores;
+  int64_t* out_ids;
+  int64_t capacity;
+  int64_t id_offset;
+};
+int ts_launch_range_sort(const TsRangeSortParams& p, int nq, uint32_t max_count, hipStream_t stream);
+// Dense path, one chunk of dense scores: dense[q * ld + i] is the score of row row0 + i, i < rows; mids (may be null)
+// holds >= 0 where the row is allowed for the query (ts_launch_mask_ids).  The chunk's tiles are tile0 .. tile0 +
+// chunk_tiles of the pass's ntiles; tilecnt[q * ntiles + t]: the count kernel writes the survivors of tile t, the
+// prefix kernel turns a query's line into its exclusive prefix (total[q] = the sum), the fill kernel reads that.
+struct TsRangeDenseParams {
+  const float* dense;
+  const int32_t* mids;
+  int64_t ld;
+  int64_t row0;
+  uint32_t rows;
+  uint32_t chunk_tiles;
+  int64_t tile0;
+  int64_t ntiles;
+  uint32_t* tilecnt;
+  float radius[TS_MAX_Q];
+  // fill only
+  int64_t off[TS_MAX_Q + 1];
+  float* out_scores;
+  int64_t* out_ids;
+  int64_t capacity;
+  int64_t id_offset;
+};
+int ts_launch_range_count(const TsRangeDenseParams& p, int nq, hipStream_t stream);
+int ts_launch_range_prefix(uint32_t* tilecnt, int64_t ntiles, int nq, uint32_t* total, hipStream_t stream);
+int ts_launch_range_fill(const TsRangeDenseParams& p, int nq, hipStream_t stream);
+
 // ---------------------------------------------------------------- maxsim
 int ts_launch_maxsim(const void* q, int Lq, const void* docs,
                      const int32_t* doc_off, const int64_t* starts, const int32_t* lens,

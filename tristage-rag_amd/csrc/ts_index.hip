@@ -204,6 +204,13 @@ struct ts_index {
   std::mutex eff_mu;
   hipEvent_t eff_ev = nullptr;
   bool eff_used = false;
+  // range search (ts_index_range_search): the packed result of the last call (rng_cap entries
+  // allocated, rng_total valid), kept for ts_index_range_fetch until the next range search or a change of the index;
+  // rng_tiles: the dense path's per-query totals and tile counts.  range_mu serialises range calls on the handle.
+  DevBuf rng_s, rng_i, rng_tiles;
+  int64_t rng_cap = 0, rng_total = 0;
+  bool rng_valid = false;
+  std::mutex range_mu;
 };
 
 static int co_flush(ts_index* h, hipStream_t s);
@@ -357,7 +364,8 @@ extern "C" int ts_index_destroy(ts_index* h) {
   for (hipEvent_t e : h->async_ev)
     if (e) (void)hipEventDestroy(e);
   if (h->co_ev) (void)hipEventDestroy(h->co_ev);
-  DevBuf* rb[] = {&h->live, &h->eff, &h->rids, &h->compact_scratch, &h->compact_stage, &h->upd_tile, &h->upd_tab};
+  DevBuf* rb[] = {&h->live, &h->eff, &h->rids, &h->compact_scratch, &h->compact_stage, &h->upd_tile, &h->upd_tab,
+                  &h->rng_s, &h->rng_i, &h->rng_tiles};
   for (DevBuf* b : rb) release(*b);
   if (h->eff_ev) (void)hipEventDestroy(h->eff_ev);
   delete h;
@@ -367,6 +375,7 @@ extern "C" int ts_index_destroy(ts_index* h) {
 extern "C" int ts_index_reset(ts_index* h) {
   if (!h) { ts_set_error("null handle"); return TS_ERR_INVALID; }
   { DeviceGuard g(h->device); TS_CHECK(co_flush(h, nullptr)); }   // held passes search the corpus they were submitted against
+  h->rng_valid = false;
   h->ntotal = 0;
   h->nremoved = 0;
   return TS_OK;
@@ -427,6 +436,7 @@ extern "C" int ts_index_add(ts_index* h, const void* rows, int64_t n, int32_t ro
   DeviceGuard g(h->device);
   hipStream_t s = (hipStream_t)stream;
   TS_CHECK(co_flush(h, s));   // held passes search the corpus they were submitted against
+  h->rng_valid = false;       // a stored range result describes the index as it was
   const int64_t need_blocks = (h->ntotal + n + TS_ROWS_PER_BLOCK - 1) / TS_ROWS_PER_BLOCK;
   TS_CHECK(grow_corpus(h, need_blocks, false, s));
   const bool norm = (flags & TS_FLAG_NORMALIZE) != 0;
@@ -1554,6 +1564,373 @@ extern "C" int ts_index_last_filter_info(const ts_index* h, int64_t info[4]) {
   return TS_OK;
 }
 
+// ---- range search (include/tristage.h "range search")
+namespace {
+constexpr int64_t kRangeDefaultMax = 1ll << 26;   // entries (12 bytes each) a call may return by default
+struct RangeStats { int64_t passes = 0, filter_passes = 0, dense_redo = 0; };
+struct SetHold {
+  ts_index* h; ts_index::WSet* W;
+  ~SetHold() { if (W) release_set(h, W); }
+};
+}  // namespace
+
+// The result buffers hold `need` entries, of which the first `have` are kept.
+static int range_reserve(ts_index* h, int64_t need, int64_t have, int64_t limit, hipStream_t s) {
+  if (need <= h->rng_cap) return TS_OK;
+  int64_t cap = std::max<int64_t>(need, std::min<int64_t>(limit, 2 * h->rng_cap));
+  cap = std::max<int64_t>(cap, 1 << 16);
+  DevBuf ns, ni;
+  int st = ensure(ns, (size_t)cap * 4);
+  if (st == TS_OK) st = ensure(ni, (size_t)cap * 8);
+  if (st == TS_OK && have > 0 &&
+      (hipMemcpyAsync(ns.p, h->rng_s.p, (size_t)have * 4, hipMemcpyDeviceToDevice, s) != hipSuccess ||
+       hipMemcpyAsync(ni.p, h->rng_i.p, (size_t)have * 8, hipMemcpyDeviceToDevice, s) != hipSuccess)) {
+    ts_set_error("range search: copying the result so far failed");
+    st = TS_ERR_HIP;
+  }
+  // (the old buffers are freed below: everything that reads or writes them has to be over)
+  if (st == TS_OK && hipStreamSynchronize(s) != hipSuccess) { ts_set_error("hipStreamSynchronize failed"); st = TS_ERR_HIP; }
+  if (st != TS_OK) { release(ns); release(ni); return st; }
+  release(h->rng_s);
+  release(h->rng_i);
+  h->rng_s = ns;
+  h->rng_i = ni;
+  h->rng_cap = cap;
+  return TS_OK;
+}
+
+// One chunk of the dense path: the dense scan of rows [row0, row0 + rows) into W.dense, the allowed ids into W.mids.
+static int range_dense_chunk(ts_index* h, ts_index::WSet& W, int nq, int qh, int64_t row0, int64_t rows,
+                             int64_t chunk_rows, const MaskCtx* mc, hipStream_t s) {
+  ScanParams sp{};
+  sp.corpus = h->corpus;
+  sp.qimg = (const uint4*)W.qimg.p;
+  sp.kg = h->L.kg;
+  sp.nq = nq;
+  sp.nwork = (rows + TS_ROWS_PER_BLOCK - 1) / TS_ROWS_PER_BLOCK;
+  sp.blk0 = row0 / TS_ROWS_PER_BLOCK;
+  sp.blk_stride = 1;
+  sp.ntotal = h->ntotal;
+  sp.dense = (float*)W.dense.p;
+  sp.dense_ld = chunk_rows;
+  TS_CHECK(ts_launch_scan(h->L, SCAN_DENSE, qh, sp, h->num_cus, s));
+  if (mc)
+    TS_CHECK(ts_launch_mask_ids(mc->bits, mc->words, mc->mp, nq, row0, (uint32_t)rows, chunk_rows, (int32_t*)W.mids.p, s));
+  return TS_OK;
+}
+
+// One pass of <= 64 queries (device pointers).  rad: the pass's radii (HOST).  *total: entries of the call so far; the
+// pass appends its own behind them and writes lims[1 .. nq] (lims[0] is the pass's first offset, already set).
+static int range_pass(ts_index* h, const void* dq, int nq, int q_dtype, const float* rad, const MaskCtx* mc,
+                      uint32_t flags, int64_t limit, int64_t* total, int64_t* lims, RangeStats* stats, hipStream_t s) {
+  const int64_t N = h->ntotal;
+  const int64_t nblk = (N + TS_ROWS_PER_BLOCK - 1) / TS_ROWS_PER_BLOCK;
+  const int qh = nq > 32 ? 2 : 1;
+  SetHold hold{h, acquire_set(h)};
+  ts_index::WSet& W = *hold.W;
+  if (W.used && hipEventQuery(W.ev_sel) != hipSuccess) TS_HIP(hipStreamWaitEvent(s, W.ev_sel, 0));
+  // the query image of search_pass_on; the scan's counts start from zero
+  TS_CHECK(ts_launch_qprep(h->L, dq, q_dtype, nq, qh, (uint4*)W.qimg.p, W.cand_cnt(), W.status(), s));
+  // (fp32 storage with a mask or tombstones: the dense path, as its filtered top-k search)
+  const bool filter = !(flags & TS_FLAG_NO_FILTER) && N >= kMinFilterRows && !(mc && h->L.dtype == TS_F32);
+  stats->passes += 1;
+  uint32_t cnt[TS_MAX_Q] = {0};
+  float tau[TS_MAX_Q];
+  for (int j = 0; j < TS_MAX_Q; ++j) tau[j] = j < nq ? rad[j] : 3.402823466e38f;
+  bool dense = !filter;
+  if (filter) {
+    stats->filter_passes += 1;
+    TS_HIP(hipMemcpyAsync(W.tau(), tau, sizeof(tau), hipMemcpyHostToDevice, s));
+    TS_CHECK(ensure(W.cand_score, (size_t)TS_MAX_Q * kCandCap * 4));
+    TS_CHECK(ensure(W.cand_id, (size_t)TS_MAX_Q * kCandCap * 4));
+    ScanParams sp{};
+    sp.corpus = h->corpus;
+    sp.qimg = (const uint4*)W.qimg.p;
+    sp.kg = h->L.kg;
+    sp.nq = nq;
+    sp.ntotal = N;
+    sp.nwork = nblk;
+    sp.blk0 = 0;
+    sp.blk_stride = 1;
+    sp.tau = W.tau();
+    sp.cand_cnt = W.cand_cnt();
+    sp.cand_score = (float*)W.cand_score.p;
+    sp.cand_id = (int32_t*)W.cand_id.p;
+    sp.cand_cap = kCandCap;
+    const int scan_cus = h->num_cus - h->num_cus / 8;
+    if (mc) {
+      TS_CHECK(ensure(W.mask, sizeof(TsMaskDev) + (size_t)nblk * 4));
+      TsMaskDev* md = (TsMaskDev*)W.mask.p;
+      TS_HIP(hipMemsetAsync(md, 0, sizeof(TsMaskDev), s));
+      TS_CHECK(ts_launch_live_blocks(mc->bits, mc->words, mc->mp, nblk, N, md, s));
+      MaskedScanParams mp{};
+      static_cast<ScanParams&>(mp) = sp;
+      mp.live = reinterpret_cast<const int32_t*>(md + 1);
+      mp.nlive = &md->nlive;
+      mp.allow_bits = mc->bits;
+      mp.allow_words = mc->words;
+      mp.qmask = md->qmask;
+      TS_CHECK(ts_launch_scan_masked(h->L, qh, mp, scan_cus, s));
+    } else {
+      TS_CHECK(ts_launch_scan(h->L, SCAN_FILTER, qh, sp, scan_cus, s));
+    }
+    // the counts are exact, also past the cap: every survivor's atomic runs, only its store is guarded
+    TS_HIP(hipMemcpyAsync(cnt, W.cand_cnt(), (size_t)nq * 4, hipMemcpyDeviceToHost, s));
+    TS_HIP(hipMemsetAsync(W.cand_cnt(), 0, 256, s));   // (the one-launch search expects the set's counts at zero)
+    TS_HIP(hipStreamSynchronize(s));
+    uint32_t maxc = 0;
+    for (int j = 0; j < nq; ++j) maxc = std::max(maxc, cnt[j]);
+    if (maxc > kCandCap) {   // the whole pass is redone densely
+      dense = true;
+      stats->dense_redo += 1;
+    } else {
+      int64_t off[TS_MAX_Q + 1];
+      off[0] = *total;
+      for (int j = 0; j < TS_MAX_Q; ++j) off[j + 1] = off[j] + (j < nq ? (int64_t)cnt[j] : 0);
+      for (int j = 0; j < nq; ++j) lims[j + 1] = off[j + 1];
+      if (off[nq] > limit) {
+        ts_set_error("range search: %lld results so far exceed the limit of %lld", (long long)off[nq], (long long)limit);
+        return TS_ERR_UNSUPPORTED;
+      }
+      TS_CHECK(range_reserve(h, off[nq], *total, limit, s));
+      TsRangeSortParams rp{};
+      rp.cand_score = (const float*)W.cand_score.p;
+      rp.cand_id = (const int32_t*)W.cand_id.p;
+      rp.cand_cap = kCandCap;
+      for (int j = 0; j < TS_MAX_Q; ++j) rp.cnt[j] = cnt[j];
+      for (int j = 0; j <= TS_MAX_Q; ++j) rp.off[j] = off[j];
+      rp.out_scores = (float*)h->rng_s.p;
+      rp.out_ids = (int64_t*)h->rng_i.p;
+      rp.capacity = h->rng_cap;
+      rp.id_offset = h->id_offset;
+      TS_CHECK(ts_launch_range_sort(rp, nq, maxc, s));
+      *total = off[nq];
+    }
+  }
+  if (dense) {
+    const int64_t chunk_rows = std::min<int64_t>(kDenseChunkRows, nblk * TS_ROWS_PER_BLOCK);
+    const int64_t nch = (nblk * TS_ROWS_PER_BLOCK + chunk_rows - 1) / chunk_rows;
+    const int64_t chunk_tiles = (chunk_rows + TS_RANGE_TILE - 1) / TS_RANGE_TILE;
+    const int64_t ntiles = nch * chunk_tiles;
+    TS_CHECK(ensure(W.dense, (size_t)nq * chunk_rows * 4));
+    if (mc) TS_CHECK(ensure(W.mids, (size_t)nq * chunk_rows * 4));
+    TS_CHECK(ensure(h->rng_tiles, 256 + (size_t)nq * ntiles * 4));
+    uint32_t* dtotal = (uint32_t*)h->rng_tiles.p;
+    TsRangeDenseParams dp{};
+    dp.dense = (const float*)W.dense.p;
+    dp.mids = mc ? (const int32_t*)W.mids.p : nullptr;
+    dp.ld = chunk_rows;
+    dp.chunk_tiles = (uint32_t)chunk_tiles;
+    dp.ntiles = ntiles;
+    dp.tilecnt = dtotal + 64;
+    for (int j = 0; j < TS_MAX_Q; ++j) dp.radius[j] = tau[j];
+    // ---- count phase: every chunk's tile counts (each tile of the pass is written), then the prefix per query
+    for (int64_t c = 0; c < nch; ++c) {
+      const int64_t row0 = c * chunk_rows;
+      const int64_t rows = std::min(chunk_rows, N - row0);
+      TS_CHECK(range_dense_chunk(h, W, nq, qh, row0, rows, chunk_rows, mc, s));
+      dp.row0 = row0;
+      dp.rows = (uint32_t)rows;
+      dp.tile0 = c * chunk_tiles;
+      TS_CHECK(ts_launch_range_count(dp, nq, s));
+    }
+    TS_CHECK(ts_launch_range_prefix(dp.tilecnt, ntiles, nq, dtotal, s));
+    uint32_t dcnt[TS_MAX_Q] = {0};
+    TS_HIP(hipMemcpyAsync(dcnt, dtotal, (size_t)nq * 4, hipMemcpyDeviceToHost, s));
+    TS_HIP(hipStreamSynchronize(s));
+    if (filter) {   // both paths counted the same predicate over the same scores
+      for (int j = 0; j < nq; ++j) {
+        if (dcnt[j] != cnt[j]) {
+          ts_set_error("range search: query %d has %u results on the dense path and %u on the filter scan", j, dcnt[j], cnt[j]);
+          return TS_ERR_HIP;
+        }
+      }
+    }
+    dp.off[0] = *total;
+    for (int j = 0; j < TS_MAX_Q; ++j) dp.off[j + 1] = dp.off[j] + (j < nq ? (int64_t)dcnt[j] : 0);
+    for (int j = 0; j < nq; ++j) lims[j + 1] = dp.off[j + 1];
+    if (dp.off[nq] > limit) {
+      ts_set_error("range search: %lld results so far exceed the limit of %lld", (long long)dp.off[nq], (long long)limit);
+      return TS_ERR_UNSUPPORTED;
+    }
+    TS_CHECK(range_reserve(h, dp.off[nq], *total, limit, s));
+    dp.out_scores = (float*)h->rng_s.p;
+    dp.out_ids = (int64_t*)h->rng_i.p;
+    dp.capacity = h->rng_cap;
+    dp.id_offset = h->id_offset;
+    // ---- fill phase (one chunk: its scores are still in W.dense)
+    for (int64_t c = 0; c < nch; ++c) {
+      const int64_t row0 = c * chunk_rows;
+      const int64_t rows = std::min(chunk_rows, N - row0);
+      if (nch > 1) TS_CHECK(range_dense_chunk(h, W, nq, qh, row0, rows, chunk_rows, mc, s));
+      dp.row0 = row0;
+      dp.rows = (uint32_t)rows;
+      dp.tile0 = c * chunk_tiles;
+      TS_CHECK(ts_launch_range_fill(dp, nq, s));
+    }
+    *total = dp.off[nq];
+  }
+  TS_HIP(hipEventRecord(W.ev_sel, s));
+  W.used = true;
+  return TS_OK;
+}
+
+extern "C" int ts_index_range_search(ts_index* h, const void* queries, int32_t nq, int32_t q_dtype, const float* radius,
+                                     const uint32_t* allow_bits, int64_t allow_words, int32_t n_masks,
+                                     const int32_t* mask_of_query, int64_t max_total, int64_t* lims, uint32_t flags,
+                                     void* stream) {
+  // the checks that need no handle come first (and none of them touches the GPU)
+  if (!lims) { ts_set_error("range_search: lims is null"); return TS_ERR_INVALID; }
+  if (nq < 0 || !dtype_ok(q_dtype) || (nq > 0 && (!queries || !radius))) {
+    ts_set_error("bad arguments to range_search");
+    return TS_ERR_INVALID;
+  }
+  if (flags & ~(uint32_t)(TS_FLAG_HOST_PTR | TS_FLAG_NO_FILTER)) {
+    ts_set_error("range_search takes TS_FLAG_HOST_PTR and TS_FLAG_NO_FILTER only (it is synchronous)");
+    return TS_ERR_INVALID;
+  }
+  for (int32_t q = 0; q < nq; ++q) {
+    if (radius[q] != radius[q]) { ts_set_error("range_search: radius[%d] is NaN", q); return TS_ERR_INVALID; }
+  }
+  if (n_masks < 0 || allow_words < 0) { ts_set_error("range_search: negative n_masks / allow_words"); return TS_ERR_INVALID; }
+  if (n_masks > 0 && !allow_bits) { ts_set_error("range_search: n_masks > 0 but allow_bits is null"); return TS_ERR_INVALID; }
+  if (mask_of_query) {
+    for (int32_t q = 0; q < nq; ++q) {
+      if (mask_of_query[q] < -1 || mask_of_query[q] >= n_masks) {
+        ts_set_error("range_search: mask_of_query[%d] = %d is outside [-1, %d)%s", q, mask_of_query[q], n_masks,
+                     allow_bits ? "" : " (allow_bits is null)");
+        return TS_ERR_INVALID;
+      }
+    }
+  }
+  lims[0] = 0;
+  if (nq == 0) {
+    if (h) {
+      std::lock_guard<std::mutex> rlk(h->range_mu);
+      h->rng_total = 0;
+      h->rng_valid = true;
+    }
+    return TS_OK;
+  }
+  for (int32_t q = 0; q < nq; ++q) lims[q + 1] = 0;
+  if (!h) { ts_set_error("null handle"); return TS_ERR_INVALID; }
+  const int64_t N = h->ntotal;
+  const int64_t need_words = (N + 31) / 32;
+  if (mask_of_query && n_masks > 0 && allow_words < need_words) {
+    ts_set_error("range_search: allow_words = %lld < ceil(ntotal / 32) = %lld", (long long)allow_words, (long long)need_words);
+    return TS_ERR_INVALID;
+  }
+  if (N == 0) { ts_set_error("No documents indexed. Call add_documents() first."); return TS_ERR_EMPTY; }
+  if (!mask_of_query) n_masks = 0;   // unfiltered
+  const int64_t limit = max_total <= 0 ? kRangeDefaultMax : max_total;
+  DeviceGuard g(h->device);
+  hipStream_t s = (hipStream_t)stream;
+  TS_CHECK(co_flush(h, s));   // a range search never joins a coalesced pass
+  std::lock_guard<std::mutex> rlk(h->range_mu);
+  h->rng_valid = false;
+  h->rng_total = 0;
+  const int qp = (ts_scan_lds_bytes(h->L, 2) <= 160 * 1024) ? 64 : 32;  // queries per pass
+  const size_t qrow = (size_t)h->L.dim * dtype_size(q_dtype);
+  const void* dq = queries;
+  const uint32_t* bits = allow_bits;
+  std::unique_lock<std::mutex> hlk(h->host_mu, std::defer_lock);
+  if (flags & TS_FLAG_HOST_PTR) {
+    hlk.lock();   // one staging area per handle
+    const size_t mbytes = (size_t)n_masks * (size_t)allow_words * 4;
+    TS_CHECK(ensure(h->qstage, (size_t)nq * qrow));
+    TS_HIP(hipMemcpyAsync(h->qstage.p, queries, (size_t)nq * qrow, hipMemcpyHostToDevice, s));
+    if (mbytes) {
+      TS_CHECK(ensure(h->mstage, mbytes));
+      TS_HIP(hipMemcpyAsync(h->mstage.p, allow_bits, mbytes, hipMemcpyHostToDevice, s));
+      bits = (const uint32_t*)h->mstage.p;
+    }
+    dq = h->qstage.p;
+  }
+  // removed rows: every mask ANDed with the tombstone bitmap, which a query without a mask gets itself
+  // (ts_index_search_filtered)
+  std::vector<int32_t> moq((size_t)nq, -1);
+  if (mask_of_query) moq.assign(mask_of_query, mask_of_query + nq);
+  std::unique_lock<std::mutex> elk(h->eff_mu, std::defer_lock);
+  if (h->nremoved > 0) {
+    elk.lock();
+    TS_CHECK(ensure(h->eff, (size_t)(n_masks + 1) * (size_t)need_words * 4));
+    if (h->eff_used) TS_HIP(hipStreamWaitEvent(s, h->eff_ev, 0));   // the previous call's passes have read `eff`
+    TS_CHECK(ts_launch_and_live(bits, allow_words, n_masks, (const uint32_t*)h->live.p, need_words, (uint32_t*)h->eff.p, s));
+    for (int32_t& m : moq)
+      if (m < 0) m = n_masks;
+    bits = (const uint32_t*)h->eff.p;
+    allow_words = need_words;
+    n_masks += 1;
+  }
+  RangeStats stats;
+  int64_t total = 0;
+  int st = TS_OK;
+  for (int q0 = 0; q0 < nq && st == TS_OK; q0 += qp) {
+    const int c = std::min(qp, nq - q0);
+    MaskCtx mc{};
+    mc.bits = bits;
+    mc.words = allow_words;
+    bool masked = false;
+    for (int j = 0; j < TS_MAX_Q; ++j) { mc.mp.qmask[j] = -1; mc.mp.qd[j] = -1; }
+    for (int j = 0; j < c; ++j) {
+      const int32_t m = moq[(size_t)q0 + j];
+      mc.mp.qmask[j] = m;
+      if (m < 0) { mc.mp.all_live = 1; continue; }
+      masked = true;
+      int d = 0;
+      while (d < mc.mp.nd && mc.mp.dist[d] != m) ++d;
+      if (d == mc.mp.nd) mc.mp.dist[mc.mp.nd++] = m;
+      mc.mp.qd[j] = d;
+    }
+    lims[q0] = total;
+    st = range_pass(h, (const char*)dq + (size_t)q0 * qrow, c, q_dtype, radius + q0, masked ? &mc : nullptr, flags, limit,
+                    &total, lims + q0, &stats, s);
+  }
+  if (st != TS_OK) {
+    // lims hold the counts so far: the passes that ran (a pass whose counts are known has written them), flat behind
+    for (int q = 1; q <= nq; ++q)
+      if (lims[q] < lims[q - 1]) lims[q] = lims[q - 1];
+    (void)hipStreamSynchronize(s);
+    if (elk.owns_lock() && hipEventRecord(h->eff_ev, s) == hipSuccess) h->eff_used = true;
+    set_info(h, 32, stats.passes, stats.filter_passes, stats.dense_redo);
+    return st;
+  }
+  if (elk.owns_lock()) {
+    TS_HIP(hipEventRecord(h->eff_ev, s));
+    h->eff_used = true;
+  }
+  TS_HIP(hipStreamSynchronize(s));
+  h->rng_total = total;
+  h->rng_valid = true;
+  set_info(h, 32 | (stats.dense_redo ? 2 : (stats.filter_passes ? 1 : 0)), stats.passes, stats.filter_passes, stats.dense_redo);
+  return TS_OK;
+}
+
+extern "C" int ts_index_range_fetch(ts_index* h, float* out_scores, int64_t* out_ids, int64_t capacity, uint32_t flags,
+                                    void* stream) {
+  if (!h) { ts_set_error("null handle"); return TS_ERR_INVALID; }
+  if (capacity < 0 || (flags & ~(uint32_t)TS_FLAG_HOST_PTR)) { ts_set_error("bad arguments to range_fetch"); return TS_ERR_INVALID; }
+  std::lock_guard<std::mutex> rlk(h->range_mu);
+  if (!h->rng_valid) {
+    ts_set_error("range_fetch: no range search result is stored (none was run, it failed, or the index has changed since)");
+    return TS_ERR_INVALID;
+  }
+  const int64_t n = h->rng_total;
+  if (capacity < n) {
+    ts_set_error("range_fetch: capacity %lld is less than the %lld stored results", (long long)capacity, (long long)n);
+    return TS_ERR_INVALID;
+  }
+  if (n == 0) return TS_OK;
+  if (!out_scores || !out_ids) { ts_set_error("range_fetch: null output"); return TS_ERR_INVALID; }
+  DeviceGuard g(h->device);
+  hipStream_t s = (hipStream_t)stream;
+  const hipMemcpyKind kind = (flags & TS_FLAG_HOST_PTR) ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+  TS_HIP(hipMemcpyAsync(out_scores, h->rng_s.p, (size_t)n * 4, kind, s));
+  TS_HIP(hipMemcpyAsync(out_ids, h->rng_i.p, (size_t)n * 8, kind, s));
+  TS_HIP(hipStreamSynchronize(s));
+  return TS_OK;
+}
+
 // ---- removal (include/tristage.h "removal")
 // `s` waits for every search enqueued so far on this handle, on any stream: each workspace set records ev_sel behind
 // the last search that used it (the five-launch, one-launch, dense and coalesced paths alike)
@@ -1575,6 +1952,7 @@ extern "C" int ts_index_remove(ts_index* h, const int64_t* ids, int64_t n, int64
   DeviceGuard g(h->device);
   hipStream_t s = (hipStream_t)stream;
   TS_CHECK(co_flush(h, s));   // held passes search the index as it was when they were submitted
+  h->rng_valid = false;
   std::lock_guard<std::mutex> elk(h->eff_mu);
   // searches submitted earlier (on any stream) have read the bitmap before it changes: eff_ev follows the last
   // call's passes, and that call's stream waited for the one before it
@@ -1646,6 +2024,7 @@ extern "C" int ts_index_update(ts_index* h, const int64_t* ids, int64_t n, const
   DeviceGuard g(h->device);
   hipStream_t s = (hipStream_t)stream;
   TS_CHECK(co_flush(h, s));   // held passes search the rows as they were when they were submitted
+  h->rng_valid = false;
   std::lock_guard<std::mutex> elk(h->eff_mu);
   // as ts_index_remove: searches submitted earlier, on any path and any stream, have read the rows before they change
   if (h->eff_used) TS_HIP(hipStreamWaitEvent(s, h->eff_ev, 0));
@@ -1770,6 +2149,7 @@ extern "C" int ts_index_compact(ts_index* h, int64_t* old2new, void* stream) {
   DeviceGuard g(h->device);
   hipStream_t s = (hipStream_t)stream;
   TS_CHECK(co_flush(h, s));
+  h->rng_valid = false;
   std::lock_guard<std::mutex> elk(h->eff_mu);
   if (h->eff_used) TS_HIP(hipStreamWaitEvent(s, h->eff_ev, 0));   // earlier searches have read the old corpus
   TS_CHECK(wait_for_searches(h, s));

@@ -97,6 +97,15 @@ def _update_call(fn, handle, ids: np.ndarray, ptr, dtype: int, flags: int, strea
     _lib.check(code)
 
 
+class RangeSearchLimitError(RuntimeError):
+    """A range search would return more entries than ``max_results`` allows; the message names both numbers.
+    ``counts``: results per query as far as the search got (zero behind that)."""
+
+    def __init__(self, message: str, counts: np.ndarray):
+        super().__init__(message)
+        self.counts = counts
+
+
 class FlatIPIndex:
     """Exact inner-product index resident in MI355X HBM."""
 
@@ -537,6 +546,125 @@ class FlatIPIndex:
                            D.ctypes.data, I.ctypes.data, flags | _lib.TS_FLAG_HOST_PTR, 0)
         return D, I
 
+    # -- range search -----------------------------------------
+    def range_search(self, q, radius, allowed=None, max_results: Optional[int] = None, sort: bool = False,
+                     exact_dense: bool = False):
+        """FAISS ``range_search``: every live row with ``score >= radius`` (inclusive), per query.  Returns
+        ``(lims, D, I)`` in FAISS's CSR form: query ``b`` owns ``D[lims[b]:lims[b + 1]]`` / ``I[...]``; ``lims`` is
+        int64 [B + 1].  numpy in -> numpy out; a CUDA tensor in -> tensors out (``lims`` on the device too).
+
+        ``radius``: a scalar or one value per query, on the index's score scale; ``-inf`` returns every live row,
+        NaN raises ``ValueError``.  Scores are bit-identical to those of :meth:`search` / :meth:`scores`.
+        ``allowed``: as for :meth:`search`; removed rows are never returned.
+        Within a query the rows come in ascending id order; ``sort=True`` reorders each query's segment by
+        descending score, ties by ascending id (the order of :meth:`search`).
+        ``max_results``: the most entries the call may return (default 2^26); exceeding it raises
+        :class:`RangeSearchLimitError`, which names the count and the limit, and the index stays usable.
+        ``exact_dense=True`` forces the dense path (tests, A/B runs).  Synchronous."""
+        was_tensor = _is_tensor(q) and q.is_cuda
+        if _is_tensor(q) and not q.is_cuda:
+            q = q.detach().float().numpy()
+        if not was_tensor:
+            q = np.ascontiguousarray(q)
+            if q.dtype not in _NP_DTYPES:
+                q = q.astype(np.float32)
+            if q.ndim != 2 or q.shape[1] != self.d:
+                raise ValueError(f"expected [B, {self.d}] queries, got {q.shape}")
+        else:
+            if q.dim() != 2 or q.shape[1] != self.d:
+                raise ValueError(f"expected [B, {self.d}] queries, got {tuple(q.shape)}")
+            q = q.contiguous()
+        B = int(q.shape[0])
+        if _is_tensor(radius):
+            radius = radius.detach().float().cpu().numpy()
+        rad = np.asarray(radius, dtype=np.float32).reshape(-1)
+        if rad.size == 1:
+            rad = np.full(B, rad[0], dtype=np.float32)
+        if rad.size != B:
+            raise ValueError(f"radius: {rad.size} values for {B} queries")
+        if np.isnan(rad).any():
+            raise ValueError("radius must not be NaN")
+        rad = np.ascontiguousarray(rad)
+        if self.ntotal == 0:
+            raise ValueError("No documents indexed. Call add_documents() first.")
+        if self._pending:   # unfinished async_ searches are verified first: this call is synchronous
+            self._auto_redone = self._auto_redone + self.finish()
+        flags = _lib.TS_FLAG_NO_FILTER if exact_dense else 0
+        keep = None
+        bits_ptr, words, n_masks, moq_ptr = None, 0, 0, None
+        if allowed is not None:
+            if getattr(allowed, "ndim", 1) == 2:
+                allowed = list(allowed)
+            words = (self.ntotal + 31) // 32
+            dev_bits = self._device_masks(allowed, B, words, q.device) if was_tensor else None
+            if dev_bits is not None:
+                keep, moq = dev_bits
+                bits_ptr = ctypes.c_void_p(keep.data_ptr())
+            else:
+                bits, words, moq = self._masks(allowed, B)
+                if was_tensor:
+                    keep = _torch().from_numpy(bits.view(np.int32)).to(q.device)
+                    bits_ptr = ctypes.c_void_p(keep.data_ptr())
+                else:
+                    keep = bits
+                    bits_ptr = bits.ctypes.data_as(ctypes.c_void_p)
+            moq = np.ascontiguousarray(moq, dtype=np.int32)
+            n_masks = int(moq.max()) + 1 if moq.size else 0
+            moq_ptr = moq.ctypes.data_as(ctypes.c_void_p)
+            if n_masks == 0:
+                bits_ptr, moq_ptr = None, None
+        lims = np.zeros(B + 1, dtype=np.int64)
+        if was_tensor:
+            q_ptr, q_dt, stream = ctypes.c_void_p(q.data_ptr()), _tensor_dtype(q), _stream_ptr(self.device)
+        else:
+            q_ptr, q_dt, stream = q.ctypes.data_as(ctypes.c_void_p), _NP_DTYPES[q.dtype], 0
+            flags |= _lib.TS_FLAG_HOST_PTR
+        stream = ctypes.c_void_p(stream) if stream else None
+        code = self._lib.ts_index_range_search(
+            self._h, q_ptr, B, q_dt, rad.ctypes.data_as(ctypes.c_void_p), bits_ptr, int(words), n_masks, moq_ptr,
+            int(max_results) if max_results is not None else 0, lims.ctypes.data_as(ctypes.c_void_p), flags, stream)
+        del keep
+        if code == _lib.TS_ERR_UNSUPPORTED and "exceed the limit" in _lib.last_error():
+            raise RangeSearchLimitError(_lib.last_error(), np.diff(lims))
+        if code == _lib.TS_ERR_EMPTY:
+            raise ValueError("No documents indexed. Call add_documents() first.")
+        _lib.check(code)
+        total = int(lims[B])
+        if was_tensor:
+            torch = _torch()
+            D = torch.empty(total, dtype=torch.float32, device=q.device)
+            I = torch.empty(total, dtype=torch.int64, device=q.device)
+            _lib.check(self._lib.ts_index_range_fetch(self._h, ctypes.c_void_p(D.data_ptr()), ctypes.c_void_p(I.data_ptr()),
+                                                      total, 0, stream))
+            L = torch.from_numpy(lims).to(q.device)
+            if sort and total:
+                # descending score with -0 equal to +0, then ascending id: ids ascend inside a segment already, so two
+                # stable sorts (score, then segment) give the order of search()
+                seg = torch.repeat_interleave(torch.arange(B, device=q.device), L[1:] - L[:-1])
+                o1 = torch.sort(D + 0.0, descending=True, stable=True).indices
+                o2 = torch.sort(seg[o1], stable=True).indices
+                order = o1[o2]
+                D, I = D[order], I[order]
+            return L, D, I
+        D = np.empty(total, dtype=np.float32)
+        I = np.empty(total, dtype=np.int64)
+        _lib.check(self._lib.ts_index_range_fetch(self._h, D.ctypes.data_as(ctypes.c_void_p), I.ctypes.data_as(ctypes.c_void_p),
+                                                  total, _lib.TS_FLAG_HOST_PTR, None))
+        if sort and total:
+            seg = np.repeat(np.arange(B), np.diff(lims))
+            order = np.lexsort((I, -(D + np.float32(0.0)), seg))   # segment, then score descending, then id
+            D, I = D[order], I[order]
+        return lims, D, I
+
+    def last_range_info(self) -> dict:
+        """The last :meth:`range_search`: its passes (of <= 64 queries), how many ran the filter scan, and how many
+        of those were redone densely because a query had more than 16384 results."""
+        arr = (ctypes.c_int64 * 4)()
+        _lib.check(self._lib.ts_index_last_search_info(self._h, arr))
+        if not arr[0] & 32:
+            raise RuntimeError("the last search on this index was not a range search")
+        return {"passes": int(arr[1]), "filter_passes": int(arr[2]), "dense_redo": int(arr[3])}
+
     def last_filter_info(self) -> dict:
         """The last filtered search: row blocks (32 rows) its scans read, row blocks of the index, passes on the
         masked filter path and on the dense path (asynchronous searches: complete after :meth:`finish`)."""
@@ -675,6 +803,9 @@ class FlatIPIndex:
     def last_search_info(self) -> dict:
         arr = (ctypes.c_int64 * 4)()
         _lib.check(self._lib.ts_index_last_search_info(self._h, arr))
+        if arr[0] & 32:   # a range search: last_range_info() reads these counters
+            return {"path": ("dense", "filter", "filter+dense-fallback")[arr[0] & 3], "one_launch": False, "range": True,
+                    "passes": int(arr[1]), "filter_passes": int(arr[2]), "dense_redo": int(arr[3])}
         return {"path": ("dense", "filter", "filter+dense-fallback")[arr[0] & 15],
                 "one_launch": bool(arr[0] & 16),   # query image + thresholds + scan+filter in ONE kernel
                 "max_candidates": int(arr[1]), "sample_rows": int(arr[2]),

@@ -100,6 +100,9 @@ class ShardedFlatIPIndex:
     def compact(self):
         raise NotImplementedError("removal is not supported on a row-sharded index")
 
+    def range_search(self, q, radius, allowed=None, max_results=None, sort: bool = False):
+        raise NotImplementedError("range search is not supported on a row-sharded index")
+
     def search(self, q, k: int, async_: bool = False, inputs_ready: bool = False, allowed=None):
         """Global top-k for the replicated query batch `q` (tensor).  Returns
         tensors (D float32 [B,k], I int64 [B,k]) identical on every rank.

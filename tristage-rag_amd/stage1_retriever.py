@@ -815,6 +815,62 @@ class Stage1Retriever:
                                 "stage": "stage1"})
         return results
 
+    def range_search(self, queries, min_score: float, filter=None, max_results: Optional[int] = None):
+        """Every document whose dense score is at least ``min_score`` (inclusive), per query: a similarity cut-off
+        instead of a top-k (FAISS ``range_search``, FlatIPIndex.range_search).  ``queries``: one string
+        (-> the records :meth:`search` returns, sorted by descending score, ties by ascending doc_id) or a list of
+        strings (-> one such list per query).  The dense index only: no BM25, no fusion.  ``filter`` as for
+        :meth:`search`; removed documents are never returned.  ``max_results``: the most records the call may return
+        in all (FlatIPIndex.range_search raises RangeSearchLimitError beyond it).  Not supported on an IVF index."""
+        if self.faiss_index is None:
+            raise ValueError("No documents indexed. Call add_documents() first.")
+        if getattr(self, "index_type_used", "flat") == "ivf":
+            raise NotImplementedError("range search is not supported on an IVF index (index_type='ivf')")
+        single = isinstance(queries, str)
+        texts = [queries] if single else list(queries)
+        if not texts:
+            return []
+        nq = len(texts)
+        masks = self._filter_masks(filter, nq)
+        if self._device_path() and hasattr(self.faiss_index, "range_search"):
+            allowed = None
+            if masks is not None:
+                per_q = self._per_query_filters(filter, nq) or [None] * nq
+                drop_live = self._index_removes()   # (the index applies its own tombstones)
+                allowed = [None if (f is None and drop_live) else self._index_mask(f, m) for f, m in zip(per_q, masks)]
+                if all(a is None for a in allowed):
+                    allowed = None
+                elif all(a is allowed[0] for a in allowed):
+                    allowed = allowed[0]
+            lims, D, I = self.faiss_index.range_search(self._normalized_query_tensor(texts), float(min_score),
+                                                       allowed=allowed, max_results=max_results, sort=True)
+            lims, D, I = lims.cpu().numpy(), D.cpu().numpy(), I.cpu().numpy()
+            per_query = [(I[lims[b]: lims[b + 1]], D[lims[b]: lims[b + 1]]) for b in range(nq)]
+        else:
+            # every score through the index's scores() route, cut on the host
+            if not hasattr(self.faiss_index, "scores"):
+                raise NotImplementedError("range search needs an index with range_search() or scores()")
+            q = self._normalize_embeddings(self._encode_batch(texts))
+            S = np.asarray(self.faiss_index.scores(np.ascontiguousarray(q, dtype=np.float32)))
+            thr = np.float32(min_score)
+            per_query, total = [], 0
+            for b in range(nq):
+                ok = S[b] >= thr
+                if masks is not None and masks[b] is not None:
+                    ok &= masks[b][: ok.shape[0]]
+                ids = np.nonzero(ok)[0]
+                order = np.lexsort((ids, -(S[b][ids] + np.float32(0.0))))
+                per_query.append((ids[order], S[b][ids][order]))
+                total += ids.size
+            if max_results is not None and total > int(max_results):
+                raise RuntimeError(f"range search: {total} results exceed the limit of {int(max_results)}")
+        out = []
+        for ids, scores in per_query:
+            out.append([{"doc_id": int(i), "document": self.documents[int(i)], "score": float(s), "stage1_score": float(s),
+                         "metadata": self.doc_metadata[int(i)], "stage": "stage1"}
+                        for i, s in zip(ids, scores) if 0 <= int(i) < len(self.documents)])
+        return out[0] if single else out
+
     def search(self, query: str, top_k: Optional[int] = None, filter=None) -> List[Dict[str, Any]]:
         """``filter``: restrict the candidates to some documents (see :meth:`filter_mask`); fewer than
         ``top_k`` results when fewer documents are allowed, none when none are."""
