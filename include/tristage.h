@@ -437,8 +437,14 @@ int ts_maxsim_indexed_batch_fp8(const void* q, int32_t q_dtype, const int32_t* q
  * ts_bm25_set_index takes HOST arrays: term_off[V+1], post_doc/post_tf[nnz] sorted
  * by term, idf[V], len_norm[N] = k1*(1-b+b*len/avg), k1p1 = k1+1.
  * ts_bm25_search: term_ids = query tokens as vocabulary ids in query order (host);
- * writes up to k (score, doc) pairs to HOST arrays; *n_out < k means all documents
- * with a non-zero score were returned (the rest score exactly 0.0).  A ts_bm25
+ * writes (score, doc) pairs to HOST arrays: the first min(k, T) of the T documents the
+ * query TOUCHES (those in the postings of at least one of its terms), by score desc, doc
+ * id asc, and *n_out = min(k, T); k <= 2048, TS_ERR_UNSUPPORTED above.  Untouched
+ * documents score exactly 0.0 and are never written.  With every idf > 0 a touched
+ * document scores above 0.0, so *n_out < k means all documents with a non-zero score were
+ * returned.  With an idf <= 0 a touched document may score 0.0 (written as +0.0) or less:
+ * it is still written, once, and ranking it against the untouched documents (which then
+ * tie with it or beat it) is left to the caller.  A ts_bm25
  * handle keeps ONE set of accumulator / candidate workspaces: calls on one handle must
  * not overlap (one caller at a time; different handles are independent).        */
 typedef struct ts_bm25 ts_bm25;
@@ -462,8 +468,8 @@ int ts_bm25_search_batch(ts_bm25* h, const int32_t* term_ids, const int64_t* ter
 /* ts_bm25_search_batch restricted per query to an allowed set of documents (the masks of
  * ts_index_search_filtered: n_masks masks of allow_words >= ceil(N / 32) words, bit d % 32 of word d / 32 =
  * document d allowed; mask_of_query a HOST array, -1 = not filtered).  allow_bits is device memory, host memory
- * with TS_FLAG_HOST_PTR.  A document outside its query's mask is never scored: the output holds the allowed
- * documents with a non-zero score only (*n_out < k: all of them), so a caller's zero-score padding must take
+ * with TS_FLAG_HOST_PTR.  A document outside its query's mask is never scored or touched: the output holds the
+ * allowed touched documents only (*n_out < k: all of them), so a caller's zero-score padding must take
  * allowed documents too.  Allowed documents score exactly as in ts_bm25_search_batch.                      */
 int ts_bm25_search_batch_filtered(ts_bm25* h, const int32_t* term_ids, const int64_t* term_off, int32_t nq,
                                   int32_t k, const uint32_t* allow_bits, int64_t allow_words, int32_t n_masks,

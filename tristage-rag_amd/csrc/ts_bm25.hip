@@ -15,6 +15,13 @@
 // the k survivors.  Documents nobody touched score 0.0 and are filled in by the
 // host in ascending id order when fewer than k documents were touched.
 //
+// What a call returns: the first min(k, n_touched) TOUCHED documents — the ones in the postings of at least one
+// query term (and in the query's allow mask), whatever their contributions add up to — by (score desc, doc id asc),
+// and n_out = min(k, n_touched).  With positive idf a touched document scores above 0.0, so n_out < k means "all
+// documents with a non-zero score"; with an idf <= 0 (BM25Index's refit_compat can produce one) a touched document may
+// score 0.0 or less, is still listed (once, its 0.0 as +0.0), and ranking it against the untouched ones is the
+// caller's business: BM25Index scores such a query, and any top_k above BM_MAX_K, on the host.
+//
 // That select is one workgroup making up to 12 gathering passes over the touched list, which
 // is fine for thousands of documents and far too slow for millions (a common term touches a
 // large share of the corpus).  Above BM_PRE_MIN touched documents the list is first cut down
@@ -84,6 +91,13 @@ struct Guard {
 // length 0 = this query has no token at this position).  Within a lane the launches follow each other in query order and a
 // token's postings hit distinct documents: the same additions in the same order as one query at a time.
 struct BmStep { int64_t off, df; double idf; };
+
+// An accumulator's bit pattern doubles as the "touched" mark: all zero = nobody has touched the document in this query.
+// A sum that comes out as +0.0 (contributions that cancel, a product that underflows) is stored as -0.0, which is the
+// same number in every later addition, so the first-touch test does not depend on the sign or size of a contribution
+// and a document enters `touched` exactly once.  Readers add 0.0 (d2key, the output), which turns -0.0 into +0.0.
+__device__ __forceinline__ bool bm_untouched(double old) { return __builtin_bit_cast(uint64_t, old) == 0ull; }
+__device__ __forceinline__ double bm_marked(double sum) { return __builtin_bit_cast(uint64_t, sum) == 0ull ? -0.0 : sum; }
 __global__ void bm25_accumulate(const int32_t* __restrict__ post_doc, const float* __restrict__ post_tf,
                                 const BmStep* __restrict__ st, double k1p1, int64_t N,
                                 const double* __restrict__ len_norm, double* __restrict__ acc,
@@ -102,8 +116,8 @@ __global__ void bm25_accumulate(const int32_t* __restrict__ post_doc, const floa
   const double tf = (double)post_tf[off + i];
   const double c = idf * ((tf * k1p1) / (tf + len_norm[d]));
   const double old = acc[d];
-  acc[d] = old + c;
-  if (old == 0.0) touched[atomicAdd(n_touched, 1u)] = d;  // contributions are > 0: first touch
+  acc[d] = bm_marked(old + c);
+  if (bm_untouched(old)) touched[atomicAdd(n_touched, 1u)] = d;
 }
 
 // bm25_accumulate for a filtered batch: a document outside the lane's allow mask (word offset moff[y] into
@@ -128,8 +142,8 @@ __global__ void bm25_accumulate_masked(const int32_t* __restrict__ post_doc, con
   const double tf = (double)post_tf[off + i];
   const double c = idf * ((tf * k1p1) / (tf + len_norm[d]));
   const double old = acc[d];
-  acc[d] = old + c;
-  if (old == 0.0) touched[atomicAdd(n_touched, 1u)] = d;
+  acc[d] = bm_marked(old + c);
+  if (bm_untouched(old)) touched[atomicAdd(n_touched, 1u)] = d;
 }
 
 __global__ void bm25_reset(const int32_t* __restrict__ touched, const uint32_t* __restrict__ counters,
@@ -141,7 +155,7 @@ __global__ void bm25_reset(const int32_t* __restrict__ touched, const uint32_t* 
     acc[touched[i]] = 0.0;
 }
 
-__device__ __forceinline__ uint64_t d2key(double v) {  // orderable; scores are >= 0 but stay general
+__device__ __forceinline__ uint64_t d2key(double v) {  // orderable for any sign; -0.0 and +0.0 get one key
   uint64_t u = __builtin_bit_cast(uint64_t, v + 0.0);
   return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
 }
@@ -344,7 +358,7 @@ __global__ __launch_bounds__(BM_SEL_THREADS) void bm25_select(const int32_t* __r
   for (uint32_t i = tid; i < kk && i < cnt; i += BM_SEL_THREADS) {
     const int32_t d = (int32_t)~sdk[i];
     out_i[i] = d;
-    out_s[i] = acc[d];
+    out_s[i] = acc[d] + 0.0;   // (a touched document's 0.0 is kept as -0.0: +0.0 goes out)
   }
 }
 
@@ -441,7 +455,7 @@ extern "C" int ts_bm25_set_index(ts_bm25* h, int64_t N, int64_t V, int64_t nnz, 
 
 // term_ids: the query's tokens mapped to vocabulary ids, in query order (unknown
 // tokens dropped, repeats kept).  Writes up to k (score, doc) pairs, best first;
-// *n_out < k means every document with a non-zero score is in the output.
+// *n_out = min(k, touched documents): below k, every touched document is in the output.
 // A chunk of up to h->lanes queries (query q0 + y in lane y): one bm25_accumulate launch per token position, then the
 // pre-filter (if some lane's postings are long enough to need it) and the two select launches, all with blockIdx.y = lane;
 // results land in rows q0 .. of bs / bi / bc (device).  Accumulators, touched lists and counters are back to zero afterwards.

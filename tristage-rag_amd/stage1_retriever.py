@@ -89,6 +89,8 @@ class BM25Index:
     """BM25 (k1=1.2, b=0.75) with the reference's tokenizer and idf
     (reference src/stage1_retriever.py:35-112), over an inverted index."""
 
+    GPU_MAX_K = 2048   # the largest k of one ts_bm25_search* call (BM_MAX_K in ts_bm25.hip)
+
     def __init__(self, k1: float = 1.2, b: float = 0.75, gpu_device: Optional[int] = None, refit_compat: bool = False):
         self.k1 = k1
         self.b = b
@@ -164,16 +166,10 @@ class BM25Index:
             self._upload()
 
     # -- GPU mode ------------------------------------------------------------
-    def _upload(self) -> None:
-        """CSR postings + statistics -> HBM (ts_bm25_set_index)."""
-        import ctypes
-        from . import _lib
-        lib = _lib.load()
-        if self._gpu is None:
-            self._gpu = ctypes.c_void_p()
-            _lib.check(lib.ts_bm25_create(int(self.gpu_device), ctypes.byref(self._gpu)))
+    def _csr(self):
+        """The index as ts_bm25_set_index takes it: (terms sorted, term_off int64 [V + 1], post_doc int32, post_tf
+        float32, idf float64 [V], len_norm float64 [N]); term t's id is its place in `terms`."""
         terms = sorted(self._postings)
-        self._term_id = {t: i for i, t in enumerate(terms)}
         off = np.zeros(len(terms) + 1, dtype=np.int64)
         for i, t in enumerate(terms):
             off[i + 1] = off[i] + len(self._postings[t][0])
@@ -184,7 +180,20 @@ class BM25Index:
                if nnz else np.zeros(1, np.float32))
         idf = np.array([self.idf[t] for t in terms], dtype=np.float64) if terms else np.zeros(1)
         ln = np.ascontiguousarray(self._len_norm, dtype=np.float64) if self.corpus_size else np.zeros(1)
-        _lib.check(lib.ts_bm25_set_index(self._gpu, self.corpus_size, len(terms), nnz,
+        return terms, off, docs, tfs, idf, ln
+
+    def _upload(self) -> None:
+        """CSR postings + statistics -> HBM (ts_bm25_set_index)."""
+        import ctypes
+        from . import _lib
+        lib = _lib.load()
+        if self._gpu is None:
+            self._gpu = ctypes.c_void_p()
+            _lib.check(lib.ts_bm25_create(int(self.gpu_device), ctypes.byref(self._gpu)))
+        terms, off, docs, tfs, idf, ln = self._csr()
+        self._term_id = {t: i for i, t in enumerate(terms)}
+        self._idf_of_id = idf[:len(terms)]
+        _lib.check(lib.ts_bm25_set_index(self._gpu, self.corpus_size, len(terms), int(off[-1]),
                                          off.ctypes.data, docs.ctypes.data, tfs.ctypes.data,
                                          idf.ctypes.data, ln.ctypes.data, float(self.k1 + 1)))
 
@@ -193,14 +202,24 @@ class BM25Index:
 
     def _search_gpu_many(self, queries: Sequence[str], top_k: int, arrays: bool = False, allowed=None):
         """All queries through ts_bm25_search_batch (ts_bm25_search_batch_filtered with ``allowed``: one bool
-        array over the documents, or None, per query): one call and one synchronisation for the batch."""
+        array over the documents, or None, per query): one call and one synchronisation for the batch.
+
+        The library lists the documents a query TOUCHES (at most GPU_MAX_K of them) and the untouched ones follow at
+        0.0, which is the host's ranking as long as every touched document scores above 0.0.  A query with an
+        idf <= 0 (refit_compat counts earlier fits' entries in df, so df > n happens) can leave touched documents at
+        0.0 or below, beside or behind the untouched ones: such a query, and every query when top_k is above
+        GPU_MAX_K, is scored by the host code from the same postings — the same arithmetic, the same lists."""
         from . import _lib
         lib = _lib.load()
-        terms = [np.array([self._term_id[t] for t in self.tokenize(q) if t in self._term_id], dtype=np.int32) for q in queries]
+        all_terms = [np.array([self._term_id[t] for t in self.tokenize(q) if t in self._term_id], dtype=np.int32) for q in queries]
+        k = min(int(top_k), max(self.corpus_size, 1))
+        on_host = [k > self.GPU_MAX_K or bool(len(t) and (self._idf_of_id[t] <= 0).any()) for t in all_terms]
+        if any(on_host):
+            return self._search_mixed(queries, top_k, arrays, allowed, on_host)
+        terms = all_terms
         off = np.zeros(len(queries) + 1, dtype=np.int64)
         off[1:] = np.cumsum([len(t) for t in terms])
         flat = np.concatenate(terms) if len(terms) and off[-1] else np.zeros(1, dtype=np.int32)
-        k = min(int(top_k), max(self.corpus_size, 1))
         nq = len(queries)
         out_s = np.zeros((nq, max(k, 1)), dtype=np.float64)
         out_i = np.zeros((nq, max(k, 1)), dtype=np.int64)
@@ -241,6 +260,23 @@ class BM25Index:
         return [self._pad_with_zero_scores(list(zip(out_i[q, : n_out[q]].tolist(), out_s[q, : n_out[q]].tolist())), top_k,
                                            allow_of(q))
                 for q in range(nq)]
+
+    def _search_mixed(self, queries, top_k, arrays, allowed, on_host):
+        """_search_gpu_many when some queries are the host's (`on_host`): those through _search_host, the others in
+        one GPU batch, every result in its query's place."""
+        gpu_q = [q for q in range(len(queries)) if not on_host[q]]
+        out = [None] * len(queries)
+        if gpu_q:
+            got = self._search_gpu_many([queries[q] for q in gpu_q], top_k, arrays,
+                                        None if allowed is None else [allowed[q] for q in gpu_q])
+            for q, r in zip(gpu_q, got):
+                out[q] = r
+        for q in range(len(queries)):
+            if on_host[q]:
+                r = self._search_host(queries[q], top_k, None if allowed is None else allowed[q])
+                out[q] = ((np.array([i for i, _ in r], dtype=np.int64), np.array([v for _, v in r], dtype=np.float64))
+                          if arrays else r)
+        return out
 
     def _pad_with_zero_scores(self, res: List[Tuple[int, float]], top_k: int, allowed=None) -> List[Tuple[int, float]]:
         """``allowed`` (bool array over the documents, or None): a filtered search pads with allowed documents only."""
@@ -325,6 +361,9 @@ class BM25Index:
             if allowed is None:
                 return self._search_gpu(query, top_k)
             return self._search_gpu_many([query], top_k, allowed=[allowed])[0]
+        return self._search_host(query, top_k, allowed)
+
+    def _search_host(self, query: str, top_k: int, allowed=None) -> List[Tuple[int, float]]:
         s = self.scores(query)
         if allowed is not None:
             cand = np.flatnonzero(np.asarray(allowed, dtype=bool))
