@@ -56,7 +56,9 @@ extern "C" {
  * ts_update_ivf: an index that is never updated runs the code it ran before.  So was ts_compact_ivf: no existing
  * signature changed, and an index that is never compacted runs the code it ran before.  So were ts_index_range_search
  * and ts_index_range_fetch: no existing signature changed, and a caller that never runs a range search sees the
- * library it was built against (no existing kernel changed).                                                    */
+ * library it was built against (no existing kernel changed).  So was e4m3 index storage (ts_index_create accepts
+ * TS_FP8_E4M3; ts_index_set_fp8_scale_log2, ts_index_fp8_scale_log2): no existing signature changed, and an index of
+ * another storage dtype runs the kernels it ran before.                                                         */
 #define TS_ABI_VERSION 4
 
 typedef struct ts_index ts_index; /* opaque */
@@ -73,7 +75,8 @@ enum ts_status {
 };
 
 enum ts_dtype { TS_F32 = 0, TS_F16 = 1, TS_BF16 = 2,
-               TS_FP8_E4M3 = 3 /* OCP e4m3fn: only the e4m3 token-store entry points below take it */ };
+               TS_FP8_E4M3 = 3 /* OCP e4m3fn: a storage dtype of ts_index_create ("e4m3 index storage" below) and the
+                                  element type of the e4m3 token-store entry points; never a rows / query dtype */ };
 
 enum ts_metric { TS_METRIC_INNER_PRODUCT = 0 };
 
@@ -109,7 +112,8 @@ enum ts_metric { TS_METRIC_INNER_PRODUCT = 0 };
 /* ---- index lifetime ------------------------------------------------------
  * replaces faiss.IndexFlatIP(d) (reference src/stage1_retriever.py:263,276).
  * storage_dtype: element type the corpus is kept in (TS_F32 = FAISS-exact
- * storage; TS_F16 / TS_BF16 halve the bytes scanned).                        */
+ * storage; TS_F16 / TS_BF16 halve the bytes scanned; TS_FP8_E4M3 halves them
+ * again, see "e4m3 index storage" below).                                    */
 int ts_index_create(int32_t dim, int32_t storage_dtype, int32_t metric,
                     int32_t device, ts_index** out);
 int ts_index_destroy(ts_index* h);
@@ -314,6 +318,22 @@ int ts_index_update(ts_index* h, const int64_t* ids, int64_t n, const void* rows
 int64_t ts_index_ntotal(const ts_index* h);
 int32_t ts_index_dim(const ts_index* h);
 int32_t ts_index_dtype(const ts_index* h);
+
+/* ---- e4m3 index storage (TS_FP8_E4M3) ----------------------------------------------------------
+ * One byte per element, scored in place.  An index carries one scale exponent s (0 .. 15, default 8): element x is
+ * stored as e4m3fn_rne(x * 2^s): round to nearest even, e4m3 subnormals kept, |x * 2^s| > 448 and +-Inf saturate to
+ * +-448, NaN stores 0x7F.  There is no per-row scale (scores are compared across rows), so add, update and several
+ * adds are bit-reproducible; with TS_FLAG_NORMALIZE the f32 quotient x / (|x| + 1e-8) is quantised.  Unit-norm rows
+ * fit the default (|x_i| <= 1 <= 448 / 256).  Queries are rounded to bf16 whatever their dtype; a score equals, bit
+ * for bit, that of a TS_BF16 index holding the decoded rows.  ts_index_reconstruct returns the decoded values
+ * e4m3 * 2^-s.  dim is padded to a multiple of 256 and is at most 2048.
+ * Supported: add, reserve, reset, id offset, reconstruct, search (synchronous, asynchronous), search_filtered, scores,
+ * remove, compact, update.  TS_FLAG_ONE_LAUNCH, TS_FLAG_PIPELINE, TS_FLAG_COALESCE and the wide-pass flags are ignored
+ * (ts_coalesce_groups* return 0 for it); ts_index_range_search returns TS_ERR_UNSUPPORTED, and there is no IVF form.
+ * ts_index_set_fp8_scale_log2: TS_ERR_INVALID for s outside 0 .. 15, for an index of another storage dtype, and once
+ * the index holds rows (ts_index_reset empties it).  ts_index_fp8_scale_log2: s, or -1 for another storage dtype.  */
+int ts_index_set_fp8_scale_log2(ts_index* h, int32_t s);
+int32_t ts_index_fp8_scale_log2(const ts_index* h);
 /* row-shard support: ids reported by search = local row + offset            */
 int ts_index_set_id_offset(ts_index* h, int64_t offset);
 /* copy rows [row0, row0+n) back out as row-major float32 (host or device):

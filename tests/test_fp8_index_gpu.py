@@ -1,0 +1,522 @@
+"""The fp8 (e4m3) stage-1 index on the GPU.
+
+Stored bytes: ``reconstruct_n()`` equals ``decode(quantize_rows_e4m3_fixed_reference(x, s))`` bit for bit.
+Scores: a bf16 ``FlatIPIndex`` built from the fp8 index's ``reconstruct_n()`` (the mirror) holds exactly the values
+the fp8 scan converts its bytes to, and walks the same k steps, so ids and score bits are EQUAL, with no tolerance,
+on every path.  Relevance: decided by the error lemma of fp8_index_model.py."""
+import ctypes
+
+import numpy as np
+import pytest
+
+import fp8_index_model as fm
+
+pytestmark = pytest.mark.gpu
+
+N_FILTER, N_DENSE = 40_000, 5_000
+
+
+@pytest.fixture(scope="module")
+def torch_mod():
+    import torch
+    assert torch.cuda.is_available()
+    return torch
+
+
+def _ix():
+    from tristage_rag_amd import index
+    return index
+
+
+def _fp8(d, rows=None, s=8, **kw):
+    idx = _ix().FlatIPIndex(d, dtype="fp8", fp8_scale_log2=s)
+    if rows is not None:
+        idx.add(rows, **kw)
+    return idx
+
+
+def _mirror(idx):
+    """The bf16 index of the decoded rows; it takes the same five-launch filter path as the fp8 index."""
+    m = _ix().FlatIPIndex(idx.d, dtype="bf16")
+    m.classic_filter = True
+    m.coalesce = False
+    rec = idx.reconstruct_n()
+    m.add(rec)
+    assert np.array_equal(m.reconstruct_n().view(np.uint32), rec.view(np.uint32))   # every e4m3 value is exact in bf16
+    return m
+
+
+def _bits(a):
+    a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def _ids(a):
+    return a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
+
+
+def _same(got, want):
+    (D, I), (Dm, Im) = got, want
+    assert np.array_equal(_ids(I), _ids(Im)), "ids"
+    assert np.array_equal(_bits(D), _bits(Dm)), "score bits"
+
+
+def _queries(b, d, seed):
+    return fm.clamp_queries(fm.unit_rows(b, d, seed))
+
+
+class Pair:
+    def __init__(self, n, d, seed, s=8):
+        self.rows = fm.unit_rows(n, d, seed)
+        self.idx = _fp8(d, self.rows, s=s)
+        self.mirror = _mirror(self.idx)
+        self.n, self.d = n, d
+
+    def close(self):
+        self.idx.close()
+        self.mirror.close()
+
+
+@pytest.fixture(scope="module")
+def big():
+    p = Pair(N_FILTER, 100, seed=1)
+    yield p
+    p.close()
+
+
+@pytest.fixture(scope="module")
+def small():
+    p = Pair(N_DENSE + 3, 100, seed=2)
+    yield p
+    p.close()
+
+
+# ------------------------------------------------------------------ stored bytes
+def _wide_rows(n, d, seed):
+    """Unit rows times magnitudes from 2^-14 to 2^3: e4m3 subnormals, normals and saturated values at every scale."""
+    g = np.random.default_rng(seed)
+    x = fm.unit_rows(n, d, seed) * np.exp2(g.integers(-14, 4, size=(n, 1))).astype(np.float32)
+    x[0, :4] = [0.0, -0.0, np.inf, -np.inf]
+    x[1, :3] = [1e30, -1e30, 2.0 ** -17]
+    return x.astype(np.float32)
+
+
+@pytest.mark.parametrize("d,s", [(100, 8), (384, 8), (768, 8), (1024, 8), (100, 0), (768, 0), (100, 15), (768, 15)])
+def test_stored_bytes_every_input_dtype_host_and_device(d, s, torch_mod):
+    torch = torch_mod
+    ix = _ix()
+    n = 1000 + 7
+    x = _wide_rows(n, d, seed=d + s)
+    with np.errstate(over="ignore"):
+        x16 = x.astype(np.float16)
+    cases = {
+        "host_f32": (x, x),
+        "host_f16": (x16, x16.astype(np.float32)),
+        "host_bf16": (torch.from_numpy(x).to(torch.bfloat16), torch.from_numpy(x).to(torch.bfloat16).float().numpy()),
+        "dev_f32": (torch.from_numpy(x).cuda(), x),
+        "dev_f16": (torch.from_numpy(x).cuda().half(), torch.from_numpy(x).half().float().numpy()),
+        "dev_bf16": (torch.from_numpy(x).cuda().bfloat16(), torch.from_numpy(x).bfloat16().float().numpy()),
+    }
+    for name, (given, exact) in cases.items():
+        idx = _fp8(d, given, s=s)
+        assert idx.storage_dtype == "fp8" and idx.fp8_scale_log2 == s and idx.ntotal == n
+        want = ix.decode_rows_e4m3_fixed(ix.quantize_rows_e4m3_fixed_reference(exact, s), s)
+        got = idx.reconstruct_n()
+        assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), name
+        assert np.array_equal(idx.reconstruct_n(33, 100).view(np.uint32), want[33:133].view(np.uint32)), name
+        idx.close()
+
+
+def test_nan_stores_7f(torch_mod):
+    x = fm.unit_rows(40, 100, 3)
+    x[5, 17] = np.nan
+    idx = _fp8(100, x)
+    rec = idx.reconstruct_n()
+    assert np.isnan(rec[5, 17]) and np.isnan(rec).sum() == 1
+    idx.close()
+
+
+@pytest.mark.parametrize("d", [100, 768])
+def test_three_adds_equal_one_add(d, torch_mod):
+    x = _wide_rows(1000 + 7, d, seed=5)
+    one = _fp8(d, x)
+    three = _fp8(d)
+    three.reserve(x.shape[0])
+    for a, b in ((0, 45), (45, 700), (700, x.shape[0])):     # cuts inside row blocks
+        three.add(torch_mod.from_numpy(x[a:b]).cuda() if a else x[a:b])
+    assert np.array_equal(one.reconstruct_n().view(np.uint32), three.reconstruct_n().view(np.uint32))
+    three.reset()
+    assert three.ntotal == 0
+    three.set_fp8_scale_log2(6)                              # empty again: the scale may change
+    three.add(x)
+    ix = _ix()
+    assert np.array_equal(three.reconstruct_n().view(np.uint32),
+                          ix.decode_rows_e4m3_fixed(ix.quantize_rows_e4m3_fixed_reference(x, 6), 6).view(np.uint32))
+    one.close()
+    three.close()
+
+
+@pytest.mark.parametrize("d", [100, 768])
+def test_normalize_quantises_the_f32_quotient(d, torch_mod):
+    ix = _ix()
+    g = np.random.default_rng(d)
+    x = (g.standard_normal((1000 + 7, d)) * 3).astype(np.float32)
+    ref = ix.FlatIPIndex(d, dtype="f32")
+    ref.add(x, normalize=True)
+    quotient = ref.reconstruct_n()
+    for given in (x, torch_mod.from_numpy(x).cuda()):
+        idx = _fp8(d, given, normalize=True)
+        want = ix.decode_rows_e4m3_fixed(ix.quantize_rows_e4m3_fixed_reference(quotient, 8), 8)
+        assert np.array_equal(idx.reconstruct_n().view(np.uint32), want.view(np.uint32))
+        idx.close()
+    ref.close()
+
+
+# ------------------------------------------------------------------ scores to the bit
+@pytest.mark.parametrize("B", [1, 31, 33, 64, 100])
+@pytest.mark.parametrize("k", [1, 10, 1000, 2048, 4096])
+def test_search_equals_the_mirror_filter_corpus(big, B, k):
+    q = _queries(B, big.d, seed=B * 7 + k)
+    _same(big.idx.search(q, k), big.mirror.search(fm.to_bf16_f32(q), k))
+    path = big.idx.last_search_info()["path"]
+    # N = 40000: the filter path needs k <= 2048 and N >= 32 k; large k takes the dense path
+    assert path == ("filter" if k <= 1000 else "dense"), path
+    assert big.mirror.last_search_info()["path"] == path
+
+
+@pytest.mark.parametrize("B", [1, 31, 33, 64, 100])
+@pytest.mark.parametrize("k", [1, 10, 1000, 2048, 4096])
+def test_search_equals_the_mirror_dense_corpus(small, B, k):
+    q = _queries(B, small.d, seed=B * 11 + k)
+    _same(small.idx.search(q, k), small.mirror.search(fm.to_bf16_f32(q), k))
+    assert small.idx.last_search_info()["path"] == "dense"
+
+
+@pytest.mark.parametrize("d,n", [(384, N_FILTER), (768, N_FILTER), (1024, N_FILTER), (2048, 33_000), (768, N_DENSE)])
+def test_other_dimensions_both_query_halves(d, n, torch_mod):
+    p = Pair(n, d, seed=d)
+    for B in (20, 64):
+        q = _queries(B, d, seed=d + B)
+        _same(p.idx.search(q, 10), p.mirror.search(fm.to_bf16_f32(q), 10))
+        assert p.idx.last_search_info()["path"] == ("filter" if n >= 32768 else "dense")
+        _same(p.idx.search(q, 10, exact_dense=True), p.mirror.search(fm.to_bf16_f32(q), 10, exact_dense=True))
+    p.close()
+
+
+def test_query_dtypes_are_rounded_to_bf16(big, torch_mod):
+    torch = torch_mod
+    q = torch.from_numpy(_queries(40, big.d, seed=77)).cuda()
+    for qt in (q, q.half(), q.bfloat16()):
+        rounded = qt.bfloat16()                    # what the fp8 index does with any query dtype
+        _same(big.idx.search(qt, 50), big.mirror.search(rounded, 50))
+        _same(big.idx.search(qt, 50, exact_dense=True), big.mirror.search(rounded, 50, exact_dense=True))
+    qh = _queries(5, big.d, seed=78).astype(np.float16)
+    _same(big.idx.search(qh, 7), big.mirror.search(fm.to_bf16_f32(qh.astype(np.float32)), 7))
+
+
+def test_scores_matrix(big, small, torch_mod):
+    for p in (big, small):
+        q = _queries(33, p.d, seed=5)
+        got, want = p.idx.scores(q), p.mirror.scores(fm.to_bf16_f32(q))
+        assert got.shape == (33, p.n) and np.array_equal(got.view(np.uint32), want.view(np.uint32))
+
+
+def test_async_finish_and_ignored_flags(big, torch_mod):
+    torch = torch_mod
+    q = torch.from_numpy(_queries(100, big.d, seed=9)).cuda()
+    want = big.mirror.search(q.bfloat16(), 100)
+    for kw in ({}, {"inputs_ready": True}, {"one_launch": True}):       # COALESCE / PIPELINE / ONE_LAUNCH: ignored
+        D, I = big.idx.search(q, 100, async_=True, **kw)
+        assert big.idx.finish() == []
+        _same((D, I), want)
+    _same(big.idx.search(q, 100, one_launch=True), want)
+    info = big.idx.last_search_info()
+    assert info["path"] == "filter" and info["one_launch"] is False
+
+
+def test_id_offset(torch_mod):
+    p = Pair(N_FILTER, 100, seed=21)
+    p.idx.set_id_offset(7_000_000_000)
+    p.mirror.set_id_offset(7_000_000_000)
+    q = _queries(33, 100, seed=22)
+    got = p.idx.search(q, 20)
+    _same(got, p.mirror.search(fm.to_bf16_f32(q), 20))
+    assert got[1].min() >= 7_000_000_000
+    p.close()
+
+
+def test_large_k_through_search_large_k(torch_mod):
+    p = Pair(20_000, 100, seed=31)
+    q = _queries(3, 100, seed=32)
+    k = 17_000
+    assert k > p.idx.MAX_KERNEL_K
+    _same(p.idx.search(q, k), p.mirror.search(fm.to_bf16_f32(q), k))
+    p.close()
+
+
+@pytest.mark.parametrize("which", ["big", "small"])
+def test_allowed_masks(which, big, small, torch_mod):
+    p = big if which == "big" else small
+    g = np.random.default_rng(4)
+    B = 40
+    q = _queries(B, p.d, seed=41)
+    qm = fm.to_bf16_f32(q)
+    shared = g.random(p.n) < 0.3
+    _same(p.idx.search(q, 25, allowed=shared), p.mirror.search(qm, 25, allowed=shared))
+    if which == "big":
+        info = p.idx.last_filter_info()
+        assert info["filter_passes"] == 1 and info["dense_passes"] == 0       # the masked scan: one 64-query pass
+        assert 0 < info["live_blocks"] <= info["total_blocks"] == (p.n + 31) // 32
+    masks = [g.random(p.n) < 0.3, g.random(p.n) < 0.002, np.arange(p.n) % 97 == 0]
+    per_q = [None if j % 4 == 3 else masks[j % 3] for j in range(B)]
+    _same(p.idx.search(q, 25, allowed=per_q), p.mirror.search(qm, 25, allowed=per_q))
+    _same(p.idx.search(q, 25, allowed=per_q, exact_dense=True), p.mirror.search(qm, 25, allowed=per_q, exact_dense=True))
+    empty = np.zeros(p.n, dtype=bool)
+    D, I = p.idx.search(q, 5, allowed=empty)
+    assert (I == -1).all()
+    _same((D, I), p.mirror.search(qm, 5, allowed=empty))
+    tq = torch_mod.from_numpy(q).cuda()
+    D, I = p.idx.search(tq, 25, allowed=shared, async_=True)
+    p.idx.finish()
+    _same((D, I), p.mirror.search(qm, 25, allowed=shared))
+
+
+def test_ties_overflow_the_candidate_list(torch_mod):
+    d = 100
+    rows = fm.unit_rows(N_FILTER, d, seed=51)
+    rows[10_000:30_000] = rows[10_000]                       # 20000 equal rows: more than the 16384 candidate slots
+    idx = _fp8(d, rows)
+    mirror = _mirror(idx)
+    q = fm.clamp_queries(rows[10_000:10_001] + 0.01 * fm.unit_rows(1, d, 52))
+    got = idx.search(q, 100)
+    assert idx.last_search_info()["path"] == "filter+dense-fallback"
+    _same(got, mirror.search(fm.to_bf16_f32(q), 100))
+    assert np.array_equal(got[1][0], np.arange(10_000, 10_100))          # equal scores: ids ascending
+    idx.close()
+    mirror.close()
+
+
+# ------------------------------------------------------------------ mutations against the mirror
+def test_remove_update_compact_add(torch_mod):
+    ix = _ix()
+    d = 100
+    p = Pair(N_FILTER, d, seed=61)
+    q = _queries(40, d, seed=62)
+    qm = fm.to_bf16_f32(q)
+
+    def check(k=30):
+        _same(p.idx.search(q, k), p.mirror.search(qm, k))
+        _same(p.idx.search(q, k, exact_dense=True), p.mirror.search(qm, k, exact_dense=True))
+        assert p.idx.nlive == p.mirror.nlive and p.idx.ntotal == p.mirror.ntotal
+
+    check()
+    top = np.unique(p.idx.search(q, 5)[1])
+    gone = np.unique(np.concatenate([top, np.arange(64, 96), np.arange(0, N_FILTER, 997)]))   # hits, a whole block, a stride
+    assert p.idx.remove_ids(gone) == p.mirror.remove_ids(gone) == gone.size
+    check()
+    assert not np.isin(p.idx.search(q, 30)[1], gone).any()
+    assert np.array_equal(p.idx.live_words(), p.mirror.live_words())
+    # update: a whole row block, scattered rows, host and device rows
+    ids = np.setdiff1d(np.concatenate([np.arange(128, 160), np.array([1, 5000, 5001, 39_999])]), gone)
+    new = fm.unit_rows(ids.size, d, seed=63)
+    new[0] = q[0] / np.linalg.norm(q[0])                     # an updated row that has to enter the results
+    p.idx.update_rows(ids, new)
+    p.mirror.update_rows(ids, ix.decode_rows_e4m3_fixed(ix.quantize_rows_e4m3_fixed_reference(new, 8), 8))
+    check()
+    assert ids[0] in p.idx.search(q, 30)[1][0]
+    ids2 = ids[::2]
+    new2 = fm.unit_rows(ids2.size, d, seed=64)
+    p.idx.update_rows(ids2, torch_mod.from_numpy(new2).cuda().half())
+    p.mirror.update_rows(ids2, ix.decode_rows_e4m3_fixed(
+        ix.quantize_rows_e4m3_fixed_reference(new2.astype(np.float16).astype(np.float32), 8), 8))
+    check()
+    assert np.array_equal(p.idx.reconstruct_n().view(np.uint32), p.mirror.reconstruct_n().view(np.uint32))
+    a, b = p.idx.compact(), p.mirror.compact()
+    assert np.array_equal(a, b) and p.idx.ntotal == N_FILTER - gone.size == p.idx.nlive
+    check()
+    assert np.array_equal(p.idx.reconstruct_n().view(np.uint32), p.mirror.reconstruct_n().view(np.uint32))
+    more = fm.unit_rows(1000 + 7, d, seed=65)
+    p.idx.add(more)
+    p.mirror.add(ix.decode_rows_e4m3_fixed(ix.quantize_rows_e4m3_fixed_reference(more, 8), 8))
+    check()
+    p.close()
+
+
+# ------------------------------------------------------------------ planted relevance, decided by the lemma
+def test_planted_rows_are_the_top_20():
+    d, n, s = 768, N_FILTER, 8
+    g = np.random.default_rng(71)
+    q = fm.unit_rows(1, d, seed=72)
+    rows = fm.unit_rows(n, d, seed=73)
+    planted = np.sort(g.choice(n, size=20, replace=False))
+    noise = fm.unit_rows(20, d, seed=74).astype(np.float64)
+    noise -= (noise @ q[0].astype(np.float64))[:, None] * q[0].astype(np.float64)
+    noise /= np.linalg.norm(noise, axis=1, keepdims=True)
+    cos = np.linspace(0.9, 0.99, 20)
+    rows[planted] = (cos[:, None] * q[0].astype(np.float64) + np.sqrt(1 - cos ** 2)[:, None] * noise).astype(np.float32)
+    q64, r64 = q.astype(np.float64), rows.astype(np.float64)
+    exact = (q64 @ r64.T)[0]
+    background = np.setdiff1d(np.arange(n), planted)
+    assert exact[background].max() <= 0.3 and exact[planted].min() >= 0.9 - 1e-6
+    # the lemma (rows) plus the query's rounding to bf16 (2^-9 relative per element): |score - exact| <= 0.0625 + small
+    bound = fm.lemma_bound(q, rows, s)[0] + 2.0 ** -9 * (np.abs(q64) @ np.abs(r64).T)[0] * (1 + 2.0 ** -4)
+    assert bound.max() <= 0.0625 + 2.0 ** -8          # Cauchy-Schwarz: sum|q_i x_i| <= 1, sum|q_i| <= sqrt(768)
+    assert exact[planted].min() - exact[background].max() > 2 * bound.max() + 1e-4    # (f32 accumulation: < 1e-4)
+    idx = _fp8(d, rows, s=s)
+    D, I = idx.search(q, 20)
+    assert idx.last_search_info()["path"] == "filter"
+    assert np.array_equal(np.sort(I[0]), planted)
+    assert (np.abs(D[0].astype(np.float64) - exact[I[0]]) <= bound[I[0]] + 1e-4).all()
+    idx.close()
+
+
+# ------------------------------------------------------------------ retriever and pipeline
+def _pipeline(tmp_path, sub, dtype="fp8", **extra):
+    from test_pipeline_gpu import _build
+    (tmp_path / sub).mkdir()
+    return _build("cuda", tmp_path / sub, doubles=False, stage1_enable_bm25=False, stage1_index_dtype=dtype,
+                  stage2_precompute_document_embeddings=True, stage3_cache_document_tokens=True, **extra)
+
+
+PQ = ["neural networks attention", "language retrieval system", "gpu memory index", "token embedding search"]
+
+
+def _stage1_equals_mirror(p, mirror, filter=None, allowed=None):
+    s1 = p.stage1
+    k = s1.config.top_k_candidates
+    qt = s1._normalized_query_tensor(PQ)
+    D, I = mirror.search(qt.bfloat16(), k) if allowed is None else mirror.search(qt.bfloat16(), k, allowed=allowed)
+    D, I = D.cpu().numpy(), I.cpu().numpy()
+    for j, res in enumerate(s1.search_many(PQ, filter=filter)):
+        keep = I[j] >= 0
+        assert [r["doc_id"] for r in res] == I[j][keep].tolist()
+        assert np.array_equal(np.array([r["stage1_score"] for r in res], dtype=np.float32).view(np.uint32),
+                              D[j][keep].view(np.uint32))
+
+
+def test_pipeline_with_an_fp8_stage1_index(tmp_path, torch_mod):
+    from test_pipeline_gpu import _corpus
+    from test_update_host import updated_texts
+    docs = _corpus()
+    p = _pipeline(tmp_path, "a")
+    p.add_documents(docs)
+    idx = p.stage1.faiss_index
+    assert type(idx).__name__ == "FlatIPIndex" and idx.storage_dtype == "fp8" and idx.ntotal == len(docs)
+    assert p.stage1.config.index_dtype == "fp8"
+    mirror = _mirror(idx)
+    _stage1_equals_mirror(p, mirror)
+    assert all(len(p.search(q)["results"]) > 0 for q in PQ)
+    # filter=
+    keep = np.arange(len(docs)) % 3 != 0
+    _stage1_equals_mirror(p, mirror, filter=keep, allowed=keep)
+    with pytest.raises(NotImplementedError):
+        p.stage1.range_search(PQ[0], 0.1)
+    with pytest.raises(NotImplementedError):
+        idx.range_search(np.zeros((1, idx.d), np.float32), 0.1)
+    # remove, update, compact
+    gone = sorted({r["doc_id"] for res in p.search_many(PQ) for r in res["stage1_results"][:3]})
+    assert p.remove_documents(gone) == len(gone)
+    mirror.remove_ids(np.asarray(gone))
+    _stage1_equals_mirror(p, mirror)
+    ids = [i for i in (1, 7, 50, len(docs) - 1) if i not in gone]
+    assert p.update_documents(ids, updated_texts(docs, ids)) == len(ids)
+    mirror.close()
+    mirror = _mirror(idx)                      # (update moved rows: rebuilt from the decoded rows, then the tombstones)
+    mirror.remove_ids(np.asarray(gone))
+    _stage1_equals_mirror(p, mirror)
+    old2new = p.compact()
+    idx = p.stage1.faiss_index
+    assert idx.ntotal == len(docs) - len(gone) == idx.nlive and (np.asarray(old2new)[gone] == -1).all()
+    mirror.close()
+    mirror = _mirror(idx)
+    _stage1_equals_mirror(p, mirror)
+    # save / load: the decoded rows quantise back to the same bytes
+    path = str(tmp_path / "saved" / "pipe.json")
+    p.save_index(path)
+    q = _pipeline(tmp_path, "b")
+    q.load_index(path)
+    jdx = q.stage1.faiss_index
+    assert jdx.storage_dtype == "fp8" and jdx.ntotal == idx.ntotal
+    assert np.array_equal(jdx.reconstruct_n().view(np.uint32), idx.reconstruct_n().view(np.uint32))
+    for a, b in zip(p.search_many(PQ), q.search_many(PQ)):
+        for stage, key in (("stage1_results", "stage1_score"), ("stage2_results", "stage2_score"), ("results", "stage3_score")):
+            assert [(r["doc_id"], r[key]) for r in a[stage]] == [(r["doc_id"], r[key]) for r in b[stage]], stage
+    mirror.close()
+
+
+def test_ivf_retriever_keeps_its_rule_for_fp8(tmp_path, torch_mod):
+    from test_pipeline_gpu import _corpus
+    p = _pipeline(tmp_path, "ivf")
+    c = p.stage1.config
+    c.index_type, c.nlist, c.nprobe = "ivf", 8, 8
+    p.add_documents(_corpus(120))
+    assert type(p.stage1.faiss_index).__name__ == "IVFFlatIndex" and p.stage1.faiss_index.storage_dtype == "f16"
+
+
+# ------------------------------------------------------------------ errors
+def test_errors(torch_mod):
+    ix = _ix()
+    idx = _fp8(64)
+    assert idx.fp8_scale_log2 == 8
+    idx.set_fp8_scale_log2(3)
+    assert idx.fp8_scale_log2 == 3
+    for bad in (16, -1):
+        with pytest.raises(ValueError):
+            idx.set_fp8_scale_log2(bad)
+    idx.add(fm.unit_rows(10, 64, 1))
+    with pytest.raises(ValueError, match="empty"):
+        idx.set_fp8_scale_log2(8)
+    assert idx.fp8_scale_log2 == 3
+    with pytest.raises(NotImplementedError):
+        idx.range_search(fm.unit_rows(1, 64, 2), 0.5)
+    from tristage_rag_amd.sharded import ShardedFlatIPIndex
+    with pytest.raises(NotImplementedError):
+        ShardedFlatIPIndex(64, 10, local_index=idx)
+    with pytest.raises(NotImplementedError):
+        ShardedFlatIPIndex(64, 10, dtype="fp8")
+    idx.close()
+    with pytest.raises(ValueError):
+        ix.FlatIPIndex(64, dtype="fp8", fp8_scale_log2=16)
+    with pytest.raises(NotImplementedError):
+        ix.FlatIPIndex(2304, dtype="fp8")
+    with pytest.raises(NotImplementedError):
+        ix.IVFFlatIndex(64, 4, dtype="fp8")
+    f16 = ix.FlatIPIndex(64, dtype="f16")
+    assert f16.fp8_scale_log2 is None
+    with pytest.raises(ValueError):
+        f16.set_fp8_scale_log2(8)
+    f16.close()
+    ok = ix.FlatIPIndex(2048, dtype="fp8")
+    ok.close()
+
+
+# ------------------------------------------------------------------ the C level
+def test_c_abi_create_add_search_with_host_pointers(torch_mod):
+    from tristage_rag_amd import _lib
+    ix = _ix()
+    lib = _lib.load()
+    d, n, B, k = 100, N_DENSE, 5, 10
+    h = ctypes.c_void_p()
+    assert lib.ts_index_create(2304, _lib.TS_FP8_E4M3, 0, 0, ctypes.byref(h)) == _lib.TS_ERR_UNSUPPORTED
+    assert lib.ts_index_create(d, _lib.TS_FP8_E4M3, 0, 0, ctypes.byref(h)) == _lib.TS_OK
+    assert lib.ts_index_dtype(h) == _lib.TS_FP8_E4M3 and lib.ts_index_fp8_scale_log2(h) == 8
+    assert lib.ts_index_set_fp8_scale_log2(h, 16) == _lib.TS_ERR_INVALID
+    assert lib.ts_index_set_fp8_scale_log2(h, 7) == _lib.TS_OK
+    rows = fm.unit_rows(n, d, seed=81)
+    q = _queries(B, d, seed=82)
+    P = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+    assert lib.ts_index_add(h, P(rows), n, _lib.TS_F32, _lib.TS_FLAG_HOST_PTR, None) == _lib.TS_OK
+    assert lib.ts_index_set_fp8_scale_log2(h, 8) == _lib.TS_ERR_INVALID
+    D, I = np.empty((B, k), np.float32), np.empty((B, k), np.int64)
+    assert lib.ts_index_search(h, P(q), B, _lib.TS_F32, k, P(D), P(I), _lib.TS_FLAG_HOST_PTR, None) == _lib.TS_OK
+    lims = np.zeros(B + 1, np.int64)
+    rad = np.zeros(B, np.float32)
+    assert lib.ts_index_range_search(h, P(q), B, _lib.TS_F32, P(rad), None, 0, 0, None, 0, P(lims),
+                                     _lib.TS_FLAG_HOST_PTR, None) == _lib.TS_ERR_UNSUPPORTED
+    assert lib.ts_index_destroy(h) == _lib.TS_OK
+    # the host model of that search: float64 scores of the decoded rows against the bf16-rounded queries
+    dec = ix.decode_rows_e4m3_fixed(ix.quantize_rows_e4m3_fixed_reference(rows, 7), 7).astype(np.float64)
+    S = fm.to_bf16_f32(q).astype(np.float64) @ dec.T
+    for b in range(B):
+        assert np.abs(D[b].astype(np.float64) - S[b][I[b]]).max() <= 1e-5
+        assert np.abs(np.sort(S[b])[::-1][:k] - D[b]).max() <= 1e-5

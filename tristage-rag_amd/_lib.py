@@ -59,6 +59,8 @@ SIGNATURES = {
     "ts_index_ntotal": (c_int64, [c_void_p]),
     "ts_index_dim": (c_int32, [c_void_p]),
     "ts_index_dtype": (c_int32, [c_void_p]),
+    "ts_index_set_fp8_scale_log2": (c_int32, [c_void_p, c_int32]),
+    "ts_index_fp8_scale_log2": (c_int32, [c_void_p]),
     "ts_index_set_id_offset": (c_int32, [c_void_p, c_int64]),
     "ts_index_reconstruct": (c_int32, [c_void_p, c_int64, c_int64, c_void_p, c_uint32, c_void_p]),
     "ts_index_last_search_info": (c_int32, [c_void_p, POINTER(c_int64)]),

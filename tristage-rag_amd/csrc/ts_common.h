@@ -77,6 +77,9 @@ static inline int ts_allow_max_lds(TsDeviceOnce& o, const void* kernel) {
 //             -> exactly the A fragment of v_mfma_f32_32x32x16_{f16,bf16}
 //   f32:      the unit holds 4 elements, k = 8*g + 2*t + h    (t = 0..3)
 //             -> element t is the A operand of the t-th v_mfma_f32_32x32x2_f32
+//   e4m3:     the unit holds 16 elements, k = 32*g + 16*m + 8*h + j   (m = 0/1, j = 0..7): bytes 0-7 and 8-15
+//             are, once converted to bf16, the A fragments of k steps 2g and 2g+1 of the 16-bit map
+//             (ts_scan_fp8.hip); its Q image is the bf16 image of the same padded dimension
 //
 // The query batch is laid out the same way (the "Q image"): unit index
 // (g*QH + hq)*64 + l holds, for query 32*hq + (l & 31), the same k's.
@@ -94,20 +97,24 @@ struct TsLayout {
   int epl;     // elements per lane per group (8 or 4)
   int gk;      // k values covered by one group (16 or 8)
   int dim;     // logical dimension
-  int dpad;    // padded dimension (multiple of gk*TS_RING)
+  int dpad;    // padded dimension (multiple of gk*TS_RING: 128 for 16-bit storage, 256 for e4m3)
   int kg;      // groups per row block = dpad / gk
+  int qkg;     // 1 KiB units of the Q image per 32 queries: kg, or 2 * kg for e4m3 storage (a bf16 image)
+  int fp8_scale_log2;   // e4m3 storage: element x is stored as e4m3(x * 2^s) (ts_index_set_fp8_scale_log2)
 };
 
 static inline TsLayout ts_make_layout(int dim, int dtype) {
   TsLayout L;
   L.dtype = dtype;
-  L.esize = (dtype == TS_F32) ? 4 : 2;
+  L.esize = (dtype == TS_F32) ? 4 : (dtype == TS_FP8_E4M3 ? 1 : 2);
   L.epl = 16 / L.esize;
   L.gk = 2 * L.epl;
   L.dim = dim;
   int q = L.gk * TS_RING;
   L.dpad = ((dim + q - 1) / q) * q;
   L.kg = L.dpad / L.gk;
+  L.qkg = (dtype == TS_FP8_E4M3) ? 2 * L.kg : L.kg;
+  L.fp8_scale_log2 = 8;
   return L;
 }
 
@@ -252,6 +259,20 @@ size_t ts_scan_f32s_lds_bytes(const TsLayout& L);
 int ts_launch_scan_f32s(const TsLayout& L, int mode, const ScanParams& p, int num_cus, hipStream_t stream);
 int ts_launch_qprep_f32s(const TsLayout& L, const void* q, int q_dtype, int nq, uint4* qimg, uint32_t* cand_cnt,
                          uint32_t* status, hipStream_t stream);
+// e4m3 storage (ts_scan_fp8.hip): the scans, the Q image (the queries rounded to bf16, times
+// 2^-fp8_scale_log2), the quantising relayout and the decoding reconstruct.  ts_launch_scan / _scan_masked / _qprep /
+// _relayout / _reconstruct hand an e4m3 layout to these.
+size_t ts_scan_fp8_lds_bytes(const TsLayout& L, int qh);
+int ts_launch_scan_fp8(const TsLayout& L, int mode, int qh, const ScanParams& p, int num_cus, hipStream_t stream);
+int ts_launch_scan_masked_fp8(const TsLayout& L, int qh, const MaskedScanParams& p, int num_cus, hipStream_t stream);
+int ts_launch_qprep_fp8(const TsLayout& L, const void* q, int q_dtype, int nq, int qh, uint4* qimg, uint32_t* cand_cnt,
+                        uint32_t* status, hipStream_t stream);
+int ts_launch_relayout_fp8(const TsLayout& L, const void* rows, int in_dtype, int64_t n, int64_t row0, uint4* tiled,
+                           bool normalize, float* den_scratch, hipStream_t stream);
+// den[i] = |row_i| + 1e-8 (ts_scan.hip: the kernel every normalising relayout uses)
+int ts_launch_row_den(const void* rows, int in_dtype, int64_t n, int dim, float* den, hipStream_t stream);
+int ts_launch_reconstruct_fp8(const TsLayout& L, const uint4* tiled, int64_t row0, int64_t n, float* out,
+                              hipStream_t stream);
 
 // rows [n, dim] (row-major, in_dtype) -> tiled storage at rows [row0, row0+n)
 int ts_launch_relayout(const TsLayout& L, const void* rows, int in_dtype,

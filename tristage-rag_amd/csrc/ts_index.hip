@@ -276,7 +276,8 @@ extern "C" int ts_index_create(int32_t dim, int32_t storage_dtype, int32_t metri
   if (!out) { ts_set_error("out is null"); return TS_ERR_INVALID; }
   *out = nullptr;
   if (dim <= 0 || dim > 65536) { ts_set_error("bad dim %d", dim); return TS_ERR_INVALID; }
-  if (storage_dtype != TS_F32 && storage_dtype != TS_F16 && storage_dtype != TS_BF16) {
+  if (storage_dtype != TS_F32 && storage_dtype != TS_F16 && storage_dtype != TS_BF16 &&
+      storage_dtype != TS_FP8_E4M3) {
     ts_set_error("bad storage dtype %d", storage_dtype);
     return TS_ERR_INVALID;
   }
@@ -311,7 +312,7 @@ extern "C" int ts_index_create(int32_t dim, int32_t storage_dtype, int32_t metri
   for (ts_index::WSet& w : h->ws) {
     if (st == TS_OK) st = ensure(w.small, 4096);
     if (st == TS_OK && hipMemset(w.small.p, 0, 4096) != hipSuccess) { ts_set_error("hipMemset failed"); st = TS_ERR_HIP; }
-    if (st == TS_OK) st = ensure(w.qimg, (size_t)L.kg * 2 * 1024);
+    if (st == TS_OK) st = ensure(w.qimg, (size_t)L.qkg * 2 * 1024);
     if (st == TS_OK && (hipEventCreateWithFlags(&w.ev_pro, hipEventDisableTiming) != hipSuccess ||
                         hipEventCreateWithFlags(&w.ev_scan, hipEventDisableTiming) != hipSuccess ||
                         hipEventCreateWithFlags(&w.ev_sel, hipEventDisableTiming) != hipSuccess ||
@@ -392,6 +393,24 @@ extern "C" int ts_index_reserve(ts_index* h, int64_t nrows) {
 extern "C" int64_t ts_index_ntotal(const ts_index* h) { return h ? h->ntotal : -1; }
 extern "C" int32_t ts_index_dim(const ts_index* h) { return h ? h->L.dim : -1; }
 extern "C" int32_t ts_index_dtype(const ts_index* h) { return h ? h->L.dtype : -1; }
+
+// e4m3 storage: element x is stored as e4m3(x * 2^s).  s belongs to the stored bytes, so it can
+// change only while there are none.
+extern "C" int ts_index_set_fp8_scale_log2(ts_index* h, int32_t s) {
+  if (!h) { ts_set_error("null handle"); return TS_ERR_INVALID; }
+  if (h->L.dtype != TS_FP8_E4M3) { ts_set_error("the index does not store e4m3"); return TS_ERR_INVALID; }
+  if (s < 0 || s > 15) { ts_set_error("fp8 scale exponent %d is outside 0 .. 15", s); return TS_ERR_INVALID; }
+  if (h->ntotal > 0) {
+    ts_set_error("the fp8 scale exponent can be set only while the index is empty (%lld rows)", (long long)h->ntotal);
+    return TS_ERR_INVALID;
+  }
+  h->L.fp8_scale_log2 = s;
+  return TS_OK;
+}
+
+extern "C" int32_t ts_index_fp8_scale_log2(const ts_index* h) {
+  return (h && h->L.dtype == TS_FP8_E4M3) ? h->L.fp8_scale_log2 : -1;
+}
 
 extern "C" int ts_index_set_id_offset(ts_index* h, int64_t offset) {
   if (!h) { ts_set_error("null handle"); return TS_ERR_INVALID; }
@@ -763,6 +782,11 @@ static int search_pass_on(ts_index* h, ts_index::WSet& W, const void* dq, int nq
     flags |= TS_FLAG_CLASSIC;
     std::lock_guard<std::mutex> lk(h->mu);
     fseq = h->fseq;
+  }
+  if (h->L.dtype == TS_FP8_E4M3) {
+    // e4m3 storage has the five-launch kernels only (ts_scan_fp8.hip): as for a masked pass
+    flags &= ~(uint32_t)(TS_FLAG_ONE_LAUNCH | TS_FLAG_PIPELINE);
+    flags |= TS_FLAG_CLASSIC;
   }
   const bool filter = !(flags & TS_FLAG_NO_FILTER) && k <= kMaxFilterK && N >= kMinFilterRows &&
                       N >= 32 * (int64_t)k && !(mc && h->L.dtype == TS_F32);
@@ -1814,6 +1838,10 @@ extern "C" int ts_index_range_search(ts_index* h, const void* queries, int32_t n
   }
   for (int32_t q = 0; q < nq; ++q) lims[q + 1] = 0;
   if (!h) { ts_set_error("null handle"); return TS_ERR_INVALID; }
+  if (h->L.dtype == TS_FP8_E4M3) {
+    ts_set_error("range_search is not supported on an e4m3 (fp8) index");
+    return TS_ERR_UNSUPPORTED;
+  }
   const int64_t N = h->ntotal;
   const int64_t need_words = (N + 31) / 32;
   if (mask_of_query && n_masks > 0 && allow_words < need_words) {

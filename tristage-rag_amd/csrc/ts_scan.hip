@@ -1129,6 +1129,7 @@ bool ts_use_f32_split(const TsLayout& L, int qh) {
 }
 
 size_t ts_scan_lds_bytes(const TsLayout& L, int qh) {
+  if (L.dtype == TS_FP8_E4M3) return ts_scan_fp8_lds_bytes(L, qh);
   if (ts_use_f32_split(L, qh)) return ts_scan_f32s_lds_bytes(L);
   return (size_t)L.kg * qh * 1024 + sizeof(StageLds);
 }
@@ -1171,6 +1172,7 @@ static int launch_scan_masked_t(const TsLayout& L, const MaskedScanParams& p, in
 
 int ts_launch_scan_masked(const TsLayout& L, int qh, const MaskedScanParams& p, int num_cus, hipStream_t stream) {
   if (p.nwork <= 0) return TS_OK;
+  if (L.dtype == TS_FP8_E4M3) return ts_launch_scan_masked_fp8(L, qh, p, num_cus, stream);
   if (ts_scan_lds_bytes(L, qh) > 160 * 1024) {
     ts_set_error("dimension %d too large for the LDS-resident query image", L.dim);
     return TS_ERR_UNSUPPORTED;
@@ -1199,6 +1201,7 @@ static int launch_scan_dt(const TsLayout& L, int mode, int qh,
 int ts_launch_scan(const TsLayout& L, int mode, int qh, const ScanParams& p,
                    int num_cus, hipStream_t stream) {
   if (p.nwork <= 0) return TS_OK;
+  if (L.dtype == TS_FP8_E4M3) return ts_launch_scan_fp8(L, mode, qh, p, num_cus, stream);
   if (ts_use_f32_split(L, qh)) return ts_launch_scan_f32s(L, mode, p, num_cus, stream);
   if (ts_scan_lds_bytes(L, qh) > 160 * 1024) {
     ts_set_error("dimension %d too large for the LDS-resident query image", L.dim);
@@ -1335,6 +1338,19 @@ __global__ void relayout_kernel(const TIN* rows, int64_t n, int dim,
   reinterpret_cast<u32x4*>(tiled)[(size_t)(b * kg + g) * 64 + lane] = out;
 }
 
+// den[i] = |row_i| + 1e-8 of n rows (the e4m3 relayout of ts_scan_fp8.hip normalises with the same kernel)
+int ts_launch_row_den(const void* rows, int in_dtype, int64_t n, int dim, float* den, hipStream_t s) {
+  const int blocks = (int)((n + 3) / 4);
+  switch (in_dtype) {
+    case TS_F32: hipLaunchKernelGGL(row_den_kernel<float>, dim3(blocks), dim3(256), 0, s, (const float*)rows, n, dim, den); break;
+    case TS_F16: hipLaunchKernelGGL(row_den_kernel<_Float16>, dim3(blocks), dim3(256), 0, s, (const _Float16*)rows, n, dim, den); break;
+    case TS_BF16: hipLaunchKernelGGL(row_den_kernel<__bf16>, dim3(blocks), dim3(256), 0, s, (const __bf16*)rows, n, dim, den); break;
+    default: ts_set_error("bad rows dtype %d", in_dtype); return TS_ERR_INVALID;
+  }
+  TS_HIP(hipGetLastError());
+  return TS_OK;
+}
+
 template <typename TIN>
 static int relayout_t(const TsLayout& L, const TIN* rows, int64_t n, int64_t row0,
                       uint4* tiled, bool normalize, float* den, hipStream_t s) {
@@ -1365,6 +1381,8 @@ int ts_launch_relayout(const TsLayout& L, const void* rows, int in_dtype, int64_
                        int64_t row0, uint4* tiled, bool normalize,
                        float* den_scratch, hipStream_t stream) {
   if (n <= 0) return TS_OK;
+  if (L.dtype == TS_FP8_E4M3)
+    return ts_launch_relayout_fp8(L, rows, in_dtype, n, row0, tiled, normalize, den_scratch, stream);
   switch (in_dtype) {
     case TS_F32: return relayout_t<float>(L, (const float*)rows, n, row0, tiled, normalize, den_scratch, stream);
     case TS_F16: return relayout_t<_Float16>(L, (const _Float16*)rows, n, row0, tiled, normalize, den_scratch, stream);
@@ -1410,6 +1428,7 @@ __global__ void reconstruct_kernel(const uint4* tiled, int64_t row0, int64_t n,
 int ts_launch_reconstruct(const TsLayout& L, const uint4* tiled, int64_t row0,
                           int64_t n, float* out, hipStream_t stream) {
   if (n <= 0) return TS_OK;
+  if (L.dtype == TS_FP8_E4M3) return ts_launch_reconstruct_fp8(L, tiled, row0, n, out, stream);
   const int64_t total = n * L.kg * 2;
   const int64_t blocks = (total + 255) / 256;
   if (blocks > 0x7fffffffLL) {
@@ -1460,6 +1479,7 @@ __global__ void qprep_kernel(const TIN* q, int nq, int dim, int kg, int qh, int 
 int ts_launch_qprep(const TsLayout& L, const void* q, int q_dtype, int nq, int qh,
                     uint4* qimg, uint32_t* cand_cnt, uint32_t* status,
                     hipStream_t stream) {
+  if (L.dtype == TS_FP8_E4M3) return ts_launch_qprep_fp8(L, q, q_dtype, nq, qh, qimg, cand_cnt, status, stream);
   if (ts_use_f32_split(L, qh)) return ts_launch_qprep_f32s(L, q, q_dtype, nq, qimg, cand_cnt, status, stream);
   const int units = L.kg * qh * 64;
   const int blocks = (units + 255) / 256;

@@ -1,0 +1,498 @@
+// e4m3-storage scan (TS_FP8_E4M3 flat index, gfx950): one byte per corpus element, scored in place.
+//
+// Format: element x of an index with scale exponent s is the byte e4m3fn_rne(x * 2^s) (fp8_quantize below: round to
+// nearest even on the f32 bits, e4m3 subnormals kept, |x * 2^s| > 448 and Inf saturate to +-448, NaN -> 0x7F).  One
+// fixed power of two per index and no per-row scale: stage-1 scores are compared across rows.
+//
+// Layout (ts_common.h): a 16-byte unit of lane h*32 + r in k group g holds k = 32g + 16m + 8h + j (m = 0/1, j = 0..7),
+// so bytes 0-7 / 8-15, converted in registers with v_cvt_scalef32_pk_bf16_fp8 (every e4m3 value is exact in bf16), are
+// the A fragments of k steps 2g / 2g + 1 of v_mfma_f32_32x32x16_bf16.  The query image is the bf16 image of a bf16
+// layout of the same padded dimension (unit ((2g + m) * QH + hq) * 64 + l), holding the queries rounded to bf16 and
+// multiplied by 2^-s (exact), so that the accumulators hold final scores and everything behind them (sample,
+// thresholds, candidate lists, selects, masks) is what it is for the 16-bit scans.  A score equals, bit for bit, the
+// score of a bf16 index that holds the decoded rows: the same operands up to the power of two, the same k order.
+//
+// The loops are scan_kernel's and scan_masked_kernel's (ts_scan.hip): persistent waves, the TS_RING-deep ring of
+// non-temporal 1 KiB loads, a sched_barrier per slot.  A slot now feeds two MFMAs per query half.
+#include "ts_scan_dev.h"
+
+__device__ __forceinline__ uint32_t fp8_pair_bf16(uint32_t w, bool hi) {
+  return hi ? __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, true))
+            : __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, 1.0f, false));
+}
+
+// the eight bytes (w0, w1) -> the bf16 A fragment of one k step
+__device__ __forceinline__ u32x4 fp8_frag(uint32_t w0, uint32_t w1) {
+  u32x4 o;
+  o[0] = fp8_pair_bf16(w0, false);
+  o[1] = fp8_pair_bf16(w0, true);
+  o[2] = fp8_pair_bf16(w1, false);
+  o[3] = fp8_pair_bf16(w1, true);
+  return o;
+}
+
+// one ring slot (k group g) against the image: k steps 2g and 2g + 1 of every query half
+template <int QH>
+__device__ __forceinline__ void fp8_slot(f32x16 (&acc)[QH], const u32x4& a, const u32x4* ql, int g) {
+  const u32x4 a0 = fp8_frag(a[0], a[1]);
+#pragma unroll
+  for (int hq = 0; hq < QH; ++hq) {
+    const u32x4 b = ql[(size_t)((2 * g) * QH + hq) * 64];
+    mma_group<TS_BF16>(acc[hq], a0, b);
+  }
+  const u32x4 a1 = fp8_frag(a[2], a[3]);
+#pragma unroll
+  for (int hq = 0; hq < QH; ++hq) {
+    const u32x4 b = ql[(size_t)((2 * g + 1) * QH + hq) * 64];
+    mma_group<TS_BF16>(acc[hq], a1, b);
+  }
+}
+
+// Q image (2 * kg * QH KiB) global(L2) -> LDS, once per workgroup: scan_kernel's copy
+template <int QH>
+__device__ __forceinline__ void fp8_load_image(u32x4* qlds, const uint4* qimg, int kg, int tid) {
+  const u32x4* src = reinterpret_cast<const u32x4*>(qimg);
+  const int units = 2 * kg * QH * 64;
+  for (int i0 = tid; i0 < units; i0 += 8 * SCAN_THREADS) {
+    u32x4 t[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int i = i0 + j * SCAN_THREADS;
+      t[j] = (i < units) ? src[i] : u32x4{0, 0, 0, 0};
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int i = i0 + j * SCAN_THREADS;
+      if (i < units) qlds[i] = t[j];
+    }
+  }
+}
+
+template <int QH, int MODE>
+__global__ __launch_bounds__(SCAN_THREADS) void scan_fp8_kernel(ScanParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  u32x4* qlds = reinterpret_cast<u32x4*>(smem);
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int kg = p.kg;   // 1 KiB units per row block (32 k each)
+
+  const int64_t nwaves = (int64_t)gridDim.x * SCAN_WAVES;
+  int64_t w = (int64_t)blockIdx.x * SCAN_WAVES + wave;
+  const bool active = w < p.nwork;  // (waves without work still join the final flush)
+  const u32x4* base = reinterpret_cast<const u32x4*>(p.corpus) + lane;
+  const size_t blk_units = (size_t)kg * 64;
+  int64_t blk = active ? p.blk0 + w * p.blk_stride : p.blk0;
+  const u32x4* cur = base + (size_t)blk * blk_units;
+  u32x4 ring[TS_RING];
+  if (active) {
+#pragma unroll
+    for (int i = 0; i < TS_RING; ++i) ring[i] = stream_load(cur + (size_t)i * 64);
+  }
+  fp8_load_image<QH>(qlds, p.qimg, kg, tid);
+  StageLds* st = reinterpret_cast<StageLds*>(smem + (size_t)2 * kg * QH * 1024);
+  if constexpr (MODE == SCAN_FILTER) {
+    if (tid == 0) st->cnt = 0;
+  }
+  __syncthreads();
+
+  if (active) {
+    float tau[QH];
+    if constexpr (MODE == SCAN_FILTER) {
+#pragma unroll
+      for (int hq = 0; hq < QH; ++hq) tau[hq] = p.tau[hq * 32 + (lane & 31)];
+    }
+    const u32x4* ql = qlds + lane;
+    while (true) {
+      const int64_t wn = w + nwaves;
+      const bool has_next = wn < p.nwork;
+      const int64_t blkn = has_next ? (p.blk0 + wn * p.blk_stride) : blk;
+      const u32x4* nxt = base + (size_t)blkn * blk_units;
+
+      f32x16 acc[QH];
+#pragma unroll
+      for (int hq = 0; hq < QH; ++hq)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[hq][r] = 0.f;
+
+      // main part: prefetch stays inside the current row block
+      int g0 = 0;
+      for (; g0 < kg - TS_RING; g0 += TS_RING) {
+#pragma unroll
+        for (int i = 0; i < TS_RING; ++i) {
+          fp8_slot<QH>(acc, ring[i], ql, g0 + i);
+          ring[i] = stream_load(cur + (size_t)(g0 + i + TS_RING) * 64);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+      // tail: the ring is refilled from the start of the wave's next row block
+#pragma unroll
+      for (int i = 0; i < TS_RING; ++i) {
+        fp8_slot<QH>(acc, ring[i], ql, g0 + i);
+        ring[i] = stream_load(nxt + (size_t)i * 64);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+
+      if constexpr (MODE == SCAN_DENSE)
+        epilogue_dense<QH>(p, acc, w, blk, lane);
+      else
+        epilogue_filter<QH>(p, st, acc, tau, blk, lane);
+
+      if (!has_next) break;
+      w = wn;
+      blk = blkn;
+      cur = nxt;
+    }
+  }  // active
+  if constexpr (MODE == SCAN_FILTER) flush_stage(p, st, tid);
+}
+
+// scan_masked_kernel (ts_scan.hip) over e4m3 rows: the live-block list and the count are scalar loads, each lane's
+// allow word of the next block is requested just before that block's first ring loads and read in its epilogue
+typedef const uint32_t __attribute__((address_space(4)))* fp8_sgpr_u32p;
+typedef const int32_t __attribute__((address_space(4)))* fp8_sgpr_i32p;
+
+template <int QH>
+__global__ __launch_bounds__(SCAN_THREADS) void scan_fp8_masked_kernel(MaskedScanParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  u32x4* qlds = reinterpret_cast<u32x4*>(smem);
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int kg = p.kg;
+
+  const int64_t nwaves = (int64_t)gridDim.x * SCAN_WAVES;
+  int64_t w = (int64_t)blockIdx.x * SCAN_WAVES + wave;
+  const int64_t nwork = (int64_t)*(fp8_sgpr_u32p)p.nlive;
+  const bool active = w < nwork;  // (waves without work still join the final flush)
+  const u32x4* base = reinterpret_cast<const u32x4*>(p.corpus) + lane;
+  const size_t blk_units = (size_t)kg * 64;
+  int64_t blk = active ? (int64_t)((fp8_sgpr_i32p)p.live)[w] : 0;
+  const u32x4* cur = base + (size_t)blk * blk_units;
+  u32x4 ring[TS_RING];
+  if (active) {
+#pragma unroll
+    for (int i = 0; i < TS_RING; ++i) ring[i] = stream_load(cur + (size_t)i * 64);
+  }
+  fp8_load_image<QH>(qlds, p.qimg, kg, tid);
+  StageLds* st = reinterpret_cast<StageLds*>(smem + (size_t)2 * kg * QH * 1024);
+  if (tid == 0) st->cnt = 0;
+  __syncthreads();
+
+  if (active) {
+    float tau[QH];
+    const uint32_t* mrow[QH];   // the lane's allow-word row
+    int64_t mstep[QH];          // 0 for an unmasked query: it keeps reading word 0
+    uint32_t mor[QH], mw[QH];   // all ones for an unmasked query; the current block's word
+#pragma unroll
+    for (int hq = 0; hq < QH; ++hq) {
+      tau[hq] = p.tau[hq * 32 + (lane & 31)];
+      const int32_t qm = p.qmask[hq * 32 + (lane & 31)];
+      mrow[hq] = p.allow_bits + (qm < 0 ? 0 : (int64_t)qm * p.allow_words);
+      mstep[hq] = qm < 0 ? 0 : 1;
+      mor[hq] = qm < 0 ? ~0u : 0u;
+      mw[hq] = mrow[hq][blk * mstep[hq]] | mor[hq];
+    }
+    const u32x4* ql = qlds + lane;
+    while (true) {
+      const int64_t wn = w + nwaves;
+      const bool has_next = wn < nwork;
+      const int64_t blkn = has_next ? (int64_t)((fp8_sgpr_i32p)p.live)[wn] : blk;
+      const u32x4* nxt = base + (size_t)blkn * blk_units;
+
+      f32x16 acc[QH];
+#pragma unroll
+      for (int hq = 0; hq < QH; ++hq)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[hq][r] = 0.f;
+
+      int g0 = 0;
+      for (; g0 < kg - TS_RING; g0 += TS_RING) {
+#pragma unroll
+        for (int i = 0; i < TS_RING; ++i) {
+          fp8_slot<QH>(acc, ring[i], ql, g0 + i);
+          ring[i] = stream_load(cur + (size_t)(g0 + i + TS_RING) * 64);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+      // tail: the next block's allow words, then the ring is refilled from the start of that block
+      uint32_t mwn[QH];
+#pragma unroll
+      for (int hq = 0; hq < QH; ++hq) mwn[hq] = mrow[hq][blkn * mstep[hq]];
+#pragma unroll
+      for (int i = 0; i < TS_RING; ++i) {
+        fp8_slot<QH>(acc, ring[i], ql, g0 + i);
+        ring[i] = stream_load(nxt + (size_t)i * 64);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+
+      epilogue_filter<QH, StageLds, true>(p, st, acc, tau, blk, lane, mw);
+
+      if (!has_next) break;
+      w = wn;
+      blk = blkn;
+      cur = nxt;
+#pragma unroll
+      for (int hq = 0; hq < QH; ++hq) mw[hq] = mwn[hq] | mor[hq];
+    }
+  }  // active
+  flush_stage(p, st, tid);
+}
+
+size_t ts_scan_fp8_lds_bytes(const TsLayout& L, int qh) {
+  return (size_t)2 * L.kg * qh * 1024 + sizeof(StageLds);
+}
+
+template <int QH, int MODE>
+static int launch_scan_fp8_t(const TsLayout& L, const ScanParams& p, int num_cus, hipStream_t stream) {
+  const size_t lds = (size_t)2 * L.kg * QH * 1024 + (MODE == SCAN_FILTER ? sizeof(StageLds) : 0);
+  auto kern = scan_fp8_kernel<QH, MODE>;
+  static TsDeviceOnce lds_attr;
+  TS_CHECK(ts_allow_max_lds(lds_attr, reinterpret_cast<const void*>(kern)));
+  // as launch_scan_t: the short dense scans take a second workgroup per CU when LDS allows
+  int wg_per_cu = 1;
+  if (MODE == SCAN_DENSE && 2 * lds <= 160 * 1024) wg_per_cu = 2;
+  const int64_t want = (p.nwork + SCAN_WAVES - 1) / SCAN_WAVES;
+  const int64_t cap = (int64_t)num_cus * wg_per_cu;
+  int grid = (int)(want < cap ? want : cap);
+  if (grid < 1) grid = 1;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(SCAN_THREADS), lds, stream, p);
+  TS_HIP(hipGetLastError());
+  return TS_OK;
+}
+
+int ts_launch_scan_fp8(const TsLayout& L, int mode, int qh, const ScanParams& p, int num_cus, hipStream_t stream) {
+  if (p.nwork <= 0) return TS_OK;
+  if (L.dtype != TS_FP8_E4M3 || p.kg != L.kg || (qh != 1 && qh != 2) || ts_scan_fp8_lds_bytes(L, qh) > 160 * 1024) {
+    ts_set_error("e4m3 scan: dimension %d does not fit the LDS-resident query image for %d queries", L.dim, 32 * qh);
+    return TS_ERR_UNSUPPORTED;
+  }
+  if (qh == 1)
+    return mode == SCAN_DENSE ? launch_scan_fp8_t<1, SCAN_DENSE>(L, p, num_cus, stream)
+                              : launch_scan_fp8_t<1, SCAN_FILTER>(L, p, num_cus, stream);
+  return mode == SCAN_DENSE ? launch_scan_fp8_t<2, SCAN_DENSE>(L, p, num_cus, stream)
+                            : launch_scan_fp8_t<2, SCAN_FILTER>(L, p, num_cus, stream);
+}
+
+template <int QH>
+static int launch_scan_fp8_masked_t(const TsLayout& L, const MaskedScanParams& p, int num_cus, hipStream_t stream) {
+  const size_t lds = (size_t)2 * L.kg * QH * 1024 + sizeof(StageLds);
+  auto kern = scan_fp8_masked_kernel<QH>;
+  static TsDeviceOnce lds_attr;
+  TS_CHECK(ts_allow_max_lds(lds_attr, reinterpret_cast<const void*>(kern)));
+  // p.nwork: every row block (the live count is only known on the device; waves past it leave at once)
+  const int64_t want = (p.nwork + SCAN_WAVES - 1) / SCAN_WAVES;
+  int grid = (int)(want < num_cus ? want : num_cus);
+  if (grid < 1) grid = 1;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(SCAN_THREADS), lds, stream, p);
+  TS_HIP(hipGetLastError());
+  return TS_OK;
+}
+
+int ts_launch_scan_masked_fp8(const TsLayout& L, int qh, const MaskedScanParams& p, int num_cus, hipStream_t stream) {
+  if (p.nwork <= 0) return TS_OK;
+  if (L.dtype != TS_FP8_E4M3 || p.kg != L.kg || (qh != 1 && qh != 2) || ts_scan_fp8_lds_bytes(L, qh) > 160 * 1024) {
+    ts_set_error("e4m3 masked scan: dimension %d does not fit the LDS-resident query image for %d queries", L.dim,
+                 32 * qh);
+    return TS_ERR_UNSUPPORTED;
+  }
+  return qh == 1 ? launch_scan_fp8_masked_t<1>(L, p, num_cus, stream)
+                 : launch_scan_fp8_masked_t<2>(L, p, num_cus, stream);
+}
+
+// ------------------------------------------------------------------ query image
+// thread per 16-byte unit: unit (G * qh + hq) * 64 + l = query 32 hq + (l & 31), k = 16 G + 8 (l >> 5) + 0..7 (the
+// bf16 image), each value bf16_rne(q) * 2^-s (exact: a power of two times a bf16 value, far above the subnormals)
+template <typename TIN>
+__global__ void qprep_fp8_kernel(const TIN* q, int nq, int dim, int ng, int qh, float inv_scale, uint4* qimg,
+                                 uint32_t* cand_cnt, uint32_t* status) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < TS_MAX_Q && cand_cnt) cand_cnt[t] = 0;
+  if (t == 0 && status) status[0] = 0;
+  if (t >= ng * qh * 64) return;
+  const int lane = t & 63;
+  const int hq = (t >> 6) % qh;
+  const int G = (t >> 6) / qh;
+  const int qi = hq * 32 + (lane & 31), h = lane >> 5;
+  const TIN* src = q + (int64_t)qi * dim;
+  uint32_t b[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const int k = 16 * G + 8 * h + e;
+    const float x = (qi < nq && k < dim) ? ElemIO<TIN>::ld(src + k) : 0.f;
+    const float r = __builtin_bit_cast(float, (uint32_t)f32_to_storage16(x, TS_BF16) << 16) * inv_scale;
+    b[e] = __builtin_bit_cast(uint32_t, r) >> 16;
+  }
+  u32x4 out;
+#pragma unroll
+  for (int d = 0; d < 4; ++d) out[d] = b[2 * d] | (b[2 * d + 1] << 16);
+  reinterpret_cast<u32x4*>(qimg)[t] = out;
+}
+
+static float fp8_pow2(int e) { return __builtin_bit_cast(float, (uint32_t)(127 + e) << 23); }
+
+int ts_launch_qprep_fp8(const TsLayout& L, const void* q, int q_dtype, int nq, int qh, uint4* qimg, uint32_t* cand_cnt,
+                        uint32_t* status, hipStream_t stream) {
+  const int ng = 2 * L.kg;
+  const int units = ng * qh * 64;
+  const int blocks = (units + 255) / 256;
+  const float inv = fp8_pow2(-L.fp8_scale_log2);
+  switch (q_dtype) {
+    case TS_F32:
+      hipLaunchKernelGGL(qprep_fp8_kernel<float>, dim3(blocks), dim3(256), 0, stream, (const float*)q, nq, L.dim, ng, qh, inv, qimg, cand_cnt, status);
+      break;
+    case TS_F16:
+      hipLaunchKernelGGL(qprep_fp8_kernel<_Float16>, dim3(blocks), dim3(256), 0, stream, (const _Float16*)q, nq, L.dim, ng, qh, inv, qimg, cand_cnt, status);
+      break;
+    case TS_BF16:
+      hipLaunchKernelGGL(qprep_fp8_kernel<__bf16>, dim3(blocks), dim3(256), 0, stream, (const __bf16*)q, nq, L.dim, ng, qh, inv, qimg, cand_cnt, status);
+      break;
+    default:
+      ts_set_error("bad query dtype %d", q_dtype);
+      return TS_ERR_INVALID;
+  }
+  TS_HIP(hipGetLastError());
+  return TS_OK;
+}
+
+// ------------------------------------------------------------------ layout
+// e4m3fn_rne(y) on the bits of y (index.py quantize_rows_e4m3_fixed_reference is the definition)
+__device__ __forceinline__ uint32_t fp8_quantize(float y) {
+  const uint32_t u = __builtin_bit_cast(uint32_t, y);
+  const uint32_t sign = (u >> 24) & 0x80u;
+  const uint32_t a = u & 0x7fffffffu;
+  if (a > 0x7f800000u) return 0x7Fu;                 // NaN
+  const uint32_t e = a >> 23;
+  if (e >= 121u) {                                    // |y| >= 2^-6: an e4m3 normal; 20 mantissa bits dropped
+    const uint32_t r = (a + 0x7FFFFu + ((a >> 20) & 1u)) >> 20;
+    const uint32_t b = r - 960u;                      // exponent bias 127 -> 7
+    return sign | (b > 0x7Eu ? 0x7Eu : b);            // above 448 (Inf too): +-448
+  }
+  if (e < 117u) return sign;                          // |y| < 2^-10: below half of the subnormal step 2^-9
+  // subnormal: round(|y| * 2^9) to nearest even, 0 .. 8 (8 is the byte of 2^-6)
+  const uint32_t m = (a & 0x7fffffu) | 0x800000u;
+  const uint32_t sh = 141u - e;                       // 21 .. 24
+  uint32_t qv = m >> sh;
+  const uint32_t rem = m & ((1u << sh) - 1u), half = 1u << (sh - 1u);
+  qv += (rem > half || (rem == half && (qv & 1u))) ? 1u : 0u;
+  return sign | qv;
+}
+
+__device__ __forceinline__ float fp8_decode(uint32_t b) {
+  const uint32_t sign = (b & 0x80u) << 24, e = (b >> 3) & 15u, m = b & 7u;
+  if ((b & 0x7Fu) == 0x7Fu) return __builtin_bit_cast(float, sign | 0x7fc00000u);
+  if (e == 0u) return __builtin_bit_cast(float, sign | __builtin_bit_cast(uint32_t, (float)m * 0.001953125f));
+  return __builtin_bit_cast(float, sign | ((e + 120u) << 23) | (m << 20));
+}
+
+// One wave per (row block, k group): 64 lanes write one contiguous 1 KiB unit row (relayout_kernel's walk).  With
+// `den` the quantiser takes the f32 quotient v / den, as the other storage types do.
+template <typename TIN>
+__global__ void relayout_fp8_kernel(const TIN* rows, int64_t n, int dim, int64_t row0, int64_t blk_first,
+                                    int64_t nunits_wave, uint4* tiled, int kg, float scale, const float* den, int vec) {
+  const int lane = threadIdx.x & 63;
+  const int64_t wv = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (wv >= nunits_wave) return;
+  const int64_t b = blk_first + wv / kg;
+  const int g = (int)(wv % kg);
+  const int r = lane & 31, h = lane >> 5;
+  const int64_t row = b * TS_ROWS_PER_BLOCK + r;
+  if (row < row0 || row >= row0 + n) return;
+  const TIN* src = rows + (row - row0) * dim;
+  const float d = den ? den[row - row0] : 1.0f;
+  u32x4 out;
+#pragma unroll
+  for (int m = 0; m < 2; ++m) {
+    const int k0 = 32 * g + 16 * m + 8 * h;
+    float v[8];
+    if (vec && k0 < dim) {   // (dim % 8 == 0: the eight values are inside the row)
+      ld8<TIN>(src + k0, v);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] = (k0 + e < dim) ? ElemIO<TIN>::ld(src + k0 + e) : 0.f;
+    }
+    uint32_t w[2] = {0u, 0u};
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      float x = v[e];
+      if (den) x = x / d;
+      w[e >> 2] |= fp8_quantize(x * scale) << (8 * (e & 3));
+    }
+    out[2 * m] = w[0];
+    out[2 * m + 1] = w[1];
+  }
+  reinterpret_cast<u32x4*>(tiled)[(size_t)(b * kg + g) * 64 + lane] = out;
+}
+
+template <typename TIN> constexpr int fp8_rows_dtype = TS_F32;
+template <> constexpr int fp8_rows_dtype<_Float16> = TS_F16;
+template <> constexpr int fp8_rows_dtype<__bf16> = TS_BF16;
+
+template <typename TIN>
+static int relayout_fp8_t(const TsLayout& L, const TIN* rows, int64_t n, int64_t row0, uint4* tiled, bool normalize,
+                          float* den, hipStream_t s) {
+  if (normalize) TS_CHECK(ts_launch_row_den(rows, fp8_rows_dtype<TIN>, n, L.dim, den, s));
+  const int64_t blk_first = row0 / TS_ROWS_PER_BLOCK;
+  const int64_t blk_last = (row0 + n - 1) / TS_ROWS_PER_BLOCK;
+  const int64_t nwave = (blk_last - blk_first + 1) * L.kg;
+  const int64_t blocks = (nwave + 3) / 4;
+  if (blocks > 0x7fffffffLL) {
+    ts_set_error("add: too many rows in one call");
+    return TS_ERR_INVALID;
+  }
+  const int vec = (int)((L.dim % 8) == 0 &&
+                        (reinterpret_cast<uintptr_t>(rows) % (4 * sizeof(TIN) >= 16 ? 32 : 16)) == 0);
+  hipLaunchKernelGGL(relayout_fp8_kernel<TIN>, dim3((unsigned)blocks), dim3(256), 0, s, rows, n, L.dim, row0,
+                     blk_first, nwave, tiled, L.kg, fp8_pow2(L.fp8_scale_log2),
+                     normalize ? den : (const float*)nullptr, vec);
+  TS_HIP(hipGetLastError());
+  return TS_OK;
+}
+
+int ts_launch_relayout_fp8(const TsLayout& L, const void* rows, int in_dtype, int64_t n, int64_t row0, uint4* tiled,
+                           bool normalize, float* den_scratch, hipStream_t stream) {
+  if (n <= 0) return TS_OK;
+  switch (in_dtype) {
+    case TS_F32: return relayout_fp8_t<float>(L, (const float*)rows, n, row0, tiled, normalize, den_scratch, stream);
+    case TS_F16: return relayout_fp8_t<_Float16>(L, (const _Float16*)rows, n, row0, tiled, normalize, den_scratch, stream);
+    case TS_BF16: return relayout_fp8_t<__bf16>(L, (const __bf16*)rows, n, row0, tiled, normalize, den_scratch, stream);
+  }
+  ts_set_error("bad rows dtype %d", in_dtype);
+  return TS_ERR_INVALID;
+}
+
+// thread per (row, 16-byte unit): the decoded values e4m3 * 2^-s (exact in f32)
+__global__ void reconstruct_fp8_kernel(const uint4* tiled, int64_t row0, int64_t n, int dim, int kg, float inv_scale,
+                                       float* out) {
+  const int upr = kg * 2;  // units per row
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n * upr) return;
+  const int64_t row = row0 + t / upr;
+  const int u = (int)(t % upr);
+  const int g = u >> 1, h = u & 1;
+  const int64_t b = row / TS_ROWS_PER_BLOCK;
+  const int lane = h * 32 + (int)(row % TS_ROWS_PER_BLOCK);
+  const u32x4 v = reinterpret_cast<const u32x4*>(tiled)[(size_t)(b * kg + g) * 64 + lane];
+  float* dst = out + (row - row0) * dim;
+#pragma unroll
+  for (int e = 0; e < 16; ++e) {
+    const int k = 32 * g + 16 * (e >> 3) + 8 * h + (e & 7);
+    const uint32_t byte = (v[e >> 2] >> (8 * (e & 3))) & 0xFFu;
+    if (k < dim) dst[k] = fp8_decode(byte) * inv_scale;
+  }
+}
+
+int ts_launch_reconstruct_fp8(const TsLayout& L, const uint4* tiled, int64_t row0, int64_t n, float* out,
+                              hipStream_t stream) {
+  if (n <= 0) return TS_OK;
+  const int64_t total = n * L.kg * 2;
+  const int64_t blocks = (total + 255) / 256;
+  if (blocks > 0x7fffffffLL) {
+    ts_set_error("reconstruct: range too large");
+    return TS_ERR_INVALID;
+  }
+  hipLaunchKernelGGL(reconstruct_fp8_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, tiled, row0, n, L.dim,
+                     L.kg, fp8_pow2(-L.fp8_scale_log2), out);
+  TS_HIP(hipGetLastError());
+  return TS_OK;
+}

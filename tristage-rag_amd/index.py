@@ -24,8 +24,10 @@ from . import _lib
 _NP_DTYPES = {np.dtype(np.float32): _lib.TS_F32, np.dtype(np.float16): _lib.TS_F16}
 _NAME_TO_DTYPE = {"f32": _lib.TS_F32, "fp32": _lib.TS_F32, "float32": _lib.TS_F32,
                   "f16": _lib.TS_F16, "fp16": _lib.TS_F16, "float16": _lib.TS_F16,
-                  "bf16": _lib.TS_BF16, "bfloat16": _lib.TS_BF16}
-_DTYPE_NAME = {_lib.TS_F32: "f32", _lib.TS_F16: "f16", _lib.TS_BF16: "bf16"}
+                  "bf16": _lib.TS_BF16, "bfloat16": _lib.TS_BF16,
+                  "fp8": _lib.TS_FP8_E4M3, "e4m3": _lib.TS_FP8_E4M3, "float8_e4m3fn": _lib.TS_FP8_E4M3}
+_DTYPE_NAME = {_lib.TS_F32: "f32", _lib.TS_F16: "f16", _lib.TS_BF16: "bf16", _lib.TS_FP8_E4M3: "fp8"}
+FP8_INDEX_MAX_D = 2048   # an e4m3 index's query image is a bf16 image: 32 queries of it fit the LDS up to here
 
 
 def _torch():
@@ -114,9 +116,16 @@ class FlatIPIndex:
     MAX_KERNEL_K = 16384  # the select kernels hold 16384 keys in LDS; larger k: _search_large_k
     MAX_ASYNC_QUERIES = 128  # per asynchronous library call (4 passes of >= 32 queries)
 
-    def __init__(self, d: int, dtype: str = "f32", device: int = 0):
+    def __init__(self, d: int, dtype: str = "f32", device: int = 0, fp8_scale_log2: int = 8):
+        """``dtype="fp8"``: one byte per element (e4m3); element x is stored as e4m3(x * 2^fp8_scale_log2)
+        (see :func:`quantize_rows_e4m3_fixed_reference`), the default 8 fits unit-norm rows."""
         if dtype not in _NAME_TO_DTYPE:
             raise ValueError(f"unknown storage dtype {dtype!r}")
+        is_fp8 = _NAME_TO_DTYPE[dtype] == _lib.TS_FP8_E4M3
+        if is_fp8 and not 0 <= int(fp8_scale_log2) <= 15:
+            raise ValueError(f"fp8_scale_log2 must be in 0 .. 15, got {fp8_scale_log2}")
+        if is_fp8 and int(d) > FP8_INDEX_MAX_D:
+            raise NotImplementedError(f"an fp8 index takes at most {FP8_INDEX_MAX_D} dimensions, got {d}")
         self._lib = _lib.load()
         self.d = int(d)
         self.device = int(device)
@@ -125,6 +134,8 @@ class FlatIPIndex:
         _lib.check(self._lib.ts_index_create(self.d, _NAME_TO_DTYPE[dtype],
                                              _lib.TS_METRIC_INNER_PRODUCT, self.device,
                                              ctypes.byref(self._h)))
+        if is_fp8:
+            self.set_fp8_scale_log2(fp8_scale_log2)
         self.is_trained = True  # FAISS attribute; a flat index needs no training
         self._pending = {}      # ticket -> (q, k, D, I) of unfinished async searches
         self._pending_passes = 0
@@ -232,6 +243,19 @@ class FlatIPIndex:
         _lib.check(self._lib.ts_index_compact(self._h, out.ctypes.data_as(ctypes.c_void_p),
                                               ctypes.c_void_p(_stream_ptr(self.device)) or None))
         return out[:n]
+
+    @property
+    def fp8_scale_log2(self) -> Optional[int]:
+        """The scale exponent of an fp8 index (None for another storage dtype)."""
+        s = int(self._lib.ts_index_fp8_scale_log2(self._h))
+        return s if s >= 0 else None
+
+    def set_fp8_scale_log2(self, s: int) -> None:
+        """fp8 storage: the scale exponent, 0 .. 15; only while the index is empty (``ValueError`` otherwise)."""
+        code = self._lib.ts_index_set_fp8_scale_log2(self._h, int(s))
+        if code == _lib.TS_ERR_INVALID:
+            raise ValueError(_lib.last_error())
+        _lib.check(code)
 
     def reset(self) -> None:
         _lib.check(self._lib.ts_index_reset(self._h))
@@ -561,6 +585,8 @@ class FlatIPIndex:
         ``max_results``: the most entries the call may return (default 2^26); exceeding it raises
         :class:`RangeSearchLimitError`, which names the count and the limit, and the index stays usable.
         ``exact_dense=True`` forces the dense path (tests, A/B runs).  Synchronous."""
+        if self.storage_dtype == "fp8":
+            raise NotImplementedError("range_search is not supported on an fp8 index")
         was_tensor = _is_tensor(q) and q.is_cuda
         if _is_tensor(q) and not q.is_cuda:
             q = q.detach().float().numpy()
@@ -999,6 +1025,45 @@ def quantize_rows_fp8_reference(x):
     return q
 
 
+def quantize_rows_e4m3_fixed_reference(x, scale_log2: int = 8) -> np.ndarray:
+    """The stored bytes of an fp8 FlatIPIndex, in numpy integer arithmetic: element x ->
+    e4m3fn_rne(x * 2^scale_log2).  x * 2^s is taken in float32 (exact, or Inf on overflow); rounding is to nearest, ties
+    to the even mantissa, on the float32 bits; e4m3 subnormals (multiples of 2^-9) are kept; magnitudes above 448 and
+    +-Inf saturate to +-448 (0x7E / 0xFE); NaN stores 0x7F; the sign is kept, also of a zero.  There is no per-row
+    scale: stage-1 scores are compared across rows.  x: f32 / f16 / bf16 array or tensor of any shape -> uint8 array."""
+    if not 0 <= int(scale_log2) <= 15:
+        raise ValueError(f"scale_log2 must be in 0 .. 15, got {scale_log2}")
+    if _is_tensor(x):
+        x = x.detach().to("cpu", _torch().float32).numpy()
+    with np.errstate(over="ignore"):
+        y = np.ascontiguousarray(x, dtype=np.float32) * np.float32(2.0 ** int(scale_log2))
+    u = y.view(np.uint32).astype(np.int64)
+    sign = (u >> 24) & 0x80
+    a = u & 0x7FFFFFFF
+    e = a >> 23
+    # normal e4m3 values (|y| >= 2^-6): 20 mantissa bits dropped with round-to-nearest-even; exponent bias 127 -> 7
+    normal = np.minimum(((a + 0x7FFFF + ((a >> 20) & 1)) >> 20) - 960, 0x7E)
+    # subnormal: |y| * 2^9 rounded to nearest even, 0 .. 8 (8 is the byte of 2^-6)
+    m = (a & 0x7FFFFF) | 0x800000
+    sh = np.clip(141 - e, 1, 40)
+    qv = m >> sh
+    rem, half = m & ((np.int64(1) << sh) - 1), np.int64(1) << (sh - 1)
+    sub = qv + ((rem > half) | ((rem == half) & ((qv & 1) == 1)))
+    b = np.where(e >= 121, normal, np.where(e < 117, 0, sub)) | sign
+    return np.where(a > 0x7F800000, 0x7F, b).astype(np.uint8)
+
+
+def decode_rows_e4m3_fixed(b, scale_log2: int = 8) -> np.ndarray:
+    """The values an fp8 FlatIPIndex scores and ``reconstruct_n`` returns: e4m3fn(b) * 2^-scale_log2 as float32 (exact;
+    0x7F / 0xFF decode to NaN).  b: uint8 array."""
+    b = np.asarray(b, dtype=np.uint8).astype(np.int64)
+    e, m = (b >> 3) & 15, b & 7
+    mag = np.where(e == 0, m * 2.0 ** -9, (8 + m) * 2.0 ** (e.astype(np.float64) - 10))
+    mag = np.where((b & 0x7F) == 0x7F, np.nan, mag)
+    v = np.where(b & 0x80, -mag, mag) * 2.0 ** -int(scale_log2)
+    return v.astype(np.float32)
+
+
 def quantize_rows_fp8(x):
     """Rows -> the e4m3 token-store format (see quantize_rows_fp8_reference, which it equals bit for bit): the
     ts_quantize_rows_fp8 kernel for a GPU tensor, the torch reference for a CPU one.  x [rows, H] f32 / f16 / bf16."""
@@ -1306,6 +1371,8 @@ class IVFFlatIndex:
     MAX_KERNEL_K = 16384
 
     def __init__(self, d: int, nlist: int, dtype: str = "f16", device: int = 0, nprobe: int = 10):
+        if _NAME_TO_DTYPE.get(dtype) == _lib.TS_FP8_E4M3:
+            raise NotImplementedError("IVFFlatIndex has no fp8 storage (fp8 is a flat-index storage dtype)")
         if dtype not in _NAME_TO_DTYPE or _NAME_TO_DTYPE[dtype] == _lib.TS_F32:
             raise ValueError(f"IVF storage dtype must be f16 or bf16, got {dtype!r}")
         self._lib = _lib.load()

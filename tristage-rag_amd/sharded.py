@@ -53,6 +53,8 @@ class ShardedFlatIPIndex:
         self.d = int(d)
         self.n_total = int(n_total)
         self.lo, self.hi = shard_bounds(self.n_total, self.world_size, self.rank)
+        if str(dtype) in ("fp8", "e4m3", "float8_e4m3fn") or getattr(local_index, "storage_dtype", None) == "fp8":
+            raise NotImplementedError("ShardedFlatIPIndex does not take an fp8 index (fp8 storage is single-GPU, flat only)")
         if local_index is None:
             from .index import FlatIPIndex
             local_index = FlatIPIndex(d, dtype=dtype, device=0 if device is None else device)

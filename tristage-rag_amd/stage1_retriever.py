@@ -62,7 +62,7 @@ class Stage1Config:
     # "auto": the reference's rule (:256-283) — IVF when the first add_documents brings more than 1000 documents
     index_type: str = "flat"
     # additive knobs (not in the reference)
-    index_dtype: str = "f32"   # storage dtype of the corpus matrix: f32 | f16 | bf16
+    index_dtype: str = "f32"   # storage dtype of the corpus matrix: f32 | f16 | bf16 | fp8 (e4m3, flat index only)
     gpu_index_device: int = 0
     bm25_on_gpu: Optional[bool] = None  # BM25 postings in HBM + HIP scoring kernels; None = whenever
                                         # the HIP index is in use (a GPU is present)
@@ -481,6 +481,9 @@ class Stage1Retriever:
             from .index import IVFFlatIndex
             # (the IVF index stores f16 / bf16 rows; an f32 index_dtype stores f16)
             dt = self.config.index_dtype if self.config.index_dtype in ("f16", "bf16") else "f16"
+            if dt != self.config.index_dtype and not getattr(self, "_ivf_dtype_logged", False):
+                self._ivf_dtype_logged = True
+                self.logger.info(f"IVF index: index_dtype={self.config.index_dtype!r} is stored as f16")
             idx = IVFFlatIndex(d, int(self.config.nlist), dtype=dt, device=self.config.gpu_index_device,
                                nprobe=int(self.config.nprobe))
         else:
@@ -1102,6 +1105,8 @@ class Stage1Retriever:
                     "ntotal": 0, "dim": self.embedding_dim, "matrix": None,
                     "index_type": getattr(self, "index_type_used", "flat"), "centroids": None}
         if self.faiss_index is not None:
+            # the stored rows, decoded to float32.  An fp8 index needs no format of its own: its decoded rows are e4m3
+            # values times 2^-s, and quantising those again at load gives back the same bytes.
             mat = self.faiss_index.reconstruct_n(0, self.faiss_index.ntotal)
             np.save(base + ".matrix.npy", mat)
             manifest.update(ntotal=int(mat.shape[0]), dim=int(mat.shape[1]),
