@@ -129,7 +129,7 @@ def test_filter_scans_are_exact(torch_mod, dtype, d, B, mode, cls):
 
 @pytest.mark.parametrize("cls", ["ints", "neg"])
 def test_masked_scan_is_exact(torch_mod, cls):
-    """scan_masked_kernel: two random half masks and one unfiltered query in the same pass."""
+    """The masked scan (scan_kernel over WalkLive): two random half masks and one unfiltered query in the same pass."""
     n, d, B = ex.N_FILTER, 768, 64
     corpus, queries = _case(cls, n, d, B)
     rng = np.random.default_rng(11)

@@ -147,8 +147,8 @@ def test_fp8_scan_kernels_use_no_scratch():
         m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
         if m and name:
             found[name] = int(m.group(1))
-    scans = {k: v for k, v in found.items() if "scan_fp8_kernel" in k}
-    masked = {k: v for k, v in found.items() if "scan_fp8_masked_kernel" in k}
+    scans = {k: v for k, v in found.items() if "scan_kernel" in k and "OpFp8" in k and "WalkStrided" in k}
+    masked = {k: v for k, v in found.items() if "scan_kernel" in k and "OpFp8" in k and "WalkLive" in k}
     assert len(scans) == 4 and len(masked) == 2, sorted(found)      # QH {1, 2} x {dense, filter}; QH {1, 2}
     others = {k: v for k, v in found.items() if any(t in k for t in ("qprep_fp8", "relayout_fp8", "reconstruct_fp8"))}
     assert len(others) == 7, sorted(found)

@@ -1,5 +1,5 @@
 """Adds the rocprofv3 FETCH_SIZE of the masked scan to tools/filter_probe.py's JSON: per row, the bytes one launch
-of scan_masked_kernel read (2 * FETCH_SIZE * 1024: gfx950 counts 64 B per 128-B request of a wide streaming read,
+of the masked scan (scan_kernel<QH, 1, Op16<DT>, WalkLive>) read (2 * FETCH_SIZE * 1024: gfx950 counts 64 B per 128-B request of a wide streaming read,
 as in tools/summarize_profile.py) against the bytes of the live row blocks.
 
     python tools/filter_pmc_summary.py PROBE_JSON PMC_DIR_OF_ROW:ROW [...] --out OUT_JSON
@@ -12,12 +12,12 @@ import os
 
 
 def scan_fetch_bytes(pmc_dir):
-    """Median over the launches of scan_masked_kernel of 2 * FETCH_SIZE * 1024, and the launch count."""
+    """Median over the launches of the masked scan of 2 * FETCH_SIZE * 1024, and the launch count."""
     vals = {}
     for f in glob.glob(os.path.join(pmc_dir, "**", "*counter_collection.csv"), recursive=True):
         with open(f) as fh:
             for r in csv.DictReader(fh):
-                if r["Counter_Name"] != "FETCH_SIZE" or "scan_masked_kernel" not in r["Kernel_Name"]:
+                if r["Counter_Name"] != "FETCH_SIZE" or not ("scan_kernel" in r["Kernel_Name"] and "Op16" in r["Kernel_Name"] and "WalkLive" in r["Kernel_Name"]):
                     continue
                 key = (f, r.get("Dispatch_Id") or r.get("Correlation_Id"))
                 vals[key] = vals.get(key, 0.0) + float(r["Counter_Value"])

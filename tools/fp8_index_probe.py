@@ -80,7 +80,8 @@ def time_alternating(torch, idxs, q, k, rounds, async_batches=8):
 
 def merge(prof_dir, res):
     """Kernel statistics and FETCH_SIZE of the scan kernels from the two rocprofv3 runs."""
-    scans = ("scan_kernel", "scan_fp8_kernel")
+    # the dense / filter scans of the 16-bit and the e4m3 index: scan_kernel<QH, MODE, Op16<DT> | OpFp8, WalkStrided>
+    scans = ("Op16<0>, WalkStrided>", "Op16<1>, WalkStrided>", "Op16<2>, WalkStrided>", "OpFp8, WalkStrided>")
     kt = {}
     for path in glob.glob(os.path.join(prof_dir, "kt", "**", "*kernel_stats.csv"), recursive=True):
         for row in csv.DictReader(open(path)):

@@ -7,6 +7,9 @@
 # template per family (scan_{multi,wide}_kernel<DT, G> and scan_{multi,wide}_tomb_kernel<DT, G> became
 # scan_{multi,wide}_kernel<DT, G, TOMB>, whose parameter type is spelled in terms of TOMB):
 #   tools/kernel_disasm_diff.sh HEAD~ 's/_Z[0-9]+scan_(multi|wide)_(tomb_)?kernel(ILi[0-9]+ELi[0-9]+)EEv[0-9]+[A-Za-z]+Params/\1 \3 Lb0\2/; s/Lb0tomb_/Lb1/; s/multi (.*) (Lb[01])/_Z17scan_multi_kernel\1E\2EEvNSt11conditionalIXT1_E15MultiTombParams15MultiScanParamsE4typeE/; s/wide (.*) (Lb[01])/_Z16scan_wide_kernel\1E\2EEvNSt11conditionalIXT1_E14WideTombParams14WideScanParamsE4typeE/'
+# For the commit that made four per-pass scans one template (scan_kernel<DT, QH, MODE>, scan_masked_kernel<DT, QH>,
+# scan_fp8_kernel<QH, MODE> and scan_fp8_masked_kernel<QH> became scan_kernel<QH, MODE, OP, WALK>):
+#   tools/kernel_disasm_diff.sh HEAD~ 's/_Z11scan_kernelILi([0-9])ELi([0-9])ELi([0-9])EEv10ScanParams/_Z11scan_kernelILi\2ELi\3E4Op16ILi\1EE11WalkStridedEvNT2_6ParamsE/; s/_Z18scan_masked_kernelILi([0-9])ELi([0-9])EEv16MaskedScanParams/_Z11scan_kernelILi\2ELi1E4Op16ILi\1EE8WalkLiveEvNT2_6ParamsE/; s/_Z15scan_fp8_kernelILi([0-9])ELi([0-9])EEv10ScanParams/_Z11scan_kernelILi\1ELi\2E5OpFp811WalkStridedEvNT2_6ParamsE/; s/_Z22scan_fp8_masked_kernelILi([0-9])EEv16MaskedScanParams/_Z11scan_kernelILi\1ELi1E5OpFp88WalkLiveEvNT2_6ParamsE/'
 # (a kernel's file holds its instructions and not its name, which is the file's: a renamed kernel can compare equal)
 set -e
 REV=${1:-HEAD}

@@ -14,7 +14,7 @@ python3 - $OUT <<'PY'
 import csv, glob, sys, collections, json
 out = sys.argv[1]
 res = {}
-for name, pat in (("scan", "scan_kernel<1, 2, 1>"), ("maxsim", "maxsim16_kernel")):
+for name, pat in (("scan", "scan_kernel<2, 1, Op16<1>, WalkStrided>"), ("maxsim", "maxsim16_kernel")):
     fs = glob.glob(out + f"/{name}/*/*_counter_collection.csv")
     if not fs:
         continue

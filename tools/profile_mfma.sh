@@ -13,7 +13,7 @@ out = sys.argv[1]
 fs = glob.glob(out + "/pmc/*/*_counter_collection.csv")
 agg = collections.defaultdict(list)
 for r in csv.DictReader(open(fs[0])):
-    if "scan_kernel<1, 2, 1>" in r["Kernel_Name"]:
+    if "scan_kernel<2, 1, Op16<1>, WalkStrided>" in r["Kernel_Name"]:
         agg[r["Counter_Name"]].append(float(r["Counter_Value"]))
 res = {k: sum(v) / len(v) for k, v in agg.items()}
 res["launches"] = len(next(iter(agg.values()))) if agg else 0

@@ -31,11 +31,11 @@ for name in ("pmc_fetch", "pmc_write"):
         agg[(r["Kernel_Name"], r["Counter_Name"], r["VGPR_Count"], r["LDS_Block_Size"],
              r["Workgroup_Size"], r["Grid_Size"])].append(float(r["Counter_Value"]))
     for (k, c, vg, lds, wg, grid), v in agg.items():
-        if "scan_kernel" in k or "select_kernel" in k or "tau_kernel" in k or "qprep" in k or "relayout" in k:
+        if ("scan_kernel" in k and "Op16" in k and "WalkStrided" in k) or "select_kernel" in k or "tau_kernel" in k or "qprep" in k or "relayout" in k:
             avg = sum(v) / len(v)
             rows.append({"kernel": k[:80], "counter": c, "dispatches": len(v), "avg_value_KB": round(avg, 1),
                          "vgpr": vg, "lds_bytes": lds, "workgroup": wg, "grid_threads": grid})
-            if "scan_kernel<1, 2, 1>" in k or "scan_kernel<2, 2, 1>" in k:
+            if "scan_kernel<2, 1, Op16<1>, WalkStrided>" in k or "scan_kernel<2, 1, Op16<2>, WalkStrided>" in k:
                 traffic[c] = avg
 with open(os.path.join(out, f"{tag}_pmc_summary.csv"), "w", newline="") as f:
     w = csv.DictWriter(f, fieldnames=list(rows[0].keys()))

@@ -2,7 +2,8 @@
 """Condense the rocprofv3 output of tools/sessions/r02_final_a.sh into the small files kept under profiles/."""
 import collections, csv, glob, json, os, sys
 src = sys.argv[1]
-OURS = ("scan_kernel", "fused_kernel", "select_kernel", "tau_kernel", "qprep", "relayout", "head_start", "maxsim")
+# (the dense / filter scans of 16-bit and f32 storage: scan_kernel<QH, MODE, Op16<DT>, WalkStrided>)
+OURS = ("Op16<0>, WalkStrided>", "Op16<1>, WalkStrided>", "Op16<2>, WalkStrided>", "fused_kernel", "select_kernel", "tau_kernel", "qprep", "relayout", "head_start", "maxsim")
 
 def kernel_stats(d, out):
     fs = glob.glob(os.path.join(src, d, "*", "*_kernel_stats.csv"))
@@ -53,6 +54,6 @@ kernel_stats("trace", "r02_kernel_stats.csv")
 kernel_stats("trace_1p25", "r02_kernel_stats_1p25M_one_launch.csv")
 rows = pmc("pmc_fetch", "pmc_write", "r02_pmc_summary.csv") or []
 rows2 = pmc("pmc_fetch_1p25", "pmc_write_1p25", "r02_pmc_summary_1p25M_one_launch.csv") or []
-out = {"10000000x768xf16": traffic_of(rows, "scan_kernel<1, 2, 1>"), "1250000x768xf16_one_launch": traffic_of(rows2, "fused_kernel")}
+out = {"10000000x768xf16": traffic_of(rows, "scan_kernel<2, 1, Op16<1>, WalkStrided>"), "1250000x768xf16_one_launch": traffic_of(rows2, "fused_kernel")}
 json.dump(out, open(os.path.join(src, "r02_traffic.json"), "w"), indent=1)
 print(json.dumps(out, indent=1))

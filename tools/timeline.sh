@@ -7,10 +7,10 @@ python3 - <<PY
 import csv,glob
 f=glob.glob("$OUT/t/*/*_kernel_trace.csv")[0]
 rows=[r for r in csv.DictReader(open(f))]
-ks=[(int(r["Start_Timestamp"]),int(r["End_Timestamp"]),r["Kernel_Name"][:40]) for r in rows]
+ks=[(int(r["Start_Timestamp"]),int(r["End_Timestamp"]),r["Kernel_Name"]) for r in rows]
 ks.sort()
 import os
-pat=os.environ.get("TL_KERNEL","scan_kernel<1, 2, 1>")
+pat=os.environ.get("TL_KERNEL","scan_kernel<2, 1, Op16<1>, WalkStrided>")
 scan=[k for k in ks if pat in k[2]]
 last=scan[-30:]
 t0=last[0][0]
@@ -24,5 +24,5 @@ print("kernels between two scans:")
 b=last[13]
 for k in ks:
     if k[0]>=a[0]-1000 and k[0]<=b[1]:
-        print("  start %8.1f dur %7.1f  %s"%((k[0]-a[0])/1e3,(k[1]-k[0])/1e3,k[2]))
+        print("  start %8.1f dur %7.1f  %s"%((k[0]-a[0])/1e3,(k[1]-k[0])/1e3,k[2][:40]))
 PY

@@ -145,8 +145,8 @@ struct ScanParams {
 
 enum { SCAN_DENSE = 0, SCAN_FILTER = 1 };
 
-// The masked filter scan of filtered searches (scan_masked_kernel, a kernel of its own, so that ScanParams
-// and the kernels that take it stay as they are): work item w is row block live[w], w < *nlive (nwork is
+// The masked filter scan of filtered searches (scan_kernel over WalkLive, ts_scan_dev.h; parameters of its own, so
+// that ScanParams stays as it is): work item w is row block live[w], w < *nlive (nwork is
 // then only the grid's upper bound), and a survivor of query q also needs bit (row % 32) of word
 // allow_bits[qmask[q] * allow_words + row / 32]; qmask[q] < 0 allows every row.
 struct MaskedScanParams : ScanParams {

@@ -24,259 +24,6 @@
 #include "ts_linear_dev.h"   // fs_barrier: the wide scan's window barrier
 #include <stdlib.h>
 
-// One persistent wave streams row blocks gw, gw+W, gw+2W, ... (W = waves in
-// the grid).  No barrier after the prologue.
-template <int DT, int QH, int MODE>
-__global__ __launch_bounds__(SCAN_THREADS) void scan_kernel(ScanParams p) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  u32x4* qlds = reinterpret_cast<u32x4*>(smem);
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-  const int kg = p.kg;
-
-  // ---- the first corpus loads go out before anything else, so the HBM round trip
-  // overlaps the Q-image copy below
-  const int64_t nwaves = (int64_t)gridDim.x * SCAN_WAVES;
-  int64_t w = (int64_t)blockIdx.x * SCAN_WAVES + wave;
-  const bool active = w < p.nwork;  // (waves without work still join the final flush)
-  const u32x4* base = reinterpret_cast<const u32x4*>(p.corpus) + lane;
-  const size_t blk_units = (size_t)kg * 64;
-  int64_t blk = active ? p.blk0 + w * p.blk_stride : p.blk0;
-  const u32x4* cur = base + (size_t)blk * blk_units;
-  u32x4 ring[TS_RING];
-  if (active) {
-#pragma unroll
-    for (int i = 0; i < TS_RING; ++i) ring[i] = stream_load(cur + (size_t)i * 64);
-  }
-
-  // ---- prologue: Q image global(L2) -> LDS, once per workgroup
-  {
-    const u32x4* src = reinterpret_cast<const u32x4*>(p.qimg);
-    const int units = kg * QH * 64;
-    // 8 independent loads in flight per thread (a one-load-at-a-time copy of the
-    // 96 KiB image costs ~18 us of serial L2 latency per workgroup)
-    for (int i0 = tid; i0 < units; i0 += 8 * SCAN_THREADS) {
-      u32x4 t[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int i = i0 + j * SCAN_THREADS;
-        t[j] = (i < units) ? src[i] : u32x4{0, 0, 0, 0};
-      }
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int i = i0 + j * SCAN_THREADS;
-        if (i < units) qlds[i] = t[j];
-      }
-    }
-  }
-  StageLds* st = reinterpret_cast<StageLds*>(smem + (size_t)kg * QH * 1024);
-  if constexpr (MODE == SCAN_FILTER) {
-    if (tid == 0) st->cnt = 0;
-  }
-  __syncthreads();
-
-  if (active) {
-
-  float tau[QH];
-  if constexpr (MODE == SCAN_FILTER) {
-#pragma unroll
-    for (int hq = 0; hq < QH; ++hq) tau[hq] = p.tau[hq * 32 + (lane & 31)];
-  }
-
-  const u32x4* ql = qlds + lane;
-
-  while (true) {
-    const int64_t wn = w + nwaves;
-    const bool has_next = wn < p.nwork;
-    const int64_t blkn = has_next ? (p.blk0 + wn * p.blk_stride) : blk;
-    const u32x4* nxt = base + (size_t)blkn * blk_units;
-
-    f32x16 acc[QH];
-#pragma unroll
-    for (int hq = 0; hq < QH; ++hq)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[hq][r] = 0.f;
-
-    // main part: prefetch stays inside the current row block
-    int g0 = 0;
-    for (; g0 < kg - TS_RING; g0 += TS_RING) {
-#pragma unroll
-      for (int i = 0; i < TS_RING; ++i) {
-#pragma unroll
-        for (int hq = 0; hq < QH; ++hq) {
-#if defined(TS_TUNING) && defined(DBG_NO_LDS)  // ablation builds only
-          const u32x4 b = ring[(i + 1) % TS_RING];
-#else
-          const u32x4 b = ql[(size_t)((g0 + i) * QH + hq) * 64];
-#endif
-          mma_group<DT>(acc[hq], ring[i], b);
-        }
-        // refill the slot just consumed; the barrier keeps the compiler from
-        // clustering the ring's loads (which would drain vmcnt to 0 mid-loop)
-        ring[i] = stream_load(cur + (size_t)(g0 + i + TS_RING) * 64);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    // tail: the ring is refilled from the start of the wave's next row block
-#pragma unroll
-    for (int i = 0; i < TS_RING; ++i) {
-#pragma unroll
-      for (int hq = 0; hq < QH; ++hq) {
-#if defined(TS_TUNING) && defined(DBG_NO_LDS)  // ablation builds only
-        const u32x4 b = ring[(i + 1) % TS_RING];
-#else
-        const u32x4 b = ql[(size_t)((g0 + i) * QH + hq) * 64];
-#endif
-        mma_group<DT>(acc[hq], ring[i], b);
-      }
-      ring[i] = stream_load(nxt + (size_t)i * 64);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-
-    if constexpr (MODE == SCAN_DENSE)
-      epilogue_dense<QH>(p, acc, w, blk, lane);
-    else
-      epilogue_filter<QH>(p, st, acc, tau, blk, lane);
-
-    if (!has_next) break;
-    w = wn;
-    blk = blkn;
-    cur = nxt;
-  }
-  }  // active
-  if constexpr (MODE == SCAN_FILTER) flush_stage(p, st, tid);
-}
-
-// Masked filter mode (filtered searches): scan_kernel's SCAN_FILTER loop, walking the live-block list
-// instead of blk0 + w * blk_stride.  Work item w is row block p.live[w], w < *p.nlive.  Both are read
-// with scalar loads (constant address space, wave-uniform index): they count against lgkmcnt, not
-// vmcnt, so fetching the next block's index never waits for the corpus ring.  Each lane's allow word
-// of the NEXT block is requested just before that block's first ring loads, unpredicated (an unmasked
-// query reads word 0 of mask 0 and ORs in all ones), and is complete by the time the block's epilogue
-// reads it: vmcnt retires in order, and the ring loads issued after it have been consumed by then.
-// (A kernel of its own rather than a third MODE of scan_kernel, so that ScanParams and the code of every
-// existing instantiation stay exactly as they were.)
-typedef const uint32_t __attribute__((address_space(4)))* ts_sgpr_u32p;
-typedef const int32_t __attribute__((address_space(4)))* ts_sgpr_i32p;
-
-template <int DT, int QH>
-__global__ __launch_bounds__(SCAN_THREADS) void scan_masked_kernel(MaskedScanParams p) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  u32x4* qlds = reinterpret_cast<u32x4*>(smem);
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int kg = p.kg;
-
-  const int64_t nwaves = (int64_t)gridDim.x * SCAN_WAVES;
-  int64_t w = (int64_t)blockIdx.x * SCAN_WAVES + wave;
-  const int64_t nwork = (int64_t)*(ts_sgpr_u32p)p.nlive;
-  const bool active = w < nwork;  // (waves without work still join the final flush)
-  const u32x4* base = reinterpret_cast<const u32x4*>(p.corpus) + lane;
-  const size_t blk_units = (size_t)kg * 64;
-  int64_t blk = active ? (int64_t)((ts_sgpr_i32p)p.live)[w] : 0;
-  const u32x4* cur = base + (size_t)blk * blk_units;
-  u32x4 ring[TS_RING];
-  if (active) {
-#pragma unroll
-    for (int i = 0; i < TS_RING; ++i) ring[i] = stream_load(cur + (size_t)i * 64);
-  }
-
-  // ---- prologue: Q image global(L2) -> LDS, once per workgroup
-  {
-    const u32x4* src = reinterpret_cast<const u32x4*>(p.qimg);
-    const int units = kg * QH * 64;
-    for (int i0 = tid; i0 < units; i0 += 8 * SCAN_THREADS) {
-      u32x4 t[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int i = i0 + j * SCAN_THREADS;
-        t[j] = (i < units) ? src[i] : u32x4{0, 0, 0, 0};
-      }
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int i = i0 + j * SCAN_THREADS;
-        if (i < units) qlds[i] = t[j];
-      }
-    }
-  }
-  StageLds* st = reinterpret_cast<StageLds*>(smem + (size_t)kg * QH * 1024);
-  if (tid == 0) st->cnt = 0;
-  __syncthreads();
-
-  if (active) {
-
-  float tau[QH];
-  const uint32_t* mrow[QH];   // the lane's allow-word row
-  int64_t mstep[QH];          // 0 for an unmasked query: it keeps reading word 0
-  uint32_t mor[QH], mw[QH];   // all ones for an unmasked query; the current block's word
-#pragma unroll
-  for (int hq = 0; hq < QH; ++hq) {
-    tau[hq] = p.tau[hq * 32 + (lane & 31)];
-    const int32_t qm = p.qmask[hq * 32 + (lane & 31)];
-    mrow[hq] = p.allow_bits + (qm < 0 ? 0 : (int64_t)qm * p.allow_words);
-    mstep[hq] = qm < 0 ? 0 : 1;
-    mor[hq] = qm < 0 ? ~0u : 0u;
-    mw[hq] = mrow[hq][blk * mstep[hq]] | mor[hq];
-  }
-
-  const u32x4* ql = qlds + lane;
-
-  while (true) {
-    const int64_t wn = w + nwaves;
-    const bool has_next = wn < nwork;
-    const int64_t blkn = has_next ? (int64_t)((ts_sgpr_i32p)p.live)[wn] : blk;
-    const u32x4* nxt = base + (size_t)blkn * blk_units;
-
-    f32x16 acc[QH];
-#pragma unroll
-    for (int hq = 0; hq < QH; ++hq)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[hq][r] = 0.f;
-
-    // main part: prefetch stays inside the current row block
-    int g0 = 0;
-    for (; g0 < kg - TS_RING; g0 += TS_RING) {
-#pragma unroll
-      for (int i = 0; i < TS_RING; ++i) {
-#pragma unroll
-        for (int hq = 0; hq < QH; ++hq) {
-          const u32x4 b = ql[(size_t)((g0 + i) * QH + hq) * 64];
-          mma_group<DT>(acc[hq], ring[i], b);
-        }
-        ring[i] = stream_load(cur + (size_t)(g0 + i + TS_RING) * 64);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-    // tail: the next block's allow words, then the ring is refilled from the start of that block
-    uint32_t mwn[QH];
-#pragma unroll
-    for (int hq = 0; hq < QH; ++hq) mwn[hq] = mrow[hq][blkn * mstep[hq]];
-#pragma unroll
-    for (int i = 0; i < TS_RING; ++i) {
-#pragma unroll
-      for (int hq = 0; hq < QH; ++hq) {
-        const u32x4 b = ql[(size_t)((g0 + i) * QH + hq) * 64];
-        mma_group<DT>(acc[hq], ring[i], b);
-      }
-      ring[i] = stream_load(nxt + (size_t)i * 64);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-
-    epilogue_filter<QH, StageLds, true>(p, st, acc, tau, blk, lane, mw);
-
-    if (!has_next) break;
-    w = wn;
-    blk = blkn;
-    cur = nxt;
-#pragma unroll
-    for (int hq = 0; hq < QH; ++hq) mw[hq] = mwn[hq] | mor[hq];
-  }
-  }  // active
-  flush_stage(p, st, tid);
-}
-
 // Multi-group filter mode (coalesced passes, TS_FLAG_COALESCE): scan_kernel's SCAN_FILTER loop for G 32-query
 // groups that may belong to different batches (MultiScanParams, ts_common.h).  The prologue gathers each group's
 // columns from its batch's Q image into one G-group image laid out like scan_kernel's (unit (kg*G + g)*64 + lane);
@@ -1134,40 +881,29 @@ size_t ts_scan_lds_bytes(const TsLayout& L, int qh) {
   return (size_t)L.kg * qh * 1024 + sizeof(StageLds);
 }
 
+#if defined(TS_TUNING) && defined(DBG_NO_LDS)
+template <int DT> using OpDense = OpNoLds<DT>;
+#else
+template <int DT> using OpDense = Op16<DT>;
+#endif
+
 template <int DT, int QH, int MODE>
 static int launch_scan_t(const TsLayout& L, const ScanParams& p, int num_cus,
                          hipStream_t stream) {
   const size_t lds = (size_t)L.kg * QH * 1024 + (MODE == SCAN_FILTER ? sizeof(StageLds) : 0);
-  auto kern = scan_kernel<DT, QH, MODE>;
-  static TsDeviceOnce lds_attr;  // per instantiation, per device (ts_common.h)
-  TS_CHECK(ts_allow_max_lds(lds_attr, reinterpret_cast<const void*>(kern)));
   // The fused scan is HBM-bound with one 8-wave workgroup per CU (more waves measured
   // slower: 16 waves/CU -1.5 %); the short dense scans (sample, small corpora) are
   // latency-bound and take a second workgroup per CU when LDS allows.
-  int wg_per_cu = 1;
-  if (MODE == SCAN_DENSE && 2 * lds <= 160 * 1024) wg_per_cu = 2;
-  int64_t want = (p.nwork + SCAN_WAVES - 1) / SCAN_WAVES;
-  int64_t cap = (int64_t)num_cus * wg_per_cu;
-  int grid = (int)(want < cap ? want : cap);
-  if (grid < 1) grid = 1;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(SCAN_THREADS), lds, stream, p);
-  TS_HIP(hipGetLastError());
-  return TS_OK;
+  const int wg_per_cu = (MODE == SCAN_DENSE && 2 * lds <= 160 * 1024) ? 2 : 1;
+  return launch_scan_ring<QH, MODE, OpDense<DT>, WalkStrided>(
+      p, lds, ts_scan_grid(p.nwork, (int64_t)num_cus * wg_per_cu), stream);
 }
 
+// p.nwork: every row block (the live count is only known on the device; waves past it leave at once)
 template <int DT, int QH>
 static int launch_scan_masked_t(const TsLayout& L, const MaskedScanParams& p, int num_cus, hipStream_t stream) {
-  const size_t lds = (size_t)L.kg * QH * 1024 + sizeof(StageLds);
-  auto kern = scan_masked_kernel<DT, QH>;
-  static TsDeviceOnce lds_attr;
-  TS_CHECK(ts_allow_max_lds(lds_attr, reinterpret_cast<const void*>(kern)));
-  // p.nwork: every row block (the live count is only known on the device; waves past it leave at once)
-  int64_t want = (p.nwork + SCAN_WAVES - 1) / SCAN_WAVES;
-  int grid = (int)(want < num_cus ? want : num_cus);
-  if (grid < 1) grid = 1;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(SCAN_THREADS), lds, stream, p);
-  TS_HIP(hipGetLastError());
-  return TS_OK;
+  return launch_scan_ring<QH, SCAN_FILTER, Op16<DT>, WalkLive>(p, (size_t)L.kg * QH * 1024 + sizeof(StageLds),
+                                                              ts_scan_grid(p.nwork, num_cus), stream);
 }
 
 int ts_launch_scan_masked(const TsLayout& L, int qh, const MaskedScanParams& p, int num_cus, hipStream_t stream) {

@@ -111,7 +111,7 @@ struct StageLdsT {
 };
 typedef StageLdsT<STAGE_CAP> StageLds;
 
-// MASKED (scan_masked_kernel, filtered searches): on the rare path a survivor of query hq*32 + (lane & 31)
+// MASKED (scan_kernel over a masked WALK, filtered searches): on the rare path a survivor of query hq*32 + (lane & 31)
 // also needs its bit in mw[hq], that query's allow word of this row block (bit i = row 32*blk + i).  The
 // common path is the same ballot: the mask costs nothing there.
 template <int QH, class SL, bool MASKED = false>
@@ -185,6 +185,249 @@ __device__ __forceinline__ void flush_stage(const ScanParams& p, SL* st, int tid
   }
 }
 
+// ------------------------------------------------------------------ the ring scan
+// Every per-pass stage-1 scan is one instantiation of scan_kernel<QH, MODE, OP, WALK> below: persistent waves, a
+// TS_RING-deep register ring of non-temporal 1 KiB loads that stays full across row-block boundaries, the query image
+// resident in LDS, a sched_barrier per step.  OP says how ring slots meet the image, WALK which row block a work
+// item is; a masked WALK also keeps each lane's allow word of the current row block.
+//
+// OP:
+//   Stage                    the survivor staging type
+//   image_kib<QH>(kg)        1 KiB units of the query image
+//   step<QH>(acc, ring, i, ql, g)   ring slot i (k group g of the row block) against the image
+// WALK:
+//   Params, kMasked
+//   wave(tid)                the wave in the workgroup (masked walks: through readfirstlane, their loads are scalar)
+//   nwork(p)                 work items of the launch
+//   block(p, w), idle(p)     a work item's row block; the block whose address an idle wave forms and never loads
+//   mask_init / mask_fetch / mask_advance (kMasked): the allow words of the first block; the request for the next
+//                            block's, just before the tail's loads; next -> current, after the epilogue.  The state,
+//                            per query half hq, is arrays of the kernel body:
+//                              mrow[hq]   the lane's row of allow words
+//                              mstep[hq]  words per row block in it (0 for an unmasked query: it keeps reading word 0)
+//                              mor[hq]    ORed into every word read (all ones for an unmasked query)
+//                              mw[hq]     the current block's allow word, what the epilogue tests
+//                              mwn[hq]    the next block's word as fetched (mor not yet applied)
+
+// 16-bit storage and the exact-f32 MFMA: one slot, one MFMA group per query half
+template <int DT>
+struct Op16 {
+  typedef StageLds Stage;
+  template <int QH> static __device__ __forceinline__ int image_kib(int kg) { return kg * QH; }
+  template <int QH>
+  static __device__ __forceinline__ void step(f32x16 (&acc)[QH], const u32x4 (&ring)[TS_RING], int i, const u32x4* ql, int g) {
+#pragma unroll
+    for (int hq = 0; hq < QH; ++hq) {
+      const u32x4 b = ql[(size_t)g * (QH * 64) + hq * 64];   // (hq as a constant offset: one address per k group)
+      mma_group<DT>(acc[hq], ring[i], b);
+    }
+  }
+};
+
+#if defined(TS_TUNING) && defined(DBG_NO_LDS)  // ablation builds only (wrong results): the B operand is the next ring slot
+template <int DT>
+struct OpNoLds : Op16<DT> {
+  template <int QH>
+  static __device__ __forceinline__ void step(f32x16 (&acc)[QH], const u32x4 (&ring)[TS_RING], int i, const u32x4*, int) {
+#pragma unroll
+    for (int hq = 0; hq < QH; ++hq) mma_group<DT>(acc[hq], ring[i], ring[(i + 1) % TS_RING]);
+  }
+};
+#endif
+
+typedef const uint32_t __attribute__((address_space(4)))* ts_sgpr_u32p;   // scalar loads: lgkmcnt, not vmcnt
+typedef const int32_t __attribute__((address_space(4)))* ts_sgpr_i32p;
+
+// work item w is row block blk0 + w * blk_stride
+struct WalkStrided {
+  typedef ScanParams Params;
+  static constexpr bool kMasked = false;
+  static __device__ __forceinline__ int wave(int tid) { return tid >> 6; }
+  static __device__ __forceinline__ int64_t nwork(const Params& p) { return p.nwork; }
+  static __device__ __forceinline__ int64_t block(const Params& p, int64_t i) { return p.blk0 + i * p.blk_stride; }
+  static __device__ __forceinline__ int64_t idle(const Params& p) { return p.blk0; }
+};
+
+// Filtered searches: work item w is row block p.live[w], w < *p.nlive.  Both are read with scalar loads (constant
+// address space, wave-uniform index): they count against lgkmcnt, not vmcnt, so fetching the next block's index never
+// waits for the corpus ring.  Each lane's allow word of the NEXT block is requested just before that block's first
+// ring loads, unpredicated (an unmasked query reads word 0 of mask 0 and ORs in all ones), and is complete by the
+// time the block's epilogue reads it: vmcnt retires in order, and the ring loads issued after it have been consumed
+// by then.
+struct WalkLive {
+  typedef MaskedScanParams Params;
+  static constexpr bool kMasked = true;
+  static __device__ __forceinline__ int wave(int tid) { return __builtin_amdgcn_readfirstlane(tid >> 6); }
+  static __device__ __forceinline__ int64_t nwork(const Params& p) { return (int64_t)*(ts_sgpr_u32p)p.nlive; }
+  static __device__ __forceinline__ int64_t block(const Params& p, int64_t i) {
+    return (int64_t)((ts_sgpr_i32p)p.live)[i];
+  }
+  static __device__ __forceinline__ int64_t idle(const Params&) { return 0; }
+  template <int QH>
+  static __device__ __forceinline__ void mask_init(const Params& p, int64_t blk, int lane, const uint32_t* (&mrow)[QH],
+                                                   int64_t (&mstep)[QH], uint32_t (&mor)[QH], uint32_t (&mw)[QH]) {
+#pragma unroll
+    for (int hq = 0; hq < QH; ++hq) {
+      const int32_t qm = p.qmask[hq * 32 + (lane & 31)];
+      mrow[hq] = p.allow_bits + (qm < 0 ? 0 : (int64_t)qm * p.allow_words);
+      mstep[hq] = qm < 0 ? 0 : 1;
+      mor[hq] = qm < 0 ? ~0u : 0u;
+      mw[hq] = mrow[hq][blk * mstep[hq]] | mor[hq];
+    }
+  }
+  template <int QH>
+  static __device__ __forceinline__ void mask_fetch(const Params&, int64_t blkn, const uint32_t* const (&mrow)[QH],
+                                                    const int64_t (&mstep)[QH], uint32_t (&mwn)[QH]) {
+#pragma unroll
+    for (int hq = 0; hq < QH; ++hq) mwn[hq] = mrow[hq][blkn * mstep[hq]];
+  }
+  template <int QH>
+  static __device__ __forceinline__ void mask_advance(const uint32_t (&mor)[QH], const uint32_t (&mwn)[QH],
+                                                      uint32_t (&mw)[QH]) {
+#pragma unroll
+    for (int hq = 0; hq < QH; ++hq) mw[hq] = mwn[hq] | mor[hq];
+  }
+};
+
+// Q image global(L2) -> LDS, once per workgroup.  8 independent loads in flight per thread (a one-load-at-a-time copy
+// of the 96 KiB image costs ~18 us of serial L2 latency per workgroup)
+__device__ __forceinline__ void scan_load_image(u32x4* qlds, const uint4* qimg, int units, int tid) {
+  const u32x4* src = reinterpret_cast<const u32x4*>(qimg);
+  for (int i0 = tid; i0 < units; i0 += 8 * SCAN_THREADS) {
+    u32x4 t[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int i = i0 + j * SCAN_THREADS;
+      t[j] = (i < units) ? src[i] : u32x4{0, 0, 0, 0};
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int i = i0 + j * SCAN_THREADS;
+      if (i < units) qlds[i] = t[j];
+    }
+  }
+}
+
+// One persistent wave streams work items gw, gw+W, gw+2W, ... (W = waves in the grid).  No barrier after the prologue.
+// The template is the __global__ function itself: a body inlined into named kernels allocates registers differently.
+template <int QH, int MODE, class OP, class WALK>
+__global__ __launch_bounds__(SCAN_THREADS) void scan_kernel(typename WALK::Params p) {
+  typedef typename OP::Stage Stage;
+  constexpr bool MASKED = WALK::kMasked && MODE == SCAN_FILTER;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  u32x4* qlds = reinterpret_cast<u32x4*>(smem);
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = WALK::wave(tid);
+  const int kg = p.kg;
+
+  // ---- the first corpus loads go out before anything else, so the HBM round trip
+  // overlaps the Q-image copy below
+  const int64_t nwaves = (int64_t)gridDim.x * SCAN_WAVES;
+  int64_t w = (int64_t)blockIdx.x * SCAN_WAVES + wave;
+  const int64_t nwork = WALK::nwork(p);
+  const bool active = w < nwork;  // (waves without work still join the final flush)
+  const u32x4* base = reinterpret_cast<const u32x4*>(p.corpus) + lane;
+  const size_t blk_units = (size_t)kg * 64;
+  int64_t blk = active ? WALK::block(p, w) : WALK::idle(p);
+  const u32x4* cur = base + (size_t)blk * blk_units;
+  u32x4 ring[TS_RING];
+  if (active) {
+#pragma unroll
+    for (int i = 0; i < TS_RING; ++i) ring[i] = stream_load(cur + (size_t)i * 64);
+  }
+
+  // ---- prologue: Q image global(L2) -> LDS, once per workgroup
+  const int image_kib = OP::template image_kib<QH>(kg);
+  scan_load_image(qlds, p.qimg, image_kib * 64, tid);
+  Stage* st = reinterpret_cast<Stage*>(smem + (size_t)image_kib * 1024);
+  if constexpr (MODE == SCAN_FILTER) {
+    if (tid == 0) st->cnt = 0;
+  }
+  __syncthreads();
+
+  if (active) {
+    float tau[QH];
+    if constexpr (MODE == SCAN_FILTER) {
+#pragma unroll
+      for (int hq = 0; hq < QH; ++hq) tau[hq] = p.tau[hq * 32 + (lane & 31)];
+    }
+    // the allow-word state of a masked walk (plain arrays: held in a struct they change the register allocation)
+    const uint32_t* mrow[QH];
+    int64_t mstep[QH];
+    uint32_t mor[QH], mw[QH];
+    if constexpr (MASKED) WALK::template mask_init<QH>(p, blk, lane, mrow, mstep, mor, mw);
+
+    const u32x4* ql = qlds + lane;
+
+    while (true) {
+      const int64_t wn = w + nwaves;
+      const bool has_next = wn < nwork;
+      const int64_t blkn = has_next ? WALK::block(p, wn) : blk;
+      const u32x4* nxt = base + (size_t)blkn * blk_units;
+
+      f32x16 acc[QH];
+#pragma unroll
+      for (int hq = 0; hq < QH; ++hq)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[hq][r] = 0.f;
+
+      // main part: prefetch stays inside the current row block
+      int g0 = 0;
+      for (; g0 < kg - TS_RING; g0 += TS_RING) {
+#pragma unroll
+        for (int i = 0; i < TS_RING; ++i) {
+          OP::template step<QH>(acc, ring, i, ql, g0 + i);
+          // refill the slot just consumed; the barrier keeps the compiler from
+          // clustering the ring's loads (which would drain vmcnt to 0 mid-loop)
+          ring[i] = stream_load(cur + (size_t)(g0 + i + TS_RING) * 64);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+      // tail: (masked: the next block's allow words, then) the ring is refilled from the start of the wave's next
+      // row block
+      uint32_t mwn[QH];
+      if constexpr (MASKED) WALK::template mask_fetch<QH>(p, blkn, mrow, mstep, mwn);
+#pragma unroll
+      for (int i = 0; i < TS_RING; ++i) {
+        OP::template step<QH>(acc, ring, i, ql, g0 + i);
+        ring[i] = stream_load(nxt + (size_t)i * 64);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+
+      if constexpr (MODE == SCAN_DENSE)
+        epilogue_dense<QH>(p, acc, w, blk, lane);
+      else if constexpr (MASKED)
+        epilogue_filter<QH, Stage, true>(p, st, acc, tau, blk, lane, mw);
+      else
+        epilogue_filter<QH>(p, st, acc, tau, blk, lane);
+
+      if (!has_next) break;
+      w = wn;
+      blk = blkn;
+      cur = nxt;
+      if constexpr (MASKED) WALK::template mask_advance<QH>(mor, mwn, mw);
+    }
+  }  // active
+  if constexpr (MODE == SCAN_FILTER) flush_stage(p, st, tid);
+}
+
+// workgroups of a scan over nwork work items: one per SCAN_WAVES items, at most cap, at least one
+static inline int ts_scan_grid(int64_t nwork, int64_t cap) {
+  const int64_t want = (nwork + SCAN_WAVES - 1) / SCAN_WAVES;
+  const int grid = (int)(want < cap ? want : cap);
+  return grid < 1 ? 1 : grid;
+}
+
+template <int QH, int MODE, class OP, class WALK>
+static int launch_scan_ring(const typename WALK::Params& p, size_t lds, int grid, hipStream_t stream) {
+  auto kern = scan_kernel<QH, MODE, OP, WALK>;
+  static TsDeviceOnce lds_attr;  // per instantiation, per device (ts_common.h)
+  TS_CHECK(ts_allow_max_lds(lds_attr, reinterpret_cast<const void*>(kern)));
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(SCAN_THREADS), lds, stream, p);
+  TS_HIP(hipGetLastError());
+  return TS_OK;
+}
 
 // ------------------------------------------------------------------ layout
 template <typename T> struct ElemIO;

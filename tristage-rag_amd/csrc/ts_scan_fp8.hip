@@ -12,8 +12,8 @@
 // thresholds, candidate lists, selects, masks) is what it is for the 16-bit scans.  A score equals, bit for bit, the
 // score of a bf16 index that holds the decoded rows: the same operands up to the power of two, the same k order.
 //
-// The loops are scan_kernel's and scan_masked_kernel's (ts_scan.hip): persistent waves, the TS_RING-deep ring of
-// non-temporal 1 KiB loads, a sched_barrier per slot.  A slot now feeds two MFMAs per query half.
+// The scans are scan_kernel (ts_scan_dev.h) with OpFp8 below, over WalkStrided or, for filtered searches, WalkLive:
+// a ring slot feeds two MFMAs per query half, and the image is twice an Op16 image.
 #include "ts_scan_dev.h"
 
 __device__ __forceinline__ uint32_t fp8_pair_bf16(uint32_t w, bool hi) {
@@ -48,196 +48,14 @@ __device__ __forceinline__ void fp8_slot(f32x16 (&acc)[QH], const u32x4& a, cons
   }
 }
 
-// Q image (2 * kg * QH KiB) global(L2) -> LDS, once per workgroup: scan_kernel's copy
-template <int QH>
-__device__ __forceinline__ void fp8_load_image(u32x4* qlds, const uint4* qimg, int kg, int tid) {
-  const u32x4* src = reinterpret_cast<const u32x4*>(qimg);
-  const int units = 2 * kg * QH * 64;
-  for (int i0 = tid; i0 < units; i0 += 8 * SCAN_THREADS) {
-    u32x4 t[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int i = i0 + j * SCAN_THREADS;
-      t[j] = (i < units) ? src[i] : u32x4{0, 0, 0, 0};
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int i = i0 + j * SCAN_THREADS;
-      if (i < units) qlds[i] = t[j];
-    }
+struct OpFp8 {
+  typedef StageLds Stage;
+  template <int QH> static __device__ __forceinline__ int image_kib(int kg) { return 2 * kg * QH; }
+  template <int QH>
+  static __device__ __forceinline__ void step(f32x16 (&acc)[QH], const u32x4 (&ring)[TS_RING], int i, const u32x4* ql, int g) {
+    fp8_slot<QH>(acc, ring[i], ql, g);
   }
-}
-
-template <int QH, int MODE>
-__global__ __launch_bounds__(SCAN_THREADS) void scan_fp8_kernel(ScanParams p) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  u32x4* qlds = reinterpret_cast<u32x4*>(smem);
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-  const int kg = p.kg;   // 1 KiB units per row block (32 k each)
-
-  const int64_t nwaves = (int64_t)gridDim.x * SCAN_WAVES;
-  int64_t w = (int64_t)blockIdx.x * SCAN_WAVES + wave;
-  const bool active = w < p.nwork;  // (waves without work still join the final flush)
-  const u32x4* base = reinterpret_cast<const u32x4*>(p.corpus) + lane;
-  const size_t blk_units = (size_t)kg * 64;
-  int64_t blk = active ? p.blk0 + w * p.blk_stride : p.blk0;
-  const u32x4* cur = base + (size_t)blk * blk_units;
-  u32x4 ring[TS_RING];
-  if (active) {
-#pragma unroll
-    for (int i = 0; i < TS_RING; ++i) ring[i] = stream_load(cur + (size_t)i * 64);
-  }
-  fp8_load_image<QH>(qlds, p.qimg, kg, tid);
-  StageLds* st = reinterpret_cast<StageLds*>(smem + (size_t)2 * kg * QH * 1024);
-  if constexpr (MODE == SCAN_FILTER) {
-    if (tid == 0) st->cnt = 0;
-  }
-  __syncthreads();
-
-  if (active) {
-    float tau[QH];
-    if constexpr (MODE == SCAN_FILTER) {
-#pragma unroll
-      for (int hq = 0; hq < QH; ++hq) tau[hq] = p.tau[hq * 32 + (lane & 31)];
-    }
-    const u32x4* ql = qlds + lane;
-    while (true) {
-      const int64_t wn = w + nwaves;
-      const bool has_next = wn < p.nwork;
-      const int64_t blkn = has_next ? (p.blk0 + wn * p.blk_stride) : blk;
-      const u32x4* nxt = base + (size_t)blkn * blk_units;
-
-      f32x16 acc[QH];
-#pragma unroll
-      for (int hq = 0; hq < QH; ++hq)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[hq][r] = 0.f;
-
-      // main part: prefetch stays inside the current row block
-      int g0 = 0;
-      for (; g0 < kg - TS_RING; g0 += TS_RING) {
-#pragma unroll
-        for (int i = 0; i < TS_RING; ++i) {
-          fp8_slot<QH>(acc, ring[i], ql, g0 + i);
-          ring[i] = stream_load(cur + (size_t)(g0 + i + TS_RING) * 64);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-      // tail: the ring is refilled from the start of the wave's next row block
-#pragma unroll
-      for (int i = 0; i < TS_RING; ++i) {
-        fp8_slot<QH>(acc, ring[i], ql, g0 + i);
-        ring[i] = stream_load(nxt + (size_t)i * 64);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-
-      if constexpr (MODE == SCAN_DENSE)
-        epilogue_dense<QH>(p, acc, w, blk, lane);
-      else
-        epilogue_filter<QH>(p, st, acc, tau, blk, lane);
-
-      if (!has_next) break;
-      w = wn;
-      blk = blkn;
-      cur = nxt;
-    }
-  }  // active
-  if constexpr (MODE == SCAN_FILTER) flush_stage(p, st, tid);
-}
-
-// scan_masked_kernel (ts_scan.hip) over e4m3 rows: the live-block list and the count are scalar loads, each lane's
-// allow word of the next block is requested just before that block's first ring loads and read in its epilogue
-typedef const uint32_t __attribute__((address_space(4)))* fp8_sgpr_u32p;
-typedef const int32_t __attribute__((address_space(4)))* fp8_sgpr_i32p;
-
-template <int QH>
-__global__ __launch_bounds__(SCAN_THREADS) void scan_fp8_masked_kernel(MaskedScanParams p) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  u32x4* qlds = reinterpret_cast<u32x4*>(smem);
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int kg = p.kg;
-
-  const int64_t nwaves = (int64_t)gridDim.x * SCAN_WAVES;
-  int64_t w = (int64_t)blockIdx.x * SCAN_WAVES + wave;
-  const int64_t nwork = (int64_t)*(fp8_sgpr_u32p)p.nlive;
-  const bool active = w < nwork;  // (waves without work still join the final flush)
-  const u32x4* base = reinterpret_cast<const u32x4*>(p.corpus) + lane;
-  const size_t blk_units = (size_t)kg * 64;
-  int64_t blk = active ? (int64_t)((fp8_sgpr_i32p)p.live)[w] : 0;
-  const u32x4* cur = base + (size_t)blk * blk_units;
-  u32x4 ring[TS_RING];
-  if (active) {
-#pragma unroll
-    for (int i = 0; i < TS_RING; ++i) ring[i] = stream_load(cur + (size_t)i * 64);
-  }
-  fp8_load_image<QH>(qlds, p.qimg, kg, tid);
-  StageLds* st = reinterpret_cast<StageLds*>(smem + (size_t)2 * kg * QH * 1024);
-  if (tid == 0) st->cnt = 0;
-  __syncthreads();
-
-  if (active) {
-    float tau[QH];
-    const uint32_t* mrow[QH];   // the lane's allow-word row
-    int64_t mstep[QH];          // 0 for an unmasked query: it keeps reading word 0
-    uint32_t mor[QH], mw[QH];   // all ones for an unmasked query; the current block's word
-#pragma unroll
-    for (int hq = 0; hq < QH; ++hq) {
-      tau[hq] = p.tau[hq * 32 + (lane & 31)];
-      const int32_t qm = p.qmask[hq * 32 + (lane & 31)];
-      mrow[hq] = p.allow_bits + (qm < 0 ? 0 : (int64_t)qm * p.allow_words);
-      mstep[hq] = qm < 0 ? 0 : 1;
-      mor[hq] = qm < 0 ? ~0u : 0u;
-      mw[hq] = mrow[hq][blk * mstep[hq]] | mor[hq];
-    }
-    const u32x4* ql = qlds + lane;
-    while (true) {
-      const int64_t wn = w + nwaves;
-      const bool has_next = wn < nwork;
-      const int64_t blkn = has_next ? (int64_t)((fp8_sgpr_i32p)p.live)[wn] : blk;
-      const u32x4* nxt = base + (size_t)blkn * blk_units;
-
-      f32x16 acc[QH];
-#pragma unroll
-      for (int hq = 0; hq < QH; ++hq)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[hq][r] = 0.f;
-
-      int g0 = 0;
-      for (; g0 < kg - TS_RING; g0 += TS_RING) {
-#pragma unroll
-        for (int i = 0; i < TS_RING; ++i) {
-          fp8_slot<QH>(acc, ring[i], ql, g0 + i);
-          ring[i] = stream_load(cur + (size_t)(g0 + i + TS_RING) * 64);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-      // tail: the next block's allow words, then the ring is refilled from the start of that block
-      uint32_t mwn[QH];
-#pragma unroll
-      for (int hq = 0; hq < QH; ++hq) mwn[hq] = mrow[hq][blkn * mstep[hq]];
-#pragma unroll
-      for (int i = 0; i < TS_RING; ++i) {
-        fp8_slot<QH>(acc, ring[i], ql, g0 + i);
-        ring[i] = stream_load(nxt + (size_t)i * 64);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-
-      epilogue_filter<QH, StageLds, true>(p, st, acc, tau, blk, lane, mw);
-
-      if (!has_next) break;
-      w = wn;
-      blk = blkn;
-      cur = nxt;
-#pragma unroll
-      for (int hq = 0; hq < QH; ++hq) mw[hq] = mwn[hq] | mor[hq];
-    }
-  }  // active
-  flush_stage(p, st, tid);
-}
+};
 
 size_t ts_scan_fp8_lds_bytes(const TsLayout& L, int qh) {
   return (size_t)2 * L.kg * qh * 1024 + sizeof(StageLds);
@@ -246,19 +64,10 @@ size_t ts_scan_fp8_lds_bytes(const TsLayout& L, int qh) {
 template <int QH, int MODE>
 static int launch_scan_fp8_t(const TsLayout& L, const ScanParams& p, int num_cus, hipStream_t stream) {
   const size_t lds = (size_t)2 * L.kg * QH * 1024 + (MODE == SCAN_FILTER ? sizeof(StageLds) : 0);
-  auto kern = scan_fp8_kernel<QH, MODE>;
-  static TsDeviceOnce lds_attr;
-  TS_CHECK(ts_allow_max_lds(lds_attr, reinterpret_cast<const void*>(kern)));
-  // as launch_scan_t: the short dense scans take a second workgroup per CU when LDS allows
-  int wg_per_cu = 1;
-  if (MODE == SCAN_DENSE && 2 * lds <= 160 * 1024) wg_per_cu = 2;
-  const int64_t want = (p.nwork + SCAN_WAVES - 1) / SCAN_WAVES;
-  const int64_t cap = (int64_t)num_cus * wg_per_cu;
-  int grid = (int)(want < cap ? want : cap);
-  if (grid < 1) grid = 1;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(SCAN_THREADS), lds, stream, p);
-  TS_HIP(hipGetLastError());
-  return TS_OK;
+  // as ts_scan.hip's launch_scan_t: the short dense scans take a second workgroup per CU when LDS allows
+  const int wg_per_cu = (MODE == SCAN_DENSE && 2 * lds <= 160 * 1024) ? 2 : 1;
+  return launch_scan_ring<QH, MODE, OpFp8, WalkStrided>(p, lds, ts_scan_grid(p.nwork, (int64_t)num_cus * wg_per_cu),
+                                                        stream);
 }
 
 int ts_launch_scan_fp8(const TsLayout& L, int mode, int qh, const ScanParams& p, int num_cus, hipStream_t stream) {
@@ -274,19 +83,11 @@ int ts_launch_scan_fp8(const TsLayout& L, int mode, int qh, const ScanParams& p,
                             : launch_scan_fp8_t<2, SCAN_FILTER>(L, p, num_cus, stream);
 }
 
+// p.nwork: every row block (the live count is only known on the device; waves past it leave at once)
 template <int QH>
 static int launch_scan_fp8_masked_t(const TsLayout& L, const MaskedScanParams& p, int num_cus, hipStream_t stream) {
-  const size_t lds = (size_t)2 * L.kg * QH * 1024 + sizeof(StageLds);
-  auto kern = scan_fp8_masked_kernel<QH>;
-  static TsDeviceOnce lds_attr;
-  TS_CHECK(ts_allow_max_lds(lds_attr, reinterpret_cast<const void*>(kern)));
-  // p.nwork: every row block (the live count is only known on the device; waves past it leave at once)
-  const int64_t want = (p.nwork + SCAN_WAVES - 1) / SCAN_WAVES;
-  int grid = (int)(want < num_cus ? want : num_cus);
-  if (grid < 1) grid = 1;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(SCAN_THREADS), lds, stream, p);
-  TS_HIP(hipGetLastError());
-  return TS_OK;
+  return launch_scan_ring<QH, SCAN_FILTER, OpFp8, WalkLive>(p, ts_scan_fp8_lds_bytes(L, QH),
+                                                            ts_scan_grid(p.nwork, num_cus), stream);
 }
 
 int ts_launch_scan_masked_fp8(const TsLayout& L, int qh, const MaskedScanParams& p, int num_cus, hipStream_t stream) {
