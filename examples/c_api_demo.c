@@ -6,7 +6,8 @@
  * Builds a deterministic corpus on the host, adds it (host pointers), searches,
  * and writes  [float scores nq*k][int64 ids nq*k]  so a test can compare with the
  * oracle computed from the same generator (tests/test_c_api_gpu.py).  Then a range search with each query's k-th
- * score as its radius (ts_index_range_search, ts_index_range_fetch): at least k rows per query, ids ascending.
+ * score as its radius (ts_index_range_search, ts_index_range_fetch): at least k rows per query, ids ascending.  Then a
+ * diversified selection of min(k, 5) of each query's k results (ts_index_mmr): lambda = 1 gives the list's head back.
  */
 #include <math.h>
 #include <stdint.h>
@@ -81,6 +82,26 @@ int main(int argc, char** argv) {
   }
   printf("range results %lld (first query %lld)\n", (long long)total, (long long)(lims[1] - lims[0]));
   free(radius); free(lims); free(RD); free(RI);
+  /* maximal marginal relevance over the search result: pick km of each query's k candidates (host pointers) */
+  const int km = k < 5 ? k : 5;
+  float* MD = (float*)malloc(sizeof(float) * (size_t)nq * km);
+  int64_t* MI = (int64_t*)malloc(sizeof(int64_t) * (size_t)nq * km);
+  if (!MD || !MI) return 3;
+  if (k <= 1024) {
+    if (ts_index_mmr(h, I, D, nq, k, k + 1, 0.5f, MD, MI, TS_FLAG_HOST_PTR, NULL) != TS_ERR_INVALID) return 8; /* k > fetch_k */
+    CHECK(ts_index_mmr(h, I, D, nq, k, km, 1.0f, MD, MI, TS_FLAG_HOST_PTR, NULL));
+    for (int q = 0; q < nq; ++q)
+      for (int j = 0; j < km; ++j)
+        if (MI[(size_t)q * km + j] != I[(size_t)q * k + j] || MD[(size_t)q * km + j] != D[(size_t)q * k + j]) return 8;
+    CHECK(ts_index_mmr(h, I, D, nq, k, km, 0.5f, MD, MI, TS_FLAG_HOST_PTR, NULL));
+    if (MI[0] != I[0]) return 8; /* step 0 is the most relevant candidate */
+    printf("mmr picks of query 0:");
+    for (int j = 0; j < km; ++j) printf(" %lld", (long long)MI[j]);
+    printf("\n");
+  } else if (ts_index_mmr(h, I, D, nq, k, km, 0.5f, MD, MI, TS_FLAG_HOST_PTR, NULL) != TS_ERR_UNSUPPORTED) {
+    return 8; /* more than 1024 candidates */
+  }
+  free(MD); free(MI);
   FILE* f = fopen(argv[5], "wb");
   if (!f) return 6;
   fwrite(D, sizeof(float), (size_t)nq * k, f);

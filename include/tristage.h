@@ -58,7 +58,9 @@ extern "C" {
  * and ts_index_range_fetch: no existing signature changed, and a caller that never runs a range search sees the
  * library it was built against (no existing kernel changed).  So was e4m3 index storage (ts_index_create accepts
  * TS_FP8_E4M3; ts_index_set_fp8_scale_log2, ts_index_fp8_scale_log2): no existing signature changed, and an index of
- * another storage dtype runs the kernels it ran before.                                                         */
+ * another storage dtype runs the kernels it ran before.  So were ts_index_mmr, ts_mmr_ivf and the measurement aid
+ * ts_index_mmr_set_timing / ts_index_mmr_get_timings: no existing signature or kernel changed, and a caller that
+ * never calls them allocates and launches nothing new.                                                          */
 #define TS_ABI_VERSION 4
 
 typedef struct ts_index ts_index; /* opaque */
@@ -334,6 +336,41 @@ int32_t ts_index_dtype(const ts_index* h);
  * the index holds rows (ts_index_reset empties it).  ts_index_fp8_scale_log2: s, or -1 for another storage dtype.  */
 int ts_index_set_fp8_scale_log2(ts_index* h, int32_t s);
 int32_t ts_index_fp8_scale_log2(const ts_index* h);
+/* ---- diversified selection: maximal marginal relevance --------------------------------------
+ * Reference call site: none (the reference returns the plain top-k of overlapping chunks, src/utils.py chunk_text).
+ * Added within version 4: no existing signature or kernel changed, and a caller that never calls these allocates
+ * and launches nothing new.
+ * Per query: fetch_k candidate ids (cand_ids [nq, fetch_k] int64, in the id space search returns, i.e. with the id
+ * offset; -1 = padding) with their relevances (cand_rel [nq, fetch_k] float32), and k picks, 1 <= k <= fetch_k <= 1024.
+ * sim(i, j) is the f32 inner product of the STORED rows i and j: f16 / bf16 rows as stored, e4m3 rows decoded to
+ * bf16 and scaled by 2^-s (what ts_index_reconstruct returns), f32 rows in exact f32 arithmetic; with the unit rows
+ * the pipeline stores, the cosine.  Step 0 picks the largest relevance; step t picks the unpicked candidate with the
+ * largest  lambda * rel_i - (1 - lambda) * max_{j picked} sim(i, j),  evaluated in f32 (each product rounded, then
+ * the difference); ties go to the lower position in the candidate list.  Padding is never picked, nor is the id of
+ * a removed (tombstoned) row: it is skipped like padding.  out_rel / out_ids [nq, k] hold the picks in selection
+ * order, out_rel their relevances; the tail is -1 / -FLT_MAX where a query has fewer than k valid candidates.
+ * lambda = 1 returns the first k valid candidates in relevance order (for a list ts_index_search returned: its
+ * first k entries).
+ * All pointers are device memory (host memory with TS_FLAG_HOST_PTR, staged; the call is then synchronous).  With
+ * device pointers the call only enqueues three kernels per chunk of queries on `stream` (gather of the candidates'
+ * 16-byte units into a tile, Gram matrix on the matrix cores, greedy selection) and returns: it chains behind a
+ * ts_index_search on the same stream without a synchronisation.  Calls on one handle share its scratch (candidate
+ * tiles and Gram matrices of one chunk of queries, at most 384 MiB whatever nq; allocated at the first call, freed
+ * with the handle) and are ordered one behind the other.
+ * TS_ERR_INVALID: null handle or pointer, k < 1, k > fetch_k, lambda outside [0, 1] (or NaN), and with
+ * TS_FLAG_HOST_PTR an id other than -1 outside [offset, offset + ntotal).  Device ids cannot be read without a
+ * synchronisation: there such an id is never dereferenced and is skipped like padding.  TS_ERR_UNSUPPORTED:
+ * fetch_k > 1024.  Both before any HIP call, with a message in ts_last_error().
+ * ts_mmr_ivf: the same over the rows of an IVF index (ids through its id-to-slot table on the device); bit for bit
+ * what ts_index_mmr returns on a flat index of the same dtype holding the same rows.  (Outside the ts_ivf_ prefix
+ * for the reason given at ts_remove_ivf.)                                                                        */
+int ts_index_mmr(ts_index* h, const int64_t* cand_ids, const float* cand_rel, int32_t nq, int32_t fetch_k, int32_t k,
+                 float lambda, float* out_rel, int64_t* out_ids, uint32_t flags, void* stream);
+/* Measurement aid of tools/mmr_probe.py (no reference counterpart): with timing on, ts_index_mmr records HIP events
+ * around the three kernels of every chunk and waits for each chunk, so the call is synchronous; ms[0..2] are the
+ * summed milliseconds of gather, Gram and greedy selection over *calls timed calls since the last reset.           */
+int ts_index_mmr_set_timing(ts_index* h, int32_t on);
+int ts_index_mmr_get_timings(ts_index* h, double ms[3], int64_t* calls, int32_t reset);
 /* row-shard support: ids reported by search = local row + offset            */
 int ts_index_set_id_offset(ts_index* h, int64_t offset);
 /* copy rows [row0, row0+n) back out as row-major float32 (host or device):
@@ -677,6 +714,9 @@ int ts_update_ivf(ts_ivf* h, const int64_t* ids, int64_t n, const void* rows, in
  * new corpus) and swapped in at the end; on an error the index is as it was.  Ordered on `stream`, synchronous.
  * Added within version 4; outside the ts_ivf_ prefix for the reason given above.                                  */
 int ts_compact_ivf(ts_ivf* h, int64_t* old2new, void* stream);
+/* ts_index_mmr over an IVF index: see "diversified selection" above */
+int ts_mmr_ivf(ts_ivf* h, const int64_t* cand_ids, const float* cand_rel, int32_t nq, int32_t fetch_k, int32_t k,
+               float lambda, float* out_rel, int64_t* out_ids, uint32_t flags, void* stream);
 int ts_ivf_set_id_offset(ts_ivf* h, int64_t offset);
 int ts_ivf_last_search_info(const ts_ivf* h, int64_t info[4]);
 

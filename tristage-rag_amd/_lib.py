@@ -91,6 +91,12 @@ SIGNATURES = {
     "ts_remove_ivf": (c_int32, [c_void_p, c_void_p, c_int64, POINTER(c_int64), c_void_p]),
     "ts_update_ivf": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_uint32, c_void_p]),
     "ts_compact_ivf": (c_int32, [c_void_p, c_void_p, c_void_p]),
+    "ts_index_mmr": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_float, c_void_p, c_void_p,
+                               c_uint32, c_void_p]),
+    "ts_index_mmr_set_timing": (c_int32, [c_void_p, c_int32]),
+    "ts_index_mmr_get_timings": (c_int32, [c_void_p, POINTER(ctypes.c_double), POINTER(c_int64), c_int32]),
+    "ts_mmr_ivf": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_float, c_void_p, c_void_p,
+                             c_uint32, c_void_p]),
     "ts_ivf_set_id_offset": (c_int32, [c_void_p, c_int64]),
     "ts_ivf_last_search_info": (c_int32, [c_void_p, POINTER(c_int64)]),
     "ts_merge_topk": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p,

@@ -484,3 +484,38 @@ int ts_launch_ivf_compact_move(const TsLayout& L, const uint4* old_corpus, const
                                const int32_t* new2old, const int32_t* dst, int64_t nlive, int64_t new_blocks,
                                uint4* new_corpus, int32_t* src_slot, int64_t* new_slot2id, int64_t* new_id2slot,
                                uint32_t* new_valid, hipStream_t stream);
+
+// ---------------------------------------------------------------- MMR (ts_mmr.hip)
+// Per-handle state of ts_index_mmr / ts_mmr_ivf: nothing is allocated before the first call; ts_mmr_release frees it
+// with the handle.  scratch: candidate tiles, Gram matrices and validity words of one chunk of queries (at most
+// 384 MiB, whatever the batch); stage: the staging of host-pointer calls; ev orders a call behind the previous one.
+struct TsMmrWork {
+  void* scratch = nullptr;
+  size_t scratch_bytes = 0;
+  void* stage = nullptr;
+  size_t stage_bytes = 0;
+  hipEvent_t ev = nullptr;
+  bool used = false;
+  // ts_index_mmr_set_timing: timed events around the three kernels of every chunk; such a call synchronises
+  bool timing = false;
+  hipEvent_t tev[4] = {};
+  double phase_ms[3] = {0.0, 0.0, 0.0};   // gather, gram, greedy
+  int64_t timed_calls = 0;
+};
+// where the candidates' rows live: a flat index (live: its tombstone words, or null while nothing is removed) or an
+// IVF index (ivf: ids go through id2slot, a slot is live while its bit of blk_valid is set)
+struct TsMmrSource {
+  bool ivf;
+  const uint4* corpus;
+  TsLayout L;
+  int64_t ntotal, id_offset;
+  const uint32_t* live;
+  const int64_t* id2slot;
+  const uint32_t* blk_valid;
+};
+// argument checks of both entry points, before any HIP call
+int ts_mmr_check_args(const void* h, const void* cand_ids, const void* cand_rel, int32_t nq, int32_t fetch_k,
+                      int32_t k, float lambda, const void* out_rel, const void* out_ids);
+int ts_mmr_run(const TsMmrSource& src, TsMmrWork& w, const int64_t* cand_ids, const float* cand_rel, int32_t nq,
+               int32_t C, int32_t k, float lambda, float* out_rel, int64_t* out_ids, uint32_t flags, hipStream_t s);
+void ts_mmr_release(TsMmrWork& w);

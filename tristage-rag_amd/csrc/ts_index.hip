@@ -211,6 +211,8 @@ struct ts_index {
   int64_t rng_cap = 0, rng_total = 0;
   bool rng_valid = false;
   std::mutex range_mu;
+  // MMR (ts_index_mmr): scratch and staging, allocated at the first call
+  TsMmrWork mmr;
 };
 
 static int co_flush(ts_index* h, hipStream_t s);
@@ -369,6 +371,7 @@ extern "C" int ts_index_destroy(ts_index* h) {
                   &h->rng_s, &h->rng_i, &h->rng_tiles};
   for (DevBuf* b : rb) release(*b);
   if (h->eff_ev) (void)hipEventDestroy(h->eff_ev);
+  ts_mmr_release(h->mmr);
   delete h;
   return TS_OK;
 }
@@ -515,6 +518,43 @@ extern "C" int ts_index_reconstruct(ts_index* h, int64_t row0, int64_t n, float*
   } else {
     TS_CHECK(ts_launch_reconstruct(h->L, h->corpus, row0, n, out, s));
     TS_HIP(hipStreamSynchronize(s));
+  }
+  return TS_OK;
+}
+
+// ------------------------------------------------------------------ MMR (kernels: ts_mmr.hip)
+extern "C" int ts_index_mmr(ts_index* h, const int64_t* cand_ids, const float* cand_rel, int32_t nq, int32_t fetch_k,
+                            int32_t k, float lambda, float* out_rel, int64_t* out_ids, uint32_t flags, void* stream) {
+  TS_CHECK(ts_mmr_check_args(h, cand_ids, cand_rel, nq, fetch_k, k, lambda, out_rel, out_ids));
+  if (nq == 0) return TS_OK;
+  DeviceGuard g(h->device);
+  hipStream_t s = (hipStream_t)stream;
+  TS_CHECK(co_flush(h, s));   // a held search's results are what the caller chains this call behind
+  TsMmrSource src;
+  src.corpus = h->corpus;
+  src.L = h->L;
+  src.ntotal = h->ntotal;
+  src.id_offset = h->id_offset;
+  src.live = h->nremoved > 0 ? (const uint32_t*)h->live.p : nullptr;
+  src.ivf = false;
+  src.id2slot = nullptr;
+  src.blk_valid = nullptr;
+  return ts_mmr_run(src, h->mmr, cand_ids, cand_rel, nq, fetch_k, k, lambda, out_rel, out_ids, flags, s);
+}
+
+extern "C" int ts_index_mmr_set_timing(ts_index* h, int32_t on) {
+  if (!h) { ts_set_error("null handle"); return TS_ERR_INVALID; }
+  h->mmr.timing = on != 0;
+  return TS_OK;
+}
+
+extern "C" int ts_index_mmr_get_timings(ts_index* h, double ms[3], int64_t* calls, int32_t reset) {
+  if (!h || !ms || !calls) { ts_set_error("bad arguments"); return TS_ERR_INVALID; }
+  for (int i = 0; i < 3; ++i) ms[i] = h->mmr.phase_ms[i];
+  *calls = h->mmr.timed_calls;
+  if (reset) {
+    for (double& m : h->mmr.phase_ms) m = 0.0;
+    h->mmr.timed_calls = 0;
   }
   return TS_OK;
 }

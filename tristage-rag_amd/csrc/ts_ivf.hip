@@ -130,6 +130,7 @@ struct ts_ivf {
   IvfBuf train_x, cent, perm, offs;
   uint32_t* host_rep = nullptr;      // pinned + mapped: select report (64 counts, status, live blocks)
   uint32_t* host_rep_dev = nullptr;
+  TsMmrWork mmr;                     // ts_mmr_ivf: scratch and staging, allocated at the first call
   float* tau() { return (float*)small.p; }
   uint32_t* cand_cnt() { return (uint32_t*)small.p + 64; }
   uint32_t* status() { return (uint32_t*)small.p + 128; }
@@ -666,6 +667,7 @@ extern "C" int ts_ivf_destroy(ts_ivf* h) {
                     &h->upd_ids};
   for (IvfBuf* b : bufs) ivf_release(*b);
   if (h->host_rep) (void)hipHostFree(h->host_rep);
+  ts_mmr_release(h->mmr);
   delete h;
   return TS_OK;
 }
@@ -1147,6 +1149,25 @@ extern "C" int ts_ivf_reconstruct(ts_ivf* h, int64_t id0, int64_t n, float* out,
   TS_HIP(hipGetLastError());
   TS_HIP(hipStreamSynchronize(s));
   return TS_OK;
+}
+
+// MMR over the rows of an IVF index (kernels: ts_mmr.hip; outside the ts_ivf_ prefix, as ts_remove_ivf)
+extern "C" int ts_mmr_ivf(ts_ivf* h, const int64_t* cand_ids, const float* cand_rel, int32_t nq, int32_t fetch_k,
+                          int32_t k, float lambda, float* out_rel, int64_t* out_ids, uint32_t flags, void* stream) {
+  TS_CHECK(ts_mmr_check_args(h, cand_ids, cand_rel, nq, fetch_k, k, lambda, out_rel, out_ids));
+  if (nq == 0) return TS_OK;
+  IvfGuard g(h->device);
+  TsMmrSource src;
+  src.corpus = (const uint4*)h->corpus.p;
+  src.L = h->L;
+  src.ntotal = h->ntotal;
+  src.id_offset = h->id_offset;
+  src.ivf = true;
+  src.live = nullptr;
+  src.id2slot = (const int64_t*)h->id2slot.p;
+  src.blk_valid = (const uint32_t*)h->blk_valid.p;
+  return ts_mmr_run(src, h->mmr, cand_ids, cand_rel, nq, fetch_k, k, lambda, out_rel, out_ids, flags,
+                    (hipStream_t)stream);
 }
 
 extern "C" int ts_ivf_probe(ts_ivf* h, const void* queries, int32_t nq, int32_t q_dtype, int32_t nprobe,

@@ -99,6 +99,70 @@ def _update_call(fn, handle, ids: np.ndarray, ptr, dtype: int, flags: int, strea
     _lib.check(code)
 
 
+MMR_MAX_FETCH = 1024   # candidates per query of mmr(): the greedy kernel runs one thread per candidate
+
+
+def mmr_default_fetch_k(k: int) -> int:
+    """Candidates ``search_mmr`` fetches when ``fetch_k`` is not given."""
+    return min(MMR_MAX_FETCH, max(4 * int(k), 20))
+
+
+def mmr_check(k, fetch_k, lambda_mult):
+    """The argument checks of ``mmr`` / ``search_mmr`` (``ValueError``), made before anything is launched."""
+    lam = float(lambda_mult)
+    if not 0.0 <= lam <= 1.0:
+        raise ValueError(f"lambda_mult must be in [0, 1], got {lambda_mult!r}")
+    k, fetch_k = int(k), int(fetch_k)
+    if k < 1:
+        raise ValueError("k must be positive")
+    if k > fetch_k:
+        raise ValueError(f"k={k} exceeds fetch_k={fetch_k}: MMR picks k out of fetch_k candidates")
+    if fetch_k > MMR_MAX_FETCH:
+        raise ValueError(f"fetch_k={fetch_k} exceeds {MMR_MAX_FETCH}")
+    return k, fetch_k, lam
+
+
+def _mmr_call(ix, entry: str, ids, relevance, k, lambda_mult):
+    """ts_index_mmr / ts_mmr_ivf (``entry``) on the index ``ix``: CUDA tensors in -> tensors out, enqueued on the current
+    stream; anything else goes through host pointers and comes back as numpy.  The arguments are checked first."""
+    device = ix.device if hasattr(ix, "device") else 0
+    if _is_tensor(ids) and ids.is_cuda:
+        torch = _torch()
+        if ids.dim() != 2 or tuple(relevance.shape) != tuple(ids.shape):
+            raise ValueError(f"expected ids and relevance of one shape [B, fetch_k], got {tuple(ids.shape)} and "
+                             f"{tuple(relevance.shape)}")
+        k, C, lam = mmr_check(k, ids.shape[1], lambda_mult)
+        if ids.device.index != device:
+            raise ValueError("the candidates live on a different GPU than the index")
+        ids = ids.to(torch.int64).contiguous()
+        rel = torch.as_tensor(relevance, device=ids.device).to(torch.float32).contiguous()
+        B = ids.shape[0]
+        D = torch.empty((B, k), dtype=torch.float32, device=ids.device)
+        I = torch.empty((B, k), dtype=torch.int64, device=ids.device)
+        args = (ctypes.c_void_p(ids.data_ptr()), ctypes.c_void_p(rel.data_ptr()), B, C, k, lam,
+                ctypes.c_void_p(D.data_ptr()), ctypes.c_void_p(I.data_ptr()), 0, ctypes.c_void_p(_stream_ptr(device)))
+    else:
+        if _is_tensor(ids):
+            ids = ids.detach().cpu().numpy()
+        if _is_tensor(relevance):
+            relevance = relevance.detach().cpu().numpy()
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        rel = np.ascontiguousarray(relevance, dtype=np.float32)
+        if ids.ndim != 2 or rel.shape != ids.shape:
+            raise ValueError(f"expected ids and relevance of one shape [B, fetch_k], got {ids.shape} and {rel.shape}")
+        k, C, lam = mmr_check(k, ids.shape[1], lambda_mult)
+        B = ids.shape[0]
+        D = np.empty((B, k), dtype=np.float32)
+        I = np.empty((B, k), dtype=np.int64)
+        args = (ids.ctypes.data_as(ctypes.c_void_p), rel.ctypes.data_as(ctypes.c_void_p), B, C, k, lam,
+                D.ctypes.data_as(ctypes.c_void_p), I.ctypes.data_as(ctypes.c_void_p), _lib.TS_FLAG_HOST_PTR, None)
+    code = getattr(ix._lib, entry)(ix._h, *args)
+    if code == _lib.TS_ERR_INVALID:
+        raise ValueError(_lib.last_error())
+    _lib.check(code)
+    return D, I
+
+
 class RangeSearchLimitError(RuntimeError):
     """A range search would return more entries than ``max_results`` allows; the message names both numbers.
     ``counts``: results per query as far as the search got (zero behind that)."""
@@ -790,6 +854,34 @@ class FlatIPIndex:
             redone = self._auto_redone + redone
             self._auto_redone = []
         return redone
+
+    # -- diversified selection (MMR) -------------------------
+    def mmr(self, ids, relevance, k: int, lambda_mult: float = 0.5):
+        """Maximal marginal relevance over stored rows: per query pick ``k`` of the candidates ``ids`` [B, fetch_k]
+        (ids as :meth:`search` returns them, -1 = padding, ``fetch_k <= 1024``) with relevances ``relevance``
+        [B, fetch_k].  Step 0 takes the largest relevance, step t the candidate maximising
+        ``lambda_mult * relevance - (1 - lambda_mult) * max similarity to the picks so far`` in f32, ties to the lower
+        position; the similarity is the inner product of the stored rows.  Returns ``(D, I)`` [B, k] in selection
+        order, ``D`` the relevances of the picks, -FLT_MAX / -1 padded.  Removed rows are skipped like padding.
+        CUDA tensors in -> tensors out, enqueued on the current stream (no synchronisation); numpy in -> numpy out."""
+        return _mmr_call(self, "ts_index_mmr", ids, relevance, k, lambda_mult)
+
+    def mmr_timings(self, on: Optional[bool] = None, reset: bool = True) -> dict:
+        """Measurement aid: ``on`` switches the per-kernel timing of :meth:`mmr` (timed calls synchronise); returns the
+        milliseconds summed since the last reset."""
+        if on is not None:
+            _lib.check(self._lib.ts_index_mmr_set_timing(self._h, 1 if on else 0))
+        ms = (ctypes.c_double * 3)()
+        calls = ctypes.c_int64(0)
+        _lib.check(self._lib.ts_index_mmr_get_timings(self._h, ms, ctypes.byref(calls), 1 if reset else 0))
+        return {"gather_ms": ms[0], "gram_ms": ms[1], "greedy_ms": ms[2], "calls": int(calls.value)}
+
+    def search_mmr(self, q, k: int, fetch_k: Optional[int] = None, lambda_mult: float = 0.5, allowed=None):
+        """``search(q, fetch_k, allowed=allowed)`` followed by :meth:`mmr` on the same stream; ``fetch_k`` defaults to
+        ``min(1024, max(4 k, 20))``."""
+        k, fetch_k, lam = mmr_check(k, mmr_default_fetch_k(k) if fetch_k is None else fetch_k, lambda_mult)
+        D, I = self.search(q, fetch_k, allowed=allowed)
+        return self.mmr(I, D, k, lam)
 
     def reconstruct_n(self, i0: int = 0, n: Optional[int] = None) -> np.ndarray:
         """Rows [i0, i0+n) as float32 (after storage rounding)."""
@@ -1570,6 +1662,17 @@ class IVFFlatIndex:
         if was_np:
             return D.cpu().numpy(), I.cpu().numpy()
         return D, I
+
+    def mmr(self, ids, relevance, k: int, lambda_mult: float = 0.5):
+        """:meth:`FlatIPIndex.mmr` over the rows of this index (ids go through the id-to-slot table on the device)."""
+        return _mmr_call(self, "ts_mmr_ivf", ids, relevance, k, lambda_mult)
+
+    def search_mmr(self, q, k: int, fetch_k: Optional[int] = None, lambda_mult: float = 0.5,
+                   nprobe: Optional[int] = None):
+        """``search(q, fetch_k, nprobe=nprobe)`` followed by :meth:`mmr` on the same stream."""
+        k, fetch_k, lam = mmr_check(k, mmr_default_fetch_k(k) if fetch_k is None else fetch_k, lambda_mult)
+        D, I = self.search(q, fetch_k, nprobe=nprobe)
+        return self.mmr(I, D, k, lam)
 
     def finish(self):
         """Asynchronous searches complete synchronously here: nothing is pending, no ticket failed."""

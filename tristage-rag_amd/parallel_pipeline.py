@@ -198,6 +198,10 @@ class ShardedRetrievalPipeline(RetrievalPipeline):
     def update_documents(self, doc_ids, documents, metadata=None) -> int:
         raise NotImplementedError("update_documents is not supported by the row-sharded pipeline")
 
+    def _refuse_mmr(self, mmr_lambda) -> None:
+        if mmr_lambda is not None or getattr(getattr(self, "config", None), "mmr_lambda", None) is not None:
+            raise NotImplementedError("mmr_lambda is not supported by the row-sharded pipeline")
+
     # -- collectives -------------------------------------------------------------
     def _host_staged(self) -> bool:
         return self.world_size > 1 and self._dist.get_backend(self.group) == "gloo"
@@ -342,9 +346,10 @@ class ShardedRetrievalPipeline(RetrievalPipeline):
                     if isinstance(r, dict) and r.get("document") is None and int(r["doc_id"]) in have:
                         r["document"], r["metadata"] = have[int(r["doc_id"])]
 
-    def search(self, query: str, top_k: Optional[int] = None, filter=None) -> Dict[str, Any]:
+    def search(self, query: str, top_k: Optional[int] = None, filter=None, mmr_lambda=None) -> Dict[str, Any]:
         if filter is not None:
             raise NotImplementedError(FILTER_UNSUPPORTED)
+        self._refuse_mmr(mmr_lambda)
         if self.world_size == 1:
             return super().search(query, top_k)
         if self.config.search_on_arrays and self._arrays_agreed():
@@ -416,12 +421,14 @@ class ShardedRetrievalPipeline(RetrievalPipeline):
         out = (pos2.cpu().numpy(), sc2.cpu().numpy(), pos3.cpu().numpy(), sc3.cpu().numpy())
         return out + (self._span(ma, mb), self._span(mb, mc))
 
-    def search_many(self, queries: List[str], top_k: Optional[int] = None, filter=None) -> List[Dict[str, Any]]:
+    def search_many(self, queries: List[str], top_k: Optional[int] = None, filter=None,
+                    mmr_lambda=None) -> List[Dict[str, Any]]:
         """Batched search over R ranks; every rank returns every query's records.  Array path (token store + id
         cache on the shards): three collectives per call besides stage 1's — two all-reduces of small score matrices
         and one gather of the returned texts.  Otherwise the per-record path, query by query."""
         if filter is not None:
             raise NotImplementedError(FILTER_UNSUPPORTED)
+        self._refuse_mmr(mmr_lambda)
         if self.world_size == 1:
             return super().search_many(queries, top_k)
         if not self.stage1 or not self.stage2 or not self.stage3:

@@ -22,6 +22,7 @@ import time
 from dataclasses import asdict, dataclass, fields
 from typing import Any, Dict, List, Optional
 
+import numpy as np
 import yaml
 
 from .stage1_retriever import Stage1Config, Stage1Retriever
@@ -86,6 +87,8 @@ class PipelineConfig:
                                                 # the cross-encoder inputs from token ids on the GPU
     stage3_many_batch_size: int = 1024       # pairs per cross-encoder forward in search_many
     stage3_many_packed_batch_size: int = 4096  # ... when the batch is packed (written-out forward on the GPU): no padding to pay
+    mmr_lambda: Optional[float] = None       # None: off.  0 .. 1: the list stage 3 returns is diversified by maximal marginal
+                                             # relevance (relevance = stage3_score, similarity from the stage-1 index)
 
 
 # (section, key) in the reference's YAML layout -> PipelineConfig field (reference :182-217)
@@ -103,6 +106,10 @@ _YAML_MAP = {
 }
 _GENERAL_KEYS = ("device", "cache_dir", "index_dir", "log_level", "log_file", "enable_timing",
                  "save_intermediate_results", "auto_cleanup", "max_memory_usage_gb")
+
+
+_NO_MMR = object()      # search(..., mmr_lambda=_NO_MMR): the plain search inside a diversified one
+_ALL_RESULTS = 1 << 30  # top_k of that plain search: the whole list stage 3 returns
 
 
 class RetrievalPipeline:
@@ -303,13 +310,57 @@ class RetrievalPipeline:
             self._cleanup_memory()
         return result
 
-    def search(self, query: str, top_k: Optional[int] = None, filter=None) -> Dict[str, Any]:
+    # -- diversified results (MMR) -------------------------------
+    def _mmr_lambda(self, mmr_lambda) -> Optional[float]:
+        """The lambda of a search (the argument, else the config); None: no diversification."""
+        if mmr_lambda is _NO_MMR:
+            return None
+        lam = self.config.mmr_lambda if mmr_lambda is None else mmr_lambda
+        if lam is None:
+            return None
+        lam = float(lam)
+        if not 0.0 <= lam <= 1.0:
+            raise ValueError(f"mmr_lambda must be in [0, 1], got {mmr_lambda!r}")
+        return lam
+
+    def _diversify(self, outs: List[Dict[str, Any]], top_k: int, lam: float) -> List[Dict[str, Any]]:
+        """``results`` of each output (the whole list stage 3 returned) -> its ``top_k`` picks by maximal marginal
+        relevance, in selection order: relevance = stage3_score as f32, similarity = the inner product of the rows the
+        stage-1 index stores (one ts_index_mmr call for the batch).  The records themselves are not changed."""
+        index = self.stage1.faiss_index
+        if not hasattr(index, "mmr"):
+            raise NotImplementedError(f"{type(index).__name__} has no mmr()")
+        lists = [o["results"] for o in outs]
+        C = max((len(r) for r in lists), default=0)
+        if C == 0:
+            return outs
+        from .index import mmr_check
+        k, C, lam = mmr_check(min(int(top_k), C), C, lam)
+        ids = np.full((len(lists), C), -1, dtype=np.int64)
+        rel = np.zeros((len(lists), C), dtype=np.float32)
+        for q, recs in enumerate(lists):
+            ids[q, : len(recs)] = [int(r["doc_id"]) for r in recs]
+            rel[q, : len(recs)] = [r["stage3_score"] for r in recs]
+        _, picked = index.mmr(ids, rel, k, lam)
+        picked = picked.cpu().numpy() if hasattr(picked, "cpu") else np.asarray(picked)
+        for o, recs, row in zip(outs, lists, picked):
+            by_id = {int(r["doc_id"]): r for r in recs}
+            o["results"] = [by_id[int(i)] for i in row if int(i) >= 0]
+        return outs
+
+    def search(self, query: str, top_k: Optional[int] = None, filter=None, mmr_lambda=None) -> Dict[str, Any]:
         """``filter``: search only the documents it allows (Stage1Retriever.filter_mask: a metadata dict, a
         callable, document indices or a bool array).  Stages 2 and 3 rescore stage 1's candidates, so fewer
-        than ``top_k`` results come back when fewer documents are allowed, and none when none are."""
+        than ``top_k`` results come back when fewer documents are allowed, and none when none are.
+        ``mmr_lambda`` (default: the config's, None = off): stages 1 to 3 run as without it, then ``top_k`` of the
+        records stage 3 returned are picked by maximal marginal relevance (see :meth:`_diversify`) and come back in
+        selection order with the keys and scores they have anyway."""
         if not self.stage1 or not self.stage2 or not self.stage3:
             self.initialize_stages()
         top_k = top_k or self.config.stage3_top_k
+        lam = self._mmr_lambda(mmr_lambda)
+        if lam is not None:
+            return self._diversify([self.search(query, _ALL_RESULTS, filter=filter, mmr_lambda=_NO_MMR)], top_k, lam)[0]
         if self.config.search_on_arrays and filter is None:
             # one query through the array path of search_many (resident token store + stage-3 id cache): no candidate
             # text is tokenised or re-encoded, one cross-encoder forward for the query's pairs; same records (tests)
@@ -329,17 +380,21 @@ class RetrievalPipeline:
             self.logger.error(f"Error during search: {e}")
             raise
 
-    def batch_search(self, queries: List[str], top_k: Optional[int] = None, filter=None) -> List[Dict[str, Any]]:
+    def batch_search(self, queries: List[str], top_k: Optional[int] = None, filter=None,
+                     mmr_lambda=None) -> List[Dict[str, Any]]:
         """Sequential, like the reference (:444-448); see search_many for the batched form.  ``filter``: one
-        filter for every query or a list with one per query."""
+        filter for every query or a list with one per query.  ``mmr_lambda``: as for :meth:`search`."""
         if filter is None:
-            return [self.search(q, top_k) for q in queries]
+            if mmr_lambda is None:
+                return [self.search(q, top_k) for q in queries]
+            return [self.search(q, top_k, mmr_lambda=mmr_lambda) for q in queries]
         if not self.stage1:
             self.initialize_stages()
         specs = self.stage1._per_query_filters(filter, len(queries))
-        return [self.search(q, top_k, filter=f) for q, f in zip(queries, specs)]
+        return [self.search(q, top_k, filter=f, mmr_lambda=mmr_lambda) for q, f in zip(queries, specs)]
 
-    def search_many(self, queries: List[str], top_k: Optional[int] = None, filter=None) -> List[Dict[str, Any]]:
+    def search_many(self, queries: List[str], top_k: Optional[int] = None, filter=None,
+                    mmr_lambda=None) -> List[Dict[str, Any]]:
         """Same result records as batch_search, every stage batched over the queries: one
         bi-encoder pass and one sweep of the corpus per 64 queries (stage 1), one query forward
         and one MaxSim launch (stage 2, with the resident token store), one length-sorted pass
@@ -351,6 +406,9 @@ class RetrievalPipeline:
         top_k = top_k or self.config.stage3_top_k
         if not queries:
             return []
+        lam = self._mmr_lambda(mmr_lambda)
+        if lam is not None:   # (mmr_lambda: as for search(); one selection call for the batch)
+            return self._diversify(self.search_many(queries, _ALL_RESULTS, filter=filter, mmr_lambda=_NO_MMR), top_k, lam)
         queries = list(queries)
         n = len(queries)
         # a batch builds ~n x stage1_top_k candidate records; the cyclic collector would rescan

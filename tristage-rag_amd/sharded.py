@@ -105,6 +105,12 @@ class ShardedFlatIPIndex:
     def range_search(self, q, radius, allowed=None, max_results=None, sort: bool = False):
         raise NotImplementedError("range search is not supported on a row-sharded index")
 
+    def mmr(self, ids, relevance, k: int, lambda_mult: float = 0.5):
+        raise NotImplementedError("MMR is not supported on a row-sharded index (the candidates' rows live on several ranks)")
+
+    def search_mmr(self, q, k: int, fetch_k=None, lambda_mult: float = 0.5, allowed=None):
+        raise NotImplementedError("MMR is not supported on a row-sharded index (the candidates' rows live on several ranks)")
+
     def search(self, q, k: int, async_: bool = False, inputs_ready: bool = False, allowed=None):
         """Global top-k for the replicated query batch `q` (tensor).  Returns
         tensors (D float32 [B,k], I int64 [B,k]) identical on every rank.

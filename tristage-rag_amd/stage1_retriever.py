@@ -69,6 +69,8 @@ class Stage1Config:
     use_hip_graph: bool = False  # replay single-query encoder forwards from HIP graphs
     bm25_refit_compat: bool = False  # BM25 statistics after a SECOND add_documents exactly as the reference computes them
                                      # (its fit() appends to the previous fit's lists; see BM25Index)
+    mmr_lambda: Optional[float] = None  # None: off.  0 .. 1: search / search_many diversify the dense candidates by maximal
+                                        # marginal relevance (top_k picks out of min(1024, 4 top_k) fetched; dense-only route)
 
 
 def amp_torch_dtype(name: str):
@@ -805,6 +807,29 @@ class Stage1Retriever:
         same = all(a is allowed[0] for a in allowed)
         return self.faiss_index.search(q, top_k, allowed=allowed[0] if same else allowed)
 
+    # -- diversified dense search (MMR) ------------------------
+    def _mmr_lambda(self, mmr_lambda) -> Optional[float]:
+        """The lambda of a search (the argument, else the config); None: no diversification."""
+        lam = self.config.mmr_lambda if mmr_lambda is None else mmr_lambda
+        if lam is None:
+            return None
+        lam = float(lam)
+        if not 0.0 <= lam <= 1.0:
+            raise ValueError(f"mmr_lambda must be in [0, 1], got {mmr_lambda!r}")
+        if self.config.enable_bm25 and self.bm25_index is not None:
+            raise ValueError("mmr_lambda applies to the dense-only route: BM25 fusion is on (enable_bm25)")
+        if self.faiss_index is not None and not hasattr(self.faiss_index, "mmr"):
+            raise NotImplementedError(f"{type(self.faiss_index).__name__} has no mmr()")
+        return lam
+
+    def _dense_search_mmr(self, q, top_k: int, lam: float, masks, filters):
+        """top_k picks by maximal marginal relevance out of the min(1024, 4 top_k) best dense candidates, selected on
+        the GPU behind the search, on its stream."""
+        from .index import MMR_MAX_FETCH, mmr_check
+        top_k, fetch, lam = mmr_check(top_k, min(MMR_MAX_FETCH, 4 * int(top_k)), lam)
+        D, I = self._dense_search(q, fetch, masks, filters)
+        return self.faiss_index.mmr(I, D, top_k, lam)
+
     # -- fusion ------------------------------------------------------------
     def _reciprocal_rank_fusion(self, dense_results, bm25_results):
         """reference :326-343"""
@@ -913,42 +938,53 @@ class Stage1Retriever:
                         for i, s in zip(ids, scores) if 0 <= int(i) < len(self.documents)])
         return out[0] if single else out
 
-    def search(self, query: str, top_k: Optional[int] = None, filter=None) -> List[Dict[str, Any]]:
+    def search(self, query: str, top_k: Optional[int] = None, filter=None,
+               mmr_lambda: Optional[float] = None) -> List[Dict[str, Any]]:
         """``filter``: restrict the candidates to some documents (see :meth:`filter_mask`); fewer than
-        ``top_k`` results when fewer documents are allowed, none when none are."""
+        ``top_k`` results when fewer documents are allowed, none when none are.
+        ``mmr_lambda`` (default: the config's, None = off): the ``top_k`` records are picked by maximal marginal
+        relevance out of the ``min(1024, 4 top_k)`` best dense candidates and come back in selection order, with their
+        dense scores; 1.0 is the plain result.  Dense-only: ``ValueError`` while BM25 fusion is on."""
         if self.faiss_index is None:
             raise ValueError("No documents indexed. Call add_documents() first.")
         top_k = top_k or self.config.top_k_candidates
+        lam = self._mmr_lambda(mmr_lambda)
         masks = self._filter_masks(filter, 1)
         if masks is not None and not masks[0].any():
             return []
+        dense_search = self._dense_search if lam is None else (
+            lambda q_, k_, m_, f_: self._dense_search_mmr(q_, k_, lam, m_, f_))
         if self._device_path():
-            D, I = self._dense_search(self._normalized_query_tensor([query]), top_k, masks, filter)
+            D, I = dense_search(self._normalized_query_tensor([query]), top_k, masks, filter)
             scores, ids = D.cpu().numpy(), I.cpu().numpy()
         else:
             q = self._normalize_embeddings(self._encode_batch([query]))
-            scores, ids = self._dense_search(q, top_k, masks, filter)
+            scores, ids = dense_search(q, top_k, masks, filter)
         dense = [(int(i), float(s)) for i, s in zip(ids[0], scores[0]) if i >= 0]
         results = self._finish(query, dense, top_k, None if masks is None else masks[0])
         self.logger.info(f"Stage 1 search completed. Found {len(results)} candidates")
         return results
 
-    def search_many(self, queries: Sequence[str], top_k: Optional[int] = None, filter=None) -> List[List[Dict[str, Any]]]:
+    def search_many(self, queries: Sequence[str], top_k: Optional[int] = None, filter=None,
+                    mmr_lambda: Optional[float] = None) -> List[List[Dict[str, Any]]]:
         """All queries through ONE encoder pass and ONE index call (64 queries share a
         single sweep over the corpus on the GPU).  ``filter``: one filter for every query, or a list with one
-        per query (None: unfiltered)."""
+        per query (None: unfiltered).  ``mmr_lambda``: as for :meth:`search`, one selection call for the batch."""
         if self.faiss_index is None:
             raise ValueError("No documents indexed. Call add_documents() first.")
         top_k = top_k or self.config.top_k_candidates
+        lam = self._mmr_lambda(mmr_lambda)
         if not queries:
             return []
         masks = self._filter_masks(filter, len(queries))
+        dense_search = self._dense_search if lam is None else (
+            lambda q_, k_, m_, f_: self._dense_search_mmr(q_, k_, lam, m_, f_))
         if self._device_path():
-            D, I = self._dense_search(self._normalized_query_tensor(list(queries)), top_k, masks, filter)
+            D, I = dense_search(self._normalized_query_tensor(list(queries)), top_k, masks, filter)
             scores, ids = D.cpu().numpy(), I.cpu().numpy()
         else:
             q = self._normalize_embeddings(self._encode_batch(list(queries)))
-            scores, ids = self._dense_search(q, top_k, masks, filter)
+            scores, ids = dense_search(q, top_k, masks, filter)
         out = []
         for qi, query in enumerate(queries):
             m = None if masks is None else masks[qi]
@@ -972,6 +1008,8 @@ class Stage1Retriever:
         top_k = top_k or self.config.top_k_candidates
         n = int(self.faiss_index.ntotal)
         if top_k > n or n != len(self.documents):
+            return None
+        if self.config.mmr_lambda is not None:   # a diversified stage 1 goes through search_many
             return None
         masks = self._filter_masks(filter, len(queries))
         if masks is not None:
