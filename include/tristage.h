@@ -60,7 +60,7 @@ extern "C" {
  * TS_FP8_E4M3; ts_index_set_fp8_scale_log2, ts_index_fp8_scale_log2): no existing signature changed, and an index of
  * another storage dtype runs the kernels it ran before.  So were ts_index_mmr, ts_mmr_ivf and the measurement aid
  * ts_index_mmr_set_timing / ts_index_mmr_get_timings: no existing signature or kernel changed, and a caller that
- * never calls them allocates and launches nothing new.                                                          */
+ * never calls them allocates and launches nothing new.  So was ts_group_topk, on the same terms.                 */
 #define TS_ABI_VERSION 4
 
 typedef struct ts_index ts_index; /* opaque */
@@ -428,6 +428,41 @@ int ts_merge_topk_strided(const float* scores, const int64_t* ids, int32_t nlist
                           int32_t nq, int32_t k, int64_t score_list_stride,
                           int64_t id_list_stride, float* out_scores, int64_t* out_ids,
                           int32_t device, void* stream);
+
+/* ---- grouped search: top-k distinct groups of a ranked list ----
+ * Reference call site: none (the reference returns the plain top-k of overlapping chunks, src/utils.py chunk_text);
+ * what Milvus calls grouping search and Elasticsearch collapse.  Added within version 4: no existing signature or
+ * kernel changed, and a caller that never calls it allocates and launches nothing new.  Stateless, like ts_merge_topk.
+ * Per query: a candidate list of ncand entries, cand_ids [nq, ncand] int64 (-1 = padding) and cand_scores [nq, ncand]
+ * float32, in rank order: the scores are carried, never compared.  groups [n_rows] int32 is shared by all queries;
+ * entry `id` belongs to row id - id_base.
+ *   valid      an entry with id != -1 and 0 <= id - id_base < n_rows.  Its group is groups[id - id_base]; a negative
+ *              table value means "no group": the entry is a group of its own.
+ *   selection  walking the list in position order, occ(i) = earlier valid entries of i's group, rank(i) = distinct
+ *              groups whose first entry comes before the first entry of i's group; entry i is kept iff rank(i) < k and
+ *              occ(i) < group_size.  An id that occurs twice counts twice.
+ *   outputs    [nq, k * group_size]: out_scores, out_ids and out_groups (-1 for an entry without a group) of the kept
+ *              entries in ascending list position (for a list ts_index_search returned: still in score order), then
+ *              -FLT_MAX / -1 / -1.  out_ngroups [nq]: the distinct groups among ALL valid entries of the list (not
+ *              capped at k); out_nvalid [nq]: its valid entries.
+ * 1 <= ncand <= 16384, k >= 1, group_size >= 1, k * group_size <= 16384; k > ncand is allowed (the rest is padding).
+ * The result depends neither on the run nor on nq.  With group_size > 1 over a list cut at ncand places, a group's
+ * entries are its best WITHIN the list (the non-strict group size of Milvus): a later entry of the group that the
+ * list does not hold cannot be returned.
+ * All pointers, `groups` included, are device memory: the call enqueues one kernel (one workgroup per query, the
+ * list sorted by (group, position) in LDS) on `stream` and returns, so it chains behind a ts_index_search on the
+ * same stream without a synchronisation.  With TS_FLAG_HOST_PTR they are all host memory, staged through one device
+ * allocation that is freed before the call returns, and the call is synchronous.
+ * TS_ERR_INVALID: a null pointer, nq < 0, ncand < 1, k < 1, group_size < 1, n_rows < 0, and with TS_FLAG_HOST_PTR an
+ * id other than -1 outside [id_base, id_base + n_rows) (nothing is written).  Device ids cannot be read without a
+ * synchronisation: there such an id is range-checked on the device, never used as an index, and skipped like
+ * padding (the convention of ts_index_mmr).  TS_ERR_UNSUPPORTED: ncand or k * group_size above 16384.  Both before
+ * any HIP call, with a message in ts_last_error().  nq == 0 is TS_OK.                                            */
+int ts_group_topk(const int64_t* cand_ids, const float* cand_scores, int32_t nq, int32_t ncand,
+                  const int32_t* groups, int64_t n_rows, int64_t id_base, int32_t k, int32_t group_size,
+                  float* out_scores, int64_t* out_ids, int32_t* out_groups,
+                  int32_t* out_ngroups, int32_t* out_nvalid,
+                  uint32_t flags, int32_t device, void* stream);
 
 /* ---- stage-2 MaxSim ------------------------------------------------------
  * replaces ColBERTScorer._maxsim_score / _colbert_score applied per candidate

@@ -103,6 +103,8 @@ SIGNATURES = {
                                 c_int32, c_void_p]),
     "ts_merge_topk_strided": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int64, c_int64,
                                         c_void_p, c_void_p, c_int32, c_void_p]),
+    "ts_group_topk": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int64, c_int64, c_int32, c_int32,
+                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_int32, c_void_p]),
     "ts_maxsim": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32,
                             c_int32, c_void_p, c_int32, c_void_p]),
     "ts_maxsim_indexed": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_int32,

@@ -163,6 +163,134 @@ def _mmr_call(ix, entry: str, ids, relevance, k, lambda_mult):
     return D, I
 
 
+GROUP_MAX_FETCH = 16384   # entries per query of group_topk(): one workgroup sorts the list in LDS (the select limit)
+
+
+def group_default_fetch_k(k: int, group_size: int = 1) -> int:
+    """Candidates ``search_grouped`` fetches in its first round when ``fetch_k`` is not given."""
+    return min(GROUP_MAX_FETCH, max(4 * int(k) * int(group_size), 64))
+
+
+def group_check(k, group_size, ncand):
+    """The argument checks of ``group_topk`` / ``search_grouped`` (``ValueError``), made before anything is launched."""
+    k, group_size, ncand = int(k), int(group_size), int(ncand)
+    if k < 1:
+        raise ValueError("k must be positive")
+    if group_size < 1:
+        raise ValueError("group_size must be positive")
+    if k * group_size > GROUP_MAX_FETCH:
+        raise ValueError(f"k * group_size = {k * group_size} exceeds {GROUP_MAX_FETCH}")
+    if ncand < 1:
+        raise ValueError("the candidate lists must hold at least one entry")
+    if ncand > GROUP_MAX_FETCH:
+        raise ValueError(f"{ncand} candidates per query exceed {GROUP_MAX_FETCH}")
+    return k, group_size, ncand
+
+
+def group_topk(ids, scores, groups, k: int, group_size: int = 1, id_base: int = 0):
+    """Collapse ranked candidate lists to their first ``k`` distinct groups, at most ``group_size`` entries of each
+    (ts_group_topk).  ``ids`` [B, C] int64 (-1 = padding) and ``scores`` [B, C] in rank order (the
+    scores are carried, never compared); ``groups`` int32, one entry per row, entry ``id`` belonging to row
+    ``id - id_base``; a negative table value makes the entry a group of its own.  Walking a list in position order an
+    entry is kept iff fewer than ``k`` distinct groups started before its group did and fewer than ``group_size``
+    earlier entries share its group.  Returns ``(D, I, G, n_groups, n_valid)``: scores, ids and groups [B, k *
+    group_size] of the kept entries in list order, -FLT_MAX / -1 / -1 padded; the distinct groups among ALL valid
+    entries of each list (not capped at ``k``) and its valid entries, int32 [B].
+    CUDA tensors in -> tensors out, enqueued on the current stream (no synchronisation; an id outside the table is
+    skipped like padding); anything else goes through host pointers and comes back as numpy (such an id is a
+    ``ValueError``)."""
+    lib = _lib.load()
+    if _is_tensor(ids) and ids.is_cuda:
+        torch = _torch()
+        if ids.dim() != 2 or tuple(scores.shape) != tuple(ids.shape):
+            raise ValueError(f"expected ids and scores of one shape [B, C], got {tuple(ids.shape)} and "
+                             f"{tuple(scores.shape)}")
+        k, group_size, C = group_check(k, group_size, ids.shape[1])
+        device = ids.device.index
+        ids = ids.to(torch.int64).contiguous()
+        sc = torch.as_tensor(scores, device=ids.device).to(torch.float32).contiguous()
+        tab = torch.as_tensor(groups, device=ids.device)
+        if tab.dim() != 1:
+            raise ValueError(f"expected a one-dimensional group table, got shape {tuple(tab.shape)}")
+        tab = tab.to(torch.int32).contiguous()
+        B, W = ids.shape[0], k * group_size
+        D = torch.empty((B, W), dtype=torch.float32, device=ids.device)
+        I = torch.empty((B, W), dtype=torch.int64, device=ids.device)
+        G = torch.empty((B, W), dtype=torch.int32, device=ids.device)
+        ng = torch.empty((B,), dtype=torch.int32, device=ids.device)
+        nv = torch.empty((B,), dtype=torch.int32, device=ids.device)
+        if tab.shape[0] == 0:   # (an empty tensor has no address: every entry is then invalid, nothing is read)
+            tab = torch.zeros((1,), dtype=torch.int32, device=ids.device)
+            n_rows = 0
+        else:
+            n_rows = tab.shape[0]
+        ptr = [ctypes.c_void_p(t.data_ptr()) for t in (ids, sc, tab, D, I, G, ng, nv)]
+        flags, stream = 0, ctypes.c_void_p(_stream_ptr(device))
+    else:
+        if _is_tensor(ids):
+            ids = ids.detach().cpu().numpy()
+        if _is_tensor(scores):
+            scores = scores.detach().cpu().numpy()
+        if _is_tensor(groups):
+            groups = groups.detach().cpu().numpy()
+        ids = np.ascontiguousarray(ids, dtype=np.int64)
+        sc = np.ascontiguousarray(scores, dtype=np.float32)
+        if ids.ndim != 2 or sc.shape != ids.shape:
+            raise ValueError(f"expected ids and scores of one shape [B, C], got {ids.shape} and {sc.shape}")
+        k, group_size, C = group_check(k, group_size, ids.shape[1])
+        tab = np.asarray(groups)
+        if tab.ndim != 1:
+            raise ValueError(f"expected a one-dimensional group table, got shape {tab.shape}")
+        n_rows = tab.shape[0]
+        tab = np.ascontiguousarray(tab if n_rows else np.zeros(1), dtype=np.int32)
+        B, W = ids.shape[0], k * group_size
+        D = np.empty((B, W), dtype=np.float32)
+        I = np.empty((B, W), dtype=np.int64)
+        G = np.empty((B, W), dtype=np.int32)
+        ng = np.empty((B,), dtype=np.int32)
+        nv = np.empty((B,), dtype=np.int32)
+        ptr = [a.ctypes.data_as(ctypes.c_void_p) for a in (ids, sc, tab, D, I, G, ng, nv)]
+        device, flags, stream = 0, _lib.TS_FLAG_HOST_PTR, None
+    code = lib.ts_group_topk(ptr[0], ptr[1], B, C, ptr[2], n_rows, int(id_base), k, group_size, ptr[3], ptr[4], ptr[5],
+                             ptr[6], ptr[7], flags, device, stream)
+    if code == _lib.TS_ERR_INVALID:
+        raise ValueError(_lib.last_error())
+    _lib.check(code)
+    return D, I, G, ng, nv
+
+
+def grouped_search(ix, search, q, k, groups, group_size=1, fetch_k=None):
+    """``search_grouped`` of both index classes (and of Stage1Retriever, whose ``search`` carries its filters):
+    ``search(q, fetch) -> (D, I)`` is a plain search of ``ix`` with the caller's filter or probe count bound in."""
+    n_tab = groups.shape[0] if hasattr(groups, "shape") and len(groups.shape) == 1 else None
+    if n_tab is None:
+        groups = np.asarray(groups)
+        if groups.ndim != 1:
+            raise ValueError(f"expected a one-dimensional group table, got shape {groups.shape}")
+        n_tab = groups.shape[0]
+    if n_tab != ix.ntotal:
+        raise ValueError(f"the group table has {n_tab} entries, the index {ix.ntotal} rows")
+    fetch = group_default_fetch_k(k, group_size) if fetch_k is None else int(fetch_k)
+    k, group_size, fetch = group_check(k, group_size, fetch)
+    if _is_tensor(q) and q.is_cuda:   # one upload for every round of the call (a device table is used as it is)
+        torch = _torch()
+        groups = torch.as_tensor(groups, device=q.device).to(torch.int32)
+    rounds = 0
+    while True:
+        D, I = search(q, fetch)
+        D, I, G, ng, nv = group_topk(I, D, groups, k, group_size, id_base=int(getattr(ix, "_id_offset", 0)))
+        rounds += 1
+        # the call's one host synchronisation per round: both count arrays
+        ng_h = ng.cpu().numpy() if _is_tensor(ng) else ng
+        nv_h = nv.cpu().numpy() if _is_tensor(nv) else nv
+        short = (ng_h < k) & (nv_h == fetch)   # too few groups in a list that was full: rows may lie behind it
+        if not short.any() or fetch >= GROUP_MAX_FETCH:
+            break
+        fetch = min(GROUP_MAX_FETCH, 4 * fetch)
+    ix._group_info = {"fetched": fetch, "rounds": rounds, "n_groups": ng_h.copy(), "complete": ~short}
+    return D, I, G
+
+
 class RangeSearchLimitError(RuntimeError):
     """A range search would return more entries than ``max_results`` allows; the message names both numbers.
     ``counts``: results per query as far as the search got (zero behind that)."""
@@ -882,6 +1010,28 @@ class FlatIPIndex:
         k, fetch_k, lam = mmr_check(k, mmr_default_fetch_k(k) if fetch_k is None else fetch_k, lambda_mult)
         D, I = self.search(q, fetch_k, allowed=allowed)
         return self.mmr(I, D, k, lam)
+
+    # -- grouped search --------------------------------------
+    def search_grouped(self, q, k: int, groups, group_size: int = 1, fetch_k: Optional[int] = None, allowed=None):
+        """``search(q, fetch)`` followed by :func:`group_topk` on the same stream: per query the ``k`` best distinct
+        groups, at most ``group_size`` rows of each, as ``(D, I, G)`` [B, k * group_size] in ``search``'s canonical order
+        (-FLT_MAX / -1 / -1 padded).  ``groups``: int32, one entry per row of the index (``ntotal``; a negative value
+        makes the row a group of its own), indexed by row: the index's id offset is taken off the ids.
+        ``fetch`` starts at ``fetch_k``, by default ``min(16384, max(4 k group_size, 64))``.  After each round the two
+        count arrays are read (the call's one host synchronisation per round); while some query found fewer than ``k``
+        groups in a list that came back full and ``fetch < 16384``, ``fetch`` is multiplied by four and the whole
+        batch is redone, so every query of a call is collapsed over the same final fetch.  :meth:`last_group_info`
+        reports ``fetched``, ``rounds``, ``n_groups`` and ``complete`` (per query: ``k`` groups were found or the list
+        was exhaustive); an incomplete query is reported there, not raised.
+        ``group_size == 1``: for a complete query the result is exactly the ``k`` groups with the best best-row, in the
+        order of those rows, each represented by that row.  ``group_size > 1``: a group's rows are its best rows WITHIN
+        THE FIRST ``fetched`` PLACES (the non-strict group size of Milvus): a further row of a returned group that
+        ranks behind place ``fetched`` is not returned."""
+        return grouped_search(self, lambda x, f: self.search(x, f, allowed=allowed), q, k, groups, group_size, fetch_k)
+
+    def last_group_info(self) -> dict:
+        """``{"fetched", "rounds", "n_groups", "complete"}`` of the last :meth:`search_grouped` (the last two per query)."""
+        return dict(getattr(self, "_group_info", {}))
 
     def reconstruct_n(self, i0: int = 0, n: Optional[int] = None) -> np.ndarray:
         """Rows [i0, i0+n) as float32 (after storage rounding)."""
@@ -1673,6 +1823,16 @@ class IVFFlatIndex:
         k, fetch_k, lam = mmr_check(k, mmr_default_fetch_k(k) if fetch_k is None else fetch_k, lambda_mult)
         D, I = self.search(q, fetch_k, nprobe=nprobe)
         return self.mmr(I, D, k, lam)
+
+    def search_grouped(self, q, k: int, groups, group_size: int = 1, fetch_k: Optional[int] = None,
+                       nprobe: Optional[int] = None):
+        """:meth:`FlatIPIndex.search_grouped` over ``search(q, fetch, nprobe=nprobe)``: the rows a query can reach are
+        those of its probed lists, and a list is exhaustive when it holds all of them."""
+        return grouped_search(self, lambda x, f: self.search(x, f, nprobe=nprobe), q, k, groups, group_size, fetch_k)
+
+    def last_group_info(self) -> dict:
+        """``{"fetched", "rounds", "n_groups", "complete"}`` of the last :meth:`search_grouped`."""
+        return dict(getattr(self, "_group_info", {}))
 
     def finish(self):
         """Asynchronous searches complete synchronously here: nothing is pending, no ticket failed."""

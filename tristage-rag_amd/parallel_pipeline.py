@@ -202,6 +202,10 @@ class ShardedRetrievalPipeline(RetrievalPipeline):
         if mmr_lambda is not None or getattr(getattr(self, "config", None), "mmr_lambda", None) is not None:
             raise NotImplementedError("mmr_lambda is not supported by the row-sharded pipeline")
 
+    def _refuse_group(self, group_by) -> None:
+        if group_by is not None or getattr(getattr(self, "config", None), "group_by", None) is not None:
+            raise NotImplementedError("group_by is not supported by the row-sharded pipeline")
+
     # -- collectives -------------------------------------------------------------
     def _host_staged(self) -> bool:
         return self.world_size > 1 and self._dist.get_backend(self.group) == "gloo"
@@ -346,10 +350,12 @@ class ShardedRetrievalPipeline(RetrievalPipeline):
                     if isinstance(r, dict) and r.get("document") is None and int(r["doc_id"]) in have:
                         r["document"], r["metadata"] = have[int(r["doc_id"])]
 
-    def search(self, query: str, top_k: Optional[int] = None, filter=None, mmr_lambda=None) -> Dict[str, Any]:
+    def search(self, query: str, top_k: Optional[int] = None, filter=None, mmr_lambda=None,
+               group_by=None, group_size: int = 1) -> Dict[str, Any]:
         if filter is not None:
             raise NotImplementedError(FILTER_UNSUPPORTED)
         self._refuse_mmr(mmr_lambda)
+        self._refuse_group(group_by)
         if self.world_size == 1:
             return super().search(query, top_k)
         if self.config.search_on_arrays and self._arrays_agreed():
@@ -422,13 +428,14 @@ class ShardedRetrievalPipeline(RetrievalPipeline):
         return out + (self._span(ma, mb), self._span(mb, mc))
 
     def search_many(self, queries: List[str], top_k: Optional[int] = None, filter=None,
-                    mmr_lambda=None) -> List[Dict[str, Any]]:
+                    mmr_lambda=None, group_by=None, group_size: int = 1) -> List[Dict[str, Any]]:
         """Batched search over R ranks; every rank returns every query's records.  Array path (token store + id
         cache on the shards): three collectives per call besides stage 1's — two all-reduces of small score matrices
         and one gather of the returned texts.  Otherwise the per-record path, query by query."""
         if filter is not None:
             raise NotImplementedError(FILTER_UNSUPPORTED)
         self._refuse_mmr(mmr_lambda)
+        self._refuse_group(group_by)
         if self.world_size == 1:
             return super().search_many(queries, top_k)
         if not self.stage1 or not self.stage2 or not self.stage3:

@@ -89,6 +89,9 @@ class PipelineConfig:
     stage3_many_packed_batch_size: int = 4096  # ... when the batch is packed (written-out forward on the GPU): no padding to pay
     mmr_lambda: Optional[float] = None       # None: off.  0 .. 1: the list stage 3 returns is diversified by maximal marginal
                                              # relevance (relevance = stage3_score, similarity from the stage-1 index)
+    group_by: Any = None                     # None: off.  A metadata key or an integer array over the documents: stage 1
+                                             # returns the stage1_top_k best GROUPS, at most group_size documents of each, so
+    group_size: int = 1                      # stages 2 and 3 and the final list see no more of any group
 
 
 # (section, key) in the reference's YAML layout -> PipelineConfig field (reference :182-217)
@@ -323,6 +326,18 @@ class RetrievalPipeline:
             raise ValueError(f"mmr_lambda must be in [0, 1], got {mmr_lambda!r}")
         return lam
 
+    def _group_kwargs(self, group_by, group_size, lam) -> Dict[str, Any]:
+        """The grouping of a search as keyword arguments for stage 1 (the arguments, else the config); {}: off."""
+        if group_by is None:
+            group_by, group_size = self.config.group_by, self.config.group_size
+        if group_by is None:
+            return {}
+        if lam is not None:
+            raise ValueError("group_by cannot be combined with mmr_lambda: pick one way to thin out near-copies")
+        if int(group_size) < 1:
+            raise ValueError(f"group_size must be positive, got {group_size}")
+        return {"group_by": group_by, "group_size": int(group_size)}
+
     def _diversify(self, outs: List[Dict[str, Any]], top_k: int, lam: float) -> List[Dict[str, Any]]:
         """``results`` of each output (the whole list stage 3 returned) -> its ``top_k`` picks by maximal marginal
         relevance, in selection order: relevance = stage3_score as f32, similarity = the inner product of the rows the
@@ -348,32 +363,38 @@ class RetrievalPipeline:
             o["results"] = [by_id[int(i)] for i in row if int(i) >= 0]
         return outs
 
-    def search(self, query: str, top_k: Optional[int] = None, filter=None, mmr_lambda=None) -> Dict[str, Any]:
+    def search(self, query: str, top_k: Optional[int] = None, filter=None, mmr_lambda=None,
+               group_by=None, group_size: int = 1) -> Dict[str, Any]:
         """``filter``: search only the documents it allows (Stage1Retriever.filter_mask: a metadata dict, a
         callable, document indices or a bool array).  Stages 2 and 3 rescore stage 1's candidates, so fewer
         than ``top_k`` results come back when fewer documents are allowed, and none when none are.
         ``mmr_lambda`` (default: the config's, None = off): stages 1 to 3 run as without it, then ``top_k`` of the
         records stage 3 returned are picked by maximal marginal relevance (see :meth:`_diversify`) and come back in
-        selection order with the keys and scores they have anyway."""
+        selection order with the keys and scores they have anyway.
+        ``group_by`` / ``group_size`` (default: the config's, None = off): the collapse is applied at stage 1
+        (Stage1Retriever.search), where ``stage1_top_k`` then counts groups: stages 2 and 3 see at most ``group_size``
+        documents of any group, and so does the final list.  Dense-only and not together with ``mmr_lambda``:
+        ``ValueError``."""
         if not self.stage1 or not self.stage2 or not self.stage3:
             self.initialize_stages()
         top_k = top_k or self.config.stage3_top_k
         lam = self._mmr_lambda(mmr_lambda)
+        gkw = self._group_kwargs(group_by, group_size, lam)
         if lam is not None:
             return self._diversify([self.search(query, _ALL_RESULTS, filter=filter, mmr_lambda=_NO_MMR)], top_k, lam)[0]
         if self.config.search_on_arrays and filter is None:
             # one query through the array path of search_many (resident token store + stage-3 id cache): no candidate
             # text is tokenised or re-encoded, one cross-encoder forward for the query's pairs; same records (tests)
-            fast = self._search_many_arrays([query], top_k)
+            fast = self._search_many_arrays([query], top_k, **gkw)
             if fast is not None:
                 return fast[0]
         total_start = self._now()
         try:
             t = self._now()
             if filter is None:
-                stage1_results = self.stage1.search(query, self.config.stage1_top_k)
+                stage1_results = self.stage1.search(query, self.config.stage1_top_k, **gkw)
             else:
-                stage1_results = self.stage1.search(query, self.config.stage1_top_k, filter=filter)
+                stage1_results = self.stage1.search(query, self.config.stage1_top_k, filter=filter, **gkw)
             stage1_time = time.time() - t if t else None
             return self._run_later_stages(query, top_k, stage1_results, total_start, stage1_time)
         except Exception as e:
@@ -381,32 +402,36 @@ class RetrievalPipeline:
             raise
 
     def batch_search(self, queries: List[str], top_k: Optional[int] = None, filter=None,
-                     mmr_lambda=None) -> List[Dict[str, Any]]:
+                     mmr_lambda=None, group_by=None, group_size: int = 1) -> List[Dict[str, Any]]:
         """Sequential, like the reference (:444-448); see search_many for the batched form.  ``filter``: one
-        filter for every query or a list with one per query.  ``mmr_lambda``: as for :meth:`search`."""
+        filter for every query or a list with one per query.  ``mmr_lambda``, ``group_by`` / ``group_size``: as for
+        :meth:`search`."""
+        gkw = {} if group_by is None else {"group_by": group_by, "group_size": group_size}
         if filter is None:
             if mmr_lambda is None:
-                return [self.search(q, top_k) for q in queries]
-            return [self.search(q, top_k, mmr_lambda=mmr_lambda) for q in queries]
+                return [self.search(q, top_k, **gkw) for q in queries]
+            return [self.search(q, top_k, mmr_lambda=mmr_lambda, **gkw) for q in queries]
         if not self.stage1:
             self.initialize_stages()
         specs = self.stage1._per_query_filters(filter, len(queries))
-        return [self.search(q, top_k, filter=f, mmr_lambda=mmr_lambda) for q, f in zip(queries, specs)]
+        return [self.search(q, top_k, filter=f, mmr_lambda=mmr_lambda, **gkw) for q, f in zip(queries, specs)]
 
     def search_many(self, queries: List[str], top_k: Optional[int] = None, filter=None,
-                    mmr_lambda=None) -> List[Dict[str, Any]]:
+                    mmr_lambda=None, group_by=None, group_size: int = 1) -> List[Dict[str, Any]]:
         """Same result records as batch_search, every stage batched over the queries: one
         bi-encoder pass and one sweep of the corpus per 64 queries (stage 1), one query forward
         and one MaxSim launch (stage 2, with the resident token store), one length-sorted pass
         of the cross-encoder over all (query, candidate) pairs (stage 3).  Stage times are
         reported as equal shares of the batch's stage times.  ``filter``: one filter for every query or a list
-        with one per query (see :meth:`search`); a filtered batch takes the record path."""
+        with one per query (see :meth:`search`); a filtered batch takes the record path.  ``group_by`` /
+        ``group_size``: as for :meth:`search`, one collapse for the batch."""
         if not self.stage1 or not self.stage2 or not self.stage3:
             self.initialize_stages()
         top_k = top_k or self.config.stage3_top_k
         if not queries:
             return []
         lam = self._mmr_lambda(mmr_lambda)
+        gkw = self._group_kwargs(group_by, group_size, lam)
         if lam is not None:   # (mmr_lambda: as for search(); one selection call for the batch)
             return self._diversify(self.search_many(queries, _ALL_RESULTS, filter=filter, mmr_lambda=_NO_MMR), top_k, lam)
         queries = list(queries)
@@ -418,15 +443,15 @@ class RetrievalPipeline:
         gc.disable()
         try:
             if filter is None:
-                fast = self._search_many_arrays(queries, top_k)
+                fast = self._search_many_arrays(queries, top_k, **gkw)
                 if fast is not None:
                     return fast
             total_start = self._now()
             t = self._now()
             if filter is None:
-                s1 = self.stage1.search_many(queries, self.config.stage1_top_k)
+                s1 = self.stage1.search_many(queries, self.config.stage1_top_k, **gkw)
             else:
-                s1 = self.stage1.search_many(queries, self.config.stage1_top_k, filter=filter)
+                s1 = self.stage1.search_many(queries, self.config.stage1_top_k, filter=filter, **gkw)
             t1 = (time.time() - t) / n if t else None
             s2, s3, t2, t3 = self._later_stages_many(queries, s1)
             total = (time.time() - total_start) / n if total_start else None
@@ -435,7 +460,7 @@ class RetrievalPipeline:
             if gc_was_on:
                 gc.enable()
 
-    def _search_many_arrays(self, queries: List[str], top_k: int) -> Optional[List[Dict[str, Any]]]:
+    def _search_many_arrays(self, queries: List[str], top_k: int, **group) -> Optional[List[Dict[str, Any]]]:
         """search_many with every stage on ARRAYS (the candidate sets never become Python records): stage 1
         returns id / score matrices, stage 2 looks the candidates up in the resident token store and keeps the
         best by one stable device sort, stage 3 assembles its (query, document) inputs from cached token ids on
@@ -453,7 +478,7 @@ class RetrievalPipeline:
             if hasattr(st, "prefetch_queries"):
                 st.prefetch_queries(queries)
         mp = self._tick()
-        got = self._arrays_stage1(queries)
+        got = self._arrays_stage1(queries, **group)
         if got is None:
             return None
         ids1_dev, sc1 = got
@@ -502,10 +527,11 @@ class RetrievalPipeline:
         return bool(getattr(s2, "token_store", None) is not None and len(s2.token_store)
                     and getattr(s3, "_pairs_usable", False) and hasattr(s1, "search_many_arrays"))
 
-    def _arrays_stage1(self, queries: List[str]):
-        """-> (ids int64 [B, k] on the token store's device, scores [B, k] tensor or numpy) or None."""
+    def _arrays_stage1(self, queries: List[str], **group):
+        """-> (ids int64 [B, k] on the token store's device, scores [B, k] tensor or numpy) or None.  ``group``:
+        group_by / group_size of a grouped search (k is then stage1_top_k * group_size)."""
         import torch
-        got = self.stage1.search_many_arrays(queries, self.config.stage1_top_k)
+        got = self.stage1.search_many_arrays(queries, self.config.stage1_top_k, **group)
         if got is None:
             return None
         ids1, sc1 = got

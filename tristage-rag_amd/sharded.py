@@ -111,6 +111,9 @@ class ShardedFlatIPIndex:
     def search_mmr(self, q, k: int, fetch_k=None, lambda_mult: float = 0.5, allowed=None):
         raise NotImplementedError("MMR is not supported on a row-sharded index (the candidates' rows live on several ranks)")
 
+    def search_grouped(self, q, k: int, groups, group_size: int = 1, fetch_k=None, allowed=None):
+        raise NotImplementedError("grouped search is not supported on a row-sharded index (the collapse needs the merged list)")
+
     def search(self, q, k: int, async_: bool = False, inputs_ready: bool = False, allowed=None):
         """Global top-k for the replicated query batch `q` (tensor).  Returns
         tensors (D float32 [B,k], I int64 [B,k]) identical on every rank.

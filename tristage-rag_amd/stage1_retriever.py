@@ -71,6 +71,9 @@ class Stage1Config:
                                      # (its fit() appends to the previous fit's lists; see BM25Index)
     mmr_lambda: Optional[float] = None  # None: off.  0 .. 1: search / search_many diversify the dense candidates by maximal
                                         # marginal relevance (top_k picks out of min(1024, 4 top_k) fetched; dense-only route)
+    group_by: Any = None   # None: off.  A metadata key, or an integer array with one entry per document: search / search_many
+                           # return the top_k best GROUPS, at most group_size documents of each (dense-only)
+    group_size: int = 1
 
 
 def amp_torch_dtype(name: str):
@@ -396,6 +399,7 @@ class Stage1Retriever:
         # are dropped and rebuilt on first use.  Metadata is append-only in between (add_documents).
         self._kv_bitmaps: Dict[Any, np.ndarray] = {}
         self._mask_lru: "OrderedDict[Any, Any]" = OrderedDict()
+        self._group_tables: Dict[Any, Dict[str, Any]] = {}   # group_by keys: value codes and their device copy (same owner)
         self._filter_cache_meta = self.doc_metadata
         self.filter_cache_size = 8
         self._index_factory = index_factory
@@ -537,6 +541,7 @@ class Stage1Retriever:
     def _reset_filter_caches(self) -> None:
         self._kv_bitmaps.clear()
         self._mask_lru.clear()
+        self._group_tables = {}
         self._filter_cache_meta = self.doc_metadata
 
     def _check_filter_caches(self) -> None:
@@ -830,6 +835,90 @@ class Stage1Retriever:
         D, I = self._dense_search(q, fetch, masks, filters)
         return self.faiss_index.mmr(I, D, top_k, lam)
 
+    # -- grouped dense search ----------------------------------
+    def _group_args(self, group_by, group_size, lam=None):
+        """The grouping of a search: ``(group_by, group_size)`` from the arguments, else from the config; None: off."""
+        if group_by is None:
+            group_by, group_size = self.config.group_by, self.config.group_size
+        if group_by is None:
+            return None
+        group_size = int(group_size)
+        if group_size < 1:
+            raise ValueError(f"group_size must be positive, got {group_size}")
+        if lam is not None:
+            raise ValueError("group_by cannot be combined with mmr_lambda: pick one way to thin out near-copies")
+        if self.config.enable_bm25 and self.bm25_index is not None:
+            raise ValueError("group_by applies to the dense-only route: BM25 fusion is on (enable_bm25)")
+        if self.faiss_index is not None and not hasattr(self.faiss_index, "search_grouped"):
+            raise NotImplementedError(f"{type(self.faiss_index).__name__} has no search_grouped()")
+        return group_by, group_size
+
+    def _group_codes(self, key) -> np.ndarray:
+        """int32 [n_docs]: the value of metadata ``key`` coded in first-seen order, -1 for a document without the key.
+        Built once per key and extended by the documents added since; dropped with the filter caches when the
+        metadata list is replaced (remove + compact, update, load_index)."""
+        self._check_filter_caches()
+        tabs = self.__dict__.setdefault("_group_tables", {})
+        ent = tabs.get(key)
+        if ent is None:
+            ent = tabs[key] = {"map": {}, "codes": np.zeros(0, dtype=np.int32), "dev": None}
+        n = len(self.doc_metadata)
+        have = ent["codes"].shape[0]
+        if have > n:   # (a shorter corpus than the table: not the corpus it was built on)
+            ent["map"], ent["codes"], ent["dev"], have = {}, ent["codes"][:0], None, 0
+        if have < n:
+            codes, ext = ent["map"], np.empty(n - have, dtype=np.int32)
+            for j, md in enumerate(self.doc_metadata[have:]):
+                v = md.get(key, _MISSING) if hasattr(md, "get") else _MISSING
+                if v is _MISSING:
+                    ext[j] = -1
+                    continue
+                try:
+                    ext[j] = codes.setdefault(v, len(codes))
+                except TypeError:
+                    raise TypeError(f"group_by={key!r}: document {have + j} has the unhashable value {v!r}") from None
+            ent["codes"] = np.concatenate([ent["codes"][:have], ext])
+            ent["dev"] = None
+        return ent["codes"]
+
+    def _group_table(self, group_by, on_device: bool):
+        """The group table of a search: a metadata key's codes (with their cached device copy) or the caller's array."""
+        n = len(self.documents)
+        if isinstance(group_by, (np.ndarray, list, tuple)) or hasattr(group_by, "detach"):
+            arr = np.asarray(group_by.detach().cpu().numpy() if hasattr(group_by, "detach") else group_by)
+            if arr.shape != (n,) or not np.issubdtype(arr.dtype, np.integer):
+                raise ValueError(f"group_by: expected a metadata key or an integer array with one entry per document ({n}), "
+                                 f"got shape {arr.shape}, dtype {arr.dtype}")
+            if arr.size and (arr.max() > np.iinfo(np.int32).max or arr.min() < np.iinfo(np.int32).min):
+                raise ValueError("group_by: the group ids must fit 32 bits")
+            return arr.astype(np.int32)
+        codes = self._group_codes(group_by)
+        if not on_device:
+            return codes
+        ent = self._group_tables[group_by]
+        if ent["dev"] is None:
+            import torch
+            ent["dev"] = torch.from_numpy(codes).to(torch.device("cuda", self.config.gpu_index_device))
+        return ent["dev"]
+
+    def _dense_search_grouped(self, q, top_k: int, grp, masks, filters):
+        """The top_k best groups, at most group_size documents of each: _dense_search (filters and removed documents
+        as ever) collapsed on the GPU behind it, refetched while a query's list was full and held too few groups.
+        -> (D, I) [B, top_k * group_size], padded."""
+        from .index import grouped_search
+        group_by, group_size = grp
+        tab = self._group_table(group_by, on_device=hasattr(q, "is_cuda") and q.is_cuda)
+        D, I, _ = grouped_search(self.faiss_index, lambda x, f: self._dense_search(x, f, masks, filters), q, top_k, tab,
+                                 group_size)
+        return D, I
+
+    def _pick_dense_search(self, lam, grp):
+        if grp is not None:
+            return lambda q_, k_, m_, f_: self._dense_search_grouped(q_, k_, grp, m_, f_)
+        if lam is not None:
+            return lambda q_, k_, m_, f_: self._dense_search_mmr(q_, k_, lam, m_, f_)
+        return self._dense_search
+
     # -- fusion ------------------------------------------------------------
     def _reciprocal_rank_fusion(self, dense_results, bm25_results):
         """reference :326-343"""
@@ -939,21 +1028,26 @@ class Stage1Retriever:
         return out[0] if single else out
 
     def search(self, query: str, top_k: Optional[int] = None, filter=None,
-               mmr_lambda: Optional[float] = None) -> List[Dict[str, Any]]:
+               mmr_lambda: Optional[float] = None, group_by=None, group_size: int = 1) -> List[Dict[str, Any]]:
         """``filter``: restrict the candidates to some documents (see :meth:`filter_mask`); fewer than
         ``top_k`` results when fewer documents are allowed, none when none are.
         ``mmr_lambda`` (default: the config's, None = off): the ``top_k`` records are picked by maximal marginal
         relevance out of the ``min(1024, 4 top_k)`` best dense candidates and come back in selection order, with their
-        dense scores; 1.0 is the plain result.  Dense-only: ``ValueError`` while BM25 fusion is on."""
+        dense scores; 1.0 is the plain result.  Dense-only: ``ValueError`` while BM25 fusion is on.
+        ``group_by`` (default: the config's, None = off): a metadata key, or an integer array with one entry per
+        document (a document without the key, or with a negative entry, is a group of its own).  ``top_k`` then counts
+        GROUPS: the records of the ``top_k`` groups with the best best-document come back in dense order, at most
+        ``group_size`` of each (its best within the places fetched, FlatIPIndex.search_grouped).  Dense-only, and not
+        together with ``mmr_lambda``: ``ValueError``."""
         if self.faiss_index is None:
             raise ValueError("No documents indexed. Call add_documents() first.")
         top_k = top_k or self.config.top_k_candidates
         lam = self._mmr_lambda(mmr_lambda)
+        grp = self._group_args(group_by, group_size, lam)
         masks = self._filter_masks(filter, 1)
         if masks is not None and not masks[0].any():
             return []
-        dense_search = self._dense_search if lam is None else (
-            lambda q_, k_, m_, f_: self._dense_search_mmr(q_, k_, lam, m_, f_))
+        dense_search = self._pick_dense_search(lam, grp)
         if self._device_path():
             D, I = dense_search(self._normalized_query_tensor([query]), top_k, masks, filter)
             scores, ids = D.cpu().numpy(), I.cpu().numpy()
@@ -961,24 +1055,25 @@ class Stage1Retriever:
             q = self._normalize_embeddings(self._encode_batch([query]))
             scores, ids = dense_search(q, top_k, masks, filter)
         dense = [(int(i), float(s)) for i, s in zip(ids[0], scores[0]) if i >= 0]
-        results = self._finish(query, dense, top_k, None if masks is None else masks[0])
+        results = self._finish(query, dense, top_k if grp is None else top_k * grp[1], None if masks is None else masks[0])
         self.logger.info(f"Stage 1 search completed. Found {len(results)} candidates")
         return results
 
     def search_many(self, queries: Sequence[str], top_k: Optional[int] = None, filter=None,
-                    mmr_lambda: Optional[float] = None) -> List[List[Dict[str, Any]]]:
+                    mmr_lambda: Optional[float] = None, group_by=None, group_size: int = 1) -> List[List[Dict[str, Any]]]:
         """All queries through ONE encoder pass and ONE index call (64 queries share a
         single sweep over the corpus on the GPU).  ``filter``: one filter for every query, or a list with one
-        per query (None: unfiltered).  ``mmr_lambda``: as for :meth:`search`, one selection call for the batch."""
+        per query (None: unfiltered).  ``mmr_lambda``: as for :meth:`search`, one selection call for the batch.
+        ``group_by`` / ``group_size``: as for :meth:`search`, one collapse for the batch."""
         if self.faiss_index is None:
             raise ValueError("No documents indexed. Call add_documents() first.")
         top_k = top_k or self.config.top_k_candidates
         lam = self._mmr_lambda(mmr_lambda)
+        grp = self._group_args(group_by, group_size, lam)
         if not queries:
             return []
         masks = self._filter_masks(filter, len(queries))
-        dense_search = self._dense_search if lam is None else (
-            lambda q_, k_, m_, f_: self._dense_search_mmr(q_, k_, lam, m_, f_))
+        dense_search = self._pick_dense_search(lam, grp)
         if self._device_path():
             D, I = dense_search(self._normalized_query_tensor(list(queries)), top_k, masks, filter)
             scores, ids = D.cpu().numpy(), I.cpu().numpy()
@@ -992,16 +1087,18 @@ class Stage1Retriever:
                 out.append([])
                 continue
             dense = [(int(i), float(s)) for i, s in zip(ids[qi], scores[qi]) if i >= 0]
-            out.append(self._finish(query, dense, top_k, m))
+            out.append(self._finish(query, dense, top_k if grp is None else top_k * grp[1], m))
         return out
 
-    def search_many_arrays(self, queries: Sequence[str], top_k: Optional[int] = None, filter=None):
+    def search_many_arrays(self, queries: Sequence[str], top_k: Optional[int] = None, filter=None,
+                           group_by=None, group_size: int = 1):
         """Stage 1 for a query batch WITHOUT building result records: (ids int64 [B, k'], scores [B, k'])
         as torch tensors on the index's device for the pure dense search, numpy arrays (float64 fused
         scores) when BM25 fusion is on.  Row q, in order, is exactly what ``search_many`` would list for
         query q.  None when the corpus holds fewer than top_k rows (the caller then uses ``search_many``,
         which deals with padded results).  ``filter`` as for :meth:`search_many`: None also when some query has
-        fewer than top_k allowed documents."""
+        fewer than top_k allowed documents.  ``group_by`` / ``group_size`` as for :meth:`search_many` (device path):
+        rows of top_k * group_size entries; None also when some query's row would be padded."""
         import torch
         if self.faiss_index is None:
             raise ValueError("No documents indexed. Call add_documents() first.")
@@ -1009,8 +1106,19 @@ class Stage1Retriever:
         n = int(self.faiss_index.ntotal)
         if top_k > n or n != len(self.documents):
             return None
+        grp = self._group_args(group_by, group_size, self.config.mmr_lambda)
         if self.config.mmr_lambda is not None:   # a diversified stage 1 goes through search_many
             return None
+        if grp is not None:
+            if not self._device_path():
+                return None
+            masks = self._filter_masks(filter, len(queries))
+            if masks is not None and any(m is not None and not m.any() for m in masks):
+                return None
+            D, I = self._dense_search_grouped(self._normalized_query_tensor(list(queries)), top_k, grp, masks, filter)
+            if bool((I[:, -1] < 0).any()):   # (kept entries come first: a padded row ends in -1)
+                return None
+            return I, D
         masks = self._filter_masks(filter, len(queries))
         if masks is not None:
             if any(m is not None and int(np.count_nonzero(m)) < top_k for m in masks):
