@@ -46,6 +46,9 @@ def main():
     many = pipe.search_many(["gpu memory attention", "token index", "ranking"], top_k=3)   # every stage batched
     for q in many:
         print("search_many", repr(q["query"]), [r["doc_id"] for r in q["results"]])
+    hit = pipe.search("gpu memory attention", top_k=1, passages=32)["results"][0]  # + the best 32-token passage of each hit
+    print("passage    ", (hit["passage"]["token_start"], hit["passage"]["token_end"]), round(hit["passage"]["score"], 4),
+          repr(hit["passage"]["text"]))
     pipe.save_index()                                                           # + the stage-2 token store
     print("timing of the last search (s):", {k: round(v, 5) for k, v in one["timing"].items()})
 

@@ -60,7 +60,8 @@ extern "C" {
  * TS_FP8_E4M3; ts_index_set_fp8_scale_log2, ts_index_fp8_scale_log2): no existing signature changed, and an index of
  * another storage dtype runs the kernels it ran before.  So were ts_index_mmr, ts_mmr_ivf and the measurement aid
  * ts_index_mmr_set_timing / ts_index_mmr_get_timings: no existing signature or kernel changed, and a caller that
- * never calls them allocates and launches nothing new.  So was ts_group_topk, on the same terms.                 */
+ * never calls them allocates and launches nothing new.  So was ts_group_topk, on the same terms.  So were
+ * ts_maxsim_passages_indexed and ts_maxsim_passages_indexed_batch, on the same terms.                             */
 #define TS_ABI_VERSION 4
 
 typedef struct ts_index ts_index; /* opaque */
@@ -521,6 +522,45 @@ int ts_maxsim_indexed_fp8(const void* q, int32_t q_dtype, int32_t Lq, const void
 int ts_maxsim_indexed_batch_fp8(const void* q, int32_t q_dtype, const int32_t* q_off, int32_t nq, const void* store,
                                 const int64_t* starts, const int32_t* lens, const int32_t* cand_off, int32_t H,
                                 int32_t mode, float* out, int32_t device, void* stream);
+
+/* ---- best passage per candidate: windowed MaxSim over the token store (added within ABI version 4) ----
+ * Extends the reference's MaxSim (src/stage2_rescorer.py:167-183), which scores a whole chunk, by saying which part
+ * of the chunk matched.  Query token rows q_t, t < Lq, 1 <= Lq <= 256; candidate i's token rows x_j, j < Ld, are
+ * rows [starts[i], starts[i] + lens[i]) of `store`; c[t][j] is the cosine of q_t and x_j formed as ts_maxsim_indexed
+ * forms it (f32 accumulation of the stored values, the same normalisation, a zero row gives 0).  For a window of
+ * `window` >= 1 tokens:
+ *   we = min(window, Ld);  positions p in [0, Ld - we];  S[p] = sum over t of max_{p <= j < p + we} c[t][j]  (f32,
+ *   added in ascending t: deterministic, no float atomics, two runs give the same bits);
+ *   p* = the position with the largest S[p], compared as f32, ties to the lowest p, a NaN sum last.
+ *   out_start[i] = p*,  out_len[i] = we,  out_score[i] = S[p*] / Lq  (one f32 division: the mean of `maxsim` mode;
+ *   there is no `colbert` form of this call);
+ *   out_align (may be NULL) [i][t] = the j in [p*, p* + we) with the largest c[t][j], ties to the lowest j, as a
+ *   position in the document.
+ * With window >= Ld the window is the document and out_score is ts_maxsim_indexed's `maxsim` score of the candidate:
+ * bit for bit where the sums are exact, within rounding of a sum of Lq cosines otherwise.
+ * A candidate with lens[i] <= 0 gets start -1, length 0, score -FLT_MAX and alignment -1 (ts_maxsim_indexed gives
+ * such a candidate the score 0.0, the reference's value for a candidate that cannot be scored).  lens is device memory
+ * and these calls do not synchronise, so a candidate of more than 1024 rows is refused where it is met: the call
+ * returns TS_OK and that candidate gets start -2 (not -1), length 0, score -FLT_MAX and alignment -1 (the Python
+ * wrappers check the lengths and raise before the launch).  Candidates of 193 .. 1024 rows are taken by a second
+ * kernel of at most 1024 workgroups, one workgroup per CU at a time: they cost more per row than shorter ones.
+ * The batch form follows ts_maxsim_indexed_batch: q_off and cand_off are HOST arrays of nq + 1 int32 starting at 0;
+ * row cand_off[j] + i of out_align has align_ld >= max Lq entries, those at t >= Lq_j are -1; the single form's rows
+ * have Lq entries.  Both run on the caller's stream without host synchronisation.
+ * TS_ERR_INVALID (before any HIP call): a null pointer other than out_align, window < 1, H < 1, Lq < 1 (a query
+ * with candidates and no tokens), a negative count, decreasing offsets, align_ld below the longest query.
+ * TS_ERR_UNSUPPORTED (before any HIP call): Lq > 256, rows whose size H * element size is no multiple of 16 bytes,
+ * q or store not 16-byte aligned, dtype TS_FP8_E4M3 (an e4m3 token store is out of scope).  Store types: TS_F16,
+ * TS_BF16, TS_F32; q has the store's type.  n_docs == 0 / nq == 0 is TS_OK.                                     */
+int ts_maxsim_passages_indexed(const void* q, int32_t Lq, const void* store, const int64_t* starts,
+                               const int32_t* lens, int32_t n_docs, int32_t H, int32_t dtype, int32_t window,
+                               int32_t* out_start, int32_t* out_len, float* out_score, int32_t* out_align,
+                               int32_t device, void* stream);
+int ts_maxsim_passages_indexed_batch(const void* q, const int32_t* q_off, int32_t nq, const void* store,
+                                     const int64_t* starts, const int32_t* lens, const int32_t* cand_off, int32_t H,
+                                     int32_t dtype, int32_t window, int32_t* out_start, int32_t* out_len,
+                                     float* out_score, int32_t* out_align, int32_t align_ld, int32_t device,
+                                     void* stream);
 
 /* ---- BM25 (the lexical half of stage 1) ---------------------------------------
  * replaces BM25Index.search (reference src/stage1_retriever.py:103-112, called at

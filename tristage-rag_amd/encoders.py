@@ -87,6 +87,14 @@ class HashTokenizer:
     def _ids(self, text: str) -> List[int]:
         return self._ids_np(text).tolist()
 
+    def offsets(self, text: str, max_length=None):
+        """The (start, end) character span of every token row ``self(text, max_length=...)`` produces for a single
+        text: [CLS], the pieces, [SEP]; special tokens get (0, 0).  Same regular expression and truncation as
+        ``__call__``.  The spans refer to the string that was split, ``text.lower()``."""
+        max_length = int(max_length or self.model_max_length)
+        spans = [m.span() for m in re.finditer(r"[a-z0-9]+|[^\sa-z0-9]", text.lower())][: max(max_length - 2, 0)]
+        return [(0, 0)] + spans + [(0, 0)]
+
     def __call__(self, text, text_pair=None, truncation=True, padding=False, max_length=None,
                  return_tensors=None, **_):
         single = isinstance(text, str)
@@ -153,6 +161,20 @@ class HashTokenizer:
         if return_tensors == "pt":
             return {k: torch.from_numpy(v) for k, v in out.items()}
         return {k: v.tolist() for k, v in out.items()}
+
+
+def token_offsets(tokenizer, text: str, max_length: int):
+    """``(spans, source)`` for a single text: the (start, end) character span of every token row the tokenizer
+    produces (special tokens: (0, 0)) and the string those spans index — or None for a tokenizer without offsets.
+    HashTokenizer splits ``text.lower()``: the source is ``text`` itself when lowering kept its length, else the
+    lowered string.  Hugging Face fast tokenizers report spans of ``text`` (``return_offsets_mapping``)."""
+    if isinstance(tokenizer, HashTokenizer):
+        low = text.lower()
+        return tokenizer.offsets(text, max_length), (text if len(low) == len(text) else low)
+    if getattr(tokenizer, "is_fast", False):
+        enc = tokenizer(text, truncation=True, max_length=max_length, return_offsets_mapping=True)
+        return [(int(a), int(b)) for a, b in enc["offset_mapping"]], text
+    return None
 
 
 # --------------------------------------------------------------------------- random models

@@ -1231,6 +1231,91 @@ def maxsim_indexed_batch(q_packed, q_offsets, store, starts, lens, cand_offsets,
     return out
 
 
+# ---- best passage per candidate (include/tristage.h) ----------------------------------------
+PASSAGE_MAX_LQ, PASSAGE_MAX_LD = 256, 1024
+
+
+def passage_check(window, H: int, store, max_lq: int, max_len: int) -> None:
+    """The refusals of ts_maxsim_passages_indexed(_batch), raised before anything is launched."""
+    if isinstance(window, bool) or not isinstance(window, (int, np.integer)) or window < 1:
+        raise ValueError(f"window must be an integer >= 1, got {window!r}")
+    if _is_fp8(store):
+        raise NotImplementedError("best passages over an e4m3 token store are not supported")
+    if (H * store.element_size()) % 16:
+        raise ValueError(f"token rows of {H * store.element_size()} bytes (H = {H}): a multiple of 16 bytes is needed")
+    if max_lq > PASSAGE_MAX_LQ:
+        raise ValueError(f"a query of {max_lq} tokens: at most {PASSAGE_MAX_LQ}")
+    if max_len > PASSAGE_MAX_LD:
+        raise ValueError(f"a candidate of {max_len} token rows: at most {PASSAGE_MAX_LD}")
+
+
+def maxsim_passages_indexed(q, store, starts, lens, window: int, align: bool = False, max_len: Optional[int] = None):
+    """The best passage of every candidate for one query: for candidate i (rows [starts[i], starts[i] + lens[i]) of
+    the resident token ``store``) the window of min(window, lens[i]) consecutive token rows whose windowed MaxSim —
+    the sum over the query tokens of the best cosine inside the window — is largest (ties: the lowest start).
+    Returns device tensors (start int32 [n], length int32 [n], score float32 [n] = that sum / Lq[, align int32
+    [n, Lq]: each query token's best row inside the window, as a position in the document]).  A candidate without
+    rows gets (-1, 0, -FLT_MAX, -1).  ``max_len``: an upper bound of ``lens`` the caller knows; without it the
+    lengths are read back once to refuse a candidate of more than 1024 rows."""
+    Lq = int(q.shape[0])
+    if Lq < 1:
+        raise ValueError("the query has no tokens")
+    n = int(starts.numel())
+    out = maxsim_passages_indexed_batch(q, [0, Lq], store, starts, lens, [0, n], window, align=align, max_len=max_len)
+    return out
+
+
+def maxsim_passages_indexed_batch(q_packed, q_offsets, store, starts, lens, cand_offsets, window: int,
+                                  align: bool = False, max_len: Optional[int] = None):
+    """maxsim_passages_indexed for SEVERAL queries in one call, with the argument conventions of
+    maxsim_indexed_batch.  The alignment has max Lq columns; row r of query j holds -1 at t >= Lq_j."""
+    torch = _torch()
+    lib = _lib.load()
+    if not store.is_contiguous():
+        raise ValueError("token store must be contiguous")
+    qo = np.ascontiguousarray(np.asarray(q_offsets, dtype=np.int32))
+    co = np.ascontiguousarray(np.asarray(cand_offsets, dtype=np.int32))
+    if qo.ndim != 1 or qo.shape != co.shape or qo.size < 1 or qo[0] != 0 or co[0] != 0:
+        raise ValueError("q_offsets / cand_offsets must be 1-D, of equal length nq+1, starting at 0")
+    if (np.diff(qo) < 0).any() or (np.diff(co) < 0).any():
+        raise ValueError("q_offsets / cand_offsets must be non-decreasing")
+    nq = qo.size - 1
+    if int(qo[-1]) != q_packed.shape[0]:
+        raise ValueError("q_offsets[-1] must equal the number of packed query tokens")
+    n = int(co[-1])
+    if starts.numel() != n or lens.numel() != n:
+        raise ValueError("starts / lens must hold cand_offsets[-1] entries")
+    lqs = np.diff(qo)
+    if ((np.diff(co) > 0) & (lqs < 1)).any():
+        raise ValueError("a query with candidates has no tokens")
+    max_lq = int(lqs.max()) if nq else 0
+    H = int(q_packed.shape[1])
+    if store.dim() != 2 or store.shape[1] != H:
+        raise ValueError("q and store must have the same row length")
+    lens = lens.to(device=q_packed.device, dtype=torch.int32).contiguous()
+    if max_len is None:
+        max_len = int(lens.max().item()) if n else 0
+    passage_check(window, H, store, max_lq, int(max_len))
+    if q_packed.dtype != store.dtype:
+        q_packed = q_packed.to(store.dtype)
+    q_packed = q_packed.contiguous()
+    starts = starts.to(device=q_packed.device, dtype=torch.int64).contiguous()
+    dev_t = q_packed.device
+    o_start = torch.empty((n,), dtype=torch.int32, device=dev_t)
+    o_len = torch.empty((n,), dtype=torch.int32, device=dev_t)
+    o_score = torch.empty((n,), dtype=torch.float32, device=dev_t)
+    o_align = torch.empty((n, max_lq), dtype=torch.int32, device=dev_t) if align else None
+    if n and nq:
+        dev = dev_t.index
+        _lib.check(lib.ts_maxsim_passages_indexed_batch(
+            ctypes.c_void_p(q_packed.data_ptr()), qo.ctypes.data_as(ctypes.c_void_p), nq,
+            ctypes.c_void_p(store.data_ptr()), ctypes.c_void_p(starts.data_ptr()), ctypes.c_void_p(lens.data_ptr()),
+            co.ctypes.data_as(ctypes.c_void_p), H, _tensor_dtype(q_packed), int(min(window, 1 << 30)),
+            ctypes.c_void_p(o_start.data_ptr()), ctypes.c_void_p(o_len.data_ptr()), ctypes.c_void_p(o_score.data_ptr()),
+            ctypes.c_void_p(o_align.data_ptr()) if align else None, max_lq, dev, ctypes.c_void_p(_stream_ptr(dev))))
+    return (o_start, o_len, o_score, o_align) if align else (o_start, o_len, o_score)
+
+
 # ---- e4m3 token store (include/tristage.h; DESIGN.md 4.10) --------------------------------------------------
 FP8_STORE_MAX_H = 2048   # the largest H whose query image fits the streaming kernel's LDS budget (at H % 16 == 0)
 

@@ -92,6 +92,8 @@ class PipelineConfig:
     group_by: Any = None                     # None: off.  A metadata key or an integer array over the documents: stage 1
                                              # returns the stage1_top_k best GROUPS, at most group_size documents of each, so
     group_size: int = 1                      # stages 2 and 3 and the final list see no more of any group
+    passage_window: Optional[int] = None     # None: off.  Tokens of the best passage every final record then carries
+                                             # under "passage" (windowed MaxSim over the stage-2 tokens)
 
 
 # (section, key) in the reference's YAML layout -> PipelineConfig field (reference :182-217)
@@ -113,6 +115,7 @@ _GENERAL_KEYS = ("device", "cache_dir", "index_dir", "log_level", "log_file", "e
 
 _NO_MMR = object()      # search(..., mmr_lambda=_NO_MMR): the plain search inside a diversified one
 _ALL_RESULTS = 1 << 30  # top_k of that plain search: the whole list stage 3 returns
+_NO_PASSAGES = object()  # search(..., passages=_NO_PASSAGES): the search inside one that adds passages
 
 
 class RetrievalPipeline:
@@ -197,7 +200,7 @@ class RetrievalPipeline:
                 scoring_method=c.stage2_scoring_method,
                 cache_document_embeddings=c.stage2_cache_document_embeddings,
                 precompute_document_embeddings=c.stage2_precompute_document_embeddings,
-                token_store_dtype=c.stage2_token_store_dtype,
+                token_store_dtype=c.stage2_token_store_dtype, passage_window=c.passage_window,
                 use_hip_graph=c.use_hip_graphs, index_batch_size=c.stage2_index_batch_size, amp_dtype=c.amp_dtype))
             self.logger.info("Stage 2 initialized")
             self.stage3 = AdaptiveCrossEncoderReranker(Stage3Config(
@@ -363,8 +366,53 @@ class RetrievalPipeline:
             o["results"] = [by_id[int(i)] for i in row if int(i) >= 0]
         return outs
 
+    # -- best passage per hit -------------------------------------
+    def _passage_window(self, passages) -> Optional[int]:
+        """The window of a search (the argument, else the config); None: no passages."""
+        if passages is _NO_PASSAGES:
+            return None
+        w = self.config.passage_window if passages is None else passages
+        if w is None:
+            return None
+        if isinstance(w, bool) or not isinstance(w, (int, np.integer)) or w < 1:
+            raise ValueError(f"passages must be a window of at least 1 token, got {passages!r}")
+        return int(w)
+
+    def _add_passages(self, outs: List[Dict[str, Any]], window: int) -> List[Dict[str, Any]]:
+        """Every record of each output's ``results`` gains ``"passage"``: the window of ``window`` stage-2 token rows
+        of the document that matches the query best (ColBERTScorer.best_passages: one kernel call for the batch,
+        from the token store where every document has a slot, else from the re-encoded texts) and the text it covers.
+        Nothing else of a record changes."""
+        from .encoders import token_offsets
+        lists = [o["results"] for o in outs]
+        if not any(lists):
+            return outs
+        st2 = self.stage2
+        ids = [[r.get("doc_id") for r in recs] for recs in lists]
+        in_store = len(st2.token_store) and all(i in st2._store_slot for lst in ids for i in lst)
+        docs = ids if in_store else [[r["document"] for r in recs] for recs in lists]
+        found = st2.best_passages([o["query"] for o in outs], docs, window)
+        L = st2.config.max_seq_length
+        for recs, spans in zip(lists, found):
+            for r, sp in zip(recs, spans):
+                a, b = sp["token_start"], sp["token_end"]
+                psg = {"token_start": a, "token_end": b, "score": sp["score"],
+                       "char_start": None, "char_end": None, "text": None}
+                doc = r["document"]
+                blank = not doc or not doc.strip()       # stage 2 encodes such a document as "empty"
+                off = token_offsets(st2.tokenizer, "empty" if blank else doc, L)
+                if off is not None:
+                    pieces = [x for x in off[0][a:b] if x != (0, 0)]      # (special tokens have no characters)
+                    if blank or not pieces:
+                        psg.update(char_start=0, char_end=0, text="")
+                    else:
+                        psg.update(char_start=pieces[0][0], char_end=pieces[-1][1],
+                                   text=off[1][pieces[0][0]: pieces[-1][1]])
+                r["passage"] = psg
+        return outs
+
     def search(self, query: str, top_k: Optional[int] = None, filter=None, mmr_lambda=None,
-               group_by=None, group_size: int = 1) -> Dict[str, Any]:
+               group_by=None, group_size: int = 1, passages=None) -> Dict[str, Any]:
         """``filter``: search only the documents it allows (Stage1Retriever.filter_mask: a metadata dict, a
         callable, document indices or a bool array).  Stages 2 and 3 rescore stage 1's candidates, so fewer
         than ``top_k`` results come back when fewer documents are allowed, and none when none are.
@@ -374,14 +422,23 @@ class RetrievalPipeline:
         ``group_by`` / ``group_size`` (default: the config's, None = off): the collapse is applied at stage 1
         (Stage1Retriever.search), where ``stage1_top_k`` then counts groups: stages 2 and 3 see at most ``group_size``
         documents of any group, and so does the final list.  Dense-only and not together with ``mmr_lambda``:
-        ``ValueError``."""
+        ``ValueError``.
+        ``passages`` (an int window in tokens; default: the config's ``passage_window``, None = off): stages 1 to 3
+        run as without it, then every record of the final list — after MMR or grouping if those are on — gains
+        ``"passage": {"token_start", "token_end" (exclusive), "score", "char_start", "char_end", "text"}`` (see
+        :meth:`_add_passages`; the character fields are None for a tokenizer without offsets)."""
         if not self.stage1 or not self.stage2 or not self.stage3:
             self.initialize_stages()
+        pw = self._passage_window(passages)
+        if pw is not None:
+            return self._add_passages([self.search(query, top_k, filter=filter, mmr_lambda=mmr_lambda, group_by=group_by,
+                                                   group_size=group_size, passages=_NO_PASSAGES)], pw)[0]
         top_k = top_k or self.config.stage3_top_k
         lam = self._mmr_lambda(mmr_lambda)
         gkw = self._group_kwargs(group_by, group_size, lam)
         if lam is not None:
-            return self._diversify([self.search(query, _ALL_RESULTS, filter=filter, mmr_lambda=_NO_MMR)], top_k, lam)[0]
+            return self._diversify([self.search(query, _ALL_RESULTS, filter=filter, mmr_lambda=_NO_MMR,
+                                                passages=_NO_PASSAGES)], top_k, lam)[0]
         if self.config.search_on_arrays and filter is None:
             # one query through the array path of search_many (resident token store + stage-3 id cache): no candidate
             # text is tokenised or re-encoded, one cross-encoder forward for the query's pairs; same records (tests)
@@ -402,11 +459,20 @@ class RetrievalPipeline:
             raise
 
     def batch_search(self, queries: List[str], top_k: Optional[int] = None, filter=None,
-                     mmr_lambda=None, group_by=None, group_size: int = 1) -> List[Dict[str, Any]]:
+                     mmr_lambda=None, group_by=None, group_size: int = 1, passages=None) -> List[Dict[str, Any]]:
         """Sequential, like the reference (:444-448); see search_many for the batched form.  ``filter``: one
         filter for every query or a list with one per query.  ``mmr_lambda``, ``group_by`` / ``group_size``: as for
-        :meth:`search`."""
+        :meth:`search`.  ``passages``: as for :meth:`search`, one kernel call for the batch."""
+        if passages is not _NO_PASSAGES:
+            if not self.stage2:
+                self.initialize_stages()
+            pw = self._passage_window(passages)
+            if pw is not None:
+                return self._add_passages(self.batch_search(queries, top_k, filter=filter, mmr_lambda=mmr_lambda,
+                                                            group_by=group_by, group_size=group_size,
+                                                            passages=_NO_PASSAGES), pw)
         gkw = {} if group_by is None else {"group_by": group_by, "group_size": group_size}
+        gkw["passages"] = _NO_PASSAGES
         if filter is None:
             if mmr_lambda is None:
                 return [self.search(q, top_k, **gkw) for q in queries]
@@ -417,23 +483,30 @@ class RetrievalPipeline:
         return [self.search(q, top_k, filter=f, mmr_lambda=mmr_lambda, **gkw) for q, f in zip(queries, specs)]
 
     def search_many(self, queries: List[str], top_k: Optional[int] = None, filter=None,
-                    mmr_lambda=None, group_by=None, group_size: int = 1) -> List[Dict[str, Any]]:
+                    mmr_lambda=None, group_by=None, group_size: int = 1, passages=None) -> List[Dict[str, Any]]:
         """Same result records as batch_search, every stage batched over the queries: one
         bi-encoder pass and one sweep of the corpus per 64 queries (stage 1), one query forward
         and one MaxSim launch (stage 2, with the resident token store), one length-sorted pass
         of the cross-encoder over all (query, candidate) pairs (stage 3).  Stage times are
         reported as equal shares of the batch's stage times.  ``filter``: one filter for every query or a list
         with one per query (see :meth:`search`); a filtered batch takes the record path.  ``group_by`` /
-        ``group_size``: as for :meth:`search`, one collapse for the batch."""
+        ``group_size``: as for :meth:`search`, one collapse for the batch.  ``passages``: as for :meth:`search`, one
+        kernel call for the batch."""
         if not self.stage1 or not self.stage2 or not self.stage3:
             self.initialize_stages()
+        pw = self._passage_window(passages)
+        if pw is not None:
+            return self._add_passages(self.search_many(queries, top_k, filter=filter, mmr_lambda=mmr_lambda,
+                                                       group_by=group_by, group_size=group_size,
+                                                       passages=_NO_PASSAGES), pw)
         top_k = top_k or self.config.stage3_top_k
         if not queries:
             return []
         lam = self._mmr_lambda(mmr_lambda)
         gkw = self._group_kwargs(group_by, group_size, lam)
         if lam is not None:   # (mmr_lambda: as for search(); one selection call for the batch)
-            return self._diversify(self.search_many(queries, _ALL_RESULTS, filter=filter, mmr_lambda=_NO_MMR), top_k, lam)
+            return self._diversify(self.search_many(queries, _ALL_RESULTS, filter=filter, mmr_lambda=_NO_MMR,
+                                                    passages=_NO_PASSAGES), top_k, lam)
         queries = list(queries)
         n = len(queries)
         # a batch builds ~n x stage1_top_k candidate records; the cyclic collector would rescan

@@ -50,6 +50,9 @@ class Stage2Config:
     index_batch_size: int = 256                   # documents per forward wherever MANY documents are encoded: filling the
                                                   # token store at add time, re-encoding a query's candidates without one
                                                   # (batch_size, the reference's 16, keeps both launch-bound)
+    passage_window: Optional[int] = None          # the default window of best_passages (tokens); filled from
+                                                  # PipelineConfig.passage_window, which is what switches the pipeline's
+                                                  # "passage" records on
 
 
 TOKEN_STORE_FORMAT = "tristage-rag_amd/token-store/1"          # rows of bf16 / f16 / f32
@@ -595,6 +598,75 @@ class ColBERTScorer:
         flat = fn(q_packed, q_off, store.data, starts_all[sel], lens_all[sel], c_off,
                   self.config.scoring_method).detach().cpu().tolist()
         return [[float(x) for x in flat[a:b]] for a, b in zip(c_off[:-1], c_off[1:])]
+
+    # -- best passage per hit -------------------------------------
+    def best_passages(self, query_or_queries, doc_ids_or_documents, window: Optional[int] = None, align: bool = False):
+        """The best passage of every document for its query: the window of min(window, Ld) consecutive token rows
+        with the largest windowed MaxSim (index.maxsim_passages_indexed_batch: one kernel call for the batch).
+        One query with a list of documents, or a list of queries with one list each.  A list holds pipeline doc ids
+        — scored from the resident token store, where every one of them has a slot — or document texts, which are
+        encoded with encode_documents_batch and packed into a temporary tensor.  Returns per query a list of
+        {"token_start", "token_end" (exclusive), "score"[, "align": each query token's best row]} (token rows
+        include [CLS] / [SEP]); a single query gets its list alone.  ``window``: default the config's
+        ``passage_window``."""
+        from .index import maxsim_passages_indexed_batch, passage_check
+        if window is None:
+            window = self.config.passage_window
+        if window is None:
+            raise ValueError("best_passages: no window given and Stage2Config.passage_window is unset")
+        single = isinstance(query_or_queries, str)
+        queries = [query_or_queries] if single else list(query_or_queries)
+        lists = [list(doc_ids_or_documents)] if single else [list(x) for x in doc_ids_or_documents]
+        if len(lists) != len(queries):
+            raise ValueError("one list of documents per query")
+        flat = [x for lst in lists for x in lst]
+        c_off = [0]
+        for lst in lists:
+            c_off.append(c_off[-1] + len(lst))
+        if not flat:
+            return [] if single else [[] for _ in queries]
+        by_id = all(not isinstance(x, str) for x in flat)
+        if by_id:
+            slots = [self._store_slot.get(int(x), -1) for x in flat]
+            if not len(self.token_store) or min(slots) < 0:
+                raise ValueError("best_passages: a doc id without a slot in the token store (pass the document text)")
+            store = self.token_store.data
+            passage_check(window, int(store.shape[1]), store, 1, 1)     # (an e4m3 store: before any forward)
+            starts_all, lens_all = self.token_store.device_tables()
+            sel = torch.tensor(slots, dtype=torch.int64, device=starts_all.device)
+            starts, lens = starts_all[sel], lens_all[sel]
+            max_len = max(self.token_store.lens[s] for s in slots)
+        elif all(isinstance(x, str) for x in flat):
+            embs = [e.reshape(-1, e.shape[-1]) for e in self.encode_documents_batch(flat)]
+            dts = {e.dtype for e in embs}
+            dt = next(iter(dts)) if len(dts) == 1 and next(iter(dts)) in (torch.float16, torch.bfloat16) else torch.float32
+            store = torch.cat(embs, 0).to(dt).contiguous()
+            n_rows = [int(e.shape[0]) for e in embs]
+            at = np.concatenate([[0], np.cumsum(n_rows)[:-1]]).astype(np.int64)
+            starts = torch.from_numpy(at).to(store.device)
+            lens = torch.tensor(n_rows, dtype=torch.int32, device=store.device)
+            max_len = max(n_rows)
+        else:
+            raise ValueError("best_passages: a list holds doc ids or document texts, not both")
+        q_embs = [e.reshape(-1, e.shape[-1]) for e in self.encode_queries_batch(queries)]
+        q_off = [0]
+        for e in q_embs:
+            q_off.append(q_off[-1] + int(e.shape[0]))
+        q_packed = torch.cat([e.to(store.dtype) for e in q_embs], 0).contiguous()
+        out = maxsim_passages_indexed_batch(q_packed, q_off, store, starts, lens, c_off, window, align=align,
+                                            max_len=max_len)
+        st, ln, sc = (t.cpu().tolist() for t in out[:3])
+        al = out[3].cpu().numpy() if align else None
+        res = []
+        for j, (a, b) in enumerate(zip(c_off[:-1], c_off[1:])):
+            recs = []
+            for i in range(a, b):
+                r = {"token_start": int(st[i]), "token_end": int(st[i]) + int(ln[i]), "score": float(sc[i])}
+                if align:
+                    r["align"] = al[i, : q_off[j + 1] - q_off[j]].tolist()
+                recs.append(r)
+            res.append(recs)
+        return res[0] if single else res
 
     def reset_token_store(self) -> None:
         """Drop the resident token store (and every table derived from it)."""
