@@ -15,6 +15,20 @@
  *     the default stream);
  *   - the library owns the corpus memory after ts_index_add; the caller owns
  *     every output buffer; a handle is freed only by ts_index_destroy;
+ *   - streams: every device-side step of a call (kernels, memsets, copies) is issued on `stream`, reads its device
+ *     inputs in stream order (they may be the output of work still pending on `stream`) and is ordered before
+ *     whatever the caller enqueues on `stream` afterwards.  The one use of the null stream is the zeroing of a
+ *     workspace that has just been allocated (ts_index_create, ts_ivf_create, ts_ivf_reset, ts_bm25_set_index, a
+ *     BM25 batch that needs more lanes than the handle has): the null stream is synchronised behind it before
+ *     anything is enqueued on `stream`, which need not wait for the null stream.  Where an entry
+ *     point's own comment does not say more: ts_index_add, ts_index_reconstruct, ts_index_range_fetch,
+ *     ts_index_live_words, ts_index_compact, ts_index_remove and ts_index_update return after a synchronisation of
+ *     `stream` behind their last step; so does every IVF call that takes a stream, ts_mmr_ivf excepted, and so do
+ *     the ts_bm25_search calls, whose results are host memory.  The stateless calls ts_merge_topk(_strided),
+ *     ts_maxsim, ts_maxsim_indexed(_batch)(_fp8), ts_quantize_rows_fp8 and the forward kernels only enqueue on
+ *     `stream` and return without a host synchronisation; two cases wait for `stream` all the same: a MaxSim call
+ *     whose scratch for that (device, stream) has to grow, and a merge of more than 16384 / k lists, which frees
+ *     its intermediate lists before it returns.  ts_index_read_probe times its passes with events and waits for them.
  *   - threading: ts_index_search on a built index is safe for
  *     concurrent callers on ONE handle that use distinct streams and output
  *     buffers: each call takes one of 4 internal workspace sets (a 5th

@@ -416,6 +416,9 @@ static int bm25_set_lanes(ts_bm25* h, int lanes) {
   TS_HIP(hipMalloc((void**)&h->tau, (size_t)lanes * 8));
   TS_HIP(hipMemset(h->acc, 0, n1 * 8));
   TS_HIP(hipMemset(h->counters, 0, (size_t)lanes * 16));
+  // The zeros are written on the null stream and read by kernels on the caller's stream, which need not wait for the
+  // null stream (a non-blocking stream does not), and a device memset need not be complete when hipMemset returns.
+  TS_HIP(hipStreamSynchronize(nullptr));
   h->lanes = lanes;
   return TS_OK;
 }
@@ -450,6 +453,7 @@ extern "C" int ts_bm25_set_index(ts_bm25* h, int64_t N, int64_t V, int64_t nnz, 
     TS_HIP(hipMemcpy(h->post_tf, post_tf, (size_t)nnz * 4, hipMemcpyHostToDevice));
   }
   if (N) TS_HIP(hipMemcpy(h->len_norm, len_norm, (size_t)N * 8, hipMemcpyHostToDevice));
+  TS_HIP(hipStreamSynchronize(nullptr));   // (a copy from pageable memory may return before its last DMA: searches run on any stream)
   return TS_OK;
 }
 

@@ -323,6 +323,8 @@ extern "C" int ts_index_create(int32_t dim, int32_t storage_dtype, int32_t metri
       st = TS_ERR_HIP;
     }
   }
+  // the workspaces' scratch pages are zeroed on the null stream: done before any stream's first search reads them
+  if (st == TS_OK && hipStreamSynchronize(nullptr) != hipSuccess) { ts_set_error("hipStreamSynchronize failed"); st = TS_ERR_HIP; }
   if (st == TS_OK && (hipEventCreateWithFlags(&h->co_ev, hipEventDisableTiming) != hipSuccess ||
                       hipEventCreateWithFlags(&h->eff_ev, hipEventDisableTiming) != hipSuccess)) {
     ts_set_error("hipEventCreate failed");

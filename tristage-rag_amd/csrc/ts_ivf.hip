@@ -641,6 +641,10 @@ extern "C" int ts_ivf_create(int32_t dim, int32_t nlist, int32_t storage_dtype, 
     ts_set_error("hipMemset failed");
     st = TS_ERR_HIP;
   }
+  if (st == TS_OK && hipStreamSynchronize(nullptr) != hipSuccess) {   // (as in ts_ivf_reset: done before any stream's first use)
+    ts_set_error("hipStreamSynchronize failed");
+    st = TS_ERR_HIP;
+  }
   if (st == TS_OK &&
       (hipHostMalloc((void**)&h->host_rep, 128 * 4, hipHostMallocMapped) != hipSuccess ||
        hipHostGetDevicePointer((void**)&h->host_rep_dev, h->host_rep, 0) != hipSuccess)) {
@@ -675,7 +679,10 @@ extern "C" int ts_ivf_destroy(ts_ivf* h) {
 extern "C" int ts_ivf_reset(ts_ivf* h) {
   if (!h) { ts_set_error("null handle"); return TS_ERR_INVALID; }
   IvfGuard g(h->device);
+  // The list sizes are cleared on the null stream, which a non-blocking caller stream does not wait for, and a memset
+  // of device memory need not be complete when hipMemset returns: the next add, on any stream, must find it done.
   TS_HIP(hipMemset(h->dlist_size.p, 0, (size_t)h->nlist * 8));
+  TS_HIP(hipStreamSynchronize(nullptr));
   h->ntotal = 0;
   h->nblocks = 0;
   for (auto& v : h->list_blocks) v.clear();
