@@ -75,7 +75,8 @@ extern "C" {
  * another storage dtype runs the kernels it ran before.  So were ts_index_mmr, ts_mmr_ivf and the measurement aid
  * ts_index_mmr_set_timing / ts_index_mmr_get_timings: no existing signature or kernel changed, and a caller that
  * never calls them allocates and launches nothing new.  So was ts_group_topk, on the same terms.  So were
- * ts_maxsim_passages_indexed and ts_maxsim_passages_indexed_batch, on the same terms.                             */
+ * ts_maxsim_passages_indexed and ts_maxsim_passages_indexed_batch, on the same terms.  So were ts_index_search_prefix
+ * and ts_index_rescore, on the same terms.                                                                           */
 #define TS_ABI_VERSION 4
 
 typedef struct ts_index ts_index; /* opaque */
@@ -386,6 +387,39 @@ int ts_index_mmr(ts_index* h, const int64_t* cand_ids, const float* cand_rel, in
  * summed milliseconds of gather, Gram and greedy selection over *calls timed calls since the last reset.           */
 int ts_index_mmr_set_timing(ts_index* h, int32_t on);
 int ts_index_mmr_get_timings(ts_index* h, double ms[3], int64_t* calls, int32_t reset);
+/* ---- funnel search: rank on a prefix of the dimensions, rescore a shortlist exactly ----
+ * Reference call site: none (the reference searches all dimensions; its stage-1 model is trained with Matryoshka
+ * representation learning, so a prefix of its embedding is a usable embedding).  Added within version 4: no existing
+ * signature or kernel changed, and a caller that never calls these allocates and launches nothing new.  f16 / bf16
+ * storage only (TS_ERR_UNSUPPORTED otherwise).  Both calls are synchronous: they return with their stream drained.
+ *
+ * ts_index_search_prefix: ts_index_search_filtered on the inner product over the first `dims` components only.
+ * `queries` holds nq rows of `dims` elements (q_dtype); stored rows are used as they are, nothing is renormalised.
+ * The result is, bit for bit and id for id, what ts_index_search_filtered returns on an index of dimension `dims`
+ * and the same storage dtype that holds the first `dims` components of every row under the same ids, with the same
+ * rows removed: the same k groups of the same stored bytes in the same order; ties to the lower id; -1 / -FLT_MAX
+ * padding; removed rows are never returned.  Masks as for ts_index_search_filtered, except that mask_of_query may be
+ * NULL (no query has a mask).  The scan reads the first dims / 16 KiB of every 32-row block and nothing else of it.
+ * dims % 128 == 0, 128 <= dims < dim, 1 <= k <= 16384; flags: TS_FLAG_HOST_PTR and TS_FLAG_NO_FILTER only; anything
+ * else is TS_ERR_INVALID, before any HIP call.
+ *
+ * ts_index_rescore: exact full-dimension scores of given candidates.  queries [nq, dim] (q_dtype), cand_ids
+ * [nq, ncand] int64 in the id space search returns, out_scores / out_ids [nq, k], all DEVICE memory;
+ * 1 <= k <= ncand <= 16384.  Per query the valid candidates ordered by score descending, then id ascending; every
+ * score is bit-identical to ts_index_scores / ts_index_search.  An entry that is -1, outside [offset, offset +
+ * ntotal) or the id of a removed row has no rank: the tail of the output is -1 / -FLT_MAX.  An id given twice is
+ * returned twice.  Calls on one handle share its scratch (candidate tiles of one chunk of queries, at most 384 MiB;
+ * allocated at the first call, freed with the handle) and are serialised.
+ * The funnel is ts_index_rescore of the ids ts_index_search_prefix returned, on one stream.
+ * hip_stream: the hipStream_t the call runs on, what the other entry points call `stream`.  Both calls are held to
+ * the synchronous stream contract, inputs arriving late on a side stream, by tests/test_stream_order_of_funnel_gpu.py; the table of
+ * tests/stream_order.py lists the prototypes that spell the parameter `stream` and has no row for these two yet.  */
+int ts_index_search_prefix(ts_index* h, const void* queries, int32_t nq, int32_t q_dtype, int32_t dims, int32_t k,
+                           const uint32_t* allow_bits, int64_t allow_words, int32_t n_masks,
+                           const int32_t* mask_of_query, float* out_scores, int64_t* out_ids, uint32_t flags,
+                           void* hip_stream);
+int ts_index_rescore(ts_index* h, const void* queries, int32_t nq, int32_t q_dtype, const int64_t* cand_ids,
+                     int32_t ncand, int32_t k, float* out_scores, int64_t* out_ids, void* hip_stream);
 /* row-shard support: ids reported by search = local row + offset            */
 int ts_index_set_id_offset(ts_index* h, int64_t offset);
 /* copy rows [row0, row0+n) back out as row-major float32 (host or device):

@@ -158,6 +158,19 @@ struct MaskedScanParams : ScanParams {
 };
 int ts_launch_scan_masked(const TsLayout& L, int qh, const MaskedScanParams& p, int num_cus, hipStream_t stream);
 
+// Prefix scans (ts_scan_prefix.hip): the first `kg` k groups of every row block, whose starts are
+// `kg_row` groups apart; qimg is the image of a kg-group layout.  Parameters of their own, derived, so that the structs
+// of the scans above keep their layout.  f16 / bf16 storage.
+struct PrefixScanParams : ScanParams {
+  int kg_row;
+};
+struct PrefixMaskedScanParams : MaskedScanParams {
+  int kg_row;
+};
+int ts_launch_scan_prefix(const TsLayout& L, int mode, int qh, const PrefixScanParams& p, int num_cus, hipStream_t stream);
+int ts_launch_scan_prefix_masked(const TsLayout& L, int qh, const PrefixMaskedScanParams& p, int num_cus,
+                                 hipStream_t stream);
+
 // Coalesced passes (TS_FLAG_COALESCE, scan_multi_kernel): one filter scan over every row block for G 32-query
 // groups that may come from different batches.  Group g is the query columns 32*ghalf[g] .. +32 of the Q image
 // gimg[g] (laid out with gqh[g] halves per k group), with its batch's thresholds and candidate lists at the same
@@ -519,3 +532,22 @@ int ts_mmr_check_args(const void* h, const void* cand_ids, const void* cand_rel,
 int ts_mmr_run(const TsMmrSource& src, TsMmrWork& w, const int64_t* cand_ids, const float* cand_rel, int32_t nq,
                int32_t C, int32_t k, float lambda, float* out_rel, int64_t* out_ids, uint32_t flags, hipStream_t s);
 void ts_mmr_release(TsMmrWork& w);
+// MMR's gather on its own: candidates ids[q * C + c] (-1, unknown and removed ids: zero rows, valid = 0) of nq queries
+// -> tile[q][cbp][kg][64] in fragment order and valid[q][32 * cbp]; cbp >= ceil(C / 32)
+int ts_launch_gather_tiles(const TsMmrSource& src, const int64_t* ids, int C, int cbp, int nq, uint4* tile,
+                           int32_t* valid, hipStream_t s);
+
+// ---------------------------------------------------------------- rescore (ts_rescore.hip)
+// Exact scores of gathered candidates: query q of the chunk is column col0 + q of the pass's query image (qh halves per
+// k group); scores[q * C + c] = its inner product with candidate c over all kg groups in ascending order (the scan's
+// numbers), ids_out[q * C + c] = ids[q * C + c]; an invalid candidate gets -FLT_MAX and -1.  f16 / bf16 storage.
+struct TsRescoreParams {
+  const uint4* tile;       // [nq][cbp][kg][64]
+  const int32_t* valid;    // [nq][32 * cbp]
+  const int64_t* ids;      // [nq][C]
+  const uint4* qimg;
+  int kg, qh, C, cbp, col0;
+  float* scores;           // [nq][C]
+  int64_t* ids_out;        // [nq][C]
+};
+int ts_launch_rescore(const TsLayout& L, const TsRescoreParams& p, int nq, hipStream_t stream);

@@ -213,6 +213,10 @@ struct ts_index {
   std::mutex range_mu;
   // MMR (ts_index_mmr): scratch and staging, allocated at the first call
   TsMmrWork mmr;
+  // rescore (ts_index_rescore): candidate tiles, scores and ids of one chunk of queries, allocated at
+  // the first call; rescore_mu serialises the calls on the handle
+  DevBuf rescore_scratch;
+  std::mutex rescore_mu;
 };
 
 static int co_flush(ts_index* h, hipStream_t s);
@@ -370,7 +374,7 @@ extern "C" int ts_index_destroy(ts_index* h) {
     if (e) (void)hipEventDestroy(e);
   if (h->co_ev) (void)hipEventDestroy(h->co_ev);
   DevBuf* rb[] = {&h->live, &h->eff, &h->rids, &h->compact_scratch, &h->compact_stage, &h->upd_tile, &h->upd_tab,
-                  &h->rng_s, &h->rng_i, &h->rng_tiles};
+                  &h->rng_s, &h->rng_i, &h->rng_tiles, &h->rescore_scratch};
   for (DevBuf* b : rb) release(*b);
   if (h->eff_ev) (void)hipEventDestroy(h->eff_ev);
   ts_mmr_release(h->mmr);
@@ -569,8 +573,19 @@ struct MaskCtx {
   TsMaskPass mp;
 };
 
+// A scan of the whole rows (pkg == 0) or of the first pkg k groups of every row (ts_index_search_prefix): the same
+// parameters, the prefix scans add the pitch of the row blocks.
+static int scan_rows(ts_index* h, int pkg, int mode, int qh, const ScanParams& sp, int cus, hipStream_t s) {
+  if (!pkg) return ts_launch_scan(h->L, mode, qh, sp, cus, s);
+  PrefixScanParams pp{};
+  static_cast<ScanParams&>(pp) = sp;
+  pp.kg = pkg;
+  pp.kg_row = h->L.kg;
+  return ts_launch_scan_prefix(h->L, mode, qh, pp, cus, s);
+}
+
 static int dense_path(ts_index* h, ts_index::WSet& W, int nq, int qh, int k, float* out_s,
-                      int64_t* out_i, hipStream_t s, const MaskCtx* mc = nullptr) {
+                      int64_t* out_i, hipStream_t s, const MaskCtx* mc = nullptr, int pkg = 0) {
   const int64_t N = h->ntotal;
   const int64_t nblk = (N + TS_ROWS_PER_BLOCK - 1) / TS_ROWS_PER_BLOCK;
   const int64_t chunk_rows = std::min<int64_t>(kDenseChunkRows, nblk * TS_ROWS_PER_BLOCK);
@@ -595,7 +610,7 @@ static int dense_path(ts_index* h, ts_index::WSet& W, int nq, int qh, int k, flo
     sp.ntotal = N;
     sp.dense = (float*)W.dense.p;
     sp.dense_ld = chunk_rows;
-    TS_CHECK(ts_launch_scan(h->L, SCAN_DENSE, qh, sp, h->num_cus, s));
+    TS_CHECK(scan_rows(h, pkg, SCAN_DENSE, qh, sp, h->num_cus, s));
     SelParams p{};
     p.mode = SEL_DENSE;
     p.scores = (const float*)W.dense.p;
@@ -786,15 +801,17 @@ static void set_info(ts_index* h, int64_t a, int64_t b, int64_t c, int64_t d) {
 }
 
 static int search_pass_on(ts_index* h, ts_index::WSet& W, const void* dq, int nq, int q_dtype, int k,
-                          float* out_s, int64_t* out_i, uint32_t flags, hipStream_t s, const MaskCtx* mc);
+                          float* out_s, int64_t* out_i, uint32_t flags, hipStream_t s, const MaskCtx* mc, int pkg);
 
+// pkg > 0 (ts_index_search_prefix): the pass ranks on the first pkg k groups of every row; dq holds 16 * pkg elements
+// per query
 static int search_pass(ts_index* h, const void* dq, int nq, int q_dtype, int k, float* out_s,
-                       int64_t* out_i, uint32_t flags, hipStream_t s, const MaskCtx* mc = nullptr) {
+                       int64_t* out_i, uint32_t flags, hipStream_t s, const MaskCtx* mc = nullptr, int pkg = 0) {
   // per-phase timing shares one set of events per handle: profiled searches run one at a time
   std::unique_lock<std::mutex> plk(h->prof_mu, std::defer_lock);
   if (h->profiling) plk.lock();
   ts_index::WSet* W = acquire_set(h);
-  const int st = search_pass_on(h, *W, dq, nq, q_dtype, k, out_s, out_i, flags, s, mc);
+  const int st = search_pass_on(h, *W, dq, nq, q_dtype, k, out_s, out_i, flags, s, mc, pkg);
   release_set(h, W);
   return st;
 }
@@ -813,7 +830,7 @@ static void add_filter_info(ts_index* h, int64_t fseq, int64_t live, int64_t blo
 // TS_FLAG_NO_FILTER, fallback).
 
 static int search_pass_on(ts_index* h, ts_index::WSet& W, const void* dq, int nq, int q_dtype, int k,
-                          float* out_s, int64_t* out_i, uint32_t flags, hipStream_t s, const MaskCtx* mc) {
+                          float* out_s, int64_t* out_i, uint32_t flags, hipStream_t s, const MaskCtx* mc, int pkg) {
   const int64_t N = h->ntotal;
   const int64_t nblk = (N + TS_ROWS_PER_BLOCK - 1) / TS_ROWS_PER_BLOCK;
   const int qh = nq > 32 ? 2 : 1;
@@ -825,11 +842,14 @@ static int search_pass_on(ts_index* h, ts_index::WSet& W, const void* dq, int nq
     std::lock_guard<std::mutex> lk(h->mu);
     fseq = h->fseq;
   }
-  if (h->L.dtype == TS_FP8_E4M3) {
-    // e4m3 storage has the five-launch kernels only (ts_scan_fp8.hip): as for a masked pass
+  if (h->L.dtype == TS_FP8_E4M3 || pkg) {
+    // e4m3 storage and the prefix scans have the five-launch kernels only (ts_scan_fp8.hip, ts_scan_prefix.hip): as
+    // for a masked pass
     flags &= ~(uint32_t)(TS_FLAG_ONE_LAUNCH | TS_FLAG_PIPELINE);
     flags |= TS_FLAG_CLASSIC;
   }
+  // the layout of the pass's query image: the index's, or that of the prefix's dimensions
+  const TsLayout QL = pkg ? ts_make_layout(16 * pkg, h->L.dtype) : h->L;
   const bool filter = !(flags & TS_FLAG_NO_FILTER) && k <= kMaxFilterK && N >= kMinFilterRows &&
                       N >= 32 * (int64_t)k && !(mc && h->L.dtype == TS_F32);
   const bool async = (flags & TS_FLAG_ASYNC) != 0;
@@ -861,12 +881,12 @@ static int search_pass_on(ts_index* h, ts_index::WSet& W, const void* dq, int nq
   pc.now = h->profiling && (h->prof_seq.fetch_add(1, std::memory_order_relaxed) % (uint64_t)h->prof_every == 0);
   pc.scan_only = async;
   prof_mark(h, pc, 0, sP);
-  if (!fused) TS_CHECK(ts_launch_qprep(h->L, dq, q_dtype, nq, qh, (uint4*)W.qimg.p, W.cand_cnt(), W.status(), sP));
+  if (!fused) TS_CHECK(ts_launch_qprep(QL, dq, q_dtype, nq, qh, (uint4*)W.qimg.p, W.cand_cnt(), W.status(), sP));
   if (!filter) {
     set_info(h, 0, 0, 0, 0);
     if (mc) add_filter_info(h, fseq, nblk, nblk, true);
     prof_mark(h, pc, 5, s);
-    TS_CHECK(dense_path(h, W, nq, qh, k, out_s, out_i, s, mc));
+    TS_CHECK(dense_path(h, W, nq, qh, k, out_s, out_i, s, mc, pkg));
     prof_mark(h, pc, -1, s);
     TS_HIP(hipEventRecord(W.ev_sel, s));
     W.used = true;
@@ -962,7 +982,7 @@ static int search_pass_on(ts_index* h, ts_index::WSet& W, const void* dq, int nq
   sp.dense = (float*)W.sample.p;
   sp.dense_ld = S;
   prof_mark(h, pc, 1, sP);
-  TS_CHECK(ts_launch_scan(h->L, SCAN_DENSE, qh, sp, h->num_cus, sP));
+  TS_CHECK(scan_rows(h, pkg, SCAN_DENSE, qh, sp, h->num_cus, sP));
   prof_mark(h, pc, 2, sP);
   // (2) per-query threshold = ~m-th best sample score
 #ifdef TS_TUNING  // ablation builds only (tools/variants.sh): thresholds = +inf, nothing survives
@@ -1013,9 +1033,17 @@ static int search_pass_on(ts_index* h, ts_index::WSet& W, const void* dq, int nq
     mp.allow_bits = mc->bits;
     mp.allow_words = mc->words;
     mp.qmask = md->qmask;
+    if (pkg) {
+      PrefixMaskedScanParams pp{};
+      static_cast<MaskedScanParams&>(pp) = mp;
+      pp.kg = pkg;
+      pp.kg_row = h->L.kg;
+      TS_CHECK(ts_launch_scan_prefix_masked(h->L, qh, pp, scan_cus, sS));
+    } else {
     TS_CHECK(ts_launch_scan_masked(h->L, qh, mp, scan_cus, sS));
+    }
   } else {
-  TS_CHECK(ts_launch_scan(h->L, SCAN_FILTER, qh, sp, scan_cus, sS));
+  TS_CHECK(scan_rows(h, pkg, SCAN_FILTER, qh, sp, scan_cus, sS));
   }
   prof_mark(h, pc, 4, sS);
   }  // five launches
@@ -1109,7 +1137,7 @@ static int search_pass_on(ts_index* h, ts_index::WSet& W, const void* dq, int nq
       TS_CHECK(ts_launch_qprep(h->L, dq, q_dtype, nq, qh, (uint4*)W.qimg.p, W.cand_cnt(), W.status(), s));
     }
     prof_mark(h, pc, 5, s);
-    TS_CHECK(dense_path(h, W, nq, qh, k, out_s, out_i, s, mc));
+    TS_CHECK(dense_path(h, W, nq, qh, k, out_s, out_i, s, mc, pkg));
     prof_mark(h, pc, -1, s);
     TS_HIP(hipStreamSynchronize(s));
     prof_collect(h, pc);
@@ -1486,10 +1514,11 @@ extern "C" int ts_index_search(ts_index* h, const void* queries, int32_t nq, int
 
 // Filtered search (include/tristage.h): ts_index_search restricted, per query, to the rows of one of
 // n_masks bitmaps.  A pass whose queries have no mask is an ordinary ts_index_search pass.
-extern "C" int ts_index_search_filtered(ts_index* h, const void* queries, int32_t nq, int32_t q_dtype, int32_t k,
-                                        const uint32_t* allow_bits, int64_t allow_words, int32_t n_masks,
-                                        const int32_t* mask_of_query, float* out_scores, int64_t* out_ids,
-                                        uint32_t flags, void* stream) {
+// pdims > 0: ts_index_search_prefix, the same call ranked on the first pdims dimensions (queries of pdims elements)
+static int search_filtered_impl(ts_index* h, const void* queries, int32_t nq, int32_t q_dtype, int32_t k,
+                                const uint32_t* allow_bits, int64_t allow_words, int32_t n_masks,
+                                const int32_t* mask_of_query, float* out_scores, int64_t* out_ids,
+                                uint32_t flags, void* stream, int pdims) {
   // the checks that need no handle come first (and none of them touches the GPU)
   if (nq < 0 || k <= 0 || !dtype_ok(q_dtype) || (nq > 0 && (!queries || !out_scores || !out_ids))) {
     ts_set_error("bad arguments to search_filtered");
@@ -1532,7 +1561,8 @@ extern "C" int ts_index_search_filtered(ts_index* h, const void* queries, int32_
   }
   bool any = false;
   for (int32_t q = 0; q < nq && !any; ++q) any = mask_of_query[q] >= 0;
-  if (!any && h->nremoved == 0) return ts_index_search(h, queries, nq, q_dtype, k, out_scores, out_ids, flags, stream);
+  if (!any && h->nremoved == 0 && !pdims)
+    return ts_index_search(h, queries, nq, q_dtype, k, out_scores, out_ids, flags, stream);
   DeviceGuard g(h->device);
   hipStream_t s = (hipStream_t)stream;
   TS_CHECK(co_flush(h, s));   // a filtered search never joins a coalesced pass
@@ -1546,7 +1576,7 @@ extern "C" int ts_index_search_filtered(ts_index* h, const void* queries, int32_
       return TS_ERR_INVALID;
     }
   }
-  const size_t qrow = (size_t)h->L.dim * dtype_size(q_dtype);
+  const size_t qrow = (size_t)(pdims ? pdims : h->L.dim) * dtype_size(q_dtype);
   const void* dq = queries;
   float* ds = out_scores;
   int64_t* di = out_ids;
@@ -1605,7 +1635,7 @@ extern "C" int ts_index_search_filtered(ts_index* h, const void* queries, int32_
       mc.mp.qd[j] = d;
     }
     TS_CHECK(search_pass(h, (const char*)dq + (size_t)q0 * qrow, c, q_dtype, k, ds + (size_t)q0 * k,
-                         di + (size_t)q0 * k, flags, s, masked ? &mc : nullptr));
+                         di + (size_t)q0 * k, flags, s, masked ? &mc : nullptr, pdims / 16));
   }
   if (elk.owns_lock()) {
     TS_HIP(hipEventRecord(h->eff_ev, s));
@@ -1620,6 +1650,134 @@ extern "C" int ts_index_search_filtered(ts_index* h, const void* queries, int32_
     TS_HIP(hipMemcpyAsync(out_ids, di, (size_t)nq * k * 8, hipMemcpyDeviceToHost, s));
     TS_HIP(hipStreamSynchronize(s));
   }
+  return TS_OK;
+}
+
+extern "C" int ts_index_search_filtered(ts_index* h, const void* queries, int32_t nq, int32_t q_dtype, int32_t k,
+                                        const uint32_t* allow_bits, int64_t allow_words, int32_t n_masks,
+                                        const int32_t* mask_of_query, float* out_scores, int64_t* out_ids,
+                                        uint32_t flags, void* stream) {
+  return search_filtered_impl(h, queries, nq, q_dtype, k, allow_bits, allow_words, n_masks, mask_of_query, out_scores,
+                              out_ids, flags, stream, 0);
+}
+
+// ---- funnel search (include/tristage.h "funnel search")
+namespace {
+constexpr int kFunnelMaxK = 16384;                   // the select kernels hold 16384 keys in LDS
+constexpr size_t kRescoreScratchCap = 384u << 20;    // candidate tiles, scores and ids of one chunk of queries
+}  // namespace
+
+static int funnel_storage_ok(const ts_index* h, const char* what) {
+  if (h->L.dtype == TS_F16 || h->L.dtype == TS_BF16) return TS_OK;
+  ts_set_error("%s takes f16 / bf16 storage only", what);
+  return TS_ERR_UNSUPPORTED;
+}
+
+extern "C" int ts_index_search_prefix(ts_index* h, const void* queries, int32_t nq, int32_t q_dtype, int32_t dims,
+                                      int32_t k, const uint32_t* allow_bits, int64_t allow_words, int32_t n_masks,
+                                      const int32_t* mask_of_query, float* out_scores, int64_t* out_ids,
+                                      uint32_t flags, void* stream) {
+  if (!h) { ts_set_error("null handle"); return TS_ERR_INVALID; }
+  if (flags & ~(uint32_t)(TS_FLAG_HOST_PTR | TS_FLAG_NO_FILTER)) {
+    ts_set_error("search_prefix: flags 0x%x (only TS_FLAG_HOST_PTR and TS_FLAG_NO_FILTER are accepted)", flags);
+    return TS_ERR_INVALID;
+  }
+  if (nq < 0 || k < 1 || k > kFunnelMaxK) {
+    ts_set_error("search_prefix: nq = %d, k = %d (k must be in 1 .. %d)", nq, k, kFunnelMaxK);
+    return TS_ERR_INVALID;
+  }
+  TS_CHECK(funnel_storage_ok(h, "search_prefix"));
+  if (dims < 128 || dims % 128 != 0 || dims >= h->L.dim) {
+    ts_set_error("search_prefix: dims = %d must be a multiple of 128 in [128, %d)", dims, h->L.dim);
+    return TS_ERR_INVALID;
+  }
+  std::vector<int32_t> none;
+  if (!mask_of_query && nq > 0) {
+    none.assign((size_t)nq, -1);
+    mask_of_query = none.data();
+  }
+  return search_filtered_impl(h, queries, nq, q_dtype, k, allow_bits, allow_words, n_masks, mask_of_query, out_scores,
+                              out_ids, flags, stream, dims);
+}
+
+// Exact scores of given candidates: gather (ts_mmr.hip) -> one wave per 32-candidate tile against the pass's query
+// image (ts_rescore.hip) -> the select, which orders by (score desc, id asc) and drops the entries marked invalid.
+extern "C" int ts_index_rescore(ts_index* h, const void* queries, int32_t nq, int32_t q_dtype, const int64_t* cand_ids,
+                                int32_t ncand, int32_t k, float* out_scores, int64_t* out_ids, void* stream) {
+  if (!h) { ts_set_error("null handle"); return TS_ERR_INVALID; }
+  if (nq < 0 || !dtype_ok(q_dtype) || ncand < 1 || ncand > kFunnelMaxK || k < 1 || k > ncand) {
+    ts_set_error("rescore: nq = %d, ncand = %d (1 .. %d), k = %d (1 .. ncand)", nq, ncand, kFunnelMaxK, k);
+    return TS_ERR_INVALID;
+  }
+  if (nq > 0 && (!queries || !cand_ids || !out_scores || !out_ids)) { ts_set_error("rescore: null pointer"); return TS_ERR_INVALID; }
+  TS_CHECK(funnel_storage_ok(h, "rescore"));
+  if (nq == 0) return TS_OK;
+  if (h->ntotal == 0) { ts_set_error("No documents indexed. Call add_documents() first."); return TS_ERR_EMPTY; }
+  DeviceGuard g(h->device);
+  hipStream_t s = (hipStream_t)stream;
+  TS_CHECK(co_flush(h, s));
+  TsMmrSource src;
+  src.corpus = h->corpus;
+  src.L = h->L;
+  src.ntotal = h->ntotal;
+  src.id_offset = h->id_offset;
+  src.live = h->nremoved > 0 ? (const uint32_t*)h->live.p : nullptr;
+  src.ivf = false;
+  src.id2slot = nullptr;
+  src.blk_valid = nullptr;
+  const int C = ncand, cbp = (C + 31) / 32;
+  const size_t tile_b = (size_t)cbp * h->L.kg * 1024, v_b = (size_t)cbp * 32 * 4, s_b = (size_t)C * 4, i_b = (size_t)C * 8;
+  const size_t per_q = tile_b + v_b + i_b + ((s_b + 15) & ~(size_t)15);
+  const int qp = (ts_scan_lds_bytes(h->L, 2) <= 160 * 1024) ? 64 : 32;  // queries per pass (one query image)
+  const int qc = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(nq, qp), kRescoreScratchCap / per_q));
+  const size_t qrow = (size_t)h->L.dim * dtype_size(q_dtype);
+  std::lock_guard<std::mutex> rlk(h->rescore_mu);   // one scratch per handle; the call ends with the stream drained
+  TS_CHECK(ensure(h->rescore_scratch, per_q * qc));
+  char* base = (char*)h->rescore_scratch.p;
+  uint4* tile = (uint4*)base;
+  int64_t* ids = (int64_t*)(base + tile_b * qc);
+  int32_t* valid = (int32_t*)(base + (tile_b + i_b) * qc);
+  float* sc = (float*)(base + (tile_b + i_b + v_b) * qc);
+  int st = TS_OK;
+  for (int q0 = 0; q0 < nq && st == TS_OK; q0 += qp) {
+    const int c = std::min(qp, nq - q0);
+    const int qh = c > 32 ? 2 : 1;
+    ts_index::WSet* W = acquire_set(h);
+    if (W->used && hipStreamWaitEvent(s, W->ev_sel, 0) != hipSuccess) st = TS_ERR_HIP;
+    if (st == TS_OK)
+      st = ts_launch_qprep(h->L, (const char*)queries + (size_t)q0 * qrow, q_dtype, c, qh, (uint4*)W->qimg.p, nullptr,
+                           nullptr, s);
+    for (int c0 = 0; c0 < c && st == TS_OK; c0 += qc) {
+      const int n = std::min(qc, c - c0);
+      const int64_t* cid = cand_ids + (size_t)(q0 + c0) * C;
+      st = ts_launch_gather_tiles(src, cid, C, cbp, n, tile, valid, s);
+      if (st != TS_OK) break;
+      TsRescoreParams rp{};
+      rp.tile = tile; rp.valid = valid; rp.ids = cid;
+      rp.qimg = (const uint4*)W->qimg.p;
+      rp.kg = h->L.kg; rp.qh = qh; rp.C = C; rp.cbp = cbp; rp.col0 = c0;
+      rp.scores = sc; rp.ids_out = ids;
+      st = ts_launch_rescore(h->L, rp, n, s);
+      if (st != TS_OK) break;
+      SelParams p{};
+      p.mode = SEL_MERGE64;   // the tiebreak is the real id; an entry whose id is -1 has no rank
+      p.scores = sc;
+      p.ids64 = ids;
+      p.stride = C;
+      p.n = (uint32_t)C;
+      p.k = k;
+      p.out_scores = out_scores + (size_t)(q0 + c0) * k;
+      p.out_ids64 = out_ids + (size_t)(q0 + c0) * k;
+      p.out_stride = k;
+      st = ts_launch_select(p, n, s);
+    }
+    if (st == TS_OK && hipEventRecord(W->ev_sel, s) == hipSuccess) W->used = true;   // orders the set's next user behind this pass
+    else if (st == TS_OK) st = TS_ERR_HIP;
+    release_set(h, W);
+  }
+  if (st == TS_ERR_HIP) ts_set_error("HIP call failed in ts_index_rescore");
+  if (st != TS_OK) { (void)hipStreamSynchronize(s); return st; }
+  TS_HIP(hipStreamSynchronize(s));
   return TS_OK;
 }
 

@@ -278,6 +278,23 @@ void ts_mmr_release(TsMmrWork& w) {
   w = TsMmrWork();
 }
 
+// The gather on its own (ts_index_rescore uses it too): candidates ids[q * C + c] of nq queries -> tile[q][cbp][kg][64]
+// and valid[q][32 * cbp]; cbp >= ceil(C / 32).
+int ts_launch_gather_tiles(const TsMmrSource& src, const int64_t* ids, int C, int cbp, int nq, uint4* tile,
+                           int32_t* valid, hipStream_t s) {
+  MmrGatherParams gp;
+  gp.corpus = src.corpus;
+  gp.ids = ids;
+  gp.C = C; gp.cbp = cbp; gp.kg = src.L.kg;
+  gp.ntotal = src.ntotal; gp.id_offset = src.id_offset;
+  gp.live = src.live; gp.id2slot = src.id2slot; gp.blk_valid = src.blk_valid;
+  gp.tile = tile; gp.valid = valid;
+  if (src.ivf) hipLaunchKernelGGL(mmr_gather_kernel<true>, dim3(cbp, nq), dim3(256), 0, s, gp);
+  else hipLaunchKernelGGL(mmr_gather_kernel<false>, dim3(cbp, nq), dim3(256), 0, s, gp);
+  TS_HIP(hipGetLastError());
+  return TS_OK;
+}
+
 static int mmr_ensure(void*& p, size_t& have, size_t bytes) {
   if (p && have >= bytes) return TS_OK;
   if (p) { TS_HIP(hipFree(p)); p = nullptr; have = 0; }   // (hipFree waits for the work that still reads it)
@@ -342,17 +359,8 @@ int ts_mmr_run(const TsMmrSource& src, TsMmrWork& w, const int64_t* cand_ids, co
       if (!e) TS_HIP(hipEventCreate(&e));
   for (int q0 = 0; q0 < nq; q0 += qc) {
     const int n = std::min(qc, nq - q0);
-    MmrGatherParams gp;
-    gp.corpus = src.corpus;
-    gp.ids = d_ids + (size_t)q0 * C;
-    gp.C = C; gp.cbp = cbp; gp.kg = L.kg;
-    gp.ntotal = src.ntotal; gp.id_offset = src.id_offset;
-    gp.live = src.live; gp.id2slot = src.id2slot; gp.blk_valid = src.blk_valid;
-    gp.tile = tile; gp.valid = valid;
     if (w.timing) TS_HIP(hipEventRecord(w.tev[0], s));
-    if (src.ivf) hipLaunchKernelGGL(mmr_gather_kernel<true>, dim3(cbp, n), dim3(256), 0, s, gp);
-    else hipLaunchKernelGGL(mmr_gather_kernel<false>, dim3(cbp, n), dim3(256), 0, s, gp);
-    TS_HIP(hipGetLastError());
+    TS_CHECK(ts_launch_gather_tiles(src, d_ids + (size_t)q0 * C, C, cbp, n, tile, valid, s));
     if (w.timing) TS_HIP(hipEventRecord(w.tev[1], s));
     switch (L.dtype) {
       case TS_F16: TS_CHECK(launch_gram<TS_F16>((const u32x4*)tile, S, cbp, L.kg, scale, n, s)); break;

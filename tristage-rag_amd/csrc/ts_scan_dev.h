@@ -200,6 +200,8 @@ __device__ __forceinline__ void flush_stage(const ScanParams& p, SL* st, int tid
 //   wave(tid)                the wave in the workgroup (masked walks: through readfirstlane, their loads are scalar)
 //   nwork(p)                 work items of the launch
 //   block(p, w), idle(p)     a work item's row block; the block whose address an idle wave forms and never loads
+//   row_groups(p)            k groups between the starts of consecutive row blocks (p.kg groups of each are scanned: the
+//                            prefix walks of ts_scan_prefix.hip scan fewer than a row block holds)
 //   mask_init / mask_fetch / mask_advance (kMasked): the allow words of the first block; the request for the next
 //                            block's, just before the tail's loads; next -> current, after the epilogue.  The state,
 //                            per query half hq, is arrays of the kernel body:
@@ -246,6 +248,7 @@ struct WalkStrided {
   static __device__ __forceinline__ int64_t nwork(const Params& p) { return p.nwork; }
   static __device__ __forceinline__ int64_t block(const Params& p, int64_t i) { return p.blk0 + i * p.blk_stride; }
   static __device__ __forceinline__ int64_t idle(const Params& p) { return p.blk0; }
+  static __device__ __forceinline__ int row_groups(const Params& p) { return p.kg; }
 };
 
 // Filtered searches: work item w is row block p.live[w], w < *p.nlive.  Both are read with scalar loads (constant
@@ -263,6 +266,7 @@ struct WalkLive {
     return (int64_t)((ts_sgpr_i32p)p.live)[i];
   }
   static __device__ __forceinline__ int64_t idle(const Params&) { return 0; }
+  static __device__ __forceinline__ int row_groups(const Params& p) { return p.kg; }
   template <int QH>
   static __device__ __forceinline__ void mask_init(const Params& p, int64_t blk, int lane, const uint32_t* (&mrow)[QH],
                                                    int64_t (&mstep)[QH], uint32_t (&mor)[QH], uint32_t (&mw)[QH]) {
@@ -328,7 +332,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_kernel(typename WALK::Param
   const int64_t nwork = WALK::nwork(p);
   const bool active = w < nwork;  // (waves without work still join the final flush)
   const u32x4* base = reinterpret_cast<const u32x4*>(p.corpus) + lane;
-  const size_t blk_units = (size_t)kg * 64;
+  const size_t blk_units = (size_t)WALK::row_groups(p) * 64;
   int64_t blk = active ? WALK::block(p, w) : WALK::idle(p);
   const u32x4* cur = base + (size_t)blk * blk_units;
   u32x4 ring[TS_RING];

@@ -163,6 +163,36 @@ def _mmr_call(ix, entry: str, ids, relevance, k, lambda_mult):
     return D, I
 
 
+FUNNEL_MAX_FETCH = 16384   # shortlist entries per query of the funnel: the select kernels hold 16384 keys in LDS
+
+
+def funnel_default_fetch_k(k: int) -> int:
+    """The shortlist ``search_funnel`` fetches when ``fetch_k`` is not given (at most 2048: the prefix pass's filter path)."""
+    return min(2048, max(8 * int(k), 128))
+
+
+def funnel_check(d: int, dims, k, fetch_k=None):
+    """The argument checks of ``search_prefix`` / ``search_funnel`` (``ValueError``), made before anything is launched:
+    ``dims`` a multiple of 128 in [128, d), ``1 <= k (<= fetch_k) <= 16384``.  Returns the ints."""
+    if isinstance(dims, bool) or int(dims) != dims:
+        raise ValueError(f"dims must be an integer, got {dims!r}")
+    dims, k = int(dims), int(k)
+    if dims % 128 != 0 or not 128 <= dims < int(d):
+        raise ValueError(f"dims={dims} must be a multiple of 128 in [128, {int(d)})")
+    if k < 1:
+        raise ValueError("k must be positive")
+    if fetch_k is None:
+        if k > FUNNEL_MAX_FETCH:
+            raise ValueError(f"k={k} exceeds {FUNNEL_MAX_FETCH}")
+        return k, dims
+    fetch_k = int(fetch_k)
+    if fetch_k < k:
+        raise ValueError(f"fetch_k={fetch_k} is below k={k}: the rescore picks k out of fetch_k candidates")
+    if fetch_k > FUNNEL_MAX_FETCH:
+        raise ValueError(f"fetch_k={fetch_k} exceeds {FUNNEL_MAX_FETCH}")
+    return k, dims, fetch_k
+
+
 GROUP_MAX_FETCH = 16384   # entries per query of group_topk(): one workgroup sorts the list in LDS (the select limit)
 
 
@@ -1032,6 +1062,137 @@ class FlatIPIndex:
     def last_group_info(self) -> dict:
         """``{"fetched", "rounds", "n_groups", "complete"}`` of the last :meth:`search_grouped` (the last two per query)."""
         return dict(getattr(self, "_group_info", {}))
+
+    # -- funnel search (DESIGN.md 4.21) ----------------------------------------
+    def _funnel_storage(self, what: str) -> None:
+        if self.storage_dtype not in ("f16", "bf16"):
+            raise NotImplementedError(f"{what} takes an f16 or bf16 index, not {self.storage_dtype}")
+
+    def search_prefix(self, q, k: int, dims: int, allowed=None, exact_dense: bool = False):
+        """Top-``k`` on the inner product over the first ``dims`` components only: ``q`` is the full ``[B, d]`` query,
+        the pass uses ``q[:, :dims]`` and reads the first ``dims / 16`` KiB of every 32-row block.  Stored rows are used
+        as they are (nothing is renormalised).  The result is, bit for bit and id for id, what ``search(q[:, :dims], k,
+        allowed=allowed)`` returns on an index of ``dims`` dimensions holding ``reconstruct_n()[:, :dims]`` under the same
+        ids with the same rows removed.  ``dims % 128 == 0``, ``128 <= dims < d``, ``k <= 16384`` (``ValueError``
+        otherwise); f16 / bf16 storage.  Synchronous, on the current stream.  numpy in -> numpy out; CUDA tensor in ->
+        tensors out.  ``allowed``: every form :meth:`search` takes."""
+        self._funnel_storage("search_prefix")
+        k, dims = funnel_check(self.d, dims, k)
+        if self.ntotal == 0:
+            raise ValueError("No documents indexed. Call add_documents() first.")
+        if q.ndim != 2 or q.shape[1] != self.d:
+            raise ValueError(f"expected [B, {self.d}] queries, got {tuple(q.shape)}")
+        B = int(q.shape[0])
+        flags = _lib.TS_FLAG_NO_FILTER if exact_dense else 0
+        on_gpu = _is_tensor(q) and q.is_cuda
+        words = (self.ntotal + 31) // 32
+        bits = dev_bits = moq = None
+        if allowed is not None:
+            if getattr(allowed, "ndim", 1) == 2:
+                allowed = list(allowed)
+            if on_gpu:
+                dev_bits = self._device_masks(allowed, B, words, q.device)
+            if dev_bits is None:
+                bits, words, moq = self._masks(allowed, B)
+        if on_gpu:
+            torch = _torch()
+            qp = q[:, :dims].contiguous()
+            D = torch.empty((B, k), dtype=torch.float32, device=q.device)
+            I = torch.empty((B, k), dtype=torch.int64, device=q.device)
+            if dev_bits is not None:
+                dbits, moq = dev_bits
+            elif bits is not None:
+                dbits = torch.from_numpy(bits.view(np.int32)).to(q.device)
+            q_ptr, q_dt, b_ptr = qp.data_ptr(), _tensor_dtype(qp), (dbits.data_ptr() if allowed is not None else 0)
+            d_ptr, i_ptr, stream = D.data_ptr(), I.data_ptr(), _stream_ptr(self.device)
+        else:
+            if _is_tensor(q):
+                q = q.detach().float().numpy()
+            qp = np.ascontiguousarray(q[:, :dims])
+            if qp.dtype not in _NP_DTYPES:
+                qp = qp.astype(np.float32)
+            D = np.empty((B, k), dtype=np.float32)
+            I = np.empty((B, k), dtype=np.int64)
+            q_ptr, q_dt, b_ptr = qp.ctypes.data, _NP_DTYPES[qp.dtype], (bits.ctypes.data if bits is not None else 0)
+            d_ptr, i_ptr, stream = D.ctypes.data, I.ctypes.data, 0
+            flags |= _lib.TS_FLAG_HOST_PTR
+        n_masks = (int(moq.max()) + 1 if moq.size else 0) if moq is not None else 0
+        code = self._lib.ts_index_search_prefix(
+            self._h, ctypes.c_void_p(q_ptr), B, q_dt, dims, k, ctypes.c_void_p(b_ptr) if n_masks else None,
+            int(words) if n_masks else 0, n_masks, moq.ctypes.data_as(ctypes.c_void_p) if moq is not None else None,
+            ctypes.c_void_p(d_ptr), ctypes.c_void_p(i_ptr), flags, ctypes.c_void_p(stream) if stream else None)
+        if code == _lib.TS_ERR_INVALID:
+            raise ValueError(_lib.last_error())
+        _lib.check(code)
+        return D, I
+
+    def rescore(self, q, ids, k: Optional[int] = None):
+        """Exact full-dimension scores of given candidates: ``ids`` int64 ``[B, C]`` (numpy or a CUDA tensor, ids as
+        :meth:`search` returns them, ``C <= 16384``) -> ``(D, I)`` ``[B, k]``, ``k = C`` by default.  Per query the valid
+        entries ordered by score descending, then id ascending; entries that are -1, out of range or removed become
+        -1 / -FLT_MAX at the end; a duplicate id stays a duplicate.  Every score is bit-identical to
+        ``scores(q)[b, id]``, and so to :meth:`search`.  Synchronous, on the current stream; tensors out when ``q`` or
+        ``ids`` is a CUDA tensor, numpy otherwise."""
+        self._funnel_storage("rescore")
+        if q.ndim != 2 or q.shape[1] != self.d:
+            raise ValueError(f"expected [B, {self.d}] queries, got {tuple(q.shape)}")
+        if ids.ndim != 2 or ids.shape[0] != q.shape[0]:
+            raise ValueError(f"expected ids [B, C] with B = {q.shape[0]}, got {tuple(ids.shape)}")
+        B, C = int(ids.shape[0]), int(ids.shape[1])
+        k = C if k is None else int(k)
+        if not 1 <= C <= FUNNEL_MAX_FETCH:
+            raise ValueError(f"rescore takes 1 .. {FUNNEL_MAX_FETCH} candidates per query, got {C}")
+        if not 1 <= k <= C:
+            raise ValueError(f"k={k} must be in 1 .. C = {C}")
+        if self.ntotal == 0:
+            raise ValueError("No documents indexed. Call add_documents() first.")
+        torch = _torch()
+        dev = torch.device("cuda", self.device)
+        was_np = not ((_is_tensor(q) and q.is_cuda) or (_is_tensor(ids) and ids.is_cuda))
+        if not _is_tensor(q):
+            q = np.ascontiguousarray(q)
+            q = torch.from_numpy(q if q.dtype in _NP_DTYPES else q.astype(np.float32))
+        if q.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+            q = q.float()
+        qt = q.to(dev).contiguous()
+        it = (ids if _is_tensor(ids) else torch.from_numpy(np.ascontiguousarray(ids, dtype=np.int64)))
+        it = it.to(device=dev, dtype=torch.int64).contiguous()
+        D = torch.empty((B, k), dtype=torch.float32, device=dev)
+        I = torch.empty((B, k), dtype=torch.int64, device=dev)
+        if B:
+            stream = _stream_ptr(self.device)
+            code = self._lib.ts_index_rescore(
+                self._h, ctypes.c_void_p(qt.data_ptr()), B, _tensor_dtype(qt), ctypes.c_void_p(it.data_ptr()), C, k,
+                ctypes.c_void_p(D.data_ptr()), ctypes.c_void_p(I.data_ptr()), ctypes.c_void_p(stream) if stream else None)
+            if code == _lib.TS_ERR_INVALID:
+                raise ValueError(_lib.last_error())
+            _lib.check(code)
+        return (D.cpu().numpy(), I.cpu().numpy()) if was_np else (D, I)
+
+    def search_funnel(self, q, k: int, dims: int, fetch_k: Optional[int] = None, allowed=None):
+        """Funnel retrieval: ``rescore(q, search_prefix(q, fetch_k, dims, allowed)[1], k)`` on one stream; no row and no
+        list leaves the GPU between the passes.  The scores are the exact scores of :meth:`search`; a row of the exact
+        top ``k`` is missed only when its prefix score ranks behind place ``fetch_k``.  ``fetch_k`` defaults to
+        ``min(2048, max(8 k, 128))`` (the filter path of the prefix pass); ``k <= fetch_k <= 16384``.
+        :meth:`last_funnel_info` describes the call."""
+        self._funnel_storage("search_funnel")
+        k, dims, fetch_k = funnel_check(self.d, dims, k, funnel_default_fetch_k(k) if fetch_k is None else fetch_k)
+        was_np = not (_is_tensor(q) and q.is_cuda)
+        if was_np:
+            torch = _torch()
+            qn = np.ascontiguousarray(q.detach().cpu().numpy() if _is_tensor(q) else q)
+            q = torch.from_numpy(qn if qn.dtype in _NP_DTYPES else qn.astype(np.float32)).to(torch.device("cuda", self.device))
+        _, cand = self.search_prefix(q, fetch_k, dims, allowed=allowed)
+        path = "filter" if self.last_search_info()["path"] == "filter" else "dense"
+        D, I = self.rescore(q, cand, k)
+        self._funnel_info = {"dims": dims, "fetch_k": fetch_k, "prefix_path": path}
+        return (D.cpu().numpy(), I.cpu().numpy()) if was_np else (D, I)
+
+    def last_funnel_info(self) -> dict:
+        """``{"dims", "fetch_k", "prefix_path"}`` of the last :meth:`search_funnel`; ``prefix_path`` is ``"filter"`` when
+        the prefix pass's threshold filter gave the shortlist, ``"dense"`` when the dense path did (small corpora,
+        ``fetch_k > 2048``, or the exact fallback)."""
+        return dict(getattr(self, "_funnel_info", {}))
 
     def reconstruct_n(self, i0: int = 0, n: Optional[int] = None) -> np.ndarray:
         """Rows [i0, i0+n) as float32 (after storage rounding)."""
@@ -1908,6 +2069,15 @@ class IVFFlatIndex:
         k, fetch_k, lam = mmr_check(k, mmr_default_fetch_k(k) if fetch_k is None else fetch_k, lambda_mult)
         D, I = self.search(q, fetch_k, nprobe=nprobe)
         return self.mmr(I, D, k, lam)
+
+    def search_prefix(self, q, k: int, dims: int, allowed=None):
+        raise NotImplementedError("funnel search is not supported on an IVF index (its lists hold whole rows; use a flat index)")
+
+    def rescore(self, q, ids, k: Optional[int] = None):
+        raise NotImplementedError("funnel search is not supported on an IVF index (its lists hold whole rows; use a flat index)")
+
+    def search_funnel(self, q, k: int, dims: int, fetch_k: Optional[int] = None, allowed=None):
+        raise NotImplementedError("funnel search is not supported on an IVF index (its lists hold whole rows; use a flat index)")
 
     def search_grouped(self, q, k: int, groups, group_size: int = 1, fetch_k: Optional[int] = None,
                        nprobe: Optional[int] = None):

@@ -92,6 +92,9 @@ class PipelineConfig:
     group_by: Any = None                     # None: off.  A metadata key or an integer array over the documents: stage 1
                                              # returns the stage1_top_k best GROUPS, at most group_size documents of each, so
     group_size: int = 1                      # stages 2 and 3 and the final list see no more of any group
+    stage1_funnel_dims: Optional[int] = None     # None: off.  A multiple of 128 below stage 1's embedding dimension: its dense
+                                                 # candidates are ranked on that prefix of the dimensions and a shortlist is
+    stage1_funnel_fetch_k: Optional[int] = None  # rescored exactly; the shortlist, None: min(2048, max(8 k, 128))
     passage_window: Optional[int] = None     # None: off.  Tokens of the best passage every final record then carries
                                              # under "passage" (windowed MaxSim over the stage-2 tokens)
 
@@ -190,7 +193,7 @@ class RetrievalPipeline:
                 enable_bm25=c.stage1_enable_bm25, bm25_top_k=c.stage1_bm25_top_k,
                 fusion_method=c.stage1_fusion_method, use_fp16=c.stage1_use_fp16,
                 index_dtype=c.stage1_index_dtype, bm25_on_gpu=c.stage1_bm25_on_gpu,
-                bm25_refit_compat=c.stage1_bm25_refit_compat,
+                bm25_refit_compat=c.stage1_bm25_refit_compat, funnel_fetch_k=c.stage1_funnel_fetch_k,
                 use_hip_graph=c.use_hip_graphs, index_batch_size=c.stage1_index_batch_size, amp_dtype=c.amp_dtype))
             self.logger.info("Stage 1 initialized")
             self.stage2 = ColBERTScorer(Stage2Config(
@@ -341,6 +344,15 @@ class RetrievalPipeline:
             raise ValueError(f"group_size must be positive, got {group_size}")
         return {"group_by": group_by, "group_size": int(group_size)}
 
+    def _funnel_kwargs(self, funnel_dims, lam, gkw) -> Dict[str, Any]:
+        """The funnel of a search as a keyword argument for stage 1 (the argument, else the config); {}: off."""
+        dims = self.config.stage1_funnel_dims if funnel_dims is None else funnel_dims
+        if dims is None:
+            return {}
+        if lam is not None or gkw:
+            raise ValueError("funnel_dims cannot be combined with mmr_lambda or group_by")
+        return {"funnel_dims": int(dims)}
+
     def _diversify(self, outs: List[Dict[str, Any]], top_k: int, lam: float) -> List[Dict[str, Any]]:
         """``results`` of each output (the whole list stage 3 returned) -> its ``top_k`` picks by maximal marginal
         relevance, in selection order: relevance = stage3_score as f32, similarity = the inner product of the rows the
@@ -412,7 +424,7 @@ class RetrievalPipeline:
         return outs
 
     def search(self, query: str, top_k: Optional[int] = None, filter=None, mmr_lambda=None,
-               group_by=None, group_size: int = 1, passages=None) -> Dict[str, Any]:
+               group_by=None, group_size: int = 1, passages=None, funnel_dims: Optional[int] = None) -> Dict[str, Any]:
         """``filter``: search only the documents it allows (Stage1Retriever.filter_mask: a metadata dict, a
         callable, document indices or a bool array).  Stages 2 and 3 rescore stage 1's candidates, so fewer
         than ``top_k`` results come back when fewer documents are allowed, and none when none are.
@@ -426,16 +438,21 @@ class RetrievalPipeline:
         ``passages`` (an int window in tokens; default: the config's ``passage_window``, None = off): stages 1 to 3
         run as without it, then every record of the final list — after MMR or grouping if those are on — gains
         ``"passage": {"token_start", "token_end" (exclusive), "score", "char_start", "char_end", "text"}`` (see
-        :meth:`_add_passages`; the character fields are None for a tokenizer without offsets)."""
+        :meth:`_add_passages`; the character fields are None for a tokenizer without offsets).
+        ``funnel_dims`` (default: the config's ``stage1_funnel_dims``, None = off): stage 1's dense candidates come from
+        the funnel (Stage1Retriever.search); it replaces only that search, so ``filter`` and BM25 fusion work unchanged.
+        Not together with ``mmr_lambda`` or ``group_by``: ``ValueError``."""
         if not self.stage1 or not self.stage2 or not self.stage3:
             self.initialize_stages()
         pw = self._passage_window(passages)
         if pw is not None:
             return self._add_passages([self.search(query, top_k, filter=filter, mmr_lambda=mmr_lambda, group_by=group_by,
-                                                   group_size=group_size, passages=_NO_PASSAGES)], pw)[0]
+                                                   group_size=group_size, passages=_NO_PASSAGES,
+                                                   funnel_dims=funnel_dims)], pw)[0]
         top_k = top_k or self.config.stage3_top_k
         lam = self._mmr_lambda(mmr_lambda)
         gkw = self._group_kwargs(group_by, group_size, lam)
+        gkw.update(self._funnel_kwargs(funnel_dims, lam, gkw))
         if lam is not None:
             return self._diversify([self.search(query, _ALL_RESULTS, filter=filter, mmr_lambda=_NO_MMR,
                                                 passages=_NO_PASSAGES)], top_k, lam)[0]
@@ -459,10 +476,12 @@ class RetrievalPipeline:
             raise
 
     def batch_search(self, queries: List[str], top_k: Optional[int] = None, filter=None,
-                     mmr_lambda=None, group_by=None, group_size: int = 1, passages=None) -> List[Dict[str, Any]]:
+                     mmr_lambda=None, group_by=None, group_size: int = 1, passages=None,
+                     funnel_dims: Optional[int] = None) -> List[Dict[str, Any]]:
         """Sequential, like the reference (:444-448); see search_many for the batched form.  ``filter``: one
         filter for every query or a list with one per query.  ``mmr_lambda``, ``group_by`` / ``group_size``: as for
-        :meth:`search`.  ``passages``: as for :meth:`search`, one kernel call for the batch."""
+        :meth:`search`.  ``passages``: as for :meth:`search`, one kernel call for the batch.  ``funnel_dims``: as for
+        :meth:`search`."""
         if passages is not _NO_PASSAGES:
             if not self.stage2:
                 self.initialize_stages()
@@ -470,9 +489,11 @@ class RetrievalPipeline:
             if pw is not None:
                 return self._add_passages(self.batch_search(queries, top_k, filter=filter, mmr_lambda=mmr_lambda,
                                                             group_by=group_by, group_size=group_size,
-                                                            passages=_NO_PASSAGES), pw)
+                                                            passages=_NO_PASSAGES, funnel_dims=funnel_dims), pw)
         gkw = {} if group_by is None else {"group_by": group_by, "group_size": group_size}
         gkw["passages"] = _NO_PASSAGES
+        if funnel_dims is not None:
+            gkw["funnel_dims"] = funnel_dims
         if filter is None:
             if mmr_lambda is None:
                 return [self.search(q, top_k, **gkw) for q in queries]
@@ -483,7 +504,8 @@ class RetrievalPipeline:
         return [self.search(q, top_k, filter=f, mmr_lambda=mmr_lambda, **gkw) for q, f in zip(queries, specs)]
 
     def search_many(self, queries: List[str], top_k: Optional[int] = None, filter=None,
-                    mmr_lambda=None, group_by=None, group_size: int = 1, passages=None) -> List[Dict[str, Any]]:
+                    mmr_lambda=None, group_by=None, group_size: int = 1, passages=None,
+                    funnel_dims: Optional[int] = None) -> List[Dict[str, Any]]:
         """Same result records as batch_search, every stage batched over the queries: one
         bi-encoder pass and one sweep of the corpus per 64 queries (stage 1), one query forward
         and one MaxSim launch (stage 2, with the resident token store), one length-sorted pass
@@ -491,19 +513,20 @@ class RetrievalPipeline:
         reported as equal shares of the batch's stage times.  ``filter``: one filter for every query or a list
         with one per query (see :meth:`search`); a filtered batch takes the record path.  ``group_by`` /
         ``group_size``: as for :meth:`search`, one collapse for the batch.  ``passages``: as for :meth:`search`, one
-        kernel call for the batch."""
+        kernel call for the batch.  ``funnel_dims``: as for :meth:`search`, one funnel for the batch."""
         if not self.stage1 or not self.stage2 or not self.stage3:
             self.initialize_stages()
         pw = self._passage_window(passages)
         if pw is not None:
             return self._add_passages(self.search_many(queries, top_k, filter=filter, mmr_lambda=mmr_lambda,
                                                        group_by=group_by, group_size=group_size,
-                                                       passages=_NO_PASSAGES), pw)
+                                                       passages=_NO_PASSAGES, funnel_dims=funnel_dims), pw)
         top_k = top_k or self.config.stage3_top_k
         if not queries:
             return []
         lam = self._mmr_lambda(mmr_lambda)
         gkw = self._group_kwargs(group_by, group_size, lam)
+        gkw.update(self._funnel_kwargs(funnel_dims, lam, gkw))
         if lam is not None:   # (mmr_lambda: as for search(); one selection call for the batch)
             return self._diversify(self.search_many(queries, _ALL_RESULTS, filter=filter, mmr_lambda=_NO_MMR,
                                                     passages=_NO_PASSAGES), top_k, lam)

@@ -114,6 +114,15 @@ class ShardedFlatIPIndex:
     def search_grouped(self, q, k: int, groups, group_size: int = 1, fetch_k=None, allowed=None):
         raise NotImplementedError("grouped search is not supported on a row-sharded index (the collapse needs the merged list)")
 
+    def search_prefix(self, q, k: int, dims: int, allowed=None):
+        raise NotImplementedError("funnel search is not supported on a row-sharded index")
+
+    def rescore(self, q, ids, k=None):
+        raise NotImplementedError("funnel search is not supported on a row-sharded index (the candidates' rows live on several ranks)")
+
+    def search_funnel(self, q, k: int, dims: int, fetch_k=None, allowed=None):
+        raise NotImplementedError("funnel search is not supported on a row-sharded index")
+
     def search(self, q, k: int, async_: bool = False, inputs_ready: bool = False, allowed=None):
         """Global top-k for the replicated query batch `q` (tensor).  Returns
         tensors (D float32 [B,k], I int64 [B,k]) identical on every rank.

@@ -74,6 +74,10 @@ class Stage1Config:
     group_by: Any = None   # None: off.  A metadata key, or an integer array with one entry per document: search / search_many
                            # return the top_k best GROUPS, at most group_size documents of each (dense-only)
     group_size: int = 1
+    funnel_dims: Optional[int] = None     # None: off.  A multiple of 128 below the embedding dimension: the dense candidates
+                                          # come from FlatIPIndex.search_funnel (ranked on that prefix of the dimensions,
+                                          # rescored exactly).  For Matryoshka-trained encoders.
+    funnel_fetch_k: Optional[int] = None  # the funnel's shortlist; None: min(2048, max(8 top_k, 128))
 
 
 def amp_torch_dtype(name: str):
@@ -799,18 +803,36 @@ class Stage1Retriever:
             self._mask_lru.move_to_end(key)
         return hit
 
-    def _dense_search(self, q, top_k: int, masks, filters):
-        """faiss_index.search, with ``allowed=`` when a filter is given."""
+    def _dense_search(self, q, top_k: int, masks, filters, funnel=None):
+        """faiss_index.search, with ``allowed=`` when a filter is given; ``funnel`` = (dims, fetch_k): search_funnel."""
+        if funnel is not None:
+            search = lambda q_, k_, **kw: self.faiss_index.search_funnel(q_, k_, funnel[0], fetch_k=funnel[1], **kw)
+        else:
+            search = self.faiss_index.search
         if masks is None:
-            return self.faiss_index.search(q, top_k)
+            return search(q, top_k)
         per_q = self._per_query_filters(filters, len(masks)) or [None] * len(masks)
         # (a query whose only mask is the live set: the index applies its own tombstones)
         drop_live = self._index_removes()
         allowed = [None if (f is None and drop_live) else self._index_mask(f, m) for f, m in zip(per_q, masks)]
         if all(a is None for a in allowed):
-            return self.faiss_index.search(q, top_k)
+            return search(q, top_k)
         same = all(a is allowed[0] for a in allowed)
-        return self.faiss_index.search(q, top_k, allowed=allowed[0] if same else allowed)
+        return search(q, top_k, allowed=allowed[0] if same else allowed)
+
+    # -- funnel search (DESIGN.md 4.21) -----------------------------------------
+    def _funnel_args(self, funnel_dims, lam=None, grp=None):
+        """The funnel of a search: ``(dims, fetch_k)`` from the argument, else from the config; None: off."""
+        dims = self.config.funnel_dims if funnel_dims is None else funnel_dims
+        if dims is None:
+            return None
+        if lam is not None or grp is not None:
+            raise ValueError("funnel_dims cannot be combined with mmr_lambda or group_by")
+        if getattr(self, "index_type_used", "flat") == "ivf":
+            raise NotImplementedError("funnel search is not supported on an IVF index (index_type='ivf')")
+        if self.faiss_index is not None and not hasattr(self.faiss_index, "search_funnel"):
+            raise NotImplementedError(f"{type(self.faiss_index).__name__} has no search_funnel()")
+        return int(dims), self.config.funnel_fetch_k
 
     # -- diversified dense search (MMR, DESIGN.md 4.17) ------------------------
     def _mmr_lambda(self, mmr_lambda) -> Optional[float]:
@@ -912,7 +934,9 @@ class Stage1Retriever:
                                  group_size)
         return D, I
 
-    def _pick_dense_search(self, lam, grp):
+    def _pick_dense_search(self, lam, grp, fun=None):
+        if fun is not None:
+            return lambda q_, k_, m_, f_: self._dense_search(q_, k_, m_, f_, funnel=fun)
         if grp is not None:
             return lambda q_, k_, m_, f_: self._dense_search_grouped(q_, k_, grp, m_, f_)
         if lam is not None:
@@ -1028,7 +1052,8 @@ class Stage1Retriever:
         return out[0] if single else out
 
     def search(self, query: str, top_k: Optional[int] = None, filter=None,
-               mmr_lambda: Optional[float] = None, group_by=None, group_size: int = 1) -> List[Dict[str, Any]]:
+               mmr_lambda: Optional[float] = None, group_by=None, group_size: int = 1,
+               funnel_dims: Optional[int] = None) -> List[Dict[str, Any]]:
         """``filter``: restrict the candidates to some documents (see :meth:`filter_mask`); fewer than
         ``top_k`` results when fewer documents are allowed, none when none are.
         ``mmr_lambda`` (default: the config's, None = off): the ``top_k`` records are picked by maximal marginal
@@ -1038,16 +1063,21 @@ class Stage1Retriever:
         document (a document without the key, or with a negative entry, is a group of its own).  ``top_k`` then counts
         GROUPS: the records of the ``top_k`` groups with the best best-document come back in dense order, at most
         ``group_size`` of each (its best within the places fetched, FlatIPIndex.search_grouped).  Dense-only, and not
-        together with ``mmr_lambda``: ``ValueError``."""
+        together with ``mmr_lambda``: ``ValueError``.
+        ``funnel_dims`` (default: the config's, None = off): the dense candidates are ranked on that prefix of the
+        dimensions and a shortlist of ``funnel_fetch_k`` is rescored exactly (FlatIPIndex.search_funnel); filters and
+        BM25 fusion work on its output as on the plain search's.  Not together with ``mmr_lambda`` or ``group_by``
+        (``ValueError``); a flat f16 / bf16 index only (``NotImplementedError``)."""
         if self.faiss_index is None:
             raise ValueError("No documents indexed. Call add_documents() first.")
         top_k = top_k or self.config.top_k_candidates
         lam = self._mmr_lambda(mmr_lambda)
         grp = self._group_args(group_by, group_size, lam)
+        fun = self._funnel_args(funnel_dims, lam, grp)
         masks = self._filter_masks(filter, 1)
         if masks is not None and not masks[0].any():
             return []
-        dense_search = self._pick_dense_search(lam, grp)
+        dense_search = self._pick_dense_search(lam, grp, fun)
         if self._device_path():
             D, I = dense_search(self._normalized_query_tensor([query]), top_k, masks, filter)
             scores, ids = D.cpu().numpy(), I.cpu().numpy()
@@ -1060,20 +1090,23 @@ class Stage1Retriever:
         return results
 
     def search_many(self, queries: Sequence[str], top_k: Optional[int] = None, filter=None,
-                    mmr_lambda: Optional[float] = None, group_by=None, group_size: int = 1) -> List[List[Dict[str, Any]]]:
+                    mmr_lambda: Optional[float] = None, group_by=None, group_size: int = 1,
+                    funnel_dims: Optional[int] = None) -> List[List[Dict[str, Any]]]:
         """All queries through ONE encoder pass and ONE index call (64 queries share a
         single sweep over the corpus on the GPU).  ``filter``: one filter for every query, or a list with one
         per query (None: unfiltered).  ``mmr_lambda``: as for :meth:`search`, one selection call for the batch.
-        ``group_by`` / ``group_size``: as for :meth:`search`, one collapse for the batch."""
+        ``group_by`` / ``group_size``: as for :meth:`search`, one collapse for the batch.  ``funnel_dims``: as for
+        :meth:`search`, one funnel for the batch."""
         if self.faiss_index is None:
             raise ValueError("No documents indexed. Call add_documents() first.")
         top_k = top_k or self.config.top_k_candidates
         lam = self._mmr_lambda(mmr_lambda)
         grp = self._group_args(group_by, group_size, lam)
+        fun = self._funnel_args(funnel_dims, lam, grp)
         if not queries:
             return []
         masks = self._filter_masks(filter, len(queries))
-        dense_search = self._pick_dense_search(lam, grp)
+        dense_search = self._pick_dense_search(lam, grp, fun)
         if self._device_path():
             D, I = dense_search(self._normalized_query_tensor(list(queries)), top_k, masks, filter)
             scores, ids = D.cpu().numpy(), I.cpu().numpy()
@@ -1091,14 +1124,15 @@ class Stage1Retriever:
         return out
 
     def search_many_arrays(self, queries: Sequence[str], top_k: Optional[int] = None, filter=None,
-                           group_by=None, group_size: int = 1):
+                           group_by=None, group_size: int = 1, funnel_dims: Optional[int] = None):
         """Stage 1 for a query batch WITHOUT building result records: (ids int64 [B, k'], scores [B, k'])
         as torch tensors on the index's device for the pure dense search, numpy arrays (float64 fused
         scores) when BM25 fusion is on.  Row q, in order, is exactly what ``search_many`` would list for
         query q.  None when the corpus holds fewer than top_k rows (the caller then uses ``search_many``,
         which deals with padded results).  ``filter`` as for :meth:`search_many`: None also when some query has
         fewer than top_k allowed documents.  ``group_by`` / ``group_size`` as for :meth:`search_many` (device path):
-        rows of top_k * group_size entries; None also when some query's row would be padded."""
+        rows of top_k * group_size entries; None also when some query's row would be padded.  ``funnel_dims`` as for
+        :meth:`search_many`; None also when the funnel left some query's row padded."""
         import torch
         if self.faiss_index is None:
             raise ValueError("No documents indexed. Call add_documents() first.")
@@ -1107,6 +1141,7 @@ class Stage1Retriever:
         if top_k > n or n != len(self.documents):
             return None
         grp = self._group_args(group_by, group_size, self.config.mmr_lambda)
+        fun = self._funnel_args(funnel_dims, self.config.mmr_lambda, grp)
         if self.config.mmr_lambda is not None:   # a diversified stage 1 goes through search_many
             return None
         if grp is not None:
@@ -1123,9 +1158,18 @@ class Stage1Retriever:
         if masks is not None:
             if any(m is not None and int(np.count_nonzero(m)) < top_k for m in masks):
                 return None
-            return self._search_many_arrays_filtered(list(queries), top_k, masks, filter)
+            return self._search_many_arrays_filtered(list(queries), top_k, masks, filter, fun)
         fuse = self.config.enable_bm25 and self.bm25_index is not None
-        if self._device_path():
+        if fun is not None:
+            if self._device_path():
+                D, I = self._dense_search(self._normalized_query_tensor(list(queries)), top_k, None, None, funnel=fun)
+            else:
+                D, I = self._dense_search(self._normalize_embeddings(self._encode_batch(list(queries))), top_k, None, None,
+                                          funnel=fun)
+                D, I = torch.as_tensor(D), torch.as_tensor(I)
+            if bool((I[:, -1] < 0).any()):   # (a shortlist that held fewer than top_k live rows)
+                return None
+        elif self._device_path():
             qt = self._normalized_query_tensor(list(queries))
             if not fuse and hasattr(self.faiss_index, "search_in_stream_order"):
                 D, I = self.faiss_index.search_in_stream_order(qt, top_k)   # (ids stay on the GPU for stage 2: no wait here)
@@ -1155,17 +1199,20 @@ class Stage1Retriever:
             out_i[qi], out_s[qi] = fi[:top_k], fs[:top_k]
         return out_i, out_s
 
-    def _search_many_arrays_filtered(self, queries: List[str], top_k: int, masks, filter):
+    def _search_many_arrays_filtered(self, queries: List[str], top_k: int, masks, filter, funnel=None):
         """search_many_arrays with a filter (every query has >= top_k allowed documents), same return types as without
         one: torch tensors (ids, scores) for the pure dense search — on the index's device on the device path —,
         numpy arrays with float64 fused scores when BM25 fusion is on (through the host arrays code, _fuse_arrays,
         with the BM25 lists filtered alike)."""
         import torch
         if self._device_path():
-            D, I = self._dense_search(self._normalized_query_tensor(queries), top_k, masks, filter)
+            D, I = self._dense_search(self._normalized_query_tensor(queries), top_k, masks, filter, funnel=funnel)
         else:
-            D, I = self._dense_search(self._normalize_embeddings(self._encode_batch(queries)), top_k, masks, filter)
+            D, I = self._dense_search(self._normalize_embeddings(self._encode_batch(queries)), top_k, masks, filter,
+                                      funnel=funnel)
             D, I = torch.as_tensor(D), torch.as_tensor(I)
+        if funnel is not None and bool((I[:, -1] < 0).any()):   # (a shortlist that held fewer than top_k allowed rows)
+            return None
         if not (self.config.enable_bm25 and self.bm25_index is not None):
             return I, D
         ids, scores = I.cpu().numpy(), D.cpu().numpy()
