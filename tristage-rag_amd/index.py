@@ -15,7 +15,7 @@ index's GPU (device pointers, no copies).
 from __future__ import annotations
 
 import ctypes
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional
 
 import numpy as np
 
@@ -91,12 +91,162 @@ def wide_pass_flags(wide_passes) -> int:
     raise ValueError(f"wide_passes must be 'auto', True or False, not {wide_passes!r}")
 
 
-def _update_call(fn, handle, ids: np.ndarray, ptr, dtype: int, flags: int, stream) -> None:
-    """ts_index_update / ts_update_ivf: a refused id (TS_ERR_INVALID, nothing written) is a ``ValueError``."""
-    code = fn(handle, ids.ctypes.data_as(ctypes.c_void_p), int(ids.shape[0]), ptr, dtype, flags, stream)
-    if code == _lib.TS_ERR_INVALID:
+def _addr(x) -> Optional[int]:
+    """The address of a numpy array or a tensor; None (a NULL pointer) for None.  Every ``c_void_p`` parameter of
+    ``_lib.SIGNATURES`` takes it as it is.  Call it in the statement of the library call that consumes the address, so
+    that the object outlives the call."""
+    if x is None:
+        return None
+    return x.data_ptr() if _is_tensor(x) else x.ctypes.data
+
+
+def _raise_empty():
+    # same exception type and text as reference src/stage1_retriever.py:370-371
+    raise ValueError("No documents indexed. Call add_documents() first.")
+
+
+def _check(code: int, invalid: bool = False) -> None:
+    """A library return code: TS_ERR_EMPTY is the reference's ``ValueError``; with ``invalid``, a refused argument
+    (TS_ERR_INVALID, nothing done) is a ``ValueError`` carrying the library's message; the rest is ``_lib.check``."""
+    if code == _lib.TS_ERR_EMPTY:
+        _raise_empty()
+    if invalid and code == _lib.TS_ERR_INVALID:
         raise ValueError(_lib.last_error())
     _lib.check(code)
+
+
+# ---- arguments -> what a library call takes -------------------------------------------------------------------
+# Queries and rows come in under one of two policies, and an entry point keeps the one it has: it decides the call.
+#   host pointers (_host_query): a CUDA tensor is read in place on the current stream; anything else stays on the
+#     host and the library copies it itself (TS_FLAG_HOST_PTR, the NULL stream).
+#   upload (_device_query): whatever is not on the index's GPU goes there through torch first.
+# Both return (x, dtype code, B, on_gpu): the object to pass (and keep alive), TS_F32 / TS_F16 / TS_BF16, its rows, and
+# whether the input was a CUDA tensor (then the results are tensors too).
+
+def _bad_shape(n, d: int, what: str, shape):
+    raise ValueError(f"expected [{n}, {d}] {what}, got {tuple(shape)}")
+
+
+def _host_query(x, d: int, what: str = "queries", n="B", device: Optional[int] = None):
+    """Host-pointer policy.  CUDA tensor: made contiguous, used in place (``device``: it must live there).  CPU tensor:
+    ``float().numpy()``.  numpy: f32 / f16 kept, any other dtype to f32, made contiguous.  ``n``: the word for the row
+    count in the message, or the count itself, which the input must then have."""
+    if _is_tensor(x) and not x.is_cuda:
+        x = x.detach().float().numpy()
+    on_gpu = _is_tensor(x)
+    if not on_gpu:
+        x = np.ascontiguousarray(x)
+        if x.dtype not in _NP_DTYPES:
+            x = x.astype(np.float32)
+    if x.ndim != 2 or x.shape[1] != d or (isinstance(n, int) and x.shape[0] != n):
+        _bad_shape(n, d, what, x.shape)
+    if on_gpu:
+        if device is not None and x.device.index != device:
+            raise ValueError(f"{what} live on a different GPU than the index")
+        x = x.contiguous()
+    return x, (_tensor_dtype(x) if on_gpu else _NP_DTYPES[x.dtype]), int(x.shape[0]), on_gpu
+
+
+def _device_query(x, d: int, device: int, what: str = "queries", n="B"):
+    """Upload policy: a contiguous f32 / f16 / bf16 tensor on GPU ``device`` (any other dtype goes to f32)."""
+    torch = _torch()
+    on_gpu = _is_tensor(x) and x.is_cuda
+    if not _is_tensor(x):
+        x = np.ascontiguousarray(x)
+        x = torch.from_numpy(x if x.dtype in _NP_DTYPES else x.astype(np.float32))
+    if x.dim() != 2 or x.shape[1] != d or (isinstance(n, int) and x.shape[0] != n):
+        _bad_shape(n, d, what, x.shape)
+    if x.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        x = x.float()
+    if not x.is_cuda or x.device.index != device:
+        x = x.to(torch.device("cuda", device))
+    x = x.contiguous()
+    return x, _tensor_dtype(x), int(x.shape[0]), on_gpu
+
+
+def _outputs(out, B: int, k: int, like):
+    """``(D, I)``, float32 / int64 ``[B, k]``: new ones where ``like`` lives (a tensor's device, or numpy), or the
+    caller's ``out`` pair, checked."""
+    if out is not None:
+        torch = _torch()
+        D, I = out
+        if (D.shape != (B, k) or I.shape != (B, k) or D.dtype != torch.float32 or
+                I.dtype != torch.int64 or not D.is_contiguous() or not I.is_contiguous()):
+            raise ValueError("out must be contiguous (float32[B,k], int64[B,k]) CUDA tensors")
+        return D, I
+    if _is_tensor(like):
+        torch = _torch()
+        return (torch.empty((B, k), dtype=torch.float32, device=like.device),
+                torch.empty((B, k), dtype=torch.int64, device=like.device))
+    return np.empty((B, k), dtype=np.float32), np.empty((B, k), dtype=np.int64)
+
+
+def _to_host(x):
+    return x.detach().cpu().numpy() if _is_tensor(x) else x
+
+
+def _id_array(ids) -> np.ndarray:
+    """Row ids in any form -> a contiguous flat int64 array on the host."""
+    return np.ascontiguousarray(np.asarray(_to_host(ids), dtype=np.int64).reshape(-1))
+
+
+class _Masks(NamedTuple):
+    """``allowed``, marshalled (:func:`_marshal_allowed`)."""
+    keep: object                  # the packed masks [max(n_masks, 1), words] the call reads: device tensor or host array
+    words: int                    # ceil(ntotal / 32)
+    n_masks: int
+    moq: Optional[np.ndarray]     # mask_of_query, int32 [B]; -1: the query is unfiltered
+    host: Optional[np.ndarray]    # the masks on the host as uint32, when they were packed there
+
+    @property
+    def bits(self):
+        """No masks at all: a NULL pointer."""
+        return self.keep if self.n_masks else None
+
+
+_NO_MASKS = _Masks(None, 0, 0, None, None)
+
+
+def _allowed_items(allowed, B: int) -> list:
+    """``allowed`` -> one entry per query: a list, a tuple or the rows of a 2-D array are per query; anything else
+    serves them all (one object, so one mask)."""
+    if not isinstance(allowed, (list, tuple)) and getattr(allowed, "ndim", 1) != 2:
+        return [allowed] * B
+    if len(allowed) != B:
+        raise ValueError(f"allowed: {len(allowed)} masks for {B} queries")
+    return list(allowed)
+
+
+def _marshal_allowed(allowed, B: int, n: int, device=None) -> _Masks:
+    """``allowed`` of a search of ``B`` queries over ``n`` rows, for a call that reads the masks on ``device`` (a torch
+    device) or on the host (None; needs neither torch nor the library).  The mask objects of a list are told apart by
+    identity: one object, one packed mask.  Masks that all are packed int32 tensors on ``device`` already are used
+    there (a single contiguous one in place); otherwise all are packed on the host (:func:`pack_allowed`) and uploaded."""
+    words = (n + 31) // 32
+    uniq, seen = [], {}
+    moq = np.full(B, -1, dtype=np.int32)
+    for qi, a in enumerate(_allowed_items(allowed, B)):
+        if a is not None:
+            if id(a) not in seen:
+                seen[id(a)] = len(uniq)
+                uniq.append(a)
+            moq[qi] = seen[id(a)]
+    if device is not None and uniq and all(
+            _is_tensor(a) and a.is_cuda and a.dtype == _torch().int32 and a.dim() == 1 and a.shape[0] >= words
+            and a.device == device for a in uniq):   # (Stage1Retriever's filter cache, tools/filter_probe.py)
+        host, rows = None, [a[:words] for a in uniq]
+        keep = rows[0].view(1, -1) if len(rows) == 1 and rows[0].is_contiguous() else _torch().stack(rows).contiguous()
+    else:
+        host = np.ascontiguousarray(np.stack([pack_allowed(a, n) for a in uniq]) if uniq
+                                    else np.zeros((1, max(words, 1)), dtype=np.uint32))
+        # the device copy lives as long as the _Masks: an asynchronous search keeps it until finish()
+        keep = host if device is None else _torch().from_numpy(host.view(np.int32)).to(device)
+    return _Masks(keep, words, len(uniq), moq, host)
+
+
+def _update_call(fn, handle, ids: np.ndarray, x, dtype: int, flags: int, stream) -> None:
+    """ts_index_update / ts_update_ivf: a refused id (TS_ERR_INVALID, nothing written) is a ``ValueError``."""
+    _check(fn(handle, _addr(ids), int(ids.shape[0]), _addr(x), dtype, flags, stream), invalid=True)
 
 
 MMR_MAX_FETCH = 1024   # candidates per query of mmr(): the greedy kernel runs one thread per candidate
@@ -125,41 +275,25 @@ def mmr_check(k, fetch_k, lambda_mult):
 def _mmr_call(ix, entry: str, ids, relevance, k, lambda_mult):
     """ts_index_mmr / ts_mmr_ivf (``entry``) on the index ``ix``: CUDA tensors in -> tensors out, enqueued on the current
     stream; anything else goes through host pointers and comes back as numpy.  The arguments are checked first."""
-    device = ix.device if hasattr(ix, "device") else 0
-    if _is_tensor(ids) and ids.is_cuda:
+    on_gpu = _is_tensor(ids) and ids.is_cuda
+    if on_gpu:
         torch = _torch()
-        if ids.dim() != 2 or tuple(relevance.shape) != tuple(ids.shape):
-            raise ValueError(f"expected ids and relevance of one shape [B, fetch_k], got {tuple(ids.shape)} and "
-                             f"{tuple(relevance.shape)}")
-        k, C, lam = mmr_check(k, ids.shape[1], lambda_mult)
-        if ids.device.index != device:
-            raise ValueError("the candidates live on a different GPU than the index")
         ids = ids.to(torch.int64).contiguous()
         rel = torch.as_tensor(relevance, device=ids.device).to(torch.float32).contiguous()
-        B = ids.shape[0]
-        D = torch.empty((B, k), dtype=torch.float32, device=ids.device)
-        I = torch.empty((B, k), dtype=torch.int64, device=ids.device)
-        args = (ctypes.c_void_p(ids.data_ptr()), ctypes.c_void_p(rel.data_ptr()), B, C, k, lam,
-                ctypes.c_void_p(D.data_ptr()), ctypes.c_void_p(I.data_ptr()), 0, ctypes.c_void_p(_stream_ptr(device)))
     else:
-        if _is_tensor(ids):
-            ids = ids.detach().cpu().numpy()
-        if _is_tensor(relevance):
-            relevance = relevance.detach().cpu().numpy()
-        ids = np.ascontiguousarray(ids, dtype=np.int64)
-        rel = np.ascontiguousarray(relevance, dtype=np.float32)
-        if ids.ndim != 2 or rel.shape != ids.shape:
-            raise ValueError(f"expected ids and relevance of one shape [B, fetch_k], got {ids.shape} and {rel.shape}")
-        k, C, lam = mmr_check(k, ids.shape[1], lambda_mult)
-        B = ids.shape[0]
-        D = np.empty((B, k), dtype=np.float32)
-        I = np.empty((B, k), dtype=np.int64)
-        args = (ids.ctypes.data_as(ctypes.c_void_p), rel.ctypes.data_as(ctypes.c_void_p), B, C, k, lam,
-                D.ctypes.data_as(ctypes.c_void_p), I.ctypes.data_as(ctypes.c_void_p), _lib.TS_FLAG_HOST_PTR, None)
-    code = getattr(ix._lib, entry)(ix._h, *args)
-    if code == _lib.TS_ERR_INVALID:
-        raise ValueError(_lib.last_error())
-    _lib.check(code)
+        ids = np.ascontiguousarray(_to_host(ids), dtype=np.int64)
+        rel = np.ascontiguousarray(_to_host(relevance), dtype=np.float32)
+    if ids.ndim != 2 or tuple(rel.shape) != tuple(ids.shape):
+        raise ValueError(f"expected ids and relevance of one shape [B, fetch_k], got {tuple(ids.shape)} and "
+                         f"{tuple(rel.shape)}")
+    k, C, lam = mmr_check(k, ids.shape[1], lambda_mult)
+    if on_gpu and ids.device.index != ix.device:
+        raise ValueError("the candidates live on a different GPU than the index")
+    B = ids.shape[0]
+    D, I = _outputs(None, B, k, ids)
+    _check(getattr(ix._lib, entry)(ix._h, _addr(ids), _addr(rel), B, C, k, lam, _addr(D), _addr(I),
+                                   0 if on_gpu else _lib.TS_FLAG_HOST_PTR, _stream_ptr(ix.device) if on_gpu else None),
+           invalid=True)
     return D, I
 
 
@@ -254,17 +388,11 @@ def group_topk(ids, scores, groups, k: int, group_size: int = 1, id_base: int = 
             n_rows = 0
         else:
             n_rows = tab.shape[0]
-        ptr = [ctypes.c_void_p(t.data_ptr()) for t in (ids, sc, tab, D, I, G, ng, nv)]
-        flags, stream = 0, ctypes.c_void_p(_stream_ptr(device))
+        flags, stream = 0, _stream_ptr(device)
     else:
-        if _is_tensor(ids):
-            ids = ids.detach().cpu().numpy()
-        if _is_tensor(scores):
-            scores = scores.detach().cpu().numpy()
-        if _is_tensor(groups):
-            groups = groups.detach().cpu().numpy()
-        ids = np.ascontiguousarray(ids, dtype=np.int64)
-        sc = np.ascontiguousarray(scores, dtype=np.float32)
+        ids = np.ascontiguousarray(_to_host(ids), dtype=np.int64)
+        sc = np.ascontiguousarray(_to_host(scores), dtype=np.float32)
+        groups = _to_host(groups)
         if ids.ndim != 2 or sc.shape != ids.shape:
             raise ValueError(f"expected ids and scores of one shape [B, C], got {ids.shape} and {sc.shape}")
         k, group_size, C = group_check(k, group_size, ids.shape[1])
@@ -279,13 +407,9 @@ def group_topk(ids, scores, groups, k: int, group_size: int = 1, id_base: int = 
         G = np.empty((B, W), dtype=np.int32)
         ng = np.empty((B,), dtype=np.int32)
         nv = np.empty((B,), dtype=np.int32)
-        ptr = [a.ctypes.data_as(ctypes.c_void_p) for a in (ids, sc, tab, D, I, G, ng, nv)]
         device, flags, stream = 0, _lib.TS_FLAG_HOST_PTR, None
-    code = lib.ts_group_topk(ptr[0], ptr[1], B, C, ptr[2], n_rows, int(id_base), k, group_size, ptr[3], ptr[4], ptr[5],
-                             ptr[6], ptr[7], flags, device, stream)
-    if code == _lib.TS_ERR_INVALID:
-        raise ValueError(_lib.last_error())
-    _lib.check(code)
+    _check(lib.ts_group_topk(_addr(ids), _addr(sc), B, C, _addr(tab), n_rows, int(id_base), k, group_size, _addr(D),
+                             _addr(I), _addr(G), _addr(ng), _addr(nv), flags, device, stream), invalid=True)
     return D, I, G, ng, nv
 
 
@@ -330,8 +454,40 @@ class RangeSearchLimitError(RuntimeError):
         self.counts = counts
 
 
-class FlatIPIndex:
+class _IndexBase:
+    """What FlatIPIndex and IVFFlatIndex share: the handle's lifetime and the searches built on ``search`` / ``mmr``."""
+
+    _DESTROY = None   # the entry that frees the handle
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None and self._h.value:
+            getattr(self._lib, self._DESTROY)(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _search_mmr(self, q, k, fetch_k, lambda_mult, **how):
+        """``search(q, fetch_k, **how)`` followed by :meth:`mmr` on the same stream."""
+        k, fetch_k, lam = mmr_check(k, mmr_default_fetch_k(k) if fetch_k is None else fetch_k, lambda_mult)
+        D, I = self.search(q, fetch_k, **how)
+        return self.mmr(I, D, k, lam)
+
+    def _search_grouped(self, q, k, groups, group_size, fetch_k, **how):
+        return grouped_search(self, lambda x, f: self.search(x, f, **how), q, k, groups, group_size, fetch_k)
+
+    def last_group_info(self) -> dict:
+        """``{"fetched", "rounds", "n_groups", "complete"}`` of the last :meth:`search_grouped` (the last two per query)."""
+        return dict(getattr(self, "_group_info", {}))
+
+
+class FlatIPIndex(_IndexBase):
     """Exact inner-product index resident in MI355X HBM."""
+
+    _DESTROY = "ts_index_destroy"
 
     supports_out = True  # search(..., out=(D, I)) writes into caller tensors
     PENDING_PASSES = 240  # passes of <= 32 queries that may wait for finish() (the library tracks 256)
@@ -373,18 +529,6 @@ class FlatIPIndex:
         self.wide_passes = "auto"
         self._filter_info = None  # set by finish() when it redid a filtered search: the counters of what was submitted
 
-    # -- lifetime ---------------------------------------------------------
-    def close(self) -> None:
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.ts_index_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     # -- FAISS duck type --------------------------------------------------
     @property
     def ntotal(self) -> int:
@@ -404,15 +548,18 @@ class FlatIPIndex:
         the id offset) are never returned again, but keep their ids and storage until :meth:`compact`.  Unknown,
         repeated and already removed ids are skipped.  Returns how many rows were removed.  Unfinished ``async_``
         searches are finished first, so that every search submitted before sees the index as it was."""
-        if _is_tensor(ids):
-            ids = ids.detach().cpu().numpy()
-        arr = np.ascontiguousarray(np.asarray(ids, dtype=np.int64).reshape(-1))
+        arr = _id_array(ids)
+        self._finish_pending()
+        n = ctypes.c_int64(0)
+        _lib.check(self._lib.ts_index_remove(self._h, _addr(arr), int(arr.shape[0]), ctypes.byref(n),
+                                             _stream_ptr(self.device)))
+        return int(n.value)
+
+    def _finish_pending(self) -> None:
+        """Before a synchronous call that must see every search submitted so far complete: finish them, and keep what
+        that repeated for the caller's own finish()."""
         if self._pending:
             self._auto_redone = self._auto_redone + self.finish()
-        n = ctypes.c_int64(0)
-        _lib.check(self._lib.ts_index_remove(self._h, arr.ctypes.data_as(ctypes.c_void_p), int(arr.shape[0]),
-                                             ctypes.byref(n), ctypes.c_void_p(_stream_ptr(self.device)) or None))
-        return int(n.value)
 
     def update_rows(self, ids, x, normalize: bool = False) -> None:
         """Replace the stored rows ``ids`` (as :meth:`search` returns them, i.e. with the id offset) by the rows of ``x``
@@ -420,36 +567,18 @@ class FlatIPIndex:
         :meth:`add` of the final matrix would have written.  All or nothing: an id out of range, given
         twice or removed raises ``ValueError`` and nothing is written.  Unfinished ``async_`` searches are finished
         first, as :meth:`remove_ids` does, so that every search submitted before reads the rows as they were."""
-        if _is_tensor(ids):
-            ids = ids.detach().cpu().numpy()
-        arr = np.ascontiguousarray(np.asarray(ids, dtype=np.int64).reshape(-1))
-        flags = _lib.TS_FLAG_NORMALIZE if normalize else 0
-        if _is_tensor(x):
-            if x.is_cuda and x.device.index != self.device:
-                raise ValueError("rows live on a different GPU than the index")
-            if not x.is_cuda:
-                x = x.detach().float().numpy()
-        if _is_tensor(x):
-            x = x.contiguous()
-            shape, ptr, dt = tuple(x.shape), ctypes.c_void_p(x.data_ptr()), _tensor_dtype(x)
-        else:
-            x = np.ascontiguousarray(x)
-            if x.dtype not in _NP_DTYPES:
-                x = x.astype(np.float32)
-            shape, ptr, dt = x.shape, x.ctypes.data_as(ctypes.c_void_p), _NP_DTYPES[x.dtype]
-            flags |= _lib.TS_FLAG_HOST_PTR
-        if len(shape) != 2 or shape[1] != self.d or shape[0] != arr.shape[0]:
-            raise ValueError(f"expected [{arr.shape[0]}, {self.d}] rows, got {tuple(shape)}")
-        if self._pending:
-            self._auto_redone = self._auto_redone + self.finish()
-        _update_call(self._lib.ts_index_update, self._h, arr, ptr, dt, flags,
-                     ctypes.c_void_p(_stream_ptr(self.device)) or None)
+        arr = _id_array(ids)
+        x, dt, _, on_gpu = _host_query(x, self.d, "rows", int(arr.shape[0]), self.device)
+        flags = (_lib.TS_FLAG_NORMALIZE if normalize else 0) | (0 if on_gpu else _lib.TS_FLAG_HOST_PTR)
+        self._finish_pending()
+        _update_call(self._lib.ts_index_update, self._h, arr, x, dt, flags, _stream_ptr(self.device))
 
     def live_words(self) -> np.ndarray:
         """The live set as packed uint32 words (the layout of :func:`pack_allowed`)."""
-        out = np.zeros(max((self.ntotal + 31) // 32, 1), dtype=np.uint32)
-        _lib.check(self._lib.ts_index_live_words(self._h, out.ctypes.data_as(ctypes.c_void_p), None))
-        return out[: (self.ntotal + 31) // 32]
+        words = (self.ntotal + 31) // 32
+        out = np.zeros(max(words, 1), dtype=np.uint32)
+        _lib.check(self._lib.ts_index_live_words(self._h, _addr(out), None))
+        return out[:words]
 
     def live_mask(self) -> np.ndarray:
         """The live set as a bool array over the ``ntotal`` rows."""
@@ -458,12 +587,10 @@ class FlatIPIndex:
     def compact(self) -> np.ndarray:
         """Move the live rows down (order kept), drop the removed ones; ``ntotal`` becomes :attr:`nlive`.  Returns
         the old -> new map int64 [old ntotal] (-1 = removed), monotone, so ties keep their order."""
-        if self._pending:
-            self._auto_redone = self._auto_redone + self.finish()
-        out = np.empty(max(self.ntotal, 1), dtype=np.int64)
+        self._finish_pending()
         n = self.ntotal
-        _lib.check(self._lib.ts_index_compact(self._h, out.ctypes.data_as(ctypes.c_void_p),
-                                              ctypes.c_void_p(_stream_ptr(self.device)) or None))
+        out = np.empty(max(n, 1), dtype=np.int64)
+        _lib.check(self._lib.ts_index_compact(self._h, _addr(out), _stream_ptr(self.device)))
         return out[:n]
 
     @property
@@ -474,10 +601,7 @@ class FlatIPIndex:
 
     def set_fp8_scale_log2(self, s: int) -> None:
         """fp8 storage: the scale exponent, 0 .. 15; only while the index is empty (``ValueError`` otherwise)."""
-        code = self._lib.ts_index_set_fp8_scale_log2(self._h, int(s))
-        if code == _lib.TS_ERR_INVALID:
-            raise ValueError(_lib.last_error())
-        _lib.check(code)
+        _check(self._lib.ts_index_set_fp8_scale_log2(self._h, int(s)), invalid=True)
 
     def reset(self) -> None:
         _lib.check(self._lib.ts_index_reset(self._h))
@@ -491,28 +615,9 @@ class FlatIPIndex:
 
     def add(self, x, normalize: bool = False) -> None:
         """Append rows ``x`` [n, d] (numpy float32/float16 or a CUDA tensor)."""
-        flags = _lib.TS_FLAG_NORMALIZE if normalize else 0
-        if _is_tensor(x):
-            if x.dim() != 2 or x.shape[1] != self.d:
-                raise ValueError(f"expected [n, {self.d}] rows, got {tuple(x.shape)}")
-            if not x.is_cuda:
-                return self.add(x.detach().float().numpy(), normalize=normalize)
-            if x.device.index != self.device:
-                raise ValueError("rows live on a different GPU than the index")
-            x = x.contiguous()
-            _lib.check(self._lib.ts_index_add(self._h, ctypes.c_void_p(x.data_ptr()), x.shape[0],
-                                              _tensor_dtype(x), flags,
-                                              ctypes.c_void_p(_stream_ptr(self.device))))
-            return None
-        x = np.ascontiguousarray(x)
-        if x.dtype not in _NP_DTYPES:
-            x = x.astype(np.float32)
-        if x.ndim != 2 or x.shape[1] != self.d:
-            raise ValueError(f"expected [n, {self.d}] rows, got {x.shape}")
-        _lib.check(self._lib.ts_index_add(self._h, x.ctypes.data_as(ctypes.c_void_p), x.shape[0],
-                                          _NP_DTYPES[x.dtype], flags | _lib.TS_FLAG_HOST_PTR,
-                                          None))
-        return None
+        x, dt, n, on_gpu = _host_query(x, self.d, "rows", "n", self.device)
+        flags = (_lib.TS_FLAG_NORMALIZE if normalize else 0) | (0 if on_gpu else _lib.TS_FLAG_HOST_PTR)
+        _lib.check(self._lib.ts_index_add(self._h, _addr(x), n, dt, flags, _stream_ptr(self.device) if on_gpu else None))
 
     def search(self, q, k: int, exact_dense: bool = False, async_: bool = False, out=None,
                inputs_ready: bool = False, classic: bool = False, one_launch: bool = False, allowed=None):
@@ -538,259 +643,113 @@ class FlatIPIndex:
         k = int(k)
         if k <= 0:
             raise ValueError("k must be positive")
-        if allowed is not None:
-            return self._search_filtered(q, k, allowed, exact_dense=exact_dense, async_=async_, out=out)
+        if allowed is not None and self.ntotal == 0:
+            _raise_empty()
         if k > self.MAX_KERNEL_K and self.ntotal > self.MAX_KERNEL_K:
-            if self.nlive < self.ntotal:   # removed rows: the live set is the one mask
-                return self._search_large_k(q, k, out, masks=(self.live_words()[None, :], np.zeros(int(q.shape[0]), np.int32)))
-            return self._search_large_k(q, k, out)
-        if async_ and _is_tensor(q) and q.is_cuda and q.shape[0] > self.MAX_ASYNC_QUERIES:
-            # the library takes at most 4 passes (256 queries) per asynchronous call: larger batches go in slices
-            torch = _torch()
-            B = q.shape[0]
-            D, I = out if out is not None else (torch.empty((B, k), dtype=torch.float32, device=q.device),
-                                                torch.empty((B, k), dtype=torch.int64, device=q.device))
+            return self._search_large_k(q, k, out, allowed)
+        if async_ and not (_is_tensor(q) and q.is_cuda):
+            raise ValueError("async_ search needs a CUDA tensor")
+        q, q_dtype, B, on_gpu = _host_query(q, self.d)
+        D, I = _outputs(out if on_gpu else None, B, k, q)
+        if async_ and B > self.MAX_ASYNC_QUERIES:
+            # the library takes at most 4 passes per asynchronous call: larger batches go in slices, a per-query
+            # ``allowed`` sliced with the queries
+            items = None if allowed is None else _allowed_items(allowed, B)
             for s in range(0, B, self.MAX_ASYNC_QUERIES):
                 e = min(B, s + self.MAX_ASYNC_QUERIES)
                 self.search(q[s:e], k, exact_dense=exact_dense, async_=True, out=(D[s:e], I[s:e]),
-                            inputs_ready=inputs_ready, classic=classic, one_launch=one_launch)
+                            inputs_ready=inputs_ready, classic=classic, one_launch=one_launch,
+                            allowed=None if items is None else items[s:e])
             return D, I
-        flags = _lib.TS_FLAG_NO_FILTER if exact_dense else 0
-        if classic or self.classic_filter:   # the five-launch filter path even where the one-launch scan is the default (A/B, tests)
-            flags |= _lib.TS_FLAG_CLASSIC
-        elif one_launch or self.one_launch_filter:   # the one-launch scan also where it is not the default
-            flags |= _lib.TS_FLAG_ONE_LAUNCH
-        if async_:
-            if not (_is_tensor(q) and q.is_cuda):
-                raise ValueError("async_ search needs a CUDA tensor")
-            # the library tracks at most 64 unfinished passes (one per <= 64 queries)
-            if self.pending_room(q.shape[0]) < 0:
-                if not self.auto_finish:
-                    raise RuntimeError("too many unfinished asynchronous searches: the owner of this index "
-                                       "must call finish() (see pending_room())")
-                self._auto_redone = self.finish()   # (finish() hands back what an earlier internal one repeated)
-            flags |= _lib.TS_FLAG_ASYNC
-            if inputs_ready:
-                flags |= _lib.TS_FLAG_PIPELINE
-            elif self.coalesce:
-                flags |= _lib.TS_FLAG_COALESCE
-                flags |= wide_pass_flags(self.wide_passes)
-        if _is_tensor(q) and q.is_cuda:
-            torch = _torch()
-            if q.dim() != 2 or q.shape[1] != self.d:
-                raise ValueError(f"expected [B, {self.d}] queries, got {tuple(q.shape)}")
-            q = q.contiguous()
-            B = q.shape[0]
-            if out is not None:
-                D, I = out
-                if (D.shape != (B, k) or I.shape != (B, k) or D.dtype != torch.float32 or
-                        I.dtype != torch.int64 or not D.is_contiguous() or not I.is_contiguous()):
-                    raise ValueError("out must be contiguous (float32[B,k], int64[B,k]) CUDA tensors")
-            else:
-                D = torch.empty((B, k), dtype=torch.float32, device=q.device)
-                I = torch.empty((B, k), dtype=torch.int64, device=q.device)
-            self._search_raw(q.data_ptr(), B, _tensor_dtype(q), k, D.data_ptr(), I.data_ptr(),
-                             flags, _stream_ptr(self.device))
+        flags = (_lib.TS_FLAG_NO_FILTER if exact_dense else 0) | (0 if on_gpu else _lib.TS_FLAG_HOST_PTR)
+        stream = _stream_ptr(self.device) if on_gpu else None
+        masks = None
+        if allowed is None:
+            if classic or self.classic_filter:   # the five-launch filter path even where the one-launch scan is the default (A/B, tests)
+                flags |= _lib.TS_FLAG_CLASSIC
+            elif one_launch or self.one_launch_filter:   # the one-launch scan also where it is not the default
+                flags |= _lib.TS_FLAG_ONE_LAUNCH
             if async_:
-                self._pending[int(self._lib.ts_index_last_ticket(self._h))] = (q, k, D, I, None)
-                self._pending_passes += (B + 31) // 32
-            return D, I
-        if _is_tensor(q):
-            q = q.detach().float().numpy()
-        q = np.ascontiguousarray(q)
-        if q.dtype not in _NP_DTYPES:
-            q = q.astype(np.float32)
-        if q.ndim != 2 or q.shape[1] != self.d:
-            raise ValueError(f"expected [B, {self.d}] queries, got {q.shape}")
-        B = q.shape[0]
-        D = np.empty((B, k), dtype=np.float32)
-        I = np.empty((B, k), dtype=np.int64)
-        self._search_raw(q.ctypes.data, B, _NP_DTYPES[q.dtype], k, D.ctypes.data, I.ctypes.data,
-                         flags | _lib.TS_FLAG_HOST_PTR, 0)
+                self._admit_async(B)
+                flags |= _lib.TS_FLAG_ASYNC
+                if inputs_ready:
+                    flags |= _lib.TS_FLAG_PIPELINE
+                elif self.coalesce:
+                    flags |= _lib.TS_FLAG_COALESCE
+                    flags |= wide_pass_flags(self.wide_passes)
+            self._search_raw(q, q_dtype, k, D, I, flags, stream)
+        else:   # (ts_index_search_filtered resets the counters last_filter_info() reads, and never coalesces)
+            self._filter_info = None   # last_filter_info() reads the library's counters of this call again
+            masks = _marshal_allowed(allowed, B, self.ntotal, q.device if on_gpu else None)
+            if async_:
+                self._admit_async(B)
+                flags |= _lib.TS_FLAG_ASYNC
+            self._filtered_raw(q, q_dtype, k, masks, D, I, flags, stream)
+        if async_:   # finish() may have to repeat the search: it keeps the queries, the outputs and the masks alive
+            self._pending[int(self._lib.ts_index_last_ticket(self._h))] = (q, k, D, I, masks)
+            self._pending_passes += (B + 31) // 32
         return D, I
 
-    def _search_large_k(self, q, k: int, out=None, masks=None):
+    def _admit_async(self, n_queries: int) -> None:
+        """Room for another asynchronous search (the library tracks a fixed number of unfinished passes), made by an
+        internal finish() where the index owns its finish() calls."""
+        if self.pending_room(n_queries) < 0:
+            if not self.auto_finish:
+                raise RuntimeError("too many unfinished asynchronous searches: the owner of this index "
+                                   "must call finish() (see pending_room())")
+            self._auto_redone = self.finish()   # (finish() hands back what an earlier internal one repeated)
+
+    def _search_raw(self, q, q_dtype: int, k: int, D, I, flags: int, stream) -> None:
+        _check(self._lib.ts_index_search(self._h, _addr(q), q.shape[0], q_dtype, k, _addr(D), _addr(I), flags, stream))
+
+    def _filtered_raw(self, q, q_dtype: int, k: int, m: _Masks, D, I, flags: int, stream) -> None:
+        _check(self._lib.ts_index_search_filtered(self._h, _addr(q), q.shape[0], q_dtype, k, _addr(m.keep), m.words,
+                                                  m.n_masks, _addr(m.moq), _addr(D), _addr(I), flags, stream))
+
+    def _search_large_k(self, q, k: int, out, allowed):
         """k > 16384 on a corpus of more than 16384 rows (the select kernels keep 16384 keys in LDS; FAISS itself takes
         any k on the CPU, reference src/stage1_retriever.py:380): every inner product from the HIP dense scan
         (ts_index_scores), then ONE stable descending device sort per slice of queries — equal scores keep ascending
         row order, the canonical tie rule — and the FAISS padding (-1 / -FLT_MAX) beyond ntotal.  Exact; not a fast path:
         it materialises 4 B x queries x rows."""
         torch = _torch()
-        was_np = not (_is_tensor(q) and q.is_cuda)
-        dev = torch.device("cuda", self.device)
-        qt = torch.as_tensor(np.ascontiguousarray(q.detach().cpu().numpy() if _is_tensor(q) else q, dtype=np.float32)).to(dev) if was_np else q
-        if qt.dim() != 2 or qt.shape[1] != self.d:
-            raise ValueError(f"expected [B, {self.d}] queries, got {tuple(qt.shape)}")
-        n, B = self.ntotal, qt.shape[0]
-        if n == 0:
-            raise ValueError("No documents indexed. Call add_documents() first.")
+        if not (_is_tensor(q) and q.is_cuda):   # host queries are scored as f32, whatever they came as
+            q = np.ascontiguousarray(_to_host(q.float() if _is_tensor(q) else q), dtype=np.float32)
+        qt, _, B, on_gpu = _device_query(q, self.d, self.device)
+        n = self.ntotal
         kk = min(k, n)
-        if out is not None and not was_np:
-            D, I = out
-        else:
-            D = torch.empty((B, k), dtype=torch.float32, device=dev)
-            I = torch.empty((B, k), dtype=torch.int64, device=dev)
+        D, I = _outputs(out if on_gpu else None, B, k, qt)
+        # filtered: rows outside a query's mask sort behind every allowed row (-inf) and are cut; removed rows: every
+        # mask ANDed with the live set, which is also the mask of the unfiltered queries
+        bits = moq = None
+        if allowed is not None:
+            m = _marshal_allowed(allowed, B, n)
+            bits, moq = m.host, m.moq
+        if self.nlive < n:
+            live = self.live_words()[None, :]
+            bits = live if bits is None else np.concatenate([bits & live, live])
+            moq = np.full(B, bits.shape[0] - 1, np.int32) if moq is None else np.where(moq < 0, bits.shape[0] - 1, moq)
         D[:, kk:] = -3.4028234663852886e38
         I[:, kk:] = -1
         step = max(1, int(2e9 // (4 * max(n, 1))))          # <= 2 GB of scores per slice
-        off = int(self._id_offset_value())
-        if masks is not None:   # filtered: rows outside a query's mask sort behind every allowed row (-inf) and are cut
-            bits, moq = masks
+        off = int(getattr(self, "_id_offset", 0))
+        if bits is not None:
             allow = np.unpackbits(bits.view(np.uint8), bitorder="little").reshape(bits.shape[0], -1)[:, :n].astype(bool)
-            allow_t = torch.from_numpy(allow).to(dev)
+            allow_t = torch.from_numpy(allow).to(qt.device)
         for s in range(0, B, step):
             sc = self.scores(qt[s: s + step])
-            if masks is not None:
-                m = torch.from_numpy(moq[s: s + step].astype(np.int64)).to(dev)
+            if bits is not None:
+                m = torch.from_numpy(moq[s: s + step].astype(np.int64)).to(qt.device)
                 rows_ok = torch.where((m >= 0)[:, None], allow_t[m.clamp(min=0)], torch.ones_like(allow_t[:1]))
                 sc = sc.masked_fill(~rows_ok, float("-inf"))
             srt, idx = torch.sort(sc, dim=1, descending=True, stable=True)
             D[s: s + step, :kk] = srt[:, :kk]
             I[s: s + step, :kk] = idx[:, :kk] + off
-            if masks is not None:
+            if bits is not None:
                 cut = torch.isneginf(D[s: s + step])
                 D[s: s + step][cut] = -3.4028234663852886e38
                 I[s: s + step][cut] = -1
-        if was_np:
-            return D.cpu().numpy(), I.cpu().numpy()
-        return D, I
-
-    # -- filtered search ----------------------------------------------------
-    def _masks(self, allowed, B: int):
-        """``allowed`` -> (packed masks uint32 [n_masks, words] on the host, mask_of_query int32 [B]).
-        Identical mask objects of a list share one packed mask."""
-        n = self.ntotal
-        per_query = isinstance(allowed, (list, tuple))
-        if not per_query and _is_tensor(allowed) and allowed.dim() == 2:
-            allowed = list(allowed)
-            per_query = True
-        elif not per_query and isinstance(allowed, np.ndarray) and allowed.ndim == 2:
-            allowed = list(allowed)
-            per_query = True
-        if per_query and len(allowed) != B:
-            raise ValueError(f"allowed: {len(allowed)} masks for {B} queries")
-        items = allowed if per_query else [allowed] * B
-        packed, seen = [], {}
-        moq = np.full(B, -1, dtype=np.int32)
-        for qi, a in enumerate(items):
-            if a is None:
-                continue
-            key = id(a)
-            if key not in seen:
-                seen[key] = len(packed)
-                packed.append(pack_allowed(a, n))
-            moq[qi] = seen[key]
-        words = (n + 31) // 32
-        bits = np.stack(packed) if packed else np.zeros((1, max(words, 1)), dtype=np.uint32)
-        return np.ascontiguousarray(bits), words, moq
-
-    def _filtered_raw(self, q_ptr: int, B: int, q_dtype: int, k: int, bits_ptr: int, words: int, moq: np.ndarray,
-                      d_ptr: int, i_ptr: int, flags: int, stream: int) -> None:
-        n_masks = int(moq.max()) + 1 if moq.size else 0
-        code = self._lib.ts_index_search_filtered(
-            self._h, ctypes.c_void_p(q_ptr), B, q_dtype, k, ctypes.c_void_p(bits_ptr), int(words), n_masks,
-            moq.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(d_ptr), ctypes.c_void_p(i_ptr), flags,
-            ctypes.c_void_p(stream) if stream else None)
-        if code == _lib.TS_ERR_EMPTY:
-            raise ValueError("No documents indexed. Call add_documents() first.")
-        _lib.check(code)
-
-    @staticmethod
-    def _device_masks(allowed, B: int, words: int, device):
-        """``allowed`` made only of packed int32 CUDA tensors (>= words each) or None -> (bits [n, words] on the
-        device, mask_of_query), else None."""
-        items = list(allowed) if isinstance(allowed, (list, tuple)) else [allowed] * B
-        if len(items) != B or not any(a is not None for a in items):
-            return None
-        for a in items:
-            if a is not None and not (_is_tensor(a) and a.is_cuda and a.dtype == _torch().int32 and a.dim() == 1
-                                      and a.shape[0] >= words and a.device == device):
-                return None
-        uniq, seen = [], {}
-        moq = np.full(B, -1, dtype=np.int32)
-        for qi, a in enumerate(items):
-            if a is not None:
-                if id(a) not in seen:
-                    seen[id(a)] = len(uniq)
-                    uniq.append(a[:words])
-                moq[qi] = seen[id(a)]
-        if len(uniq) == 1 and uniq[0].is_contiguous():   # one mask for the call: used in place, no copy
-            return uniq[0].view(1, -1), moq
-        return _torch().stack(uniq).contiguous(), moq
-
-    def _search_filtered(self, q, k: int, allowed, exact_dense: bool = False, async_: bool = False, out=None):
-        if self.ntotal == 0:
-            raise ValueError("No documents indexed. Call add_documents() first.")
-        B = int(q.shape[0])
-        self._filter_info = None   # last_filter_info() reads the library's counters of this call again
-        if getattr(allowed, "ndim", 1) == 2:   # one row per query: the list form (sliced with the queries below)
-            allowed = list(allowed)
-        words = (self.ntotal + 31) // 32
-        dev_bits = None
-        if (_is_tensor(q) and q.is_cuda and not (k > self.MAX_KERNEL_K and self.ntotal > self.MAX_KERNEL_K)
-                and not (async_ and B > self.MAX_ASYNC_QUERIES)):
-            dev_bits = self._device_masks(allowed, B, words, q.device)   # packed on the device already: no host copy
-        if dev_bits is None:
-            bits, words, moq = self._masks(allowed, B)
-        if k > self.MAX_KERNEL_K and self.ntotal > self.MAX_KERNEL_K:
-            if self.nlive < self.ntotal:   # removed rows: every mask ANDed with the live set, which unfiltered queries get
-                live = self.live_words()
-                bits = np.concatenate([bits[:, :words] & live[None, :], live[None, :]]) if words else bits
-                moq = np.where(moq < 0, bits.shape[0] - 1, moq).astype(np.int32)
-            return self._search_large_k(q, k, out, masks=(bits, moq))
-        flags = _lib.TS_FLAG_NO_FILTER if exact_dense else 0
-        if _is_tensor(q) and q.is_cuda:
-            torch = _torch()
-            if q.dim() != 2 or q.shape[1] != self.d:
-                raise ValueError(f"expected [B, {self.d}] queries, got {tuple(q.shape)}")
-            if async_ and B > self.MAX_ASYNC_QUERIES:
-                D, I = out if out is not None else (torch.empty((B, k), dtype=torch.float32, device=q.device),
-                                                    torch.empty((B, k), dtype=torch.int64, device=q.device))
-                for s in range(0, B, self.MAX_ASYNC_QUERIES):
-                    e = min(B, s + self.MAX_ASYNC_QUERIES)
-                    sub = [allowed[i] for i in range(s, e)] if isinstance(allowed, (list, tuple)) else allowed
-                    self._search_filtered(q[s:e], k, sub, exact_dense=exact_dense, async_=True, out=(D[s:e], I[s:e]))
-                return D, I
-            q = q.contiguous()
-            if out is not None:
-                D, I = out
-                if (D.shape != (B, k) or I.shape != (B, k) or D.dtype != torch.float32 or
-                        I.dtype != torch.int64 or not D.is_contiguous() or not I.is_contiguous()):
-                    raise ValueError("out must be contiguous (float32[B,k], int64[B,k]) CUDA tensors")
-            else:
-                D = torch.empty((B, k), dtype=torch.float32, device=q.device)
-                I = torch.empty((B, k), dtype=torch.int64, device=q.device)
-            if dev_bits is not None:   # (Stage1Retriever's filter cache, tools/filter_probe.py)
-                dbits, moq = dev_bits
-            else:
-                dbits = torch.from_numpy(bits.view(np.int32)).to(q.device)   # device copy, kept alive with the search
-            if async_:
-                if self.pending_room(B) < 0:
-                    if not self.auto_finish:
-                        raise RuntimeError("too many unfinished asynchronous searches: the owner of this index "
-                                           "must call finish() (see pending_room())")
-                    self._auto_redone = self.finish()
-                flags |= _lib.TS_FLAG_ASYNC
-            self._filtered_raw(q.data_ptr(), B, _tensor_dtype(q), k, dbits.data_ptr(), words, moq,
-                               D.data_ptr(), I.data_ptr(), flags, _stream_ptr(self.device))
-            if async_:
-                self._pending[int(self._lib.ts_index_last_ticket(self._h))] = (q, k, D, I, (dbits, words, moq))
-                self._pending_passes += (B + 31) // 32
-            return D, I
-        if async_:
-            raise ValueError("async_ search needs a CUDA tensor")
-        if _is_tensor(q):
-            q = q.detach().float().numpy()
-        q = np.ascontiguousarray(q)
-        if q.dtype not in _NP_DTYPES:
-            q = q.astype(np.float32)
-        if q.ndim != 2 or q.shape[1] != self.d:
-            raise ValueError(f"expected [B, {self.d}] queries, got {q.shape}")
-        D = np.empty((B, k), dtype=np.float32)
-        I = np.empty((B, k), dtype=np.int64)
-        self._filtered_raw(q.ctypes.data, B, _NP_DTYPES[q.dtype], k, bits.ctypes.data, words, moq,
-                           D.ctypes.data, I.ctypes.data, flags | _lib.TS_FLAG_HOST_PTR, 0)
-        return D, I
+        return (D, I) if on_gpu else (D.cpu().numpy(), I.cpu().numpy())
 
     # -- range search (DESIGN.md 4.13) -----------------------------------------
     def range_search(self, q, radius, allowed=None, max_results: Optional[int] = None, sort: bool = False,
@@ -809,23 +768,8 @@ class FlatIPIndex:
         ``exact_dense=True`` forces the dense path (tests, A/B runs).  Synchronous."""
         if self.storage_dtype == "fp8":
             raise NotImplementedError("range_search is not supported on an fp8 index")
-        was_tensor = _is_tensor(q) and q.is_cuda
-        if _is_tensor(q) and not q.is_cuda:
-            q = q.detach().float().numpy()
-        if not was_tensor:
-            q = np.ascontiguousarray(q)
-            if q.dtype not in _NP_DTYPES:
-                q = q.astype(np.float32)
-            if q.ndim != 2 or q.shape[1] != self.d:
-                raise ValueError(f"expected [B, {self.d}] queries, got {q.shape}")
-        else:
-            if q.dim() != 2 or q.shape[1] != self.d:
-                raise ValueError(f"expected [B, {self.d}] queries, got {tuple(q.shape)}")
-            q = q.contiguous()
-        B = int(q.shape[0])
-        if _is_tensor(radius):
-            radius = radius.detach().float().cpu().numpy()
-        rad = np.asarray(radius, dtype=np.float32).reshape(-1)
+        q, q_dtype, B, on_gpu = _host_query(q, self.d)
+        rad = np.asarray(_to_host(radius.float() if _is_tensor(radius) else radius), dtype=np.float32).reshape(-1)
         if rad.size == 1:
             rad = np.full(B, rad[0], dtype=np.float32)
         if rad.size != B:
@@ -834,75 +778,45 @@ class FlatIPIndex:
             raise ValueError("radius must not be NaN")
         rad = np.ascontiguousarray(rad)
         if self.ntotal == 0:
-            raise ValueError("No documents indexed. Call add_documents() first.")
-        if self._pending:   # unfinished async_ searches are verified first: this call is synchronous
-            self._auto_redone = self._auto_redone + self.finish()
-        flags = _lib.TS_FLAG_NO_FILTER if exact_dense else 0
-        keep = None
-        bits_ptr, words, n_masks, moq_ptr = None, 0, 0, None
-        if allowed is not None:
-            if getattr(allowed, "ndim", 1) == 2:
-                allowed = list(allowed)
-            words = (self.ntotal + 31) // 32
-            dev_bits = self._device_masks(allowed, B, words, q.device) if was_tensor else None
-            if dev_bits is not None:
-                keep, moq = dev_bits
-                bits_ptr = ctypes.c_void_p(keep.data_ptr())
-            else:
-                bits, words, moq = self._masks(allowed, B)
-                if was_tensor:
-                    keep = _torch().from_numpy(bits.view(np.int32)).to(q.device)
-                    bits_ptr = ctypes.c_void_p(keep.data_ptr())
-                else:
-                    keep = bits
-                    bits_ptr = bits.ctypes.data_as(ctypes.c_void_p)
-            moq = np.ascontiguousarray(moq, dtype=np.int32)
-            n_masks = int(moq.max()) + 1 if moq.size else 0
-            moq_ptr = moq.ctypes.data_as(ctypes.c_void_p)
-            if n_masks == 0:
-                bits_ptr, moq_ptr = None, None
+            _raise_empty()
+        self._finish_pending()   # unfinished async_ searches are verified first: this call is synchronous
+        flags = (_lib.TS_FLAG_NO_FILTER if exact_dense else 0) | (0 if on_gpu else _lib.TS_FLAG_HOST_PTR)
+        stream = _stream_ptr(self.device) if on_gpu else None
+        m = _NO_MASKS if allowed is None else _marshal_allowed(allowed, B, self.ntotal, q.device if on_gpu else None)
         lims = np.zeros(B + 1, dtype=np.int64)
-        if was_tensor:
-            q_ptr, q_dt, stream = ctypes.c_void_p(q.data_ptr()), _tensor_dtype(q), _stream_ptr(self.device)
-        else:
-            q_ptr, q_dt, stream = q.ctypes.data_as(ctypes.c_void_p), _NP_DTYPES[q.dtype], 0
-            flags |= _lib.TS_FLAG_HOST_PTR
-        stream = ctypes.c_void_p(stream) if stream else None
         code = self._lib.ts_index_range_search(
-            self._h, q_ptr, B, q_dt, rad.ctypes.data_as(ctypes.c_void_p), bits_ptr, int(words), n_masks, moq_ptr,
-            int(max_results) if max_results is not None else 0, lims.ctypes.data_as(ctypes.c_void_p), flags, stream)
-        del keep
+            self._h, _addr(q), B, q_dtype, _addr(rad), _addr(m.bits), m.words, m.n_masks,
+            _addr(m.moq) if m.n_masks else None, int(max_results) if max_results is not None else 0, _addr(lims),
+            flags, stream)
         if code == _lib.TS_ERR_UNSUPPORTED and "exceed the limit" in _lib.last_error():
             raise RangeSearchLimitError(_lib.last_error(), np.diff(lims))
-        if code == _lib.TS_ERR_EMPTY:
-            raise ValueError("No documents indexed. Call add_documents() first.")
-        _lib.check(code)
+        _check(code)
         total = int(lims[B])
-        if was_tensor:
+        if on_gpu:
             torch = _torch()
             D = torch.empty(total, dtype=torch.float32, device=q.device)
             I = torch.empty(total, dtype=torch.int64, device=q.device)
-            _lib.check(self._lib.ts_index_range_fetch(self._h, ctypes.c_void_p(D.data_ptr()), ctypes.c_void_p(I.data_ptr()),
-                                                      total, 0, stream))
-            L = torch.from_numpy(lims).to(q.device)
+        else:
+            D = np.empty(total, dtype=np.float32)
+            I = np.empty(total, dtype=np.int64)
+        _lib.check(self._lib.ts_index_range_fetch(self._h, _addr(D), _addr(I), total,
+                                                  0 if on_gpu else _lib.TS_FLAG_HOST_PTR, stream))
+        if not on_gpu:
             if sort and total:
-                # descending score with -0 equal to +0, then ascending id: ids ascend inside a segment already, so two
-                # stable sorts (score, then segment) give the order of search()
-                seg = torch.repeat_interleave(torch.arange(B, device=q.device), L[1:] - L[:-1])
-                o1 = torch.sort(D + 0.0, descending=True, stable=True).indices
-                o2 = torch.sort(seg[o1], stable=True).indices
-                order = o1[o2]
+                seg = np.repeat(np.arange(B), np.diff(lims))
+                order = np.lexsort((I, -(D + np.float32(0.0)), seg))   # segment, then score descending, then id
                 D, I = D[order], I[order]
-            return L, D, I
-        D = np.empty(total, dtype=np.float32)
-        I = np.empty(total, dtype=np.int64)
-        _lib.check(self._lib.ts_index_range_fetch(self._h, D.ctypes.data_as(ctypes.c_void_p), I.ctypes.data_as(ctypes.c_void_p),
-                                                  total, _lib.TS_FLAG_HOST_PTR, None))
+            return lims, D, I
+        L = torch.from_numpy(lims).to(q.device)
         if sort and total:
-            seg = np.repeat(np.arange(B), np.diff(lims))
-            order = np.lexsort((I, -(D + np.float32(0.0)), seg))   # segment, then score descending, then id
+            # descending score with -0 equal to +0, then ascending id: ids ascend inside a segment already, so two
+            # stable sorts (score, then segment) give the order of search()
+            seg = torch.repeat_interleave(torch.arange(B, device=q.device), L[1:] - L[:-1])
+            o1 = torch.sort(D + 0.0, descending=True, stable=True).indices
+            o2 = torch.sort(seg[o1], stable=True).indices
+            order = o1[o2]
             D, I = D[order], I[order]
-        return lims, D, I
+        return L, D, I
 
     def last_range_info(self) -> dict:
         """The last :meth:`range_search`: its passes (of <= 64 queries), how many ran the filter scan, and how many
@@ -926,41 +840,21 @@ class FlatIPIndex:
         return {"live_blocks": int(arr[0]), "total_blocks": int(arr[1]), "filter_passes": int(arr[2]),
                 "dense_passes": int(arr[3])}
 
-    def _id_offset_value(self) -> int:
-        return getattr(self, "_id_offset", 0)
-
     def scores(self, q):
         """All inner products, in row order: float32 [B, ntotal] (a CUDA tensor for tensor
         input, numpy for numpy input).  No selection; the dense scan writes the matrix."""
-        torch = _torch()
         was_np = not _is_tensor(q)
-        dev = torch.device("cuda", self.device)
-        qt = torch.as_tensor(np.ascontiguousarray(q, dtype=np.float32)) if was_np else q
-        if qt.dim() != 2 or qt.shape[1] != self.d:
-            raise ValueError(f"expected [B, {self.d}] queries, got {tuple(qt.shape)}")
-        if qt.dtype not in (torch.float32, torch.float16, torch.bfloat16):
-            qt = qt.float()
-        qt = qt.to(dev).contiguous()
+        if was_np:   # a host array is scored as f32, whatever it came as
+            q = np.ascontiguousarray(q, dtype=np.float32)
+        qt, q_dtype, B, _ = _device_query(q, self.d, self.device)
         n = self.ntotal
         if n == 0:
-            raise ValueError("No documents indexed. Call add_documents() first.")
+            _raise_empty()
         ld = (n + 31) // 32 * 32
-        out = torch.empty((qt.shape[0], ld), dtype=torch.float32, device=dev)
-        _lib.check(self._lib.ts_index_scores(self._h, ctypes.c_void_p(qt.data_ptr()), qt.shape[0],
-                                             _tensor_dtype(qt), ctypes.c_void_p(out.data_ptr()), ld,
-                                             ctypes.c_void_p(_stream_ptr(self.device)) if _stream_ptr(self.device) else None))
+        out = _torch().empty((B, ld), dtype=_torch().float32, device=qt.device)
+        _lib.check(self._lib.ts_index_scores(self._h, _addr(qt), B, q_dtype, _addr(out), ld, _stream_ptr(self.device)))
         out = out[:, :n]
         return out.cpu().numpy() if was_np else out
-
-    def _search_raw(self, q_ptr: int, B: int, q_dtype: int, k: int, d_ptr: int, i_ptr: int,
-                    flags: int, stream: int) -> None:
-        code = self._lib.ts_index_search(self._h, ctypes.c_void_p(q_ptr), B, q_dtype, k,
-                                         ctypes.c_void_p(d_ptr), ctypes.c_void_p(i_ptr), flags,
-                                         ctypes.c_void_p(stream) if stream else None)
-        if code == _lib.TS_ERR_EMPTY:
-            # same exception type and text as reference src/stage1_retriever.py:370-371
-            raise ValueError("No documents indexed. Call add_documents() first.")
-        _lib.check(code)
 
     def search_in_stream_order(self, q, k: int):
         """search() for a caller that consumes (D, I) on the current stream only: when the dense path will be taken
@@ -978,8 +872,7 @@ class FlatIPIndex:
     def flush(self) -> None:
         """Enqueue the scans that coalesced ``async_`` searches are holding, without a host sync: their results
         are then ordered on the current stream (still verified only by :meth:`finish`)."""
-        _lib.check(self._lib.ts_index_flush(self._h, ctypes.c_void_p(_stream_ptr(self.device)) if
-                                            _stream_ptr(self.device) else None))
+        _lib.check(self._lib.ts_index_flush(self._h, _stream_ptr(self.device)))
 
     def finish(self):
         """Complete every asynchronous search: one stream sync, then the (rare)
@@ -989,8 +882,7 @@ class FlatIPIndex:
         too many searches were pending — had to repeat)."""
         failed = (ctypes.c_int64 * 256)()
         nf = ctypes.c_int32(0)
-        _lib.check(self._lib.ts_index_finish(self._h, ctypes.c_void_p(_stream_ptr(self.device)) if
-                                             _stream_ptr(self.device) else None, failed, 256, ctypes.byref(nf)))
+        _lib.check(self._lib.ts_index_finish(self._h, _stream_ptr(self.device), failed, 256, ctypes.byref(nf)))
         redone = []
         if any(self._pending[int(failed[i])][4] is not None for i in range(nf.value)):
             # a redo is a new library call that resets the filter counters: last_filter_info() keeps describing the
@@ -999,12 +891,9 @@ class FlatIPIndex:
         for i in range(nf.value):
             q, k, D, I, masks = self._pending[int(failed[i])]
             if masks is None:
-                self._search_raw(q.data_ptr(), q.shape[0], _tensor_dtype(q), k, D.data_ptr(), I.data_ptr(),
-                                 _lib.TS_FLAG_NO_FILTER, _stream_ptr(self.device))
+                self._search_raw(q, _tensor_dtype(q), k, D, I, _lib.TS_FLAG_NO_FILTER, _stream_ptr(self.device))
             else:   # a filtered search: redone on the exact dense path with the masks it kept alive
-                bits, words, moq = masks
-                self._filtered_raw(q.data_ptr(), q.shape[0], _tensor_dtype(q), k, bits.data_ptr(), words,
-                                   moq, D.data_ptr(), I.data_ptr(), _lib.TS_FLAG_NO_FILTER, _stream_ptr(self.device))
+                self._filtered_raw(q, _tensor_dtype(q), k, masks, D, I, _lib.TS_FLAG_NO_FILTER, _stream_ptr(self.device))
             redone.append(int(failed[i]))
         self._pending.clear()
         self._pending_passes = 0
@@ -1037,9 +926,7 @@ class FlatIPIndex:
     def search_mmr(self, q, k: int, fetch_k: Optional[int] = None, lambda_mult: float = 0.5, allowed=None):
         """``search(q, fetch_k, allowed=allowed)`` followed by :meth:`mmr` on the same stream; ``fetch_k`` defaults to
         ``min(1024, max(4 k, 20))``."""
-        k, fetch_k, lam = mmr_check(k, mmr_default_fetch_k(k) if fetch_k is None else fetch_k, lambda_mult)
-        D, I = self.search(q, fetch_k, allowed=allowed)
-        return self.mmr(I, D, k, lam)
+        return self._search_mmr(q, k, fetch_k, lambda_mult, allowed=allowed)
 
     # -- grouped search (DESIGN.md 4.18) --------------------------------------
     def search_grouped(self, q, k: int, groups, group_size: int = 1, fetch_k: Optional[int] = None, allowed=None):
@@ -1057,11 +944,7 @@ class FlatIPIndex:
         order of those rows, each represented by that row.  ``group_size > 1``: a group's rows are its best rows WITHIN
         THE FIRST ``fetched`` PLACES (the non-strict group size of Milvus): a further row of a returned group that
         ranks behind place ``fetched`` is not returned."""
-        return grouped_search(self, lambda x, f: self.search(x, f, allowed=allowed), q, k, groups, group_size, fetch_k)
-
-    def last_group_info(self) -> dict:
-        """``{"fetched", "rounds", "n_groups", "complete"}`` of the last :meth:`search_grouped` (the last two per query)."""
-        return dict(getattr(self, "_group_info", {}))
+        return self._search_grouped(q, k, groups, group_size, fetch_k, allowed=allowed)
 
     # -- funnel search (DESIGN.md 4.21) ----------------------------------------
     def _funnel_storage(self, what: str) -> None:
@@ -1079,51 +962,15 @@ class FlatIPIndex:
         self._funnel_storage("search_prefix")
         k, dims = funnel_check(self.d, dims, k)
         if self.ntotal == 0:
-            raise ValueError("No documents indexed. Call add_documents() first.")
-        if q.ndim != 2 or q.shape[1] != self.d:
-            raise ValueError(f"expected [B, {self.d}] queries, got {tuple(q.shape)}")
-        B = int(q.shape[0])
-        flags = _lib.TS_FLAG_NO_FILTER if exact_dense else 0
-        on_gpu = _is_tensor(q) and q.is_cuda
-        words = (self.ntotal + 31) // 32
-        bits = dev_bits = moq = None
-        if allowed is not None:
-            if getattr(allowed, "ndim", 1) == 2:
-                allowed = list(allowed)
-            if on_gpu:
-                dev_bits = self._device_masks(allowed, B, words, q.device)
-            if dev_bits is None:
-                bits, words, moq = self._masks(allowed, B)
-        if on_gpu:
-            torch = _torch()
-            qp = q[:, :dims].contiguous()
-            D = torch.empty((B, k), dtype=torch.float32, device=q.device)
-            I = torch.empty((B, k), dtype=torch.int64, device=q.device)
-            if dev_bits is not None:
-                dbits, moq = dev_bits
-            elif bits is not None:
-                dbits = torch.from_numpy(bits.view(np.int32)).to(q.device)
-            q_ptr, q_dt, b_ptr = qp.data_ptr(), _tensor_dtype(qp), (dbits.data_ptr() if allowed is not None else 0)
-            d_ptr, i_ptr, stream = D.data_ptr(), I.data_ptr(), _stream_ptr(self.device)
-        else:
-            if _is_tensor(q):
-                q = q.detach().float().numpy()
-            qp = np.ascontiguousarray(q[:, :dims])
-            if qp.dtype not in _NP_DTYPES:
-                qp = qp.astype(np.float32)
-            D = np.empty((B, k), dtype=np.float32)
-            I = np.empty((B, k), dtype=np.int64)
-            q_ptr, q_dt, b_ptr = qp.ctypes.data, _NP_DTYPES[qp.dtype], (bits.ctypes.data if bits is not None else 0)
-            d_ptr, i_ptr, stream = D.ctypes.data, I.ctypes.data, 0
-            flags |= _lib.TS_FLAG_HOST_PTR
-        n_masks = (int(moq.max()) + 1 if moq.size else 0) if moq is not None else 0
-        code = self._lib.ts_index_search_prefix(
-            self._h, ctypes.c_void_p(q_ptr), B, q_dt, dims, k, ctypes.c_void_p(b_ptr) if n_masks else None,
-            int(words) if n_masks else 0, n_masks, moq.ctypes.data_as(ctypes.c_void_p) if moq is not None else None,
-            ctypes.c_void_p(d_ptr), ctypes.c_void_p(i_ptr), flags, ctypes.c_void_p(stream) if stream else None)
-        if code == _lib.TS_ERR_INVALID:
-            raise ValueError(_lib.last_error())
-        _lib.check(code)
+            _raise_empty()
+        q, q_dtype, B, on_gpu = _host_query(q, self.d)
+        q = q[:, :dims].contiguous() if on_gpu else np.ascontiguousarray(q[:, :dims])
+        D, I = _outputs(None, B, k, q)
+        flags = (_lib.TS_FLAG_NO_FILTER if exact_dense else 0) | (0 if on_gpu else _lib.TS_FLAG_HOST_PTR)
+        m = _NO_MASKS if allowed is None else _marshal_allowed(allowed, B, self.ntotal, q.device if on_gpu else None)
+        _check(self._lib.ts_index_search_prefix(
+            self._h, _addr(q), B, q_dtype, dims, k, _addr(m.bits), m.words if m.n_masks else 0, m.n_masks,
+            _addr(m.moq), _addr(D), _addr(I), flags, _stream_ptr(self.device) if on_gpu else None), invalid=True)
         return D, I
 
     def rescore(self, q, ids, k: Optional[int] = None):
@@ -1134,39 +981,27 @@ class FlatIPIndex:
         ``scores(q)[b, id]``, and so to :meth:`search`.  Synchronous, on the current stream; tensors out when ``q`` or
         ``ids`` is a CUDA tensor, numpy otherwise."""
         self._funnel_storage("rescore")
-        if q.ndim != 2 or q.shape[1] != self.d:
-            raise ValueError(f"expected [B, {self.d}] queries, got {tuple(q.shape)}")
+        if q.ndim != 2 or q.shape[1] != self.d:   # (every argument is checked before anything is uploaded)
+            _bad_shape("B", self.d, "queries", q.shape)
         if ids.ndim != 2 or ids.shape[0] != q.shape[0]:
             raise ValueError(f"expected ids [B, C] with B = {q.shape[0]}, got {tuple(ids.shape)}")
-        B, C = int(ids.shape[0]), int(ids.shape[1])
+        C = int(ids.shape[1])
         k = C if k is None else int(k)
         if not 1 <= C <= FUNNEL_MAX_FETCH:
             raise ValueError(f"rescore takes 1 .. {FUNNEL_MAX_FETCH} candidates per query, got {C}")
         if not 1 <= k <= C:
             raise ValueError(f"k={k} must be in 1 .. C = {C}")
         if self.ntotal == 0:
-            raise ValueError("No documents indexed. Call add_documents() first.")
+            _raise_empty()
         torch = _torch()
-        dev = torch.device("cuda", self.device)
-        was_np = not ((_is_tensor(q) and q.is_cuda) or (_is_tensor(ids) and ids.is_cuda))
-        if not _is_tensor(q):
-            q = np.ascontiguousarray(q)
-            q = torch.from_numpy(q if q.dtype in _NP_DTYPES else q.astype(np.float32))
-        if q.dtype not in (torch.float32, torch.float16, torch.bfloat16):
-            q = q.float()
-        qt = q.to(dev).contiguous()
-        it = (ids if _is_tensor(ids) else torch.from_numpy(np.ascontiguousarray(ids, dtype=np.int64)))
-        it = it.to(device=dev, dtype=torch.int64).contiguous()
-        D = torch.empty((B, k), dtype=torch.float32, device=dev)
-        I = torch.empty((B, k), dtype=torch.int64, device=dev)
+        q, q_dtype, B, on_gpu = _device_query(q, self.d, self.device)
+        was_np = not (on_gpu or (_is_tensor(ids) and ids.is_cuda))
+        ids = ids if _is_tensor(ids) else torch.from_numpy(np.ascontiguousarray(ids, dtype=np.int64))
+        ids = ids.to(device=q.device, dtype=torch.int64).contiguous()
+        D, I = _outputs(None, B, k, q)
         if B:
-            stream = _stream_ptr(self.device)
-            code = self._lib.ts_index_rescore(
-                self._h, ctypes.c_void_p(qt.data_ptr()), B, _tensor_dtype(qt), ctypes.c_void_p(it.data_ptr()), C, k,
-                ctypes.c_void_p(D.data_ptr()), ctypes.c_void_p(I.data_ptr()), ctypes.c_void_p(stream) if stream else None)
-            if code == _lib.TS_ERR_INVALID:
-                raise ValueError(_lib.last_error())
-            _lib.check(code)
+            _check(self._lib.ts_index_rescore(self._h, _addr(q), B, q_dtype, _addr(ids), C, k, _addr(D), _addr(I),
+                                              _stream_ptr(self.device)), invalid=True)
         return (D.cpu().numpy(), I.cpu().numpy()) if was_np else (D, I)
 
     def search_funnel(self, q, k: int, dims: int, fetch_k: Optional[int] = None, allowed=None):
@@ -1177,16 +1012,14 @@ class FlatIPIndex:
         :meth:`last_funnel_info` describes the call."""
         self._funnel_storage("search_funnel")
         k, dims, fetch_k = funnel_check(self.d, dims, k, funnel_default_fetch_k(k) if fetch_k is None else fetch_k)
-        was_np = not (_is_tensor(q) and q.is_cuda)
-        if was_np:
-            torch = _torch()
-            qn = np.ascontiguousarray(q.detach().cpu().numpy() if _is_tensor(q) else q)
-            q = torch.from_numpy(qn if qn.dtype in _NP_DTYPES else qn.astype(np.float32)).to(torch.device("cuda", self.device))
+        if self.ntotal == 0:
+            _raise_empty()
+        q, _, _, on_gpu = _device_query(q, self.d, self.device)
         _, cand = self.search_prefix(q, fetch_k, dims, allowed=allowed)
         path = "filter" if self.last_search_info()["path"] == "filter" else "dense"
         D, I = self.rescore(q, cand, k)
         self._funnel_info = {"dims": dims, "fetch_k": fetch_k, "prefix_path": path}
-        return (D.cpu().numpy(), I.cpu().numpy()) if was_np else (D, I)
+        return (D, I) if on_gpu else (D.cpu().numpy(), I.cpu().numpy())
 
     def last_funnel_info(self) -> dict:
         """``{"dims", "fetch_k", "prefix_path"}`` of the last :meth:`search_funnel`; ``prefix_path`` is ``"filter"`` when
@@ -1200,9 +1033,7 @@ class FlatIPIndex:
             n = self.ntotal - i0
         out = np.empty((n, self.d), dtype=np.float32)
         if n:
-            _lib.check(self._lib.ts_index_reconstruct(self._h, int(i0), int(n),
-                                                      out.ctypes.data_as(ctypes.c_void_p),
-                                                      _lib.TS_FLAG_HOST_PTR, None))
+            _lib.check(self._lib.ts_index_reconstruct(self._h, int(i0), int(n), _addr(out), _lib.TS_FLAG_HOST_PTR, None))
         return out
 
     PHASES = ("qprep", "sample_scan", "tau", "filter_scan", "select", "dense", "_6", "_7")
@@ -1223,9 +1054,8 @@ class FlatIPIndex:
         the streaming ceiling of THIS box, measured with HIP events.  {"bytes", "ms_avg", "ms_best", "gbps_avg",
         "gbps_best"}."""
         ms_avg, ms_best, nbytes = ctypes.c_double(0), ctypes.c_double(0), ctypes.c_int64(0)
-        st = _stream_ptr(self.device)
         _lib.check(self._lib.ts_index_read_probe(self._h, int(reps), ctypes.byref(ms_avg), ctypes.byref(ms_best),
-                                                 ctypes.byref(nbytes), ctypes.c_void_p(st) if st else None))
+                                                 ctypes.byref(nbytes), _stream_ptr(self.device)))
         return {"bytes": int(nbytes.value), "ms_avg": ms_avg.value, "ms_best": ms_best.value,
                 "gbps_avg": nbytes.value / (ms_avg.value * 1e-3) / 1e9, "gbps_best": nbytes.value / (ms_best.value * 1e-3) / 1e9}
 
@@ -1256,10 +1086,8 @@ def merge_topk(scores, ids, k: Optional[int] = None):
     out_s = torch.empty((B, kk), dtype=torch.float32, device=scores.device)
     out_i = torch.empty((B, kk), dtype=torch.int64, device=scores.device)
     dev = scores.device.index
-    _lib.check(lib.ts_merge_topk(ctypes.c_void_p(scores.data_ptr()), ctypes.c_void_p(ids.data_ptr()),
-                                 R, B, kk, ctypes.c_void_p(out_s.data_ptr()),
-                                 ctypes.c_void_p(out_i.data_ptr()), dev,
-                                 ctypes.c_void_p(_stream_ptr(dev))))
+    _lib.check(lib.ts_merge_topk(_addr(scores), _addr(ids), R, B, kk, _addr(out_s), _addr(out_i), dev,
+                                 _stream_ptr(dev)))
     return out_s, out_i
 
 
@@ -1282,10 +1110,8 @@ def merge_topk_packed(gathered, R: int, B: int, k: int):
     out_i = torch.empty((B, k), dtype=torch.int64, device=gathered.device)
     base = gathered.data_ptr()
     dev = gathered.device.index
-    _lib.check(lib.ts_merge_topk_strided(ctypes.c_void_p(base), ctypes.c_void_p(base + ids_at), R, B, k,
-                                         nbytes // 4, nbytes // 8, ctypes.c_void_p(out_s.data_ptr()),
-                                         ctypes.c_void_p(out_i.data_ptr()), dev,
-                                         ctypes.c_void_p(_stream_ptr(dev))))
+    _lib.check(lib.ts_merge_topk_strided(base, base + ids_at, R, B, k, nbytes // 4, nbytes // 8, _addr(out_s),
+                                         _addr(out_i), dev, _stream_ptr(dev)))
     return out_s, out_i
 
 
@@ -1306,12 +1132,8 @@ def maxsim(q, docs, doc_offsets, mode: str = "maxsim"):
     if n_docs <= 0:
         return out
     dev = q.device.index
-    _lib.check(lib.ts_maxsim(ctypes.c_void_p(q.data_ptr()), q.shape[0],
-                             ctypes.c_void_p(docs.data_ptr()),
-                             ctypes.c_void_p(doc_offsets.data_ptr()), n_docs, q.shape[1],
-                             _tensor_dtype(q), 0 if mode == "maxsim" else 1,
-                             ctypes.c_void_p(out.data_ptr()), dev,
-                             ctypes.c_void_p(_stream_ptr(dev))))
+    _lib.check(lib.ts_maxsim(_addr(q), q.shape[0], _addr(docs), _addr(doc_offsets), n_docs, q.shape[1],
+                             _tensor_dtype(q), 0 if mode == "maxsim" else 1, _addr(out), dev, _stream_ptr(dev)))
     return out
 
 
@@ -1336,11 +1158,8 @@ def maxsim_indexed(q, store, starts, lens, mode: str = "maxsim"):
     if n == 0:
         return out
     dev = q.device.index
-    _lib.check(lib.ts_maxsim_indexed(ctypes.c_void_p(q.data_ptr()), q.shape[0],
-                                     ctypes.c_void_p(store.data_ptr()), ctypes.c_void_p(starts.data_ptr()),
-                                     ctypes.c_void_p(lens.data_ptr()), n, q.shape[1], _tensor_dtype(q),
-                                     0 if mode == "maxsim" else 1, ctypes.c_void_p(out.data_ptr()), dev,
-                                     ctypes.c_void_p(_stream_ptr(dev))))
+    _lib.check(lib.ts_maxsim_indexed(_addr(q), q.shape[0], _addr(store), _addr(starts), _addr(lens), n, q.shape[1],
+                                     _tensor_dtype(q), 0 if mode == "maxsim" else 1, _addr(out), dev, _stream_ptr(dev)))
     return out
 
 
@@ -1377,18 +1196,14 @@ def maxsim_indexed_batch(q_packed, q_offsets, store, starts, lens, cand_offsets,
         return out
     dev = q_packed.device.index
     if fp8:
-        _lib.check(lib.ts_maxsim_indexed_batch_fp8(ctypes.c_void_p(q_packed.data_ptr()), _tensor_dtype(q_packed),
-                                                   qo.ctypes.data_as(ctypes.c_void_p), nq,
-                                                   ctypes.c_void_p(store.data_ptr()), ctypes.c_void_p(starts.data_ptr()),
-                                                   ctypes.c_void_p(lens.data_ptr()), co.ctypes.data_as(ctypes.c_void_p),
-                                                   q_packed.shape[1], 0 if mode == "maxsim" else 1,
-                                                   ctypes.c_void_p(out.data_ptr()), dev, ctypes.c_void_p(_stream_ptr(dev))))
+        _lib.check(lib.ts_maxsim_indexed_batch_fp8(_addr(q_packed), _tensor_dtype(q_packed), _addr(qo), nq,
+                                                   _addr(store), _addr(starts), _addr(lens), _addr(co),
+                                                   q_packed.shape[1], 0 if mode == "maxsim" else 1, _addr(out), dev,
+                                                   _stream_ptr(dev)))
         return out
-    _lib.check(lib.ts_maxsim_indexed_batch(ctypes.c_void_p(q_packed.data_ptr()), qo.ctypes.data_as(ctypes.c_void_p), nq,
-                                           ctypes.c_void_p(store.data_ptr()), ctypes.c_void_p(starts.data_ptr()),
-                                           ctypes.c_void_p(lens.data_ptr()), co.ctypes.data_as(ctypes.c_void_p),
-                                           q_packed.shape[1], _tensor_dtype(q_packed), 0 if mode == "maxsim" else 1,
-                                           ctypes.c_void_p(out.data_ptr()), dev, ctypes.c_void_p(_stream_ptr(dev))))
+    _lib.check(lib.ts_maxsim_indexed_batch(_addr(q_packed), _addr(qo), nq, _addr(store), _addr(starts), _addr(lens),
+                                           _addr(co), q_packed.shape[1], _tensor_dtype(q_packed),
+                                           0 if mode == "maxsim" else 1, _addr(out), dev, _stream_ptr(dev)))
     return out
 
 
@@ -1468,12 +1283,10 @@ def maxsim_passages_indexed_batch(q_packed, q_offsets, store, starts, lens, cand
     o_align = torch.empty((n, max_lq), dtype=torch.int32, device=dev_t) if align else None
     if n and nq:
         dev = dev_t.index
-        _lib.check(lib.ts_maxsim_passages_indexed_batch(
-            ctypes.c_void_p(q_packed.data_ptr()), qo.ctypes.data_as(ctypes.c_void_p), nq,
-            ctypes.c_void_p(store.data_ptr()), ctypes.c_void_p(starts.data_ptr()), ctypes.c_void_p(lens.data_ptr()),
-            co.ctypes.data_as(ctypes.c_void_p), H, _tensor_dtype(q_packed), int(min(window, 1 << 30)),
-            ctypes.c_void_p(o_start.data_ptr()), ctypes.c_void_p(o_len.data_ptr()), ctypes.c_void_p(o_score.data_ptr()),
-            ctypes.c_void_p(o_align.data_ptr()) if align else None, max_lq, dev, ctypes.c_void_p(_stream_ptr(dev))))
+        _lib.check(lib.ts_maxsim_passages_indexed_batch(_addr(q_packed), _addr(qo), nq, _addr(store), _addr(starts),
+                                                        _addr(lens), _addr(co), H, _tensor_dtype(q_packed),
+                                                        int(min(window, 1 << 30)), _addr(o_start), _addr(o_len),
+                                                        _addr(o_score), _addr(o_align), max_lq, dev, _stream_ptr(dev)))
     return (o_start, o_len, o_score, o_align) if align else (o_start, o_len, o_score)
 
 
@@ -1571,8 +1384,7 @@ def quantize_rows_fp8(x):
     if rows == 0:
         return out
     dev = x.device.index
-    _lib.check(lib.ts_quantize_rows_fp8(ctypes.c_void_p(x.data_ptr()), _tensor_dtype(x), rows, H,
-                                        ctypes.c_void_p(out.data_ptr()), dev, ctypes.c_void_p(_stream_ptr(dev))))
+    _lib.check(lib.ts_quantize_rows_fp8(_addr(x), _tensor_dtype(x), rows, H, _addr(out), dev, _stream_ptr(dev)))
     return out
 
 
@@ -1593,11 +1405,9 @@ def _maxsim_indexed_fp8(q, store, starts, lens, mode):
     if n == 0:
         return out
     dev = q.device.index
-    _lib.check(lib.ts_maxsim_indexed_fp8(ctypes.c_void_p(q.data_ptr()), _tensor_dtype(q), q.shape[0],
-                                         ctypes.c_void_p(store.data_ptr()), ctypes.c_void_p(starts.data_ptr()),
-                                         ctypes.c_void_p(lens.data_ptr()), n, q.shape[1],
-                                         0 if mode == "maxsim" else 1, ctypes.c_void_p(out.data_ptr()), dev,
-                                         ctypes.c_void_p(_stream_ptr(dev))))
+    _lib.check(lib.ts_maxsim_indexed_fp8(_addr(q), _tensor_dtype(q), q.shape[0], _addr(store), _addr(starts),
+                                         _addr(lens), n, q.shape[1], 0 if mode == "maxsim" else 1, _addr(out), dev,
+                                         _stream_ptr(dev)))
     return out
 
 
@@ -1624,10 +1434,10 @@ def add_layernorm(x, residual, gamma, beta, eps: float, lp_dtype=None, want_f32:
     out32 = torch.empty(x.shape, dtype=torch.float32, device=x.device) if want_f32 else None
     outlp = torch.empty(x.shape, dtype=lp_dtype, device=x.device) if lp_dtype is not None else None
     dev = x.device.index
-    ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
     fn = lib.ts_add_prenorm if prenorm else lib.ts_add_layernorm
-    _lib.check(fn(ptr(x), _tensor_dtype(x), ptr(residual), ptr(gamma), ptr(beta), float(eps), rows, H, ptr(out32), ptr(outlp),
-                  _tensor_dtype(outlp) if outlp is not None else _lib.TS_BF16, dev, ctypes.c_void_p(_stream_ptr(dev))))
+    _lib.check(fn(_addr(x), _tensor_dtype(x), _addr(residual), _addr(gamma), _addr(beta), float(eps), rows, H,
+                  _addr(out32), _addr(outlp), _tensor_dtype(outlp) if outlp is not None else _lib.TS_BF16, dev,
+                  _stream_ptr(dev)))
     return out32, outlp
 
 
@@ -1666,10 +1476,9 @@ def attention_varlen(qkv, lens, heads: int, out=None, scale: Optional[float] = N
             if (t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] < L or t.shape[1] != dh or not t.is_contiguous()
                     or t.device != qkv.device):
                 raise ValueError("rope tables must be contiguous float32 [>= L, head_dim] on qkv's device")
-    ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
-    _lib.check(lib.ts_attention_varlen(ptr(qkv), ptr(lens), B, L, heads, dh, _tensor_dtype(qkv),
-                                       float(scale if scale is not None else dh ** -0.5), int(window), ptr(cos), ptr(sin),
-                                       ptr(offs), ptr(out), dev, ctypes.c_void_p(_stream_ptr(dev))))
+    _lib.check(lib.ts_attention_varlen(_addr(qkv), _addr(lens), B, L, heads, dh, _tensor_dtype(qkv),
+                                       float(scale if scale is not None else dh ** -0.5), int(window), _addr(cos),
+                                       _addr(sin), _addr(offs), _addr(out), dev, _stream_ptr(dev)))
     return out
 
 
@@ -1686,8 +1495,8 @@ def rope_inplace(qkv, cos, sin, heads: int):
         if t.dtype != torch.float32 or tuple(t.shape) != (L, dh) or not t.is_contiguous() or t.device != qkv.device:
             raise ValueError("cos / sin must be contiguous float32 [L, head_dim] on qkv's device")
     dev = qkv.device.index
-    _lib.check(lib.ts_rope_inplace(ctypes.c_void_p(qkv.data_ptr()), _tensor_dtype(qkv), ctypes.c_void_p(cos.data_ptr()),
-                                   ctypes.c_void_p(sin.data_ptr()), B, L, heads, dh, dev, ctypes.c_void_p(_stream_ptr(dev))))
+    _lib.check(lib.ts_rope_inplace(_addr(qkv), _tensor_dtype(qkv), _addr(cos), _addr(sin), B, L, heads, dh, dev,
+                                   _stream_ptr(dev)))
     return qkv
 
 
@@ -1700,8 +1509,7 @@ def geglu(u):
     I = int(u.shape[-1]) // 2
     out = torch.empty(tuple(u.shape[:-1]) + (I,), dtype=u.dtype, device=u.device)
     dev = u.device.index
-    _lib.check(lib.ts_geglu(ctypes.c_void_p(u.data_ptr()), _tensor_dtype(u), u.numel() // (2 * I), I,
-                            ctypes.c_void_p(out.data_ptr()), dev, ctypes.c_void_p(_stream_ptr(dev))))
+    _lib.check(lib.ts_geglu(_addr(u), _tensor_dtype(u), u.numel() // (2 * I), I, _addr(out), dev, _stream_ptr(dev)))
     return out
 
 
@@ -1725,11 +1533,11 @@ def embed_layernorm(ids, pos_ids, type_ids, word, pos, typ, gamma, beta, eps: fl
     out32 = torch.empty(shape, dtype=torch.float32, device=ids.device) if want_f32 else None
     outlp = torch.empty(shape, dtype=lp_dtype, device=ids.device) if lp_dtype is not None else None
     dev = ids.device.index
-    ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
-    _lib.check(lib.ts_embed_layernorm(ptr(idx[0]), ptr(idx[1]), ptr(idx[2]), ptr(tabs[0]), ptr(tabs[1]), ptr(tabs[2]),
-                                      ptr(tabs[3]), ptr(tabs[4]), float(eps), ids.numel(), H, ptr(out32), ptr(outlp),
+    _lib.check(lib.ts_embed_layernorm(_addr(idx[0]), _addr(idx[1]), _addr(idx[2]), _addr(tabs[0]), _addr(tabs[1]),
+                                      _addr(tabs[2]), _addr(tabs[3]), _addr(tabs[4]), float(eps), ids.numel(), H,
+                                      _addr(out32), _addr(outlp),
                                       _tensor_dtype(outlp) if outlp is not None else _lib.TS_BF16, dev,
-                                      ctypes.c_void_p(_stream_ptr(dev))))
+                                      _stream_ptr(dev)))
     return out32, outlp
 
 
@@ -1756,10 +1564,10 @@ def mlp_add_layernorm(up: "TiledLinear", down: "TiledLinear", x, residual, gamma
     out32 = torch.empty(x.shape, dtype=torch.float32, device=x.device) if want_f32 else None
     outlp = torch.empty(x.shape, dtype=x.dtype, device=x.device)
     dev = x.device.index
-    ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
-    _lib.check(_lib.load().ts_mlp_add_layernorm(ptr(up.tiled), ptr(up.bias), ptr(down.tiled), ptr(down.bias), ptr(x), ptr(residual),
-                                                ptr(gamma), ptr(beta), float(eps), _tensor_dtype(x), x.numel() // H, H, up.N,
-                                                ptr(out32), ptr(outlp), dev, ctypes.c_void_p(_stream_ptr(dev))))
+    _lib.check(_lib.load().ts_mlp_add_layernorm(_addr(up.tiled), _addr(up.bias), _addr(down.tiled), _addr(down.bias),
+                                                _addr(x), _addr(residual), _addr(gamma), _addr(beta), float(eps),
+                                                _tensor_dtype(x), x.numel() // H, H, up.N, _addr(out32), _addr(outlp),
+                                                dev, _stream_ptr(dev)))
     return out32, outlp
 
 
@@ -1800,8 +1608,8 @@ class TiledLinear:
         self.bias = bias.detach().to(w.dtype).contiguous() if bias is not None else None
         self.tiled = torch.empty_like(w)
         dev = w.device.index
-        _lib.check(lib.ts_linear_tile_weight(ctypes.c_void_p(w.data_ptr()), _tensor_dtype(w), self.N, self.K,
-                                             ctypes.c_void_p(self.tiled.data_ptr()), dev, ctypes.c_void_p(_stream_ptr(dev))))
+        _lib.check(lib.ts_linear_tile_weight(_addr(w), _tensor_dtype(w), self.N, self.K, _addr(self.tiled), dev,
+                                             _stream_ptr(dev)))
 
     def __call__(self, x, gelu: bool = False):
         torch = _torch()
@@ -1809,10 +1617,9 @@ class TiledLinear:
             raise ValueError("x must be a contiguous [..., K] tensor of the weight's dtype on its device")
         out = torch.empty(tuple(x.shape[:-1]) + (self.N,), dtype=x.dtype, device=x.device)
         dev = x.device.index
-        _lib.check(_lib.load().ts_linear_act(ctypes.c_void_p(self.tiled.data_ptr()), ctypes.c_void_p(x.data_ptr()),
-                                             ctypes.c_void_p(self.bias.data_ptr()) if self.bias is not None else None,
-                                             _tensor_dtype(x), x.numel() // self.K, self.N, self.K, 1 if gelu else 0,
-                                             ctypes.c_void_p(out.data_ptr()), dev, ctypes.c_void_p(_stream_ptr(dev))))
+        _lib.check(_lib.load().ts_linear_act(_addr(self.tiled), _addr(x), _addr(self.bias), _tensor_dtype(x),
+                                             x.numel() // self.K, self.N, self.K, 1 if gelu else 0, _addr(out), dev,
+                                             _stream_ptr(dev)))
         return out
 
     def add_layernorm(self, x, residual, gamma, beta, eps: float, want_f32: bool = True, gelu_input: bool = False):
@@ -1840,15 +1647,14 @@ class TiledLinear:
         out32 = torch.empty(shape, dtype=torch.float32, device=x.device) if want_f32 else None
         outlp = torch.empty(shape, dtype=x.dtype, device=x.device)
         dev = x.device.index
-        ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
-        _lib.check(_lib.load().ts_linear_add_layernorm(ptr(self.tiled), ptr(x), ptr(self.bias), ptr(residual), ptr(gamma), ptr(beta),
-                                                       float(eps), _tensor_dtype(x), x.numel() // self.K, self.N, self.K,
-                                                       1 if gelu_input else 0, ptr(out32), ptr(outlp), dev,
-                                                       ctypes.c_void_p(_stream_ptr(dev))))
+        _lib.check(_lib.load().ts_linear_add_layernorm(_addr(self.tiled), _addr(x), _addr(self.bias), _addr(residual),
+                                                       _addr(gamma), _addr(beta), float(eps), _tensor_dtype(x),
+                                                       x.numel() // self.K, self.N, self.K, 1 if gelu_input else 0,
+                                                       _addr(out32), _addr(outlp), dev, _stream_ptr(dev)))
         return out32, outlp
 
 
-class IVFFlatIndex:
+class IVFFlatIndex(_IndexBase):
     """Inverted-file index over f16 / bf16 rows resident in MI355X HBM: FAISS ``IndexIVFFlat`` with inner product
     (reference src/stage1_retriever.py:256-283, ``nlist`` lists, ``nprobe`` probed per query).
 
@@ -1856,6 +1662,7 @@ class IVFFlatIndex:
     ``nprobe`` probed lists, with scores bit-identical to :class:`FlatIPIndex` on the same rows and ties by ascending id.
     Inputs may be numpy arrays or torch tensors; host inputs are copied to the index's GPU first."""
 
+    _DESTROY = "ts_ivf_destroy"
     MAX_KERNEL_K = 16384
 
     def __init__(self, d: int, nlist: int, dtype: str = "f16", device: int = 0, nprobe: int = 10):
@@ -1877,36 +1684,13 @@ class IVFFlatIndex:
         _lib.check(self._lib.ts_ivf_create(self.d, self.nlist, _NAME_TO_DTYPE[dtype], self.device,
                                            ctypes.byref(self._h)))
 
-    def close(self) -> None:
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._lib.ts_ivf_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     # -- helpers -------------------------------------------------------------
     def _dev(self, x, what: str):
-        """x -> a contiguous [n, d] tensor on the index's GPU (f32 / f16 / bf16)."""
-        torch = _torch()
-        if not _is_tensor(x):
-            a = np.ascontiguousarray(x)
-            if a.dtype not in _NP_DTYPES:
-                a = a.astype(np.float32)
-            x = torch.from_numpy(a)
-        if x.dim() != 2 or x.shape[1] != self.d:
-            raise ValueError(f"expected [n, {self.d}] {what}, got {tuple(x.shape)}")
-        if x.dtype not in (torch.float32, torch.float16, torch.bfloat16):
-            x = x.float()
-        if not x.is_cuda or x.device.index != self.device:
-            x = x.to(torch.device("cuda", self.device))
-        return x.contiguous()
+        """The upload policy for [n, d] ``what``: (tensor on the index's GPU, dtype code, n, whether x was a CUDA tensor)."""
+        return _device_query(x, self.d, self.device, what, "n")
 
-    def _stream(self) -> ctypes.c_void_p:
-        return ctypes.c_void_p(_stream_ptr(self.device))
+    def _stream(self) -> int:
+        return _stream_ptr(self.device)
 
     # -- FAISS duck type -----------------------------------------------------
     @property
@@ -1925,12 +1709,9 @@ class IVFFlatIndex:
     def remove_ids(self, ids) -> int:
         """:meth:`FlatIPIndex.remove_ids` for the IVF index: removed rows leave their lists (holes stay until
         :meth:`compact`).  Returns how many rows were removed."""
-        if _is_tensor(ids):
-            ids = ids.detach().cpu().numpy()
-        arr = np.ascontiguousarray(np.asarray(ids, dtype=np.int64).reshape(-1))
+        arr = _id_array(ids)
         n = ctypes.c_int64(0)
-        _lib.check(self._lib.ts_remove_ivf(self._h, arr.ctypes.data_as(ctypes.c_void_p), int(arr.shape[0]),
-                                           ctypes.byref(n), self._stream()))
+        _lib.check(self._lib.ts_remove_ivf(self._h, _addr(arr), int(arr.shape[0]), ctypes.byref(n), self._stream()))
         return int(n.value)
 
     def update_rows(self, ids, x, normalize: bool = False) -> None:
@@ -1938,14 +1719,11 @@ class IVFFlatIndex:
         :meth:`add` assigns a new row and joins the end of its new list under its old id (the hole stays, as after a
         removal, until :meth:`compact`).  All or nothing: an id out of range, given twice or removed raises
         ``ValueError``."""
-        if _is_tensor(ids):
-            ids = ids.detach().cpu().numpy()
-        arr = np.ascontiguousarray(np.asarray(ids, dtype=np.int64).reshape(-1))
-        x = self._dev(x, "rows")
-        if x.shape[0] != arr.shape[0]:
-            raise ValueError(f"expected [{arr.shape[0]}, {self.d}] rows, got {tuple(x.shape)}")
-        flags = _lib.TS_FLAG_NORMALIZE if normalize else 0
-        _update_call(self._lib.ts_update_ivf, self._h, arr, ctypes.c_void_p(x.data_ptr()), _tensor_dtype(x), flags,
+        arr = _id_array(ids)
+        x, x_dtype, n, _ = self._dev(x, "rows")
+        if n != arr.shape[0]:
+            _bad_shape(arr.shape[0], self.d, "rows", x.shape)
+        _update_call(self._lib.ts_update_ivf, self._h, arr, x, x_dtype, _lib.TS_FLAG_NORMALIZE if normalize else 0,
                      self._stream())
 
     def compact(self) -> np.ndarray:
@@ -1956,26 +1734,25 @@ class IVFFlatIndex:
         removed), monotone, so ties keep their order."""
         n = self.ntotal
         out = np.empty(max(n, 1), dtype=np.int64)
-        _lib.check(self._lib.ts_compact_ivf(self._h, out.ctypes.data_as(ctypes.c_void_p), self._stream()))
+        _lib.check(self._lib.ts_compact_ivf(self._h, _addr(out), self._stream()))
         return out[:n]
 
     def train(self, x, seed: Optional[int] = None, niter: Optional[int] = None) -> None:
-        x = self._dev(x, "training points")
-        if x.shape[0] < self.nlist:
-            raise ValueError(f"{x.shape[0]} training points for nlist={self.nlist}: need at least nlist")
+        x, x_dtype, n, _ = self._dev(x, "training points")
+        if n < self.nlist:
+            raise ValueError(f"{n} training points for nlist={self.nlist}: need at least nlist")
         it = self.niter if niter is None else int(niter)
         obj = (ctypes.c_double * max(it, 1))()
-        _lib.check(self._lib.ts_ivf_train(self._h, ctypes.c_void_p(x.data_ptr()), x.shape[0], _tensor_dtype(x),
-                                          int(self.seed if seed is None else seed), it, obj, self._stream()))
+        _lib.check(self._lib.ts_ivf_train(self._h, _addr(x), n, x_dtype, int(self.seed if seed is None else seed), it,
+                                          obj, self._stream()))
         self.objective = [float(obj[i]) for i in range(it)]
 
     def add(self, x, normalize: bool = False) -> None:
         if not self.is_trained:
             raise RuntimeError("IVFFlatIndex.add before train(): the index has no centroids")
-        x = self._dev(x, "rows")
-        flags = _lib.TS_FLAG_NORMALIZE if normalize else 0
-        _lib.check(self._lib.ts_ivf_add(self._h, ctypes.c_void_p(x.data_ptr()), x.shape[0], _tensor_dtype(x),
-                                        flags, self._stream()))
+        x, x_dtype, n, _ = self._dev(x, "rows")
+        _lib.check(self._lib.ts_ivf_add(self._h, _addr(x), n, x_dtype, _lib.TS_FLAG_NORMALIZE if normalize else 0,
+                                        self._stream()))
 
     def reset(self) -> None:
         _lib.check(self._lib.ts_ivf_reset(self._h))
@@ -1989,38 +1766,31 @@ class IVFFlatIndex:
         """[nlist, d] float32 (host)."""
         torch = _torch()
         out = torch.empty((self.nlist, self.d), dtype=torch.float32, device=torch.device("cuda", self.device))
-        _lib.check(self._lib.ts_ivf_get_centroids(self._h, ctypes.c_void_p(out.data_ptr()), self._stream()))
+        _lib.check(self._lib.ts_ivf_get_centroids(self._h, _addr(out), self._stream()))
         return out.cpu().numpy()
 
     def set_centroids(self, c) -> None:
         """Load trained centroids [nlist, d] (no training); the index must be empty."""
-        torch = _torch()
-        c = self._dev(c, "centroids").float().contiguous()
+        c = self._dev(c, "centroids")[0].float().contiguous()
         if c.shape[0] != self.nlist:
             raise ValueError(f"expected {self.nlist} centroids, got {c.shape[0]}")
-        _lib.check(self._lib.ts_ivf_set_centroids(self._h, ctypes.c_void_p(c.data_ptr()), self._stream()))
-        torch.cuda.current_stream(self.device).synchronize()
+        _lib.check(self._lib.ts_ivf_set_centroids(self._h, _addr(c), self._stream()))
+        _torch().cuda.current_stream(self.device).synchronize()
 
     def list_sizes(self) -> np.ndarray:
         out = np.zeros(self.nlist, dtype=np.int64)
-        _lib.check(self._lib.ts_ivf_list_sizes(self._h, out.ctypes.data_as(ctypes.c_void_p)))
+        _lib.check(self._lib.ts_ivf_list_sizes(self._h, _addr(out)))
         return out
 
     def probe(self, q, nprobe: Optional[int] = None):
         """``(scores float32 [B, nprobe], lists int64 [B, nprobe])``: the lists a search probes, best first."""
-        torch = _torch()
-        was_np = not (_is_tensor(q) and q.is_cuda)
-        q = self._dev(q, "queries")
+        q, q_dtype, B, on_gpu = self._dev(q, "queries")
         p = min(self.nprobe if nprobe is None else int(nprobe), self.nlist)
         if p <= 0:
             raise ValueError("nprobe must be positive")
-        B = q.shape[0]
-        S = torch.empty((B, p), dtype=torch.float32, device=q.device)
-        L = torch.empty((B, p), dtype=torch.int64, device=q.device)
-        _lib.check(self._lib.ts_ivf_probe(self._h, ctypes.c_void_p(q.data_ptr()), B, _tensor_dtype(q), p,
-                                          ctypes.c_void_p(S.data_ptr()), ctypes.c_void_p(L.data_ptr()),
-                                          self._stream()))
-        return (S.cpu().numpy(), L.cpu().numpy()) if was_np else (S, L)
+        S, L = _outputs(None, B, p, q)
+        _lib.check(self._lib.ts_ivf_probe(self._h, _addr(q), B, q_dtype, p, _addr(S), _addr(L), self._stream()))
+        return (S, L) if on_gpu else (S.cpu().numpy(), L.cpu().numpy())
 
     def search(self, q, k: int, async_: bool = False, out=None, allowed=None, nprobe: Optional[int] = None):
         """Top-``k`` over the rows of each query's probed lists (FAISS convention, -1 / -FLT_MAX padded).  numpy in
@@ -2036,28 +1806,15 @@ class IVFFlatIndex:
         if not self.is_trained:
             raise RuntimeError("IVFFlatIndex.search before train()")
         if self.ntotal == 0:
-            raise ValueError("No documents indexed. Call add_documents() first.")
-        torch = _torch()
-        was_np = not (_is_tensor(q) and q.is_cuda)
-        q = self._dev(q, "queries")
-        B = q.shape[0]
-        if out is not None:
-            D, I = out
-            if (D.shape != (B, k) or I.shape != (B, k) or D.dtype != torch.float32 or I.dtype != torch.int64
-                    or not D.is_contiguous() or not I.is_contiguous()):
-                raise ValueError("out must be contiguous (float32[B,k], int64[B,k]) CUDA tensors")
-        else:
-            D = torch.empty((B, k), dtype=torch.float32, device=q.device)
-            I = torch.empty((B, k), dtype=torch.int64, device=q.device)
+            _raise_empty()
+        q, q_dtype, B, on_gpu = self._dev(q, "queries")
+        D, I = _outputs(out, B, k, q)
         p = self.nprobe if nprobe is None else int(nprobe)
         if p <= 0:
             raise ValueError("nprobe must be positive")
-        _lib.check(self._lib.ts_ivf_search(self._h, ctypes.c_void_p(q.data_ptr()), B, _tensor_dtype(q), k,
-                                           min(p, self.nlist), ctypes.c_void_p(D.data_ptr()),
-                                           ctypes.c_void_p(I.data_ptr()), self._stream()))
-        if was_np:
-            return D.cpu().numpy(), I.cpu().numpy()
-        return D, I
+        _lib.check(self._lib.ts_ivf_search(self._h, _addr(q), B, q_dtype, k, min(p, self.nlist), _addr(D), _addr(I),
+                                           self._stream()))
+        return (D, I) if on_gpu else (D.cpu().numpy(), I.cpu().numpy())
 
     def mmr(self, ids, relevance, k: int, lambda_mult: float = 0.5):
         """:meth:`FlatIPIndex.mmr` over the rows of this index (ids go through the id-to-slot table on the device)."""
@@ -2066,9 +1823,7 @@ class IVFFlatIndex:
     def search_mmr(self, q, k: int, fetch_k: Optional[int] = None, lambda_mult: float = 0.5,
                    nprobe: Optional[int] = None):
         """``search(q, fetch_k, nprobe=nprobe)`` followed by :meth:`mmr` on the same stream."""
-        k, fetch_k, lam = mmr_check(k, mmr_default_fetch_k(k) if fetch_k is None else fetch_k, lambda_mult)
-        D, I = self.search(q, fetch_k, nprobe=nprobe)
-        return self.mmr(I, D, k, lam)
+        return self._search_mmr(q, k, fetch_k, lambda_mult, nprobe=nprobe)
 
     def search_prefix(self, q, k: int, dims: int, allowed=None):
         raise NotImplementedError("funnel search is not supported on an IVF index (its lists hold whole rows; use a flat index)")
@@ -2083,11 +1838,7 @@ class IVFFlatIndex:
                        nprobe: Optional[int] = None):
         """:meth:`FlatIPIndex.search_grouped` over ``search(q, fetch, nprobe=nprobe)``: the rows a query can reach are
         those of its probed lists, and a list is exhaustive when it holds all of them."""
-        return grouped_search(self, lambda x, f: self.search(x, f, nprobe=nprobe), q, k, groups, group_size, fetch_k)
-
-    def last_group_info(self) -> dict:
-        """``{"fetched", "rounds", "n_groups", "complete"}`` of the last :meth:`search_grouped`."""
-        return dict(getattr(self, "_group_info", {}))
+        return self._search_grouped(q, k, groups, group_size, fetch_k, nprobe=nprobe)
 
     def finish(self):
         """Asynchronous searches complete synchronously here: nothing is pending, no ticket failed."""
@@ -2103,8 +1854,7 @@ class IVFFlatIndex:
             n = self.ntotal - i0
         out = torch.empty((max(n, 0), self.d), dtype=torch.float32, device=torch.device("cuda", self.device))
         if n:
-            _lib.check(self._lib.ts_ivf_reconstruct(self._h, int(i0), int(n), ctypes.c_void_p(out.data_ptr()),
-                                                    self._stream()))
+            _lib.check(self._lib.ts_ivf_reconstruct(self._h, int(i0), int(n), _addr(out), self._stream()))
         return out.cpu().numpy()
 
     def last_search_info(self) -> dict:
