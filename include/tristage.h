@@ -64,7 +64,8 @@ extern "C" {
  * (TS_FLAG_COALESCE, ts_index_flush, ts_coalesce_groups) were added within version 4: no signature changed, and a
  * caller that never sets the flag sees the library it was built against.  The IVF-Flat entry points (ts_ivf_*) were
  * added within version 4 as well: no existing signature changed.  So were wide coalesced passes
- * (TS_FLAG_WIDE_PASSES, TS_FLAG_NO_WIDE_PASSES, ts_coalesce_groups_wide, ts_coalesce_wide_min_bytes), and removal
+ * (TS_FLAG_WIDE_PASSES, TS_FLAG_NO_WIDE_PASSES, ts_coalesce_groups_wide, ts_coalesce_wide_min_bytes), query-stationary
+ * passes (TS_FLAG_STATIONARY_PASSES, TS_FLAG_NO_STATIONARY_PASSES, ts_coalesce_groups_stationary), and removal
  * (ts_index_remove, ts_index_live_count, ts_index_live_words, ts_index_compact): no existing signature changed, and
  * an index from which nothing is removed behaves as before; so was ts_remove_ivf.  So were ts_index_update and
  * ts_update_ivf: an index that is never updated runs the code it ran before.  So was ts_compact_ivf: no existing
@@ -124,6 +125,10 @@ enum ts_metric { TS_METRIC_INNER_PRODUCT = 0 };
 #define TS_FLAG_WIDE_PASSES 256u     /* with TS_FLAG_COALESCE: wide passes (ts_coalesce_groups_wide() groups)
                                         whatever the corpus size; results are identical              */
 #define TS_FLAG_NO_WIDE_PASSES 512u  /* with TS_FLAG_COALESCE: never wide passes (ts_coalesce_groups())  */
+#define TS_FLAG_STATIONARY_PASSES 1024u     /* with TS_FLAG_COALESCE: query-stationary passes
+                                               (ts_coalesce_groups_stationary() groups) wherever their kernel
+                                               exists, whatever the corpus size; results are identical        */
+#define TS_FLAG_NO_STATIONARY_PASSES 2048u  /* with TS_FLAG_COALESCE: never query-stationary passes          */
 #define TS_FLAG_NORMALIZE 4u    /* add: L2-normalise rows x/(|x|+1e-8) on device first
                                    (reference src/stage1_retriever.py:285-288) */
 
@@ -285,6 +290,14 @@ int32_t ts_coalesce_groups(int32_t dim, int32_t storage_dtype);
  * of one width: a search that asks for the other flushes it first.  Added within version 4.  Need no GPU.     */
 int32_t ts_coalesce_groups_wide(int32_t dim, int32_t storage_dtype);
 int64_t ts_coalesce_wide_min_bytes(void);
+/* Query-stationary passes: each of a workgroup's eight waves keeps one group's query image in registers and the
+ * corpus goes through LDS once per compute unit, so a pass takes ts_coalesce_groups_stationary() groups: 8 for
+ * f16 / bf16 storage at a padded dimension of 640 or 768 (512 < dim <= 768), 0 otherwise (the image of a larger
+ * dimension does not fit the registers; at a smaller one the LDS-resident passes read at the ceiling already).  The
+ * queue uses them where it would use wide passes by its own policy (neither wide-pass flag set) and nothing has been
+ * removed from the index, unless TS_FLAG_STATIONARY_PASSES / TS_FLAG_NO_STATIONARY_PASSES decide; a forced
+ * TS_FLAG_WIDE_PASSES / TS_FLAG_NO_WIDE_PASSES keeps the widths it had.  Added within version 4.  Needs no GPU.  */
+int32_t ts_coalesce_groups_stationary(int32_t dim, int32_t storage_dtype);
 
 /* ---- removal (tombstones) ------------------------------------------------
  * FAISS remove_ids with stable ids: a removed row keeps its id, is never returned by a search, and keeps its

@@ -34,6 +34,7 @@ def header_abi_version() -> int:
 TS_FLAG_HOST_PTR, TS_FLAG_NO_FILTER, TS_FLAG_NORMALIZE, TS_FLAG_ASYNC, TS_FLAG_PIPELINE, TS_FLAG_CLASSIC, TS_FLAG_ONE_LAUNCH = 1, 2, 4, 8, 16, 32, 64
 TS_FLAG_COALESCE = 128
 TS_FLAG_WIDE_PASSES, TS_FLAG_NO_WIDE_PASSES = 256, 512
+TS_FLAG_STATIONARY_PASSES, TS_FLAG_NO_STATIONARY_PASSES = 1024, 2048
 
 # name -> (restype, argtypes); mirrors include/tristage.h one to one
 SIGNATURES = {
@@ -70,6 +71,7 @@ SIGNATURES = {
     "ts_index_flush": (c_int32, [c_void_p, c_void_p]),
     "ts_coalesce_groups": (c_int32, [c_int32, c_int32]),
     "ts_coalesce_groups_wide": (c_int32, [c_int32, c_int32]),
+    "ts_coalesce_groups_stationary": (c_int32, [c_int32, c_int32]),
     "ts_coalesce_wide_min_bytes": (c_int64, []),
     "ts_index_set_profiling": (c_int32, [c_void_p, c_int32]),
     "ts_index_get_timings": (c_int32, [c_void_p, POINTER(ctypes.c_double), POINTER(c_int64), c_int32]),

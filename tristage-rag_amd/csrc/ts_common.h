@@ -219,6 +219,19 @@ uint32_t ts_scan_wide_stage_cap(const TsLayout& L, int G);
 bool ts_scan_wide_fits(int64_t nblk, int num_cus);
 int ts_launch_scan_wide(const TsLayout& L, int G, const WideScanParams& p, int num_cus, hipStream_t stream);
 
+// Query-stationary coalesced passes (scan_qstat_kernel, ts_scan_qstat.hip): the groups of WideScanParams, up to 8, one
+// per wave, each wave holding its group's image in registers while the corpus goes through an LDS ring shared by the
+// workgroup.  Padded dimensions 640 and 768, f16 / bf16 storage; no tombstone form.
+// groups per stationary pass (0: no kernel for the layout); host-only arithmetic
+int ts_scan_qstat_groups(const TsLayout& L);
+// staging entries the kernel gets (what the ring leaves of the LDS; 0: no kernel for the layout)
+uint32_t ts_scan_qstat_stage_cap(const TsLayout& L);
+// false where the survivor keys could not encode a workgroup's step count
+bool ts_scan_qstat_fits(int64_t nblk, int num_cus);
+// the kernel's LDS attribute on the current device, ahead of the first launch
+int ts_scan_qstat_prepare(const TsLayout& L);
+int ts_launch_scan_qstat(const TsLayout& L, int G, const WideScanParams& p, int num_cus, hipStream_t stream);
+
 // Tombstone passes: the coalesced passes of an index with removed rows.  live: its live words (bit
 // r % 32 of word r / 32 = row r live); each wave reads its block's word as a scalar load and its survivor epilogue
 // drops the rows whose bit is clear.  Derived structs, so that the existing instantiations keep their arguments.

@@ -102,6 +102,9 @@ constexpr int64_t kCoalesceOversample = 3;
 // ceiling too
 constexpr int64_t kWideMinCorpusBytes = 256ll << 20;
 constexpr int kWideMaxResidentGroups = 3;
+// query-stationary passes (scan_qstat_kernel) wherever the policy above picks a wide pass and their kernel exists
+// (DESIGN.md 4.2c has the measurement that decides this)
+constexpr bool kStationaryByDefault = true;
 
 }  // namespace
 
@@ -172,7 +175,9 @@ struct ts_index {
   std::mutex co_mu;
   int co_gmax = 0;                       // groups per LDS-resident pass (ts_coalesce_groups)
   int co_gwide = 0;                      // groups per wide pass (ts_coalesce_groups_wide)
+  int co_gstat = 0;                      // groups per query-stationary pass (ts_coalesce_groups_stationary)
   int co_width = 0;                      // groups per pass of the queue's pending groups (co_pass_width)
+  bool co_stat_forced = false;           // the queue's last search set TS_FLAG_STATIONARY_PASSES (co_launch_pass)
   hipStream_t co_stream = nullptr;       // the stream of the held batches
   CoBatch co_batch[TS_MAX_WIDE_GROUPS] = {};  // held batches in submission order
   int co_nbatch = 0;
@@ -311,10 +316,12 @@ extern "C" int ts_index_create(int32_t dim, int32_t storage_dtype, int32_t metri
   h->L = L;
   h->co_gmax = ts_coalesce_groups(dim, storage_dtype);
   h->co_gwide = ts_coalesce_groups_wide(dim, storage_dtype);
+  h->co_gstat = ts_coalesce_groups_stationary(dim, storage_dtype);
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
     h->num_cus = prop.multiProcessorCount;
-  int st = TS_OK;
+  // (the stationary pass's LDS attribute now: no first-launch cost inside a caller's timed pass)
+  int st = ts_scan_qstat_prepare(L);
   for (ts_index::WSet& w : h->ws) {
     if (st == TS_OK) st = ensure(w.small, 4096);
     if (st == TS_OK && hipMemset(w.small.p, 0, 4096) != hipSuccess) { ts_set_error("hipMemset failed"); st = TS_ERR_HIP; }
@@ -1158,12 +1165,21 @@ extern "C" int32_t ts_coalesce_groups_wide(int32_t dim, int32_t storage_dtype) {
 
 extern "C" int64_t ts_coalesce_wide_min_bytes() { return kWideMinCorpusBytes; }
 
+extern "C" int32_t ts_coalesce_groups_stationary(int32_t dim, int32_t storage_dtype) {
+  if (dim <= 0 || (storage_dtype != TS_F16 && storage_dtype != TS_BF16)) return 0;
+  return ts_scan_qstat_groups(ts_make_layout(dim, storage_dtype));
+}
+
 // Groups per pass of an unfiltered pass of a search with these flags, or 0 where it does not join the pending-pass
 // queue: asynchronous, not pipelined, on the five-launch filter path (the one-launch kernel has no multi-group form),
 // and at least three groups per pass (at two, one pass per 64-query batch is what the plain scan already does).
 // Wide passes where the corpus (padded rows x padded dimension) is larger than kWideMinCorpusBytes and the resident
 // passes take at most kWideMaxResidentGroups groups, or where TS_FLAG_WIDE_PASSES asks for them;
 // TS_FLAG_NO_WIDE_PASSES keeps the LDS-resident ones.
+// Query-stationary passes (scan_qstat_kernel, 8 groups) where their kernel exists for the layout, nothing is removed
+// (there is no tombstone form) and either TS_FLAG_STATIONARY_PASSES asks for them or the policy above, left to itself
+// (neither wide-pass flag), picks a wide pass; TS_FLAG_NO_STATIONARY_PASSES, and a forced wide-pass flag without
+// TS_FLAG_STATIONARY_PASSES, keep the widths above.
 static int co_pass_width(const ts_index* h, int k, uint32_t flags) {
   const int64_t N = h->ntotal;
   const int64_t nblk = (N + TS_ROWS_PER_BLOCK - 1) / TS_ROWS_PER_BLOCK;
@@ -1175,6 +1191,11 @@ static int co_pass_width(const ts_index* h, int k, uint32_t flags) {
   const int grid = h->num_cus - h->num_cus / 8;
   bool wide = (int64_t)nblk * (int64_t)ts_block_bytes(h->L) > kWideMinCorpusBytes &&
               h->co_gmax <= kWideMaxResidentGroups;
+  if (h->co_gstat > 0 && h->nremoved == 0 && !(flags & TS_FLAG_NO_STATIONARY_PASSES) &&
+      ts_scan_qstat_fits(nblk, h->num_cus)) {
+    const bool auto_wide = wide && !(flags & (TS_FLAG_WIDE_PASSES | TS_FLAG_NO_WIDE_PASSES));
+    if ((flags & TS_FLAG_STATIONARY_PASSES) || (kStationaryByDefault && auto_wide)) return h->co_gstat;
+  }
   if (flags & TS_FLAG_WIDE_PASSES) wide = true;
   if (flags & TS_FLAG_NO_WIDE_PASSES) wide = false;
   if (wide && h->co_gwide >= 3 && ts_scan_wide_fits(nblk, h->num_cus)) return h->co_gwide;   // (co_launch_pass: every CU)
@@ -1207,7 +1228,8 @@ static void co_fill_params(const ts_index* h, int G, P& mp) {
 }
 
 // One filter scan over the pending groups; then the select of every batch whose last group was in it.  Groups whose
-// images all fit the LDS take scan_multi_kernel, more take scan_wide_kernel.  Caller holds co_mu.
+// images all fit the LDS take scan_multi_kernel, more take scan_wide_kernel, or scan_qstat_kernel in a queue of
+// query-stationary passes.  Caller holds co_mu.
 static int co_launch_pass(ts_index* h) {
   if (h->co_ngroup == 0) return TS_OK;
   const int G = h->co_ngroup;
@@ -1225,7 +1247,23 @@ static int co_launch_pass(ts_index* h) {
   int st;
   // removed rows: the tombstone instantiations (the queue is flushed whenever removals change)
   const bool tomb = h->nremoved > 0;
-  if (G <= h->co_gmax) {
+  // A queue of query-stationary passes (co_pass_width): its full passes and the partial ones of 7 groups take
+  // scan_qstat_kernel.  A partial pass that a wide pass can take goes there (6 groups: 3.08 ms against 3.53 ms at
+  // 10 M x 768), one the LDS-resident kernel can take goes there, as in a wide queue.  With
+  // TS_FLAG_STATIONARY_PASSES every pass above co_gmax groups is a stationary one (tests, A/B runs).
+  const int stat_above = h->co_stat_forced ? h->co_gmax : std::max(h->co_gmax, h->co_gwide);
+  if (!tomb && h->co_gstat > 0 && h->co_width == h->co_gstat && G > stat_above) {
+    // one group per wave, any G up to 8; every CU, like the wide pass
+    WideScanParams wp{};
+    co_fill_params(h, G, wp);
+    wp.stage_cap = ts_scan_qstat_stage_cap(h->L);
+    int stat_cus = h->num_cus;
+#ifdef TS_TUNING   // A/B only: how many CUs the stationary pass may occupy
+    static const int dbg_stat_cus = getenv("TS_QSTAT_CUS") ? atoi(getenv("TS_QSTAT_CUS")) : 0;
+    if (dbg_stat_cus > 0) stat_cus = dbg_stat_cus;
+#endif
+    st = ts_launch_scan_qstat(h->L, G, wp, stat_cus, s);
+  } else if (G <= h->co_gmax) {
     MultiTombParams mp{};
     co_fill_params(h, G, mp);
     mp.stage_cap = ts_scan_multi_stage_cap(h->L, G);
@@ -1470,6 +1508,7 @@ extern "C" int ts_index_search(ts_index* h, const void* queries, int32_t nq, int
     if (h->co_ngroup > 0 && h->co_width != width) TS_CHECK(co_flush_locked(h, s));
     h->co_stream = s;
     h->co_width = width;
+    h->co_stat_forced = (flags & TS_FLAG_STATIONARY_PASSES) != 0;
     for (int q0 = 0; q0 < nq; q0 += qp) {
       const int c = std::min(qp, nq - q0);
       TS_CHECK(co_submit(h, (const char*)queries + (size_t)q0 * qrow, c, q_dtype, k, out_scores + (size_t)q0 * k,

@@ -1,0 +1,326 @@
+// Query-stationary coalesced passes (scan_qstat_kernel<DT, NWIN>): the wide pass turned round.
+//
+// scan_wide_kernel keeps the corpus in registers and re-gathers a window of every group's query image from L2 into LDS
+// for every window of every row block: 48 KiB of image beside 64 KiB of corpus per window at G = 6.  Here the queries
+// stay put and the corpus moves through LDS:
+//   * one 8-wave workgroup per CU; wave g owns group g of the pass (G <= 8, a run-time argument) and holds the group's
+//     whole image in registers, u32x4 q[kg] (192 VGPRs at padded d = 768): loaded once, in the prologue;
+//   * the corpus goes from HBM into a ring of 8 KiB windows in LDS by LDS-DMA, each byte once per CU, shared by the
+//     eight waves; wave w requests k group w of every window (one 1 KiB piece).  The tiled corpus is in A-fragment
+//     order, so a piece lands lane-linear and a ds_read_b128 at lane * 16 is the operand stream_load delivers;
+//   * per 32-row block a wave runs kg MFMAs (A from LDS, a few slots ahead; B = q[i]; one accumulator, the first MFMA on
+//     a literal zero), the ballot epilogue of epilogue_multi for its one group, and meets the others at ONE barrier.
+// The MFMA chain of a score is scan_kernel's (A the corpus, B the query, k groups in order, zeroed start), so its bits do
+// not depend on which kernel scored it.
+//
+// Ring and counted waits.  The ring is `depth` windows, counted across row blocks (workgroup b walks row blocks
+// b, b + grid, ...; window W of its walk is k window W % NWIN of its row block W / NWIN and lives in slot W % depth).
+// The prologue requests windows 0 .. depth-1 and drains them.  Step s then
+//     computes block s out of its NWIN slots,
+//     waits vmcnt(depth - 2 * NWIN): requests are retired in order, a wave has issued windows 0 .. depth + s*NWIN - 1, so
+//       at most that many outstanding means windows .. (s + 2) * NWIN - 1, block s + 1's, have landed (its own pieces),
+//     meets the others (lgkmcnt(0) + s_barrier: the DMA stays in flight; every wave's reads of block s are retired),
+//     requests windows depth + s*NWIN .. + NWIN - 1 into the slots block s freed.
+// So a window is read one barrier after the wait that retired it, and restaged one barrier after its last read was
+// waited for; depth - NWIN windows are in flight while a block computes.  Past the end of the walk the requests read the
+// first 8 KiB of group 0's image instead (in bounds, L2-resident, never consumed), as scan_wide_kernel's refills do, so
+// every step issues NWIN requests and the one count holds in the prologue, in walks shorter than the ring and in the tail.
+#include "ts_scan_dev.h"
+#include "ts_linear_dev.h"   // fs_barrier
+#include <algorithm>
+#include <type_traits>
+
+struct StageQstatHdr {
+  uint32_t cnt;
+  uint32_t pad[3];
+  uint32_t qcnt[TS_MAX_WIDE_GROUPS * 32];
+  uint32_t qbase[TS_MAX_WIDE_GROUPS * 32];
+  uint32_t qoff[TS_MAX_WIDE_GROUPS * 32];
+  // followed by float score[stage_cap], uint32_t key[stage_cap]
+};
+static_assert(SCAN_WAVES == 8 && TS_MAX_WIDE_GROUPS == SCAN_WAVES, "one group per wave");
+static_assert(TS_RING == SCAN_WAVES, "a window is one piece per wave");
+#define TS_QSTAT_GROUPS 8
+#define TS_QSTAT_MAX_STEPS (1 << 16)   // survivor key: (step << 16) | (row in block << 8) | query of the pass
+#define TS_QSTAT_MIN_STAGE 4096u       // entries (TS_WIDE_MIN_STAGE): about 3 k survivors per workgroup and pass of 8
+#define TS_QSTAT_WINDOW 8192u          // bytes
+#define TS_QSTAT_DEPTH 15              // windows: 120 KiB of ring, 4734 staging entries
+#define TS_QSTAT_AHEAD 4               // A operands read ahead of their MFMA (6 and 8 measured the same)
+#define TS_QSTAT_MAX_LEAD 8            // depth - 2 * NWIN, the walk's vmcnt
+
+// a[g] for a wave-uniform run-time g, without a dynamically indexed kernel argument (that would go through scratch)
+template <class T>
+__device__ __forceinline__ T qstat_pick(const T (&a)[TS_MAX_WIDE_GROUPS], int g) {
+  T r = a[0];
+#pragma unroll
+  for (int i = 1; i < TS_MAX_WIDE_GROUPS; ++i) r = (g == i) ? a[i] : r;
+  return r;
+}
+
+template <int N, int I = 0, class F>
+__device__ __forceinline__ void qstat_static_for(F&& f) {
+  if constexpr (I < N) {
+    f(std::integral_constant<int, I>{});
+    qstat_static_for<N, I + 1>(f);
+  }
+}
+
+// at most n requests outstanding (n is wave-uniform; the count is an immediate)
+__device__ __forceinline__ void qstat_wait_vm(int n) {
+  switch (n) {
+    case 0: __builtin_amdgcn_s_waitcnt(0x3F70 | 0); break;
+    case 1: __builtin_amdgcn_s_waitcnt(0x3F70 | 1); break;
+    case 2: __builtin_amdgcn_s_waitcnt(0x3F70 | 2); break;
+    case 3: __builtin_amdgcn_s_waitcnt(0x3F70 | 3); break;
+    case 4: __builtin_amdgcn_s_waitcnt(0x3F70 | 4); break;
+    case 5: __builtin_amdgcn_s_waitcnt(0x3F70 | 5); break;
+    case 6: __builtin_amdgcn_s_waitcnt(0x3F70 | 6); break;
+    case 7: __builtin_amdgcn_s_waitcnt(0x3F70 | 7); break;
+    default: __builtin_amdgcn_s_waitcnt(0x3F70 | 8); break;
+  }
+}
+
+template <int DT, int NWIN>
+__global__ __launch_bounds__(SCAN_THREADS) void scan_qstat_kernel(WideScanParams p, int G, int depth) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr int KG = NWIN * TS_RING;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const bool owner = wave < G;   // a wave without a group still requests its pieces and meets the barriers
+  const int grid = (int)gridDim.x;
+  // this workgroup's walk: row blocks blockIdx.x + s * grid, s < steps (the launcher keeps grid <= nwork)
+  const int steps = (int)((p.nwork - 1 - (int64_t)blockIdx.x) / grid) + 1;
+
+  StageQstatHdr* st = reinterpret_cast<StageQstatHdr*>(smem + (size_t)depth * TS_QSTAT_WINDOW);
+  float* sscore = reinterpret_cast<float*>(st + 1);
+  uint32_t* skey = reinterpret_cast<uint32_t*>(sscore + p.stage_cap);
+  if (tid == 0) st->cnt = 0;
+
+  // ---- the ring's requests: this wave's piece (k group `wave` of the window) of the next window of the walk
+  const unsigned char* corpus = reinterpret_cast<const unsigned char*>(p.corpus);
+  const size_t blk_bytes = (size_t)KG * 1024;
+  const uint32_t loff = (uint32_t)lane * 16;
+  const uint32_t ring_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)smem + (uint32_t)wave * 1024u;
+  const unsigned char* const dead = reinterpret_cast<const unsigned char*>(p.gimg[0]) + (size_t)wave * 1024;
+  auto blk_of = [&](int s) { return p.blk0 + ((int64_t)blockIdx.x + (int64_t)s * grid) * p.blk_stride; };
+  int fstep = 0, fkw = 0, fslot = 0;
+  const unsigned char* fsrc = corpus + (size_t)blk_of(0) * blk_bytes + (size_t)wave * 1024;
+  auto request = [&]() {
+    const unsigned char* src = fstep < steps ? fsrc : dead;
+    const uint32_t dst = ring_lds + (uint32_t)fslot * TS_QSTAT_WINDOW;
+    // s_nop 4: a VMEM instruction may read an SGPR only 5 wait states after a VALU wrote it.  s_nop 0: an LDS-DMA may
+    // read M0 one wait state after an SALU wrote it.  M0 is saved and restored: the compiler reserves it.
+    uint32_t keep;
+    // nt: the corpus is read once per pass (measured against the default policy: 3.93-3.94 against 3.97-4.01 ms)
+    __asm__ volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
+                     "global_load_lds_dwordx4 %1, %2 nt\n\ts_mov_b32 m0, %0"
+                     : "=&s"(keep) : "v"(loff), "s"(src), "s"(dst) : "memory");
+    fslot = fslot + 1 == depth ? 0 : fslot + 1;
+    if (++fkw == NWIN) {
+      fkw = 0;
+      ++fstep;
+      if (fstep < steps) fsrc = corpus + (size_t)blk_of(fstep) * blk_bytes + (size_t)wave * 1024;
+    } else {
+      fsrc += TS_QSTAT_WINDOW;
+    }
+  };
+  for (int i = 0; i < depth; ++i) request();
+
+  // ---- the wave's group: its image into registers, its thresholds.  These loads follow the ring's requests, so the
+  // compiler's own counts for them (it does not see the requests) only wait for more than it thinks.
+  const int gqh = qstat_pick(p.gqh, wave), ghalf = qstat_pick(p.ghalf, wave);
+  u32x4 q[KG];
+  float tau = __builtin_huge_valf();
+  if (owner) {
+    const u32x4* img = reinterpret_cast<const u32x4*>(qstat_pick(p.gimg, wave)) + (size_t)ghalf * 64 + lane;
+#pragma unroll
+    for (int i = 0; i < KG; ++i) q[i] = img[(size_t)i * gqh * 64];
+    tau = qstat_pick(p.gtau, wave)[lane & 31];
+  } else {
+#pragma unroll
+    for (int i = 0; i < KG; ++i) q[i] = u32x4{0u, 0u, 0u, 0u};
+  }
+  // (loaded here, not sunk into the walk, where a compiler-counted load would wait for the ring's requests too)
+#pragma unroll
+  for (int i = 0; i < KG; ++i) __asm__ volatile("" : "+v"(q[i]));
+  __asm__ volatile("" : "+v"(tau));
+  __builtin_amdgcn_s_waitcnt(0x3F70);   // vmcnt(0): the first depth windows have landed (this wave's pieces)
+  fs_barrier();
+
+  const int lead = depth - 2 * NWIN;
+  int slot0 = 0;         // ring slot of the block's first window
+
+  // epilogue_multi's ballot epilogue for one group, block `sb` of the walk: the group's maximum against tau, then one
+  // ballot per accumulator register, the staging code under the execution mask of the lanes that hit
+  auto survivors = [&](const f32x16& acc, int sb) {
+    if (__builtin_amdgcn_ballot_w64(acc_max(acc) >= tau) == 0ull) return;   // the common case
+    const int64_t row_base = blk_of(sb) * TS_ROWS_PER_BLOCK;
+    const bool partial = row_base + TS_ROWS_PER_BLOCK > p.ntotal;   // the corpus's last row block, wave-uniform
+    const int rows_left = (int)(p.ntotal - row_base);
+    const uint32_t keyhi = (uint32_t)sb << 16;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const bool ok = acc[r] >= tau;
+      if (__builtin_expect(__builtin_amdgcn_ballot_w64(ok) == 0ull, 1)) continue;
+      if (!ok) continue;
+      int ln = lane;
+      __asm__ volatile("" : "+v"(ln));
+      const int row = acc_row(r, ln), j = ln & 31;
+      if (!partial || row < rows_left) {
+        const uint32_t slot = atomicAdd(&st->cnt, 1u);  // LDS
+        if (slot < p.stage_cap) {
+          sscore[slot] = acc[r];
+          skey[slot] = keyhi | ((uint32_t)row << 8) | (uint32_t)(wave * 32 + j);
+        } else {
+          // staging area full: append directly
+          const uint32_t g = atomicAdd(&qstat_pick(p.gcnt, wave)[j], 1u);
+          if (g < p.cand_cap) {
+            qstat_pick(p.gscore, wave)[(size_t)j * p.cand_cap + g] = acc[r];
+            qstat_pick(p.gid, wave)[(size_t)j * p.cand_cap + g] = (int32_t)(row_base + row);
+          }
+        }
+      }
+    }
+  };
+
+  for (int s = 0; s < steps; ++s) {
+    if (owner) {
+      // the block's windows: LDS byte offsets of this lane's 16 bytes of each window's k group 0
+      uint32_t woff[NWIN];
+#pragma unroll
+      for (int kw = 0; kw < NWIN; ++kw) {
+        int sl = slot0 + kw;
+        sl = sl >= depth ? sl - depth : sl;
+        woff[kw] = (uint32_t)sl * TS_QSTAT_WINDOW + loff;
+      }
+      auto a_read = [&](auto i) {
+        constexpr int I = decltype(i)::value;
+        return *reinterpret_cast<const u32x4*>(smem + woff[I / TS_RING] + (I % TS_RING) * 1024);
+      };
+      u32x4 a[TS_QSTAT_AHEAD];
+      qstat_static_for<TS_QSTAT_AHEAD>([&](auto i) { a[decltype(i)::value] = a_read(i); });
+      f32x16 acc;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[r] = 0.f;   // (folds into the first MFMA's C operand: a literal 0)
+      // rolling A operands: a register set is re-read with the operand TS_QSTAT_AHEAD slots on as soon as its MFMA has
+      // issued (lgkmcnt(TS_QSTAT_AHEAD - 1) before each MFMA, counted by the compiler).  The sched_barriers pin that
+      // order: left alone the scheduler puts each read right in front of its MFMA.
+      __builtin_amdgcn_sched_barrier(0);
+      qstat_static_for<KG>([&](auto i) {
+        constexpr int I = decltype(i)::value;
+        mma_group<DT>(acc, a[I % TS_QSTAT_AHEAD], q[I]);
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (I + TS_QSTAT_AHEAD < KG) {
+          a[I % TS_QSTAT_AHEAD] = a_read(std::integral_constant<int, I + TS_QSTAT_AHEAD>{});
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      });
+      survivors(acc, s);
+    }
+    // this wave's pieces of block s + 1 have landed; every wave is done reading block s
+    qstat_wait_vm(lead);
+    fs_barrier();
+    // refill the windows block s freed
+#pragma unroll
+    for (int kw = 0; kw < NWIN; ++kw) request();
+    slot0 += NWIN;
+    slot0 = slot0 >= depth ? slot0 - depth : slot0;
+  }
+  // the tail's requests (never consumed) are still landing in the ring
+  __builtin_amdgcn_s_waitcnt(0x3F70);   // vmcnt(0)
+
+  // ---- flush (scan_wide_kernel's): one global atomic per (workgroup, query) reserves the slots
+  __syncthreads();
+  const uint32_t n = st->cnt < p.stage_cap ? st->cnt : p.stage_cap;
+  if (n == 0) return;  // uniform: cnt is final after the barrier
+  for (int t = tid; t < TS_QSTAT_GROUPS * 32; t += SCAN_THREADS) { st->qcnt[t] = 0; st->qoff[t] = 0; }
+  __syncthreads();
+  for (uint32_t e = tid; e < n; e += SCAN_THREADS) atomicAdd(&st->qcnt[skey[e] & 255u], 1u);
+  __syncthreads();
+  for (int t = tid; t < TS_QSTAT_GROUPS * 32; t += SCAN_THREADS)
+    if (st->qcnt[t] > 0) st->qbase[t] = atomicAdd(qstat_pick(p.gcnt, t >> 5) + (t & 31), st->qcnt[t]);
+  __syncthreads();
+  for (uint32_t e = tid; e < n; e += SCAN_THREADS) {
+    const uint32_t key = skey[e];
+    const uint32_t qi = key & 255u;
+    const uint32_t slot = st->qbase[qi] + atomicAdd(&st->qoff[qi], 1u);
+    if (slot < p.cand_cap) {
+      const int g = (int)(qi >> 5);
+      const size_t at = (size_t)(qi & 31u) * p.cand_cap + slot;
+      const int64_t wi = (int64_t)blockIdx.x + (int64_t)(key >> 16) * grid;
+      qstat_pick(p.gscore, g)[at] = sscore[e];
+      qstat_pick(p.gid, g)[at] = (int32_t)((p.blk0 + wi * p.blk_stride) * TS_ROWS_PER_BLOCK + ((key >> 8) & 31u));
+    }
+  }
+}
+
+// ---- host
+static int qstat_nwin(const TsLayout& L) {
+  if (L.dtype != TS_F16 && L.dtype != TS_BF16) return 0;
+  const int nwin = L.kg / TS_RING;
+  return (L.kg % TS_RING == 0 && (nwin == 5 || nwin == 6)) ? nwin : 0;   // padded d = 640 and 768
+}
+
+// windows of the ring
+static int qstat_depth(const TsLayout& L) {
+  const int depth = TS_QSTAT_DEPTH;
+  const int nwin = qstat_nwin(L);
+  return std::max(2 * nwin, std::min(depth, 2 * nwin + TS_QSTAT_MAX_LEAD));
+}
+
+int ts_scan_qstat_groups(const TsLayout& L) {
+  return qstat_nwin(L) > 0 && ts_scan_qstat_stage_cap(L) > 0 ? TS_QSTAT_GROUPS : 0;
+}
+
+uint32_t ts_scan_qstat_stage_cap(const TsLayout& L) {
+  if (qstat_nwin(L) == 0) return 0;
+  const size_t fixed = (size_t)qstat_depth(L) * TS_QSTAT_WINDOW + sizeof(StageQstatHdr);
+  if (fixed + 8 * (size_t)TS_QSTAT_MIN_STAGE > 160 * 1024) return 0;
+  return (uint32_t)((160 * 1024 - fixed) / 8);
+}
+
+bool ts_scan_qstat_fits(int64_t nblk, int num_cus) {
+  const int64_t grid = std::max<int64_t>(1, std::min<int64_t>(nblk, num_cus));
+  return (nblk + grid - 1) / grid <= TS_QSTAT_MAX_STEPS;
+}
+
+template <int DT, int NWIN>
+static int qstat_kernel_t(const WideScanParams* p, int G, int depth, size_t lds, int grid, hipStream_t stream) {
+  void (*kern)(WideScanParams, int, int) = scan_qstat_kernel<DT, NWIN>;
+  static TsDeviceOnce lds_attr;
+  TS_CHECK(ts_allow_max_lds(lds_attr, reinterpret_cast<const void*>(kern)));
+  if (!p) return TS_OK;   // ts_scan_qstat_prepare
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(SCAN_THREADS), lds, stream, *p, G, depth);
+  TS_HIP(hipGetLastError());
+  return TS_OK;
+}
+
+static int qstat_dispatch(const TsLayout& L, const WideScanParams* p, int G, int depth, size_t lds, int grid,
+                          hipStream_t stream) {
+  const int nwin = qstat_nwin(L);
+  if (L.dtype == TS_F16 && nwin == 5) return qstat_kernel_t<TS_F16, 5>(p, G, depth, lds, grid, stream);
+  if (L.dtype == TS_F16 && nwin == 6) return qstat_kernel_t<TS_F16, 6>(p, G, depth, lds, grid, stream);
+  if (L.dtype == TS_BF16 && nwin == 5) return qstat_kernel_t<TS_BF16, 5>(p, G, depth, lds, grid, stream);
+  if (L.dtype == TS_BF16 && nwin == 6) return qstat_kernel_t<TS_BF16, 6>(p, G, depth, lds, grid, stream);
+  ts_set_error("stationary scan: no kernel for dtype %d at dimension %d", L.dtype, L.dim);
+  return TS_ERR_UNSUPPORTED;
+}
+
+int ts_scan_qstat_prepare(const TsLayout& L) {
+  if (ts_scan_qstat_groups(L) == 0) return TS_OK;
+  return qstat_dispatch(L, nullptr, 0, 0, 0, 0, nullptr);
+}
+
+int ts_launch_scan_qstat(const TsLayout& L, int G, const WideScanParams& p, int num_cus, hipStream_t stream) {
+  if (p.nwork <= 0) return TS_OK;
+  if (G < 1 || G > TS_QSTAT_GROUPS || ts_scan_qstat_groups(L) == 0 || p.kg != L.kg || p.stage_cap == 0 ||
+      p.stage_cap > ts_scan_qstat_stage_cap(L) || !ts_scan_qstat_fits(p.nwork, num_cus)) {
+    ts_set_error("stationary scan: %d groups do not fit at dimension %d", G, L.dim);
+    return TS_ERR_UNSUPPORTED;
+  }
+  const int depth = qstat_depth(L);
+  const size_t lds = (size_t)depth * TS_QSTAT_WINDOW + sizeof(StageQstatHdr) + 8 * (size_t)p.stage_cap;
+  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(p.nwork, num_cus));
+  return qstat_dispatch(L, &p, G, depth, lds, grid, stream);
+}

@@ -91,6 +91,17 @@ def wide_pass_flags(wide_passes) -> int:
     raise ValueError(f"wide_passes must be 'auto', True or False, not {wide_passes!r}")
 
 
+def stationary_pass_flags(stationary_passes) -> int:
+    """Search flags of FlatIPIndex.stationary_passes: "auto" (the library's policy), True / False (forced on / off)."""
+    if stationary_passes is True:
+        return _lib.TS_FLAG_STATIONARY_PASSES
+    if stationary_passes is False:
+        return _lib.TS_FLAG_NO_STATIONARY_PASSES
+    if isinstance(stationary_passes, str) and stationary_passes == "auto":
+        return 0
+    raise ValueError(f"stationary_passes must be 'auto', True or False, not {stationary_passes!r}")
+
+
 def _addr(x) -> Optional[int]:
     """The address of a numpy array or a tensor; None (a NULL pointer) for None.  Every ``c_void_p`` parameter of
     ``_lib.SIGNATURES`` takes it as it is.  Call it in the statement of the library call that consumes the address, so
@@ -527,6 +538,9 @@ class FlatIPIndex(_IndexBase):
         # coalesced passes of ts_coalesce_groups_wide() groups: "auto" where the corpus is larger than the Infinity
         # Cache (ts_coalesce_wide_min_bytes()), True / False to force them on / off (tests, A/B runs)
         self.wide_passes = "auto"
+        # coalesced passes of ts_coalesce_groups_stationary() groups (8 at 512 < d <= 768, f16 / bf16): "auto" wherever
+        # "auto" wide passes would run and nothing is removed, True / False to force them on / off (tests, A/B runs)
+        self.stationary_passes = "auto"
         self._filter_info = None  # set by finish() when it redid a filtered search: the counters of what was submitted
 
     # -- FAISS duck type --------------------------------------------------
@@ -677,6 +691,7 @@ class FlatIPIndex(_IndexBase):
                 elif self.coalesce:
                     flags |= _lib.TS_FLAG_COALESCE
                     flags |= wide_pass_flags(self.wide_passes)
+                    flags |= stationary_pass_flags(self.stationary_passes)
             self._search_raw(q, q_dtype, k, D, I, flags, stream)
         else:   # (ts_index_search_filtered resets the counters last_filter_info() reads, and never coalesces)
             self._filter_info = None   # last_filter_info() reads the library's counters of this call again
