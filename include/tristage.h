@@ -77,7 +77,8 @@ extern "C" {
  * ts_index_mmr_set_timing / ts_index_mmr_get_timings: no existing signature or kernel changed, and a caller that
  * never calls them allocates and launches nothing new.  So was ts_group_topk, on the same terms.  So were
  * ts_maxsim_passages_indexed and ts_maxsim_passages_indexed_batch, on the same terms.  So were ts_index_search_prefix
- * and ts_index_rescore, on the same terms.                                                                           */
+ * and ts_index_rescore, on the same terms.  So were ts_index_search_biased and ts_index_last_bias_info, on the same
+ * terms.                                                                                                             */
 #define TS_ABI_VERSION 4
 
 typedef struct ts_index ts_index; /* opaque */
@@ -433,6 +434,38 @@ int ts_index_search_prefix(ts_index* h, const void* queries, int32_t nq, int32_t
                            void* hip_stream);
 int ts_index_rescore(ts_index* h, const void* queries, int32_t nq, int32_t q_dtype, const int64_t* cand_ids,
                      int32_t ncand, int32_t k, float* out_scores, int64_t* out_ids, void* hip_stream);
+/* ---- boosted search: a per-row score prior added inside the stage-1 scan ----
+ * Reference call site: none (the reference ranks stage 1 by the inner product alone).  Added within version 4: no
+ * existing signature or kernel changed, and a caller that never calls these allocates and launches nothing new.
+ * f16 / bf16 storage only (TS_ERR_UNSUPPORTED otherwise).
+ *
+ * ts_index_search_biased: ts_index_search_filtered ranked on boosted(q, r) = fl32(score(q, r) + bias[r]).  score(q, r)
+ * is exactly the float ts_index_search / ts_index_scores produce for the pair (the same query image, the same order of
+ * the MFMA k groups); the addition is one IEEE f32 addition, round to nearest even, nothing fused or reassociated.
+ * Per query the k allowed live rows with the largest boosted score, ties to the lower id, -1 / -FLT_MAX padding
+ * where fewer than k rows are eligible; out_scores are the boosted scores, out_ids carry the id offset.  The result
+ * is exact: a row with a modest score and a large bias is found, whatever its rank by score alone.  Masks as for
+ * ts_index_search_filtered, except that mask_of_query may be NULL (no query has a mask); removed rows are never
+ * returned.
+ * bias: float32, entry r belongs to local row r (no id offset); bias_rows >= ntotal entries, of which exactly the first
+ * ntotal are read, whatever ntotal % 32 is.  Device memory, 16-byte aligned, read in stream order on `hip_stream`; host
+ * memory with TS_FLAG_HOST_PTR (any alignment).  One bias serves every query of the call.  Entries must be finite:
+ * with TS_FLAG_HOST_PTR a NaN or an infinity is TS_ERR_INVALID; a device array is not checked: a row whose boosted
+ * score is NaN is never returned, and the effect of an infinite entry is undefined (it may be returned or not, and
+ * may cost the call its fast path).
+ * Synchronous: the call returns with its stream drained; held coalesced passes are flushed first.  1 <= k <= 16384;
+ * flags: TS_FLAG_HOST_PTR and TS_FLAG_NO_FILTER only.  A null pointer, bias_rows < ntotal, a bad mask argument, k out
+ * of range or any other flag is TS_ERR_INVALID, before any HIP call.  Calls on one handle are serialised; the handle
+ * keeps 128 bytes (plus a copy of the bias for host-pointer calls) from the first call on.
+ * ts_index_last_bias_info, the last ts_index_search_biased on the handle: [0] passes (of at most 64 queries), [1]
+ * passes whose first attempt was the fused path (thresholds, then the biased filter scan), [2] of those, passes redone
+ * on the exact dense path (too few or too many candidates), [3] 32-row blocks its scans read.
+ * hip_stream: the hipStream_t the call runs on, what the other entry points call `stream`.                        */
+int ts_index_search_biased(ts_index* h, const void* queries, int32_t nq, int32_t q_dtype, int32_t k, const float* bias,
+                           int64_t bias_rows, const uint32_t* allow_bits, int64_t allow_words, int32_t n_masks,
+                           const int32_t* mask_of_query, float* out_scores, int64_t* out_ids, uint32_t flags,
+                           void* hip_stream);
+int ts_index_last_bias_info(const ts_index* h, int64_t info[4]);
 /* row-shard support: ids reported by search = local row + offset            */
 int ts_index_set_id_offset(ts_index* h, int64_t offset);
 /* copy rows [row0, row0+n) back out as row-major float32 (host or device):

@@ -99,6 +99,9 @@ SIGNATURES = {
                                          c_void_p, c_void_p, c_void_p, c_uint32, c_void_p]),
     "ts_index_rescore": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p,
                                    c_void_p]),
+    "ts_index_search_biased": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_int64,
+                                         c_int32, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p]),
+    "ts_index_last_bias_info": (c_int32, [c_void_p, POINTER(c_int64)]),
     "ts_index_mmr_set_timing": (c_int32, [c_void_p, c_int32]),
     "ts_index_mmr_get_timings": (c_int32, [c_void_p, POINTER(ctypes.c_double), POINTER(c_int64), c_int32]),
     "ts_mmr_ivf": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_float, c_void_p, c_void_p,

@@ -171,6 +171,16 @@ int ts_launch_scan_prefix(const TsLayout& L, int mode, int qh, const PrefixScanP
 int ts_launch_scan_prefix_masked(const TsLayout& L, int qh, const PrefixMaskedScanParams& p, int num_cus,
                                  hipStream_t stream);
 
+// Boosted scans (ts_scan_bias.hip): the masked filter scan on score + bias[row].  bias: ntotal floats,
+// 16-byte aligned, of which the whole row blocks are read; the partial last block tail_blk (-1: ntotal is a multiple of
+// 32) reads the 32 floats of bias_tail instead.  Parameters of their own, derived.  f16 / bf16 storage.
+struct BiasScanParams : MaskedScanParams {
+  const float* bias;
+  const float* bias_tail;
+  int64_t tail_blk;
+};
+int ts_launch_scan_biased(const TsLayout& L, int qh, const BiasScanParams& p, int num_cus, hipStream_t stream);
+
 // Coalesced passes (TS_FLAG_COALESCE, scan_multi_kernel): one filter scan over every row block for G 32-query
 // groups that may come from different batches.  Group g is the query columns 32*ghalf[g] .. +32 of the Q image
 // gimg[g] (laid out with gqh[g] halves per k group), with its batch's thresholds and candidate lists at the same
@@ -277,6 +287,13 @@ int ts_launch_live_blocks(const uint32_t* bits, int64_t words, const TsMaskPass&
 int ts_launch_tau_masked(const float* sample, int64_t S, int64_t sstride, int64_t ntotal, const uint32_t* bits,
                          int64_t words, TsMaskDev* md, int nq, int k, uint32_t over, uint32_t min_rank,
                          float* tau, uint32_t* report, hipStream_t stream);
+// Boosted passes (ts_scan_bias.hip): ts_launch_tau_masked on sample score + bias[row]; and the dense path's chunk,
+// dense[q][i] += bias[row0 + i] with the ids of ts_launch_mask_ids (-1 also where the sum is NaN)
+int ts_launch_tau_biased(const float* sample, int64_t S, int64_t sstride, int64_t ntotal, const uint32_t* bits,
+                         int64_t words, const float* bias, TsMaskDev* md, int nq, int k, uint32_t over,
+                         uint32_t min_rank, float* tau, uint32_t* report, hipStream_t stream);
+int ts_launch_bias_ids(const uint32_t* bits, int64_t words, const TsMaskPass& mp, const float* bias, int nq,
+                       int64_t row0, uint32_t rows, int64_t ld, float* dense, int32_t* ids, hipStream_t stream);
 // LDS bytes the scan kernel needs for qh*32 queries (Q image + candidate staging)
 size_t ts_scan_lds_bytes(const TsLayout& L, int qh);
 // fp32 storage, 32-query passes, 512 < d <= 768: the bf16x3 split scan (ts_scan_f32s.hip) instead of the exact-f32 MFMA

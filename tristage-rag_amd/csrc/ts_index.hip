@@ -9,6 +9,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <condition_variable>
 #include <mutex>
 #include <new>
@@ -222,6 +223,12 @@ struct ts_index {
   // the first call; rescore_mu serialises the calls on the handle
   DevBuf rescore_scratch;
   std::mutex rescore_mu;
+  // boosted search (ts_index_search_biased): the staged bias of a host-pointer call followed by the
+  // 32-float padded copy of the last, partial row block's entries, allocated at the first call; bias_mu serialises
+  // the calls on the handle; binfo: ts_index_last_bias_info
+  DevBuf bias_stage;
+  std::mutex bias_mu;
+  int64_t binfo[4] = {0, 0, 0, 0};
 };
 
 static int co_flush(ts_index* h, hipStream_t s);
@@ -381,7 +388,7 @@ extern "C" int ts_index_destroy(ts_index* h) {
     if (e) (void)hipEventDestroy(e);
   if (h->co_ev) (void)hipEventDestroy(h->co_ev);
   DevBuf* rb[] = {&h->live, &h->eff, &h->rids, &h->compact_scratch, &h->compact_stage, &h->upd_tile, &h->upd_tab,
-                  &h->rng_s, &h->rng_i, &h->rng_tiles, &h->rescore_scratch};
+                  &h->rng_s, &h->rng_i, &h->rng_tiles, &h->rescore_scratch, &h->bias_stage};
   for (DevBuf* b : rb) release(*b);
   if (h->eff_ev) (void)hipEventDestroy(h->eff_ev);
   ts_mmr_release(h->mmr);
@@ -578,6 +585,9 @@ struct MaskCtx {
   const uint32_t* bits;
   int64_t words;
   TsMaskPass mp;
+  // boosted passes (ts_index_search_biased): the per-row bias and the padded copy of its last partial row block
+  const float* bias;
+  const float* bias_tail;
 };
 
 // A scan of the whole rows (pkg == 0) or of the first pkg k groups of every row (ts_index_search_prefix): the same
@@ -628,6 +638,10 @@ static int dense_path(ts_index* h, ts_index::WSet& W, int nq, int qh, int k, flo
     if (mc) {
       // filtered: the rows outside a query's mask get id -1 and with it no rank (SEL_PAIRS32 skips them),
       // so the result is padded with -1 / -FLT_MAX, never with disallowed rows
+      if (mc->bias)   // boosted: the same ids, and the chunk's scores become score + bias
+        TS_CHECK(ts_launch_bias_ids(mc->bits, mc->words, mc->mp, mc->bias, nq, row0, (uint32_t)rows, chunk_rows,
+                                    (float*)W.dense.p, (int32_t*)W.mids.p, s));
+      else
       TS_CHECK(ts_launch_mask_ids(mc->bits, mc->words, mc->mp, nq, row0, (uint32_t)rows, chunk_rows,
                                   (int32_t*)W.mids.p, s));
       p.mode = SEL_PAIRS32;
@@ -832,6 +846,15 @@ static void add_filter_info(ts_index* h, int64_t fseq, int64_t live, int64_t blo
   h->finfo[dense ? 3 : 2] += 1;
 }
 
+// ts_index_last_bias_info: one pass of a boosted call (bias_mu is held: one call at a time)
+static void add_bias_info(ts_index* h, bool fused, bool redone, int64_t blocks) {
+  std::lock_guard<std::mutex> lk(h->mu);
+  h->binfo[0] += 1;
+  h->binfo[1] += fused ? 1 : 0;
+  h->binfo[2] += redone ? 1 : 0;
+  h->binfo[3] += blocks;
+}
+
 // Filtered passes (mc != null) take the five-launch path with the live-block list and the masked scan
 // (f16 / bf16 storage), or the dense path with masked selection (fp32 storage, small corpora, large k,
 // TS_FLAG_NO_FILTER, fallback).
@@ -857,8 +880,11 @@ static int search_pass_on(ts_index* h, ts_index::WSet& W, const void* dq, int nq
   }
   // the layout of the pass's query image: the index's, or that of the prefix's dimensions
   const TsLayout QL = pkg ? ts_make_layout(16 * pkg, h->L.dtype) : h->L;
+  // (a boosted pass takes the filter path for every k <= kMaxFilterK of a corpus of kMinFilterRows rows: at the floor
+  // of both, k = 2048 of 32768 rows, the rank 3 k S / N = 1536 of 8192 sample rows still lies inside the threshold
+  // kernel's 4096 kept keys and the ~6 k expected candidates inside the 16384 slots)
   const bool filter = !(flags & TS_FLAG_NO_FILTER) && k <= kMaxFilterK && N >= kMinFilterRows &&
-                      N >= 32 * (int64_t)k && !(mc && h->L.dtype == TS_F32);
+                      (N >= 32 * (int64_t)k || (mc && mc->bias)) && !(mc && h->L.dtype == TS_F32);
   const bool async = (flags & TS_FLAG_ASYNC) != 0;
   const bool pipe = filter && async && (flags & TS_FLAG_PIPELINE) != 0;
   if (pipe) TS_CHECK(ensure_streams(h));
@@ -892,6 +918,7 @@ static int search_pass_on(ts_index* h, ts_index::WSet& W, const void* dq, int nq
   if (!filter) {
     set_info(h, 0, 0, 0, 0);
     if (mc) add_filter_info(h, fseq, nblk, nblk, true);
+    if (mc && mc->bias) add_bias_info(h, false, false, nblk);
     prof_mark(h, pc, 5, s);
     TS_CHECK(dense_path(h, W, nq, qh, k, out_s, out_i, s, mc, pkg));
     prof_mark(h, pc, -1, s);
@@ -1004,6 +1031,11 @@ static int search_pass_on(ts_index* h, ts_index::WSet& W, const void* dq, int nq
     md = (TsMaskDev*)W.mask.p;
     TS_HIP(hipMemsetAsync(md, 0, sizeof(TsMaskDev), sP));
     TS_CHECK(ts_launch_live_blocks(mc->bits, mc->words, mc->mp, nblk, N, md, sP));
+    if (mc->bias)   // boosted: the m_q-th best allowed sample score + bias
+      TS_CHECK(ts_launch_tau_biased((const float*)W.sample.p, S, sstride, N, mc->bits, mc->words, mc->bias, md, nq, k,
+                                    (uint32_t)oversample, kMinSampleRank, W.tau(),
+                                    h->host_status_dev + (size_t)slot_guard.slot * TS_SLOT_WORDS + 65, sP));
+    else
     TS_CHECK(ts_launch_tau_masked((const float*)W.sample.p, S, sstride, N, mc->bits, mc->words, md, nq, k,
                                   (uint32_t)oversample, kMinSampleRank, W.tau(),
                                   h->host_status_dev + (size_t)slot_guard.slot * TS_SLOT_WORDS + 65, sP));
@@ -1040,7 +1072,14 @@ static int search_pass_on(ts_index* h, ts_index::WSet& W, const void* dq, int nq
     mp.allow_bits = mc->bits;
     mp.allow_words = mc->words;
     mp.qmask = md->qmask;
-    if (pkg) {
+    if (mc->bias) {
+      BiasScanParams bp{};
+      static_cast<MaskedScanParams&>(bp) = mp;
+      bp.bias = mc->bias;
+      bp.bias_tail = mc->bias_tail;
+      bp.tail_blk = (N % TS_ROWS_PER_BLOCK) ? N / TS_ROWS_PER_BLOCK : -1;
+      TS_CHECK(ts_launch_scan_biased(h->L, qh, bp, scan_cus, sS));
+    } else if (pkg) {
       PrefixMaskedScanParams pp{};
       static_cast<MaskedScanParams&>(pp) = mp;
       pp.kg = pkg;
@@ -1136,6 +1175,7 @@ static int search_pass_on(ts_index* h, ts_index::WSet& W, const void* dq, int nq
   const bool redo = rep[64] != 0;
   set_info(h, (redo ? 2 : 1) | (fused ? 16 : 0), maxc, S, m);
   if (mc) add_filter_info(h, fseq, rep[65], nblk, false);
+  if (mc && mc->bias) add_bias_info(h, true, redo, (int64_t)rep[65] + (redo ? nblk : 0));
   if (redo) {
     // a threshold was too high (fewer than k survivors) or too low (candidate
     // list overflowed, e.g. massive score ties): redo this pass exactly.
@@ -1557,7 +1597,8 @@ extern "C" int ts_index_search(ts_index* h, const void* queries, int32_t nq, int
 static int search_filtered_impl(ts_index* h, const void* queries, int32_t nq, int32_t q_dtype, int32_t k,
                                 const uint32_t* allow_bits, int64_t allow_words, int32_t n_masks,
                                 const int32_t* mask_of_query, float* out_scores, int64_t* out_ids,
-                                uint32_t flags, void* stream, int pdims) {
+                                uint32_t flags, void* stream, int pdims, const float* bias = nullptr,
+                                const float* bias_tail = nullptr) {
   // the checks that need no handle come first (and none of them touches the GPU)
   if (nq < 0 || k <= 0 || !dtype_ok(q_dtype) || (nq > 0 && (!queries || !out_scores || !out_ids))) {
     ts_set_error("bad arguments to search_filtered");
@@ -1600,7 +1641,7 @@ static int search_filtered_impl(ts_index* h, const void* queries, int32_t nq, in
   }
   bool any = false;
   for (int32_t q = 0; q < nq && !any; ++q) any = mask_of_query[q] >= 0;
-  if (!any && h->nremoved == 0 && !pdims)
+  if (!any && h->nremoved == 0 && !pdims && !bias)
     return ts_index_search(h, queries, nq, q_dtype, k, out_scores, out_ids, flags, stream);
   DeviceGuard g(h->device);
   hipStream_t s = (hipStream_t)stream;
@@ -1661,7 +1702,9 @@ static int search_filtered_impl(ts_index* h, const void* queries, int32_t nq, in
     MaskCtx mc{};
     mc.bits = bits;
     mc.words = allow_words;
-    bool masked = false;
+    mc.bias = bias;
+    mc.bias_tail = bias_tail;
+    bool masked = bias != nullptr;   // a boosted pass always takes the masked path
     for (int j = 0; j < TS_MAX_Q; ++j) { mc.mp.qmask[j] = -1; mc.mp.qd[j] = -1; }
     for (int j = 0; j < c; ++j) {
       const int32_t m = mask_of_query[q0 + j];
@@ -1673,6 +1716,11 @@ static int search_filtered_impl(ts_index* h, const void* queries, int32_t nq, in
       if (d == mc.mp.nd) mc.mp.dist[mc.mp.nd++] = m;
       mc.mp.qd[j] = d;
     }
+    // A boosted pass none of whose queries has a mask still takes the masked scan, whose unmasked queries read word 0
+    // of "mask 0" and OR all ones into it (WalkLive): the pointer has to be readable on the device, whatever the caller
+    // left in allow_bits (with n_masks == 0 it is not staged and may be a host address or anything else).  The padded
+    // tail of the bias is.
+    if (bias && mc.mp.nd == 0) mc.bits = reinterpret_cast<const uint32_t*>(bias_tail);
     TS_CHECK(search_pass(h, (const char*)dq + (size_t)q0 * qrow, c, q_dtype, k, ds + (size_t)q0 * k,
                          di + (size_t)q0 * k, flags, s, masked ? &mc : nullptr, pdims / 16));
   }
@@ -1737,6 +1785,105 @@ extern "C" int ts_index_search_prefix(ts_index* h, const void* queries, int32_t 
   }
   return search_filtered_impl(h, queries, nq, q_dtype, k, allow_bits, allow_words, n_masks, mask_of_query, out_scores,
                               out_ids, flags, stream, dims);
+}
+
+// ---- boosted search (include/tristage.h "boosted search")
+// The filtered search on score + bias[row]: every pass takes the masked path (live-block list, thresholds on boosted
+// sample scores, the biased masked scan of ts_scan_bias.hip) or the dense path with the bias added to each chunk.
+extern "C" int ts_index_search_biased(ts_index* h, const void* queries, int32_t nq, int32_t q_dtype, int32_t k,
+                                      const float* bias, int64_t bias_rows, const uint32_t* allow_bits,
+                                      int64_t allow_words, int32_t n_masks, const int32_t* mask_of_query,
+                                      float* out_scores, int64_t* out_ids, uint32_t flags, void* stream) {
+  // the checks that need no handle come first; none of the checks touches the GPU
+  if (flags & ~(uint32_t)(TS_FLAG_HOST_PTR | TS_FLAG_NO_FILTER)) {
+    ts_set_error("search_biased: flags 0x%x (only TS_FLAG_HOST_PTR and TS_FLAG_NO_FILTER are accepted)", flags);
+    return TS_ERR_INVALID;
+  }
+  if (nq < 0 || k < 1 || k > kFunnelMaxK || !dtype_ok(q_dtype)) {
+    ts_set_error("search_biased: nq = %d, k = %d (k must be in 1 .. %d), query dtype %d", nq, k, kFunnelMaxK, q_dtype);
+    return TS_ERR_INVALID;
+  }
+  if (!bias || (nq > 0 && (!queries || !out_scores || !out_ids))) {
+    ts_set_error("search_biased: null queries, bias or outputs");
+    return TS_ERR_INVALID;
+  }
+  if (n_masks < 0 || allow_words < 0 || (n_masks > 0 && !allow_bits)) {
+    ts_set_error("search_biased: n_masks = %d, allow_words = %lld, allow_bits %s", n_masks, (long long)allow_words,
+                 allow_bits ? "set" : "null");
+    return TS_ERR_INVALID;
+  }
+  for (int32_t q = 0; mask_of_query && q < nq; ++q) {
+    if (mask_of_query[q] < -1 || mask_of_query[q] >= n_masks) {
+      ts_set_error("search_biased: mask_of_query[%d] = %d is outside [-1, %d)", q, mask_of_query[q], n_masks);
+      return TS_ERR_INVALID;
+    }
+  }
+  if (!h) { ts_set_error("null handle"); return TS_ERR_INVALID; }
+  TS_CHECK(funnel_storage_ok(h, "search_biased"));
+  const int64_t N = h->ntotal;
+  if (bias_rows < N) {
+    ts_set_error("search_biased: bias_rows = %lld < ntotal = %lld", (long long)bias_rows, (long long)N);
+    return TS_ERR_INVALID;
+  }
+  if (n_masks > 0 && allow_words < (N + 31) / 32) {
+    ts_set_error("search_biased: allow_words = %lld < ceil(ntotal / 32) = %lld", (long long)allow_words,
+                 (long long)((N + 31) / 32));
+    return TS_ERR_INVALID;
+  }
+  const bool host = (flags & TS_FLAG_HOST_PTR) != 0;
+  if (host) {
+    for (int64_t r = 0; r < N; ++r) {
+      if (!std::isfinite(bias[r])) {
+        ts_set_error("search_biased: bias[%lld] is not finite", (long long)r);
+        return TS_ERR_INVALID;
+      }
+    }
+  } else if (reinterpret_cast<uintptr_t>(bias) % 16 != 0) {
+    ts_set_error("search_biased: a device bias must be 16-byte aligned");
+    return TS_ERR_INVALID;
+  }
+  std::lock_guard<std::mutex> blk(h->bias_mu);
+  {
+    std::lock_guard<std::mutex> lk(h->mu);
+    for (int i = 0; i < 4; ++i) h->binfo[i] = 0;
+  }
+  if (nq == 0) return TS_OK;
+  if (N == 0) {
+    ts_set_error("No documents indexed. Call add_documents() first.");
+    return TS_ERR_EMPTY;
+  }
+  std::vector<int32_t> none;
+  if (!mask_of_query) {
+    none.assign((size_t)nq, -1);
+    mask_of_query = none.data();
+  }
+  const float* dbias = bias;
+  float* tail = nullptr;
+  {
+    // bias_stage: [0, 32) the padded entries of the last, partial row block; from float 32 on the staged copy of a
+    // host array.  Written in stream order; the call returns with the stream drained, so the next call may reuse it.
+    DeviceGuard g(h->device);
+    hipStream_t s = (hipStream_t)stream;
+    TS_CHECK(co_flush(h, s));   // held coalesced passes first, then the call's own work
+    const int64_t full = N / TS_ROWS_PER_BLOCK * TS_ROWS_PER_BLOCK;
+    TS_CHECK(ensure(h->bias_stage, (size_t)(TS_ROWS_PER_BLOCK + (host ? N : 0)) * 4));
+    tail = (float*)h->bias_stage.p;
+    if (host) {
+      TS_HIP(hipMemcpyAsync(tail + TS_ROWS_PER_BLOCK, bias, (size_t)N * 4, hipMemcpyHostToDevice, s));
+      dbias = tail + TS_ROWS_PER_BLOCK;
+    }
+    TS_HIP(hipMemsetAsync(tail, 0, TS_ROWS_PER_BLOCK * 4, s));
+    if (N > full) TS_HIP(hipMemcpyAsync(tail, dbias + full, (size_t)(N - full) * 4, hipMemcpyDeviceToDevice, s));
+  }
+  return search_filtered_impl(h, queries, nq, q_dtype, k, allow_bits, allow_words, n_masks, mask_of_query, out_scores,
+                              out_ids, flags, stream, 0, dbias, tail);
+}
+
+extern "C" int ts_index_last_bias_info(const ts_index* h, int64_t info[4]) {
+  if (!h || !info) { ts_set_error("bad arguments"); return TS_ERR_INVALID; }
+  std::lock_guard<std::mutex> lk(const_cast<ts_index*>(h)->mu);
+  for (int i = 0; i < 4; ++i) info[i] = h->binfo[i];
+  return TS_OK;
 }
 
 // Exact scores of given candidates: gather (ts_mmr.hip) -> one wave per 32-candidate tile against the pass's query

@@ -210,6 +210,9 @@ __device__ __forceinline__ void flush_stage(const ScanParams& p, SL* st, int tid
 //                              mor[hq]    ORed into every word read (all ones for an unmasked query)
 //                              mw[hq]     the current block's allow word, what the epilogue tests
 //                              mwn[hq]    the next block's word as fetched (mor not yet applied)
+//   kBiased                  a masked walk that also carries the per-row bias of the current row block (WalkLiveBias,
+//                            ts_scan_bias.hip): bias_init / bias_fetch / bias_advance beside the mask hooks, and an
+//                            epilogue of its own that tests and stages score + bias
 
 // 16-bit storage and the exact-f32 MFMA: one slot, one MFMA group per query half
 template <int DT>
@@ -244,6 +247,7 @@ typedef const int32_t __attribute__((address_space(4)))* ts_sgpr_i32p;
 struct WalkStrided {
   typedef ScanParams Params;
   static constexpr bool kMasked = false;
+  static constexpr bool kBiased = false;
   static __device__ __forceinline__ int wave(int tid) { return tid >> 6; }
   static __device__ __forceinline__ int64_t nwork(const Params& p) { return p.nwork; }
   static __device__ __forceinline__ int64_t block(const Params& p, int64_t i) { return p.blk0 + i * p.blk_stride; }
@@ -260,6 +264,7 @@ struct WalkStrided {
 struct WalkLive {
   typedef MaskedScanParams Params;
   static constexpr bool kMasked = true;
+  static constexpr bool kBiased = false;
   static __device__ __forceinline__ int wave(int tid) { return __builtin_amdgcn_readfirstlane(tid >> 6); }
   static __device__ __forceinline__ int64_t nwork(const Params& p) { return (int64_t)*(ts_sgpr_u32p)p.nlive; }
   static __device__ __forceinline__ int64_t block(const Params& p, int64_t i) {
@@ -318,6 +323,7 @@ template <int QH, int MODE, class OP, class WALK>
 __global__ __launch_bounds__(SCAN_THREADS) void scan_kernel(typename WALK::Params p) {
   typedef typename OP::Stage Stage;
   constexpr bool MASKED = WALK::kMasked && MODE == SCAN_FILTER;
+  constexpr bool BIASED = MASKED && WALK::kBiased;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   u32x4* qlds = reinterpret_cast<u32x4*>(smem);
   const int tid = threadIdx.x;
@@ -361,6 +367,11 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_kernel(typename WALK::Param
     int64_t mstep[QH];
     uint32_t mor[QH], mw[QH];
     if constexpr (MASKED) WALK::template mask_init<QH>(p, blk, lane, mrow, mstep, mor, mw);
+    // the bias state of a biased walk: bcur[r >> 2][r & 3] is the bias of the row of accumulator register r, bmax
+    // the largest of the lane's 16
+    f32x4 bcur[4];
+    float bmax;
+    if constexpr (BIASED) WALK::bias_init(p, blk, lane, bcur, bmax);
 
     const u32x4* ql = qlds + lane;
 
@@ -392,6 +403,8 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_kernel(typename WALK::Param
       // row block
       uint32_t mwn[QH];
       if constexpr (MASKED) WALK::template mask_fetch<QH>(p, blkn, mrow, mstep, mwn);
+      f32x4 bnxt[4];
+      if constexpr (BIASED) WALK::bias_fetch(p, blkn, lane, bnxt);
 #pragma unroll
       for (int i = 0; i < TS_RING; ++i) {
         OP::template step<QH>(acc, ring, i, ql, g0 + i);
@@ -401,6 +414,8 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_kernel(typename WALK::Param
 
       if constexpr (MODE == SCAN_DENSE)
         epilogue_dense<QH>(p, acc, w, blk, lane);
+      else if constexpr (BIASED)
+        WALK::template epilogue<QH, Stage>(p, st, acc, tau, blk, lane, mw, bcur, bmax);
       else if constexpr (MASKED)
         epilogue_filter<QH, Stage, true>(p, st, acc, tau, blk, lane, mw);
       else
@@ -411,6 +426,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_kernel(typename WALK::Param
       blk = blkn;
       cur = nxt;
       if constexpr (MASKED) WALK::template mask_advance<QH>(mor, mwn, mw);
+      if constexpr (BIASED) WALK::bias_advance(bnxt, bcur, bmax);
     }
   }  // active
   if constexpr (MODE == SCAN_FILTER) flush_stage(p, st, tid);

@@ -338,6 +338,42 @@ def funnel_check(d: int, dims, k, fetch_k=None):
     return k, dims, fetch_k
 
 
+BIAS_MAX_K = 16384   # results per query of search_biased(): the select kernels hold 16384 keys in LDS
+
+
+def bias_check_k(k) -> int:
+    """The ``k`` of ``search_biased`` (``ValueError``), checked before anything is launched."""
+    k = int(k)
+    if not 1 <= k <= BIAS_MAX_K:
+        raise ValueError(f"k={k} must be in 1 .. {BIAS_MAX_K}")
+    return k
+
+
+def _marshal_bias(bias, n: int, device, check_finite: bool):
+    """``bias`` of a ``search_biased`` over ``n`` rows, for a call that reads it on ``device`` (a torch device) or on the
+    host (None): one float32 entry per row, contiguous (16-byte aligned on the device).  A wrong length is a
+    ``ValueError``; so is a NaN or an infinity, on the device with ``check_finite`` and on the host always (the library
+    refuses such a host array itself)."""
+    shape = tuple(bias.shape) if hasattr(bias, "shape") else (len(bias),)
+    if shape != (n,):
+        raise ValueError(f"bias must hold one entry per row, [{n}], got {shape}")
+    if device is None:
+        b = np.ascontiguousarray(_to_host(bias), dtype=np.float32)
+        if not np.isfinite(b).all():
+            raise ValueError("bias holds a NaN or an infinity (every entry must be finite); a bias that goes through the "
+                             "host is always checked, check_finite=False applies to CUDA tensors only")
+        return b
+    else:
+        torch = _torch()
+        b = bias if _is_tensor(bias) else torch.from_numpy(np.ascontiguousarray(bias, dtype=np.float32))
+        b = b.to(device=device, dtype=torch.float32).contiguous()
+        if b.data_ptr() % 16:
+            b = b.clone()
+        if check_finite and not bool(torch.isfinite(b).all()):
+            raise ValueError("bias holds a NaN or an infinity (every entry must be finite)")
+        return b
+
+
 GROUP_MAX_FETCH = 16384   # entries per query of group_topk(): one workgroup sorts the list in LDS (the select limit)
 
 
@@ -1041,6 +1077,44 @@ class FlatIPIndex(_IndexBase):
         the prefix pass's threshold filter gave the shortlist, ``"dense"`` when the dense path did (small corpora,
         ``fetch_k > 2048``, or the exact fallback)."""
         return dict(getattr(self, "_funnel_info", {}))
+
+    # -- boosted search (DESIGN.md 4.22) ---------------------------------------
+    def search_biased(self, q, k: int, bias, allowed=None, exact_dense: bool = False, check_finite: bool = True):
+        """Top-``k`` by ``score + bias``: ``bias`` is float32 with one entry per row (``ntotal``, indexed by local row:
+        the index's id offset is taken off the ids), added to every query's score inside the scan, so the result is
+        exact: the ``k`` allowed live rows with the largest ``float32(score + bias[row])``, ties to the lower id,
+        -1 / -FLT_MAX padded.  ``D`` holds the boosted scores; each is one f32 addition of the score :meth:`search` and
+        :meth:`scores` give the pair and the row's bias.  ``k <= 16384`` (``ValueError`` otherwise); f16 / bf16 storage.
+        ``check_finite`` (default): a NaN or an infinity in ``bias`` is a ``ValueError``.  ``check_finite=False`` applies
+        to CUDA tensor queries only (the bias is then read on the device as it is): a row whose boosted score is NaN is
+        never returned and the effect of an infinite entry is undefined.  With numpy queries the bias goes through the
+        host, where it is always checked.  Synchronous, on the current
+        stream.  numpy queries in -> numpy out (``bias`` then goes through the host); CUDA tensor queries in -> tensors
+        out (``bias`` is used in place when it is a 16-byte aligned float32 tensor on the index's GPU, uploaded
+        otherwise).  ``allowed``: every form :meth:`search` takes.  :meth:`last_bias_info` describes the call."""
+        if self.storage_dtype not in ("f16", "bf16"):
+            raise NotImplementedError(f"search_biased takes an f16 or bf16 index, not {self.storage_dtype}")
+        k = bias_check_k(k)
+        n = self.ntotal
+        if n == 0:
+            _raise_empty()
+        q, q_dtype, B, on_gpu = _host_query(q, self.d)
+        b = _marshal_bias(bias, n, q.device if on_gpu else None, check_finite)
+        D, I = _outputs(None, B, k, q)
+        flags = (_lib.TS_FLAG_NO_FILTER if exact_dense else 0) | (0 if on_gpu else _lib.TS_FLAG_HOST_PTR)
+        m = _NO_MASKS if allowed is None else _marshal_allowed(allowed, B, n, q.device if on_gpu else None)
+        _check(self._lib.ts_index_search_biased(
+            self._h, _addr(q), B, q_dtype, k, _addr(b), n, _addr(m.bits), m.words if m.n_masks else 0, m.n_masks,
+            _addr(m.moq), _addr(D), _addr(I), flags, _stream_ptr(self.device) if on_gpu else None), invalid=True)
+        return D, I
+
+    def last_bias_info(self) -> dict:
+        """The last :meth:`search_biased`: its passes (of <= 64 queries), those whose first attempt was the fused path
+        (thresholds and the biased filter scan), those of them redone on the exact dense path, and the 32-row blocks
+        its scans read."""
+        arr = (ctypes.c_int64 * 4)()
+        _lib.check(self._lib.ts_index_last_bias_info(self._h, arr))
+        return {"passes": int(arr[0]), "fused_passes": int(arr[1]), "redone": int(arr[2]), "blocks_read": int(arr[3])}
 
     def reconstruct_n(self, i0: int = 0, n: Optional[int] = None) -> np.ndarray:
         """Rows [i0, i0+n) as float32 (after storage rounding)."""
@@ -1848,6 +1922,9 @@ class IVFFlatIndex(_IndexBase):
 
     def search_funnel(self, q, k: int, dims: int, fetch_k: Optional[int] = None, allowed=None):
         raise NotImplementedError("funnel search is not supported on an IVF index (its lists hold whole rows; use a flat index)")
+
+    def search_biased(self, q, k: int, bias, allowed=None, exact_dense: bool = False, check_finite: bool = True):
+        raise NotImplementedError("boosted search (search_biased) is not supported on an IVF index (use a flat index)")
 
     def search_grouped(self, q, k: int, groups, group_size: int = 1, fetch_k: Optional[int] = None,
                        nprobe: Optional[int] = None):

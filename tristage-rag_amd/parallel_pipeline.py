@@ -210,6 +210,10 @@ class ShardedRetrievalPipeline(RetrievalPipeline):
         if funnel_dims is not None or getattr(getattr(self, "config", None), "stage1_funnel_dims", None) is not None:
             raise NotImplementedError("funnel_dims is not supported by the row-sharded pipeline")
 
+    def _refuse_boost(self, boost) -> None:
+        if boost is not None or getattr(getattr(self, "config", None), "stage1_boost", None) is not None:
+            raise NotImplementedError("boost is not supported by the row-sharded pipeline")
+
     def _refuse_passages(self, passages) -> None:
         asked = passages is not None and passages is not _NO_PASSAGES     # (the marker: batch_search's own "off")
         if asked or getattr(getattr(self, "config", None), "passage_window", None) is not None:
@@ -217,10 +221,11 @@ class ShardedRetrievalPipeline(RetrievalPipeline):
 
     def batch_search(self, queries: List[str], top_k: Optional[int] = None, filter=None,
                      mmr_lambda=None, group_by=None, group_size: int = 1, passages=None,
-                     funnel_dims=None) -> List[Dict[str, Any]]:
+                     funnel_dims=None, boost=None) -> List[Dict[str, Any]]:
         # (refused HERE: the base class resolves the window and then calls search() with its own "off" marker)
         self._refuse_passages(passages)
         self._refuse_funnel(funnel_dims)
+        self._refuse_boost(boost)
         return super().batch_search(queries, top_k, filter=filter, mmr_lambda=mmr_lambda, group_by=group_by,
                                     group_size=group_size, passages=_NO_PASSAGES)
 
@@ -369,13 +374,14 @@ class ShardedRetrievalPipeline(RetrievalPipeline):
                         r["document"], r["metadata"] = have[int(r["doc_id"])]
 
     def search(self, query: str, top_k: Optional[int] = None, filter=None, mmr_lambda=None,
-               group_by=None, group_size: int = 1, passages=None, funnel_dims=None) -> Dict[str, Any]:
+               group_by=None, group_size: int = 1, passages=None, funnel_dims=None, boost=None) -> Dict[str, Any]:
         if filter is not None:
             raise NotImplementedError(FILTER_UNSUPPORTED)
         self._refuse_mmr(mmr_lambda)
         self._refuse_group(group_by)
         self._refuse_passages(passages)
         self._refuse_funnel(funnel_dims)
+        self._refuse_boost(boost)
         if self.world_size == 1:
             return super().search(query, top_k)
         if self.config.search_on_arrays and self._arrays_agreed():
@@ -449,7 +455,7 @@ class ShardedRetrievalPipeline(RetrievalPipeline):
 
     def search_many(self, queries: List[str], top_k: Optional[int] = None, filter=None,
                     mmr_lambda=None, group_by=None, group_size: int = 1, passages=None,
-                    funnel_dims=None) -> List[Dict[str, Any]]:
+                    funnel_dims=None, boost=None) -> List[Dict[str, Any]]:
         """Batched search over R ranks; every rank returns every query's records.  Array path (token store + id
         cache on the shards): three collectives per call besides stage 1's — two all-reduces of small score matrices
         and one gather of the returned texts.  Otherwise the per-record path, query by query."""
@@ -459,6 +465,7 @@ class ShardedRetrievalPipeline(RetrievalPipeline):
         self._refuse_group(group_by)
         self._refuse_passages(passages)
         self._refuse_funnel(funnel_dims)
+        self._refuse_boost(boost)
         if self.world_size == 1:
             return super().search_many(queries, top_k)
         if not self.stage1 or not self.stage2 or not self.stage3:

@@ -97,6 +97,8 @@ class PipelineConfig:
     stage1_funnel_fetch_k: Optional[int] = None  # rescored exactly; the shortlist, None: min(2048, max(8 k, 128))
     passage_window: Optional[int] = None     # None: off.  Tokens of the best passage every final record then carries
                                              # under "passage" (windowed MaxSim over the stage-2 tokens)
+    stage1_boost: Any = None                 # None: off.  A boost spec (boost.py): stage 1's dense candidates are ranked by
+                                             # score + a per-document bias, exactly
 
 
 # (section, key) in the reference's YAML layout -> PipelineConfig field (reference :182-217)
@@ -353,6 +355,15 @@ class RetrievalPipeline:
             raise ValueError("funnel_dims cannot be combined with mmr_lambda or group_by")
         return {"funnel_dims": int(dims)}
 
+    def _boost_kwargs(self, boost, lam, gkw) -> Dict[str, Any]:
+        """The boost of a search as a keyword argument for stage 1 (the argument, else the config); {}: off."""
+        spec = self.config.stage1_boost if boost is None else boost
+        if spec is None:
+            return {}
+        if lam is not None or gkw:
+            raise ValueError("boost cannot be combined with mmr_lambda, group_by or funnel_dims")
+        return {"boost": spec}
+
     def _diversify(self, outs: List[Dict[str, Any]], top_k: int, lam: float) -> List[Dict[str, Any]]:
         """``results`` of each output (the whole list stage 3 returned) -> its ``top_k`` picks by maximal marginal
         relevance, in selection order: relevance = stage3_score as f32, similarity = the inner product of the rows the
@@ -424,7 +435,8 @@ class RetrievalPipeline:
         return outs
 
     def search(self, query: str, top_k: Optional[int] = None, filter=None, mmr_lambda=None,
-               group_by=None, group_size: int = 1, passages=None, funnel_dims: Optional[int] = None) -> Dict[str, Any]:
+               group_by=None, group_size: int = 1, passages=None, funnel_dims: Optional[int] = None,
+               boost=None) -> Dict[str, Any]:
         """``filter``: search only the documents it allows (Stage1Retriever.filter_mask: a metadata dict, a
         callable, document indices or a bool array).  Stages 2 and 3 rescore stage 1's candidates, so fewer
         than ``top_k`` results come back when fewer documents are allowed, and none when none are.
@@ -441,18 +453,24 @@ class RetrievalPipeline:
         :meth:`_add_passages`; the character fields are None for a tokenizer without offsets).
         ``funnel_dims`` (default: the config's ``stage1_funnel_dims``, None = off): stage 1's dense candidates come from
         the funnel (Stage1Retriever.search); it replaces only that search, so ``filter`` and BM25 fusion work unchanged.
-        Not together with ``mmr_lambda`` or ``group_by``: ``ValueError``."""
+        Not together with ``mmr_lambda`` or ``group_by``: ``ValueError``.
+        ``boost`` (default: the config's ``stage1_boost``, None = off): a boost spec (boost.py); stage 1's dense candidates
+        are the documents with the largest score + bias (Stage1Retriever.search).  It replaces only that search, so
+        ``filter`` and BM25 fusion work unchanged; stages 2 and 3 score as ever.  Stage 1 keeps the bias arrays of the
+        last 4 specs; an array or a callable is one spec by IDENTITY: one changed in place has to be passed as a new
+        object.  Not together with ``mmr_lambda``, ``group_by`` or ``funnel_dims``: ``ValueError``."""
         if not self.stage1 or not self.stage2 or not self.stage3:
             self.initialize_stages()
         pw = self._passage_window(passages)
         if pw is not None:
             return self._add_passages([self.search(query, top_k, filter=filter, mmr_lambda=mmr_lambda, group_by=group_by,
                                                    group_size=group_size, passages=_NO_PASSAGES,
-                                                   funnel_dims=funnel_dims)], pw)[0]
+                                                   funnel_dims=funnel_dims, boost=boost)], pw)[0]
         top_k = top_k or self.config.stage3_top_k
         lam = self._mmr_lambda(mmr_lambda)
         gkw = self._group_kwargs(group_by, group_size, lam)
         gkw.update(self._funnel_kwargs(funnel_dims, lam, gkw))
+        gkw.update(self._boost_kwargs(boost, lam, gkw))
         if lam is not None:
             return self._diversify([self.search(query, _ALL_RESULTS, filter=filter, mmr_lambda=_NO_MMR,
                                                 passages=_NO_PASSAGES)], top_k, lam)[0]
@@ -477,11 +495,11 @@ class RetrievalPipeline:
 
     def batch_search(self, queries: List[str], top_k: Optional[int] = None, filter=None,
                      mmr_lambda=None, group_by=None, group_size: int = 1, passages=None,
-                     funnel_dims: Optional[int] = None) -> List[Dict[str, Any]]:
+                     funnel_dims: Optional[int] = None, boost=None) -> List[Dict[str, Any]]:
         """Sequential, like the reference (:444-448); see search_many for the batched form.  ``filter``: one
         filter for every query or a list with one per query.  ``mmr_lambda``, ``group_by`` / ``group_size``: as for
-        :meth:`search`.  ``passages``: as for :meth:`search`, one kernel call for the batch.  ``funnel_dims``: as for
-        :meth:`search`."""
+        :meth:`search`.  ``passages``: as for :meth:`search`, one kernel call for the batch.  ``funnel_dims``, ``boost``:
+        as for :meth:`search`."""
         if passages is not _NO_PASSAGES:
             if not self.stage2:
                 self.initialize_stages()
@@ -489,11 +507,14 @@ class RetrievalPipeline:
             if pw is not None:
                 return self._add_passages(self.batch_search(queries, top_k, filter=filter, mmr_lambda=mmr_lambda,
                                                             group_by=group_by, group_size=group_size,
-                                                            passages=_NO_PASSAGES, funnel_dims=funnel_dims), pw)
+                                                            passages=_NO_PASSAGES, funnel_dims=funnel_dims,
+                                                            boost=boost), pw)
         gkw = {} if group_by is None else {"group_by": group_by, "group_size": group_size}
         gkw["passages"] = _NO_PASSAGES
         if funnel_dims is not None:
             gkw["funnel_dims"] = funnel_dims
+        if boost is not None:
+            gkw["boost"] = boost
         if filter is None:
             if mmr_lambda is None:
                 return [self.search(q, top_k, **gkw) for q in queries]
@@ -505,7 +526,7 @@ class RetrievalPipeline:
 
     def search_many(self, queries: List[str], top_k: Optional[int] = None, filter=None,
                     mmr_lambda=None, group_by=None, group_size: int = 1, passages=None,
-                    funnel_dims: Optional[int] = None) -> List[Dict[str, Any]]:
+                    funnel_dims: Optional[int] = None, boost=None) -> List[Dict[str, Any]]:
         """Same result records as batch_search, every stage batched over the queries: one
         bi-encoder pass and one sweep of the corpus per 64 queries (stage 1), one query forward
         and one MaxSim launch (stage 2, with the resident token store), one length-sorted pass
@@ -513,20 +534,22 @@ class RetrievalPipeline:
         reported as equal shares of the batch's stage times.  ``filter``: one filter for every query or a list
         with one per query (see :meth:`search`); a filtered batch takes the record path.  ``group_by`` /
         ``group_size``: as for :meth:`search`, one collapse for the batch.  ``passages``: as for :meth:`search`, one
-        kernel call for the batch.  ``funnel_dims``: as for :meth:`search`, one funnel for the batch."""
+        kernel call for the batch.  ``funnel_dims``: as for :meth:`search`, one funnel for the batch.
+        ``boost``: as for :meth:`search`, one bias for the batch."""
         if not self.stage1 or not self.stage2 or not self.stage3:
             self.initialize_stages()
         pw = self._passage_window(passages)
         if pw is not None:
             return self._add_passages(self.search_many(queries, top_k, filter=filter, mmr_lambda=mmr_lambda,
                                                        group_by=group_by, group_size=group_size,
-                                                       passages=_NO_PASSAGES, funnel_dims=funnel_dims), pw)
+                                                       passages=_NO_PASSAGES, funnel_dims=funnel_dims, boost=boost), pw)
         top_k = top_k or self.config.stage3_top_k
         if not queries:
             return []
         lam = self._mmr_lambda(mmr_lambda)
         gkw = self._group_kwargs(group_by, group_size, lam)
         gkw.update(self._funnel_kwargs(funnel_dims, lam, gkw))
+        gkw.update(self._boost_kwargs(boost, lam, gkw))
         if lam is not None:   # (mmr_lambda: as for search(); one selection call for the batch)
             return self._diversify(self.search_many(queries, _ALL_RESULTS, filter=filter, mmr_lambda=_NO_MMR,
                                                     passages=_NO_PASSAGES), top_k, lam)
@@ -752,8 +775,17 @@ class RetrievalPipeline:
         self.logger.info(f"Pipeline index loaded from {index_path}")
 
     # -- introspection -----------------------------------------------------------
+    def _config_dict(self) -> Dict[str, Any]:
+        """The configuration as plain data: a boost spec that is an array or a callable is named, not dumped."""
+        d = asdict(self.config)
+        b = self.config.stage1_boost
+        if b is not None and not isinstance(b, dict):
+            d["stage1_boost"] = (f"<callable {getattr(b, '__name__', type(b).__name__)}>" if callable(b)
+                                 else f"<array of {len(b)} biases>")
+        return d
+
     def get_pipeline_info(self) -> Dict[str, Any]:
-        info = {"config": asdict(self.config),
+        info = {"config": self._config_dict(),
                 "stages_initialized": {"stage1": self.stage1 is not None, "stage2": self.stage2 is not None,
                                        "stage3": self.stage3 is not None},
                 "performance_stats": self.performance_stats}
@@ -792,5 +824,5 @@ class RetrievalPipeline:
 
     def export_config(self, config_path: str):
         with open(config_path, "w") as f:
-            yaml.dump({"pipeline": asdict(self.config)}, f, default_flow_style=False)
+            yaml.dump({"pipeline": self._config_dict()}, f, default_flow_style=False)
         self.logger.info(f"Configuration exported to {config_path}")

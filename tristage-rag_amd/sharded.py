@@ -123,6 +123,9 @@ class ShardedFlatIPIndex:
     def search_funnel(self, q, k: int, dims: int, fetch_k=None, allowed=None):
         raise NotImplementedError("funnel search is not supported on a row-sharded index")
 
+    def search_biased(self, q, k: int, bias, allowed=None, exact_dense: bool = False, check_finite: bool = True):
+        raise NotImplementedError("boosted search (search_biased) is not supported on a row-sharded index")
+
     def search(self, q, k: int, async_: bool = False, inputs_ready: bool = False, allowed=None):
         """Global top-k for the replicated query batch `q` (tensor).  Returns
         tensors (D float32 [B,k], I int64 [B,k]) identical on every rank.

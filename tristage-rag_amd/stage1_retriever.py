@@ -34,6 +34,8 @@ from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from . import boost as _boost
+
 
 @dataclass
 class Stage1Config:
@@ -78,6 +80,9 @@ class Stage1Config:
                                           # come from FlatIPIndex.search_funnel (ranked on that prefix of the dimensions,
                                           # rescored exactly).  For Matryoshka-trained encoders.
     funnel_fetch_k: Optional[int] = None  # the funnel's shortlist; None: min(2048, max(8 top_k, 128))
+    boost: Any = None                     # None: off.  A boost spec (boost.py): an array with one bias per document, a field
+                                          # or decay dict, or a callable metadata -> float; the dense candidates come from
+                                          # FlatIPIndex.search_biased, ranked by score + bias
 
 
 def amp_torch_dtype(name: str):
@@ -404,6 +409,7 @@ class Stage1Retriever:
         self._kv_bitmaps: Dict[Any, np.ndarray] = {}
         self._mask_lru: "OrderedDict[Any, Any]" = OrderedDict()
         self._group_tables: Dict[Any, Dict[str, Any]] = {}   # group_by keys: value codes and their device copy (same owner)
+        self._boost_lru: "OrderedDict[Any, Any]" = OrderedDict()   # boost specs: their bias arrays (_boost_bias)
         self._filter_cache_meta = self.doc_metadata
         self.filter_cache_size = 8
         self._index_factory = index_factory
@@ -521,6 +527,7 @@ class Stage1Retriever:
         if metadata is None:
             metadata = [{}] * len(documents)  # one shared dict, as in the reference (:302)
         self.doc_metadata.extend(metadata)
+        self._drop_boost_cache()
         if self._device_path():
             emb = self._encode_batch_tensor(list(documents), bulk=True)
             if self.faiss_index is None:
@@ -546,6 +553,7 @@ class Stage1Retriever:
         self._kv_bitmaps.clear()
         self._mask_lru.clear()
         self._group_tables = {}
+        self._drop_boost_cache()
         self._filter_cache_meta = self.doc_metadata
 
     def _check_filter_caches(self) -> None:
@@ -683,6 +691,7 @@ class Stage1Retriever:
             if got != ids.size:
                 raise RuntimeError(f"the index removed {got} of {ids.size} rows: it is out of step with the documents")
         r[ids] = True
+        self._drop_boost_cache()
         return int(ids.size)
 
     def compact(self) -> np.ndarray:
@@ -771,6 +780,7 @@ class Stage1Retriever:
                 self.doc_metadata[i] = metadata[j]
         if metadata is not None:
             self._reset_filter_caches()
+        self._drop_boost_cache()
         if self.config.enable_bm25 and self.bm25_index is not None:
             if self.bm25_index.refit_compat:   # (its fit() appends to the old entries: document i would keep the old
                 self.bm25_index.close()        # text's term frequencies; a fresh index, as compact() builds)
@@ -803,9 +813,13 @@ class Stage1Retriever:
             self._mask_lru.move_to_end(key)
         return hit
 
-    def _dense_search(self, q, top_k: int, masks, filters, funnel=None):
-        """faiss_index.search, with ``allowed=`` when a filter is given; ``funnel`` = (dims, fetch_k): search_funnel."""
-        if funnel is not None:
+    def _dense_search(self, q, top_k: int, masks, filters, funnel=None, boost=None):
+        """faiss_index.search, with ``allowed=`` when a filter is given; ``funnel`` = (dims, fetch_k): search_funnel;
+        ``boost`` = a boost spec: search_biased with the spec's bias."""
+        if boost is not None:
+            bias = self._boost_bias(boost, on_device=hasattr(q, "is_cuda") and q.is_cuda)
+            search = lambda q_, k_, **kw: self.faiss_index.search_biased(q_, k_, bias, **kw)
+        elif funnel is not None:
             search = lambda q_, k_, **kw: self.faiss_index.search_funnel(q_, k_, funnel[0], fetch_k=funnel[1], **kw)
         else:
             search = self.faiss_index.search
@@ -833,6 +847,56 @@ class Stage1Retriever:
         if self.faiss_index is not None and not hasattr(self.faiss_index, "search_funnel"):
             raise NotImplementedError(f"{type(self.faiss_index).__name__} has no search_funnel()")
         return int(dims), self.config.funnel_fetch_k
+
+    # -- boosted search ----------------------------------------
+    BOOST_CACHE_SIZE = 4
+
+    def _drop_boost_cache(self) -> None:
+        lru = getattr(self, "_boost_lru", None)
+        if lru:
+            lru.clear()
+
+    def _boost_args(self, boost, lam=None, grp=None, fun=None):
+        """The boost spec of a search (the argument, else the config), checked; None: off."""
+        spec = self.config.boost if boost is None else boost
+        if spec is None:
+            return None
+        if lam is not None or grp is not None or fun is not None:
+            raise ValueError("boost cannot be combined with mmr_lambda, group_by or funnel_dims")
+        _boost.check_spec(spec)
+        if getattr(self, "index_type_used", "flat") == "ivf":
+            raise NotImplementedError("boosted search is not supported on an IVF index (index_type='ivf')")
+        if self.faiss_index is not None and not hasattr(self.faiss_index, "search_biased"):
+            raise NotImplementedError(f"{type(self.faiss_index).__name__} has no search_biased()")
+        dt = getattr(self.faiss_index, "storage_dtype", "f16")
+        if dt not in ("f16", "bf16"):
+            raise NotImplementedError(f"boosted search takes an f16 or bf16 index, not {dt}")
+        return spec
+
+    def _boost_bias(self, spec, on_device: bool):
+        """The bias of ``spec`` over the documents: float32, one entry per document, a tensor on the index's GPU when
+        ``on_device``.  An LRU of BOOST_CACHE_SIZE specs keeps the arrays (an array or a callable is one spec by
+        identity); it is dropped whenever documents are added, updated, removed or compacted or the metadata list is
+        replaced, as the filter caches are."""
+        self._check_filter_caches()
+        lru = getattr(self, "_boost_lru", None)
+        if lru is None:
+            lru = self._boost_lru = OrderedDict()
+        key, keep = _boost.spec_key(spec)
+        hit = lru.get(key)
+        if hit is None:
+            hit = {"keep": keep, "host": _boost.bias_array(spec, self.doc_metadata), "dev": None}
+            lru[key] = hit
+            while len(lru) > self.BOOST_CACHE_SIZE:
+                lru.popitem(last=False)
+        else:
+            lru.move_to_end(key)
+        if not on_device:
+            return hit["host"]
+        if hit["dev"] is None:
+            import torch
+            hit["dev"] = torch.from_numpy(hit["host"]).to(torch.device("cuda", self.config.gpu_index_device))
+        return hit["dev"]
 
     # -- diversified dense search (MMR, DESIGN.md 4.17) ------------------------
     def _mmr_lambda(self, mmr_lambda) -> Optional[float]:
@@ -934,7 +998,9 @@ class Stage1Retriever:
                                  group_size)
         return D, I
 
-    def _pick_dense_search(self, lam, grp, fun=None):
+    def _pick_dense_search(self, lam, grp, fun=None, bst=None):
+        if bst is not None:
+            return lambda q_, k_, m_, f_: self._dense_search(q_, k_, m_, f_, boost=bst)
         if fun is not None:
             return lambda q_, k_, m_, f_: self._dense_search(q_, k_, m_, f_, funnel=fun)
         if grp is not None:
@@ -1053,7 +1119,7 @@ class Stage1Retriever:
 
     def search(self, query: str, top_k: Optional[int] = None, filter=None,
                mmr_lambda: Optional[float] = None, group_by=None, group_size: int = 1,
-               funnel_dims: Optional[int] = None) -> List[Dict[str, Any]]:
+               funnel_dims: Optional[int] = None, boost=None) -> List[Dict[str, Any]]:
         """``filter``: restrict the candidates to some documents (see :meth:`filter_mask`); fewer than
         ``top_k`` results when fewer documents are allowed, none when none are.
         ``mmr_lambda`` (default: the config's, None = off): the ``top_k`` records are picked by maximal marginal
@@ -1067,17 +1133,25 @@ class Stage1Retriever:
         ``funnel_dims`` (default: the config's, None = off): the dense candidates are ranked on that prefix of the
         dimensions and a shortlist of ``funnel_fetch_k`` is rescored exactly (FlatIPIndex.search_funnel); filters and
         BM25 fusion work on its output as on the plain search's.  Not together with ``mmr_lambda`` or ``group_by``
-        (``ValueError``); a flat f16 / bf16 index only (``NotImplementedError``)."""
+        (``ValueError``); a flat f16 / bf16 index only (``NotImplementedError``).
+        ``boost`` (default: the config's, None = off): a boost spec (boost.py): the dense candidates are the ``top_k``
+        documents with the largest ``score + bias`` and carry that sum as their score (FlatIPIndex.search_biased, exact);
+        filters and BM25 fusion work on its output as on the plain search's.  The bias arrays of the last 4 specs are kept:
+        a dict is one spec by value, an array or a callable by IDENTITY, so an array changed in place (or a callable whose
+        closure changed) has to be passed as a new object, or it gets the bias computed from it before.  Not together
+        with ``mmr_lambda``, ``group_by`` or ``funnel_dims`` (``ValueError``); a flat f16 / bf16 index only
+        (``NotImplementedError``)."""
         if self.faiss_index is None:
             raise ValueError("No documents indexed. Call add_documents() first.")
         top_k = top_k or self.config.top_k_candidates
         lam = self._mmr_lambda(mmr_lambda)
         grp = self._group_args(group_by, group_size, lam)
         fun = self._funnel_args(funnel_dims, lam, grp)
+        bst = self._boost_args(boost, lam, grp, fun)
         masks = self._filter_masks(filter, 1)
         if masks is not None and not masks[0].any():
             return []
-        dense_search = self._pick_dense_search(lam, grp, fun)
+        dense_search = self._pick_dense_search(lam, grp, fun, bst)
         if self._device_path():
             D, I = dense_search(self._normalized_query_tensor([query]), top_k, masks, filter)
             scores, ids = D.cpu().numpy(), I.cpu().numpy()
@@ -1091,22 +1165,23 @@ class Stage1Retriever:
 
     def search_many(self, queries: Sequence[str], top_k: Optional[int] = None, filter=None,
                     mmr_lambda: Optional[float] = None, group_by=None, group_size: int = 1,
-                    funnel_dims: Optional[int] = None) -> List[List[Dict[str, Any]]]:
+                    funnel_dims: Optional[int] = None, boost=None) -> List[List[Dict[str, Any]]]:
         """All queries through ONE encoder pass and ONE index call (64 queries share a
         single sweep over the corpus on the GPU).  ``filter``: one filter for every query, or a list with one
         per query (None: unfiltered).  ``mmr_lambda``: as for :meth:`search`, one selection call for the batch.
         ``group_by`` / ``group_size``: as for :meth:`search`, one collapse for the batch.  ``funnel_dims``: as for
-        :meth:`search`, one funnel for the batch."""
+        :meth:`search`, one funnel for the batch.  ``boost``: as for :meth:`search`, one bias for the batch."""
         if self.faiss_index is None:
             raise ValueError("No documents indexed. Call add_documents() first.")
         top_k = top_k or self.config.top_k_candidates
         lam = self._mmr_lambda(mmr_lambda)
         grp = self._group_args(group_by, group_size, lam)
         fun = self._funnel_args(funnel_dims, lam, grp)
+        bst = self._boost_args(boost, lam, grp, fun)
         if not queries:
             return []
         masks = self._filter_masks(filter, len(queries))
-        dense_search = self._pick_dense_search(lam, grp, fun)
+        dense_search = self._pick_dense_search(lam, grp, fun, bst)
         if self._device_path():
             D, I = dense_search(self._normalized_query_tensor(list(queries)), top_k, masks, filter)
             scores, ids = D.cpu().numpy(), I.cpu().numpy()
@@ -1124,7 +1199,7 @@ class Stage1Retriever:
         return out
 
     def search_many_arrays(self, queries: Sequence[str], top_k: Optional[int] = None, filter=None,
-                           group_by=None, group_size: int = 1, funnel_dims: Optional[int] = None):
+                           group_by=None, group_size: int = 1, funnel_dims: Optional[int] = None, boost=None):
         """Stage 1 for a query batch WITHOUT building result records: (ids int64 [B, k'], scores [B, k'])
         as torch tensors on the index's device for the pure dense search, numpy arrays (float64 fused
         scores) when BM25 fusion is on.  Row q, in order, is exactly what ``search_many`` would list for
@@ -1132,7 +1207,8 @@ class Stage1Retriever:
         which deals with padded results).  ``filter`` as for :meth:`search_many`: None also when some query has
         fewer than top_k allowed documents.  ``group_by`` / ``group_size`` as for :meth:`search_many` (device path):
         rows of top_k * group_size entries; None also when some query's row would be padded.  ``funnel_dims`` as for
-        :meth:`search_many`; None also when the funnel left some query's row padded."""
+        :meth:`search_many`; None also when the funnel left some query's row padded.  ``boost`` as for
+        :meth:`search_many`; None also when some query's boosted row would be padded."""
         import torch
         if self.faiss_index is None:
             raise ValueError("No documents indexed. Call add_documents() first.")
@@ -1142,6 +1218,7 @@ class Stage1Retriever:
             return None
         grp = self._group_args(group_by, group_size, self.config.mmr_lambda)
         fun = self._funnel_args(funnel_dims, self.config.mmr_lambda, grp)
+        bst = self._boost_args(boost, self.config.mmr_lambda, grp, fun)
         if self.config.mmr_lambda is not None:   # a diversified stage 1 goes through search_many
             return None
         if grp is not None:
@@ -1158,16 +1235,17 @@ class Stage1Retriever:
         if masks is not None:
             if any(m is not None and int(np.count_nonzero(m)) < top_k for m in masks):
                 return None
-            return self._search_many_arrays_filtered(list(queries), top_k, masks, filter, fun)
+            return self._search_many_arrays_filtered(list(queries), top_k, masks, filter, fun, bst)
         fuse = self.config.enable_bm25 and self.bm25_index is not None
-        if fun is not None:
+        if fun is not None or bst is not None:
             if self._device_path():
-                D, I = self._dense_search(self._normalized_query_tensor(list(queries)), top_k, None, None, funnel=fun)
+                D, I = self._dense_search(self._normalized_query_tensor(list(queries)), top_k, None, None, funnel=fun,
+                                          boost=bst)
             else:
                 D, I = self._dense_search(self._normalize_embeddings(self._encode_batch(list(queries))), top_k, None, None,
-                                          funnel=fun)
+                                          funnel=fun, boost=bst)
                 D, I = torch.as_tensor(D), torch.as_tensor(I)
-            if bool((I[:, -1] < 0).any()):   # (a shortlist that held fewer than top_k live rows)
+            if bool((I[:, -1] < 0).any()):   # (a shortlist, or a boosted list, that held fewer than top_k live rows)
                 return None
         elif self._device_path():
             qt = self._normalized_query_tensor(list(queries))
@@ -1199,19 +1277,20 @@ class Stage1Retriever:
             out_i[qi], out_s[qi] = fi[:top_k], fs[:top_k]
         return out_i, out_s
 
-    def _search_many_arrays_filtered(self, queries: List[str], top_k: int, masks, filter, funnel=None):
+    def _search_many_arrays_filtered(self, queries: List[str], top_k: int, masks, filter, funnel=None, boost=None):
         """search_many_arrays with a filter (every query has >= top_k allowed documents), same return types as without
         one: torch tensors (ids, scores) for the pure dense search — on the index's device on the device path —,
         numpy arrays with float64 fused scores when BM25 fusion is on (through the host arrays code, _fuse_arrays,
         with the BM25 lists filtered alike)."""
         import torch
         if self._device_path():
-            D, I = self._dense_search(self._normalized_query_tensor(queries), top_k, masks, filter, funnel=funnel)
+            D, I = self._dense_search(self._normalized_query_tensor(queries), top_k, masks, filter, funnel=funnel,
+                                      boost=boost)
         else:
             D, I = self._dense_search(self._normalize_embeddings(self._encode_batch(queries)), top_k, masks, filter,
-                                      funnel=funnel)
+                                      funnel=funnel, boost=boost)
             D, I = torch.as_tensor(D), torch.as_tensor(I)
-        if funnel is not None and bool((I[:, -1] < 0).any()):   # (a shortlist that held fewer than top_k allowed rows)
+        if (funnel is not None or boost is not None) and bool((I[:, -1] < 0).any()):   # (a shortlist that held fewer than top_k allowed rows)
             return None
         if not (self.config.enable_bm25 and self.bm25_index is not None):
             return I, D
@@ -1294,7 +1373,9 @@ class Stage1Retriever:
         base = os.path.splitext(index_path)[0]
         os.makedirs(os.path.dirname(os.path.abspath(index_path)), exist_ok=True)
         manifest = {"format": "tristage-rag_amd/1", "documents": self.documents,
-                    "doc_metadata": self.doc_metadata, "config": dict(self.config.__dict__),
+                    "doc_metadata": self.doc_metadata,
+                    # (a boost spec may be an array or a callable and belongs to the searches, not to the stored index)
+                    "config": {k: v for k, v in self.config.__dict__.items() if k != "boost"},
                     "ntotal": 0, "dim": self.embedding_dim, "matrix": None,
                     "index_type": getattr(self, "index_type_used", "flat"), "centroids": None}
         if self.faiss_index is not None:
