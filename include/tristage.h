@@ -65,7 +65,8 @@ extern "C" {
  * caller that never sets the flag sees the library it was built against.  The IVF-Flat entry points (ts_ivf_*) were
  * added within version 4 as well: no existing signature changed.  So were wide coalesced passes
  * (TS_FLAG_WIDE_PASSES, TS_FLAG_NO_WIDE_PASSES, ts_coalesce_groups_wide, ts_coalesce_wide_min_bytes), query-stationary
- * passes (TS_FLAG_STATIONARY_PASSES, TS_FLAG_NO_STATIONARY_PASSES, ts_coalesce_groups_stationary), and removal
+ * passes (TS_FLAG_STATIONARY_PASSES, TS_FLAG_NO_STATIONARY_PASSES, ts_coalesce_groups_stationary), their pass
+ * prologue (TS_FLAG_PASS_PROLOGUE, TS_FLAG_NO_PASS_PROLOGUE), and removal
  * (ts_index_remove, ts_index_live_count, ts_index_live_words, ts_index_compact): no existing signature changed, and
  * an index from which nothing is removed behaves as before; so was ts_remove_ivf.  So were ts_index_update and
  * ts_update_ivf: an index that is never updated runs the code it ran before.  So was ts_compact_ivf: no existing
@@ -130,6 +131,12 @@ enum ts_metric { TS_METRIC_INNER_PRODUCT = 0 };
                                                (ts_coalesce_groups_stationary() groups) wherever their kernel
                                                exists, whatever the corpus size; results are identical        */
 #define TS_FLAG_NO_STATIONARY_PASSES 2048u  /* with TS_FLAG_COALESCE: never query-stationary passes          */
+#define TS_FLAG_PASS_PROLOGUE 4096u     /* with TS_FLAG_COALESCE: in a queue of query-stationary passes of an index
+                                           without removed rows, a batch's sample scan and thresholds are enqueued
+                                           with its first pass, and a pass's sample scans, thresholds and selects
+                                           share one launch each ("pass prologue"); the default there, and without
+                                           effect elsewhere; results are identical                              */
+#define TS_FLAG_NO_PASS_PROLOGUE 8192u  /* with TS_FLAG_COALESCE: never: every batch keeps launches of its own  */
 #define TS_FLAG_NORMALIZE 4u    /* add: L2-normalise rows x/(|x|+1e-8) on device first
                                    (reference src/stage1_retriever.py:285-288) */
 
@@ -297,7 +304,12 @@ int64_t ts_coalesce_wide_min_bytes(void);
  * dimension does not fit the registers; at a smaller one the LDS-resident passes read at the ceiling already).  The
  * queue uses them where it would use wide passes by its own policy (neither wide-pass flag set) and nothing has been
  * removed from the index, unless TS_FLAG_STATIONARY_PASSES / TS_FLAG_NO_STATIONARY_PASSES decide; a forced
- * TS_FLAG_WIDE_PASSES / TS_FLAG_NO_WIDE_PASSES keeps the widths it had.  Added within version 4.  Needs no GPU.  */
+ * TS_FLAG_WIDE_PASSES / TS_FLAG_NO_WIDE_PASSES keeps the widths it had.  Added within version 4.  Needs no GPU.
+ * Pass prologue: in a queue of these passes, while nothing is removed, only the query preparation of a batch is
+ * enqueued when it is submitted (it alone reads the caller's queries); its sample scan and thresholds are enqueued in
+ * front of the first pass that holds one of its groups, and a pass's sample scans, thresholds and selects share one
+ * launch each.  TS_FLAG_NO_PASS_PROLOGUE keeps every batch's own launches; a queue holds one setting, and a search
+ * that asks for the other flushes it first.  Results, reports and redo are the same.  Added within version 4.       */
 int32_t ts_coalesce_groups_stationary(int32_t dim, int32_t storage_dtype);
 
 /* ---- removal (tombstones) ------------------------------------------------

@@ -35,6 +35,7 @@ TS_FLAG_HOST_PTR, TS_FLAG_NO_FILTER, TS_FLAG_NORMALIZE, TS_FLAG_ASYNC, TS_FLAG_P
 TS_FLAG_COALESCE = 128
 TS_FLAG_WIDE_PASSES, TS_FLAG_NO_WIDE_PASSES = 256, 512
 TS_FLAG_STATIONARY_PASSES, TS_FLAG_NO_STATIONARY_PASSES = 1024, 2048
+TS_FLAG_PASS_PROLOGUE, TS_FLAG_NO_PASS_PROLOGUE = 4096, 8192
 
 # name -> (restype, argtypes); mirrors include/tristage.h one to one
 SIGNATURES = {

@@ -241,6 +241,23 @@ bool ts_scan_qstat_fits(int64_t nblk, int num_cus);
 // the kernel's LDS attribute on the current device, ahead of the first launch
 int ts_scan_qstat_prepare(const TsLayout& L);
 int ts_launch_scan_qstat(const TsLayout& L, int G, const WideScanParams& p, int num_cus, hipStream_t stream);
+// Sample mode (scan_qstat_sample_kernel): the dense scan of one strided sample of the corpus for up to 8 groups of
+// several batches at once, instead of one ts_launch_scan(SCAN_DENSE) per batch.  Group g is the query columns
+// 32 * ghalf[g] .. of the image gimg[g] (gqh[g] halves per k group); its gnq[g] valid queries write what scan_kernel's
+// dense mode writes for them, gdense[g][(32 * ghalf[g] + j) * dense_ld + w * 32 + i] for row i of work item w (row
+// block blk0 + w * blk_stride).  Same chain of MFMAs per score, so the same bits.
+struct QstatSampleParams {
+  const uint4* corpus;
+  int kg;
+  int64_t nwork, blk0, blk_stride, ntotal;
+  int64_t dense_ld;
+  const uint4* gimg[TS_MAX_WIDE_GROUPS];
+  int gqh[TS_MAX_WIDE_GROUPS];
+  int ghalf[TS_MAX_WIDE_GROUPS];
+  int gnq[TS_MAX_WIDE_GROUPS];
+  float* gdense[TS_MAX_WIDE_GROUPS];
+};
+int ts_launch_scan_qstat_sample(const TsLayout& L, int G, const QstatSampleParams& p, int num_cus, hipStream_t stream);
 
 // Tombstone passes: the coalesced passes of an index with removed rows.  live: its live words (bit
 // r % 32 of word r / 32 = row r live); each wave reads its block's word as a scalar load and its survivor epilogue
@@ -404,6 +421,28 @@ int ts_launch_select(const SelParams& p, int nq, hipStream_t stream);
 // +FLT_MAX for nq <= q < 64
 int ts_launch_tau(const float* sample, int64_t ld, uint32_t n, uint32_t m,
                   int nq, float* tau, hipStream_t stream);
+
+// Thresholds and selects of a coalesced pass in one launch each ("pass prologue"): entry b is what
+// batch b's own ts_launch_tau / ts_launch_select call would take, and gets exactly that call's results.
+#define TS_PASS_BATCHES 8   // batches with a group in one pass of 8 groups
+struct TauBatch {
+  const float* sample[TS_PASS_BATCHES];
+  int64_t ld[TS_PASS_BATCHES];
+  uint32_t n[TS_PASS_BATCHES];
+  uint32_t m[TS_PASS_BATCHES];
+  int nq[TS_PASS_BATCHES];
+  float* tau[TS_PASS_BATCHES];
+};
+// batches share a launch where this agrees (the kernel ts_launch_tau picks for m)
+int ts_tau_batch_key(uint32_t m);
+int ts_launch_tau_batch(const TauBatch& t, int nb, hipStream_t stream);
+struct SelBatch {
+  SelParams p[TS_PASS_BATCHES];   // SEL_PAIRS32
+  int nq[TS_PASS_BATCHES];
+};
+// batches share a launch where this agrees (the LDS keys ts_launch_select gives the batch)
+int ts_select_batch_key(const SelParams& p, uint32_t* lds_keys);
+int ts_launch_select_batch(const SelBatch& t, int nb, hipStream_t stream);
 
 // ---------------------------------------------------------------- range search (ts_range.hip)
 // Results in CSR form: query q of the pass owns out[off[q] .. off[q + 1]) of the call's result buffers (`capacity`

@@ -171,7 +171,13 @@ struct ts_index {
   // enqueued but whose filter scan and select wait for co_width 32-query groups to share one scan.  A held batch
   // keeps its workspace set busy until its select is enqueued.  co_mu serialises coalesced submissions and
   // flushes; it is taken before `mu`, never while `mu` is held.
-  struct CoBatch { WSet* W; int nq, qh, k, slot, groups_left; float* out_s; int64_t* out_i; };
+  // With the queue's pass prologue (co_prologue) a batch's sample scan and thresholds are not enqueued at submission
+  // but in front of the first pass that holds one of its groups (co_pass_prologue): m, S, sstride, nsb are what those
+  // launches take, tau_done marks a batch that has them, failed one whose deferred launches could not be enqueued.
+  struct CoBatch {
+    WSet* W; int nq, qh, k, slot, groups_left; float* out_s; int64_t* out_i;
+    uint32_t m; int64_t S, sstride, nsb; bool tau_done, failed;
+  };
   struct CoGroup { int batch, half; };
   std::mutex co_mu;
   int co_gmax = 0;                       // groups per LDS-resident pass (ts_coalesce_groups)
@@ -179,6 +185,8 @@ struct ts_index {
   int co_gstat = 0;                      // groups per query-stationary pass (ts_coalesce_groups_stationary)
   int co_width = 0;                      // groups per pass of the queue's pending groups (co_pass_width)
   bool co_stat_forced = false;           // the queue's last search set TS_FLAG_STATIONARY_PASSES (co_launch_pass)
+  bool co_prologue = false;              // the queue's batches get their sample scores and thresholds with their pass,
+                                         // and a pass's thresholds / selects share a launch (co_pass_prologue)
   hipStream_t co_stream = nullptr;       // the stream of the held batches
   CoBatch co_batch[TS_MAX_WIDE_GROUPS] = {};  // held batches in submission order
   int co_nbatch = 0;
@@ -1267,6 +1275,98 @@ static void co_fill_params(const ts_index* h, int G, P& mp) {
   }
 }
 
+// the dense scan of a batch's sample by scan_kernel (one launch per batch)
+static int co_sample_scan(ts_index* h, const ts_index::CoBatch& b, hipStream_t s) {
+  ScanParams sp{};
+  sp.corpus = h->corpus;
+  sp.qimg = (const uint4*)b.W->qimg.p;
+  sp.kg = h->L.kg;
+  sp.nq = b.nq;
+  sp.ntotal = h->ntotal;
+  sp.nwork = b.nsb;
+  sp.blk0 = 0;
+  sp.blk_stride = b.sstride;
+  sp.dense = (float*)b.W->sample.p;
+  sp.dense_ld = b.S;
+  return ts_launch_scan(h->L, SCAN_DENSE, b.qh, sp, h->num_cus, s);
+}
+
+// The pass prologue: every batch with a group among the G pending ones that has no thresholds yet (a
+// batch whose groups straddle two passes gets them with the first) gets its sample scores and thresholds now, on the
+// queue's stream, ahead of the filter pass.  Two batches or more: one sample-mode launch of the stationary kernel per
+// 8 groups (the sample is read once for all of them) and one threshold launch per kernel ts_launch_tau would pick; a
+// single batch keeps scan_kernel's dense scan and its own ts_launch_tau.  Every batch gets the sample buffer and so
+// the thresholds of its own launches.  On a failure the batches are marked, and reported for a redo with their pass.
+static int co_pass_prologue(ts_index* h, int G) {
+  int owed[TS_MAX_WIDE_GROUPS], no = 0;
+  for (int g = 0; g < G; ++g) {
+    const int bi = h->co_group[g].batch;
+    if (!h->co_batch[bi].tau_done && (no == 0 || owed[no - 1] != bi)) owed[no++] = bi;   // (groups are in batch order)
+  }
+  if (no == 0) return TS_OK;
+  hipStream_t s = h->co_stream;
+  int st = TS_OK;
+  if (no == 1) {
+    const ts_index::CoBatch& b = h->co_batch[owed[0]];
+    st = co_sample_scan(h, b, s);
+    if (st == TS_OK) st = ts_launch_tau((const float*)b.W->sample.p, b.S, (uint32_t)b.S, b.m, b.nq, b.W->tau(), s);
+  } else {
+    // sample scores: groups of batches with one sample geometry share a launch (in one queue they all have it)
+    QstatSampleParams sp{};
+    int ng = 0;
+    auto flush = [&]() {
+      if (ng > 0 && st == TS_OK) st = ts_launch_scan_qstat_sample(h->L, ng, sp, h->num_cus, s);
+      ng = 0;
+    };
+    for (int i = 0; i < no; ++i) {
+      const ts_index::CoBatch& b = h->co_batch[owed[i]];
+      for (int half = 0; half < b.qh; ++half) {
+        if (ng == TS_MAX_WIDE_GROUPS || (ng > 0 && (sp.nwork != b.nsb || sp.blk_stride != b.sstride || sp.dense_ld != b.S)))
+          flush();
+        if (ng == 0) {
+          sp.corpus = h->corpus;
+          sp.kg = h->L.kg;
+          sp.nwork = b.nsb;
+          sp.blk0 = 0;
+          sp.blk_stride = b.sstride;
+          sp.ntotal = h->ntotal;
+          sp.dense_ld = b.S;
+        }
+        sp.gimg[ng] = (const uint4*)b.W->qimg.p;
+        sp.gqh[ng] = b.qh;
+        sp.ghalf[ng] = half;
+        sp.gnq[ng] = std::min(32, b.nq - 32 * half);
+        sp.gdense[ng] = (float*)b.W->sample.p;
+        ++ng;
+      }
+    }
+    flush();
+    // thresholds: one launch per kernel
+    for (int key = 1; key <= 4 && st == TS_OK; key += 3) {
+      TauBatch tb{};
+      int n = 0;
+      for (int i = 0; i < no; ++i) {
+        const ts_index::CoBatch& b = h->co_batch[owed[i]];
+        if (ts_tau_batch_key(b.m) != key) continue;
+        tb.sample[n] = (const float*)b.W->sample.p;
+        tb.ld[n] = b.S;
+        tb.n[n] = (uint32_t)b.S;
+        tb.m[n] = b.m;
+        tb.nq[n] = b.nq;
+        tb.tau[n] = b.W->tau();
+        ++n;
+      }
+      if (n == 1) st = ts_launch_tau(tb.sample[0], tb.ld[0], tb.n[0], tb.m[0], tb.nq[0], tb.tau[0], s);
+      else if (n > 1) st = ts_launch_tau_batch(tb, n, s);
+    }
+  }
+  for (int i = 0; i < no; ++i) {
+    h->co_batch[owed[i]].tau_done = true;
+    h->co_batch[owed[i]].failed = st != TS_OK;
+  }
+  return st;
+}
+
 // One filter scan over the pending groups; then the select of every batch whose last group was in it.  Groups whose
 // images all fit the LDS take scan_multi_kernel, more take scan_wide_kernel, or scan_qstat_kernel in a queue of
 // query-stationary passes.  Caller holds co_mu.
@@ -1275,6 +1375,8 @@ static int co_launch_pass(ts_index* h) {
   const int G = h->co_ngroup;
   const int64_t N = h->ntotal;
   hipStream_t s = h->co_stream;
+  // the sample scores and thresholds its batches still owe (a queue with the pass prologue), ahead of the timed scan
+  int st = co_pass_prologue(h, G);
   // per-launch timing of the scan (ts_index_get_timings "filter_scan"), handed to a batch that ends in this pass
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if (h->profiling && h->co_pass_seq++ % (uint64_t)h->prof_every == 0) {
@@ -1284,7 +1386,6 @@ static int co_launch_pass(ts_index* h) {
       e0 = e1 = nullptr;
     }
   }
-  int st;
   // removed rows: the tombstone instantiations (the queue is flushed whenever removals change)
   const bool tomb = h->nremoved > 0;
   // A queue of query-stationary passes (co_pass_width): its full passes and the partial ones of 7 groups take
@@ -1292,7 +1393,9 @@ static int co_launch_pass(ts_index* h) {
   // 10 M x 768), one the LDS-resident kernel can take goes there, as in a wide queue.  With
   // TS_FLAG_STATIONARY_PASSES every pass above co_gmax groups is a stationary one (tests, A/B runs).
   const int stat_above = h->co_stat_forced ? h->co_gmax : std::max(h->co_gmax, h->co_gwide);
-  if (!tomb && h->co_gstat > 0 && h->co_width == h->co_gstat && G > stat_above) {
+  if (st != TS_OK) {
+    // no thresholds: no scan; the pass's batches are reported for a redo below
+  } else if (!tomb && h->co_gstat > 0 && h->co_width == h->co_gstat && G > stat_above) {
     // one group per wave, any G up to 8; every CU, like the wide pass
     WideScanParams wp{};
     co_fill_params(h, G, wp);
@@ -1334,37 +1437,73 @@ static int co_launch_pass(ts_index* h) {
   for (int g = 0; g < G; ++g) --h->co_batch[h->co_group[g].batch].groups_left;
   h->co_ngroup = 0;
   // the selects of the finished batches, in submission order; unfinished ones move to the front
-  int keep = 0;
+  int keep = 0, nfin = 0;
   const int nb = h->co_nbatch;
+  ts_index::CoBatch fin[TS_MAX_WIDE_GROUPS];
   for (int i = 0; i < nb; ++i) {
-    ts_index::CoBatch b = h->co_batch[i];
-    if (b.groups_left > 0) { h->co_batch[keep++] = b; continue; }
-    if (st == TS_OK) {
-      SelParams p{};
-      p.mode = SEL_PAIRS32;
-      p.scores = (const float*)b.W->cand_score.p;
-      p.ids32 = (const int32_t*)b.W->cand_id.p;
-      p.stride = kCandCap;
-      p.n_per_q = b.W->cand_cnt();
-      p.n_cap = kCandCap;
-      p.need = tomb ? 0u : (uint32_t)std::min<int64_t>(b.k, N);   // (tomb: need_check_kernel, min(k, live rows))
-      p.k = b.k;
-      p.out_scores = b.out_s;
-      p.out_ids64 = b.out_i;
-      p.out_stride = b.k;
-      p.id_offset = h->id_offset;
-      p.status = b.W->status();
-      p.clear_counts = b.W->cand_cnt();
-      p.host_report = h->host_status_dev + (size_t)b.slot * TS_SLOT_WORDS;
-      if (tomb) st = ts_launch_need_check(b.W->cand_cnt(), ((TsMaskDev*)b.W->mask.p)->need, b.nq, b.W->status(),
-                                          p.host_report, s);
-      if (st == TS_OK) st = ts_launch_select(p, b.nq, s);
+    const ts_index::CoBatch b = h->co_batch[i];
+    if (b.groups_left > 0) h->co_batch[keep++] = b;
+    else fin[nfin++] = b;
+  }
+  auto sel_params = [&](const ts_index::CoBatch& b) {
+    SelParams p{};
+    p.mode = SEL_PAIRS32;
+    p.scores = (const float*)b.W->cand_score.p;
+    p.ids32 = (const int32_t*)b.W->cand_id.p;
+    p.stride = kCandCap;
+    p.n_per_q = b.W->cand_cnt();
+    p.n_cap = kCandCap;
+    p.need = tomb ? 0u : (uint32_t)std::min<int64_t>(b.k, N);   // (tomb: need_check_kernel, min(k, live rows))
+    p.k = b.k;
+    p.out_scores = b.out_s;
+    p.out_ids64 = b.out_i;
+    p.out_stride = b.k;
+    p.id_offset = h->id_offset;
+    p.status = b.W->status();
+    p.clear_counts = b.W->cand_cnt();
+    p.host_report = h->host_status_dev + (size_t)b.slot * TS_SLOT_WORDS;
+    return p;
+  };
+  // A queue with the pass prologue: the selects of the pass in one launch (select_batch_kernel), where
+  // ts_launch_select would give the batches the same LDS; a batch that differs keeps a launch of its own below.
+  bool launched[TS_MAX_WIDE_GROUPS] = {};
+  if (h->co_prologue && !tomb && st == TS_OK && nfin >= 2) {
+    SelBatch sb{};
+    int idx[TS_MAX_WIDE_GROUPS], n = 0;
+    uint32_t key0 = 0;
+    for (int i = 0; i < nfin && st == TS_OK; ++i) {
+      if (fin[i].failed) continue;
+      const SelParams p = sel_params(fin[i]);
+      uint32_t key = 0;
+      if (ts_select_batch_key(p, &key) != TS_OK) continue;   // (its own launch reports the error)
+      if (n == 0) key0 = key;
+      if (key != key0) continue;
+      sb.p[n] = p;
+      sb.nq[n] = fin[i].nq;
+      idx[n++] = i;
+    }
+    if (n >= 2) {
+      st = ts_launch_select_batch(sb, n, s);
+      for (int j = 0; j < n; ++j) launched[idx[j]] = true;
+    }
+  }
+  for (int i = 0; i < nfin; ++i) {
+    const ts_index::CoBatch& b = fin[i];
+    bool ok = st == TS_OK && !b.failed;
+    if (ok) {
+      if (!launched[i]) {
+        const SelParams p = sel_params(b);
+        if (tomb) st = ts_launch_need_check(b.W->cand_cnt(), ((TsMaskDev*)b.W->mask.p)->need, b.nq, b.W->status(),
+                                            p.host_report, s);
+        if (st == TS_OK) st = ts_launch_select(p, b.nq, s);
+      }
       if (st == TS_OK) {
         if (hipEventRecord(b.W->ev_sel, s) == hipSuccess) b.W->used = true;   // (the set's next user waits for it)
         else { ts_set_error("hipEventRecord failed"); st = TS_ERR_HIP; }
       }
+      ok = st == TS_OK;
     }
-    if (st != TS_OK) {
+    if (!ok) {
       // nothing verifies a batch whose select is missing: finish() must report it for a redo
       h->host_status[(size_t)b.slot * TS_SLOT_WORDS + 64] = TS_STATUS_OVERFLOW;
     }
@@ -1407,13 +1546,18 @@ static int co_flush(ts_index* h, hipStream_t s) {
   return co_flush_locked(h, s);
 }
 
-// One coalesced batch of <= 64 queries: query prep, sample scan and thresholds on the caller's stream now (they
-// read the caller's queries), its groups into the pending-pass queue.  Caller holds co_mu; the stream is the queue's.
+// One coalesced batch of <= 64 queries: query prep on the caller's stream now (it reads the caller's queries), then
+// the sample scan and the thresholds, or with the queue's pass prologue neither (they read only the set's own image
+// and sample buffer: co_pass_prologue); its groups into the pending-pass queue.  Caller holds co_mu; the stream is the
+// queue's.
 static int co_submit(ts_index* h, const void* dq, int nq, int q_dtype, int k, float* out_s, int64_t* out_i,
                      hipStream_t s) {
   const int64_t N = h->ntotal;
   const int64_t nblk = (N + TS_ROWS_PER_BLOCK - 1) / TS_ROWS_PER_BLOCK;
   const int qh = nq > 32 ? 2 : 1;
+  // the pass prologue: the sample scan and the thresholds read only the set's own image and sample buffer, and go in
+  // front of the batch's first pass (co_pass_prologue)
+  const bool defer = h->co_prologue && h->nremoved == 0;
   ts_index::WSet* W = acquire_set(h);   // (at most co_width - 1 < TS_NSETS sets are held by the queue here)
   struct SetGuard {
     ts_index* h; ts_index::WSet* W;
@@ -1437,19 +1581,11 @@ static int co_submit(ts_index* h, const void* dq, int nq, int q_dtype, int k, fl
   uint32_t m = (uint32_t)((oversample * (int64_t)k * S + N - 1) / N);
   m = std::max(m, kMinSampleRank);
   TS_CHECK(ensure(W->sample, (size_t)nq * S * 4));
-  ScanParams sp{};
-  sp.corpus = h->corpus;
-  sp.qimg = (const uint4*)W->qimg.p;
-  sp.kg = h->L.kg;
-  sp.nq = nq;
-  sp.ntotal = N;
-  sp.nwork = nsb;
-  sp.blk0 = 0;
-  sp.blk_stride = sstride;
-  sp.dense = (float*)W->sample.p;
-  sp.dense_ld = S;
-  TS_CHECK(ts_launch_scan(h->L, SCAN_DENSE, qh, sp, h->num_cus, s));
-  if (h->nremoved > 0) {
+  ts_index::CoBatch cb{W, nq, qh, k, slot_guard.slot, qh, out_s, out_i, m, S, sstride, nsb, !defer, false};
+  if (!defer) TS_CHECK(co_sample_scan(h, cb, s));
+  if (defer) {
+    // (co_pass_prologue)
+  } else if (h->nremoved > 0) {
     // removed rows: the thresholds of the filtered path (tau_masked_kernel) with the live words as the
     // batch's one mask: the m_q-th best LIVE sample score with N_q = the live rows; need[q] = min(k, live rows)
     TS_CHECK(ensure(W->mask, sizeof(TsMaskDev) + (size_t)nblk * 4));
@@ -1476,7 +1612,7 @@ static int co_submit(ts_index* h, const void* dq, int nq, int q_dtype, int k, fl
     pe.fseq = -1;
     ++h->npending;
   }
-  h->co_batch[h->co_nbatch++] = ts_index::CoBatch{W, nq, qh, k, slot_guard.slot, qh, out_s, out_i};
+  h->co_batch[h->co_nbatch++] = cb;
   slot_guard.handed_over();
   set_guard.W = nullptr;   // released by co_launch_pass once its select is enqueued
   int st = TS_OK;
@@ -1545,9 +1681,12 @@ extern "C" int ts_index_search(ts_index* h, const void* queries, int32_t nq, int
     // the queue holds one stream's batches: moving it to `s` flushes it and orders `s` behind the old stream's passes
     if (h->co_stream != s) TS_CHECK(co_flush_locked(h, s));
     // and passes of one width: a search that asks for another one flushes the pending groups first
-    if (h->co_ngroup > 0 && h->co_width != width) TS_CHECK(co_flush_locked(h, s));
+    // and one setting of the pass prologue: stationary queues without removed rows, unless the search declines it
+    const bool prologue = width == h->co_gstat && h->nremoved == 0 && !(flags & TS_FLAG_NO_PASS_PROLOGUE);
+    if (h->co_ngroup > 0 && (h->co_width != width || h->co_prologue != prologue)) TS_CHECK(co_flush_locked(h, s));
     h->co_stream = s;
     h->co_width = width;
+    h->co_prologue = prologue;
     h->co_stat_forced = (flags & TS_FLAG_STATIONARY_PASSES) != 0;
     for (int q0 = 0; q0 < nq; q0 += qp) {
       const int c = std::min(qp, nq - q0);

@@ -255,6 +255,132 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_qstat_kernel(WideScanParams
   }
 }
 
+// Sample mode: the dense scan of a strided sample of the corpus for the groups of several batches at once, in place of
+// one scan_kernel dense launch per batch (coalesced passes, DESIGN.md 4.2c "pass prologue").  A sibling of
+// scan_qstat_kernel and not a template parameter of it: a shared body moved the scalar register allocation of the
+// filter form, whose instruction stream is kept as it is.  The walk is the filter form's, statement for statement: the
+// ring and its requests, the counted waits and the one barrier per block, the rolling A operands and the
+// one-accumulator MFMA chain (so a score has scan_kernel's bits).  What differs: no thresholds, no staging, no flush;
+// the LDS is the ring only, and a wave's accumulator goes to its group's lines of its batch's sample buffer as
+// epilogue_dense writes them.  Those stores share vmcnt with the ring's requests and are younger than the requests a
+// counted wait is for, so the wait only waits for more.
+template <int DT, int NWIN>
+__global__ __launch_bounds__(SCAN_THREADS) void scan_qstat_sample_kernel(QstatSampleParams p, int G, int depth) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr int KG = NWIN * TS_RING;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const bool owner = wave < G;
+  const int grid = (int)gridDim.x;
+  const int steps = (int)((p.nwork - 1 - (int64_t)blockIdx.x) / grid) + 1;
+
+  const unsigned char* corpus = reinterpret_cast<const unsigned char*>(p.corpus);
+  const size_t blk_bytes = (size_t)KG * 1024;
+  const uint32_t loff = (uint32_t)lane * 16;
+  const uint32_t ring_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)smem + (uint32_t)wave * 1024u;
+  const unsigned char* const dead = reinterpret_cast<const unsigned char*>(p.gimg[0]) + (size_t)wave * 1024;
+  auto blk_of = [&](int s) { return p.blk0 + ((int64_t)blockIdx.x + (int64_t)s * grid) * p.blk_stride; };
+  int fstep = 0, fkw = 0, fslot = 0;
+  const unsigned char* fsrc = corpus + (size_t)blk_of(0) * blk_bytes + (size_t)wave * 1024;
+  auto request = [&]() {   // (scan_qstat_kernel's: the wait states, M0)
+    const unsigned char* src = fstep < steps ? fsrc : dead;
+    const uint32_t dst = ring_lds + (uint32_t)fslot * TS_QSTAT_WINDOW;
+    uint32_t keep;
+    __asm__ volatile("s_nop 4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
+                     "global_load_lds_dwordx4 %1, %2 nt\n\ts_mov_b32 m0, %0"
+                     : "=&s"(keep) : "v"(loff), "s"(src), "s"(dst) : "memory");
+    fslot = fslot + 1 == depth ? 0 : fslot + 1;
+    if (++fkw == NWIN) {
+      fkw = 0;
+      ++fstep;
+      if (fstep < steps) fsrc = corpus + (size_t)blk_of(fstep) * blk_bytes + (size_t)wave * 1024;
+    } else {
+      fsrc += TS_QSTAT_WINDOW;
+    }
+  };
+  for (int i = 0; i < depth; ++i) request();
+
+  // ---- the wave's group: its image into registers; its valid queries and this lane's line of the sample buffer
+  const int gqh = qstat_pick(p.gqh, wave), ghalf = qstat_pick(p.ghalf, wave);
+  u32x4 q[KG];
+  int snq = 0;
+  float* sdst = nullptr;
+  if (owner) {
+    const u32x4* img = reinterpret_cast<const u32x4*>(qstat_pick(p.gimg, wave)) + (size_t)ghalf * 64 + lane;
+#pragma unroll
+    for (int i = 0; i < KG; ++i) q[i] = img[(size_t)i * gqh * 64];
+    snq = qstat_pick(p.gnq, wave);
+    sdst = qstat_pick(p.gdense, wave) + (int64_t)(ghalf * 32 + (lane & 31)) * p.dense_ld;
+  } else {
+#pragma unroll
+    for (int i = 0; i < KG; ++i) q[i] = u32x4{0u, 0u, 0u, 0u};
+  }
+#pragma unroll
+  for (int i = 0; i < KG; ++i) __asm__ volatile("" : "+v"(q[i]));
+  __builtin_amdgcn_s_waitcnt(0x3F70);   // vmcnt(0): the first depth windows have landed (this wave's pieces)
+  fs_barrier();
+
+  const int lead = depth - 2 * NWIN;
+  int slot0 = 0;
+
+  for (int s = 0; s < steps; ++s) {
+    if (owner) {
+      uint32_t woff[NWIN];
+#pragma unroll
+      for (int kw = 0; kw < NWIN; ++kw) {
+        int sl = slot0 + kw;
+        sl = sl >= depth ? sl - depth : sl;
+        woff[kw] = (uint32_t)sl * TS_QSTAT_WINDOW + loff;
+      }
+      auto a_read = [&](auto i) {
+        constexpr int I = decltype(i)::value;
+        return *reinterpret_cast<const u32x4*>(smem + woff[I / TS_RING] + (I % TS_RING) * 1024);
+      };
+      u32x4 a[TS_QSTAT_AHEAD];
+      qstat_static_for<TS_QSTAT_AHEAD>([&](auto i) { a[decltype(i)::value] = a_read(i); });
+      f32x16 acc;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+      __builtin_amdgcn_sched_barrier(0);
+      qstat_static_for<KG>([&](auto i) {
+        constexpr int I = decltype(i)::value;
+        mma_group<DT>(acc, a[I % TS_QSTAT_AHEAD], q[I]);
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (I + TS_QSTAT_AHEAD < KG) {
+          a[I % TS_QSTAT_AHEAD] = a_read(std::integral_constant<int, I + TS_QSTAT_AHEAD>{});
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      });
+      // epilogue_dense for one group: work item blockIdx.x + s * grid, rows past the corpus's end get -FLT_MAX
+      if ((lane & 31) < snq) {
+        const int64_t w = (int64_t)blockIdx.x + (int64_t)s * grid;
+        const int64_t row_base = blk_of(s) * TS_ROWS_PER_BLOCK;
+        float* dst = sdst + w * TS_ROWS_PER_BLOCK;
+#pragma unroll
+        for (int r4 = 0; r4 < 4; ++r4) {
+          const int i0 = 8 * r4 + 4 * (lane >> 5);
+          float4 v;
+          v.x = (row_base + i0 + 0 < p.ntotal) ? acc[4 * r4 + 0] : -3.402823466e38f;
+          v.y = (row_base + i0 + 1 < p.ntotal) ? acc[4 * r4 + 1] : -3.402823466e38f;
+          v.z = (row_base + i0 + 2 < p.ntotal) ? acc[4 * r4 + 2] : -3.402823466e38f;
+          v.w = (row_base + i0 + 3 < p.ntotal) ? acc[4 * r4 + 3] : -3.402823466e38f;
+          *reinterpret_cast<float4*>(dst + i0) = v;
+        }
+      }
+    }
+    // this wave's pieces of block s + 1 have landed; every wave is done reading block s
+    qstat_wait_vm(lead);
+    fs_barrier();
+#pragma unroll
+    for (int kw = 0; kw < NWIN; ++kw) request();
+    slot0 += NWIN;
+    slot0 = slot0 >= depth ? slot0 - depth : slot0;
+  }
+  // the tail's requests (never consumed) are still landing in the ring
+  __builtin_amdgcn_s_waitcnt(0x3F70);   // vmcnt(0)
+}
+
 // ---- host
 static int qstat_nwin(const TsLayout& L) {
   if (L.dtype != TS_F16 && L.dtype != TS_BF16) return 0;
@@ -286,6 +412,28 @@ bool ts_scan_qstat_fits(int64_t nblk, int num_cus) {
 }
 
 template <int DT, int NWIN>
+static int qstat_sample_t(const QstatSampleParams* p, int G, int depth, size_t lds, int grid, hipStream_t stream) {
+  void (*kern)(QstatSampleParams, int, int) = scan_qstat_sample_kernel<DT, NWIN>;
+  static TsDeviceOnce lds_attr;
+  TS_CHECK(ts_allow_max_lds(lds_attr, reinterpret_cast<const void*>(kern)));
+  if (!p) return TS_OK;   // ts_scan_qstat_prepare
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(SCAN_THREADS), lds, stream, *p, G, depth);
+  TS_HIP(hipGetLastError());
+  return TS_OK;
+}
+
+static int qstat_sample_dispatch(const TsLayout& L, const QstatSampleParams* p, int G, int depth, size_t lds, int grid,
+                                 hipStream_t stream) {
+  const int nwin = qstat_nwin(L);
+  if (L.dtype == TS_F16 && nwin == 5) return qstat_sample_t<TS_F16, 5>(p, G, depth, lds, grid, stream);
+  if (L.dtype == TS_F16 && nwin == 6) return qstat_sample_t<TS_F16, 6>(p, G, depth, lds, grid, stream);
+  if (L.dtype == TS_BF16 && nwin == 5) return qstat_sample_t<TS_BF16, 5>(p, G, depth, lds, grid, stream);
+  if (L.dtype == TS_BF16 && nwin == 6) return qstat_sample_t<TS_BF16, 6>(p, G, depth, lds, grid, stream);
+  ts_set_error("stationary sample scan: no kernel for dtype %d at dimension %d", L.dtype, L.dim);
+  return TS_ERR_UNSUPPORTED;
+}
+
+template <int DT, int NWIN>
 static int qstat_kernel_t(const WideScanParams* p, int G, int depth, size_t lds, int grid, hipStream_t stream) {
   void (*kern)(WideScanParams, int, int) = scan_qstat_kernel<DT, NWIN>;
   static TsDeviceOnce lds_attr;
@@ -309,7 +457,27 @@ static int qstat_dispatch(const TsLayout& L, const WideScanParams* p, int G, int
 
 int ts_scan_qstat_prepare(const TsLayout& L) {
   if (ts_scan_qstat_groups(L) == 0) return TS_OK;
+  TS_CHECK(qstat_sample_dispatch(L, nullptr, 0, 0, 0, 0, nullptr));
   return qstat_dispatch(L, nullptr, 0, 0, 0, 0, nullptr);
+}
+
+int ts_launch_scan_qstat_sample(const TsLayout& L, int G, const QstatSampleParams& p, int num_cus, hipStream_t stream) {
+  if (p.nwork <= 0) return TS_OK;
+  // every sampled block lies inside the corpus, every line inside its buffer (the caller sizes it nq x dense_ld)
+  bool ok = G >= 1 && G <= TS_QSTAT_GROUPS && ts_scan_qstat_groups(L) > 0 && p.kg == L.kg && p.blk_stride >= 1 &&
+            p.blk0 >= 0 && (p.blk0 + (p.nwork - 1) * p.blk_stride) * TS_ROWS_PER_BLOCK < p.ntotal &&
+            p.dense_ld >= p.nwork * TS_ROWS_PER_BLOCK && p.dense_ld % 4 == 0;
+  for (int g = 0; ok && g < G; ++g)
+    ok = p.gimg[g] && p.gdense[g] && p.gqh[g] >= 1 && p.gqh[g] <= 2 && p.ghalf[g] >= 0 && p.ghalf[g] < p.gqh[g] &&
+         p.gnq[g] >= 1 && p.gnq[g] <= 32;
+  if (!ok) {
+    ts_set_error("stationary sample scan: bad geometry for %d groups at dimension %d", G, L.dim);
+    return TS_ERR_UNSUPPORTED;
+  }
+  const int depth = qstat_depth(L);
+  const size_t lds = (size_t)depth * TS_QSTAT_WINDOW;   // the ring only
+  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(p.nwork, num_cus));
+  return qstat_sample_dispatch(L, &p, G, depth, lds, grid, stream);
 }
 
 int ts_launch_scan_qstat(const TsLayout& L, int G, const WideScanParams& p, int num_cus, hipStream_t stream) {

@@ -198,8 +198,9 @@ __device__ __forceinline__ void bitonic_desc_reg(const SelParams& p, int64_t qba
   __syncthreads();
 }
 
+// the select of query q (one workgroup): select_kernel's body, shared with select_batch_kernel
 template <int MODE>
-__global__ __launch_bounds__(SEL_THREADS) void select_kernel(SelParams p, uint32_t lds_keys) {
+__device__ __forceinline__ void select_body(const SelParams& p, uint32_t lds_keys, const int q) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   uint64_t* keys = reinterpret_cast<uint64_t*>(smem);                 // [lds_keys]
   uint64_t* outk = keys + lds_keys;                                   // [SEL_OUT_CAP]
@@ -207,7 +208,6 @@ __global__ __launch_bounds__(SEL_THREADS) void select_kernel(SelParams p, uint32
   uint32_t* hist = reinterpret_cast<uint32_t*>(ties + (MODE == SEL_MERGE64 ? SEL_TIE_CAP : 0));
   uint32_t* sh = hist + 256;   // [8]
   uint32_t* wtot = sh + 8;     // [4]
-  const int q = blockIdx.x;
   const int tid = threadIdx.x;
   const int64_t qbase = (int64_t)q * p.stride;
 
@@ -464,8 +464,21 @@ __global__ __launch_bounds__(SEL_THREADS) void select_kernel(SelParams p, uint32
 }
 
 template <int MODE>
-static int launch_select_t(const SelParams& p, int nq, hipStream_t stream) {
-  // LDS: enough 64-bit keys for the entries (or for k when radix-selecting in global)
+__global__ __launch_bounds__(SEL_THREADS) void select_kernel(SelParams p, uint32_t lds_keys) {
+  select_body<MODE>(p, lds_keys, blockIdx.x);
+}
+
+// The selects of several batches in one launch (coalesced passes, ts_launch_select_batch): workgroup (q, b) is
+// workgroup q of batch b's own select_kernel launch; one beyond its batch's queries exits.
+template <int MODE>
+__global__ __launch_bounds__(SEL_THREADS) void select_batch_kernel(SelBatch t, uint32_t lds_keys) {
+  const int b = blockIdx.y;
+  if ((int)blockIdx.x >= t.nq[b]) return;
+  select_body<MODE>(t.p[b], lds_keys, blockIdx.x);
+}
+
+// LDS of a select: enough 64-bit keys for the entries (or for k when radix-selecting in global)
+static int select_lds_keys(const SelParams& p, uint32_t* out) {
   uint32_t nmax = p.n_per_q ? p.n_cap : p.n;
   uint32_t need = nmax;
   const uint32_t lds_cap = TS_SEL_LDS_KEYS;
@@ -482,8 +495,20 @@ static int launch_select_t(const SelParams& p, int nq, hipStream_t stream) {
     lds_keys = 2;
     while (lds_keys < kk) lds_keys <<= 1;
   }
-  const size_t lds = ((size_t)lds_keys + SEL_OUT_CAP + (MODE == SEL_MERGE64 ? SEL_TIE_CAP : 0)) * 8 +
-                     (256 + 8 + 4) * 4;
+  *out = lds_keys;
+  return TS_OK;
+}
+
+template <int MODE>
+static size_t select_lds_bytes(uint32_t lds_keys) {
+  return ((size_t)lds_keys + SEL_OUT_CAP + (MODE == SEL_MERGE64 ? SEL_TIE_CAP : 0)) * 8 + (256 + 8 + 4) * 4;
+}
+
+template <int MODE>
+static int launch_select_t(const SelParams& p, int nq, hipStream_t stream) {
+  uint32_t lds_keys = 0;
+  TS_CHECK(select_lds_keys(p, &lds_keys));
+  const size_t lds = select_lds_bytes<MODE>(lds_keys);
   auto kern = select_kernel<MODE>;
   static TsDeviceOnce lds_attr;  // per instantiation, per device (ts_common.h)
   TS_CHECK(ts_allow_max_lds(lds_attr, reinterpret_cast<const void*>(kern)));
@@ -503,6 +528,32 @@ int ts_launch_select(const SelParams& p, int nq, hipStream_t stream) {
   return TS_ERR_INVALID;
 }
 
+int ts_select_batch_key(const SelParams& p, uint32_t* lds_keys) { return select_lds_keys(p, lds_keys); }
+
+int ts_launch_select_batch(const SelBatch& t, int nb, hipStream_t stream) {
+  if (nb <= 0) return TS_OK;
+  if (nb > TS_PASS_BATCHES) { ts_set_error("select: %d batches in one launch", nb); return TS_ERR_INVALID; }
+  uint32_t lds_keys = 0;
+  TS_CHECK(select_lds_keys(t.p[0], &lds_keys));
+  int nq = 0;
+  for (int b = 0; b < nb; ++b) {
+    uint32_t kb = 0;
+    TS_CHECK(select_lds_keys(t.p[b], &kb));
+    if (t.p[b].mode != SEL_PAIRS32 || kb != lds_keys || t.p[b].k <= 0 || t.nq[b] <= 0 || t.nq[b] > TS_MAX_Q) {
+      ts_set_error("select: batches of one launch need one mode and one LDS size");
+      return TS_ERR_INVALID;
+    }
+    nq = t.nq[b] > nq ? t.nq[b] : nq;
+  }
+  auto kern = select_batch_kernel<SEL_PAIRS32>;
+  static TsDeviceOnce lds_attr;
+  TS_CHECK(ts_allow_max_lds(lds_attr, reinterpret_cast<const void*>(kern)));
+  hipLaunchKernelGGL(kern, dim3(nq, nb), dim3(SEL_THREADS), select_lds_bytes<SEL_PAIRS32>(lds_keys), stream, t,
+                     lds_keys);
+  TS_HIP(hipGetLastError());
+  return TS_OK;
+}
+
 // ------------------------------------------------------------------ tau
 // Per-query threshold from the dense sample scores: roughly the m-th largest.
 // Every thread keeps the KEEP largest keys of its share; the m-th largest of
@@ -512,11 +563,9 @@ int ts_launch_select(const SelParams& p, int nq, hipStream_t stream) {
 // The exactness of the search never depends on this value (ts_index.hip
 // verifies the candidate counts).
 template <int KEEP>
-__global__ __launch_bounds__(SEL_THREADS) void tau_kernel(const float* sample, int64_t ld,
-                                                          uint32_t n, uint32_t m, int nq,
-                                                          float* tau) {
+__device__ __forceinline__ void tau_body(const float* sample, int64_t ld, uint32_t n, uint32_t m, int nq,
+                                         float* tau, const int q) {
   __shared__ __attribute__((aligned(16))) uint32_t keys[KEEP * SEL_THREADS];
-  const int q = blockIdx.x;
   const int tid = threadIdx.x;
   if (q >= nq) {
     if (tid == 0) tau[q] = 3.402823466e38f;
@@ -609,10 +658,55 @@ __global__ __launch_bounds__(SEL_THREADS) void tau_kernel(const float* sample, i
   }
 }
 
+template <int KEEP>
+__global__ __launch_bounds__(SEL_THREADS) void tau_kernel(const float* sample, int64_t ld,
+                                                          uint32_t n, uint32_t m, int nq,
+                                                          float* tau) {
+  tau_body<KEEP>(sample, ld, n, m, nq, tau, blockIdx.x);
+}
+
+// a[b] for a workgroup-uniform b, without a dynamically indexed kernel argument
+template <class T>
+__device__ __forceinline__ T tau_pick(const T (&a)[TS_PASS_BATCHES], int b) {
+  T r = a[0];
+#pragma unroll
+  for (int i = 1; i < TS_PASS_BATCHES; ++i) r = (b == i) ? a[i] : r;
+  return r;
+}
+
+// The thresholds of several batches in one launch (coalesced passes, ts_launch_tau_batch): workgroup (q, b) is
+// workgroup q of batch b's own tau_kernel launch.
+template <int KEEP>
+__global__ __launch_bounds__(SEL_THREADS) void tau_batch_kernel(TauBatch t) {
+  const int b = blockIdx.y;
+  tau_body<KEEP>(tau_pick(t.sample, b), tau_pick(t.ld, b), tau_pick(t.n, b), tau_pick(t.m, b), tau_pick(t.nq, b),
+                 tau_pick(t.tau, b), blockIdx.x);
+}
+
+// one key per thread is enough while the wanted rank is far below 1024
+static int tau_keep(uint32_t m) { return m <= 64 ? 1 : 4; }
+
+int ts_tau_batch_key(uint32_t m) { return tau_keep(m); }
+
+int ts_launch_tau_batch(const TauBatch& t, int nb, hipStream_t stream) {
+  if (nb <= 0) return TS_OK;
+  if (nb > TS_PASS_BATCHES) { ts_set_error("thresholds: %d batches in one launch", nb); return TS_ERR_INVALID; }
+  for (int b = 1; b < nb; ++b)
+    if (tau_keep(t.m[b]) != tau_keep(t.m[0])) {
+      ts_set_error("thresholds: batches of one launch need one kernel");
+      return TS_ERR_INVALID;
+    }
+  if (tau_keep(t.m[0]) == 1)
+    hipLaunchKernelGGL(tau_batch_kernel<1>, dim3(TS_MAX_Q, nb), dim3(SEL_THREADS), 0, stream, t);
+  else
+    hipLaunchKernelGGL(tau_batch_kernel<4>, dim3(TS_MAX_Q, nb), dim3(SEL_THREADS), 0, stream, t);
+  TS_HIP(hipGetLastError());
+  return TS_OK;
+}
+
 int ts_launch_tau(const float* sample, int64_t ld, uint32_t n, uint32_t m, int nq, float* tau,
                   hipStream_t stream) {
-  // one key per thread is enough while the wanted rank is far below 1024
-  if (m <= 64)
+  if (tau_keep(m) == 1)
     hipLaunchKernelGGL(tau_kernel<1>, dim3(TS_MAX_Q), dim3(SEL_THREADS), 0, stream, sample, ld, n,
                        m, nq, tau);
   else

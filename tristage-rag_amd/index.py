@@ -102,6 +102,17 @@ def stationary_pass_flags(stationary_passes) -> int:
     raise ValueError(f"stationary_passes must be 'auto', True or False, not {stationary_passes!r}")
 
 
+def pass_prologue_flags(pass_prologue) -> int:
+    """Search flags of FlatIPIndex.pass_prologue: "auto" (the library's policy), True / False (forced on / off)."""
+    if pass_prologue is True:
+        return _lib.TS_FLAG_PASS_PROLOGUE
+    if pass_prologue is False:
+        return _lib.TS_FLAG_NO_PASS_PROLOGUE
+    if isinstance(pass_prologue, str) and pass_prologue == "auto":
+        return 0
+    raise ValueError(f"pass_prologue must be 'auto', True or False, not {pass_prologue!r}")
+
+
 def _addr(x) -> Optional[int]:
     """The address of a numpy array or a tensor; None (a NULL pointer) for None.  Every ``c_void_p`` parameter of
     ``_lib.SIGNATURES`` takes it as it is.  Call it in the statement of the library call that consumes the address, so
@@ -577,6 +588,10 @@ class FlatIPIndex(_IndexBase):
         # coalesced passes of ts_coalesce_groups_stationary() groups (8 at 512 < d <= 768, f16 / bf16): "auto" wherever
         # "auto" wide passes would run and nothing is removed, True / False to force them on / off (tests, A/B runs)
         self.stationary_passes = "auto"
+        # in a queue of stationary passes with nothing removed: sample scans and thresholds enqueued with the pass, one
+        # launch each per pass for sample scans, thresholds and selects.  "auto" / True: wherever that applies; False:
+        # every batch keeps launches of its own (tests, A/B runs).  Results are identical
+        self.pass_prologue = "auto"
         self._filter_info = None  # set by finish() when it redid a filtered search: the counters of what was submitted
 
     # -- FAISS duck type --------------------------------------------------
@@ -728,6 +743,7 @@ class FlatIPIndex(_IndexBase):
                     flags |= _lib.TS_FLAG_COALESCE
                     flags |= wide_pass_flags(self.wide_passes)
                     flags |= stationary_pass_flags(self.stationary_passes)
+                    flags |= pass_prologue_flags(self.pass_prologue)
             self._search_raw(q, q_dtype, k, D, I, flags, stream)
         else:   # (ts_index_search_filtered resets the counters last_filter_info() reads, and never coalesces)
             self._filter_info = None   # last_filter_info() reads the library's counters of this call again
