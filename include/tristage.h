@@ -74,7 +74,8 @@ extern "C" {
  * and ts_index_range_fetch: no existing signature changed, and a caller that never runs a range search sees the
  * library it was built against (no existing kernel changed).  So was e4m3 index storage (ts_index_create accepts
  * TS_FP8_E4M3; ts_index_set_fp8_scale_log2, ts_index_fp8_scale_log2): no existing signature changed, and an index of
- * another storage dtype runs the kernels it ran before.  So were ts_index_mmr, ts_mmr_ivf and the measurement aid
+ * another storage dtype runs the kernels it ran before.  So was 4-bit MX index storage (ts_index_create accepts
+ * TS_MXFP4_E2M1): no signature changed. So were ts_index_mmr, ts_mmr_ivf and the measurement aid
  * ts_index_mmr_set_timing / ts_index_mmr_get_timings: no existing signature or kernel changed, and a caller that
  * never calls them allocates and launches nothing new.  So was ts_group_topk, on the same terms.  So were
  * ts_maxsim_passages_indexed and ts_maxsim_passages_indexed_batch, on the same terms.  So were ts_index_search_prefix
@@ -97,7 +98,9 @@ enum ts_status {
 
 enum ts_dtype { TS_F32 = 0, TS_F16 = 1, TS_BF16 = 2,
                TS_FP8_E4M3 = 3 /* OCP e4m3fn: a storage dtype of ts_index_create ("e4m3 index storage" below) and the
-                                  element type of the e4m3 token-store entry points; never a rows / query dtype */ };
+                                  element type of the e4m3 token-store entry points; never a rows / query dtype */,
+               TS_MXFP4_E2M1 = 4 /* OCP e2m1 elements with one E8M0 scale per 32: a storage dtype of ts_index_create only
+                                    ("4-bit MX index storage" below); never a rows / query / store dtype */ };
 
 enum ts_metric { TS_METRIC_INNER_PRODUCT = 0 };
 
@@ -144,7 +147,8 @@ enum ts_metric { TS_METRIC_INNER_PRODUCT = 0 };
  * replaces faiss.IndexFlatIP(d) (reference src/stage1_retriever.py:263,276).
  * storage_dtype: element type the corpus is kept in (TS_F32 = FAISS-exact
  * storage; TS_F16 / TS_BF16 halve the bytes scanned; TS_FP8_E4M3 halves them
- * again, see "e4m3 index storage" below).                                    */
+ * again, see "e4m3 index storage" below; TS_MXFP4_E2M1 once more, see
+ * "4-bit MX index storage").                                                 */
 int ts_index_create(int32_t dim, int32_t storage_dtype, int32_t metric,
                     int32_t device, ts_index** out);
 int ts_index_destroy(ts_index* h);
@@ -478,6 +482,21 @@ int ts_index_search_biased(ts_index* h, const void* queries, int32_t nq, int32_t
                            const int32_t* mask_of_query, float* out_scores, int64_t* out_ids, uint32_t flags,
                            void* hip_stream);
 int ts_index_last_bias_info(const ts_index* h, int64_t info[4]);
+
+/* ---- 4-bit MX index storage (TS_MXFP4_E2M1) -----------------------------------------------------
+ * Half a byte per element plus one scale byte per 32 elements, scored in place.  A row is zero-padded to a multiple
+ * of 64 dimensions; scale block (g, h), h = 0/1, holds the 32 dimensions k = 64 g + 16 m + 8 h + j (m = 0..3,
+ * j = 0..7).  With amax the block's largest |x| (NaN counts as 0, +-Inf as +-FLT_MAX; with TS_FLAG_NORMALIZE x is the
+ * f32 quotient x / (|x| + 1e-8)): e = 0 if amax == 0, else floor(log2 amax) - 2, plus 1 if amax > 6 * 2^e, clamped to
+ * -100 .. 100; the scale byte is e + 127.  An element is its sign bit and the index of the value of
+ * {0, 0.5, 1, 1.5, 2, 3, 4, 6} nearest to |x| / 2^e (ties to the even index).  It decodes to sign * grid * 2^e, exact
+ * in bf16.  Queries are rounded to bf16 whatever their dtype; a score equals, bit for bit, that of a TS_BF16 index
+ * holding the decoded rows, and ts_index_reconstruct returns the decoded rows.  dim is at most 2048 (64-query passes up
+ * to 1024).
+ * Supported: add, reserve, reset, id offset, reconstruct, search (synchronous, asynchronous), search_filtered, scores,
+ * grouped search, remove, compact, update.  TS_FLAG_ONE_LAUNCH, TS_FLAG_PIPELINE, TS_FLAG_COALESCE and the wide-pass
+ * flags are ignored (ts_coalesce_groups* return 0 for it).  TS_ERR_UNSUPPORTED: range search, prefix search, rescore,
+ * funnel search, boosted search, MMR; there is no IVF form.                                                        */
 /* row-shard support: ids reported by search = local row + offset            */
 int ts_index_set_id_offset(ts_index* h, int64_t offset);
 /* copy rows [row0, row0+n) back out as row-major float32 (host or device):

@@ -17,7 +17,7 @@ CSRC_DIR = os.path.join(_HERE, "csrc")
 
 TS_OK = 0
 TS_ERR_INVALID, TS_ERR_HIP, TS_ERR_OOM, TS_ERR_EMPTY, TS_ERR_UNSUPPORTED = -1, -2, -3, -4, -5
-TS_F32, TS_F16, TS_BF16, TS_FP8_E4M3 = 0, 1, 2, 3
+TS_F32, TS_F16, TS_BF16, TS_FP8_E4M3, TS_MXFP4_E2M1 = 0, 1, 2, 3, 4
 TS_METRIC_INNER_PRODUCT = 0
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "tristage.h")
 

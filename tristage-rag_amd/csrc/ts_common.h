@@ -80,6 +80,11 @@ static inline int ts_allow_max_lds(TsDeviceOnce& o, const void* kernel) {
 //   e4m3:     the unit holds 16 elements, k = 32*g + 16*m + 8*h + j   (m = 0/1, j = 0..7): bytes 0-7 and 8-15
 //             are, once converted to bf16, the A fragments of k steps 2g and 2g+1 of the 16-bit map
 //             (ts_scan_fp8.hip); its Q image is the bf16 image of the same padded dimension
+//   mxfp4:    a row block is NS scale units, then NG code units (KG = NS + NG, NG = dpad / 64, NS = ceil(NG / 16)).
+//             Code unit g holds 32 e2m1 nibbles, k = 64*g + 16*m + 8*h + j (m = 0..3, j = 0..7; nibble j of dword m):
+//             dword m, once converted to bf16, is the A fragment of k step 4g + m of the 16-bit map.  Byte g % 16 of
+//             the lane's unit in scale unit g / 16 is the E8M0 scale of those 32 elements (ts_scan_fp4.hip,
+//             DESIGN.md 4.23); its Q image is the bf16 image of the same padded dimension
 //
 // The query batch is laid out the same way (the "Q image"): unit index
 // (g*QH + hq)*64 + l holds, for query 32*hq + (l & 31), the same k's.
@@ -97,12 +102,15 @@ struct TsLayout {
   int epl;     // elements per lane per group (8 or 4)
   int gk;      // k values covered by one group (16 or 8)
   int dim;     // logical dimension
-  int dpad;    // padded dimension (multiple of gk*TS_RING: 128 for 16-bit storage, 256 for e4m3)
-  int kg;      // groups per row block = dpad / gk
-  int qkg;     // 1 KiB units of the Q image per 32 queries: kg, or 2 * kg for e4m3 storage (a bf16 image)
+  int dpad;    // padded dimension (multiple of gk*TS_RING: 128 for 16-bit storage, 256 for e4m3 and mxfp4)
+  int kg;      // 1 KiB units per row block = dpad / gk (mxfp4: plus the scale units at its head)
+  int qkg;     // 1 KiB units of the Q image per 32 queries: kg, or that of a bf16 image for e4m3 and mxfp4 storage
   int fp8_scale_log2;   // e4m3 storage: element x is stored as e4m3(x * 2^s) (ts_index_set_fp8_scale_log2)
 };
 
+// (A translation unit with a ring depth of its own, ts_scan_fp4.hip, defines TS_NO_LAYOUT_BUILDER: the padding below
+// depends on TS_RING, so such a unit takes the layouts it is handed and cannot build one that disagrees.)
+#ifndef TS_NO_LAYOUT_BUILDER
 static inline TsLayout ts_make_layout(int dim, int dtype) {
   TsLayout L;
   L.dtype = dtype;
@@ -115,8 +123,20 @@ static inline TsLayout ts_make_layout(int dim, int dtype) {
   L.kg = L.dpad / L.gk;
   L.qkg = (dtype == TS_FP8_E4M3) ? 2 * L.kg : L.kg;
   L.fp8_scale_log2 = 8;
+  if (dtype == TS_MXFP4_E2M1) {
+    // 64 elements per lane pair and code unit; a ring of four code units (ts_scan_fp4.hip), so dpad % 256 == 0 and
+    // d = 768 keeps its 12 code units; the scale units at the head of the row block count as groups of it
+    L.esize = 1;   // (unused: two elements per byte)
+    L.epl = 32;
+    L.gk = 64;
+    L.dpad = ((dim + 255) / 256) * 256;
+    const int ng = L.dpad / 64;
+    L.kg = ng + (ng + 15) / 16;
+    L.qkg = 4 * ng;
+  }
   return L;
 }
+#endif
 
 static inline size_t ts_block_bytes(const TsLayout& L) {
   return (size_t)L.kg * 1024;  // 32 rows * dpad * esize
@@ -333,6 +353,22 @@ int ts_launch_relayout_fp8(const TsLayout& L, const void* rows, int in_dtype, in
 int ts_launch_row_den(const void* rows, int in_dtype, int64_t n, int dim, float* den, hipStream_t stream);
 int ts_launch_reconstruct_fp8(const TsLayout& L, const uint4* tiled, int64_t row0, int64_t n, float* out,
                               hipStream_t stream);
+// 4-bit MX storage (ts_scan_fp4.hip): the same set for TS_MXFP4_E2M1, whose Q image is the plain bf16
+// image.  ts_launch_update_rows hands its layout to ts_launch_update_rows_fp4 (a row block of it is not a multiple of
+// TS_RING units).
+static inline int ts_fp4_code_groups(const TsLayout& L) { return L.dpad / 64; }
+static inline int ts_fp4_scale_units(const TsLayout& L) { return L.kg - L.dpad / 64; }
+size_t ts_scan_fp4_lds_bytes(const TsLayout& L, int qh);
+int ts_launch_scan_fp4(const TsLayout& L, int mode, int qh, const ScanParams& p, int num_cus, hipStream_t stream);
+int ts_launch_scan_masked_fp4(const TsLayout& L, int qh, const MaskedScanParams& p, int num_cus, hipStream_t stream);
+int ts_launch_qprep_fp4(const TsLayout& L, const void* q, int q_dtype, int nq, int qh, uint4* qimg, uint32_t* cand_cnt,
+                        uint32_t* status, hipStream_t stream);
+int ts_launch_relayout_fp4(const TsLayout& L, const void* rows, int in_dtype, int64_t n, int64_t row0, uint4* tiled,
+                           bool normalize, float* den_scratch, hipStream_t stream);
+int ts_launch_reconstruct_fp4(const TsLayout& L, const uint4* tiled, int64_t row0, int64_t n, float* out,
+                              hipStream_t stream);
+int ts_launch_update_rows_fp4(const TsLayout& L, const uint4* stage, uint4* corpus, const int32_t* blk,
+                              const int32_t* first, const int32_t* item, int64_t n_entries, hipStream_t stream);
 
 // rows [n, dim] (row-major, in_dtype) -> tiled storage at rows [row0, row0+n)
 int ts_launch_relayout(const TsLayout& L, const void* rows, int in_dtype,

@@ -303,7 +303,7 @@ extern "C" int ts_index_create(int32_t dim, int32_t storage_dtype, int32_t metri
   *out = nullptr;
   if (dim <= 0 || dim > 65536) { ts_set_error("bad dim %d", dim); return TS_ERR_INVALID; }
   if (storage_dtype != TS_F32 && storage_dtype != TS_F16 && storage_dtype != TS_BF16 &&
-      storage_dtype != TS_FP8_E4M3) {
+      storage_dtype != TS_FP8_E4M3 && storage_dtype != TS_MXFP4_E2M1) {
     ts_set_error("bad storage dtype %d", storage_dtype);
     return TS_ERR_INVALID;
   }
@@ -318,6 +318,10 @@ extern "C" int ts_index_create(int32_t dim, int32_t storage_dtype, int32_t metri
     return TS_ERR_INVALID;
   }
   TsLayout L = ts_make_layout(dim, storage_dtype);
+  if (storage_dtype == TS_MXFP4_E2M1 && dim > 2048) {   // (32 scale bytes per lane: two scale units, ts_scan_fp4.hip)
+    ts_set_error("dim %d exceeds the 2048 dimensions of 4-bit MX (mxfp4) storage", dim);
+    return TS_ERR_UNSUPPORTED;
+  }
   if (ts_scan_lds_bytes(L, 1) > 160 * 1024) {
     ts_set_error("dim %d with dtype %d needs %zu bytes of LDS for 32 queries (max 163840)", dim,
                  storage_dtype, ts_scan_lds_bytes(L, 1));
@@ -880,8 +884,8 @@ static int search_pass_on(ts_index* h, ts_index::WSet& W, const void* dq, int nq
     std::lock_guard<std::mutex> lk(h->mu);
     fseq = h->fseq;
   }
-  if (h->L.dtype == TS_FP8_E4M3 || pkg) {
-    // e4m3 storage and the prefix scans have the five-launch kernels only (ts_scan_fp8.hip, ts_scan_prefix.hip): as
+  if (h->L.dtype == TS_FP8_E4M3 || h->L.dtype == TS_MXFP4_E2M1 || pkg) {
+    // e4m3 and 4-bit MX storage and the prefix scans have the five-launch kernels only (ts_scan_fp8.hip, ts_scan_prefix.hip): as
     // for a masked pass
     flags &= ~(uint32_t)(TS_FLAG_ONE_LAUNCH | TS_FLAG_PIPELINE);
     flags |= TS_FLAG_CLASSIC;
@@ -1895,6 +1899,7 @@ constexpr size_t kRescoreScratchCap = 384u << 20;    // candidate tiles, scores 
 
 static int funnel_storage_ok(const ts_index* h, const char* what) {
   if (h->L.dtype == TS_F16 || h->L.dtype == TS_BF16) return TS_OK;
+  if (h->L.dtype == TS_MXFP4_E2M1) { ts_set_error("%s is not supported on a 4-bit MX (mxfp4) index", what); return TS_ERR_UNSUPPORTED; }
   ts_set_error("%s takes f16 / bf16 storage only", what);
   return TS_ERR_UNSUPPORTED;
 }
@@ -2365,6 +2370,10 @@ extern "C" int ts_index_range_search(ts_index* h, const void* queries, int32_t n
   if (!h) { ts_set_error("null handle"); return TS_ERR_INVALID; }
   if (h->L.dtype == TS_FP8_E4M3) {
     ts_set_error("range_search is not supported on an e4m3 (fp8) index");
+    return TS_ERR_UNSUPPORTED;
+  }
+  if (h->L.dtype == TS_MXFP4_E2M1) {
+    ts_set_error("range_search is not supported on a 4-bit MX (mxfp4) index");
     return TS_ERR_UNSUPPORTED;
   }
   const int64_t N = h->ntotal;

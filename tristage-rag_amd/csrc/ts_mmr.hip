@@ -313,6 +313,10 @@ int ts_mmr_run(const TsMmrSource& src, TsMmrWork& w, const int64_t* cand_ids, co
                int32_t C, int32_t k, float lambda, float* out_rel, int64_t* out_ids, uint32_t flags,
                hipStream_t s) {
   const TsLayout& L = src.L;
+  if (L.dtype == TS_MXFP4_E2M1) {
+    ts_set_error("mmr is not supported on a 4-bit MX (mxfp4) index");
+    return TS_ERR_UNSUPPORTED;
+  }
   const bool host = (flags & TS_FLAG_HOST_PTR) != 0;
   const size_t n_in = (size_t)nq * C, n_out = (size_t)nq * k;
   if (host) {   // the ids are readable here: an id that is neither padding nor a row of the index fails the call

@@ -877,6 +877,7 @@ bool ts_use_f32_split(const TsLayout& L, int qh) {
 
 size_t ts_scan_lds_bytes(const TsLayout& L, int qh) {
   if (L.dtype == TS_FP8_E4M3) return ts_scan_fp8_lds_bytes(L, qh);
+  if (L.dtype == TS_MXFP4_E2M1) return ts_scan_fp4_lds_bytes(L, qh);
   if (ts_use_f32_split(L, qh)) return ts_scan_f32s_lds_bytes(L);
   return (size_t)L.kg * qh * 1024 + sizeof(StageLds);
 }
@@ -909,6 +910,7 @@ static int launch_scan_masked_t(const TsLayout& L, const MaskedScanParams& p, in
 int ts_launch_scan_masked(const TsLayout& L, int qh, const MaskedScanParams& p, int num_cus, hipStream_t stream) {
   if (p.nwork <= 0) return TS_OK;
   if (L.dtype == TS_FP8_E4M3) return ts_launch_scan_masked_fp8(L, qh, p, num_cus, stream);
+  if (L.dtype == TS_MXFP4_E2M1) return ts_launch_scan_masked_fp4(L, qh, p, num_cus, stream);
   if (ts_scan_lds_bytes(L, qh) > 160 * 1024) {
     ts_set_error("dimension %d too large for the LDS-resident query image", L.dim);
     return TS_ERR_UNSUPPORTED;
@@ -938,6 +940,7 @@ int ts_launch_scan(const TsLayout& L, int mode, int qh, const ScanParams& p,
                    int num_cus, hipStream_t stream) {
   if (p.nwork <= 0) return TS_OK;
   if (L.dtype == TS_FP8_E4M3) return ts_launch_scan_fp8(L, mode, qh, p, num_cus, stream);
+  if (L.dtype == TS_MXFP4_E2M1) return ts_launch_scan_fp4(L, mode, qh, p, num_cus, stream);
   if (ts_use_f32_split(L, qh)) return ts_launch_scan_f32s(L, mode, p, num_cus, stream);
   if (ts_scan_lds_bytes(L, qh) > 160 * 1024) {
     ts_set_error("dimension %d too large for the LDS-resident query image", L.dim);
@@ -1119,6 +1122,8 @@ int ts_launch_relayout(const TsLayout& L, const void* rows, int in_dtype, int64_
   if (n <= 0) return TS_OK;
   if (L.dtype == TS_FP8_E4M3)
     return ts_launch_relayout_fp8(L, rows, in_dtype, n, row0, tiled, normalize, den_scratch, stream);
+  if (L.dtype == TS_MXFP4_E2M1)
+    return ts_launch_relayout_fp4(L, rows, in_dtype, n, row0, tiled, normalize, den_scratch, stream);
   switch (in_dtype) {
     case TS_F32: return relayout_t<float>(L, (const float*)rows, n, row0, tiled, normalize, den_scratch, stream);
     case TS_F16: return relayout_t<_Float16>(L, (const _Float16*)rows, n, row0, tiled, normalize, den_scratch, stream);
@@ -1165,6 +1170,7 @@ int ts_launch_reconstruct(const TsLayout& L, const uint4* tiled, int64_t row0,
                           int64_t n, float* out, hipStream_t stream) {
   if (n <= 0) return TS_OK;
   if (L.dtype == TS_FP8_E4M3) return ts_launch_reconstruct_fp8(L, tiled, row0, n, out, stream);
+  if (L.dtype == TS_MXFP4_E2M1) return ts_launch_reconstruct_fp4(L, tiled, row0, n, out, stream);
   const int64_t total = n * L.kg * 2;
   const int64_t blocks = (total + 255) / 256;
   if (blocks > 0x7fffffffLL) {
@@ -1216,6 +1222,7 @@ int ts_launch_qprep(const TsLayout& L, const void* q, int q_dtype, int nq, int q
                     uint4* qimg, uint32_t* cand_cnt, uint32_t* status,
                     hipStream_t stream) {
   if (L.dtype == TS_FP8_E4M3) return ts_launch_qprep_fp8(L, q, q_dtype, nq, qh, qimg, cand_cnt, status, stream);
+  if (L.dtype == TS_MXFP4_E2M1) return ts_launch_qprep_fp4(L, q, q_dtype, nq, qh, qimg, cand_cnt, status, stream);
   if (ts_use_f32_split(L, qh)) return ts_launch_qprep_f32s(L, q, q_dtype, nq, qimg, cand_cnt, status, stream);
   const int units = L.kg * qh * 64;
   const int blocks = (units + 255) / 256;

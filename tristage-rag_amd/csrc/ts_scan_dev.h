@@ -213,6 +213,14 @@ __device__ __forceinline__ void flush_stage(const ScanParams& p, SL* st, int tid
 //   kBiased                  a masked walk that also carries the per-row bias of the current row block (WalkLiveBias,
 //                            ts_scan_bias.hip): bias_init / bias_fetch / bias_advance beside the mask hooks, and an
 //                            epilogue of its own that tests and stages score + bias
+// OP::kScaled (optional; OpFp4 of ts_scan_fp4.hip, which needs TS_RING == 4): ring slots carry block-scaled elements
+// whose scale bytes lie in units just before the row block's ring units.  scale_fetch(blk_ptr, kg, sc) requests a
+// lane's scale bytes of a row block: for the first block just before its first ring loads, for the next one beside the
+// mask words just before the tail's loads, unpredicated, so it is complete before that block's first slot is (vmcnt
+// retires in order).  scale_word(sc, g0) picks the bytes of ring turn g0 .. g0 + 3 and step_scaled takes them.
+
+template <class OP, class = void> struct ScanOpScaled { static constexpr bool value = false; };
+template <class OP> struct ScanOpScaled<OP, decltype((void)OP::kScaled)> { static constexpr bool value = OP::kScaled; };
 
 // 16-bit storage and the exact-f32 MFMA: one slot, one MFMA group per query half
 template <int DT>
@@ -324,6 +332,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_kernel(typename WALK::Param
   typedef typename OP::Stage Stage;
   constexpr bool MASKED = WALK::kMasked && MODE == SCAN_FILTER;
   constexpr bool BIASED = MASKED && WALK::kBiased;
+  constexpr bool SCALED = ScanOpScaled<OP>::value;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   u32x4* qlds = reinterpret_cast<u32x4*>(smem);
   const int tid = threadIdx.x;
@@ -342,7 +351,13 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_kernel(typename WALK::Param
   int64_t blk = active ? WALK::block(p, w) : WALK::idle(p);
   const u32x4* cur = base + (size_t)blk * blk_units;
   u32x4 ring[TS_RING];
+  // the scale bytes of a scaled op: the current row block's, the next one's, the ring turn's.  The first block's are
+  // requested ahead of its ring loads, as every later block's are: a request younger than the ring would make the
+  // first use of them a wait for the whole ring, in every row block (the waits of a loop are those of its worst entry)
+  u32x4 sc[2], scn[2];
+  uint32_t sw = 0;
   if (active) {
+    if constexpr (SCALED) OP::scale_fetch(cur, kg, sc);
 #pragma unroll
     for (int i = 0; i < TS_RING; ++i) ring[i] = stream_load(cur + (size_t)i * 64);
   }
@@ -390,9 +405,11 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_kernel(typename WALK::Param
       // main part: prefetch stays inside the current row block
       int g0 = 0;
       for (; g0 < kg - TS_RING; g0 += TS_RING) {
+        if constexpr (SCALED) sw = OP::scale_word(sc, g0);
 #pragma unroll
         for (int i = 0; i < TS_RING; ++i) {
-          OP::template step<QH>(acc, ring, i, ql, g0 + i);
+          if constexpr (SCALED) OP::template step_scaled<QH>(acc, ring, i, ql, g0 + i, sw);
+          else OP::template step<QH>(acc, ring, i, ql, g0 + i);
           // refill the slot just consumed; the barrier keeps the compiler from
           // clustering the ring's loads (which would drain vmcnt to 0 mid-loop)
           ring[i] = stream_load(cur + (size_t)(g0 + i + TS_RING) * 64);
@@ -405,9 +422,14 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_kernel(typename WALK::Param
       if constexpr (MASKED) WALK::template mask_fetch<QH>(p, blkn, mrow, mstep, mwn);
       f32x4 bnxt[4];
       if constexpr (BIASED) WALK::bias_fetch(p, blkn, lane, bnxt);
+      if constexpr (SCALED) {
+        sw = OP::scale_word(sc, g0);
+        OP::scale_fetch(nxt, kg, scn);
+      }
 #pragma unroll
       for (int i = 0; i < TS_RING; ++i) {
-        OP::template step<QH>(acc, ring, i, ql, g0 + i);
+        if constexpr (SCALED) OP::template step_scaled<QH>(acc, ring, i, ql, g0 + i, sw);
+        else OP::template step<QH>(acc, ring, i, ql, g0 + i);
         ring[i] = stream_load(nxt + (size_t)i * 64);
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -427,6 +449,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_kernel(typename WALK::Param
       cur = nxt;
       if constexpr (MASKED) WALK::template mask_advance<QH>(mor, mwn, mw);
       if constexpr (BIASED) WALK::bias_advance(bnxt, bcur, bmax);
+      if constexpr (SCALED) { sc[0] = scn[0]; sc[1] = scn[1]; }
     }
   }  // active
   if constexpr (MODE == SCAN_FILTER) flush_stage(p, st, tid);

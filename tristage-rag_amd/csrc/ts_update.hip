@@ -182,6 +182,8 @@ int ts_launch_update_blocks(const TsLayout& L, const uint4* stage, uint4* corpus
 int ts_launch_update_rows(const TsLayout& L, const uint4* stage, uint4* corpus, const int32_t* blk,
                           const int32_t* first, const int32_t* item, int64_t n_entries, hipStream_t stream) {
   if (n_entries <= 0) return TS_OK;
+  if (L.dtype == TS_MXFP4_E2M1)   // (its row block is not a multiple of TS_RING units: ts_scan_fp4.hip)
+    return ts_launch_update_rows_fp4(L, stage, corpus, blk, first, item, n_entries, stream);
   const int64_t nwave = n_entries * (L.kg / TS_RING);
   const int64_t blocks = (nwave + 3) / 4;
   if (blocks > 0x7fffffffLL) { ts_set_error("update: too many rows in one chunk"); return TS_ERR_INVALID; }

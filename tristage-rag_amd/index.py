@@ -25,8 +25,11 @@ _NP_DTYPES = {np.dtype(np.float32): _lib.TS_F32, np.dtype(np.float16): _lib.TS_F
 _NAME_TO_DTYPE = {"f32": _lib.TS_F32, "fp32": _lib.TS_F32, "float32": _lib.TS_F32,
                   "f16": _lib.TS_F16, "fp16": _lib.TS_F16, "float16": _lib.TS_F16,
                   "bf16": _lib.TS_BF16, "bfloat16": _lib.TS_BF16,
-                  "fp8": _lib.TS_FP8_E4M3, "e4m3": _lib.TS_FP8_E4M3, "float8_e4m3fn": _lib.TS_FP8_E4M3}
-_DTYPE_NAME = {_lib.TS_F32: "f32", _lib.TS_F16: "f16", _lib.TS_BF16: "bf16", _lib.TS_FP8_E4M3: "fp8"}
+                  "fp8": _lib.TS_FP8_E4M3, "e4m3": _lib.TS_FP8_E4M3, "float8_e4m3fn": _lib.TS_FP8_E4M3,
+                  "fp4": _lib.TS_MXFP4_E2M1, "mxfp4": _lib.TS_MXFP4_E2M1, "e2m1": _lib.TS_MXFP4_E2M1}
+_DTYPE_NAME = {_lib.TS_F32: "f32", _lib.TS_F16: "f16", _lib.TS_BF16: "bf16", _lib.TS_FP8_E4M3: "fp8",
+               _lib.TS_MXFP4_E2M1: "fp4"}
+FP4_INDEX_MAX_D = 2048   # an fp4 index's query image is a bf16 image too, and a lane keeps at most 32 scale bytes
 FP8_INDEX_MAX_D = 2048   # an e4m3 index's query image is a bf16 image: 32 queries of it fit the LDS up to here
 
 
@@ -554,7 +557,9 @@ class FlatIPIndex(_IndexBase):
 
     def __init__(self, d: int, dtype: str = "f32", device: int = 0, fp8_scale_log2: int = 8):
         """``dtype="fp8"``: one byte per element (e4m3); element x is stored as e4m3(x * 2^fp8_scale_log2)
-        (see :func:`quantize_rows_e4m3_fixed_reference`), the default 8 fits unit-norm rows."""
+        (see :func:`quantize_rows_e4m3_fixed_reference`), the default 8 fits unit-norm rows.
+        ``dtype="fp4"``: half a byte per element plus a scale byte per 32 (OCP e2m1 with E8M0 block scales, DESIGN.md
+        4.23; see :func:`quantize_rows_mxfp4_reference`): a candidate generator for the stages that rerank."""
         if dtype not in _NAME_TO_DTYPE:
             raise ValueError(f"unknown storage dtype {dtype!r}")
         is_fp8 = _NAME_TO_DTYPE[dtype] == _lib.TS_FP8_E4M3
@@ -562,6 +567,8 @@ class FlatIPIndex(_IndexBase):
             raise ValueError(f"fp8_scale_log2 must be in 0 .. 15, got {fp8_scale_log2}")
         if is_fp8 and int(d) > FP8_INDEX_MAX_D:
             raise NotImplementedError(f"an fp8 index takes at most {FP8_INDEX_MAX_D} dimensions, got {d}")
+        if _NAME_TO_DTYPE[dtype] == _lib.TS_MXFP4_E2M1 and int(d) > FP4_INDEX_MAX_D:
+            raise NotImplementedError(f"an fp4 index takes at most {FP4_INDEX_MAX_D} dimensions, got {d}")
         self._lib = _lib.load()
         self.d = int(d)
         self.device = int(device)
@@ -833,8 +840,8 @@ class FlatIPIndex(_IndexBase):
         ``max_results``: the most entries the call may return (default 2^26); exceeding it raises
         :class:`RangeSearchLimitError`, which names the count and the limit, and the index stays usable.
         ``exact_dense=True`` forces the dense path (tests, A/B runs).  Synchronous."""
-        if self.storage_dtype == "fp8":
-            raise NotImplementedError("range_search is not supported on an fp8 index")
+        if self.storage_dtype in ("fp8", "fp4"):
+            raise NotImplementedError(f"range_search is not supported on an {self.storage_dtype} index")
         q, q_dtype, B, on_gpu = _host_query(q, self.d)
         rad = np.asarray(_to_host(radius.float() if _is_tensor(radius) else radius), dtype=np.float32).reshape(-1)
         if rad.size == 1:
@@ -978,7 +985,12 @@ class FlatIPIndex(_IndexBase):
         position; the similarity is the inner product of the stored rows.  Returns ``(D, I)`` [B, k] in selection
         order, ``D`` the relevances of the picks, -FLT_MAX / -1 padded.  Removed rows are skipped like padding.
         CUDA tensors in -> tensors out, enqueued on the current stream (no synchronisation); numpy in -> numpy out."""
+        self._no_fp4("mmr")
         return _mmr_call(self, "ts_index_mmr", ids, relevance, k, lambda_mult)
+
+    def _no_fp4(self, what: str) -> None:
+        if getattr(self, "storage_dtype", None) == "fp4":
+            raise NotImplementedError(f"{what} is not supported on an fp4 index")
 
     def mmr_timings(self, on: Optional[bool] = None, reset: bool = True) -> dict:
         """Measurement aid: ``on`` switches the per-kernel timing of :meth:`mmr` (timed calls synchronise); returns the
@@ -993,6 +1005,7 @@ class FlatIPIndex(_IndexBase):
     def search_mmr(self, q, k: int, fetch_k: Optional[int] = None, lambda_mult: float = 0.5, allowed=None):
         """``search(q, fetch_k, allowed=allowed)`` followed by :meth:`mmr` on the same stream; ``fetch_k`` defaults to
         ``min(1024, max(4 k, 20))``."""
+        self._no_fp4("search_mmr")
         return self._search_mmr(q, k, fetch_k, lambda_mult, allowed=allowed)
 
     # -- grouped search (DESIGN.md 4.18) --------------------------------------
@@ -1470,6 +1483,73 @@ def decode_rows_e4m3_fixed(b, scale_log2: int = 8) -> np.ndarray:
     return v.astype(np.float32)
 
 
+MXFP4_GRID = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)   # the magnitudes of OCP e2m1, by 3-bit index
+
+
+def _mxfp4_block_dims(dpad: int) -> np.ndarray:
+    """[dpad // 32, 32]: the dimensions of scale block 2 g + h, k = 64 g + 16 m + 8 h + j in the order (m, j)."""
+    g, h, m, j = np.meshgrid(np.arange(dpad // 64), np.arange(2), np.arange(4), np.arange(8), indexing="ij")
+    return (64 * g + 16 * m + 8 * h + j).reshape(dpad // 32, 32)
+
+
+def quantize_rows_mxfp4_reference(x):
+    """The stored values of an fp4 FlatIPIndex, in numpy: OCP e2m1 elements with one E8M0 scale per
+    32 elements.  x [n, d] (f32 / f16 / bf16 array or tensor; taken as float32, NaN as 0, +-Inf as +-FLT_MAX) is
+    zero-padded to dpad, a multiple of 64.  Scale block (g, h), h = 0/1, holds the dimensions k = 64 g + 16 m + 8 h + j
+    (m = 0..3, j = 0..7); its exponent e, column 2 g + h of ``exps``, is 0 for an all-zero block and otherwise
+    floor(log2 amax) - 2 on the float32 bits of the block's largest magnitude, plus 1 if amax > 6 * 2^e, clamped to
+    -100 .. 100 (the stored byte is e + 127).  Code = 8 * (sign bit of x) + the index of the value of
+    :data:`MXFP4_GRID` nearest to |x| / 2^e, ties to the even index, values above 6 to index 7.
+    Returns (codes uint8 [n, dpad], exps int8 [n, dpad // 32])."""
+    if _is_tensor(x):
+        x = x.detach().to("cpu", _torch().float32).numpy()
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if x.ndim != 2:
+        raise ValueError("quantize_rows_mxfp4_reference: x must be [n, d]")
+    n, d = x.shape
+    dpad = -(-d // 64) * 64
+    v = np.zeros((n, dpad), dtype=np.float32)
+    v[:, :d] = x
+    bits = v.view(np.uint32)
+    mag = bits & np.uint32(0x7FFFFFFF)
+    v[mag > 0x7F800000] = 0.0                                           # NaN -> +0
+    inf = mag == 0x7F800000
+    bits[inf] = (bits[inf] & np.uint32(0x80000000)) | np.uint32(0x7F7FFFFF)   # +-Inf -> +-FLT_MAX
+    dims = _mxfp4_block_dims(dpad)
+    blocks = v[:, dims]                                                  # [n, dpad // 32, 32]
+    amax = np.abs(blocks).max(axis=2)
+    a = amax.view(np.uint32).astype(np.int64)
+    e = (a >> 23) - 127 - 2 + ((a & 0x7FFFFF) > 0x400000)               # (f32 subnormals land below the clamp)
+    e = np.where(a == 0, 0, np.clip(e, -100, 100))
+    # |x| * 2^-e in float32: exact, or underflows far below 0.25, or overflows far above 6
+    with np.errstate(over="ignore", under="ignore"):
+        y = np.abs(blocks) * np.ldexp(np.float32(1.0), -e).astype(np.float32)[:, :, None]
+    f = np.float32
+    idx = ((y > f(0.25)).astype(np.uint8) + (y >= f(0.75)) + (y > f(1.25)) + (y >= f(1.75)) + (y > f(2.5))
+           + (y >= f(3.5)) + (y > f(5.0))).astype(np.uint8)
+    code = idx | ((blocks.view(np.uint32) >> 28) & 8).astype(np.uint8)
+    codes = np.zeros((n, dpad), dtype=np.uint8)
+    codes[:, dims] = code
+    return codes, e.astype(np.int8)
+
+
+def decode_rows_mxfp4(codes, exps, d: int) -> np.ndarray:
+    """The values an fp4 FlatIPIndex scores and ``reconstruct_n`` returns: sign * MXFP4_GRID[index] * 2^e as float32
+    [n, d] (exact, also in bf16), from what :func:`quantize_rows_mxfp4_reference` returns."""
+    codes = np.asarray(codes, dtype=np.uint8)
+    exps = np.asarray(exps, dtype=np.int8)
+    n, dpad = codes.shape
+    if dpad % 64 or exps.shape != (n, dpad // 32) or not 0 < int(d) <= dpad:
+        raise ValueError("decode_rows_mxfp4: codes [n, dpad], exps [n, dpad // 32], dpad % 64 == 0, 0 < d <= dpad")
+    dims = _mxfp4_block_dims(dpad)
+    mag = np.asarray(MXFP4_GRID, dtype=np.float32)[codes[:, dims] & 7]
+    val = np.ldexp(mag, exps.astype(np.int32)[:, :, None]).astype(np.float32)
+    val = np.where(codes[:, dims] & 8, -val, val)
+    out = np.zeros((n, dpad), dtype=np.float32)
+    out[:, dims] = val
+    return np.ascontiguousarray(out[:, :int(d)])
+
+
 def quantize_rows_fp8(x):
     """Rows -> the e4m3 token-store format (see quantize_rows_fp8_reference, which it equals bit for bit): the
     ts_quantize_rows_fp8 kernel for a GPU tensor, the torch reference for a CPU one.  x [rows, H] f32 / f16 / bf16."""
@@ -1773,6 +1853,8 @@ class IVFFlatIndex(_IndexBase):
     def __init__(self, d: int, nlist: int, dtype: str = "f16", device: int = 0, nprobe: int = 10):
         if _NAME_TO_DTYPE.get(dtype) == _lib.TS_FP8_E4M3:
             raise NotImplementedError("IVFFlatIndex has no fp8 storage (fp8 is a flat-index storage dtype)")
+        if _NAME_TO_DTYPE.get(dtype) == _lib.TS_MXFP4_E2M1:
+            raise NotImplementedError("IVFFlatIndex has no fp4 storage (fp4 is a flat-index storage dtype)")
         if dtype not in _NAME_TO_DTYPE or _NAME_TO_DTYPE[dtype] == _lib.TS_F32:
             raise ValueError(f"IVF storage dtype must be f16 or bf16, got {dtype!r}")
         self._lib = _lib.load()

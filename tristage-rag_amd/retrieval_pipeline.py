@@ -65,7 +65,7 @@ class PipelineConfig:
     auto_cleanup: bool = True
     max_memory_usage_gb: float = 4.0
     # ---- additive (MI355X) ----
-    stage1_index_dtype: str = "f32"          # corpus storage on the GPU: f32 | f16 | bf16 | fp8 (e4m3, flat index)
+    stage1_index_dtype: str = "f32"          # corpus storage on the GPU: f32 | f16 | bf16 | fp8 (e4m3) | fp4 (4-bit MX), the last two flat index only
     stage1_bm25_on_gpu: Optional[bool] = None  # BM25 postings in HBM, HIP scoring; None = when a GPU is used
     stage1_bm25_refit_compat: bool = False     # BM25 after a second add_documents as the reference computes it (appended statistics)
     stage2_cache_document_embeddings: bool = False

@@ -55,6 +55,8 @@ class ShardedFlatIPIndex:
         self.lo, self.hi = shard_bounds(self.n_total, self.world_size, self.rank)
         if str(dtype) in ("fp8", "e4m3", "float8_e4m3fn") or getattr(local_index, "storage_dtype", None) == "fp8":
             raise NotImplementedError("ShardedFlatIPIndex does not take an fp8 index (fp8 storage is single-GPU, flat only)")
+        if str(dtype) in ("fp4", "mxfp4", "e2m1") or getattr(local_index, "storage_dtype", None) == "fp4":
+            raise NotImplementedError("ShardedFlatIPIndex does not take an fp4 index (fp4 storage is single-GPU, flat only)")
         if local_index is None:
             from .index import FlatIPIndex
             local_index = FlatIPIndex(d, dtype=dtype, device=0 if device is None else device)

@@ -64,7 +64,7 @@ class Stage1Config:
     # "auto": the reference's rule (:256-283) — IVF when the first add_documents brings more than 1000 documents
     index_type: str = "flat"
     # additive knobs (not in the reference)
-    index_dtype: str = "f32"   # storage dtype of the corpus matrix: f32 | f16 | bf16 | fp8 (e4m3, flat index only)
+    index_dtype: str = "f32"   # storage dtype of the corpus matrix: f32 | f16 | bf16 | fp8 (e4m3) | fp4 (4-bit MX), the last two flat index only
     gpu_index_device: int = 0
     bm25_on_gpu: Optional[bool] = None  # BM25 postings in HBM + HIP scoring kernels; None = whenever
                                         # the HIP index is in use (a GPU is present)
@@ -1380,7 +1380,8 @@ class Stage1Retriever:
                     "index_type": getattr(self, "index_type_used", "flat"), "centroids": None}
         if self.faiss_index is not None:
             # the stored rows, decoded to float32.  An fp8 index needs no format of its own: its decoded rows are e4m3
-            # values times 2^-s, and quantising those again at load gives back the same bytes.
+            # values times 2^-s, and quantising those again at load gives back the same bytes.  Nor does an fp4 index:
+            # quantising its decoded rows gives back the same decoded values.
             mat = self.faiss_index.reconstruct_n(0, self.faiss_index.ntotal)
             np.save(base + ".matrix.npy", mat)
             manifest.update(ntotal=int(mat.shape[0]), dim=int(mat.shape[1]),
