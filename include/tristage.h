@@ -31,7 +31,7 @@
  *     its intermediate lists before it returns.  ts_index_read_probe times its passes with events and waits for them.
  *   - threading: ts_index_search on a built index is safe for
  *     concurrent callers on ONE handle that use distinct streams and output
- *     buffers: each call takes one of 4 internal workspace sets (a 5th
+ *     buffers: each call takes one of 8 internal workspace sets (a 9th
  *     synchronous caller waits for a set), its own report slot, and the exact
  *     fallback of a synchronous call runs on that call's set.  Host-pointer
  *     searches (TS_FLAG_HOST_PTR) share one staging area and are serialised

@@ -184,7 +184,7 @@ def test_one_handle_many_host_threads():
         except Exception as e:  # noqa: BLE001
             errors.append((t, repr(e)))
 
-    threads = [threading.Thread(target=worker, args=(t,)) for t in range(9)]   # 9 threads > 4 workspace sets
+    threads = [threading.Thread(target=worker, args=(t,)) for t in range(9)]   # 9 threads > 8 workspace sets
     for th in threads:
         th.start()
     for th in threads:

@@ -915,7 +915,7 @@ static int search_pass_on(ts_index* h, ts_index::WSet& W, const void* dq, int nq
   hipStream_t sP = pipe ? (fused ? h->s_scan : h->s_pro) : s, sS = pipe ? h->s_scan : s, sL = pipe ? h->s_sel : s;
   // the set may still be in use on the GPU by the (asynchronous) search that had it last, possibly
   // on another stream
-  // (asked first whether that search is already over — with four sets in rotation it normally is: a wait on
+  // (asked first whether that search is already over — with eight sets in rotation it normally is: a wait on
   // another stream's event in front of every scan, even a satisfied one, costs the scan stream 10-20 us)
   if (W.used && hipEventQuery(W.ev_sel) != hipSuccess) TS_HIP(hipStreamWaitEvent(sP, W.ev_sel, 0));
   // the output buffers may be memory the caller's stream is still reading (a recycled
