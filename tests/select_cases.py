@@ -483,7 +483,7 @@ def filter_path_expected(n, k):
 
 
 def sample_rank(n, k):
-    """The rank tau_kernel is asked for on the five-launch filter path (ts_index.hip search_pass_on, corpora whose
+    """The rank tau_kernel is asked for on the five-launch filter path (ts_index.hip sample_geometry, corpora whose
     sample is smaller than one round of scan waves): <= 64 takes tau_kernel<1>, above that tau_kernel<4>."""
     nblk = -(-n // 32)
     nsb = min(nblk, max(8192, n // 128) // 32)

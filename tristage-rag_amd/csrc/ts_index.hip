@@ -141,6 +141,7 @@ struct ts_index {
     float* tau() { return (float*)small.p; }
     uint32_t* cand_cnt() { return (uint32_t*)small.p + 64; }
     uint32_t* status() { return (uint32_t*)small.p + 128; }
+    TsMaskDev* mask_dev() { return (TsMaskDev*)mask.p; }   // a masked pass's tables, its live-block list behind them
   };
   WSet ws[TS_NSETS];
   uint64_t set_next = 0;
@@ -592,6 +593,24 @@ extern "C" int ts_index_mmr_get_timings(ts_index* h, double ms[3], int64_t* call
 }
 
 // ------------------------------------------------------------------ search
+static int queries_per_pass(const ts_index* h) { return (ts_scan_lds_bytes(h->L, 2) <= 160 * 1024) ? 64 : 32; }
+
+static int err_empty() {
+  ts_set_error("No documents indexed. Call add_documents() first.");
+  return TS_ERR_EMPTY;
+}
+
+// The CUs of an HBM-bound filter scan, 7/8 of them: 224 CUs stream 1.5 % FASTER than 256 (tools/cus.sh), and the free
+// eighth is where the threshold workgroups of the one-launch search and the neighbouring searches' small kernels run.
+static int filter_scan_cus(const ts_index* h) {
+  int cus = h->num_cus - h->num_cus / 8;
+#ifdef TS_TUNING  // ablation builds only: how many CUs a filter scan may occupy
+  static const int dbg_cus = getenv("TS_SCAN_CUS") ? atoi(getenv("TS_SCAN_CUS")) : 0;
+  if (dbg_cus > 0) cus = dbg_cus;
+#endif
+  return cus;
+}
+
 // One pass of a filtered search (ts_index_search_filtered): the masks (device) and the pass's tables.
 struct MaskCtx {
   const uint32_t* bits;
@@ -601,6 +620,78 @@ struct MaskCtx {
   const float* bias;
   const float* bias_tail;
 };
+
+// The tables of a pass of c queries, query j on mask moq[j] (-1: none): each query's mask and the distinct masks among
+// them.  Returns whether a query has a mask.
+static bool build_mask_pass(const int32_t* moq, int c, TsMaskPass& mp) {
+  mp = TsMaskPass{};
+  bool masked = false;
+  for (int j = 0; j < TS_MAX_Q; ++j) {
+    const int32_t m = j < c ? moq[j] : -1;
+    mp.qmask[j] = m;
+    mp.qd[j] = -1;
+    if (j >= c) continue;
+    if (m < 0) { mp.all_live = 1; continue; }
+    masked = true;
+    int d = 0;
+    while (d < mp.nd && mp.dist[d] != m) ++d;
+    if (d == mp.nd) mp.dist[mp.nd++] = m;
+    mp.qd[j] = d;
+  }
+  return masked;
+}
+
+// The mask arguments of the filtered entry points, in two parts: what needs no handle (a null mask_of_query, no query
+// with a mask, is the caller's to accept or refuse), then what needs the row count.
+static int check_mask_args(const char* entry, int32_t nq, const uint32_t* allow_bits, int64_t allow_words,
+                           int32_t n_masks, const int32_t* mask_of_query) {
+  if (n_masks < 0 || allow_words < 0) { ts_set_error("%s: negative n_masks / allow_words", entry); return TS_ERR_INVALID; }
+  if (n_masks > 0 && !allow_bits) { ts_set_error("%s: n_masks > 0 but allow_bits is null", entry); return TS_ERR_INVALID; }
+  for (int32_t q = 0; mask_of_query && q < nq; ++q) {
+    if (mask_of_query[q] < -1 || mask_of_query[q] >= n_masks) {
+      ts_set_error("%s: mask_of_query[%d] = %d is outside [-1, %d)%s", entry, q, mask_of_query[q], n_masks,
+                   allow_bits ? "" : " (allow_bits is null)");
+      return TS_ERR_INVALID;
+    }
+  }
+  return TS_OK;
+}
+static int check_mask_words(const char* entry, int32_t n_masks, int64_t allow_words, int64_t ntotal) {
+  const int64_t need_words = (ntotal + 31) / 32;
+  if (n_masks > 0 && allow_words < need_words) {
+    ts_set_error("%s: allow_words = %lld < ceil(ntotal / 32) = %lld", entry, (long long)allow_words, (long long)need_words);
+    return TS_ERR_INVALID;
+  }
+  return TS_OK;
+}
+
+// The parameters every scan of a pass takes; scan_window() or scan_filter() add those of its mode.
+static ScanParams scan_base(const ts_index* h, const ts_index::WSet& W, int nq) {
+  ScanParams sp{};
+  sp.corpus = h->corpus;
+  sp.qimg = (const uint4*)W.qimg.p;
+  sp.kg = h->L.kg;
+  sp.nq = nq;
+  sp.ntotal = h->ntotal;
+  return sp;
+}
+// dense mode: the scores of nwork row blocks, `stride` apart from blk0 on, to dense[q * ld + ..]
+static void scan_window(ScanParams& sp, int64_t blk0, int64_t nwork, int64_t stride, float* dense, int64_t ld) {
+  sp.blk0 = blk0;
+  sp.nwork = nwork;
+  sp.blk_stride = stride;
+  sp.dense = dense;
+  sp.dense_ld = ld;
+}
+// filter mode: every row block against the set's thresholds, the survivors to its candidate lists
+static void scan_filter(ScanParams& sp, ts_index::WSet& W, int64_t nblk) {
+  scan_window(sp, 0, nblk, 1, nullptr, 0);
+  sp.tau = W.tau();
+  sp.cand_cnt = W.cand_cnt();
+  sp.cand_score = (float*)W.cand_score.p;
+  sp.cand_id = (int32_t*)W.cand_id.p;
+  sp.cand_cap = kCandCap;
+}
 
 // A scan of the whole rows (pkg == 0) or of the first pkg k groups of every row (ts_index_search_prefix): the same
 // parameters, the prefix scans add the pitch of the row blocks.
@@ -613,12 +704,46 @@ static int scan_rows(ts_index* h, int pkg, int mode, int qh, const ScanParams& s
   return ts_launch_scan_prefix(h->L, mode, qh, pp, cus, s);
 }
 
+// The live-block list of a masked pass into the set's TsMaskDev (W.mask_dev()), on `s`.
+static int launch_live_blocks(ts_index* h, ts_index::WSet& W, const MaskCtx& mc, hipStream_t s) {
+  const int64_t nblk = (h->ntotal + TS_ROWS_PER_BLOCK - 1) / TS_ROWS_PER_BLOCK;
+  TS_CHECK(ensure(W.mask, sizeof(TsMaskDev) + (size_t)nblk * 4));
+  TS_HIP(hipMemsetAsync(W.mask_dev(), 0, sizeof(TsMaskDev), s));
+  return ts_launch_live_blocks(mc.bits, mc.words, mc.mp, nblk, h->ntotal, W.mask_dev(), s);
+}
+// the masked form of a filter scan: its work items are the blocks of that list
+static MaskedScanParams masked_scan_params(const ScanParams& sp, ts_index::WSet& W, const MaskCtx& mc) {
+  const TsMaskDev* md = W.mask_dev();
+  MaskedScanParams mp{};
+  static_cast<ScanParams&>(mp) = sp;
+  mp.live = reinterpret_cast<const int32_t*>(md + 1);
+  mp.nlive = &md->nlive;
+  mp.allow_bits = mc.bits;
+  mp.allow_words = mc.words;
+  mp.qmask = md->qmask;
+  return mp;
+}
+
+// The dense path scores the corpus in chunks of at most kDenseChunkRows rows (whole row blocks).
+struct DenseChunks { int64_t chunk_rows, nch; };
+static DenseChunks dense_chunks(int64_t ntotal) {
+  const int64_t nblk = (ntotal + TS_ROWS_PER_BLOCK - 1) / TS_ROWS_PER_BLOCK;
+  const int64_t chunk_rows = std::min<int64_t>(kDenseChunkRows, nblk * TS_ROWS_PER_BLOCK);
+  return DenseChunks{chunk_rows, (nblk * TS_ROWS_PER_BLOCK + chunk_rows - 1) / chunk_rows};
+}
+// one chunk: the scores of rows [row0, row0 + rows) into W.dense
+static int dense_chunk_scan(ts_index* h, ts_index::WSet& W, int nq, int qh, int pkg, int64_t row0, int64_t rows,
+                            int64_t chunk_rows, hipStream_t s) {
+  ScanParams sp = scan_base(h, W, nq);
+  scan_window(sp, row0 / TS_ROWS_PER_BLOCK, (rows + TS_ROWS_PER_BLOCK - 1) / TS_ROWS_PER_BLOCK, 1, (float*)W.dense.p,
+              chunk_rows);
+  return scan_rows(h, pkg, SCAN_DENSE, qh, sp, h->num_cus, s);
+}
+
 static int dense_path(ts_index* h, ts_index::WSet& W, int nq, int qh, int k, float* out_s,
                       int64_t* out_i, hipStream_t s, const MaskCtx* mc = nullptr, int pkg = 0) {
   const int64_t N = h->ntotal;
-  const int64_t nblk = (N + TS_ROWS_PER_BLOCK - 1) / TS_ROWS_PER_BLOCK;
-  const int64_t chunk_rows = std::min<int64_t>(kDenseChunkRows, nblk * TS_ROWS_PER_BLOCK);
-  const int64_t nch = (nblk * TS_ROWS_PER_BLOCK + chunk_rows - 1) / chunk_rows;
+  const auto [chunk_rows, nch] = dense_chunks(N);
   TS_CHECK(ensure(W.dense, (size_t)nq * chunk_rows * 4));
   if (mc) TS_CHECK(ensure(W.mids, (size_t)nq * chunk_rows * 4));
   if (nch > 1) {
@@ -628,18 +753,7 @@ static int dense_path(ts_index* h, ts_index::WSet& W, int nq, int qh, int k, flo
   for (int64_t c = 0; c < nch; ++c) {
     const int64_t row0 = c * chunk_rows;
     const int64_t rows = std::min(chunk_rows, N - row0);
-    ScanParams sp{};
-    sp.corpus = h->corpus;
-    sp.qimg = (const uint4*)W.qimg.p;
-    sp.kg = h->L.kg;
-    sp.nq = nq;
-    sp.nwork = (rows + TS_ROWS_PER_BLOCK - 1) / TS_ROWS_PER_BLOCK;
-    sp.blk0 = row0 / TS_ROWS_PER_BLOCK;
-    sp.blk_stride = 1;
-    sp.ntotal = N;
-    sp.dense = (float*)W.dense.p;
-    sp.dense_ld = chunk_rows;
-    TS_CHECK(scan_rows(h, pkg, SCAN_DENSE, qh, sp, h->num_cus, s));
+    TS_CHECK(dense_chunk_scan(h, W, nq, qh, pkg, row0, rows, chunk_rows, s));
     SelParams p{};
     p.mode = SEL_DENSE;
     p.scores = (const float*)W.dense.p;
@@ -654,8 +768,8 @@ static int dense_path(ts_index* h, ts_index::WSet& W, int nq, int qh, int k, flo
         TS_CHECK(ts_launch_bias_ids(mc->bits, mc->words, mc->mp, mc->bias, nq, row0, (uint32_t)rows, chunk_rows,
                                     (float*)W.dense.p, (int32_t*)W.mids.p, s));
       else
-      TS_CHECK(ts_launch_mask_ids(mc->bits, mc->words, mc->mp, nq, row0, (uint32_t)rows, chunk_rows,
-                                  (int32_t*)W.mids.p, s));
+        TS_CHECK(ts_launch_mask_ids(mc->bits, mc->words, mc->mp, nq, row0, (uint32_t)rows, chunk_rows,
+                                    (int32_t*)W.mids.p, s));
       p.mode = SEL_PAIRS32;
       p.ids32 = (const int32_t*)W.mids.p;
     }
@@ -714,17 +828,6 @@ static int ensure_streams(ts_index* h) {
   return TS_OK;
 }
 
-// One pass of <= 32*qh queries (device pointers).
-//
-// A pass has three phases, each touching one workspace set W:
-//   P   query prep, sample scan, thresholds      writes W.qimg, W.sample, W.tau; clears W.cand_cnt
-//   S   fused scan+filter over the whole shard   reads W.qimg, W.tau; writes W.cand_*
-//   Sel exact top-k of the candidates            reads W.cand_*; writes the caller's outputs + host slot
-// Normally all three are enqueued on the caller's stream.  With TS_FLAG_PIPELINE they go to
-// three internal streams chained by events (P -> S -> Sel), and the caller's stream only waits
-// for Sel: P of the NEXT search and Sel of the PREVIOUS one then run beside the current S, which
-// leaves an eighth of the CUs free and is HBM-bound anyway.  Passes alternate between two
-// workspace sets; a set is reused only after the Sel that last read it (its ev_sel).
 // ---- geometry of the one-launch search
 struct FusedPlan {
   int scan_wgs, tau_wgs;
@@ -737,11 +840,7 @@ static bool plan_fused(const ts_index* h, int64_t N, int64_t nblk, int k, bool p
   // search's kernel follows on the SAME stream, so its workgroups are dispatched the moment this one ends, ahead
   // of the select that waits for this kernel through an event on another stream: no placement race.
   (void)pipe;
-  int scan_wgs = h->num_cus - h->num_cus / 8;
-#ifdef TS_TUNING
-  static const int dbg_cus = getenv("TS_SCAN_CUS") ? atoi(getenv("TS_SCAN_CUS")) : 0;
-  if (dbg_cus > 0) scan_wgs = dbg_cus;
-#endif
+  const int scan_wgs = filter_scan_cus(h);
   if (scan_wgs < 1) return false;
   const int tau_wgs = std::max(1, std::min(64, h->num_cus - scan_wgs));
   const int64_t nwaves = (int64_t)scan_wgs * 8;
@@ -801,6 +900,36 @@ static void release_set(ts_index* h, ts_index::WSet* w) {
   }
   h->cv.notify_one();
 }
+namespace {
+// A workspace set held for one pass: taken from the pool, given back on every exit.  wait_previous() orders a stream
+// behind the set's last user, done() records the end of this one for the next.
+struct SetLease {
+  ts_index* h;
+  ts_index::WSet* W;
+  explicit SetLease(ts_index* h_) : h(h_), W(acquire_set(h_)) {}
+  ~SetLease() { if (W) release_set(h, W); }
+  SetLease(const SetLease&) = delete;
+  SetLease& operator=(const SetLease&) = delete;
+  // the set may still be in use on the GPU by the (asynchronous) search that had it last, possibly on another stream
+  // (asked first whether that search is already over — with eight sets in rotation it normally is: a wait on
+  // another stream's event in front of every scan, even a satisfied one, costs the scan stream 10-20 us)
+  int wait_previous(hipStream_t s) {
+    if (W->used && hipEventQuery(W->ev_sel) != hipSuccess) TS_HIP(hipStreamWaitEvent(s, W->ev_sel, 0));
+    return TS_OK;
+  }
+  int done(hipStream_t s) {
+    TS_HIP(hipEventRecord(W->ev_sel, s));
+    W->used = true;
+    return TS_OK;
+  }
+  // the set stays busy in its new holder's hands (co_submit: until co_launch_pass has enqueued the batch's select)
+  ts_index::WSet* detach() {
+    ts_index::WSet* w = W;
+    W = nullptr;
+    return w;
+  }
+};
+}  // namespace
 // a free slot of the mapped host ring (at most 64 asynchronous passes + TS_NSETS synchronous ones hold one)
 static int alloc_slot(ts_index* h) {
   std::lock_guard<std::mutex> lk(h->mu);
@@ -833,20 +962,14 @@ static void set_info(ts_index* h, int64_t a, int64_t b, int64_t c, int64_t d) {
   h->info[0] = a; h->info[1] = b; h->info[2] = c; h->info[3] = d;
 }
 
-static int search_pass_on(ts_index* h, ts_index::WSet& W, const void* dq, int nq, int q_dtype, int k,
-                          float* out_s, int64_t* out_i, uint32_t flags, hipStream_t s, const MaskCtx* mc, int pkg);
-
-// pkg > 0 (ts_index_search_prefix): the pass ranks on the first pkg k groups of every row; dq holds 16 * pkg elements
-// per query
-static int search_pass(ts_index* h, const void* dq, int nq, int q_dtype, int k, float* out_s,
-                       int64_t* out_i, uint32_t flags, hipStream_t s, const MaskCtx* mc = nullptr, int pkg = 0) {
-  // per-phase timing shares one set of events per handle: profiled searches run one at a time
-  std::unique_lock<std::mutex> plk(h->prof_mu, std::defer_lock);
-  if (h->profiling) plk.lock();
-  ts_index::WSet* W = acquire_set(h);
-  const int st = search_pass_on(h, *W, dq, nq, q_dtype, k, out_s, out_i, flags, s, mc, pkg);
-  release_set(h, W);
-  return st;
+// An unfinished asynchronous pass, verified by ts_index_finish().  Caller holds h->mu.
+static ts_index::Pending& push_pending(ts_index* h, int slot, int nq, int64_t S, uint32_t m, int set, int64_t fseq) {
+  ts_index::Pending& pe = h->pending[h->npending++];
+  pe.ticket = h->next_ticket; pe.slot = slot; pe.nq = nq; pe.S = (uint32_t)S; pe.m = m;
+  pe.e0 = pe.e1 = nullptr;
+  pe.set = set;
+  pe.fseq = fseq;
+  return pe;
 }
 
 // ts_index_last_filter_info: one pass of the filtered call `fseq` (a later call has reset the counters)
@@ -867,12 +990,296 @@ static void add_bias_info(ts_index* h, bool fused, bool redone, int64_t blocks) 
   h->binfo[3] += blocks;
 }
 
+// ---- geometry of the five-launch path: the strided sample of row blocks whose scores give the thresholds, and the
+// rank m of the sample score that becomes one, for about oversample * k expected survivors per query
+struct SampleGeom {
+  int64_t nsb, sstride, S;   // sample blocks, the stride between them, sample rows
+  uint32_t m;
+};
+static SampleGeom sample_geometry(const ts_index* h, int k, int64_t oversample) {
+  const int64_t N = h->ntotal;
+  const int64_t nblk = (N + TS_ROWS_PER_BLOCK - 1) / TS_ROWS_PER_BLOCK;
+  int64_t nsb = std::max(kMinSampleRows, N / kSampleDiv) / TS_ROWS_PER_BLOCK;
+  // one sample block per scan wave (8 waves per CU): a ragged last round would
+  // make the short sample scan ~1.7x longer than it has to be
+  const int64_t round = (int64_t)h->num_cus * 8;
+  if (nsb > round) nsb -= nsb % round;
+  nsb = std::min(nsb, nblk);
+  SampleGeom g{nsb, nblk / nsb, nsb * TS_ROWS_PER_BLOCK, 0};
+  g.m = std::max((uint32_t)((oversample * (int64_t)k * g.S + N - 1) / N), kMinSampleRank);
+  return g;
+}
+
+// The exact top-k of a set's candidates.  The select kernel verifies that `need` of them exist (0: need_check_kernel
+// has the per-query figure) and reports the candidate counts and the status word straight into mapped host memory: no
+// copy kernel between it and the sync; every search in flight has its own slot of the ring.
+static SelParams cand_select_params(const ts_index* h, ts_index::WSet& W, int k, uint32_t need, float* out_s,
+                                    int64_t* out_i, int slot) {
+  SelParams p{};
+  p.mode = SEL_PAIRS32;
+  p.scores = (const float*)W.cand_score.p;
+  p.ids32 = (const int32_t*)W.cand_id.p;
+  p.stride = kCandCap;
+  p.n_per_q = W.cand_cnt();
+  p.n_cap = kCandCap;
+  p.need = need;
+  p.k = k;
+  p.out_scores = out_s;
+  p.out_ids64 = out_i;
+  p.out_stride = k;
+  p.id_offset = h->id_offset;
+  p.status = W.status();
+  p.clear_counts = W.cand_cnt();   // counts go back to zero: the one-launch search has no preparation kernel to do it
+  p.host_report = h->host_status_dev + (size_t)slot * TS_SLOT_WORDS;
+  return p;
+}
+
+namespace {
+// ---- one pass of <= 32*qh queries (device pointers): what its phases share.  search_pass_on fixes the first part;
+// the phases write the second.
+struct Pass {
+  ts_index* const h;
+  SetLease& set;
+  const void* const dq;
+  const int nq, q_dtype, qh, k, pkg;
+  float* const out_s;
+  int64_t* const out_i;
+  const MaskCtx* const mc;
+  const int64_t N, nblk, fseq;
+  const bool async, pipe, fused;
+  const hipStream_t s, sP, sS, sL;   // the caller's stream; those of the phases P, S and Sel
+  SlotGuard slot;                    // the report slot: every early return gives it back
+  ProfCtx pc{};
+  int64_t S = 0;                     // sample rows and the rank behind the thresholds (ts_index_last_search_info)
+  uint32_t m = 0;
+};
+}  // namespace
+
+// The dense pass (no filter: small corpora, large k, TS_FLAG_NO_FILTER, masked fp32 storage), all on the caller's stream.
+static int pass_dense(Pass& p) {
+  ts_index* h = p.h;
+  set_info(h, 0, 0, 0, 0);
+  if (p.mc) add_filter_info(h, p.fseq, p.nblk, p.nblk, true);
+  if (p.mc && p.mc->bias) add_bias_info(h, false, false, p.nblk);
+  prof_mark(h, p.pc, 5, p.s);
+  TS_CHECK(dense_path(h, *p.set.W, p.nq, p.qh, p.k, p.out_s, p.out_i, p.s, p.mc, p.pkg));
+  prof_mark(h, p.pc, -1, p.s);
+  TS_CHECK(p.set.done(p.s));
+  if (p.async) return TS_OK;  // exact by construction: nothing to verify
+  TS_HIP(hipStreamSynchronize(p.s));
+  prof_collect(h, p.pc);
+  return TS_OK;
+}
+
+// ONE launch: query image, thresholds and scan+filter (see ts_fused.hip)
+static int pass_one_launch(Pass& p, const FusedPlan& fp) {
+  ts_index* h = p.h;
+  ts_index::WSet& W = *p.set.W;
+  if (!W.hist.p) {
+    TS_CHECK(ensure(W.hist, ts_fused_keys_bytes()));
+    W.hist_dirty = true;
+  }
+  if (W.hist_dirty) {
+    // a launch on this set gave up somewhere: slots may hold stale keys, and sample workgroups that left before
+    // reporting have put the arrival counter behind its running goal for good — start all three from zero
+    TS_HIP(hipMemsetAsync(W.hist.p, 0, ts_fused_keys_bytes(), p.sS));
+    TS_HIP(hipMemsetAsync(W.cand_cnt(), 0, 256, p.sS));
+    TS_HIP(hipMemsetAsync(W.arrive(), 0, 4, p.sS));
+    W.arrive_total = 0;
+    W.hist_dirty = false;
+  }
+  if (++W.gen == 0) W.gen = 1;
+  W.arrive_total += fp.sample_waves;
+  TsFusedArgs a{};
+  a.corpus = h->corpus;
+  a.queries = p.dq;
+  a.q_dtype = p.q_dtype;
+  a.nq = p.nq;
+  a.nblk = p.nblk;
+  a.ntotal = p.N;
+  a.scan_wgs = fp.scan_wgs;
+  a.tau_wgs = fp.tau_wgs;
+  a.n_sample = fp.n_sample;
+  a.sample_stride = fp.sample_stride;
+  a.m = fp.m;
+  a.expect = fp.expect;
+  a.gen = W.gen;
+  a.arrive_goal = W.arrive_total;
+  a.wait_iters = 40000;
+  a.skeys = (uint32_t*)W.hist.p;
+  a.arrive = W.arrive();
+  a.tau64 = W.tau64();
+  a.cand_cnt = W.cand_cnt();
+  a.cand_score = (float*)W.cand_score.p;
+  a.cand_id = (int32_t*)W.cand_id.p;
+  a.cand_cap = kCandCap;
+  prof_mark(h, p.pc, 3, p.sS);
+  TS_CHECK(ts_launch_fused(h->L, p.qh, a, p.sS));
+  prof_mark(h, p.pc, 4, p.sS);
+  p.S = fp.sample_rows;
+  p.m = fp.m;
+  return TS_OK;
+}
+
+// Five launches: sample -> thresholds -> scan+filter (-> select: pass_select).  Filtered passes (mc != null) take the
+// live-block list and the masked scan, boosted ones its biased form, prefix passes the prefix kernels.
+static int pass_five_launch(Pass& p) {
+  ts_index* h = p.h;
+  ts_index::WSet& W = *p.set.W;
+  const MaskCtx* mc = p.mc;
+  // expected survivors per query ~ oversample * k; 3x for large k keeps the worst query of a
+  // batch (about 1.5x the mean) well inside the 16384 candidate slots
+  const int64_t oversample = p.k > 1024 ? 3 : kOversample;
+  const SampleGeom g = sample_geometry(h, p.k, oversample);
+  p.S = g.S;
+  p.m = g.m;
+  TS_CHECK(ensure(W.sample, (size_t)p.nq * g.S * 4));
+  ScanParams sp = scan_base(h, W, p.nq);
+  // (1) dense scores of a strided sample of row blocks
+  scan_window(sp, 0, g.nsb, g.sstride, (float*)W.sample.p, g.S);
+  prof_mark(h, p.pc, 1, p.sP);
+  TS_CHECK(scan_rows(h, p.pkg, SCAN_DENSE, p.qh, sp, h->num_cus, p.sP));
+  prof_mark(h, p.pc, 2, p.sP);
+  // (2) per-query threshold = ~m-th best sample score
+  if (mc) {
+    // (2') the live-block list of the pass, then per query the m_q-th best ALLOWED sample score (+ bias: boosted); the
+    // threshold kernel also reports the live-block count (word 65 of the slot)
+    TS_CHECK(launch_live_blocks(h, W, *mc, p.sP));
+    uint32_t* report = h->host_status_dev + (size_t)p.slot.slot * TS_SLOT_WORDS + 65;
+    if (mc->bias)
+      TS_CHECK(ts_launch_tau_biased((const float*)W.sample.p, g.S, g.sstride, p.N, mc->bits, mc->words, mc->bias,
+                                    W.mask_dev(), p.nq, p.k, (uint32_t)oversample, kMinSampleRank, W.tau(), report, p.sP));
+    else
+      TS_CHECK(ts_launch_tau_masked((const float*)W.sample.p, g.S, g.sstride, p.N, mc->bits, mc->words, W.mask_dev(),
+                                    p.nq, p.k, (uint32_t)oversample, kMinSampleRank, W.tau(), report, p.sP));
+  } else {
+#ifdef TS_TUNING  // ablation builds only (tools/variants.sh): thresholds = +inf, nothing survives
+    static const bool dbg_tau_inf = getenv("TS_DEBUG_TAU_INF") != nullptr;
+#else
+    constexpr bool dbg_tau_inf = false;
+#endif
+    TS_CHECK(ts_launch_tau((const float*)W.sample.p, g.S, dbg_tau_inf ? 0xFFFFFFFFu : (uint32_t)g.S, g.m, p.nq, W.tau(),
+                           p.sP));
+  }
+  if (p.pipe) {
+    TS_HIP(hipEventRecord(W.ev_pro, p.sP));
+    TS_HIP(hipStreamWaitEvent(p.sS, W.ev_pro, 0));
+  }
+  // (3) the full scan; only scores >= tau leave the registers
+  scan_filter(sp, W, p.nblk);
+  const int scan_cus = filter_scan_cus(h);
+  prof_mark(h, p.pc, 3, p.sS);
+  if (!mc) {
+    TS_CHECK(scan_rows(h, p.pkg, SCAN_FILTER, p.qh, sp, scan_cus, p.sS));
+  } else if (mc->bias) {
+    BiasScanParams bp{};
+    static_cast<MaskedScanParams&>(bp) = masked_scan_params(sp, W, *mc);
+    bp.bias = mc->bias;
+    bp.bias_tail = mc->bias_tail;
+    bp.tail_blk = (p.N % TS_ROWS_PER_BLOCK) ? p.N / TS_ROWS_PER_BLOCK : -1;
+    TS_CHECK(ts_launch_scan_biased(h->L, p.qh, bp, scan_cus, p.sS));
+  } else if (p.pkg) {
+    PrefixMaskedScanParams pp{};
+    static_cast<MaskedScanParams&>(pp) = masked_scan_params(sp, W, *mc);
+    pp.kg = p.pkg;
+    pp.kg_row = h->L.kg;
+    TS_CHECK(ts_launch_scan_prefix_masked(h->L, p.qh, pp, scan_cus, p.sS));
+  } else {
+    TS_CHECK(ts_launch_scan_masked(h->L, p.qh, masked_scan_params(sp, W, *mc), scan_cus, p.sS));
+  }
+  prof_mark(h, p.pc, 4, p.sS);
+  return TS_OK;
+}
+
+// Select and report: (4) the exact top-k of the candidates on the select stream, which verifies that >= k of them
+// exist; the set's next user and, pipelined, the caller's stream are ordered behind it.
+static int pass_select(Pass& p) {
+  ts_index* h = p.h;
+  ts_index::WSet& W = *p.set.W;
+  if (p.pipe) {
+    TS_HIP(hipEventRecord(W.ev_scan, p.sS));
+    TS_HIP(hipStreamWaitEvent(p.sL, W.ev_scan, 0));
+    TS_HIP(hipStreamWaitEvent(p.sL, W.ev_in, 0));
+    // This select and the NEXT search's scan wait for the same event.  If the select's 64
+    // workgroups (128 KiB of LDS each: they cannot share a CU with a scan workgroup) are placed
+    // first they take 64 CUs, 32 of the scan's 224 persistent workgroups have to wait for them,
+    // and the whole scan ends that much later — stream priority does not prevent it (measured:
+    // overlapped scans of 0.305-0.326 ms instead of 0.289 at 1.25 M rows, 2.263 instead of 2.207
+    // at 10 M).  A head start of a few microseconds for the scan does: the select then finds the
+    // 32 CUs the scan grid leaves free.
+#ifdef TS_TUNING
+    static const int head_us = getenv("TS_HEAD_START_US") ? atoi(getenv("TS_HEAD_START_US")) : kHeadStartUs;
+#else
+    constexpr int head_us = kHeadStartUs;
+#endif
+    // (the one-launch scan occupies 3/4 of the CUs: the select's 64 workgroups always fit beside it)
+    if (head_us > 0 && !p.fused) hipLaunchKernelGGL(head_start_kernel, dim3(1), dim3(64), 0, p.sL, head_us, 4096);
+  }
+  // (a filtered pass has its slot already: its threshold kernel reports into it)
+  if (!p.mc) {
+    p.slot.slot = alloc_slot(h);
+    if (p.slot.slot < 0) { ts_set_error("no free report slot"); return TS_ERR_INVALID; }
+  }
+  // (filtered: need_check_kernel, min(k, N_q))
+  const SelParams sel = cand_select_params(h, W, p.k, p.mc ? 0u : (uint32_t)std::min<int64_t>(p.k, p.N), p.out_s,
+                                           p.out_i, p.slot.slot);
+  if (p.mc) {
+    TS_CHECK(ts_launch_need_check(W.cand_cnt(), W.mask_dev()->need, p.nq, W.status(), sel.host_report, p.sL));
+  } else {
+    uint32_t* rep = h->host_status + (size_t)p.slot.slot * TS_SLOT_WORDS;
+    for (int i = 0; i < 65; ++i) rep[i] = 0;
+  }
+  TS_CHECK(ts_launch_select(sel, p.nq, p.sL));
+  TS_CHECK(p.set.done(p.sL));
+  if (p.pipe) TS_HIP(hipStreamWaitEvent(p.s, W.ev_sel, 0));  // later work on the caller's stream sees the result
+  return TS_OK;
+}
+
+// The synchronous end of a filter pass: wait, read the report, and redo the pass exactly where a threshold was too
+// high (fewer than k survivors) or too low (candidate list overflowed, e.g. massive score ties).
+static int pass_verify(Pass& p) {
+  ts_index* h = p.h;
+  ts_index::WSet& W = *p.set.W;
+  const MaskCtx* mc = p.mc;
+  const uint32_t* rep = h->host_status + (size_t)p.slot.slot * TS_SLOT_WORDS;
+  prof_mark(h, p.pc, -1, p.s);
+  TS_HIP(hipStreamSynchronize(p.s));
+  prof_collect(h, p.pc);
+  uint32_t maxc = 0;
+  for (int i = 0; i < p.nq; ++i) maxc = std::max(maxc, rep[i]);
+  const bool redo = rep[64] != 0;
+  set_info(h, (redo ? 2 : 1) | (p.fused ? 16 : 0), maxc, p.S, p.m);
+  if (mc) add_filter_info(h, p.fseq, rep[65], p.nblk, false);
+  if (mc && mc->bias) add_bias_info(h, true, redo, (int64_t)rep[65] + (redo ? p.nblk : 0));
+  if (!redo) return TS_OK;
+  if (p.fused) {   // (no prepared query image yet; a threshold workgroup that gave up may have left entries behind)
+    W.hist_dirty = true;
+    TS_CHECK(ts_launch_qprep(h->L, p.dq, p.q_dtype, p.nq, p.qh, (uint4*)W.qimg.p, W.cand_cnt(), W.status(), p.s));
+  }
+  prof_mark(h, p.pc, 5, p.s);
+  TS_CHECK(dense_path(h, W, p.nq, p.qh, p.k, p.out_s, p.out_i, p.s, mc, p.pkg));
+  prof_mark(h, p.pc, -1, p.s);
+  TS_HIP(hipStreamSynchronize(p.s));
+  prof_collect(h, p.pc);
+  return TS_OK;
+}
+
+// A pass has three phases, each touching one workspace set W:
+//   P   query prep, sample scan, thresholds      writes W.qimg, W.sample, W.tau; clears W.cand_cnt
+//   S   fused scan+filter over the whole shard   reads W.qimg, W.tau; writes W.cand_*
+//   Sel exact top-k of the candidates            reads W.cand_*; writes the caller's outputs + host slot
+// Normally all three are enqueued on the caller's stream.  With TS_FLAG_PIPELINE they go to
+// three internal streams chained by events (P -> S -> Sel), and the caller's stream only waits
+// for Sel: P of the NEXT search and Sel of the PREVIOUS one then run beside the current S, which
+// leaves an eighth of the CUs free and is HBM-bound anyway.  Passes alternate between two
+// workspace sets; a set is reused only after the Sel that last read it (its ev_sel).
+//
 // Filtered passes (mc != null) take the five-launch path with the live-block list and the masked scan
 // (f16 / bf16 storage), or the dense path with masked selection (fp32 storage, small corpora, large k,
 // TS_FLAG_NO_FILTER, fallback).
-
-static int search_pass_on(ts_index* h, ts_index::WSet& W, const void* dq, int nq, int q_dtype, int k,
-                          float* out_s, int64_t* out_i, uint32_t flags, hipStream_t s, const MaskCtx* mc, int pkg) {
+static int search_pass_on(ts_index* h, SetLease& set, const void* dq, int nq, int q_dtype, int k, float* out_s,
+                          int64_t* out_i, uint32_t flags, hipStream_t s, const MaskCtx* mc, int pkg) {
+  ts_index::WSet& W = *set.W;
   const int64_t N = h->ntotal;
   const int64_t nblk = (N + TS_ROWS_PER_BLOCK - 1) / TS_ROWS_PER_BLOCK;
   const int qh = nq > 32 ? 2 : 1;
@@ -885,8 +1292,8 @@ static int search_pass_on(ts_index* h, ts_index::WSet& W, const void* dq, int nq
     fseq = h->fseq;
   }
   if (h->L.dtype == TS_FP8_E4M3 || h->L.dtype == TS_MXFP4_E2M1 || pkg) {
-    // e4m3 and 4-bit MX storage and the prefix scans have the five-launch kernels only (ts_scan_fp8.hip, ts_scan_prefix.hip): as
-    // for a masked pass
+    // e4m3 and 4-bit MX storage and the prefix scans have the five-launch kernels only (ts_scan_fp8.hip,
+    // ts_scan_prefix.hip): as for a masked pass
     flags &= ~(uint32_t)(TS_FLAG_ONE_LAUNCH | TS_FLAG_PIPELINE);
     flags |= TS_FLAG_CLASSIC;
   }
@@ -913,295 +1320,54 @@ static int search_pass_on(ts_index* h, ts_index::WSet& W, const void* dq, int nq
                      plan_fused(h, N, nblk, k, pipe, &fp);   // (fp32 storage at 32 queries per pass: the split scan, five launches)
   // (the one-launch search has no preparation phase: what remains of "P" rides on the scan stream)
   hipStream_t sP = pipe ? (fused ? h->s_scan : h->s_pro) : s, sS = pipe ? h->s_scan : s, sL = pipe ? h->s_sel : s;
-  // the set may still be in use on the GPU by the (asynchronous) search that had it last, possibly
-  // on another stream
-  // (asked first whether that search is already over — with eight sets in rotation it normally is: a wait on
-  // another stream's event in front of every scan, even a satisfied one, costs the scan stream 10-20 us)
-  if (W.used && hipEventQuery(W.ev_sel) != hipSuccess) TS_HIP(hipStreamWaitEvent(sP, W.ev_sel, 0));
+  TS_CHECK(set.wait_previous(sP));
   // the output buffers may be memory the caller's stream is still reading (a recycled
   // allocation): the final phase must not start before the stream's work issued so far
   if (pipe) TS_HIP(hipEventRecord(W.ev_in, s));
 
-  ProfCtx pc;
-  pc.now = h->profiling && (h->prof_seq.fetch_add(1, std::memory_order_relaxed) % (uint64_t)h->prof_every == 0);
-  pc.scan_only = async;
-  prof_mark(h, pc, 0, sP);
+  Pass p{h, set, dq, nq, q_dtype, qh, k, pkg, out_s, out_i, mc, N, nblk, fseq, async, pipe, fused, s, sP, sS, sL, {h, -1}};
+  p.pc.now = h->profiling && (h->prof_seq.fetch_add(1, std::memory_order_relaxed) % (uint64_t)h->prof_every == 0);
+  p.pc.scan_only = async;
+  prof_mark(h, p.pc, 0, sP);
   if (!fused) TS_CHECK(ts_launch_qprep(QL, dq, q_dtype, nq, qh, (uint4*)W.qimg.p, W.cand_cnt(), W.status(), sP));
-  if (!filter) {
-    set_info(h, 0, 0, 0, 0);
-    if (mc) add_filter_info(h, fseq, nblk, nblk, true);
-    if (mc && mc->bias) add_bias_info(h, false, false, nblk);
-    prof_mark(h, pc, 5, s);
-    TS_CHECK(dense_path(h, W, nq, qh, k, out_s, out_i, s, mc, pkg));
-    prof_mark(h, pc, -1, s);
-    TS_HIP(hipEventRecord(W.ev_sel, s));
-    W.used = true;
-    if (async) return TS_OK;  // exact by construction: nothing to verify
-    TS_HIP(hipStreamSynchronize(s));
-    prof_collect(h, pc);
-    return TS_OK;
-  }
-  int64_t S = 0;
-  uint32_t m = 0;
+  if (!filter) return pass_dense(p);
   // the report slot: the select kernel writes the candidate counts and the status word into it, a filtered
   // pass's threshold kernel also the live-block count (word 65)
-  SlotGuard slot_guard(h, -1);   // every early return below gives the slot back
   if (mc) {
-    slot_guard.slot = alloc_slot(h);
-    if (slot_guard.slot < 0) { ts_set_error("no free report slot"); return TS_ERR_INVALID; }
-    for (int i = 0; i < 66; ++i) h->host_status[(size_t)slot_guard.slot * TS_SLOT_WORDS + i] = 0;
+    p.slot.slot = alloc_slot(h);
+    if (p.slot.slot < 0) { ts_set_error("no free report slot"); return TS_ERR_INVALID; }
+    for (int i = 0; i < 66; ++i) h->host_status[(size_t)p.slot.slot * TS_SLOT_WORDS + i] = 0;
   }
   TS_CHECK(ensure(W.cand_score, (size_t)TS_MAX_Q * kCandCap * 4));
   TS_CHECK(ensure(W.cand_id, (size_t)TS_MAX_Q * kCandCap * 4));
-  if (fused) {
-    // ---- ONE launch: query image, thresholds and scan+filter (see ts_fused.hip)
-    if (!W.hist.p) {
-      TS_CHECK(ensure(W.hist, ts_fused_keys_bytes()));
-      W.hist_dirty = true;
-    }
-    if (W.hist_dirty) {
-      // a launch on this set gave up somewhere: slots may hold stale keys, and sample workgroups that left before
-      // reporting have put the arrival counter behind its running goal for good — start all three from zero
-      TS_HIP(hipMemsetAsync(W.hist.p, 0, ts_fused_keys_bytes(), sS));
-      TS_HIP(hipMemsetAsync(W.cand_cnt(), 0, 256, sS));
-      TS_HIP(hipMemsetAsync(W.arrive(), 0, 4, sS));
-      W.arrive_total = 0;
-      W.hist_dirty = false;
-    }
-    if (++W.gen == 0) W.gen = 1;
-    W.arrive_total += fp.sample_waves;
-    TsFusedArgs a{};
-    a.corpus = h->corpus;
-    a.queries = dq;
-    a.q_dtype = q_dtype;
-    a.nq = nq;
-    a.nblk = nblk;
-    a.ntotal = N;
-    a.scan_wgs = fp.scan_wgs;
-    a.tau_wgs = fp.tau_wgs;
-    a.n_sample = fp.n_sample;
-    a.sample_stride = fp.sample_stride;
-    a.m = fp.m;
-    a.expect = fp.expect;
-    a.gen = W.gen;
-    a.arrive_goal = W.arrive_total;
-    a.wait_iters = 40000;
-    a.skeys = (uint32_t*)W.hist.p;
-    a.arrive = W.arrive();
-    a.tau64 = W.tau64();
-    a.cand_cnt = W.cand_cnt();
-    a.cand_score = (float*)W.cand_score.p;
-    a.cand_id = (int32_t*)W.cand_id.p;
-    a.cand_cap = kCandCap;
-    prof_mark(h, pc, 3, sS);
-    TS_CHECK(ts_launch_fused(h->L, qh, a, sS));
-    prof_mark(h, pc, 4, sS);
-    S = fp.sample_rows;
-    m = fp.m;
-  } else {
-  // ---- five launches: sample -> thresholds -> scan+filter (-> select below)
-  int64_t nsb = std::max(kMinSampleRows, N / kSampleDiv) / TS_ROWS_PER_BLOCK;
-  // one sample block per scan wave (8 waves per CU): a ragged last round would
-  // make the short sample scan ~1.7x longer than it has to be
-  const int64_t round = (int64_t)h->num_cus * 8;
-  if (nsb > round) nsb -= nsb % round;
-  nsb = std::min(nsb, nblk);
-  const int64_t sstride = nblk / nsb;
-  S = nsb * TS_ROWS_PER_BLOCK;
-  // expected survivors per query ~ oversample * k; 3x for large k keeps the worst query of a
-  // batch (about 1.5x the mean) well inside the 16384 candidate slots
-  const int64_t oversample = k > 1024 ? 3 : kOversample;
-  m = (uint32_t)((oversample * (int64_t)k * S + N - 1) / N);
-  m = std::max(m, kMinSampleRank);
-  TS_CHECK(ensure(W.sample, (size_t)nq * S * 4));
-
-  ScanParams sp{};
-  sp.corpus = h->corpus;
-  sp.qimg = (const uint4*)W.qimg.p;
-  sp.kg = h->L.kg;
-  sp.nq = nq;
-  sp.ntotal = N;
-  // (1) dense scores of a strided sample of row blocks
-  sp.nwork = nsb;
-  sp.blk0 = 0;
-  sp.blk_stride = sstride;
-  sp.dense = (float*)W.sample.p;
-  sp.dense_ld = S;
-  prof_mark(h, pc, 1, sP);
-  TS_CHECK(scan_rows(h, pkg, SCAN_DENSE, qh, sp, h->num_cus, sP));
-  prof_mark(h, pc, 2, sP);
-  // (2) per-query threshold = ~m-th best sample score
-#ifdef TS_TUNING  // ablation builds only (tools/variants.sh): thresholds = +inf, nothing survives
-  static const bool dbg_tau_inf = getenv("TS_DEBUG_TAU_INF") != nullptr;
-#else
-  constexpr bool dbg_tau_inf = false;
-#endif
-  TsMaskDev* md = nullptr;
-  if (mc) {
-    // (2') the live-block list of the pass, then per query the m_q-th best ALLOWED sample score
-    TS_CHECK(ensure(W.mask, sizeof(TsMaskDev) + (size_t)nblk * 4));
-    md = (TsMaskDev*)W.mask.p;
-    TS_HIP(hipMemsetAsync(md, 0, sizeof(TsMaskDev), sP));
-    TS_CHECK(ts_launch_live_blocks(mc->bits, mc->words, mc->mp, nblk, N, md, sP));
-    if (mc->bias)   // boosted: the m_q-th best allowed sample score + bias
-      TS_CHECK(ts_launch_tau_biased((const float*)W.sample.p, S, sstride, N, mc->bits, mc->words, mc->bias, md, nq, k,
-                                    (uint32_t)oversample, kMinSampleRank, W.tau(),
-                                    h->host_status_dev + (size_t)slot_guard.slot * TS_SLOT_WORDS + 65, sP));
-    else
-    TS_CHECK(ts_launch_tau_masked((const float*)W.sample.p, S, sstride, N, mc->bits, mc->words, md, nq, k,
-                                  (uint32_t)oversample, kMinSampleRank, W.tau(),
-                                  h->host_status_dev + (size_t)slot_guard.slot * TS_SLOT_WORDS + 65, sP));
-  } else {
-  TS_CHECK(ts_launch_tau((const float*)W.sample.p, S, dbg_tau_inf ? 0xFFFFFFFFu : (uint32_t)S, m, nq,
-                         W.tau(), sP));
+  if (fused) TS_CHECK(pass_one_launch(p, fp));
+  else TS_CHECK(pass_five_launch(p));
+  TS_CHECK(pass_select(p));
+  if (!async) return pass_verify(p);
+  // verified later, by ts_index_finish(); nothing here waits for the GPU
+  std::lock_guard<std::mutex> lk(h->mu);
+  ts_index::Pending& pe = push_pending(h, p.slot.slot, nq, p.S, p.m, fused ? (int)(&W - h->ws) : -1, mc ? fseq : -1);
+  if (mc) { h->finfo[1] += (fseq == h->fseq) ? nblk : 0; h->finfo[2] += (fseq == h->fseq) ? 1 : 0; }
+  if (p.pc.now && p.pc.nev == 2) {  // the scan+filter interval of this pass (prof_mu is held: h->ev is ours)
+    pe.e0 = h->ev[0]; pe.e1 = h->ev[1];
+    // hand the two events over and give the handle fresh ones
+    hipEvent_t n0 = nullptr, n1 = nullptr;
+    if (hipEventCreate(&n0) == hipSuccess && hipEventCreate(&n1) == hipSuccess) { h->ev[0] = n0; h->ev[1] = n1; }
+    else { pe.e0 = pe.e1 = nullptr; }
   }
-  if (pipe) {
-    TS_HIP(hipEventRecord(W.ev_pro, sP));
-    TS_HIP(hipStreamWaitEvent(sS, W.ev_pro, 0));
-  }
-  // (3) the full scan; only scores >= tau leave the registers.  It occupies 7/8 of the CUs:
-  // the kernel is HBM-bound (measured: 224 CUs stream 1.5 % FASTER than 256, tools/cus.sh)
-  // and the free CUs are where the neighbouring searches' small kernels run.
-  sp.nwork = nblk;
-  sp.blk_stride = 1;
-  sp.dense = nullptr;
-  sp.tau = W.tau();
-  sp.cand_cnt = W.cand_cnt();
-  sp.cand_score = (float*)W.cand_score.p;
-  sp.cand_id = (int32_t*)W.cand_id.p;
-  sp.cand_cap = kCandCap;
-  int scan_cus = h->num_cus - h->num_cus / 8;
-#ifdef TS_TUNING  // ablation builds only: how many CUs the fused scan may occupy
-  static const int dbg_cus = getenv("TS_SCAN_CUS") ? atoi(getenv("TS_SCAN_CUS")) : 0;
-  if (dbg_cus > 0) scan_cus = dbg_cus;
-#endif
-  prof_mark(h, pc, 3, sS);
-  if (mc) {
-    MaskedScanParams mp{};
-    static_cast<ScanParams&>(mp) = sp;
-    mp.live = reinterpret_cast<const int32_t*>(md + 1);
-    mp.nlive = &md->nlive;
-    mp.allow_bits = mc->bits;
-    mp.allow_words = mc->words;
-    mp.qmask = md->qmask;
-    if (mc->bias) {
-      BiasScanParams bp{};
-      static_cast<MaskedScanParams&>(bp) = mp;
-      bp.bias = mc->bias;
-      bp.bias_tail = mc->bias_tail;
-      bp.tail_blk = (N % TS_ROWS_PER_BLOCK) ? N / TS_ROWS_PER_BLOCK : -1;
-      TS_CHECK(ts_launch_scan_biased(h->L, qh, bp, scan_cus, sS));
-    } else if (pkg) {
-      PrefixMaskedScanParams pp{};
-      static_cast<MaskedScanParams&>(pp) = mp;
-      pp.kg = pkg;
-      pp.kg_row = h->L.kg;
-      TS_CHECK(ts_launch_scan_prefix_masked(h->L, qh, pp, scan_cus, sS));
-    } else {
-    TS_CHECK(ts_launch_scan_masked(h->L, qh, mp, scan_cus, sS));
-    }
-  } else {
-  TS_CHECK(scan_rows(h, pkg, SCAN_FILTER, qh, sp, scan_cus, sS));
-  }
-  prof_mark(h, pc, 4, sS);
-  }  // five launches
-  if (pipe) {
-    TS_HIP(hipEventRecord(W.ev_scan, sS));
-    TS_HIP(hipStreamWaitEvent(sL, W.ev_scan, 0));
-    TS_HIP(hipStreamWaitEvent(sL, W.ev_in, 0));
-    // This select and the NEXT search's scan wait for the same event.  If the select's 64
-    // workgroups (128 KiB of LDS each: they cannot share a CU with a scan workgroup) are placed
-    // first they take 64 CUs, 32 of the scan's 224 persistent workgroups have to wait for them,
-    // and the whole scan ends that much later — stream priority does not prevent it (measured:
-    // overlapped scans of 0.305-0.326 ms instead of 0.289 at 1.25 M rows, 2.263 instead of 2.207
-    // at 10 M).  A head start of a few microseconds for the scan does: the select then finds the
-    // 32 CUs the scan grid leaves free.
-#ifdef TS_TUNING
-    static const int head_us = getenv("TS_HEAD_START_US") ? atoi(getenv("TS_HEAD_START_US")) : kHeadStartUs;
-#else
-    constexpr int head_us = kHeadStartUs;
-#endif
-    // (the one-launch scan occupies 3/4 of the CUs: the select's 64 workgroups always fit beside it)
-    if (head_us > 0 && !fused) hipLaunchKernelGGL(head_start_kernel, dim3(1), dim3(64), 0, sL, head_us, 4096);
-  }
-  // (4) exact top-k of the candidates; verifies that >= k of them exist
-  SelParams p{};
-  p.mode = SEL_PAIRS32;
-  p.scores = (const float*)W.cand_score.p;
-  p.ids32 = (const int32_t*)W.cand_id.p;
-  p.stride = kCandCap;
-  p.n_per_q = W.cand_cnt();
-  p.n_cap = kCandCap;
-  p.need = mc ? 0u : (uint32_t)std::min<int64_t>(k, N);   // (filtered: need_check_kernel, min(k, N_q))
-  p.k = k;
-  p.out_scores = out_s;
-  p.out_ids64 = out_i;
-  p.out_stride = k;
-  p.id_offset = h->id_offset;
-  p.status = W.status();
-  p.clear_counts = W.cand_cnt();   // counts go back to zero: the one-launch search has no preparation kernel to do it
-  // the select kernel reports the candidate counts and the status word straight
-  // into mapped host memory: no copy kernel between it and the sync; every search in flight
-  // has its own slot of the ring
-  if (!mc) {
-    slot_guard.slot = alloc_slot(h);
-    if (slot_guard.slot < 0) { ts_set_error("no free report slot"); return TS_ERR_INVALID; }
-  }
-  const int slot = slot_guard.slot;
-  uint32_t* rep = h->host_status + (size_t)slot * TS_SLOT_WORDS;
-  p.host_report = h->host_status_dev + (size_t)slot * TS_SLOT_WORDS;
-  if (mc) {
-    TS_CHECK(ts_launch_need_check(W.cand_cnt(), ((TsMaskDev*)W.mask.p)->need, nq, W.status(), p.host_report, sL));
-  } else {
-    for (int i = 0; i < 65; ++i) rep[i] = 0;
-  }
-  TS_CHECK(ts_launch_select(p, nq, sL));
-  TS_HIP(hipEventRecord(W.ev_sel, sL));
-  W.used = true;
-  if (pipe) TS_HIP(hipStreamWaitEvent(s, W.ev_sel, 0));  // later work on the caller's stream sees the result
-  if (async) {
-    // verified later, by ts_index_finish(); nothing here waits for the GPU
-    std::lock_guard<std::mutex> lk(h->mu);
-    ts_index::Pending& pe = h->pending[h->npending];
-    pe.ticket = h->next_ticket; pe.slot = slot; pe.nq = nq; pe.S = (uint32_t)S; pe.m = m;
-    pe.e0 = pe.e1 = nullptr;
-    pe.set = fused ? (int)(&W - h->ws) : -1;
-    pe.fseq = mc ? fseq : -1;
-    if (mc) { h->finfo[1] += (fseq == h->fseq) ? nblk : 0; h->finfo[2] += (fseq == h->fseq) ? 1 : 0; }
-    if (pc.now && pc.nev == 2) {  // the scan+filter interval of this pass (prof_mu is held: h->ev is ours)
-      pe.e0 = h->ev[0]; pe.e1 = h->ev[1];
-      // hand the two events over and give the handle fresh ones
-      hipEvent_t n0 = nullptr, n1 = nullptr;
-      if (hipEventCreate(&n0) == hipSuccess && hipEventCreate(&n1) == hipSuccess) { h->ev[0] = n0; h->ev[1] = n1; }
-      else { pe.e0 = pe.e1 = nullptr; }
-    }
-    ++h->npending;
-    slot_guard.handed_over();   // ts_index_finish() frees it
-    return TS_OK;
-  }
-  prof_mark(h, pc, -1, s);
-  TS_HIP(hipStreamSynchronize(s));
-  prof_collect(h, pc);
-  uint32_t maxc = 0;
-  for (int i = 0; i < nq; ++i) maxc = std::max(maxc, rep[i]);
-  const bool redo = rep[64] != 0;
-  set_info(h, (redo ? 2 : 1) | (fused ? 16 : 0), maxc, S, m);
-  if (mc) add_filter_info(h, fseq, rep[65], nblk, false);
-  if (mc && mc->bias) add_bias_info(h, true, redo, (int64_t)rep[65] + (redo ? nblk : 0));
-  if (redo) {
-    // a threshold was too high (fewer than k survivors) or too low (candidate
-    // list overflowed, e.g. massive score ties): redo this pass exactly.
-    if (fused) {   // (no prepared query image yet; a threshold workgroup that gave up may have left entries behind)
-      W.hist_dirty = true;
-      TS_CHECK(ts_launch_qprep(h->L, dq, q_dtype, nq, qh, (uint4*)W.qimg.p, W.cand_cnt(), W.status(), s));
-    }
-    prof_mark(h, pc, 5, s);
-    TS_CHECK(dense_path(h, W, nq, qh, k, out_s, out_i, s, mc, pkg));
-    prof_mark(h, pc, -1, s);
-    TS_HIP(hipStreamSynchronize(s));
-    prof_collect(h, pc);
-  }
+  p.slot.handed_over();   // ts_index_finish() frees it
   return TS_OK;
+}
+
+// pkg > 0 (ts_index_search_prefix): the pass ranks on the first pkg k groups of every row; dq holds 16 * pkg elements
+// per query
+static int search_pass(ts_index* h, const void* dq, int nq, int q_dtype, int k, float* out_s,
+                       int64_t* out_i, uint32_t flags, hipStream_t s, const MaskCtx* mc = nullptr, int pkg = 0) {
+  // per-phase timing shares one set of events per handle: profiled searches run one at a time
+  std::unique_lock<std::mutex> plk(h->prof_mu, std::defer_lock);
+  if (h->profiling) plk.lock();
+  SetLease set(h);
+  return search_pass_on(h, set, dq, nq, q_dtype, k, out_s, out_i, flags, s, mc, pkg);
 }
 
 // ---- coalesced passes (TS_FLAG_COALESCE)
@@ -1240,7 +1406,7 @@ static int co_pass_width(const ts_index* h, int k, uint32_t flags) {
     return 0;
   if (k > kMaxFilterK || N < kMinFilterRows || N < 32 * (int64_t)k) return 0;
   if (!(flags & TS_FLAG_CLASSIC) && N <= kOneLaunchMaxRows) return 0;   // the one-launch search's regime
-  const int grid = h->num_cus - h->num_cus / 8;
+  const int grid = filter_scan_cus(h);
   bool wide = (int64_t)nblk * (int64_t)ts_block_bytes(h->L) > kWideMinCorpusBytes &&
               h->co_gmax <= kWideMaxResidentGroups;
   if (h->co_gstat > 0 && h->nremoved == 0 && !(flags & TS_FLAG_NO_STATIONARY_PASSES) &&
@@ -1281,17 +1447,8 @@ static void co_fill_params(const ts_index* h, int G, P& mp) {
 
 // the dense scan of a batch's sample by scan_kernel (one launch per batch)
 static int co_sample_scan(ts_index* h, const ts_index::CoBatch& b, hipStream_t s) {
-  ScanParams sp{};
-  sp.corpus = h->corpus;
-  sp.qimg = (const uint4*)b.W->qimg.p;
-  sp.kg = h->L.kg;
-  sp.nq = b.nq;
-  sp.ntotal = h->ntotal;
-  sp.nwork = b.nsb;
-  sp.blk0 = 0;
-  sp.blk_stride = b.sstride;
-  sp.dense = (float*)b.W->sample.p;
-  sp.dense_ld = b.S;
+  ScanParams sp = scan_base(h, *b.W, b.nq);
+  scan_window(sp, 0, b.nsb, b.sstride, (float*)b.W->sample.p, b.S);
   return ts_launch_scan(h->L, SCAN_DENSE, b.qh, sp, h->num_cus, s);
 }
 
@@ -1415,8 +1572,8 @@ static int co_launch_pass(ts_index* h) {
     co_fill_params(h, G, mp);
     mp.stage_cap = ts_scan_multi_stage_cap(h->L, G);
     mp.live = (const uint32_t*)h->live.p;
-    st = tomb ? ts_launch_scan_multi_tomb(h->L, G, mp, h->num_cus - h->num_cus / 8, s)
-              : ts_launch_scan_multi(h->L, G, mp, h->num_cus - h->num_cus / 8, s);
+    st = tomb ? ts_launch_scan_multi_tomb(h->L, G, mp, filter_scan_cus(h), s)
+              : ts_launch_scan_multi(h->L, G, mp, filter_scan_cus(h), s);
   } else {
     WideTombParams wp{};
     co_fill_params(h, G, wp);
@@ -1449,24 +1606,8 @@ static int co_launch_pass(ts_index* h) {
     if (b.groups_left > 0) h->co_batch[keep++] = b;
     else fin[nfin++] = b;
   }
-  auto sel_params = [&](const ts_index::CoBatch& b) {
-    SelParams p{};
-    p.mode = SEL_PAIRS32;
-    p.scores = (const float*)b.W->cand_score.p;
-    p.ids32 = (const int32_t*)b.W->cand_id.p;
-    p.stride = kCandCap;
-    p.n_per_q = b.W->cand_cnt();
-    p.n_cap = kCandCap;
-    p.need = tomb ? 0u : (uint32_t)std::min<int64_t>(b.k, N);   // (tomb: need_check_kernel, min(k, live rows))
-    p.k = b.k;
-    p.out_scores = b.out_s;
-    p.out_ids64 = b.out_i;
-    p.out_stride = b.k;
-    p.id_offset = h->id_offset;
-    p.status = b.W->status();
-    p.clear_counts = b.W->cand_cnt();
-    p.host_report = h->host_status_dev + (size_t)b.slot * TS_SLOT_WORDS;
-    return p;
+  auto sel_params = [&](const ts_index::CoBatch& b) {   // (tomb: need_check_kernel, min(k, live rows))
+    return cand_select_params(h, *b.W, b.k, tomb ? 0u : (uint32_t)std::min<int64_t>(b.k, N), b.out_s, b.out_i, b.slot);
   };
   // A queue with the pass prologue: the selects of the pass in one launch (select_batch_kernel), where
   // ts_launch_select would give the batches the same LDS; a batch that differs keeps a launch of its own below.
@@ -1497,8 +1638,7 @@ static int co_launch_pass(ts_index* h) {
     if (ok) {
       if (!launched[i]) {
         const SelParams p = sel_params(b);
-        if (tomb) st = ts_launch_need_check(b.W->cand_cnt(), ((TsMaskDev*)b.W->mask.p)->need, b.nq, b.W->status(),
-                                            p.host_report, s);
+        if (tomb) st = ts_launch_need_check(b.W->cand_cnt(), b.W->mask_dev()->need, b.nq, b.W->status(), p.host_report, s);
         if (st == TS_OK) st = ts_launch_select(p, b.nq, s);
       }
       if (st == TS_OK) {
@@ -1556,69 +1696,51 @@ static int co_flush(ts_index* h, hipStream_t s) {
 // queue's.
 static int co_submit(ts_index* h, const void* dq, int nq, int q_dtype, int k, float* out_s, int64_t* out_i,
                      hipStream_t s) {
-  const int64_t N = h->ntotal;
-  const int64_t nblk = (N + TS_ROWS_PER_BLOCK - 1) / TS_ROWS_PER_BLOCK;
   const int qh = nq > 32 ? 2 : 1;
   // the pass prologue: the sample scan and the thresholds read only the set's own image and sample buffer, and go in
   // front of the batch's first pass (co_pass_prologue)
   const bool defer = h->co_prologue && h->nremoved == 0;
-  ts_index::WSet* W = acquire_set(h);   // (at most co_width - 1 < TS_NSETS sets are held by the queue here)
-  struct SetGuard {
-    ts_index* h; ts_index::WSet* W;
-    ~SetGuard() { if (W) release_set(h, W); }
-  } set_guard{h, W};
+  SetLease set(h);   // (at most co_width - 1 < TS_NSETS sets are held by the queue here)
+  ts_index::WSet* W = set.W;
   SlotGuard slot_guard(h, alloc_slot(h));
   if (slot_guard.slot < 0) { ts_set_error("no free report slot"); return TS_ERR_INVALID; }
-  if (W->used && hipEventQuery(W->ev_sel) != hipSuccess) TS_HIP(hipStreamWaitEvent(s, W->ev_sel, 0));
+  TS_CHECK(set.wait_previous(s));
   TS_CHECK(ts_launch_qprep(h->L, dq, q_dtype, nq, qh, (uint4*)W->qimg.p, W->cand_cnt(), W->status(), s));
   TS_CHECK(ensure(W->cand_score, (size_t)TS_MAX_Q * kCandCap * 4));
   TS_CHECK(ensure(W->cand_id, (size_t)TS_MAX_Q * kCandCap * 4));
-  // the five-launch geometry of search_pass_on, with a lower survivor target: three groups share the staging area
-  // that two have in scan_kernel (ts_scan.hip, scan_multi_kernel)
-  int64_t nsb = std::max(kMinSampleRows, N / kSampleDiv) / TS_ROWS_PER_BLOCK;
-  const int64_t round = (int64_t)h->num_cus * 8;
-  if (nsb > round) nsb -= nsb % round;
-  nsb = std::min(nsb, nblk);
-  const int64_t sstride = nblk / nsb;
-  const int64_t S = nsb * TS_ROWS_PER_BLOCK;
-  const int64_t oversample = kCoalesceOversample;
-  uint32_t m = (uint32_t)((oversample * (int64_t)k * S + N - 1) / N);
-  m = std::max(m, kMinSampleRank);
-  TS_CHECK(ensure(W->sample, (size_t)nq * S * 4));
-  ts_index::CoBatch cb{W, nq, qh, k, slot_guard.slot, qh, out_s, out_i, m, S, sstride, nsb, !defer, false};
-  if (!defer) TS_CHECK(co_sample_scan(h, cb, s));
+  // the five-launch geometry with a lower survivor target: three groups share the staging area that two have in
+  // scan_kernel (ts_scan.hip, scan_multi_kernel)
+  const SampleGeom g = sample_geometry(h, k, kCoalesceOversample);
+  TS_CHECK(ensure(W->sample, (size_t)nq * g.S * 4));
+  ts_index::CoBatch cb{W, nq, qh, k, slot_guard.slot, qh, out_s, out_i, g.m, g.S, g.sstride, g.nsb, !defer, false};
   if (defer) {
     // (co_pass_prologue)
   } else if (h->nremoved > 0) {
     // removed rows: the thresholds of the filtered path (tau_masked_kernel) with the live words as the
     // batch's one mask: the m_q-th best LIVE sample score with N_q = the live rows; need[q] = min(k, live rows)
-    TS_CHECK(ensure(W->mask, sizeof(TsMaskDev) + (size_t)nblk * 4));
-    TsMaskDev* md = (TsMaskDev*)W->mask.p;
-    TsMaskPass mp{};
-    mp.nd = 1;
-    mp.dist[0] = 0;
-    for (int j = 0; j < TS_MAX_Q; ++j) { mp.qmask[j] = j < nq ? 0 : -1; mp.qd[j] = j < nq ? 0 : -1; }
-    TS_HIP(hipMemsetAsync(md, 0, sizeof(TsMaskDev), s));
-    TS_CHECK(ts_launch_live_blocks((const uint32_t*)h->live.p, nblk, mp, nblk, N, md, s));
-    TS_CHECK(ts_launch_tau_masked((const float*)W->sample.p, S, sstride, N, (const uint32_t*)h->live.p, nblk, md, nq,
-                                  k, (uint32_t)oversample, kMinSampleRank, W->tau(), nullptr, s));
+    TS_CHECK(co_sample_scan(h, cb, s));
+    MaskCtx live{};
+    live.bits = (const uint32_t*)h->live.p;
+    live.words = (h->ntotal + TS_ROWS_PER_BLOCK - 1) / TS_ROWS_PER_BLOCK;   // one word per row block
+    const int32_t mask0[TS_MAX_Q] = {};
+    build_mask_pass(mask0, nq, live.mp);
+    TS_CHECK(launch_live_blocks(h, *W, live, s));
+    TS_CHECK(ts_launch_tau_masked((const float*)W->sample.p, g.S, g.sstride, h->ntotal, live.bits, live.words,
+                                  W->mask_dev(), nq, k, (uint32_t)kCoalesceOversample, kMinSampleRank, W->tau(), nullptr,
+                                  s));
   } else {
-  TS_CHECK(ts_launch_tau((const float*)W->sample.p, S, (uint32_t)S, m, nq, W->tau(), s));
+    TS_CHECK(co_sample_scan(h, cb, s));
+    TS_CHECK(ts_launch_tau((const float*)W->sample.p, g.S, (uint32_t)g.S, g.m, nq, W->tau(), s));
   }
   uint32_t* rep = h->host_status + (size_t)slot_guard.slot * TS_SLOT_WORDS;
   for (int i = 0; i < 65; ++i) rep[i] = 0;
   {
     std::lock_guard<std::mutex> lk(h->mu);
-    ts_index::Pending& pe = h->pending[h->npending];
-    pe.ticket = h->next_ticket; pe.slot = slot_guard.slot; pe.nq = nq; pe.S = (uint32_t)S; pe.m = m;
-    pe.e0 = pe.e1 = nullptr;
-    pe.set = -1;
-    pe.fseq = -1;
-    ++h->npending;
+    push_pending(h, slot_guard.slot, nq, g.S, g.m, -1, -1);
   }
   h->co_batch[h->co_nbatch++] = cb;
   slot_guard.handed_over();
-  set_guard.W = nullptr;   // released by co_launch_pass once its select is enqueued
+  set.detach();   // released by co_launch_pass once its select is enqueued
   int st = TS_OK;
   for (int half = 0; half < qh; ++half) {
     h->co_group[h->co_ngroup++] = ts_index::CoGroup{h->co_nbatch - 1, half};
@@ -1637,6 +1759,106 @@ extern "C" int ts_index_flush(ts_index* h, void* stream) {
   return co_flush_locked(h, (hipStream_t)stream);   // later work on `stream` is ordered behind the flushed passes
 }
 
+// TS_FLAG_ASYNC: a call takes at most 4 passes, and at most a quarter of the report slots hold unfinished passes
+static int admit_async(ts_index* h, int nq, int qp, hipStream_t s) {
+  const int passes = (nq + qp - 1) / qp;
+  if (passes > 4) { ts_set_error("TS_FLAG_ASYNC: at most %d queries per call", 4 * qp); return TS_ERR_INVALID; }
+  bool full = false;
+  {
+    std::lock_guard<std::mutex> lk(h->mu);
+    full = h->npending + passes > TS_ASYNC_SLOTS / 4;
+  }
+  if (!full) return TS_OK;
+  (void)co_flush(h, s);   // nothing stays held behind the error (a filtered search has flushed already)
+  ts_set_error("too many unfinished asynchronous searches; call ts_index_finish()");
+  return TS_ERR_INVALID;
+}
+
+namespace {
+// The device side of a call's queries, masks and results: the caller's own pointers, or with TS_FLAG_HOST_PTR the
+// handle's one staging area, held under host_mu until the call ends.
+struct CallBuffers {
+  ts_index* h;
+  std::unique_lock<std::mutex> lk;
+  explicit CallBuffers(ts_index* h_) : h(h_), lk(h_->host_mu, std::defer_lock) {}
+  const void* dq = nullptr;
+  const uint32_t* bits = nullptr;
+  float* ds = nullptr;
+  int64_t* di = nullptr;
+  // mbytes == 0: no masks; nout == 0: no results of nout scores and ids
+  int in(bool host, const void* queries, size_t qbytes, const uint32_t* allow_bits, size_t mbytes,
+         float* out_scores, int64_t* out_ids, size_t nout, hipStream_t s) {
+    dq = queries;
+    bits = allow_bits;
+    ds = out_scores;
+    di = out_ids;
+    if (!host) return TS_OK;
+    lk.lock();
+    TS_CHECK(ensure(h->qstage, qbytes));
+    if (nout) {
+      TS_CHECK(ensure(h->out_s, nout * 4));
+      TS_CHECK(ensure(h->out_i, nout * 8));
+      ds = (float*)h->out_s.p;
+      di = (int64_t*)h->out_i.p;
+    }
+    TS_HIP(hipMemcpyAsync(h->qstage.p, queries, qbytes, hipMemcpyHostToDevice, s));
+    dq = h->qstage.p;
+    if (mbytes) {
+      TS_CHECK(ensure(h->mstage, mbytes));
+      TS_HIP(hipMemcpyAsync(h->mstage.p, allow_bits, mbytes, hipMemcpyHostToDevice, s));
+      bits = (const uint32_t*)h->mstage.p;
+    }
+    return TS_OK;
+  }
+  // the results back to the caller's host arrays; returns with the stream drained
+  int out(float* out_scores, int64_t* out_ids, size_t nout, hipStream_t s) {
+    if (!lk.owns_lock()) return TS_OK;
+    TS_HIP(hipMemcpyAsync(out_scores, ds, nout * 4, hipMemcpyDeviceToHost, s));
+    TS_HIP(hipMemcpyAsync(out_ids, di, nout * 8, hipMemcpyDeviceToHost, s));
+    TS_HIP(hipStreamSynchronize(s));
+    return TS_OK;
+  }
+};
+
+// Removed rows: every mask of a filtered call is ANDed with the tombstone bitmap on the device, and a
+// query without a mask gets the bitmap itself, so the call is the filtered call of the live rows.  The masks go to
+// h->eff, one call at a time: eff_mu is held until the call ends, and done() records eff_ev behind the call's passes.
+struct LiveMasks {
+  ts_index* h;
+  std::unique_lock<std::mutex> lk;
+  std::vector<int32_t> moq;
+  explicit LiveMasks(ts_index* h_) : h(h_), lk(h_->eff_mu, std::defer_lock) {}
+  int apply(int nq, const uint32_t*& bits, int64_t& allow_words, int32_t& n_masks,
+            const int32_t*& mask_of_query, hipStream_t s) {
+    if (h->nremoved == 0) return TS_OK;
+    const int64_t need_words = (h->ntotal + 31) / 32;
+    lk.lock();
+    TS_CHECK(ensure(h->eff, (size_t)(n_masks + 1) * (size_t)need_words * 4));
+    if (h->eff_used) TS_HIP(hipStreamWaitEvent(s, h->eff_ev, 0));   // the previous call's passes have read `eff`
+    TS_CHECK(ts_launch_and_live(bits, allow_words, n_masks, (const uint32_t*)h->live.p, need_words,
+                                (uint32_t*)h->eff.p, s));
+    moq.assign(mask_of_query, mask_of_query + nq);
+    for (int32_t& m : moq)
+      if (m < 0) m = n_masks;
+    mask_of_query = moq.data();
+    bits = (const uint32_t*)h->eff.p;
+    allow_words = need_words;
+    n_masks += 1;
+    return TS_OK;
+  }
+  int done(hipStream_t s) {
+    if (!lk.owns_lock()) return TS_OK;
+    TS_HIP(hipEventRecord(h->eff_ev, s));
+    h->eff_used = true;
+    return TS_OK;
+  }
+  // the same record behind a call that has failed, which keeps its own error text
+  void done_after_failure(hipStream_t s) {
+    if (lk.owns_lock() && hipEventRecord(h->eff_ev, s) == hipSuccess) h->eff_used = true;
+  }
+};
+}  // namespace
+
 extern "C" int ts_index_search(ts_index* h, const void* queries, int32_t nq, int32_t q_dtype,
                                int32_t k, float* out_scores, int64_t* out_ids, uint32_t flags,
                                void* stream) {
@@ -1646,10 +1868,7 @@ extern "C" int ts_index_search(ts_index* h, const void* queries, int32_t nq, int
     ts_set_error("bad arguments to search");
     return TS_ERR_INVALID;
   }
-  if (h->ntotal == 0) {
-    ts_set_error("No documents indexed. Call add_documents() first.");
-    return TS_ERR_EMPTY;
-  }
+  if (h->ntotal == 0) return err_empty();
   if (h->nremoved > 0 && !co_pass_width(h, k, flags)) {
     // removed rows: the filtered search whose only mask is the tombstone bitmap; a search that
     // joins the coalesced passes takes their tombstone form instead (co_submit, co_launch_pass)
@@ -1659,25 +1878,14 @@ extern "C" int ts_index_search(ts_index* h, const void* queries, int32_t nq, int
   }
   DeviceGuard g(h->device);
   hipStream_t s = (hipStream_t)stream;
-  const int qp = (ts_scan_lds_bytes(h->L, 2) <= 160 * 1024) ? 64 : 32;  // queries per pass
+  const int qp = queries_per_pass(h);
   if ((flags & TS_FLAG_PIPELINE) && !(flags & TS_FLAG_ASYNC)) {
     ts_set_error("TS_FLAG_PIPELINE needs TS_FLAG_ASYNC");
     return TS_ERR_INVALID;
   }
   if (flags & TS_FLAG_ASYNC) {
     if (flags & TS_FLAG_HOST_PTR) { ts_set_error("TS_FLAG_ASYNC needs device pointers"); return TS_ERR_INVALID; }
-    const int passes = (nq + qp - 1) / qp;
-    if (passes > 4) { ts_set_error("TS_FLAG_ASYNC: at most %d queries per call", 4 * qp); return TS_ERR_INVALID; }
-    bool full = false;
-    {
-      std::lock_guard<std::mutex> lk(h->mu);
-      full = h->npending + passes > TS_ASYNC_SLOTS / 4;
-    }
-    if (full) {
-      (void)co_flush(h, s);   // the unfinished-pass limit: nothing stays held behind the error
-      ts_set_error("too many unfinished asynchronous searches; call ts_index_finish()");
-      return TS_ERR_INVALID;
-    }
+    TS_CHECK(admit_async(h, nq, qp, s));
   }
   const size_t qrow = (size_t)h->L.dim * dtype_size(q_dtype);
   if (const int width = co_pass_width(h, k, flags)) {
@@ -1702,36 +1910,19 @@ extern "C" int ts_index_search(ts_index* h, const void* queries, int32_t nq, int
     return TS_OK;
   }
   TS_CHECK(co_flush(h, s));   // a search that cannot join the queue runs after the held ones
-  const void* dq = queries;
-  float* ds = out_scores;
-  int64_t* di = out_ids;
-  const bool host = (flags & TS_FLAG_HOST_PTR) != 0;
-  std::unique_lock<std::mutex> hlk(h->host_mu, std::defer_lock);
-  if (host) {
-    hlk.lock();   // one staging area per handle
-    TS_CHECK(ensure(h->qstage, (size_t)nq * qrow));
-    TS_CHECK(ensure(h->out_s, (size_t)nq * k * 4));
-    TS_CHECK(ensure(h->out_i, (size_t)nq * k * 8));
-    TS_HIP(hipMemcpyAsync(h->qstage.p, queries, (size_t)nq * qrow, hipMemcpyHostToDevice, s));
-    dq = h->qstage.p;
-    ds = (float*)h->out_s.p;
-    di = (int64_t*)h->out_i.p;
-  }
+  CallBuffers b(h);
+  TS_CHECK(b.in((flags & TS_FLAG_HOST_PTR) != 0, queries, (size_t)nq * qrow, nullptr, 0, out_scores, out_ids,
+                (size_t)nq * k, s));
   for (int q0 = 0; q0 < nq; q0 += qp) {
     const int c = std::min(qp, nq - q0);
-    TS_CHECK(search_pass(h, (const char*)dq + (size_t)q0 * qrow, c, q_dtype, k,
-                         ds + (size_t)q0 * k, di + (size_t)q0 * k, flags, s));
+    TS_CHECK(search_pass(h, (const char*)b.dq + (size_t)q0 * qrow, c, q_dtype, k, b.ds + (size_t)q0 * k,
+                         b.di + (size_t)q0 * k, flags, s));
   }
   if (flags & TS_FLAG_ASYNC) {
     std::lock_guard<std::mutex> lk(h->mu);
     ++h->next_ticket;
   }
-  if (host) {
-    TS_HIP(hipMemcpyAsync(out_scores, ds, (size_t)nq * k * 4, hipMemcpyDeviceToHost, s));
-    TS_HIP(hipMemcpyAsync(out_ids, di, (size_t)nq * k * 8, hipMemcpyDeviceToHost, s));
-    TS_HIP(hipStreamSynchronize(s));
-  }
-  return TS_OK;
+  return b.out(out_scores, out_ids, (size_t)nq * k, s);
 }
 
 // Filtered search (include/tristage.h): ts_index_search restricted, per query, to the rows of one of
@@ -1747,23 +1938,11 @@ static int search_filtered_impl(ts_index* h, const void* queries, int32_t nq, in
     ts_set_error("bad arguments to search_filtered");
     return TS_ERR_INVALID;
   }
-  if (n_masks < 0 || allow_words < 0) { ts_set_error("search_filtered: negative n_masks / allow_words"); return TS_ERR_INVALID; }
-  if (n_masks > 0 && !allow_bits) { ts_set_error("search_filtered: n_masks > 0 but allow_bits is null"); return TS_ERR_INVALID; }
+  TS_CHECK(check_mask_args("search_filtered", nq, allow_bits, allow_words, n_masks, mask_of_query));
   if (nq > 0 && !mask_of_query) { ts_set_error("search_filtered: mask_of_query is null"); return TS_ERR_INVALID; }
-  for (int32_t q = 0; q < nq; ++q) {
-    if (mask_of_query[q] < -1 || mask_of_query[q] >= n_masks) {
-      ts_set_error("search_filtered: mask_of_query[%d] = %d is outside [-1, %d)", q, mask_of_query[q], n_masks);
-      return TS_ERR_INVALID;
-    }
-  }
   if (!h) { ts_set_error("null handle"); return TS_ERR_INVALID; }
   const int64_t N = h->ntotal;
-  const int64_t need_words = (N + 31) / 32;
-  if (n_masks > 0 && allow_words < need_words) {
-    ts_set_error("search_filtered: allow_words = %lld < ceil(ntotal / 32) = %lld", (long long)allow_words,
-                 (long long)need_words);
-    return TS_ERR_INVALID;
-  }
+  TS_CHECK(check_mask_words("search_filtered", n_masks, allow_words, N));
   if ((flags & TS_FLAG_PIPELINE) && !(flags & TS_FLAG_ASYNC)) {
     ts_set_error("TS_FLAG_PIPELINE needs TS_FLAG_ASYNC");
     return TS_ERR_INVALID;
@@ -1773,10 +1952,7 @@ static int search_filtered_impl(ts_index* h, const void* queries, int32_t nq, in
     return TS_ERR_INVALID;
   }
   if (nq == 0) return TS_OK;
-  if (N == 0) {
-    ts_set_error("No documents indexed. Call add_documents() first.");
-    return TS_ERR_EMPTY;
-  }
+  if (N == 0) return err_empty();
   {
     std::lock_guard<std::mutex> lk(h->mu);
     ++h->fseq;
@@ -1789,98 +1965,37 @@ static int search_filtered_impl(ts_index* h, const void* queries, int32_t nq, in
   DeviceGuard g(h->device);
   hipStream_t s = (hipStream_t)stream;
   TS_CHECK(co_flush(h, s));   // a filtered search never joins a coalesced pass
-  const int qp = (ts_scan_lds_bytes(h->L, 2) <= 160 * 1024) ? 64 : 32;  // queries per pass
-  if (flags & TS_FLAG_ASYNC) {
-    const int passes = (nq + qp - 1) / qp;
-    if (passes > 4) { ts_set_error("TS_FLAG_ASYNC: at most %d queries per call", 4 * qp); return TS_ERR_INVALID; }
-    std::lock_guard<std::mutex> lk(h->mu);
-    if (h->npending + passes > TS_ASYNC_SLOTS / 4) {
-      ts_set_error("too many unfinished asynchronous searches; call ts_index_finish()");
-      return TS_ERR_INVALID;
-    }
-  }
+  const int qp = queries_per_pass(h);
+  if (flags & TS_FLAG_ASYNC) TS_CHECK(admit_async(h, nq, qp, s));
   const size_t qrow = (size_t)(pdims ? pdims : h->L.dim) * dtype_size(q_dtype);
-  const void* dq = queries;
-  float* ds = out_scores;
-  int64_t* di = out_ids;
-  const uint32_t* bits = allow_bits;
-  const bool host = (flags & TS_FLAG_HOST_PTR) != 0;
-  std::unique_lock<std::mutex> hlk(h->host_mu, std::defer_lock);
-  if (host) {
-    hlk.lock();   // one staging area per handle
-    const size_t mbytes = (size_t)n_masks * (size_t)allow_words * 4;
-    TS_CHECK(ensure(h->qstage, (size_t)nq * qrow));
-    TS_CHECK(ensure(h->out_s, (size_t)nq * k * 4));
-    TS_CHECK(ensure(h->out_i, (size_t)nq * k * 8));
-    TS_HIP(hipMemcpyAsync(h->qstage.p, queries, (size_t)nq * qrow, hipMemcpyHostToDevice, s));
-    if (mbytes) {
-      TS_CHECK(ensure(h->mstage, mbytes));
-      TS_HIP(hipMemcpyAsync(h->mstage.p, allow_bits, mbytes, hipMemcpyHostToDevice, s));
-      bits = (const uint32_t*)h->mstage.p;
-    }
-    dq = h->qstage.p;
-    ds = (float*)h->out_s.p;
-    di = (int64_t*)h->out_i.p;
-  }
-  // removed rows: every mask is ANDed with the tombstone bitmap on the device, and a query without a
-  // mask gets the bitmap itself, so the call is the filtered search of the live rows
-  std::unique_lock<std::mutex> elk(h->eff_mu, std::defer_lock);
-  std::vector<int32_t> moq_live;
-  if (h->nremoved > 0) {
-    elk.lock();
-    TS_CHECK(ensure(h->eff, (size_t)(n_masks + 1) * (size_t)need_words * 4));
-    if (h->eff_used) TS_HIP(hipStreamWaitEvent(s, h->eff_ev, 0));   // the previous call's passes have read `eff`
-    TS_CHECK(ts_launch_and_live(bits, allow_words, n_masks, (const uint32_t*)h->live.p, need_words,
-                                (uint32_t*)h->eff.p, s));
-    moq_live.assign(mask_of_query, mask_of_query + nq);
-    for (int32_t& m : moq_live)
-      if (m < 0) m = n_masks;
-    mask_of_query = moq_live.data();
-    bits = (const uint32_t*)h->eff.p;
-    allow_words = need_words;
-    n_masks += 1;
-  }
+  CallBuffers b(h);
+  TS_CHECK(b.in((flags & TS_FLAG_HOST_PTR) != 0, queries, (size_t)nq * qrow, allow_bits,
+                (size_t)n_masks * (size_t)allow_words * 4, out_scores, out_ids, (size_t)nq * k, s));
+  LiveMasks eff(h);
+  TS_CHECK(eff.apply(nq, b.bits, allow_words, n_masks, mask_of_query, s));
   for (int q0 = 0; q0 < nq; q0 += qp) {
     const int c = std::min(qp, nq - q0);
     MaskCtx mc{};
-    mc.bits = bits;
+    mc.bits = b.bits;
     mc.words = allow_words;
     mc.bias = bias;
     mc.bias_tail = bias_tail;
-    bool masked = bias != nullptr;   // a boosted pass always takes the masked path
-    for (int j = 0; j < TS_MAX_Q; ++j) { mc.mp.qmask[j] = -1; mc.mp.qd[j] = -1; }
-    for (int j = 0; j < c; ++j) {
-      const int32_t m = mask_of_query[q0 + j];
-      mc.mp.qmask[j] = m;
-      if (m < 0) { mc.mp.all_live = 1; continue; }
-      masked = true;
-      int d = 0;
-      while (d < mc.mp.nd && mc.mp.dist[d] != m) ++d;
-      if (d == mc.mp.nd) mc.mp.dist[mc.mp.nd++] = m;
-      mc.mp.qd[j] = d;
-    }
+    // (a boosted pass always takes the masked path)
+    const bool masked = build_mask_pass(mask_of_query + q0, c, mc.mp) || bias != nullptr;
     // A boosted pass none of whose queries has a mask still takes the masked scan, whose unmasked queries read word 0
     // of "mask 0" and OR all ones into it (WalkLive): the pointer has to be readable on the device, whatever the caller
     // left in allow_bits (with n_masks == 0 it is not staged and may be a host address or anything else).  The padded
     // tail of the bias is.
     if (bias && mc.mp.nd == 0) mc.bits = reinterpret_cast<const uint32_t*>(bias_tail);
-    TS_CHECK(search_pass(h, (const char*)dq + (size_t)q0 * qrow, c, q_dtype, k, ds + (size_t)q0 * k,
-                         di + (size_t)q0 * k, flags, s, masked ? &mc : nullptr, pdims / 16));
+    TS_CHECK(search_pass(h, (const char*)b.dq + (size_t)q0 * qrow, c, q_dtype, k, b.ds + (size_t)q0 * k,
+                         b.di + (size_t)q0 * k, flags, s, masked ? &mc : nullptr, pdims / 16));
   }
-  if (elk.owns_lock()) {
-    TS_HIP(hipEventRecord(h->eff_ev, s));
-    h->eff_used = true;
-  }
+  TS_CHECK(eff.done(s));
   if (flags & TS_FLAG_ASYNC) {
     std::lock_guard<std::mutex> lk(h->mu);
     ++h->next_ticket;
   }
-  if (host) {
-    TS_HIP(hipMemcpyAsync(out_scores, ds, (size_t)nq * k * 4, hipMemcpyDeviceToHost, s));
-    TS_HIP(hipMemcpyAsync(out_ids, di, (size_t)nq * k * 8, hipMemcpyDeviceToHost, s));
-    TS_HIP(hipStreamSynchronize(s));
-  }
-  return TS_OK;
+  return b.out(out_scores, out_ids, (size_t)nq * k, s);
 }
 
 extern "C" int ts_index_search_filtered(ts_index* h, const void* queries, int32_t nq, int32_t q_dtype, int32_t k,
@@ -1951,17 +2066,7 @@ extern "C" int ts_index_search_biased(ts_index* h, const void* queries, int32_t 
     ts_set_error("search_biased: null queries, bias or outputs");
     return TS_ERR_INVALID;
   }
-  if (n_masks < 0 || allow_words < 0 || (n_masks > 0 && !allow_bits)) {
-    ts_set_error("search_biased: n_masks = %d, allow_words = %lld, allow_bits %s", n_masks, (long long)allow_words,
-                 allow_bits ? "set" : "null");
-    return TS_ERR_INVALID;
-  }
-  for (int32_t q = 0; mask_of_query && q < nq; ++q) {
-    if (mask_of_query[q] < -1 || mask_of_query[q] >= n_masks) {
-      ts_set_error("search_biased: mask_of_query[%d] = %d is outside [-1, %d)", q, mask_of_query[q], n_masks);
-      return TS_ERR_INVALID;
-    }
-  }
+  TS_CHECK(check_mask_args("search_biased", nq, allow_bits, allow_words, n_masks, mask_of_query));
   if (!h) { ts_set_error("null handle"); return TS_ERR_INVALID; }
   TS_CHECK(funnel_storage_ok(h, "search_biased"));
   const int64_t N = h->ntotal;
@@ -1969,11 +2074,7 @@ extern "C" int ts_index_search_biased(ts_index* h, const void* queries, int32_t 
     ts_set_error("search_biased: bias_rows = %lld < ntotal = %lld", (long long)bias_rows, (long long)N);
     return TS_ERR_INVALID;
   }
-  if (n_masks > 0 && allow_words < (N + 31) / 32) {
-    ts_set_error("search_biased: allow_words = %lld < ceil(ntotal / 32) = %lld", (long long)allow_words,
-                 (long long)((N + 31) / 32));
-    return TS_ERR_INVALID;
-  }
+  TS_CHECK(check_mask_words("search_biased", n_masks, allow_words, N));
   const bool host = (flags & TS_FLAG_HOST_PTR) != 0;
   if (host) {
     for (int64_t r = 0; r < N; ++r) {
@@ -1992,10 +2093,7 @@ extern "C" int ts_index_search_biased(ts_index* h, const void* queries, int32_t 
     for (int i = 0; i < 4; ++i) h->binfo[i] = 0;
   }
   if (nq == 0) return TS_OK;
-  if (N == 0) {
-    ts_set_error("No documents indexed. Call add_documents() first.");
-    return TS_ERR_EMPTY;
-  }
+  if (N == 0) return err_empty();
   std::vector<int32_t> none;
   if (!mask_of_query) {
     none.assign((size_t)nq, -1);
@@ -2042,7 +2140,7 @@ extern "C" int ts_index_rescore(ts_index* h, const void* queries, int32_t nq, in
   if (nq > 0 && (!queries || !cand_ids || !out_scores || !out_ids)) { ts_set_error("rescore: null pointer"); return TS_ERR_INVALID; }
   TS_CHECK(funnel_storage_ok(h, "rescore"));
   if (nq == 0) return TS_OK;
-  if (h->ntotal == 0) { ts_set_error("No documents indexed. Call add_documents() first."); return TS_ERR_EMPTY; }
+  if (h->ntotal == 0) return err_empty();
   DeviceGuard g(h->device);
   hipStream_t s = (hipStream_t)stream;
   TS_CHECK(co_flush(h, s));
@@ -2058,7 +2156,7 @@ extern "C" int ts_index_rescore(ts_index* h, const void* queries, int32_t nq, in
   const int C = ncand, cbp = (C + 31) / 32;
   const size_t tile_b = (size_t)cbp * h->L.kg * 1024, v_b = (size_t)cbp * 32 * 4, s_b = (size_t)C * 4, i_b = (size_t)C * 8;
   const size_t per_q = tile_b + v_b + i_b + ((s_b + 15) & ~(size_t)15);
-  const int qp = (ts_scan_lds_bytes(h->L, 2) <= 160 * 1024) ? 64 : 32;  // queries per pass (one query image)
+  const int qp = queries_per_pass(h);   // (one query image)
   const int qc = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(nq, qp), kRescoreScratchCap / per_q));
   const size_t qrow = (size_t)h->L.dim * dtype_size(q_dtype);
   std::lock_guard<std::mutex> rlk(h->rescore_mu);   // one scratch per handle; the call ends with the stream drained
@@ -2068,27 +2166,24 @@ extern "C" int ts_index_rescore(ts_index* h, const void* queries, int32_t nq, in
   int64_t* ids = (int64_t*)(base + tile_b * qc);
   int32_t* valid = (int32_t*)(base + (tile_b + i_b) * qc);
   float* sc = (float*)(base + (tile_b + i_b + v_b) * qc);
-  int st = TS_OK;
-  for (int q0 = 0; q0 < nq && st == TS_OK; q0 += qp) {
+  auto pass = [&](int q0) -> int {
     const int c = std::min(qp, nq - q0);
     const int qh = c > 32 ? 2 : 1;
-    ts_index::WSet* W = acquire_set(h);
-    if (W->used && hipStreamWaitEvent(s, W->ev_sel, 0) != hipSuccess) st = TS_ERR_HIP;
-    if (st == TS_OK)
-      st = ts_launch_qprep(h->L, (const char*)queries + (size_t)q0 * qrow, q_dtype, c, qh, (uint4*)W->qimg.p, nullptr,
-                           nullptr, s);
-    for (int c0 = 0; c0 < c && st == TS_OK; c0 += qc) {
+    SetLease set(h);
+    ts_index::WSet* W = set.W;
+    TS_CHECK(set.wait_previous(s));
+    TS_CHECK(ts_launch_qprep(h->L, (const char*)queries + (size_t)q0 * qrow, q_dtype, c, qh, (uint4*)W->qimg.p, nullptr,
+                             nullptr, s));
+    for (int c0 = 0; c0 < c; c0 += qc) {
       const int n = std::min(qc, c - c0);
       const int64_t* cid = cand_ids + (size_t)(q0 + c0) * C;
-      st = ts_launch_gather_tiles(src, cid, C, cbp, n, tile, valid, s);
-      if (st != TS_OK) break;
+      TS_CHECK(ts_launch_gather_tiles(src, cid, C, cbp, n, tile, valid, s));
       TsRescoreParams rp{};
       rp.tile = tile; rp.valid = valid; rp.ids = cid;
       rp.qimg = (const uint4*)W->qimg.p;
       rp.kg = h->L.kg; rp.qh = qh; rp.C = C; rp.cbp = cbp; rp.col0 = c0;
       rp.scores = sc; rp.ids_out = ids;
-      st = ts_launch_rescore(h->L, rp, n, s);
-      if (st != TS_OK) break;
+      TS_CHECK(ts_launch_rescore(h->L, rp, n, s));
       SelParams p{};
       p.mode = SEL_MERGE64;   // the tiebreak is the real id; an entry whose id is -1 has no rank
       p.scores = sc;
@@ -2099,13 +2194,12 @@ extern "C" int ts_index_rescore(ts_index* h, const void* queries, int32_t nq, in
       p.out_scores = out_scores + (size_t)(q0 + c0) * k;
       p.out_ids64 = out_ids + (size_t)(q0 + c0) * k;
       p.out_stride = k;
-      st = ts_launch_select(p, n, s);
+      TS_CHECK(ts_launch_select(p, n, s));
     }
-    if (st == TS_OK && hipEventRecord(W->ev_sel, s) == hipSuccess) W->used = true;   // orders the set's next user behind this pass
-    else if (st == TS_OK) st = TS_ERR_HIP;
-    release_set(h, W);
-  }
-  if (st == TS_ERR_HIP) ts_set_error("HIP call failed in ts_index_rescore");
+    return set.done(s);
+  };
+  int st = TS_OK;
+  for (int q0 = 0; q0 < nq && st == TS_OK; q0 += qp) st = pass(q0);
   if (st != TS_OK) { (void)hipStreamSynchronize(s); return st; }
   TS_HIP(hipStreamSynchronize(s));
   return TS_OK;
@@ -2122,10 +2216,6 @@ extern "C" int ts_index_last_filter_info(const ts_index* h, int64_t info[4]) {
 namespace {
 constexpr int64_t kRangeDefaultMax = 1ll << 26;   // entries (12 bytes each) a call may return by default
 struct RangeStats { int64_t passes = 0, filter_passes = 0, dense_redo = 0; };
-struct SetHold {
-  ts_index* h; ts_index::WSet* W;
-  ~SetHold() { if (W) release_set(h, W); }
-};
 }  // namespace
 
 // The result buffers hold `need` entries, of which the first `have` are kept.
@@ -2156,18 +2246,7 @@ static int range_reserve(ts_index* h, int64_t need, int64_t have, int64_t limit,
 // One chunk of the dense path: the dense scan of rows [row0, row0 + rows) into W.dense, the allowed ids into W.mids.
 static int range_dense_chunk(ts_index* h, ts_index::WSet& W, int nq, int qh, int64_t row0, int64_t rows,
                              int64_t chunk_rows, const MaskCtx* mc, hipStream_t s) {
-  ScanParams sp{};
-  sp.corpus = h->corpus;
-  sp.qimg = (const uint4*)W.qimg.p;
-  sp.kg = h->L.kg;
-  sp.nq = nq;
-  sp.nwork = (rows + TS_ROWS_PER_BLOCK - 1) / TS_ROWS_PER_BLOCK;
-  sp.blk0 = row0 / TS_ROWS_PER_BLOCK;
-  sp.blk_stride = 1;
-  sp.ntotal = h->ntotal;
-  sp.dense = (float*)W.dense.p;
-  sp.dense_ld = chunk_rows;
-  TS_CHECK(ts_launch_scan(h->L, SCAN_DENSE, qh, sp, h->num_cus, s));
+  TS_CHECK(dense_chunk_scan(h, W, nq, qh, 0, row0, rows, chunk_rows, s));
   if (mc)
     TS_CHECK(ts_launch_mask_ids(mc->bits, mc->words, mc->mp, nq, row0, (uint32_t)rows, chunk_rows, (int32_t*)W.mids.p, s));
   return TS_OK;
@@ -2180,9 +2259,9 @@ static int range_pass(ts_index* h, const void* dq, int nq, int q_dtype, const fl
   const int64_t N = h->ntotal;
   const int64_t nblk = (N + TS_ROWS_PER_BLOCK - 1) / TS_ROWS_PER_BLOCK;
   const int qh = nq > 32 ? 2 : 1;
-  SetHold hold{h, acquire_set(h)};
-  ts_index::WSet& W = *hold.W;
-  if (W.used && hipEventQuery(W.ev_sel) != hipSuccess) TS_HIP(hipStreamWaitEvent(s, W.ev_sel, 0));
+  SetLease set(h);
+  ts_index::WSet& W = *set.W;
+  TS_CHECK(set.wait_previous(s));
   // the query image of search_pass_on; the scan's counts start from zero
   TS_CHECK(ts_launch_qprep(h->L, dq, q_dtype, nq, qh, (uint4*)W.qimg.p, W.cand_cnt(), W.status(), s));
   // (fp32 storage with a mask or tombstones: the dense path, as its filtered top-k search)
@@ -2197,36 +2276,13 @@ static int range_pass(ts_index* h, const void* dq, int nq, int q_dtype, const fl
     TS_HIP(hipMemcpyAsync(W.tau(), tau, sizeof(tau), hipMemcpyHostToDevice, s));
     TS_CHECK(ensure(W.cand_score, (size_t)TS_MAX_Q * kCandCap * 4));
     TS_CHECK(ensure(W.cand_id, (size_t)TS_MAX_Q * kCandCap * 4));
-    ScanParams sp{};
-    sp.corpus = h->corpus;
-    sp.qimg = (const uint4*)W.qimg.p;
-    sp.kg = h->L.kg;
-    sp.nq = nq;
-    sp.ntotal = N;
-    sp.nwork = nblk;
-    sp.blk0 = 0;
-    sp.blk_stride = 1;
-    sp.tau = W.tau();
-    sp.cand_cnt = W.cand_cnt();
-    sp.cand_score = (float*)W.cand_score.p;
-    sp.cand_id = (int32_t*)W.cand_id.p;
-    sp.cand_cap = kCandCap;
-    const int scan_cus = h->num_cus - h->num_cus / 8;
+    ScanParams sp = scan_base(h, W, nq);
+    scan_filter(sp, W, nblk);
     if (mc) {
-      TS_CHECK(ensure(W.mask, sizeof(TsMaskDev) + (size_t)nblk * 4));
-      TsMaskDev* md = (TsMaskDev*)W.mask.p;
-      TS_HIP(hipMemsetAsync(md, 0, sizeof(TsMaskDev), s));
-      TS_CHECK(ts_launch_live_blocks(mc->bits, mc->words, mc->mp, nblk, N, md, s));
-      MaskedScanParams mp{};
-      static_cast<ScanParams&>(mp) = sp;
-      mp.live = reinterpret_cast<const int32_t*>(md + 1);
-      mp.nlive = &md->nlive;
-      mp.allow_bits = mc->bits;
-      mp.allow_words = mc->words;
-      mp.qmask = md->qmask;
-      TS_CHECK(ts_launch_scan_masked(h->L, qh, mp, scan_cus, s));
+      TS_CHECK(launch_live_blocks(h, W, *mc, s));
+      TS_CHECK(ts_launch_scan_masked(h->L, qh, masked_scan_params(sp, W, *mc), filter_scan_cus(h), s));
     } else {
-      TS_CHECK(ts_launch_scan(h->L, SCAN_FILTER, qh, sp, scan_cus, s));
+      TS_CHECK(ts_launch_scan(h->L, SCAN_FILTER, qh, sp, filter_scan_cus(h), s));
     }
     // the counts are exact, also past the cap: every survivor's atomic runs, only its store is guarded
     TS_HIP(hipMemcpyAsync(cnt, W.cand_cnt(), (size_t)nq * 4, hipMemcpyDeviceToHost, s));
@@ -2262,8 +2318,7 @@ static int range_pass(ts_index* h, const void* dq, int nq, int q_dtype, const fl
     }
   }
   if (dense) {
-    const int64_t chunk_rows = std::min<int64_t>(kDenseChunkRows, nblk * TS_ROWS_PER_BLOCK);
-    const int64_t nch = (nblk * TS_ROWS_PER_BLOCK + chunk_rows - 1) / chunk_rows;
+    const auto [chunk_rows, nch] = dense_chunks(N);
     const int64_t chunk_tiles = (chunk_rows + TS_RANGE_TILE - 1) / TS_RANGE_TILE;
     const int64_t ntiles = nch * chunk_tiles;
     TS_CHECK(ensure(W.dense, (size_t)nq * chunk_rows * 4));
@@ -2324,9 +2379,7 @@ static int range_pass(ts_index* h, const void* dq, int nq, int q_dtype, const fl
     }
     *total = dp.off[nq];
   }
-  TS_HIP(hipEventRecord(W.ev_sel, s));
-  W.used = true;
-  return TS_OK;
+  return set.done(s);
 }
 
 extern "C" int ts_index_range_search(ts_index* h, const void* queries, int32_t nq, int32_t q_dtype, const float* radius,
@@ -2346,17 +2399,7 @@ extern "C" int ts_index_range_search(ts_index* h, const void* queries, int32_t n
   for (int32_t q = 0; q < nq; ++q) {
     if (radius[q] != radius[q]) { ts_set_error("range_search: radius[%d] is NaN", q); return TS_ERR_INVALID; }
   }
-  if (n_masks < 0 || allow_words < 0) { ts_set_error("range_search: negative n_masks / allow_words"); return TS_ERR_INVALID; }
-  if (n_masks > 0 && !allow_bits) { ts_set_error("range_search: n_masks > 0 but allow_bits is null"); return TS_ERR_INVALID; }
-  if (mask_of_query) {
-    for (int32_t q = 0; q < nq; ++q) {
-      if (mask_of_query[q] < -1 || mask_of_query[q] >= n_masks) {
-        ts_set_error("range_search: mask_of_query[%d] = %d is outside [-1, %d)%s", q, mask_of_query[q], n_masks,
-                     allow_bits ? "" : " (allow_bits is null)");
-        return TS_ERR_INVALID;
-      }
-    }
-  }
+  TS_CHECK(check_mask_args("range_search", nq, allow_bits, allow_words, n_masks, mask_of_query));
   lims[0] = 0;
   if (nq == 0) {
     if (h) {
@@ -2377,13 +2420,9 @@ extern "C" int ts_index_range_search(ts_index* h, const void* queries, int32_t n
     return TS_ERR_UNSUPPORTED;
   }
   const int64_t N = h->ntotal;
-  const int64_t need_words = (N + 31) / 32;
-  if (mask_of_query && n_masks > 0 && allow_words < need_words) {
-    ts_set_error("range_search: allow_words = %lld < ceil(ntotal / 32) = %lld", (long long)allow_words, (long long)need_words);
-    return TS_ERR_INVALID;
-  }
-  if (N == 0) { ts_set_error("No documents indexed. Call add_documents() first."); return TS_ERR_EMPTY; }
   if (!mask_of_query) n_masks = 0;   // unfiltered
+  TS_CHECK(check_mask_words("range_search", n_masks, allow_words, N));
+  if (N == 0) return err_empty();
   const int64_t limit = max_total <= 0 ? kRangeDefaultMax : max_total;
   DeviceGuard g(h->device);
   hipStream_t s = (hipStream_t)stream;
@@ -2391,76 +2430,38 @@ extern "C" int ts_index_range_search(ts_index* h, const void* queries, int32_t n
   std::lock_guard<std::mutex> rlk(h->range_mu);
   h->rng_valid = false;
   h->rng_total = 0;
-  const int qp = (ts_scan_lds_bytes(h->L, 2) <= 160 * 1024) ? 64 : 32;  // queries per pass
+  const int qp = queries_per_pass(h);
   const size_t qrow = (size_t)h->L.dim * dtype_size(q_dtype);
-  const void* dq = queries;
-  const uint32_t* bits = allow_bits;
-  std::unique_lock<std::mutex> hlk(h->host_mu, std::defer_lock);
-  if (flags & TS_FLAG_HOST_PTR) {
-    hlk.lock();   // one staging area per handle
-    const size_t mbytes = (size_t)n_masks * (size_t)allow_words * 4;
-    TS_CHECK(ensure(h->qstage, (size_t)nq * qrow));
-    TS_HIP(hipMemcpyAsync(h->qstage.p, queries, (size_t)nq * qrow, hipMemcpyHostToDevice, s));
-    if (mbytes) {
-      TS_CHECK(ensure(h->mstage, mbytes));
-      TS_HIP(hipMemcpyAsync(h->mstage.p, allow_bits, mbytes, hipMemcpyHostToDevice, s));
-      bits = (const uint32_t*)h->mstage.p;
-    }
-    dq = h->qstage.p;
-  }
-  // removed rows: every mask ANDed with the tombstone bitmap, which a query without a mask gets itself
-  // (ts_index_search_filtered)
-  std::vector<int32_t> moq((size_t)nq, -1);
-  if (mask_of_query) moq.assign(mask_of_query, mask_of_query + nq);
-  std::unique_lock<std::mutex> elk(h->eff_mu, std::defer_lock);
-  if (h->nremoved > 0) {
-    elk.lock();
-    TS_CHECK(ensure(h->eff, (size_t)(n_masks + 1) * (size_t)need_words * 4));
-    if (h->eff_used) TS_HIP(hipStreamWaitEvent(s, h->eff_ev, 0));   // the previous call's passes have read `eff`
-    TS_CHECK(ts_launch_and_live(bits, allow_words, n_masks, (const uint32_t*)h->live.p, need_words, (uint32_t*)h->eff.p, s));
-    for (int32_t& m : moq)
-      if (m < 0) m = n_masks;
-    bits = (const uint32_t*)h->eff.p;
-    allow_words = need_words;
-    n_masks += 1;
-  }
+  CallBuffers b(h);
+  TS_CHECK(b.in((flags & TS_FLAG_HOST_PTR) != 0, queries, (size_t)nq * qrow, allow_bits,
+                (size_t)n_masks * (size_t)allow_words * 4, nullptr, nullptr, 0, s));
+  const std::vector<int32_t> none((size_t)nq, -1);
+  if (!mask_of_query) mask_of_query = none.data();
+  LiveMasks eff(h);
+  TS_CHECK(eff.apply(nq, b.bits, allow_words, n_masks, mask_of_query, s));
   RangeStats stats;
   int64_t total = 0;
   int st = TS_OK;
   for (int q0 = 0; q0 < nq && st == TS_OK; q0 += qp) {
     const int c = std::min(qp, nq - q0);
     MaskCtx mc{};
-    mc.bits = bits;
+    mc.bits = b.bits;
     mc.words = allow_words;
-    bool masked = false;
-    for (int j = 0; j < TS_MAX_Q; ++j) { mc.mp.qmask[j] = -1; mc.mp.qd[j] = -1; }
-    for (int j = 0; j < c; ++j) {
-      const int32_t m = moq[(size_t)q0 + j];
-      mc.mp.qmask[j] = m;
-      if (m < 0) { mc.mp.all_live = 1; continue; }
-      masked = true;
-      int d = 0;
-      while (d < mc.mp.nd && mc.mp.dist[d] != m) ++d;
-      if (d == mc.mp.nd) mc.mp.dist[mc.mp.nd++] = m;
-      mc.mp.qd[j] = d;
-    }
+    const bool masked = build_mask_pass(mask_of_query + q0, c, mc.mp);
     lims[q0] = total;
-    st = range_pass(h, (const char*)dq + (size_t)q0 * qrow, c, q_dtype, radius + q0, masked ? &mc : nullptr, flags, limit,
-                    &total, lims + q0, &stats, s);
+    st = range_pass(h, (const char*)b.dq + (size_t)q0 * qrow, c, q_dtype, radius + q0, masked ? &mc : nullptr, flags,
+                    limit, &total, lims + q0, &stats, s);
   }
   if (st != TS_OK) {
     // lims hold the counts so far: the passes that ran (a pass whose counts are known has written them), flat behind
     for (int q = 1; q <= nq; ++q)
       if (lims[q] < lims[q - 1]) lims[q] = lims[q - 1];
     (void)hipStreamSynchronize(s);
-    if (elk.owns_lock() && hipEventRecord(h->eff_ev, s) == hipSuccess) h->eff_used = true;
+    eff.done_after_failure(s);
     set_info(h, 32, stats.passes, stats.filter_passes, stats.dense_redo);
     return st;
   }
-  if (elk.owns_lock()) {
-    TS_HIP(hipEventRecord(h->eff_ev, s));
-    h->eff_used = true;
-  }
+  TS_CHECK(eff.done(s));
   TS_HIP(hipStreamSynchronize(s));
   h->rng_total = total;
   h->rng_valid = true;
@@ -2748,42 +2749,23 @@ extern "C" int ts_index_scores(ts_index* h, const void* queries, int32_t nq, int
     ts_set_error("bad arguments to scores (ld must be a multiple of 4 and >= ntotal rounded up to 32, out 16-byte aligned)");
     return TS_ERR_INVALID;
   }
-  if (N == 0) { ts_set_error("No documents indexed. Call add_documents() first."); return TS_ERR_EMPTY; }
+  if (N == 0) return err_empty();
   DeviceGuard g(h->device);
   hipStream_t s = (hipStream_t)stream;
   TS_CHECK(co_flush(h, s));
-  const int qp = (ts_scan_lds_bytes(h->L, 2) <= 160 * 1024) ? 64 : 32;
+  const int qp = queries_per_pass(h);
   const size_t qrow = (size_t)h->L.dim * dtype_size(q_dtype);
   for (int q0 = 0; q0 < nq; q0 += qp) {
     const int c = std::min(qp, nq - q0);
     const int qh = c > 32 ? 2 : 1;
-    ts_index::WSet* W = acquire_set(h);
-    int st = TS_OK;
-    if (W->used && hipStreamWaitEvent(s, W->ev_sel, 0) != hipSuccess) st = TS_ERR_HIP;
-    if (st == TS_OK)
-      st = ts_launch_qprep(h->L, (const char*)queries + (size_t)q0 * qrow, q_dtype, c, qh, (uint4*)W->qimg.p,
-                           nullptr, nullptr, s);
-    if (st == TS_OK) {
-      ScanParams sp{};
-      sp.corpus = h->corpus;
-      sp.qimg = (const uint4*)W->qimg.p;
-      sp.kg = h->L.kg;
-      sp.nq = c;
-      sp.nwork = nblk;
-      sp.blk0 = 0;
-      sp.blk_stride = 1;
-      sp.ntotal = N;
-      sp.dense = out + (size_t)q0 * ld;
-      sp.dense_ld = ld;
-      st = ts_launch_scan(h->L, SCAN_DENSE, qh, sp, h->num_cus, s);
-    }
-    if (st == TS_OK && hipEventRecord(W->ev_sel, s) == hipSuccess) W->used = true;   // orders the set's next user behind this scan
-    else if (st == TS_OK) st = TS_ERR_HIP;
-    release_set(h, W);
-    if (st != TS_OK) {
-      if (st == TS_ERR_HIP) ts_set_error("HIP call failed in ts_index_scores");
-      return st;
-    }
+    SetLease set(h);
+    TS_CHECK(set.wait_previous(s));
+    TS_CHECK(ts_launch_qprep(h->L, (const char*)queries + (size_t)q0 * qrow, q_dtype, c, qh, (uint4*)set.W->qimg.p,
+                             nullptr, nullptr, s));
+    ScanParams sp = scan_base(h, *set.W, c);
+    scan_window(sp, 0, nblk, 1, out + (size_t)q0 * ld, ld);
+    TS_CHECK(ts_launch_scan(h->L, SCAN_DENSE, qh, sp, h->num_cus, s));
+    TS_CHECK(set.done(s));
   }
   TS_HIP(hipStreamSynchronize(s));
   return TS_OK;
@@ -2920,11 +2902,11 @@ extern "C" int ts_index_read_probe(ts_index* h, int32_t reps, double* ms_avg, do
     ts_set_error("bad arguments to read_probe");
     return TS_ERR_INVALID;
   }
-  if (h->ntotal == 0) { ts_set_error("No documents indexed. Call add_documents() first."); return TS_ERR_EMPTY; }
+  if (h->ntotal == 0) return err_empty();
   DeviceGuard g(h->device);
   hipStream_t s = (hipStream_t)stream;
   const int64_t nblk = (h->ntotal + TS_ROWS_PER_BLOCK - 1) / TS_ROWS_PER_BLOCK;
-  const int grid = std::max(1, h->num_cus - h->num_cus / 8);
+  const int grid = std::max(1, filter_scan_cus(h));
   ts_index::WSet* W = acquire_set(h);          // its 4 KiB scratch page: word 1023 is nobody's
   uint32_t* sink = (uint32_t*)W->small.p + 1023;
   hipEvent_t e0 = nullptr, e1 = nullptr;
