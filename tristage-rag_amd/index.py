@@ -893,8 +893,9 @@ class FlatIPIndex(_IndexBase):
         return L, D, I
 
     def last_range_info(self) -> dict:
-        """The last :meth:`range_search`: its passes (of <= 64 queries), how many ran the filter scan, and how many
-        of those were redone densely because a query had more than 16384 results."""
+        """The last :meth:`range_search`: its passes (of <= 64 queries; 32 where the 64-query image does not fit the LDS),
+        how many ran the filter scan, and how many of those were redone densely because a query had more than 16384
+        results."""
         arr = (ctypes.c_int64 * 4)()
         _lib.check(self._lib.ts_index_last_search_info(self._h, arr))
         if not arr[0] & 32:
@@ -1138,7 +1139,8 @@ class FlatIPIndex(_IndexBase):
         return D, I
 
     def last_bias_info(self) -> dict:
-        """The last :meth:`search_biased`: its passes (of <= 64 queries), those whose first attempt was the fused path
+        """The last :meth:`search_biased`: its passes (of <= 64 queries; 32 where the 64-query image does not fit the LDS),
+        those whose first attempt was the fused path
         (thresholds and the biased filter scan), those of them redone on the exact dense path, and the 32-row blocks
         its scans read."""
         arr = (ctypes.c_int64 * 4)()
