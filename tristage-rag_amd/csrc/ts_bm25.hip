@@ -73,20 +73,6 @@ struct ts_bm25 {
   size_t batch_bytes = 0;
 };
 
-namespace {
-struct Guard {
-  int prev = -1;
-  explicit Guard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) (void)hipSetDevice(dev);
-  }
-  ~Guard() {
-    int cur = -1;
-    if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-  }
-};
-}  // namespace
-
 // One token position of every lane's query: lane y = blockIdx.y adds the postings of ITS token (st[y]: offset, length, idf;
 // length 0 = this query has no token at this position).  Within a lane the launches follow each other in query order and a
 // token's postings hit distinct documents: the same additions in the same order as one query at a time.
@@ -392,7 +378,7 @@ static void bm25_free(ts_bm25* h) {
 
 extern "C" int ts_bm25_destroy(ts_bm25* h) {
   if (!h) return TS_OK;
-  Guard g(h->device);
+  TsDeviceGuard g(h->device);
   (void)hipDeviceSynchronize();
   bm25_free(h);
   delete h;
@@ -433,7 +419,7 @@ extern "C" int ts_bm25_set_index(ts_bm25* h, int64_t N, int64_t V, int64_t nnz, 
     ts_set_error("bad arguments to bm25_set_index");
     return TS_ERR_INVALID;
   }
-  Guard g(h->device);
+  TsDeviceGuard g(h->device);
   bm25_free(h);
   h->N = N; h->V = V; h->nnz = nnz; h->k1p1 = k1p1;
   h->term_off = new (std::nothrow) int64_t[V + 1];
@@ -566,7 +552,7 @@ extern "C" int ts_bm25_search_batch_filtered(ts_bm25* h, const int32_t* term_ids
   hipStream_t s = (hipStream_t)stream;
   BmMasks mk{allow_bits, allow_words, mask_of_query};
   if ((flags & TS_FLAG_HOST_PTR) && n_masks > 0 && h->N > 0) {
-    Guard g(h->device);
+    TsDeviceGuard g(h->device);
     const size_t bytes = (size_t)n_masks * (size_t)allow_words * 4;
     if (bytes > h->mstage_bytes) {
       TS_HIP(hipStreamSynchronize(s));
@@ -594,7 +580,7 @@ static int bm25_batch(ts_bm25* h, const int32_t* term_ids, const int64_t* term_o
     max_terms = std::max(max_terms, term_off[q + 1] - term_off[q]);
   }
   if (nq == 0 || h->N == 0) return TS_OK;
-  Guard g(h->device);
+  TsDeviceGuard g(h->device);
   // lanes: as many as the batch has queries, within the workspace budget (64 at most)
   {
     const size_t per_lane = (size_t)h->N * 20 + (size_t)BM_CAND_CAP * 4 + 32;

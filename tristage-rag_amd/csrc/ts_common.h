@@ -51,15 +51,84 @@ static inline int ts_once_per_device(TsDeviceOnce& o, int dev, F&& action) {
   if (st == TS_OK) o.done.fetch_or(bit, std::memory_order_release);
   return st;
 }
+#define TS_LDS_BYTES (160 * 1024)   // the LDS of a CU (gfx950)
 // the 96-160 KiB LDS kernels: allow the full 160 KiB of dynamic LDS on the CURRENT device
 static inline int ts_allow_max_lds(TsDeviceOnce& o, const void* kernel) {
   int dev = -1;
   TS_HIP(hipGetDevice(&dev));
   return ts_once_per_device(o, dev, [&]() -> int {
-    TS_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    TS_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, TS_LDS_BYTES));
     return TS_OK;
   });
 }
+
+// ---------------------------------------------------------------- host plumbing of the entry points
+// Makes `dev` the calling thread's device for the guard's lifetime.  ok: hipSetDevice took it.  (Internal linkage: the
+// library exports no symbol of it.)
+namespace {
+struct TsDeviceGuard {
+  int prev = -1;
+  bool ok = true;
+  explicit TsDeviceGuard(int dev) {
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    if (prev != dev) ok = (hipSetDevice(dev) == hipSuccess);
+  }
+  ~TsDeviceGuard() {
+    int cur = -1;
+    if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
+  }
+};
+}  // namespace
+
+// A device buffer that only grows (its contents are not kept when it does).
+struct TsDevBuf {
+  void* p = nullptr;
+  size_t bytes = 0;
+};
+static inline int ts_buf_ensure(TsDevBuf& b, size_t bytes) {
+  if (b.bytes >= bytes && b.p) return TS_OK;
+  if (b.p) {
+    TS_HIP(hipFree(b.p));
+    b.p = nullptr;
+    b.bytes = 0;
+  }
+  // round up so slowly growing requests do not reallocate every time
+  const size_t want = (bytes + 0xFFFFF) & ~(size_t)0xFFFFF;
+  hipError_t e = hipMalloc(&b.p, want);
+  if (e != hipSuccess) {
+    b.p = nullptr;
+    ts_set_error("hipMalloc(%zu bytes) failed: %s", want, hipGetErrorString(e));
+    return TS_ERR_OOM;
+  }
+  b.bytes = want;
+  return TS_OK;
+}
+static inline void ts_buf_release(TsDevBuf& b) {
+  if (b.p) (void)hipFree(b.p);
+  b.p = nullptr;
+  b.bytes = 0;
+}
+
+// The caller's element type (TS_F32 / TS_F16 / TS_BF16) as a type: f(p) with p a pointer to it.
+template <class F>
+static inline int ts_typed(const void* p, int dtype, const char* bad_fmt, F&& f) {
+  switch (dtype) {
+    case TS_F32: return f((const float*)p);
+    case TS_F16: return f((const _Float16*)p);
+    case TS_BF16: return f((const __bf16*)p);
+  }
+  ts_set_error(bad_fmt, dtype);
+  return TS_ERR_INVALID;
+}
+template <class F> static inline int ts_typed_rows(const void* rows, int dtype, F&& f) {
+  return ts_typed(rows, dtype, "bad rows dtype %d", f);
+}
+template <class F> static inline int ts_typed_queries(const void* q, int dtype, F&& f) {
+  return ts_typed(q, dtype, "bad query dtype %d", f);
+}
+// the element type of such a pointer
+template <class P> struct TsPointee;
+template <class T> struct TsPointee<const T*> { typedef T type; };
 
 // ---------------------------------------------------------------- layout
 //
@@ -333,6 +402,8 @@ int ts_launch_bias_ids(const uint32_t* bits, int64_t words, const TsMaskPass& mp
                        int64_t row0, uint32_t rows, int64_t ld, float* dense, int32_t* ids, hipStream_t stream);
 // LDS bytes the scan kernel needs for qh*32 queries (Q image + candidate staging)
 size_t ts_scan_lds_bytes(const TsLayout& L, int qh);
+// queries per pass: 64 where the image of 64 fits the LDS, else 32
+static inline int ts_queries_per_pass(const TsLayout& L) { return ts_scan_lds_bytes(L, 2) <= TS_LDS_BYTES ? 64 : 32; }
 // fp32 storage, 32-query passes, 512 < d <= 768: the bf16x3 split scan (ts_scan_f32s.hip) instead of the exact-f32 MFMA
 bool ts_use_f32_split(const TsLayout& L, int qh);
 size_t ts_scan_f32s_lds_bytes(const TsLayout& L);

@@ -574,13 +574,13 @@ int ts_launch_fused(const TsLayout& L, int qh, const TsFusedArgs& a, hipStream_t
   // every workgroup gets the same dynamic LDS: the scan's query image + staging, or the threshold role's keys
   // threshold role: every wave that takes queries keeps its keys + a 256-bin histogram in LDS
   const size_t per_wave = (size_t)a.expect * 4;
-  int tau_waves = (int)std::min<size_t>(SCAN_WAVES, (160 * 1024) / per_wave);
+  int tau_waves = (int)std::min<size_t>(SCAN_WAVES, (TS_LDS_BYTES) / per_wave);
   if (tau_waves < 1) { ts_set_error("one-launch search: sample too large for LDS"); return TS_ERR_INVALID; }
   // (no more workgroups x waves than queries; at least enough to leave each wave one or two queries)
   while (tau_waves > 1 && (a.tau_wgs * (tau_waves - 1)) >= TS_MAX_Q) --tau_waves;
   p.tau_waves = tau_waves;
   const size_t lds = std::max(ts_scan_lds_bytes(L, qh), per_wave * tau_waves);
-  if (a.expect > TS_FUSED_MAX_KEYS || (a.expect & 511u) || lds > 160 * 1024 || a.expect != 2 * a.n_sample ||
+  if (a.expect > TS_FUSED_MAX_KEYS || (a.expect & 511u) || lds > TS_LDS_BYTES || a.expect != 2 * a.n_sample ||
       (a.n_sample % SAMPLE_GROUP) != 0 || (a.n_sample / SAMPLE_GROUP) * a.sample_stride > a.nblk ||
       a.n_sample < SAMPLE_GROUP || a.sample_stride < SAMPLE_GROUP) {
     ts_set_error("one-launch search: bad sample geometry (%u slots)", a.expect);

@@ -558,7 +558,7 @@ extern "C" int ts_attention_varlen(const void* qkv, const int32_t* lens, int32_t
     return TS_ERR_INVALID;
   }
   const size_t lds = attn_lds_bytes(L, dh);
-  if ((dh != 32 && dh != 64) || lds > 160 * 1024 || B > 65535 ||
+  if ((dh != 32 && dh != 64) || lds > TS_LDS_BYTES || B > 65535 ||
       ((reinterpret_cast<uintptr_t>(qkv) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(rope_cos) |
         reinterpret_cast<uintptr_t>(rope_sin)) & 15)) {
     ts_set_error("attention_varlen: head dimension %d / length %d / alignment not supported", dh, L);

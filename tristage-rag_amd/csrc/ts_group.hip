@@ -272,19 +272,6 @@ size_t group_lds_bytes(int n) {
   return (size_t)n * 8 + 4 * nw * 4 + 2 * 16 * 4;
 }
 
-struct GroupDeviceGuard {
-  int prev = -1;
-  bool ok = true;
-  explicit GroupDeviceGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) ok = (hipSetDevice(dev) == hipSuccess);
-  }
-  ~GroupDeviceGuard() {
-    int cur = -1;
-    if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-  }
-};
-
 TsDeviceOnce g_group_lds_once;
 
 // Size classes by the sorted length n: up to 1024 keys a 256-thread workgroup, above that 1024 threads; above 4096
@@ -347,7 +334,7 @@ extern "C" int ts_group_topk(const int64_t* cand_ids, const float* cand_scores, 
       }
     }
   }
-  GroupDeviceGuard g(device);
+  TsDeviceGuard g(device);
   if (!g.ok) { ts_set_error("hipSetDevice(%d) failed", device); return TS_ERR_HIP; }
   hipStream_t s = (hipStream_t)stream;
   GroupParams p;

@@ -31,52 +31,6 @@ void ts_set_error(const char* fmt, ...) {
 extern "C" const char* ts_last_error(void) { return g_err; }
 extern "C" int ts_abi_version(void) { return TS_ABI_VERSION; }
 
-namespace {
-
-struct DeviceGuard {
-  int prev = -1;
-  bool ok = true;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) ok = (hipSetDevice(dev) == hipSuccess);
-  }
-  ~DeviceGuard() {
-    int cur = -1;
-    if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-  }
-};
-
-struct DevBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-};
-
-int ensure(DevBuf& b, size_t bytes) {
-  if (b.bytes >= bytes && b.p) return TS_OK;
-  if (b.p) {
-    TS_HIP(hipFree(b.p));
-    b.p = nullptr;
-    b.bytes = 0;
-  }
-  // round up so slowly growing requests do not reallocate every time
-  size_t want = (bytes + 0xFFFFF) & ~(size_t)0xFFFFF;
-  hipError_t e = hipMalloc(&b.p, want);
-  if (e != hipSuccess) {
-    b.p = nullptr;
-    ts_set_error("hipMalloc(%zu bytes) failed: %s", want, hipGetErrorString(e));
-    return TS_ERR_OOM;
-  }
-  b.bytes = want;
-  return TS_OK;
-}
-
-void release(DevBuf& b) {
-  if (b.p) (void)hipFree(b.p);
-  b.p = nullptr;
-  b.bytes = 0;
-}
-
-}  // namespace
 #define TS_NPHASE 8
 #define TS_NSETS 8         // workspace sets = synchronous searches that may run at once on one handle; also the
                            // coalesced queue's held batches (at most TS_MAX_WIDE_GROUPS - 1) plus the one it acquires
@@ -126,10 +80,10 @@ struct ts_index {
   // Per-search workspace, double-buffered so that consecutive pipelined searches never
   // share a buffer that is still being read (see search_pass).
   struct WSet {
-    DevBuf qimg, small, cand_score, cand_id, sample;
-    DevBuf dense, list_score, list_id;   // the dense path's score chunk and per-chunk lists
-    DevBuf hist, spill;                  // one-launch search (ts_fused.hip): threshold histogram, parked score tiles
-    DevBuf mask, mids;                   // filtered searches: TsMaskDev + live-block list; the dense path's masked ids
+    TsDevBuf qimg, small, cand_score, cand_id, sample;
+    TsDevBuf dense, list_score, list_id;   // the dense path's score chunk and per-chunk lists
+    TsDevBuf hist, spill;                  // one-launch search (ts_fused.hip): threshold histogram, parked score tiles
+    TsDevBuf mask, mids;                   // filtered searches: TsMaskDev + live-block list; the dense path's masked ids
     uint32_t gen = 0;                    // generation tag of the last one-launch search on this set
     uint32_t arrive_total = 0;           // running goal of the set's arrival hint counter
     bool hist_dirty = false;             // a launch may have left entries behind: cleared before the next one
@@ -157,7 +111,7 @@ struct ts_index {
   bool slot_busy[TS_ASYNC_SLOTS] = {};
   hipStream_t s_pro = nullptr, s_scan = nullptr, s_sel = nullptr;  // TS_FLAG_PIPELINE only
   // staging of host-pointer calls (add / reconstruct need exclusive access anyway; searches: host_mu)
-  DevBuf stage, den, qstage, out_s, out_i, mstage;
+  TsDevBuf stage, den, qstage, out_s, out_i, mstage;
   uint32_t* host_status = nullptr;  // pinned + mapped: written by the select kernel
   uint32_t* host_status_dev = nullptr;  // device view of host_status
   // asynchronous searches (TS_FLAG_ASYNC): each pass reports into its own slot of
@@ -208,21 +162,21 @@ struct ts_index {
   int64_t phase_cnt[TS_NPHASE] = {};
   // tombstones (ts_index_remove): bit r % 32 of word r / 32 of `live` set = row r live.  The bitmap
   // is written at the first removal; while nremoved == 0 no search reads it and every path is the one without it.
-  DevBuf live;
+  TsDevBuf live;
   int64_t live_cap_words = 0;
   int64_t nremoved = 0;
   // a search of an index with removed rows is a filtered one: its masks ANDed with `live` go to `eff`, one call at a
   // time (eff_mu); eff_ev, recorded behind the call's passes, orders the next writer of `eff` or `live` after them
-  DevBuf eff, rids, compact_scratch, compact_stage;
+  TsDevBuf eff, rids, compact_scratch, compact_stage;
   // update in place (ts_index_update): the staging tile of a chunk and its block tables
-  DevBuf upd_tile, upd_tab;
+  TsDevBuf upd_tile, upd_tab;
   std::mutex eff_mu;
   hipEvent_t eff_ev = nullptr;
   bool eff_used = false;
   // range search (ts_index_range_search): the packed result of the last call (rng_cap entries
   // allocated, rng_total valid), kept for ts_index_range_fetch until the next range search or a change of the index;
   // rng_tiles: the dense path's per-query totals and tile counts.  range_mu serialises range calls on the handle.
-  DevBuf rng_s, rng_i, rng_tiles;
+  TsDevBuf rng_s, rng_i, rng_tiles;
   int64_t rng_cap = 0, rng_total = 0;
   bool rng_valid = false;
   std::mutex range_mu;
@@ -230,12 +184,12 @@ struct ts_index {
   TsMmrWork mmr;
   // rescore (ts_index_rescore): candidate tiles, scores and ids of one chunk of queries, allocated at
   // the first call; rescore_mu serialises the calls on the handle
-  DevBuf rescore_scratch;
+  TsDevBuf rescore_scratch;
   std::mutex rescore_mu;
   // boosted search (ts_index_search_biased): the staged bias of a host-pointer call followed by the
   // 32-float padded copy of the last, partial row block's entries, allocated at the first call; bias_mu serialises
   // the calls on the handle; binfo: ts_index_last_bias_info
-  DevBuf bias_stage;
+  TsDevBuf bias_stage;
   std::mutex bias_mu;
   int64_t binfo[4] = {0, 0, 0, 0};
 };
@@ -323,12 +277,12 @@ extern "C" int ts_index_create(int32_t dim, int32_t storage_dtype, int32_t metri
     ts_set_error("dim %d exceeds the 2048 dimensions of 4-bit MX (mxfp4) storage", dim);
     return TS_ERR_UNSUPPORTED;
   }
-  if (ts_scan_lds_bytes(L, 1) > 160 * 1024) {
+  if (ts_scan_lds_bytes(L, 1) > TS_LDS_BYTES) {
     ts_set_error("dim %d with dtype %d needs %zu bytes of LDS for 32 queries (max 163840)", dim,
                  storage_dtype, ts_scan_lds_bytes(L, 1));
     return TS_ERR_UNSUPPORTED;
   }
-  DeviceGuard g(device);
+  TsDeviceGuard g(device);
   if (!g.ok) { ts_set_error("hipSetDevice(%d) failed", device); return TS_ERR_HIP; }
   ts_index* h = new (std::nothrow) ts_index();
   if (!h) { ts_set_error("out of host memory"); return TS_ERR_OOM; }
@@ -343,9 +297,9 @@ extern "C" int ts_index_create(int32_t dim, int32_t storage_dtype, int32_t metri
   // (the stationary pass's LDS attribute now: no first-launch cost inside a caller's timed pass)
   int st = ts_scan_qstat_prepare(L);
   for (ts_index::WSet& w : h->ws) {
-    if (st == TS_OK) st = ensure(w.small, 4096);
+    if (st == TS_OK) st = ts_buf_ensure(w.small, 4096);
     if (st == TS_OK && hipMemset(w.small.p, 0, 4096) != hipSuccess) { ts_set_error("hipMemset failed"); st = TS_ERR_HIP; }
-    if (st == TS_OK) st = ensure(w.qimg, (size_t)L.qkg * 2 * 1024);
+    if (st == TS_OK) st = ts_buf_ensure(w.qimg, (size_t)L.qkg * 2 * 1024);
     if (st == TS_OK && (hipEventCreateWithFlags(&w.ev_pro, hipEventDisableTiming) != hipSuccess ||
                         hipEventCreateWithFlags(&w.ev_scan, hipEventDisableTiming) != hipSuccess ||
                         hipEventCreateWithFlags(&w.ev_sel, hipEventDisableTiming) != hipSuccess ||
@@ -377,16 +331,16 @@ extern "C" int ts_index_create(int32_t dim, int32_t storage_dtype, int32_t metri
 
 extern "C" int ts_index_destroy(ts_index* h) {
   if (!h) return TS_OK;
-  DeviceGuard g(h->device);
+  TsDeviceGuard g(h->device);
   (void)co_flush(h, nullptr);
   (void)hipDeviceSynchronize();
   if (h->corpus) (void)hipFree(h->corpus);
-  DevBuf* bufs[] = {&h->stage, &h->den, &h->qstage, &h->out_s, &h->out_i, &h->mstage};
-  for (DevBuf* b : bufs) release(*b);
+  TsDevBuf* bufs[] = {&h->stage, &h->den, &h->qstage, &h->out_s, &h->out_i, &h->mstage};
+  for (TsDevBuf* b : bufs) ts_buf_release(*b);
   for (ts_index::WSet& w : h->ws) {
-    DevBuf* wb[] = {&w.qimg, &w.small, &w.cand_score, &w.cand_id, &w.sample, &w.dense, &w.list_score, &w.list_id,
-                    &w.hist, &w.spill, &w.mask, &w.mids};
-    for (DevBuf* b : wb) release(*b);
+    TsDevBuf* wb[] = {&w.qimg, &w.small, &w.cand_score, &w.cand_id, &w.sample, &w.dense, &w.list_score, &w.list_id,
+                      &w.hist, &w.spill, &w.mask, &w.mids};
+    for (TsDevBuf* b : wb) ts_buf_release(*b);
     hipEvent_t evs[] = {w.ev_pro, w.ev_scan, w.ev_sel, w.ev_in};
     for (hipEvent_t e : evs)
       if (e) (void)hipEventDestroy(e);
@@ -400,9 +354,9 @@ extern "C" int ts_index_destroy(ts_index* h) {
   for (hipEvent_t e : h->async_ev)
     if (e) (void)hipEventDestroy(e);
   if (h->co_ev) (void)hipEventDestroy(h->co_ev);
-  DevBuf* rb[] = {&h->live, &h->eff, &h->rids, &h->compact_scratch, &h->compact_stage, &h->upd_tile, &h->upd_tab,
-                  &h->rng_s, &h->rng_i, &h->rng_tiles, &h->rescore_scratch, &h->bias_stage};
-  for (DevBuf* b : rb) release(*b);
+  TsDevBuf* rb[] = {&h->live, &h->eff, &h->rids, &h->compact_scratch, &h->compact_stage, &h->upd_tile, &h->upd_tab,
+                    &h->rng_s, &h->rng_i, &h->rng_tiles, &h->rescore_scratch, &h->bias_stage};
+  for (TsDevBuf* b : rb) ts_buf_release(*b);
   if (h->eff_ev) (void)hipEventDestroy(h->eff_ev);
   ts_mmr_release(h->mmr);
   delete h;
@@ -411,7 +365,7 @@ extern "C" int ts_index_destroy(ts_index* h) {
 
 extern "C" int ts_index_reset(ts_index* h) {
   if (!h) { ts_set_error("null handle"); return TS_ERR_INVALID; }
-  { DeviceGuard g(h->device); TS_CHECK(co_flush(h, nullptr)); }   // held passes search the corpus they were submitted against
+  { TsDeviceGuard g(h->device); TS_CHECK(co_flush(h, nullptr)); }   // held passes search the corpus they were submitted against
   h->rng_valid = false;
   h->ntotal = 0;
   h->nremoved = 0;
@@ -421,7 +375,7 @@ extern "C" int ts_index_reset(ts_index* h) {
 extern "C" int ts_index_reserve(ts_index* h, int64_t nrows) {
   if (!h || nrows < 0) { ts_set_error("bad arguments"); return TS_ERR_INVALID; }
   if (nrows >= (1LL << 31)) { ts_set_error("at most 2^31-1 rows per index"); return TS_ERR_UNSUPPORTED; }
-  DeviceGuard g(h->device);
+  TsDeviceGuard g(h->device);
   TS_CHECK(co_flush(h, nullptr));   // (grow_corpus frees the old corpus after a sync of the null stream)
   return grow_corpus(h, (nrows + TS_ROWS_PER_BLOCK - 1) / TS_ROWS_PER_BLOCK, true, nullptr);
 }
@@ -450,7 +404,7 @@ extern "C" int32_t ts_index_fp8_scale_log2(const ts_index* h) {
 
 extern "C" int ts_index_set_id_offset(ts_index* h, int64_t offset) {
   if (!h) { ts_set_error("null handle"); return TS_ERR_INVALID; }
-  { DeviceGuard g(h->device); TS_CHECK(co_flush(h, nullptr)); }   // a held batch's ids carry the offset of its submission
+  { TsDeviceGuard g(h->device); TS_CHECK(co_flush(h, nullptr)); }   // a held batch's ids carry the offset of its submission
   h->id_offset = offset;
   return TS_OK;
 }
@@ -469,13 +423,13 @@ static int live_reserve(ts_index* h, int64_t rows, hipStream_t s) {
   const int64_t words = (rows + 31) / 32;
   if (words <= h->live_cap_words) return TS_OK;
   const int64_t cap = std::max<int64_t>(words, h->live_cap_words + h->live_cap_words / 2);
-  DevBuf nb;
-  TS_CHECK(ensure(nb, (size_t)cap * 4));
+  TsDevBuf nb;
+  TS_CHECK(ts_buf_ensure(nb, (size_t)cap * 4));
   TS_HIP(hipMemsetAsync(nb.p, 0, (size_t)cap * 4, s));
   if (h->live_cap_words > 0)
     TS_HIP(hipMemcpyAsync(nb.p, h->live.p, (size_t)h->live_cap_words * 4, hipMemcpyDeviceToDevice, s));
   TS_HIP(hipStreamSynchronize(s));
-  release(h->live);
+  ts_buf_release(h->live);
   h->live = nb;
   h->live_cap_words = cap;
   return TS_OK;
@@ -488,7 +442,7 @@ extern "C" int ts_index_add(ts_index* h, const void* rows, int64_t n, int32_t ro
   if (n == 0) return TS_OK;
   if (!rows || n < 0 || !dtype_ok(rows_dtype)) { ts_set_error("bad arguments to add"); return TS_ERR_INVALID; }
   if (h->ntotal + n >= (1LL << 31)) { ts_set_error("at most 2^31-1 rows per index"); return TS_ERR_UNSUPPORTED; }
-  DeviceGuard g(h->device);
+  TsDeviceGuard g(h->device);
   hipStream_t s = (hipStream_t)stream;
   TS_CHECK(co_flush(h, s));   // held passes search the corpus they were submitted against
   h->rng_valid = false;       // a stored range result describes the index as it was
@@ -500,8 +454,8 @@ extern "C" int ts_index_add(ts_index* h, const void* rows, int64_t n, int32_t ro
     // chunked upload through a device staging buffer
     int64_t chunk = std::max<int64_t>(1, (int64_t)((64u << 20) / row_bytes));
     chunk = std::min(chunk, n);
-    TS_CHECK(ensure(h->stage, (size_t)chunk * row_bytes));
-    if (norm) TS_CHECK(ensure(h->den, (size_t)chunk * 4));
+    TS_CHECK(ts_buf_ensure(h->stage, (size_t)chunk * row_bytes));
+    if (norm) TS_CHECK(ts_buf_ensure(h->den, (size_t)chunk * 4));
     for (int64_t r0 = 0; r0 < n; r0 += chunk) {
       const int64_t c = std::min(chunk, n - r0);
       TS_HIP(hipMemcpyAsync(h->stage.p, (const char*)rows + (size_t)r0 * row_bytes,
@@ -512,7 +466,7 @@ extern "C" int ts_index_add(ts_index* h, const void* rows, int64_t n, int32_t ro
       TS_HIP(hipStreamSynchronize(s));
     }
   } else {
-    if (norm) TS_CHECK(ensure(h->den, (size_t)n * 4));
+    if (norm) TS_CHECK(ts_buf_ensure(h->den, (size_t)n * 4));
     TS_CHECK(ts_launch_relayout(h->L, rows, rows_dtype, n, h->ntotal, h->corpus, norm,
                                 (float*)h->den.p, s));
     TS_HIP(hipStreamSynchronize(s));
@@ -533,14 +487,14 @@ extern "C" int ts_index_reconstruct(ts_index* h, int64_t row0, int64_t n, float*
     return TS_ERR_INVALID;
   }
   if (n == 0) return TS_OK;
-  DeviceGuard g(h->device);
+  TsDeviceGuard g(h->device);
   hipStream_t s = (hipStream_t)stream;
   TS_CHECK(co_flush(h, s));
   if (flags & TS_FLAG_HOST_PTR) {
     const size_t row_bytes = (size_t)h->L.dim * 4;
     int64_t chunk = std::max<int64_t>(1, (int64_t)((64u << 20) / row_bytes));
     chunk = std::min(chunk, n);
-    TS_CHECK(ensure(h->stage, (size_t)chunk * row_bytes));
+    TS_CHECK(ts_buf_ensure(h->stage, (size_t)chunk * row_bytes));
     for (int64_t r0 = 0; r0 < n; r0 += chunk) {
       const int64_t c = std::min(chunk, n - r0);
       TS_CHECK(ts_launch_reconstruct(h->L, h->corpus, row0 + r0, c, (float*)h->stage.p, s));
@@ -560,7 +514,7 @@ extern "C" int ts_index_mmr(ts_index* h, const int64_t* cand_ids, const float* c
                             int32_t k, float lambda, float* out_rel, int64_t* out_ids, uint32_t flags, void* stream) {
   TS_CHECK(ts_mmr_check_args(h, cand_ids, cand_rel, nq, fetch_k, k, lambda, out_rel, out_ids));
   if (nq == 0) return TS_OK;
-  DeviceGuard g(h->device);
+  TsDeviceGuard g(h->device);
   hipStream_t s = (hipStream_t)stream;
   TS_CHECK(co_flush(h, s));   // a held search's results are what the caller chains this call behind
   TsMmrSource src;
@@ -593,7 +547,7 @@ extern "C" int ts_index_mmr_get_timings(ts_index* h, double ms[3], int64_t* call
 }
 
 // ------------------------------------------------------------------ search
-static int queries_per_pass(const ts_index* h) { return (ts_scan_lds_bytes(h->L, 2) <= 160 * 1024) ? 64 : 32; }
+static int queries_per_pass(const ts_index* h) { return ts_queries_per_pass(h->L); }
 
 static int err_empty() {
   ts_set_error("No documents indexed. Call add_documents() first.");
@@ -707,7 +661,7 @@ static int scan_rows(ts_index* h, int pkg, int mode, int qh, const ScanParams& s
 // The live-block list of a masked pass into the set's TsMaskDev (W.mask_dev()), on `s`.
 static int launch_live_blocks(ts_index* h, ts_index::WSet& W, const MaskCtx& mc, hipStream_t s) {
   const int64_t nblk = (h->ntotal + TS_ROWS_PER_BLOCK - 1) / TS_ROWS_PER_BLOCK;
-  TS_CHECK(ensure(W.mask, sizeof(TsMaskDev) + (size_t)nblk * 4));
+  TS_CHECK(ts_buf_ensure(W.mask, sizeof(TsMaskDev) + (size_t)nblk * 4));
   TS_HIP(hipMemsetAsync(W.mask_dev(), 0, sizeof(TsMaskDev), s));
   return ts_launch_live_blocks(mc.bits, mc.words, mc.mp, nblk, h->ntotal, W.mask_dev(), s);
 }
@@ -744,11 +698,11 @@ static int dense_path(ts_index* h, ts_index::WSet& W, int nq, int qh, int k, flo
                       int64_t* out_i, hipStream_t s, const MaskCtx* mc = nullptr, int pkg = 0) {
   const int64_t N = h->ntotal;
   const auto [chunk_rows, nch] = dense_chunks(N);
-  TS_CHECK(ensure(W.dense, (size_t)nq * chunk_rows * 4));
-  if (mc) TS_CHECK(ensure(W.mids, (size_t)nq * chunk_rows * 4));
+  TS_CHECK(ts_buf_ensure(W.dense, (size_t)nq * chunk_rows * 4));
+  if (mc) TS_CHECK(ts_buf_ensure(W.mids, (size_t)nq * chunk_rows * 4));
   if (nch > 1) {
-    TS_CHECK(ensure(W.list_score, (size_t)nq * nch * k * 4));
-    TS_CHECK(ensure(W.list_id, (size_t)nq * nch * k * 4));
+    TS_CHECK(ts_buf_ensure(W.list_score, (size_t)nq * nch * k * 4));
+    TS_CHECK(ts_buf_ensure(W.list_id, (size_t)nq * nch * k * 4));
   }
   for (int64_t c = 0; c < nch; ++c) {
     const int64_t row0 = c * chunk_rows;
@@ -1076,7 +1030,7 @@ static int pass_one_launch(Pass& p, const FusedPlan& fp) {
   ts_index* h = p.h;
   ts_index::WSet& W = *p.set.W;
   if (!W.hist.p) {
-    TS_CHECK(ensure(W.hist, ts_fused_keys_bytes()));
+    TS_CHECK(ts_buf_ensure(W.hist, ts_fused_keys_bytes()));
     W.hist_dirty = true;
   }
   if (W.hist_dirty) {
@@ -1133,7 +1087,7 @@ static int pass_five_launch(Pass& p) {
   const SampleGeom g = sample_geometry(h, p.k, oversample);
   p.S = g.S;
   p.m = g.m;
-  TS_CHECK(ensure(W.sample, (size_t)p.nq * g.S * 4));
+  TS_CHECK(ts_buf_ensure(W.sample, (size_t)p.nq * g.S * 4));
   ScanParams sp = scan_base(h, W, p.nq);
   // (1) dense scores of a strided sample of row blocks
   scan_window(sp, 0, g.nsb, g.sstride, (float*)W.sample.p, g.S);
@@ -1338,8 +1292,8 @@ static int search_pass_on(ts_index* h, SetLease& set, const void* dq, int nq, in
     if (p.slot.slot < 0) { ts_set_error("no free report slot"); return TS_ERR_INVALID; }
     for (int i = 0; i < 66; ++i) h->host_status[(size_t)p.slot.slot * TS_SLOT_WORDS + i] = 0;
   }
-  TS_CHECK(ensure(W.cand_score, (size_t)TS_MAX_Q * kCandCap * 4));
-  TS_CHECK(ensure(W.cand_id, (size_t)TS_MAX_Q * kCandCap * 4));
+  TS_CHECK(ts_buf_ensure(W.cand_score, (size_t)TS_MAX_Q * kCandCap * 4));
+  TS_CHECK(ts_buf_ensure(W.cand_id, (size_t)TS_MAX_Q * kCandCap * 4));
   if (fused) TS_CHECK(pass_one_launch(p, fp));
   else TS_CHECK(pass_five_launch(p));
   TS_CHECK(pass_select(p));
@@ -1706,12 +1660,12 @@ static int co_submit(ts_index* h, const void* dq, int nq, int q_dtype, int k, fl
   if (slot_guard.slot < 0) { ts_set_error("no free report slot"); return TS_ERR_INVALID; }
   TS_CHECK(set.wait_previous(s));
   TS_CHECK(ts_launch_qprep(h->L, dq, q_dtype, nq, qh, (uint4*)W->qimg.p, W->cand_cnt(), W->status(), s));
-  TS_CHECK(ensure(W->cand_score, (size_t)TS_MAX_Q * kCandCap * 4));
-  TS_CHECK(ensure(W->cand_id, (size_t)TS_MAX_Q * kCandCap * 4));
+  TS_CHECK(ts_buf_ensure(W->cand_score, (size_t)TS_MAX_Q * kCandCap * 4));
+  TS_CHECK(ts_buf_ensure(W->cand_id, (size_t)TS_MAX_Q * kCandCap * 4));
   // the five-launch geometry with a lower survivor target: three groups share the staging area that two have in
   // scan_kernel (ts_scan.hip, scan_multi_kernel)
   const SampleGeom g = sample_geometry(h, k, kCoalesceOversample);
-  TS_CHECK(ensure(W->sample, (size_t)nq * g.S * 4));
+  TS_CHECK(ts_buf_ensure(W->sample, (size_t)nq * g.S * 4));
   ts_index::CoBatch cb{W, nq, qh, k, slot_guard.slot, qh, out_s, out_i, g.m, g.S, g.sstride, g.nsb, !defer, false};
   if (defer) {
     // (co_pass_prologue)
@@ -1754,7 +1708,7 @@ static int co_submit(ts_index* h, const void* dq, int nq, int q_dtype, int k, fl
 
 extern "C" int ts_index_flush(ts_index* h, void* stream) {
   if (!h) { ts_set_error("null handle"); return TS_ERR_INVALID; }
-  DeviceGuard g(h->device);
+  TsDeviceGuard g(h->device);
   std::lock_guard<std::mutex> lk(h->co_mu);
   return co_flush_locked(h, (hipStream_t)stream);   // later work on `stream` is ordered behind the flushed passes
 }
@@ -1794,17 +1748,17 @@ struct CallBuffers {
     di = out_ids;
     if (!host) return TS_OK;
     lk.lock();
-    TS_CHECK(ensure(h->qstage, qbytes));
+    TS_CHECK(ts_buf_ensure(h->qstage, qbytes));
     if (nout) {
-      TS_CHECK(ensure(h->out_s, nout * 4));
-      TS_CHECK(ensure(h->out_i, nout * 8));
+      TS_CHECK(ts_buf_ensure(h->out_s, nout * 4));
+      TS_CHECK(ts_buf_ensure(h->out_i, nout * 8));
       ds = (float*)h->out_s.p;
       di = (int64_t*)h->out_i.p;
     }
     TS_HIP(hipMemcpyAsync(h->qstage.p, queries, qbytes, hipMemcpyHostToDevice, s));
     dq = h->qstage.p;
     if (mbytes) {
-      TS_CHECK(ensure(h->mstage, mbytes));
+      TS_CHECK(ts_buf_ensure(h->mstage, mbytes));
       TS_HIP(hipMemcpyAsync(h->mstage.p, allow_bits, mbytes, hipMemcpyHostToDevice, s));
       bits = (const uint32_t*)h->mstage.p;
     }
@@ -1833,7 +1787,7 @@ struct LiveMasks {
     if (h->nremoved == 0) return TS_OK;
     const int64_t need_words = (h->ntotal + 31) / 32;
     lk.lock();
-    TS_CHECK(ensure(h->eff, (size_t)(n_masks + 1) * (size_t)need_words * 4));
+    TS_CHECK(ts_buf_ensure(h->eff, (size_t)(n_masks + 1) * (size_t)need_words * 4));
     if (h->eff_used) TS_HIP(hipStreamWaitEvent(s, h->eff_ev, 0));   // the previous call's passes have read `eff`
     TS_CHECK(ts_launch_and_live(bits, allow_words, n_masks, (const uint32_t*)h->live.p, need_words,
                                 (uint32_t*)h->eff.p, s));
@@ -1876,7 +1830,7 @@ extern "C" int ts_index_search(ts_index* h, const void* queries, int32_t nq, int
     return ts_index_search_filtered(h, queries, nq, q_dtype, k, nullptr, 0, 0, moq.data(), out_scores, out_ids, flags,
                                     stream);
   }
-  DeviceGuard g(h->device);
+  TsDeviceGuard g(h->device);
   hipStream_t s = (hipStream_t)stream;
   const int qp = queries_per_pass(h);
   if ((flags & TS_FLAG_PIPELINE) && !(flags & TS_FLAG_ASYNC)) {
@@ -1962,7 +1916,7 @@ static int search_filtered_impl(ts_index* h, const void* queries, int32_t nq, in
   for (int32_t q = 0; q < nq && !any; ++q) any = mask_of_query[q] >= 0;
   if (!any && h->nremoved == 0 && !pdims && !bias)
     return ts_index_search(h, queries, nq, q_dtype, k, out_scores, out_ids, flags, stream);
-  DeviceGuard g(h->device);
+  TsDeviceGuard g(h->device);
   hipStream_t s = (hipStream_t)stream;
   TS_CHECK(co_flush(h, s));   // a filtered search never joins a coalesced pass
   const int qp = queries_per_pass(h);
@@ -2104,11 +2058,11 @@ extern "C" int ts_index_search_biased(ts_index* h, const void* queries, int32_t 
   {
     // bias_stage: [0, 32) the padded entries of the last, partial row block; from float 32 on the staged copy of a
     // host array.  Written in stream order; the call returns with the stream drained, so the next call may reuse it.
-    DeviceGuard g(h->device);
+    TsDeviceGuard g(h->device);
     hipStream_t s = (hipStream_t)stream;
     TS_CHECK(co_flush(h, s));   // held coalesced passes first, then the call's own work
     const int64_t full = N / TS_ROWS_PER_BLOCK * TS_ROWS_PER_BLOCK;
-    TS_CHECK(ensure(h->bias_stage, (size_t)(TS_ROWS_PER_BLOCK + (host ? N : 0)) * 4));
+    TS_CHECK(ts_buf_ensure(h->bias_stage, (size_t)(TS_ROWS_PER_BLOCK + (host ? N : 0)) * 4));
     tail = (float*)h->bias_stage.p;
     if (host) {
       TS_HIP(hipMemcpyAsync(tail + TS_ROWS_PER_BLOCK, bias, (size_t)N * 4, hipMemcpyHostToDevice, s));
@@ -2141,7 +2095,7 @@ extern "C" int ts_index_rescore(ts_index* h, const void* queries, int32_t nq, in
   TS_CHECK(funnel_storage_ok(h, "rescore"));
   if (nq == 0) return TS_OK;
   if (h->ntotal == 0) return err_empty();
-  DeviceGuard g(h->device);
+  TsDeviceGuard g(h->device);
   hipStream_t s = (hipStream_t)stream;
   TS_CHECK(co_flush(h, s));
   TsMmrSource src;
@@ -2160,7 +2114,7 @@ extern "C" int ts_index_rescore(ts_index* h, const void* queries, int32_t nq, in
   const int qc = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(nq, qp), kRescoreScratchCap / per_q));
   const size_t qrow = (size_t)h->L.dim * dtype_size(q_dtype);
   std::lock_guard<std::mutex> rlk(h->rescore_mu);   // one scratch per handle; the call ends with the stream drained
-  TS_CHECK(ensure(h->rescore_scratch, per_q * qc));
+  TS_CHECK(ts_buf_ensure(h->rescore_scratch, per_q * qc));
   char* base = (char*)h->rescore_scratch.p;
   uint4* tile = (uint4*)base;
   int64_t* ids = (int64_t*)(base + tile_b * qc);
@@ -2223,9 +2177,9 @@ static int range_reserve(ts_index* h, int64_t need, int64_t have, int64_t limit,
   if (need <= h->rng_cap) return TS_OK;
   int64_t cap = std::max<int64_t>(need, std::min<int64_t>(limit, 2 * h->rng_cap));
   cap = std::max<int64_t>(cap, 1 << 16);
-  DevBuf ns, ni;
-  int st = ensure(ns, (size_t)cap * 4);
-  if (st == TS_OK) st = ensure(ni, (size_t)cap * 8);
+  TsDevBuf ns, ni;
+  int st = ts_buf_ensure(ns, (size_t)cap * 4);
+  if (st == TS_OK) st = ts_buf_ensure(ni, (size_t)cap * 8);
   if (st == TS_OK && have > 0 &&
       (hipMemcpyAsync(ns.p, h->rng_s.p, (size_t)have * 4, hipMemcpyDeviceToDevice, s) != hipSuccess ||
        hipMemcpyAsync(ni.p, h->rng_i.p, (size_t)have * 8, hipMemcpyDeviceToDevice, s) != hipSuccess)) {
@@ -2234,9 +2188,9 @@ static int range_reserve(ts_index* h, int64_t need, int64_t have, int64_t limit,
   }
   // (the old buffers are freed below: everything that reads or writes them has to be over)
   if (st == TS_OK && hipStreamSynchronize(s) != hipSuccess) { ts_set_error("hipStreamSynchronize failed"); st = TS_ERR_HIP; }
-  if (st != TS_OK) { release(ns); release(ni); return st; }
-  release(h->rng_s);
-  release(h->rng_i);
+  if (st != TS_OK) { ts_buf_release(ns); ts_buf_release(ni); return st; }
+  ts_buf_release(h->rng_s);
+  ts_buf_release(h->rng_i);
   h->rng_s = ns;
   h->rng_i = ni;
   h->rng_cap = cap;
@@ -2274,8 +2228,8 @@ static int range_pass(ts_index* h, const void* dq, int nq, int q_dtype, const fl
   if (filter) {
     stats->filter_passes += 1;
     TS_HIP(hipMemcpyAsync(W.tau(), tau, sizeof(tau), hipMemcpyHostToDevice, s));
-    TS_CHECK(ensure(W.cand_score, (size_t)TS_MAX_Q * kCandCap * 4));
-    TS_CHECK(ensure(W.cand_id, (size_t)TS_MAX_Q * kCandCap * 4));
+    TS_CHECK(ts_buf_ensure(W.cand_score, (size_t)TS_MAX_Q * kCandCap * 4));
+    TS_CHECK(ts_buf_ensure(W.cand_id, (size_t)TS_MAX_Q * kCandCap * 4));
     ScanParams sp = scan_base(h, W, nq);
     scan_filter(sp, W, nblk);
     if (mc) {
@@ -2321,9 +2275,9 @@ static int range_pass(ts_index* h, const void* dq, int nq, int q_dtype, const fl
     const auto [chunk_rows, nch] = dense_chunks(N);
     const int64_t chunk_tiles = (chunk_rows + TS_RANGE_TILE - 1) / TS_RANGE_TILE;
     const int64_t ntiles = nch * chunk_tiles;
-    TS_CHECK(ensure(W.dense, (size_t)nq * chunk_rows * 4));
-    if (mc) TS_CHECK(ensure(W.mids, (size_t)nq * chunk_rows * 4));
-    TS_CHECK(ensure(h->rng_tiles, 256 + (size_t)nq * ntiles * 4));
+    TS_CHECK(ts_buf_ensure(W.dense, (size_t)nq * chunk_rows * 4));
+    if (mc) TS_CHECK(ts_buf_ensure(W.mids, (size_t)nq * chunk_rows * 4));
+    TS_CHECK(ts_buf_ensure(h->rng_tiles, 256 + (size_t)nq * ntiles * 4));
     uint32_t* dtotal = (uint32_t*)h->rng_tiles.p;
     TsRangeDenseParams dp{};
     dp.dense = (const float*)W.dense.p;
@@ -2424,7 +2378,7 @@ extern "C" int ts_index_range_search(ts_index* h, const void* queries, int32_t n
   TS_CHECK(check_mask_words("range_search", n_masks, allow_words, N));
   if (N == 0) return err_empty();
   const int64_t limit = max_total <= 0 ? kRangeDefaultMax : max_total;
-  DeviceGuard g(h->device);
+  TsDeviceGuard g(h->device);
   hipStream_t s = (hipStream_t)stream;
   TS_CHECK(co_flush(h, s));   // a range search never joins a coalesced pass
   std::lock_guard<std::mutex> rlk(h->range_mu);
@@ -2485,7 +2439,7 @@ extern "C" int ts_index_range_fetch(ts_index* h, float* out_scores, int64_t* out
   }
   if (n == 0) return TS_OK;
   if (!out_scores || !out_ids) { ts_set_error("range_fetch: null output"); return TS_ERR_INVALID; }
-  DeviceGuard g(h->device);
+  TsDeviceGuard g(h->device);
   hipStream_t s = (hipStream_t)stream;
   const hipMemcpyKind kind = (flags & TS_FLAG_HOST_PTR) ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
   TS_HIP(hipMemcpyAsync(out_scores, h->rng_s.p, (size_t)n * 4, kind, s));
@@ -2512,7 +2466,7 @@ extern "C" int ts_index_remove(ts_index* h, const int64_t* ids, int64_t n, int64
   if (!h || !n_removed || n < 0 || (n > 0 && !ids)) { ts_set_error("bad arguments to remove"); return TS_ERR_INVALID; }
   *n_removed = 0;
   if (n == 0 || h->ntotal == 0) return TS_OK;
-  DeviceGuard g(h->device);
+  TsDeviceGuard g(h->device);
   hipStream_t s = (hipStream_t)stream;
   TS_CHECK(co_flush(h, s));   // held passes search the index as it was when they were submitted
   h->rng_valid = false;
@@ -2527,7 +2481,7 @@ extern "C" int ts_index_remove(ts_index* h, const int64_t* ids, int64_t n, int64
     TS_CHECK(ts_launch_live_set((uint32_t*)h->live.p, 0, h->ntotal, s));
   }
   const int64_t chunk = std::min<int64_t>(n, 1 << 22);
-  TS_CHECK(ensure(h->rids, (size_t)chunk * 8 + 256));
+  TS_CHECK(ts_buf_ensure(h->rids, (size_t)chunk * 8 + 256));
   unsigned long long* cnt = (unsigned long long*)((char*)h->rids.p + (size_t)chunk * 8);
   TS_HIP(hipMemsetAsync(cnt, 0, 8, s));
   for (int64_t i0 = 0; i0 < n; i0 += chunk) {
@@ -2584,7 +2538,7 @@ extern "C" int ts_index_update(ts_index* h, const int64_t* ids, int64_t n, const
   std::vector<uint64_t> keys;   // row << 32 | position, ordered by row
   TS_CHECK(ts_update_check_ids(ids, n, h->id_offset, h->ntotal, r.data(), &keys));
   UPD_MARK(0);
-  DeviceGuard g(h->device);
+  TsDeviceGuard g(h->device);
   hipStream_t s = (hipStream_t)stream;
   TS_CHECK(co_flush(h, s));   // held passes search the rows as they were when they were submitted
   h->rng_valid = false;
@@ -2595,7 +2549,7 @@ extern "C" int ts_index_update(ts_index* h, const int64_t* ids, int64_t n, const
   UPD_MARK(1);
   if (h->nremoved > 0) {   // a removed row cannot be updated: counted before anything is written
     const int64_t chunk = std::min<int64_t>(n, 1 << 22);
-    TS_CHECK(ensure(h->rids, (size_t)chunk * 8 + 256));
+    TS_CHECK(ts_buf_ensure(h->rids, (size_t)chunk * 8 + 256));
     unsigned long long* cnt = (unsigned long long*)((char*)h->rids.p + (size_t)chunk * 8);
     unsigned long long dead[2] = {0ull, ~0ull};
     for (int64_t i0 = 0; i0 < n; i0 += chunk) {
@@ -2626,9 +2580,9 @@ extern "C" int ts_index_update(ts_index* h, const int64_t* ids, int64_t n, const
   if (host) chunk = std::min(chunk, std::max<int64_t>(TS_ROWS_PER_BLOCK, (int64_t)((64u << 20) / row_bytes) / TS_ROWS_PER_BLOCK * TS_ROWS_PER_BLOCK));
   chunk = std::min(chunk, (n + TS_ROWS_PER_BLOCK - 1) / TS_ROWS_PER_BLOCK * TS_ROWS_PER_BLOCK);
   const size_t tile_bytes = run ? 0 : (size_t)(chunk / TS_ROWS_PER_BLOCK) * bb;
-  if (!run) TS_CHECK(ensure(h->upd_tile, tile_bytes));
-  if (host) TS_CHECK(ensure(h->stage, (size_t)chunk * row_bytes));
-  if (norm) TS_CHECK(ensure(h->den, (size_t)chunk * 4));
+  if (!run) TS_CHECK(ts_buf_ensure(h->upd_tile, tile_bytes));
+  if (host) TS_CHECK(ts_buf_ensure(h->stage, (size_t)chunk * row_bytes));
+  if (norm) TS_CHECK(ts_buf_ensure(h->den, (size_t)chunk * 4));
   TsUpdateTables tab;
   std::vector<uint64_t> chunk_keys;
   if (!run && keys.empty()) ts_update_sort_rows(r.data(), n, &keys);   // (ascending ids that are not one run)
@@ -2662,7 +2616,7 @@ extern "C" int ts_index_update(ts_index* h, const int64_t* ids, int64_t n, const
     const std::vector<int32_t>* parts[5] = {&tab.full_blk, &tab.full_src, &tab.part_blk, &tab.part_first, &tab.part_item};
     size_t off[6] = {0};
     for (int i = 0; i < 5; ++i) off[i + 1] = off[i] + ((parts[i]->size() + 63) & ~(size_t)63);
-    TS_CHECK(ensure(h->upd_tab, off[5] * 4));
+    TS_CHECK(ts_buf_ensure(h->upd_tab, off[5] * 4));
     int32_t* dtab = (int32_t*)h->upd_tab.p;
     for (int i = 0; i < 5; ++i)
       if (!parts[i]->empty())
@@ -2694,7 +2648,7 @@ extern "C" int ts_index_live_words(ts_index* h, uint32_t* out, void* stream) {
     }
     return TS_OK;
   }
-  DeviceGuard g(h->device);
+  TsDeviceGuard g(h->device);
   hipStream_t s = (hipStream_t)stream;
   TS_HIP(hipMemcpyAsync(out, h->live.p, (size_t)words * 4, hipMemcpyDeviceToHost, s));
   TS_HIP(hipStreamSynchronize(s));
@@ -2709,7 +2663,7 @@ extern "C" int ts_index_compact(ts_index* h, int64_t* old2new, void* stream) {
       for (int64_t r = 0; r < N; ++r) old2new[r] = r;
     return TS_OK;
   }
-  DeviceGuard g(h->device);
+  TsDeviceGuard g(h->device);
   hipStream_t s = (hipStream_t)stream;
   TS_CHECK(co_flush(h, s));
   h->rng_valid = false;
@@ -2718,9 +2672,9 @@ extern "C" int ts_index_compact(ts_index* h, int64_t* old2new, void* stream) {
   TS_CHECK(wait_for_searches(h, s));
   const size_t sb = ts_compact_scratch_bytes(N);
   if (sb == 0) { ts_set_error("bad compaction size"); return TS_ERR_INVALID; }
-  TS_CHECK(ensure(h->compact_scratch, sb + (old2new ? (size_t)N * 8 : 0)));
+  TS_CHECK(ts_buf_ensure(h->compact_scratch, sb + (old2new ? (size_t)N * 8 : 0)));
   const size_t stage = std::max(kCompactStageBytes - kCompactStageBytes % ts_block_bytes(h->L), ts_block_bytes(h->L));
-  TS_CHECK(ensure(h->compact_stage, stage));
+  TS_CHECK(ts_buf_ensure(h->compact_stage, stage));
   int64_t* o2n = old2new ? (int64_t*)((char*)h->compact_scratch.p + sb) : nullptr;
   int64_t nlive = 0;
   const int st = ts_compact_corpus(h->L, h->corpus, (const uint32_t*)h->live.p, N, h->compact_scratch.p, sb,
@@ -2730,8 +2684,8 @@ extern "C" int ts_index_compact(ts_index* h, int64_t* old2new, void* stream) {
   if (old2new) TS_HIP(hipMemcpyAsync(old2new, o2n, (size_t)N * 8, hipMemcpyDeviceToHost, s));
   TS_HIP(hipStreamSynchronize(s));
   // the staging buffer is the size of a few hundred row blocks: given back, as the scratch is
-  release(h->compact_stage);
-  release(h->compact_scratch);
+  ts_buf_release(h->compact_stage);
+  ts_buf_release(h->compact_scratch);
   h->ntotal = nlive;
   h->nremoved = 0;
   return TS_OK;
@@ -2750,7 +2704,7 @@ extern "C" int ts_index_scores(ts_index* h, const void* queries, int32_t nq, int
     return TS_ERR_INVALID;
   }
   if (N == 0) return err_empty();
-  DeviceGuard g(h->device);
+  TsDeviceGuard g(h->device);
   hipStream_t s = (hipStream_t)stream;
   TS_CHECK(co_flush(h, s));
   const int qp = queries_per_pass(h);
@@ -2792,7 +2746,7 @@ extern "C" int ts_index_finish(ts_index* h, void* stream, int64_t* failed_ticket
     ts_set_error("bad arguments to finish");
     return TS_ERR_INVALID;
   }
-  DeviceGuard g(h->device);
+  TsDeviceGuard g(h->device);
   {
     std::lock_guard<std::mutex> clk(h->co_mu);
     TS_CHECK(co_flush_locked(h, (hipStream_t)stream));   // the sync below then covers every held pass
@@ -2831,7 +2785,7 @@ extern "C" int ts_index_finish(ts_index* h, void* stream, int64_t* failed_ticket
 
 extern "C" int ts_index_set_profiling(ts_index* h, int32_t on) {
   if (!h) { ts_set_error("null handle"); return TS_ERR_INVALID; }
-  DeviceGuard g(h->device);
+  TsDeviceGuard g(h->device);
   if (on && !h->ev[0]) {
     for (hipEvent_t& e : h->ev) TS_HIP(hipEventCreate(&e));
   }
@@ -2903,7 +2857,7 @@ extern "C" int ts_index_read_probe(ts_index* h, int32_t reps, double* ms_avg, do
     return TS_ERR_INVALID;
   }
   if (h->ntotal == 0) return err_empty();
-  DeviceGuard g(h->device);
+  TsDeviceGuard g(h->device);
   hipStream_t s = (hipStream_t)stream;
   const int64_t nblk = (h->ntotal + TS_ROWS_PER_BLOCK - 1) / TS_ROWS_PER_BLOCK;
   const int grid = std::max(1, filter_scan_cus(h));
@@ -3008,7 +2962,7 @@ static int merge_impl(const float* scores, const int64_t* ids, int32_t nlists, i
     ts_set_error("merge: k = %d exceeds %d", k, TS_SEL_LDS_KEYS / 2);
     return TS_ERR_UNSUPPORTED;
   }
-  DeviceGuard g(device);
+  TsDeviceGuard g(device);
   if (!g.ok) { ts_set_error("hipSetDevice(%d) failed", device); return TS_ERR_HIP; }
   if ((int64_t)nlists * k <= TS_SEL_LDS_KEYS)
     return merge_once(scores, ids, nlists, nq, k, score_list_stride, id_list_stride, out_scores, out_ids, stream);
@@ -3067,7 +3021,7 @@ extern "C" int ts_maxsim(const void* q, int32_t Lq, const void* docs, const int3
     ts_set_error("bad arguments to maxsim");
     return TS_ERR_INVALID;
   }
-  DeviceGuard g(device);
+  TsDeviceGuard g(device);
   if (!g.ok) { ts_set_error("hipSetDevice(%d) failed", device); return TS_ERR_HIP; }
   const int st = ts_launch_maxsim16(q, Lq, docs, doc_off, nullptr, nullptr, n_docs, H, dtype, mode, out,
                                     device, (hipStream_t)stream);
@@ -3085,7 +3039,7 @@ extern "C" int ts_maxsim_indexed(const void* q, int32_t Lq, const void* store, c
     ts_set_error("bad arguments to maxsim_indexed");
     return TS_ERR_INVALID;
   }
-  DeviceGuard g(device);
+  TsDeviceGuard g(device);
   if (!g.ok) { ts_set_error("hipSetDevice(%d) failed", device); return TS_ERR_HIP; }
   const int st = ts_launch_maxsim16(q, Lq, store, nullptr, starts, lens, n_docs, H, dtype, mode, out,
                                     device, (hipStream_t)stream);
@@ -3109,7 +3063,7 @@ extern "C" int ts_maxsim_indexed_batch(const void* q, const int32_t* q_off, int3
       ts_set_error("maxsim_indexed_batch: offsets must be non-decreasing");
       return TS_ERR_INVALID;
     }
-  DeviceGuard g(device);
+  TsDeviceGuard g(device);
   if (!g.ok) { ts_set_error("hipSetDevice(%d) failed", device); return TS_ERR_HIP; }
   const int st = ts_launch_maxsim16_batch(q, q_off, nq, store, starts, lens, cand_off, H, dtype, mode, out,
                                           device, (hipStream_t)stream);
@@ -3142,7 +3096,7 @@ extern "C" int ts_maxsim_indexed_fp8(const void* q, int32_t q_dtype, int32_t Lq,
     return TS_ERR_UNSUPPORTED;
   }
   if (n_docs == 0) return TS_OK;
-  DeviceGuard g(device);
+  TsDeviceGuard g(device);
   if (!g.ok) { ts_set_error("hipSetDevice(%d) failed", device); return TS_ERR_HIP; }
   const int st = ts_launch_maxsim16(q, Lq, store, nullptr, starts, lens, n_docs, H, TS_FP8_E4M3, mode, out,
                                     device, (hipStream_t)stream, q_dtype);
@@ -3170,7 +3124,7 @@ extern "C" int ts_maxsim_indexed_batch_fp8(const void* q, int32_t q_dtype, const
     return TS_ERR_UNSUPPORTED;
   }
   if (nq == 0) return TS_OK;
-  DeviceGuard g(device);
+  TsDeviceGuard g(device);
   if (!g.ok) { ts_set_error("hipSetDevice(%d) failed", device); return TS_ERR_HIP; }
   const int st = ts_launch_maxsim16_batch(q, q_off, nq, store, starts, lens, cand_off, H, TS_FP8_E4M3, mode, out,
                                           device, (hipStream_t)stream, q_dtype);
@@ -3197,7 +3151,7 @@ extern "C" int ts_quantize_rows_fp8(const void* x, int32_t x_dtype, int64_t rows
     return TS_ERR_UNSUPPORTED;
   }
   if (rows == 0) return TS_OK;
-  DeviceGuard g(device);
+  TsDeviceGuard g(device);
   if (!g.ok) { ts_set_error("hipSetDevice(%d) failed", device); return TS_ERR_HIP; }
   return ts_launch_quantize_rows_fp8(x, x_dtype, rows, H, out, (hipStream_t)stream);
 }

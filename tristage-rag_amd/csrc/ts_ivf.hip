@@ -36,44 +36,8 @@ constexpr int64_t kIvfAddChunkRows = 1 << 16;
 constexpr int kIvfTrainPerList = 256;          // FAISS max_points_per_centroid
 constexpr float kIvfSplitEps = 1.0f / 1024.0f; // FAISS's empty-cluster split perturbation
 
-struct IvfGuard {
-  int prev = -1;
-  bool ok = true;
-  explicit IvfGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) ok = (hipSetDevice(dev) == hipSuccess);
-  }
-  ~IvfGuard() {
-    int cur = -1;
-    if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-  }
-};
-
-struct IvfBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-};
-
-int ivf_ensure(IvfBuf& b, size_t bytes) {
-  if (b.bytes >= bytes && b.p) return TS_OK;
-  if (b.p) {
-    TS_HIP(hipFree(b.p));
-    b.p = nullptr;
-    b.bytes = 0;
-  }
-  const size_t want = (bytes + 0xFFFFF) & ~(size_t)0xFFFFF;
-  hipError_t e = hipMalloc(&b.p, want);
-  if (e != hipSuccess) {
-    b.p = nullptr;
-    ts_set_error("hipMalloc(%zu bytes) failed: %s", want, hipGetErrorString(e));
-    return TS_ERR_OOM;
-  }
-  b.bytes = want;
-  return TS_OK;
-}
-
 // a buffer that keeps its first `keep` bytes when it grows
-int ivf_grow(IvfBuf& b, size_t bytes, size_t keep, hipStream_t s) {
+int ivf_grow(TsDevBuf& b, size_t bytes, size_t keep, hipStream_t s) {
   if (b.bytes >= bytes && b.p) return TS_OK;
   const size_t want = std::max((bytes + 0xFFFFF) & ~(size_t)0xFFFFF, b.bytes + b.bytes / 2);
   void* np = nullptr;
@@ -88,12 +52,6 @@ int ivf_grow(IvfBuf& b, size_t bytes, size_t keep, hipStream_t s) {
   b.p = np;
   b.bytes = want;
   return TS_OK;
-}
-
-void ivf_release(IvfBuf& b) {
-  if (b.p) (void)hipFree(b.p);
-  b.p = nullptr;
-  b.bytes = 0;
 }
 
 uint64_t splitmix64(uint64_t& x) {
@@ -120,14 +78,14 @@ struct ts_ivf {
   std::vector<std::vector<int32_t>> list_blocks;
   std::vector<int64_t> list_size;      // slots taken per list (where add continues)
   std::vector<int64_t> list_removed;   // of them removed (ts_remove_ivf): dlist_size = list_size - list_removed
-  IvfBuf corpus, blk_list, blk_valid, slot2id, id2slot, dlist_size;
+  TsDevBuf corpus, blk_list, blk_valid, slot2id, id2slot, dlist_size;
   // add staging
-  IvfBuf tmp_tiled, tmp_f32, den, assign, ascore, dst;
-  IvfBuf upd_ids;   // ts_update_ivf: the chunk's local ids
+  TsDevBuf tmp_tiled, tmp_f32, den, assign, ascore, dst;
+  TsDevBuf upd_ids;   // ts_update_ivf: the chunk's local ids
   // search workspace
-  IvfBuf qimg, small, pid, pscore, bits, live, sample, cand_score, cand_id, dense, mids, list_score, list_id;
+  TsDevBuf qimg, small, pid, pscore, bits, live, sample, cand_score, cand_id, dense, mids, list_score, list_id;
   // training
-  IvfBuf train_x, cent, perm, offs;
+  TsDevBuf train_x, cent, perm, offs;
   uint32_t* host_rep = nullptr;      // pinned + mapped: select report (64 counts, status, live blocks)
   uint32_t* host_rep_dev = nullptr;
   TsMmrWork mmr;                     // ts_mmr_ivf: scratch and staging, allocated at the first call
@@ -549,9 +507,7 @@ __global__ __launch_bounds__(256) void ivf_normalize_kernel(float* cent, int dim
 }
 
 // ------------------------------------------------------------------ host helpers
-static size_t ivf_scan_lds(const TsLayout& L, int qh, int mode) {
-  return (size_t)L.kg * qh * 1024 + (mode == SCAN_FILTER ? sizeof(StageLds) : 0);
-}
+static size_t ivf_scan_lds(const TsLayout& L, int qh, int mode) { return ts_scan_lds(L.kg, qh, mode, sizeof(StageLds)); }
 
 template <int DT, int QH, int MODE>
 static int launch_ivf_t(const TsLayout& L, const IvfScanParams& p, int grid, hipStream_t s) {
@@ -577,17 +533,13 @@ static int launch_ivf_scan(const TsLayout& L, int mode, int qh, const IvfScanPar
                  : launch_ivf_t<TS_BF16, 2, SCAN_FILTER>(L, p, grid, s);
 }
 
-static int ivf_queries_per_pass(const TsLayout& L) {
-  return ivf_scan_lds(L, 2, SCAN_FILTER) <= 160 * 1024 ? 64 : 32;
-}
-
 // the quantizer's exact top-k of `n` fp32 / f16 / bf16 rows against the centroids, in asynchronous slices (its dense
 // path: nothing to verify); the results are complete in stream order
 static int ivf_quant_topk(ts_ivf* h, const void* x, int64_t n, int dt, int k, float* out_s, int64_t* out_i,
                           hipStream_t s) {
   const size_t row = (size_t)h->L.dim * (dt == TS_F32 ? 4 : 2);
   const TsLayout QL = ts_make_layout(h->L.dim, TS_F32);
-  const int64_t slice = (ts_scan_lds_bytes(QL, 2) <= 160 * 1024 ? 64 : 32) * 4;
+  const int64_t slice = ts_queries_per_pass(QL) * 4;
   for (int64_t r0 = 0; r0 < n; r0 += slice) {
     const int c = (int)std::min(slice, n - r0);
     TS_CHECK(ts_index_search(h->quant, (const char*)x + (size_t)r0 * row, c, dt, k, out_s + (size_t)r0 * k,
@@ -613,14 +565,14 @@ extern "C" int ts_ivf_create(int32_t dim, int32_t nlist, int32_t storage_dtype, 
     return TS_ERR_INVALID;
   }
   const TsLayout L = ts_make_layout(dim, storage_dtype);
-  if (ivf_scan_lds(L, 1, SCAN_FILTER) > 160 * 1024) {
+  if (ivf_scan_lds(L, 1, SCAN_FILTER) > TS_LDS_BYTES) {
     ts_set_error("dim %d too large for the LDS-resident query image", dim);
     return TS_ERR_UNSUPPORTED;
   }
   int ndev = 0;
   TS_HIP(hipGetDeviceCount(&ndev));
   if (device < 0 || device >= ndev) { ts_set_error("device %d not present (%d HIP devices)", device, ndev); return TS_ERR_INVALID; }
-  IvfGuard g(device);
+  TsDeviceGuard g(device);
   if (!g.ok) { ts_set_error("hipSetDevice(%d) failed", device); return TS_ERR_HIP; }
   ts_ivf* h = new (std::nothrow) ts_ivf();
   if (!h) { ts_set_error("out of host memory"); return TS_ERR_OOM; }
@@ -635,8 +587,8 @@ extern "C" int ts_ivf_create(int32_t dim, int32_t nlist, int32_t storage_dtype, 
   if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
     h->num_cus = prop.multiProcessorCount;
   int st = ts_index_create(dim, TS_F32, TS_METRIC_INNER_PRODUCT, device, &h->quant);
-  if (st == TS_OK) st = ivf_ensure(h->small, 4096);
-  if (st == TS_OK) st = ivf_ensure(h->dlist_size, (size_t)nlist * 8);
+  if (st == TS_OK) st = ts_buf_ensure(h->small, 4096);
+  if (st == TS_OK) st = ts_buf_ensure(h->dlist_size, (size_t)nlist * 8);
   if (st == TS_OK && (hipMemset(h->small.p, 0, 4096) != hipSuccess || hipMemset(h->dlist_size.p, 0, (size_t)nlist * 8) != hipSuccess)) {
     ts_set_error("hipMemset failed");
     st = TS_ERR_HIP;
@@ -661,15 +613,15 @@ extern "C" int ts_ivf_create(int32_t dim, int32_t nlist, int32_t storage_dtype, 
 
 extern "C" int ts_ivf_destroy(ts_ivf* h) {
   if (!h) { ts_set_error("null handle"); return TS_ERR_INVALID; }
-  IvfGuard g(h->device);
+  TsDeviceGuard g(h->device);
   (void)hipDeviceSynchronize();
   if (h->quant) ts_index_destroy(h->quant);
-  IvfBuf* bufs[] = {&h->corpus, &h->blk_list, &h->blk_valid, &h->slot2id, &h->id2slot, &h->dlist_size,
-                    &h->tmp_tiled, &h->tmp_f32, &h->den, &h->assign, &h->ascore, &h->dst, &h->qimg, &h->small,
-                    &h->pid, &h->pscore, &h->bits, &h->live, &h->sample, &h->cand_score, &h->cand_id, &h->dense,
-                    &h->mids, &h->list_score, &h->list_id, &h->train_x, &h->cent, &h->perm, &h->offs,
-                    &h->upd_ids};
-  for (IvfBuf* b : bufs) ivf_release(*b);
+  TsDevBuf* bufs[] = {&h->corpus, &h->blk_list, &h->blk_valid, &h->slot2id, &h->id2slot, &h->dlist_size,
+                      &h->tmp_tiled, &h->tmp_f32, &h->den, &h->assign, &h->ascore, &h->dst, &h->qimg, &h->small,
+                      &h->pid, &h->pscore, &h->bits, &h->live, &h->sample, &h->cand_score, &h->cand_id, &h->dense,
+                      &h->mids, &h->list_score, &h->list_id, &h->train_x, &h->cent, &h->perm, &h->offs,
+                      &h->upd_ids};
+  for (TsDevBuf* b : bufs) ts_buf_release(*b);
   if (h->host_rep) (void)hipHostFree(h->host_rep);
   ts_mmr_release(h->mmr);
   delete h;
@@ -678,7 +630,7 @@ extern "C" int ts_ivf_destroy(ts_ivf* h) {
 
 extern "C" int ts_ivf_reset(ts_ivf* h) {
   if (!h) { ts_set_error("null handle"); return TS_ERR_INVALID; }
-  IvfGuard g(h->device);
+  TsDeviceGuard g(h->device);
   // The list sizes are cleared on the null stream, which a non-blocking caller stream does not wait for, and a memset
   // of device memory need not be complete when hipMemset returns: the next add, on any stream, must find it done.
   TS_HIP(hipMemset(h->dlist_size.p, 0, (size_t)h->nlist * 8));
@@ -699,11 +651,11 @@ extern "C" int ts_remove_ivf(ts_ivf* h, const int64_t* ids, int64_t n, int64_t* 
   if (!h || !n_removed || n < 0 || (n > 0 && !ids)) { ts_set_error("bad arguments to remove"); return TS_ERR_INVALID; }
   *n_removed = 0;
   if (n == 0 || h->ntotal == 0) return TS_OK;
-  IvfGuard g(h->device);
+  TsDeviceGuard g(h->device);
   hipStream_t s = (hipStream_t)stream;
   const int64_t chunk = std::min<int64_t>(n, 1 << 20);
-  TS_CHECK(ivf_ensure(h->dst, (size_t)chunk * 8));
-  TS_CHECK(ivf_ensure(h->assign, (size_t)chunk * 8));
+  TS_CHECK(ts_buf_ensure(h->dst, (size_t)chunk * 8));
+  TS_CHECK(ts_buf_ensure(h->assign, (size_t)chunk * 8));
   std::vector<int32_t> lists(chunk);
   std::vector<int64_t> live_size(h->nlist);
   int64_t cleared = 0;
@@ -748,7 +700,7 @@ extern "C" int ts_ivf_last_search_info(const ts_ivf* h, int64_t info[4]) {
 extern "C" int ts_ivf_set_centroids(ts_ivf* h, const float* centroids, void* stream) {
   if (!h || !centroids) { ts_set_error("bad arguments to set_centroids"); return TS_ERR_INVALID; }
   if (h->ntotal > 0) { ts_set_error("set_centroids on a non-empty IVF index: reset() first"); return TS_ERR_INVALID; }
-  IvfGuard g(h->device);
+  TsDeviceGuard g(h->device);
   hipStream_t s = (hipStream_t)stream;
   TS_CHECK(ivf_load_centroids(h, centroids, s));
   TS_HIP(hipStreamSynchronize(s));
@@ -759,7 +711,7 @@ extern "C" int ts_ivf_set_centroids(ts_ivf* h, const float* centroids, void* str
 extern "C" int ts_ivf_get_centroids(ts_ivf* h, float* out, void* stream) {
   if (!h || !out) { ts_set_error("bad arguments to get_centroids"); return TS_ERR_INVALID; }
   if (!h->trained) { ts_set_error("the IVF index is not trained"); return TS_ERR_INVALID; }
-  IvfGuard g(h->device);
+  TsDeviceGuard g(h->device);
   return ts_index_reconstruct(h->quant, 0, h->nlist, out, 0, stream);
 }
 
@@ -774,7 +726,7 @@ extern "C" int ts_ivf_train(ts_ivf* h, const void* x, int64_t n, int32_t x_dtype
     return TS_ERR_INVALID;
   }
   if (h->ntotal > 0) { ts_set_error("train on a non-empty IVF index: reset() first"); return TS_ERR_INVALID; }
-  IvfGuard g(h->device);
+  TsDeviceGuard g(h->device);
   hipStream_t s = (hipStream_t)stream;
   const int dim = h->L.dim, nl = h->nlist;
   // the training sample and the initial centroids: a seeded partial Fisher-Yates shuffle of the point ids
@@ -786,12 +738,12 @@ extern "C" int ts_ivf_train(ts_ivf* h, const void* x, int64_t n, int32_t x_dtype
     const int64_t j = i + (int64_t)(splitmix64(rs) % (uint64_t)(n - i));
     std::swap(ids[i], ids[j]);
   }
-  TS_CHECK(ivf_ensure(h->perm, (size_t)std::max<int64_t>(nt, 1) * 8));
-  TS_CHECK(ivf_ensure(h->train_x, (size_t)nt * dim * 4));
-  TS_CHECK(ivf_ensure(h->cent, (size_t)nl * dim * 4));
-  TS_CHECK(ivf_ensure(h->assign, (size_t)nt * 8));
-  TS_CHECK(ivf_ensure(h->ascore, (size_t)nt * 4));
-  TS_CHECK(ivf_ensure(h->offs, (size_t)(nl + 1) * 8));
+  TS_CHECK(ts_buf_ensure(h->perm, (size_t)std::max<int64_t>(nt, 1) * 8));
+  TS_CHECK(ts_buf_ensure(h->train_x, (size_t)nt * dim * 4));
+  TS_CHECK(ts_buf_ensure(h->cent, (size_t)nl * dim * 4));
+  TS_CHECK(ts_buf_ensure(h->assign, (size_t)nt * 8));
+  TS_CHECK(ts_buf_ensure(h->ascore, (size_t)nt * 4));
+  TS_CHECK(ts_buf_ensure(h->offs, (size_t)(nl + 1) * 8));
   TS_HIP(hipMemcpyAsync(h->perm.p, ids.data(), (size_t)nt * 8, hipMemcpyHostToDevice, s));
   const int64_t tot = nt * dim;
   const unsigned gb = (unsigned)((tot + 255) / 256);
@@ -902,18 +854,18 @@ extern "C" int ts_ivf_add(ts_ivf* h, const void* rows, int64_t n, int32_t rows_d
   }
   if (!h->trained) { ts_set_error("add before train: the IVF index has no centroids"); return TS_ERR_INVALID; }
   if ((h->ntotal + n) + 32LL * h->nlist >= (1LL << 31)) { ts_set_error("at most 2^31 slots per IVF index"); return TS_ERR_UNSUPPORTED; }
-  IvfGuard g(h->device);
+  TsDeviceGuard g(h->device);
   hipStream_t s = (hipStream_t)stream;
   const bool norm = (flags & TS_FLAG_NORMALIZE) != 0;
   const size_t row_bytes = (size_t)h->L.dim * (rows_dtype == TS_F32 ? 4 : 2);
   const int64_t chunk = std::min(n, kIvfAddChunkRows);
   const int64_t cblk = (chunk + 31) / 32;
-  TS_CHECK(ivf_ensure(h->tmp_tiled, (size_t)cblk * ts_block_bytes(h->L)));
-  TS_CHECK(ivf_ensure(h->tmp_f32, (size_t)chunk * h->L.dim * 4));
-  TS_CHECK(ivf_ensure(h->den, (size_t)chunk * 4));
-  TS_CHECK(ivf_ensure(h->assign, (size_t)chunk * 8));
-  TS_CHECK(ivf_ensure(h->ascore, (size_t)chunk * 4));
-  TS_CHECK(ivf_ensure(h->dst, (size_t)chunk * 8));
+  TS_CHECK(ts_buf_ensure(h->tmp_tiled, (size_t)cblk * ts_block_bytes(h->L)));
+  TS_CHECK(ts_buf_ensure(h->tmp_f32, (size_t)chunk * h->L.dim * 4));
+  TS_CHECK(ts_buf_ensure(h->den, (size_t)chunk * 4));
+  TS_CHECK(ts_buf_ensure(h->assign, (size_t)chunk * 8));
+  TS_CHECK(ts_buf_ensure(h->ascore, (size_t)chunk * 4));
+  TS_CHECK(ts_buf_ensure(h->dst, (size_t)chunk * 8));
   std::vector<int64_t> asg(chunk), dst(chunk), live_size(h->nlist);
   for (int64_t r0 = 0; r0 < n; r0 += chunk) {
     const int64_t c = std::min(chunk, n - r0);
@@ -966,19 +918,19 @@ extern "C" int ts_update_ivf(ts_ivf* h, const int64_t* ids, int64_t n, const voi
   std::vector<uint64_t> keys;
   TS_CHECK(ts_update_check_ids(ids, n, h->id_offset, h->ntotal, loc.data(), &keys));
   if (h->nblocks * 32 + n + 32LL * h->nlist >= (1LL << 31)) { ts_set_error("at most 2^31 slots per IVF index"); return TS_ERR_UNSUPPORTED; }
-  IvfGuard g(h->device);
+  TsDeviceGuard g(h->device);
   hipStream_t s = (hipStream_t)stream;
   const bool norm = (flags & TS_FLAG_NORMALIZE) != 0;
   const size_t row_bytes = (size_t)h->L.dim * (rows_dtype == TS_F32 ? 4 : 2);
   const int64_t chunk = std::min(n, kIvfAddChunkRows);
   const int64_t cblk = (chunk + 31) / 32;
-  TS_CHECK(ivf_ensure(h->tmp_tiled, (size_t)cblk * ts_block_bytes(h->L)));
-  TS_CHECK(ivf_ensure(h->tmp_f32, (size_t)chunk * h->L.dim * 4));
-  TS_CHECK(ivf_ensure(h->den, (size_t)chunk * 4));
-  TS_CHECK(ivf_ensure(h->assign, (size_t)chunk * 8));
-  TS_CHECK(ivf_ensure(h->ascore, (size_t)chunk * 4));
-  TS_CHECK(ivf_ensure(h->dst, (size_t)chunk * 8));
-  TS_CHECK(ivf_ensure(h->upd_ids, (size_t)chunk * 8 + 256));
+  TS_CHECK(ts_buf_ensure(h->tmp_tiled, (size_t)cblk * ts_block_bytes(h->L)));
+  TS_CHECK(ts_buf_ensure(h->tmp_f32, (size_t)chunk * h->L.dim * 4));
+  TS_CHECK(ts_buf_ensure(h->den, (size_t)chunk * 4));
+  TS_CHECK(ts_buf_ensure(h->assign, (size_t)chunk * 8));
+  TS_CHECK(ts_buf_ensure(h->ascore, (size_t)chunk * 4));
+  TS_CHECK(ts_buf_ensure(h->dst, (size_t)chunk * 8));
+  TS_CHECK(ts_buf_ensure(h->upd_ids, (size_t)chunk * 8 + 256));
   unsigned long long* cnt = (unsigned long long*)((char*)h->upd_ids.p + (size_t)chunk * 8);
   // a removed id cannot be updated: every id is checked before the first row moves
   for (int64_t i0 = 0; i0 < n; i0 += chunk) {
@@ -1045,10 +997,10 @@ extern "C" int ts_update_ivf(ts_ivf* h, const int64_t* ids, int64_t n, const voi
 // beside the old ones (peak: old + new corpus) and take their place at the end; until then nothing of the index changes.
 namespace {
 struct IvfCompactBufs {   // the new index while it is built; after the swap, the old one
-  IvfBuf corpus, blk_list, blk_valid, slot2id, id2slot, dlist_size, src_slot;
+  TsDevBuf corpus, blk_list, blk_valid, slot2id, id2slot, dlist_size, src_slot;
   ~IvfCompactBufs() {
-    IvfBuf* bufs[] = {&corpus, &blk_list, &blk_valid, &slot2id, &id2slot, &dlist_size, &src_slot};
-    for (IvfBuf* b : bufs) ivf_release(*b);
+    TsDevBuf* bufs[] = {&corpus, &blk_list, &blk_valid, &slot2id, &id2slot, &dlist_size, &src_slot};
+    for (TsDevBuf* b : bufs) ts_buf_release(*b);
   }
 };
 }  // namespace
@@ -1063,11 +1015,11 @@ extern "C" int ts_compact_ivf(ts_ivf* h, int64_t* old2new, void* stream) {
       for (int64_t i = 0; i < n; ++i) old2new[i] = i;
     return TS_OK;
   }
-  IvfGuard g(h->device);
+  TsDeviceGuard g(h->device);
   hipStream_t s = (hipStream_t)stream;
   // (1) the list of every id, -1 for a removed one
   std::vector<int32_t> lists((size_t)n);
-  TS_CHECK(ivf_ensure(h->assign, (size_t)n * 4));
+  TS_CHECK(ts_buf_ensure(h->assign, (size_t)n * 4));
   TS_CHECK(ts_launch_ivf_compact_classify((const int64_t*)h->id2slot.p, (const int64_t*)h->slot2id.p,
                                           (const int32_t*)h->blk_list.p, n, (int32_t*)h->assign.p, s));
   TS_HIP(hipMemcpyAsync(lists.data(), h->assign.p, (size_t)n * 4, hipMemcpyDeviceToHost, s));
@@ -1102,16 +1054,16 @@ extern "C" int ts_compact_ivf(ts_ivf* h, int64_t* old2new, void* stream) {
   ivf_place(new_blocks, new_size, &nb, lists.data(), nlive, dst, &new_blk_list);
   // (3) the new corpus and tables beside the old ones
   IvfCompactBufs nw;
-  TS_CHECK(ivf_ensure(nw.dlist_size, (size_t)h->nlist * 8));
+  TS_CHECK(ts_buf_ensure(nw.dlist_size, (size_t)h->nlist * 8));
   TS_HIP(hipMemcpyAsync(nw.dlist_size.p, new_size.data(), (size_t)h->nlist * 8, hipMemcpyHostToDevice, s));
   if (nlive > 0) {
-    TS_CHECK(ivf_ensure(nw.corpus, (size_t)nb * ts_block_bytes(h->L)));
-    TS_CHECK(ivf_ensure(nw.blk_list, (size_t)nb * 4));
-    TS_CHECK(ivf_ensure(nw.blk_valid, (size_t)nb * 4));
-    TS_CHECK(ivf_ensure(nw.slot2id, (size_t)nb * 32 * 8));
-    TS_CHECK(ivf_ensure(nw.id2slot, (size_t)nlive * 8));
-    TS_CHECK(ivf_ensure(nw.src_slot, (size_t)nb * 32 * 4));
-    TS_CHECK(ivf_ensure(h->dst, (size_t)nlive * 8));
+    TS_CHECK(ts_buf_ensure(nw.corpus, (size_t)nb * ts_block_bytes(h->L)));
+    TS_CHECK(ts_buf_ensure(nw.blk_list, (size_t)nb * 4));
+    TS_CHECK(ts_buf_ensure(nw.blk_valid, (size_t)nb * 4));
+    TS_CHECK(ts_buf_ensure(nw.slot2id, (size_t)nb * 32 * 8));
+    TS_CHECK(ts_buf_ensure(nw.id2slot, (size_t)nlive * 8));
+    TS_CHECK(ts_buf_ensure(nw.src_slot, (size_t)nb * 32 * 4));
+    TS_CHECK(ts_buf_ensure(h->dst, (size_t)nlive * 8));
     TS_HIP(hipMemcpyAsync(h->dst.p, up.data(), (size_t)nlive * 8, hipMemcpyHostToDevice, s));
     TS_HIP(hipMemcpyAsync(nw.blk_list.p, new_blk_list.data(), (size_t)nb * 4, hipMemcpyHostToDevice, s));
     TS_CHECK(ts_launch_ivf_compact_move(h->L, (const uint4*)h->corpus.p, (const int64_t*)h->id2slot.p,
@@ -1148,7 +1100,7 @@ extern "C" int ts_compact_ivf(ts_ivf* h, int64_t* old2new, void* stream) {
 extern "C" int ts_ivf_reconstruct(ts_ivf* h, int64_t id0, int64_t n, float* out, void* stream) {
   if (!h || !out || id0 < 0 || n < 0 || id0 + n > h->ntotal) { ts_set_error("bad arguments to reconstruct"); return TS_ERR_INVALID; }
   if (n == 0) return TS_OK;
-  IvfGuard g(h->device);
+  TsDeviceGuard g(h->device);
   hipStream_t s = (hipStream_t)stream;
   const int64_t t = n * h->L.dim;
   hipLaunchKernelGGL(ivf_reconstruct_kernel, dim3((unsigned)((t + 255) / 256)), dim3(256), 0, s,
@@ -1163,7 +1115,7 @@ extern "C" int ts_mmr_ivf(ts_ivf* h, const int64_t* cand_ids, const float* cand_
                           int32_t k, float lambda, float* out_rel, int64_t* out_ids, uint32_t flags, void* stream) {
   TS_CHECK(ts_mmr_check_args(h, cand_ids, cand_rel, nq, fetch_k, k, lambda, out_rel, out_ids));
   if (nq == 0) return TS_OK;
-  IvfGuard g(h->device);
+  TsDeviceGuard g(h->device);
   TsMmrSource src;
   src.corpus = (const uint4*)h->corpus.p;
   src.L = h->L;
@@ -1187,7 +1139,7 @@ extern "C" int ts_ivf_probe(ts_ivf* h, const void* queries, int32_t nq, int32_t 
   if (nprobe > h->nlist) { ts_set_error("nprobe %d > nlist %d", nprobe, h->nlist); return TS_ERR_INVALID; }
   if (!h->trained) { ts_set_error("the IVF index is not trained"); return TS_ERR_INVALID; }
   if (nq == 0) return TS_OK;
-  IvfGuard g(h->device);
+  TsDeviceGuard g(h->device);
   return ts_index_search(h->quant, queries, nq, q_dtype, nprobe, out_scores, out_lists, 0, stream);
 }
 
@@ -1196,11 +1148,11 @@ static int ivf_dense(ts_ivf* h, int nq, int qh, int k, float* out_s, int64_t* ou
   const int64_t N = h->nblocks * 32;
   const int64_t chunk_rows = std::min<int64_t>(kIvfDenseChunkRows, N);
   const int64_t nch = (N + chunk_rows - 1) / chunk_rows;
-  TS_CHECK(ivf_ensure(h->dense, (size_t)nq * chunk_rows * 4));
-  TS_CHECK(ivf_ensure(h->mids, (size_t)nq * chunk_rows * 4));
+  TS_CHECK(ts_buf_ensure(h->dense, (size_t)nq * chunk_rows * 4));
+  TS_CHECK(ts_buf_ensure(h->mids, (size_t)nq * chunk_rows * 4));
   if (nch > 1) {
-    TS_CHECK(ivf_ensure(h->list_score, (size_t)nq * nch * k * 4));
-    TS_CHECK(ivf_ensure(h->list_id, (size_t)nq * nch * k * 4));
+    TS_CHECK(ts_buf_ensure(h->list_score, (size_t)nq * nch * k * 4));
+    TS_CHECK(ts_buf_ensure(h->list_id, (size_t)nq * nch * k * 4));
   }
   for (int64_t c = 0; c < nch; ++c) {
     const int64_t row0 = c * chunk_rows;
@@ -1262,9 +1214,9 @@ static int ivf_pass(ts_ivf* h, const void* dq, int nq, int q_dtype, int k, int n
   const int qh = nq > 32 ? 2 : 1;
   const int pw = h->pwords;
   // (1) the probed lists (the quantizer's exact top-nprobe), the probe bitmaps and their union
-  TS_CHECK(ivf_ensure(h->pid, (size_t)TS_MAX_Q * nprobe * 8));
-  TS_CHECK(ivf_ensure(h->pscore, (size_t)TS_MAX_Q * nprobe * 4));
-  TS_CHECK(ivf_ensure(h->bits, (size_t)(TS_MAX_Q + 1) * pw * 4));
+  TS_CHECK(ts_buf_ensure(h->pid, (size_t)TS_MAX_Q * nprobe * 8));
+  TS_CHECK(ts_buf_ensure(h->pscore, (size_t)TS_MAX_Q * nprobe * 4));
+  TS_CHECK(ts_buf_ensure(h->bits, (size_t)(TS_MAX_Q + 1) * pw * 4));
   TS_CHECK(ts_index_search(h->quant, dq, nq, q_dtype, nprobe, (float*)h->pscore.p, (int64_t*)h->pid.p, 0, s));
   TS_HIP(hipMemsetAsync(h->bits.p, 0, (size_t)(TS_MAX_Q + 1) * pw * 4, s));
   TS_HIP(hipMemsetAsync(h->nlive(), 0, 4, s));
@@ -1272,7 +1224,7 @@ static int ivf_pass(ts_ivf* h, const void* dq, int nq, int q_dtype, int k, int n
   hipLaunchKernelGGL(ivf_probe_bits_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, s,
                      (const int64_t*)h->pid.p, nq, nprobe, pw, (uint32_t*)h->bits.p);
   TS_HIP(hipGetLastError());
-  TS_CHECK(ivf_ensure(h->qimg, (size_t)h->L.kg * 2 * 1024));
+  TS_CHECK(ts_buf_ensure(h->qimg, (size_t)h->L.kg * 2 * 1024));
   TS_CHECK(ts_launch_qprep(h->L, dq, q_dtype, nq, qh, (uint4*)h->qimg.p, h->cand_cnt(), h->status(), s));
   const int64_t N = h->nblocks * 32;
   const bool filter = k <= kIvfMaxFilterK && N >= kIvfMinFilterSlots;
@@ -1283,7 +1235,7 @@ static int ivf_pass(ts_ivf* h, const void* dq, int nq, int q_dtype, int k, int n
     return TS_OK;
   }
   // (2) the live list: occupied blocks of a list some query of the pass probes
-  TS_CHECK(ivf_ensure(h->live, (size_t)h->nblocks * 4));
+  TS_CHECK(ts_buf_ensure(h->live, (size_t)h->nblocks * 4));
   hipLaunchKernelGGL(ivf_live_kernel, dim3((unsigned)((h->nblocks + 255) / 256)), dim3(256), 0, s,
                      (const int32_t*)h->blk_list.p, (const uint32_t*)h->blk_valid.p, h->nblocks,
                      (const uint32_t*)h->bits.p + (size_t)TS_MAX_Q * pw, (int32_t*)h->live.p, h->nlive());
@@ -1291,7 +1243,7 @@ static int ivf_pass(ts_ivf* h, const void* dq, int nq, int q_dtype, int k, int n
   // (3) dense scores of a strided sample of the live list, (4) per-query thresholds from its probed rows
   const int64_t sitems = std::min<int64_t>(h->nblocks, std::max<int64_t>(kIvfMinSampleBlocks, h->nblocks / kIvfSampleDiv));
   const int64_t sld = sitems * 32;   // (bounds the device-side item count: nlive <= nblocks)
-  TS_CHECK(ivf_ensure(h->sample, (size_t)nq * sld * 4));
+  TS_CHECK(ts_buf_ensure(h->sample, (size_t)nq * sld * 4));
   IvfScanParams ip{};
   ip.corpus = (const uint4*)h->corpus.p;
   ip.qimg = (const uint4*)h->qimg.p;
@@ -1319,8 +1271,8 @@ static int ivf_pass(ts_ivf* h, const void* dq, int nq, int q_dtype, int k, int n
                      kIvfMinSampleRank, h->tau(), h->need(), h->host_rep_dev + 65);
   TS_HIP(hipGetLastError());
   // (5) the filter scan over the live list
-  TS_CHECK(ivf_ensure(h->cand_score, (size_t)TS_MAX_Q * kIvfCandCap * 4));
-  TS_CHECK(ivf_ensure(h->cand_id, (size_t)TS_MAX_Q * kIvfCandCap * 4));
+  TS_CHECK(ts_buf_ensure(h->cand_score, (size_t)TS_MAX_Q * kIvfCandCap * 4));
+  TS_CHECK(ts_buf_ensure(h->cand_id, (size_t)TS_MAX_Q * kIvfCandCap * 4));
   ip.dense = nullptr;
   ip.tau = h->tau();
   ip.cand_cnt = h->cand_cnt();
@@ -1375,10 +1327,10 @@ extern "C" int ts_ivf_search(ts_ivf* h, const void* queries, int32_t nq, int32_t
   if (nq == 0) return TS_OK;
   if (h->ntotal == 0) { ts_set_error("No documents indexed. Call add_documents() first."); return TS_ERR_EMPTY; }
   nprobe = std::min(nprobe, h->nlist);
-  IvfGuard g(h->device);
+  TsDeviceGuard g(h->device);
   hipStream_t s = (hipStream_t)stream;
   for (int i = 0; i < 4; ++i) h->info[i] = 0;
-  const int qp = ivf_queries_per_pass(h->L);
+  const int qp = ts_queries_per_pass(h->L);
   const size_t qrow = (size_t)h->L.dim * (q_dtype == TS_F32 ? 4 : 2);
   for (int q0 = 0; q0 < nq; q0 += qp) {
     const int c = std::min(qp, nq - q0);

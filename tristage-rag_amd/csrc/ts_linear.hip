@@ -747,10 +747,10 @@ extern "C" int ts_linear_act(const void* w_tiled, const void* x, const void* bia
     return TS_ERR_INVALID;
   }
   // rows of x per workgroup: three quarters of 32 when their whole-K image fits LDS, else two, else one
-  const int qh = fs_lds_bytes(K / 16, 3) <= 160 * 1024 ? 3 : fs_lds_bytes(K / 16, 2) <= 160 * 1024 ? 2 : 1;
+  const int qh = fs_lds_bytes(K / 16, 3) <= TS_LDS_BYTES ? 3 : fs_lds_bytes(K / 16, 2) <= TS_LDS_BYTES ? 2 : 1;
   const int gelu = act;
   const uintptr_t al = reinterpret_cast<uintptr_t>(w_tiled) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out);
-  if ((N % 32) || (K % 128) || fs_lds_bytes(K / 16, qh) > 160 * 1024 || (al & 15) || (reinterpret_cast<uintptr_t>(bias) & 7) ||
+  if ((N % 32) || (K % 128) || fs_lds_bytes(K / 16, qh) > TS_LDS_BYTES || (al & 15) || (reinterpret_cast<uintptr_t>(bias) & 7) ||
       (M + 32 * qh - 1) / (32 * qh) > 0x7fffffff) {
     ts_set_error("linear_act: N = %d (multiple of 32), K = %d (multiple of 128, at most 2176) or alignment not supported", N, K);
     return TS_ERR_UNSUPPORTED;

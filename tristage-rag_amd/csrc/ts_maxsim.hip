@@ -227,11 +227,7 @@ int ts_launch_maxsim(const void* q, int Lq, const void* docs, const int32_t* doc
                      int n_docs, int H, int dtype, int mode, float* out,
                      hipStream_t stream) {
   if (n_docs <= 0) return TS_OK;
-  switch (dtype) {
-    case TS_F32: return launch_maxsim_t<float>((const float*)q, Lq, (const float*)docs, doc_off, starts, lens, n_docs, H, mode, out, stream);
-    case TS_F16: return launch_maxsim_t<_Float16>((const _Float16*)q, Lq, (const _Float16*)docs, doc_off, starts, lens, n_docs, H, mode, out, stream);
-    case TS_BF16: return launch_maxsim_t<__bf16>((const __bf16*)q, Lq, (const __bf16*)docs, doc_off, starts, lens, n_docs, H, mode, out, stream);
-  }
-  ts_set_error("bad dtype %d", dtype);
-  return TS_ERR_INVALID;
+  return ts_typed(q, dtype, "bad dtype %d", [&](auto* qt) -> int {
+    return launch_maxsim_t(qt, Lq, (decltype(qt))docs, doc_off, starts, lens, n_docs, H, mode, out, stream);
+  });
 }

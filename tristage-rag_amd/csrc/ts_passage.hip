@@ -317,7 +317,7 @@ static int psg_launch_t(const PsgParams& p, int pairs, hipStream_t s) {
   using Small = PsgLds<32, PSG_SMALL_LD + 1>;
   using Large = PsgLds<16, PSG_MAX_LD + 1>;
   static_assert(Small::bytes <= 53 * 1024, "three small workgroups per CU");
-  static_assert(Large::bytes <= 160 * 1024, "the large tile fits the CU's LDS");
+  static_assert(Large::bytes <= TS_LDS_BYTES, "the large tile fits the CU's LDS");
   hipLaunchKernelGGL(passage_small_kernel<DT>, dim3(pairs), dim3(PSG_THREADS), Small::bytes, s, p);
   TS_HIP(hipGetLastError());
   static TsDeviceOnce lds_attr;   // per instantiation, per device
@@ -327,21 +327,6 @@ static int psg_launch_t(const PsgParams& p, int pairs, hipStream_t s) {
   TS_HIP(hipGetLastError());
   return TS_OK;
 }
-
-namespace {
-struct PsgDeviceGuard {
-  int prev = -1;
-  bool ok = true;
-  explicit PsgDeviceGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != dev) ok = (hipSetDevice(dev) == hipSuccess);
-  }
-  ~PsgDeviceGuard() {
-    int cur = -1;
-    if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-  }
-};
-}  // namespace
 
 // argument checks shared by both entry points, before any HIP call
 static int psg_check(const char* who, const void* q, const void* store, const void* starts, const void* lens,
@@ -417,7 +402,7 @@ extern "C" int ts_maxsim_passages_indexed_batch(const void* q, const int32_t* q_
   TS_CHECK(psg_check_shape(who, q, store, H, dtype));
   if (nq == 0 || cand_off[nq] == 0) return TS_OK;
 
-  PsgDeviceGuard g(device);
+  TsDeviceGuard g(device);
   if (!g.ok) { ts_set_error("hipSetDevice(%d) failed", device); return TS_ERR_HIP; }
   PsgParams p;
   p.row_bytes = H * (dtype == TS_F32 ? 4 : 2);

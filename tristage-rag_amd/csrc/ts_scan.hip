@@ -328,8 +328,8 @@ int ts_scan_multi_groups(const TsLayout& L) {
 
 uint32_t ts_scan_multi_stage_cap(const TsLayout& L, int G) {
   const size_t fixed = (size_t)L.kg * G * 1024 + sizeof(StageMultiHdr);
-  if (G < 1 || G > TS_MAX_GROUPS || fixed + 8 * (size_t)TS_MULTI_MIN_STAGE > 160 * 1024) return 0;
-  return (uint32_t)std::min<size_t>(TS_MULTI_MAX_STAGE, (160 * 1024 - fixed) / 8);
+  if (G < 1 || G > TS_MAX_GROUPS || fixed + 8 * (size_t)TS_MULTI_MIN_STAGE > TS_LDS_BYTES) return 0;
+  return (uint32_t)std::min<size_t>(TS_MULTI_MAX_STAGE, (TS_LDS_BYTES - fixed) / 8);
 }
 
 // the grid of ts_launch_scan_multi: at most num_cus workgroups of SCAN_WAVES waves
@@ -804,8 +804,8 @@ int ts_scan_wide_groups(const TsLayout& L) {
 uint32_t ts_scan_wide_stage_cap(const TsLayout& L, int G) {
   (void)L;   // the windows do not depend on the dimension
   const size_t fixed = (size_t)2 * G * TS_RING * 1024 + sizeof(StageWideHdr);
-  if (G < 2 || G > TS_WIDE_GROUPS || fixed + 8 * (size_t)TS_WIDE_MIN_STAGE > 160 * 1024) return 0;
-  return (uint32_t)std::min<size_t>(TS_WIDE_MAX_STAGE, (160 * 1024 - fixed) / 8);
+  if (G < 2 || G > TS_WIDE_GROUPS || fixed + 8 * (size_t)TS_WIDE_MIN_STAGE > TS_LDS_BYTES) return 0;
+  return (uint32_t)std::min<size_t>(TS_WIDE_MAX_STAGE, (TS_LDS_BYTES - fixed) / 8);
 }
 
 bool ts_scan_wide_fits(int64_t nblk, int num_cus) {
@@ -870,9 +870,9 @@ bool ts_use_f32_split(const TsLayout& L, int qh) {
   if (off) return false;
 #endif
   const size_t s = ts_scan_f32s_lds_bytes(L);
-  if (s == 0 || s > 160 * 1024) return false;
+  if (s == 0 || s > TS_LDS_BYTES) return false;
   // only where the exact-f32 kernel could not take 64 queries per pass anyway
-  return (size_t)L.kg * 2 * 1024 + sizeof(StageLds) > 160 * 1024;
+  return (size_t)L.kg * 2 * 1024 + sizeof(StageLds) > TS_LDS_BYTES;
 }
 
 size_t ts_scan_lds_bytes(const TsLayout& L, int qh) {
@@ -888,52 +888,20 @@ template <int DT> using OpDense = OpNoLds<DT>;
 template <int DT> using OpDense = Op16<DT>;
 #endif
 
-template <int DT, int QH, int MODE>
-static int launch_scan_t(const TsLayout& L, const ScanParams& p, int num_cus,
-                         hipStream_t stream) {
-  const size_t lds = (size_t)L.kg * QH * 1024 + (MODE == SCAN_FILTER ? sizeof(StageLds) : 0);
-  // The fused scan is HBM-bound with one 8-wave workgroup per CU (more waves measured
-  // slower: 16 waves/CU -1.5 %); the short dense scans (sample, small corpora) are
-  // latency-bound and take a second workgroup per CU when LDS allows.
-  const int wg_per_cu = (MODE == SCAN_DENSE && 2 * lds <= 160 * 1024) ? 2 : 1;
-  return launch_scan_ring<QH, MODE, OpDense<DT>, WalkStrided>(
-      p, lds, ts_scan_grid(p.nwork, (int64_t)num_cus * wg_per_cu), stream);
-}
-
-// p.nwork: every row block (the live count is only known on the device; waves past it leave at once)
-template <int DT, int QH>
-static int launch_scan_masked_t(const TsLayout& L, const MaskedScanParams& p, int num_cus, hipStream_t stream) {
-  return launch_scan_ring<QH, SCAN_FILTER, Op16<DT>, WalkLive>(p, (size_t)L.kg * QH * 1024 + sizeof(StageLds),
-                                                              ts_scan_grid(p.nwork, num_cus), stream);
-}
-
 int ts_launch_scan_masked(const TsLayout& L, int qh, const MaskedScanParams& p, int num_cus, hipStream_t stream) {
   if (p.nwork <= 0) return TS_OK;
   if (L.dtype == TS_FP8_E4M3) return ts_launch_scan_masked_fp8(L, qh, p, num_cus, stream);
   if (L.dtype == TS_MXFP4_E2M1) return ts_launch_scan_masked_fp4(L, qh, p, num_cus, stream);
-  if (ts_scan_lds_bytes(L, qh) > 160 * 1024) {
+  if (ts_scan_lds_bytes(L, qh) > TS_LDS_BYTES) {
     ts_set_error("dimension %d too large for the LDS-resident query image", L.dim);
     return TS_ERR_UNSUPPORTED;
   }
   switch (L.dtype) {   // (fp32 storage: filtered searches take the dense path)
-    case TS_F16: return qh == 1 ? launch_scan_masked_t<TS_F16, 1>(L, p, num_cus, stream)
-                                : launch_scan_masked_t<TS_F16, 2>(L, p, num_cus, stream);
-    case TS_BF16: return qh == 1 ? launch_scan_masked_t<TS_BF16, 1>(L, p, num_cus, stream)
-                                 : launch_scan_masked_t<TS_BF16, 2>(L, p, num_cus, stream);
+    case TS_F16: return launch_scan<Op16<TS_F16>, WalkLive>(SCAN_FILTER, qh, L.kg, p, num_cus, stream);
+    case TS_BF16: return launch_scan<Op16<TS_BF16>, WalkLive>(SCAN_FILTER, qh, L.kg, p, num_cus, stream);
   }
   ts_set_error("the masked scan takes f16 / bf16 storage only");
   return TS_ERR_UNSUPPORTED;
-}
-
-template <int DT>
-static int launch_scan_dt(const TsLayout& L, int mode, int qh,
-                          const ScanParams& p, int num_cus, hipStream_t s) {
-  if (qh == 1) {
-    return mode == SCAN_DENSE ? launch_scan_t<DT, 1, SCAN_DENSE>(L, p, num_cus, s)
-                              : launch_scan_t<DT, 1, SCAN_FILTER>(L, p, num_cus, s);
-  }
-  return mode == SCAN_DENSE ? launch_scan_t<DT, 2, SCAN_DENSE>(L, p, num_cus, s)
-                            : launch_scan_t<DT, 2, SCAN_FILTER>(L, p, num_cus, s);
 }
 
 int ts_launch_scan(const TsLayout& L, int mode, int qh, const ScanParams& p,
@@ -942,14 +910,14 @@ int ts_launch_scan(const TsLayout& L, int mode, int qh, const ScanParams& p,
   if (L.dtype == TS_FP8_E4M3) return ts_launch_scan_fp8(L, mode, qh, p, num_cus, stream);
   if (L.dtype == TS_MXFP4_E2M1) return ts_launch_scan_fp4(L, mode, qh, p, num_cus, stream);
   if (ts_use_f32_split(L, qh)) return ts_launch_scan_f32s(L, mode, p, num_cus, stream);
-  if (ts_scan_lds_bytes(L, qh) > 160 * 1024) {
+  if (ts_scan_lds_bytes(L, qh) > TS_LDS_BYTES) {
     ts_set_error("dimension %d too large for the LDS-resident query image", L.dim);
     return TS_ERR_UNSUPPORTED;
   }
   switch (L.dtype) {
-    case TS_F16: return launch_scan_dt<TS_F16>(L, mode, qh, p, num_cus, stream);
-    case TS_BF16: return launch_scan_dt<TS_BF16>(L, mode, qh, p, num_cus, stream);
-    case TS_F32: return launch_scan_dt<TS_F32>(L, mode, qh, p, num_cus, stream);
+    case TS_F16: return launch_scan<OpDense<TS_F16>, WalkStrided>(mode, qh, L.kg, p, num_cus, stream);
+    case TS_BF16: return launch_scan<OpDense<TS_BF16>, WalkStrided>(mode, qh, L.kg, p, num_cus, stream);
+    case TS_F32: return launch_scan<OpDense<TS_F32>, WalkStrided>(mode, qh, L.kg, p, num_cus, stream);
   }
   ts_set_error("bad dtype %d", L.dtype);
   return TS_ERR_INVALID;
@@ -1077,43 +1045,15 @@ __global__ void relayout_kernel(const TIN* rows, int64_t n, int dim,
   reinterpret_cast<u32x4*>(tiled)[(size_t)(b * kg + g) * 64 + lane] = out;
 }
 
-// den[i] = |row_i| + 1e-8 of n rows (the e4m3 relayout of ts_scan_fp8.hip normalises with the same kernel)
+// den[i] = |row_i| + 1e-8 of n rows: what every normalising relayout divides by
 int ts_launch_row_den(const void* rows, int in_dtype, int64_t n, int dim, float* den, hipStream_t s) {
   const int blocks = (int)((n + 3) / 4);
-  switch (in_dtype) {
-    case TS_F32: hipLaunchKernelGGL(row_den_kernel<float>, dim3(blocks), dim3(256), 0, s, (const float*)rows, n, dim, den); break;
-    case TS_F16: hipLaunchKernelGGL(row_den_kernel<_Float16>, dim3(blocks), dim3(256), 0, s, (const _Float16*)rows, n, dim, den); break;
-    case TS_BF16: hipLaunchKernelGGL(row_den_kernel<__bf16>, dim3(blocks), dim3(256), 0, s, (const __bf16*)rows, n, dim, den); break;
-    default: ts_set_error("bad rows dtype %d", in_dtype); return TS_ERR_INVALID;
-  }
-  TS_HIP(hipGetLastError());
-  return TS_OK;
-}
-
-template <typename TIN>
-static int relayout_t(const TsLayout& L, const TIN* rows, int64_t n, int64_t row0,
-                      uint4* tiled, bool normalize, float* den, hipStream_t s) {
-  if (normalize) {
-    int blocks = (int)((n + 3) / 4);
-    hipLaunchKernelGGL(row_den_kernel<TIN>, dim3(blocks), dim3(256), 0, s, rows, n,
-                       L.dim, den);
+  return ts_typed_rows(rows, in_dtype, [&](auto* r) -> int {
+    typedef typename TsPointee<decltype(r)>::type TIN;
+    hipLaunchKernelGGL(row_den_kernel<TIN>, dim3(blocks), dim3(256), 0, s, r, n, dim, den);
     TS_HIP(hipGetLastError());
-  }
-  const int64_t blk_first = row0 / TS_ROWS_PER_BLOCK;
-  const int64_t blk_last = (row0 + n - 1) / TS_ROWS_PER_BLOCK;
-  const int64_t nwave = (blk_last - blk_first + 1) * L.kg;
-  const int64_t blocks = (nwave + 3) / 4;
-  if (blocks > 0x7fffffffLL) {
-    ts_set_error("add: too many rows in one call");
-    return TS_ERR_INVALID;
-  }
-  hipLaunchKernelGGL(relayout_kernel<TIN>, dim3((unsigned)blocks), dim3(256), 0, s,
-                     rows, n, L.dim, row0, blk_first, nwave, tiled, L.kg, L.dtype,
-                     normalize ? den : (const float*)nullptr,
-                     (int)(L.dtype != TS_F32 && (L.dim % 8) == 0 &&
-                           (reinterpret_cast<uintptr_t>(rows) % (4 * sizeof(TIN) >= 16 ? 32 : 16)) == 0));
-  TS_HIP(hipGetLastError());
-  return TS_OK;
+    return TS_OK;
+  });
 }
 
 int ts_launch_relayout(const TsLayout& L, const void* rows, int in_dtype, int64_t n,
@@ -1124,13 +1064,17 @@ int ts_launch_relayout(const TsLayout& L, const void* rows, int in_dtype, int64_
     return ts_launch_relayout_fp8(L, rows, in_dtype, n, row0, tiled, normalize, den_scratch, stream);
   if (L.dtype == TS_MXFP4_E2M1)
     return ts_launch_relayout_fp4(L, rows, in_dtype, n, row0, tiled, normalize, den_scratch, stream);
-  switch (in_dtype) {
-    case TS_F32: return relayout_t<float>(L, (const float*)rows, n, row0, tiled, normalize, den_scratch, stream);
-    case TS_F16: return relayout_t<_Float16>(L, (const _Float16*)rows, n, row0, tiled, normalize, den_scratch, stream);
-    case TS_BF16: return relayout_t<__bf16>(L, (const __bf16*)rows, n, row0, tiled, normalize, den_scratch, stream);
-  }
-  ts_set_error("bad rows dtype %d", in_dtype);
-  return TS_ERR_INVALID;
+  if (normalize) TS_CHECK(ts_launch_row_den(rows, in_dtype, n, L.dim, den_scratch, stream));
+  return ts_typed_rows(rows, in_dtype, [&](auto* r) -> int {
+    typedef typename TsPointee<decltype(r)>::type TIN;
+    TsRelayoutGeom g;
+    TS_CHECK(ts_relayout_geom(L.dim, L.kg, r, sizeof(TIN), row0, n, g));
+    hipLaunchKernelGGL(relayout_kernel<TIN>, dim3(g.blocks), dim3(256), 0, stream, r, n, L.dim, row0, g.blk_first,
+                       g.nwave, tiled, L.kg, L.dtype, normalize ? den_scratch : (const float*)nullptr,
+                       (int)(L.dtype != TS_F32 && g.vec));   // (f32 storage has no vector path)
+    TS_HIP(hipGetLastError());
+    return TS_OK;
+  });
 }
 
 __global__ void reconstruct_kernel(const uint4* tiled, int64_t row0, int64_t n,
@@ -1171,13 +1115,9 @@ int ts_launch_reconstruct(const TsLayout& L, const uint4* tiled, int64_t row0,
   if (n <= 0) return TS_OK;
   if (L.dtype == TS_FP8_E4M3) return ts_launch_reconstruct_fp8(L, tiled, row0, n, out, stream);
   if (L.dtype == TS_MXFP4_E2M1) return ts_launch_reconstruct_fp4(L, tiled, row0, n, out, stream);
-  const int64_t total = n * L.kg * 2;
-  const int64_t blocks = (total + 255) / 256;
-  if (blocks > 0x7fffffffLL) {
-    ts_set_error("reconstruct: range too large");
-    return TS_ERR_INVALID;
-  }
-  hipLaunchKernelGGL(reconstruct_kernel, dim3((unsigned)blocks), dim3(256), 0, stream,
+  unsigned blocks;
+  TS_CHECK(ts_reconstruct_blocks(n, L.kg, blocks));
+  hipLaunchKernelGGL(reconstruct_kernel, dim3(blocks), dim3(256), 0, stream,
                      tiled, row0, n, L.dim, L.kg, L.dtype, out);
   TS_HIP(hipGetLastError());
   return TS_OK;
@@ -1226,23 +1166,11 @@ int ts_launch_qprep(const TsLayout& L, const void* q, int q_dtype, int nq, int q
   if (ts_use_f32_split(L, qh)) return ts_launch_qprep_f32s(L, q, q_dtype, nq, qimg, cand_cnt, status, stream);
   const int units = L.kg * qh * 64;
   const int blocks = (units + 255) / 256;
-  switch (q_dtype) {
-    case TS_F32:
-      hipLaunchKernelGGL(qprep_kernel<float>, dim3(blocks), dim3(256), 0, stream,
-                         (const float*)q, nq, L.dim, L.kg, qh, L.dtype, qimg, cand_cnt, status);
-      break;
-    case TS_F16:
-      hipLaunchKernelGGL(qprep_kernel<_Float16>, dim3(blocks), dim3(256), 0, stream,
-                         (const _Float16*)q, nq, L.dim, L.kg, qh, L.dtype, qimg, cand_cnt, status);
-      break;
-    case TS_BF16:
-      hipLaunchKernelGGL(qprep_kernel<__bf16>, dim3(blocks), dim3(256), 0, stream,
-                         (const __bf16*)q, nq, L.dim, L.kg, qh, L.dtype, qimg, cand_cnt, status);
-      break;
-    default:
-      ts_set_error("bad query dtype %d", q_dtype);
-      return TS_ERR_INVALID;
-  }
-  TS_HIP(hipGetLastError());
-  return TS_OK;
+  return ts_typed_queries(q, q_dtype, [&](auto* qt) -> int {
+    typedef typename TsPointee<decltype(qt)>::type TIN;
+    hipLaunchKernelGGL(qprep_kernel<TIN>, dim3(blocks), dim3(256), 0, stream, qt, nq, L.dim, L.kg, qh, L.dtype, qimg,
+                       cand_cnt, status);
+    TS_HIP(hipGetLastError());
+    return TS_OK;
+  });
 }

@@ -105,13 +105,6 @@ struct WalkLiveBias : WalkLive {
   }
 };
 
-// p.nwork: every row block (the live count is only known on the device; waves past it leave at once)
-template <int DT, int QH>
-int launch_scan_biased_t(const TsLayout& L, const BiasScanParams& p, int num_cus, hipStream_t stream) {
-  return launch_scan_ring<QH, SCAN_FILTER, Op16<DT>, WalkLiveBias>(p, (size_t)L.kg * QH * 1024 + sizeof(StageLds),
-                                                                  ts_scan_grid(p.nwork, num_cus), stream);
-}
-
 #define BIAS_SEL_THREADS 1024
 #define BIAS_NEG_MAX (-3.402823466e38f)
 
@@ -249,11 +242,10 @@ int ts_launch_scan_biased(const TsLayout& L, int qh, const BiasScanParams& p, in
     ts_set_error("biased scan: %d query halves, bias %p, tail %p", qh, (const void*)p.bias, (const void*)p.bias_tail);
     return TS_ERR_INVALID;
   }
-  if (ts_scan_lds_bytes(L, qh) > 160 * 1024) {
+  if (ts_scan_lds_bytes(L, qh) > TS_LDS_BYTES) {
     ts_set_error("dimension %d too large for the LDS-resident query image", L.dim);
     return TS_ERR_UNSUPPORTED;
   }
-  if (L.dtype == TS_F16)
-    return qh == 1 ? launch_scan_biased_t<TS_F16, 1>(L, p, num_cus, stream) : launch_scan_biased_t<TS_F16, 2>(L, p, num_cus, stream);
-  return qh == 1 ? launch_scan_biased_t<TS_BF16, 1>(L, p, num_cus, stream) : launch_scan_biased_t<TS_BF16, 2>(L, p, num_cus, stream);
+  return L.dtype == TS_F16 ? launch_scan<Op16<TS_F16>, WalkLiveBias>(SCAN_FILTER, qh, L.kg, p, num_cus, stream)
+                           : launch_scan<Op16<TS_BF16>, WalkLiveBias>(SCAN_FILTER, qh, L.kg, p, num_cus, stream);
 }

@@ -462,6 +462,33 @@ static inline int ts_scan_grid(int64_t nwork, int64_t cap) {
   return grid < 1 ? 1 : grid;
 }
 
+// The launch rule of scan_kernel, in plain host arithmetic (no HIP call: tests/test_scan_launch_host.py runs it
+// without a device).  kib: KiB of the query image per query half (32 queries); stage_bytes: sizeof(OP::Stage).
+//   mode   a masked (or biased) walk is filter-only, whatever the caller asks for
+//   LDS    the image, and behind it the survivor staging of a filter scan
+//   admit  a pass of qh halves is taken where its filter form fits the LDS (each file's check, with its own text)
+//   grid   the filter scan is HBM-bound with one 8-wave workgroup per CU (more waves measured slower: 16 waves/CU
+//          -1.5 %); the short dense scans (sample, small corpora) are latency-bound and take a second workgroup per CU
+//          when LDS allows
+struct TsScanGeom {
+  int mode;
+  size_t lds;
+  int grid;
+};
+static inline size_t ts_scan_lds(int kib, int qh, int mode, size_t stage_bytes) {
+  return (size_t)kib * qh * 1024 + (mode == SCAN_FILTER ? stage_bytes : 0);
+}
+static inline bool ts_scan_admits(int kib, int qh, size_t stage_bytes) {
+  return ts_scan_lds(kib, qh, SCAN_FILTER, stage_bytes) <= TS_LDS_BYTES;
+}
+static inline TsScanGeom ts_scan_geom(int kib, int qh, int mode, bool masked, size_t stage_bytes, int64_t nwork,
+                                      int num_cus) {
+  if (masked) mode = SCAN_FILTER;
+  const size_t lds = ts_scan_lds(kib, qh, mode, stage_bytes);
+  const int wg_per_cu = (mode == SCAN_DENSE && 2 * lds <= TS_LDS_BYTES) ? 2 : 1;
+  return {mode, lds, ts_scan_grid(nwork, (int64_t)num_cus * wg_per_cu)};
+}
+
 template <int QH, int MODE, class OP, class WALK>
 static int launch_scan_ring(const typename WALK::Params& p, size_t lds, int grid, hipStream_t stream) {
   auto kern = scan_kernel<QH, MODE, OP, WALK>;
@@ -470,6 +497,21 @@ static int launch_scan_ring(const typename WALK::Params& p, size_t lds, int grid
   hipLaunchKernelGGL(kern, dim3(grid), dim3(SCAN_THREADS), lds, stream, p);
   TS_HIP(hipGetLastError());
   return TS_OK;
+}
+
+// Every launch of scan_kernel: run-time (qh, mode) -> <QH, MODE>, with the geometry above.  A masked walk has no dense
+// instantiation, and its p.nwork is every row block (the live count is only known on the device; waves past it leave
+// at once).  The caller has made its admission check.
+template <class OP, class WALK>
+static int launch_scan(int mode, int qh, int kib, const typename WALK::Params& p, int num_cus, hipStream_t stream) {
+  const TsScanGeom g = ts_scan_geom(kib, qh, mode, WALK::kMasked, sizeof(typename OP::Stage), p.nwork, num_cus);
+  if constexpr (!WALK::kMasked) {
+    if (g.mode == SCAN_DENSE)
+      return qh == 1 ? launch_scan_ring<1, SCAN_DENSE, OP, WALK>(p, g.lds, g.grid, stream)
+                     : launch_scan_ring<2, SCAN_DENSE, OP, WALK>(p, g.lds, g.grid, stream);
+  }
+  return qh == 1 ? launch_scan_ring<1, SCAN_FILTER, OP, WALK>(p, g.lds, g.grid, stream)
+                 : launch_scan_ring<2, SCAN_FILTER, OP, WALK>(p, g.lds, g.grid, stream);
 }
 
 // ------------------------------------------------------------------ layout
@@ -522,5 +564,39 @@ __device__ __forceinline__ int frag_k(int dt, int g, int h, int e) {
   // so that a pair of units is the A operand of one 16-wide k step of the bf16x3 split scan (ts_scan_f32s.hip);
   // the exact-f32 MFMA path does not care about the order (the query image uses the same map)
   return (dt == TS_F32) ? (16 * (g >> 1) + 8 * h + 4 * (g & 1) + e) : (16 * g + 8 * h + e);
+}
+
+// What every relayout kernel walks: one wave per (row block, unit) of the row blocks that rows [row0, row0 + n) touch,
+// `units` units of each, four waves per workgroup.  vec: the 8-element loads of ld8 may be used (rows of whole
+// 8-element groups from a base aligned to 16 bytes, 32 for float rows).
+struct TsRelayoutGeom {
+  int64_t blk_first, nwave;
+  unsigned blocks;
+  int vec;
+};
+static inline int ts_relayout_geom(int dim, int units, const void* rows, size_t elem_bytes, int64_t row0, int64_t n,
+                                   TsRelayoutGeom& g) {
+  g.blk_first = row0 / TS_ROWS_PER_BLOCK;
+  const int64_t blk_last = (row0 + n - 1) / TS_ROWS_PER_BLOCK;
+  g.nwave = (blk_last - g.blk_first + 1) * units;
+  const int64_t blocks = (g.nwave + 3) / 4;
+  if (blocks > 0x7fffffffLL) {
+    ts_set_error("add: too many rows in one call");
+    return TS_ERR_INVALID;
+  }
+  g.blocks = (unsigned)blocks;
+  g.vec = (int)((dim % 8) == 0 && (reinterpret_cast<uintptr_t>(rows) % (4 * elem_bytes >= 16 ? 32 : 16)) == 0);
+  return TS_OK;
+}
+
+// workgroups of a reconstruct kernel: a thread per (row, unit, lane half) of n rows
+static inline int ts_reconstruct_blocks(int64_t n, int units, unsigned& blocks) {
+  const int64_t b = (n * units * 2 + 255) / 256;
+  if (b > 0x7fffffffLL) {
+    ts_set_error("reconstruct: range too large");
+    return TS_ERR_INVALID;
+  }
+  blocks = (unsigned)b;
+  return TS_OK;
 }
 

@@ -217,20 +217,11 @@ int ts_launch_qprep_f32s(const TsLayout& L, const void* q, int q_dtype, int nq, 
   const int ng = L.kg / 2;
   const int units = ng * 3 * 64;
   const int blocks = (units + 255) / 256;
-  switch (q_dtype) {
-    case TS_F32:
-      hipLaunchKernelGGL(qprep_f32s_kernel<float>, dim3(blocks), dim3(256), 0, stream, (const float*)q, nq, L.dim, ng, qimg, cand_cnt, status);
-      break;
-    case TS_F16:
-      hipLaunchKernelGGL(qprep_f32s_kernel<_Float16>, dim3(blocks), dim3(256), 0, stream, (const _Float16*)q, nq, L.dim, ng, qimg, cand_cnt, status);
-      break;
-    case TS_BF16:
-      hipLaunchKernelGGL(qprep_f32s_kernel<__bf16>, dim3(blocks), dim3(256), 0, stream, (const __bf16*)q, nq, L.dim, ng, qimg, cand_cnt, status);
-      break;
-    default:
-      ts_set_error("bad query dtype %d", q_dtype);
-      return TS_ERR_INVALID;
-  }
-  TS_HIP(hipGetLastError());
-  return TS_OK;
+  return ts_typed_queries(q, q_dtype, [&](auto* qt) -> int {
+    typedef typename TsPointee<decltype(qt)>::type TIN;
+    hipLaunchKernelGGL(qprep_f32s_kernel<TIN>, dim3(blocks), dim3(256), 0, stream, qt, nq, L.dim, ng, qimg, cand_cnt,
+                       status);
+    TS_HIP(hipGetLastError());
+    return TS_OK;
+  });
 }

@@ -92,7 +92,7 @@ size_t ts_scan_fp4_lds_bytes(const TsLayout& L, int qh) {
 
 static bool fp4_scan_ok(const TsLayout& L, int kg, int qh) {
   return L.dtype == TS_MXFP4_E2M1 && kg == L.kg && (qh == 1 || qh == 2) && ts_fp4_code_groups(L) % TS_RING == 0 &&
-         ts_fp4_code_groups(L) <= 32 && ts_scan_fp4_lds_bytes(L, qh) <= 160 * 1024;
+         ts_fp4_code_groups(L) <= 32 && ts_scan_fp4_lds_bytes(L, qh) <= TS_LDS_BYTES;
 }
 
 // the kernel's view of the corpus: p.corpus at the first code unit of row block 0, p.kg the code units of a row block
@@ -104,33 +104,13 @@ static P fp4_params(const TsLayout& L, const P& p) {
   return q;
 }
 
-template <int QH, int MODE>
-static int launch_scan_fp4_t(const TsLayout& L, const ScanParams& p, int num_cus, hipStream_t stream) {
-  const size_t lds = (size_t)L.qkg * QH * 1024 + (MODE == SCAN_FILTER ? sizeof(StageLds) : 0);
-  // as ts_scan.hip's launch_scan_t: the short dense scans take a second workgroup per CU when LDS allows
-  const int wg_per_cu = (MODE == SCAN_DENSE && 2 * lds <= 160 * 1024) ? 2 : 1;
-  return launch_scan_ring<QH, MODE, OpFp4, WalkStridedFp4>(fp4_params(L, p), lds,
-                                                           ts_scan_grid(p.nwork, (int64_t)num_cus * wg_per_cu), stream);
-}
-
 int ts_launch_scan_fp4(const TsLayout& L, int mode, int qh, const ScanParams& p, int num_cus, hipStream_t stream) {
   if (p.nwork <= 0) return TS_OK;
   if (!fp4_scan_ok(L, p.kg, qh)) {
     ts_set_error("mxfp4 scan: dimension %d does not fit the LDS-resident query image for %d queries", L.dim, 32 * qh);
     return TS_ERR_UNSUPPORTED;
   }
-  if (qh == 1)
-    return mode == SCAN_DENSE ? launch_scan_fp4_t<1, SCAN_DENSE>(L, p, num_cus, stream)
-                              : launch_scan_fp4_t<1, SCAN_FILTER>(L, p, num_cus, stream);
-  return mode == SCAN_DENSE ? launch_scan_fp4_t<2, SCAN_DENSE>(L, p, num_cus, stream)
-                            : launch_scan_fp4_t<2, SCAN_FILTER>(L, p, num_cus, stream);
-}
-
-// p.nwork: every row block (the live count is only known on the device; waves past it leave at once)
-template <int QH>
-static int launch_scan_fp4_masked_t(const TsLayout& L, const MaskedScanParams& p, int num_cus, hipStream_t stream) {
-  return launch_scan_ring<QH, SCAN_FILTER, OpFp4, WalkLiveFp4>(fp4_params(L, p), ts_scan_fp4_lds_bytes(L, QH),
-                                                               ts_scan_grid(p.nwork, num_cus), stream);
+  return launch_scan<OpFp4, WalkStridedFp4>(mode, qh, L.qkg, fp4_params(L, p), num_cus, stream);
 }
 
 int ts_launch_scan_masked_fp4(const TsLayout& L, int qh, const MaskedScanParams& p, int num_cus, hipStream_t stream) {
@@ -140,8 +120,7 @@ int ts_launch_scan_masked_fp4(const TsLayout& L, int qh, const MaskedScanParams&
                  32 * qh);
     return TS_ERR_UNSUPPORTED;
   }
-  return qh == 1 ? launch_scan_fp4_masked_t<1>(L, p, num_cus, stream)
-                 : launch_scan_fp4_masked_t<2>(L, p, num_cus, stream);
+  return launch_scan<OpFp4, WalkLiveFp4>(SCAN_FILTER, qh, L.qkg, fp4_params(L, p), num_cus, stream);
 }
 
 // ------------------------------------------------------------------ query image
@@ -247,41 +226,20 @@ __global__ void relayout_fp4_kernel(const TIN* rows, int64_t n, int dim, int64_t
   reinterpret_cast<uint8_t*>(tiled)[((blk_unit + (g >> 4)) * 64 + lane) * 16 + (g & 15)] = (uint8_t)(be + 127);
 }
 
-template <typename TIN> constexpr int fp4_rows_dtype = TS_F32;
-template <> constexpr int fp4_rows_dtype<_Float16> = TS_F16;
-template <> constexpr int fp4_rows_dtype<__bf16> = TS_BF16;
-
-template <typename TIN>
-static int relayout_fp4_t(const TsLayout& L, const TIN* rows, int64_t n, int64_t row0, uint4* tiled, bool normalize,
-                          float* den, hipStream_t s) {
-  if (normalize) TS_CHECK(ts_launch_row_den(rows, fp4_rows_dtype<TIN>, n, L.dim, den, s));
-  const int ng = ts_fp4_code_groups(L), ns = ts_fp4_scale_units(L);
-  const int64_t blk_first = row0 / TS_ROWS_PER_BLOCK;
-  const int64_t blk_last = (row0 + n - 1) / TS_ROWS_PER_BLOCK;
-  const int64_t nwave = (blk_last - blk_first + 1) * ng;
-  const int64_t blocks = (nwave + 3) / 4;
-  if (blocks > 0x7fffffffLL) {
-    ts_set_error("add: too many rows in one call");
-    return TS_ERR_INVALID;
-  }
-  const int vec = (int)((L.dim % 8) == 0 &&
-                        (reinterpret_cast<uintptr_t>(rows) % (4 * sizeof(TIN) >= 16 ? 32 : 16)) == 0);
-  hipLaunchKernelGGL(relayout_fp4_kernel<TIN>, dim3((unsigned)blocks), dim3(256), 0, s, rows, n, L.dim, row0,
-                     blk_first, nwave, tiled, ng, ns, normalize ? den : (const float*)nullptr, vec);
-  TS_HIP(hipGetLastError());
-  return TS_OK;
-}
-
 int ts_launch_relayout_fp4(const TsLayout& L, const void* rows, int in_dtype, int64_t n, int64_t row0, uint4* tiled,
                            bool normalize, float* den_scratch, hipStream_t stream) {
   if (n <= 0) return TS_OK;
-  switch (in_dtype) {
-    case TS_F32: return relayout_fp4_t<float>(L, (const float*)rows, n, row0, tiled, normalize, den_scratch, stream);
-    case TS_F16: return relayout_fp4_t<_Float16>(L, (const _Float16*)rows, n, row0, tiled, normalize, den_scratch, stream);
-    case TS_BF16: return relayout_fp4_t<__bf16>(L, (const __bf16*)rows, n, row0, tiled, normalize, den_scratch, stream);
-  }
-  ts_set_error("bad rows dtype %d", in_dtype);
-  return TS_ERR_INVALID;
+  if (normalize) TS_CHECK(ts_launch_row_den(rows, in_dtype, n, L.dim, den_scratch, stream));
+  const int ng = ts_fp4_code_groups(L), ns = ts_fp4_scale_units(L);
+  return ts_typed_rows(rows, in_dtype, [&](auto* r) -> int {
+    typedef typename TsPointee<decltype(r)>::type TIN;
+    TsRelayoutGeom g;
+    TS_CHECK(ts_relayout_geom(L.dim, ng, r, sizeof(TIN), row0, n, g));
+    hipLaunchKernelGGL(relayout_fp4_kernel<TIN>, dim3(g.blocks), dim3(256), 0, stream, r, n, L.dim, row0, g.blk_first,
+                       g.nwave, tiled, ng, ns, normalize ? den_scratch : (const float*)nullptr, g.vec);
+    TS_HIP(hipGetLastError());
+    return TS_OK;
+  });
 }
 
 // thread per (row, code unit, lane half): the 32 decoded values of one scale block, by integer operations
@@ -311,14 +269,9 @@ int ts_launch_reconstruct_fp4(const TsLayout& L, const uint4* tiled, int64_t row
                               hipStream_t stream) {
   if (n <= 0) return TS_OK;
   const int ng = ts_fp4_code_groups(L), ns = ts_fp4_scale_units(L);
-  const int64_t total = n * ng * 2;
-  const int64_t blocks = (total + 255) / 256;
-  if (blocks > 0x7fffffffLL) {
-    ts_set_error("reconstruct: range too large");
-    return TS_ERR_INVALID;
-  }
-  hipLaunchKernelGGL(reconstruct_fp4_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, tiled, row0, n, L.dim, ng,
-                     ns, out);
+  unsigned blocks;
+  TS_CHECK(ts_reconstruct_blocks(n, ng, blocks));
+  hipLaunchKernelGGL(reconstruct_fp4_kernel, dim3(blocks), dim3(256), 0, stream, tiled, row0, n, L.dim, ng, ns, out);
   TS_HIP(hipGetLastError());
   return TS_OK;
 }

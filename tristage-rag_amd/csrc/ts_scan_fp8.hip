@@ -61,44 +61,23 @@ size_t ts_scan_fp8_lds_bytes(const TsLayout& L, int qh) {
   return (size_t)2 * L.kg * qh * 1024 + sizeof(StageLds);
 }
 
-template <int QH, int MODE>
-static int launch_scan_fp8_t(const TsLayout& L, const ScanParams& p, int num_cus, hipStream_t stream) {
-  const size_t lds = (size_t)2 * L.kg * QH * 1024 + (MODE == SCAN_FILTER ? sizeof(StageLds) : 0);
-  // as ts_scan.hip's launch_scan_t: the short dense scans take a second workgroup per CU when LDS allows
-  const int wg_per_cu = (MODE == SCAN_DENSE && 2 * lds <= 160 * 1024) ? 2 : 1;
-  return launch_scan_ring<QH, MODE, OpFp8, WalkStrided>(p, lds, ts_scan_grid(p.nwork, (int64_t)num_cus * wg_per_cu),
-                                                        stream);
-}
-
 int ts_launch_scan_fp8(const TsLayout& L, int mode, int qh, const ScanParams& p, int num_cus, hipStream_t stream) {
   if (p.nwork <= 0) return TS_OK;
-  if (L.dtype != TS_FP8_E4M3 || p.kg != L.kg || (qh != 1 && qh != 2) || ts_scan_fp8_lds_bytes(L, qh) > 160 * 1024) {
+  if (L.dtype != TS_FP8_E4M3 || p.kg != L.kg || (qh != 1 && qh != 2) || ts_scan_fp8_lds_bytes(L, qh) > TS_LDS_BYTES) {
     ts_set_error("e4m3 scan: dimension %d does not fit the LDS-resident query image for %d queries", L.dim, 32 * qh);
     return TS_ERR_UNSUPPORTED;
   }
-  if (qh == 1)
-    return mode == SCAN_DENSE ? launch_scan_fp8_t<1, SCAN_DENSE>(L, p, num_cus, stream)
-                              : launch_scan_fp8_t<1, SCAN_FILTER>(L, p, num_cus, stream);
-  return mode == SCAN_DENSE ? launch_scan_fp8_t<2, SCAN_DENSE>(L, p, num_cus, stream)
-                            : launch_scan_fp8_t<2, SCAN_FILTER>(L, p, num_cus, stream);
-}
-
-// p.nwork: every row block (the live count is only known on the device; waves past it leave at once)
-template <int QH>
-static int launch_scan_fp8_masked_t(const TsLayout& L, const MaskedScanParams& p, int num_cus, hipStream_t stream) {
-  return launch_scan_ring<QH, SCAN_FILTER, OpFp8, WalkLive>(p, ts_scan_fp8_lds_bytes(L, QH),
-                                                            ts_scan_grid(p.nwork, num_cus), stream);
+  return launch_scan<OpFp8, WalkStrided>(mode, qh, 2 * L.kg, p, num_cus, stream);
 }
 
 int ts_launch_scan_masked_fp8(const TsLayout& L, int qh, const MaskedScanParams& p, int num_cus, hipStream_t stream) {
   if (p.nwork <= 0) return TS_OK;
-  if (L.dtype != TS_FP8_E4M3 || p.kg != L.kg || (qh != 1 && qh != 2) || ts_scan_fp8_lds_bytes(L, qh) > 160 * 1024) {
+  if (L.dtype != TS_FP8_E4M3 || p.kg != L.kg || (qh != 1 && qh != 2) || ts_scan_fp8_lds_bytes(L, qh) > TS_LDS_BYTES) {
     ts_set_error("e4m3 masked scan: dimension %d does not fit the LDS-resident query image for %d queries", L.dim,
                  32 * qh);
     return TS_ERR_UNSUPPORTED;
   }
-  return qh == 1 ? launch_scan_fp8_masked_t<1>(L, p, num_cus, stream)
-                 : launch_scan_fp8_masked_t<2>(L, p, num_cus, stream);
+  return launch_scan<OpFp8, WalkLive>(SCAN_FILTER, qh, 2 * L.kg, p, num_cus, stream);
 }
 
 // ------------------------------------------------------------------ query image
@@ -138,22 +117,13 @@ int ts_launch_qprep_fp8(const TsLayout& L, const void* q, int q_dtype, int nq, i
   const int units = ng * qh * 64;
   const int blocks = (units + 255) / 256;
   const float inv = fp8_pow2(-L.fp8_scale_log2);
-  switch (q_dtype) {
-    case TS_F32:
-      hipLaunchKernelGGL(qprep_fp8_kernel<float>, dim3(blocks), dim3(256), 0, stream, (const float*)q, nq, L.dim, ng, qh, inv, qimg, cand_cnt, status);
-      break;
-    case TS_F16:
-      hipLaunchKernelGGL(qprep_fp8_kernel<_Float16>, dim3(blocks), dim3(256), 0, stream, (const _Float16*)q, nq, L.dim, ng, qh, inv, qimg, cand_cnt, status);
-      break;
-    case TS_BF16:
-      hipLaunchKernelGGL(qprep_fp8_kernel<__bf16>, dim3(blocks), dim3(256), 0, stream, (const __bf16*)q, nq, L.dim, ng, qh, inv, qimg, cand_cnt, status);
-      break;
-    default:
-      ts_set_error("bad query dtype %d", q_dtype);
-      return TS_ERR_INVALID;
-  }
-  TS_HIP(hipGetLastError());
-  return TS_OK;
+  return ts_typed_queries(q, q_dtype, [&](auto* qt) -> int {
+    typedef typename TsPointee<decltype(qt)>::type TIN;
+    hipLaunchKernelGGL(qprep_fp8_kernel<TIN>, dim3(blocks), dim3(256), 0, stream, qt, nq, L.dim, ng, qh, inv, qimg,
+                       cand_cnt, status);
+    TS_HIP(hipGetLastError());
+    return TS_OK;
+  });
 }
 
 // ------------------------------------------------------------------ layout
@@ -225,41 +195,20 @@ __global__ void relayout_fp8_kernel(const TIN* rows, int64_t n, int dim, int64_t
   reinterpret_cast<u32x4*>(tiled)[(size_t)(b * kg + g) * 64 + lane] = out;
 }
 
-template <typename TIN> constexpr int fp8_rows_dtype = TS_F32;
-template <> constexpr int fp8_rows_dtype<_Float16> = TS_F16;
-template <> constexpr int fp8_rows_dtype<__bf16> = TS_BF16;
-
-template <typename TIN>
-static int relayout_fp8_t(const TsLayout& L, const TIN* rows, int64_t n, int64_t row0, uint4* tiled, bool normalize,
-                          float* den, hipStream_t s) {
-  if (normalize) TS_CHECK(ts_launch_row_den(rows, fp8_rows_dtype<TIN>, n, L.dim, den, s));
-  const int64_t blk_first = row0 / TS_ROWS_PER_BLOCK;
-  const int64_t blk_last = (row0 + n - 1) / TS_ROWS_PER_BLOCK;
-  const int64_t nwave = (blk_last - blk_first + 1) * L.kg;
-  const int64_t blocks = (nwave + 3) / 4;
-  if (blocks > 0x7fffffffLL) {
-    ts_set_error("add: too many rows in one call");
-    return TS_ERR_INVALID;
-  }
-  const int vec = (int)((L.dim % 8) == 0 &&
-                        (reinterpret_cast<uintptr_t>(rows) % (4 * sizeof(TIN) >= 16 ? 32 : 16)) == 0);
-  hipLaunchKernelGGL(relayout_fp8_kernel<TIN>, dim3((unsigned)blocks), dim3(256), 0, s, rows, n, L.dim, row0,
-                     blk_first, nwave, tiled, L.kg, fp8_pow2(L.fp8_scale_log2),
-                     normalize ? den : (const float*)nullptr, vec);
-  TS_HIP(hipGetLastError());
-  return TS_OK;
-}
-
 int ts_launch_relayout_fp8(const TsLayout& L, const void* rows, int in_dtype, int64_t n, int64_t row0, uint4* tiled,
                            bool normalize, float* den_scratch, hipStream_t stream) {
   if (n <= 0) return TS_OK;
-  switch (in_dtype) {
-    case TS_F32: return relayout_fp8_t<float>(L, (const float*)rows, n, row0, tiled, normalize, den_scratch, stream);
-    case TS_F16: return relayout_fp8_t<_Float16>(L, (const _Float16*)rows, n, row0, tiled, normalize, den_scratch, stream);
-    case TS_BF16: return relayout_fp8_t<__bf16>(L, (const __bf16*)rows, n, row0, tiled, normalize, den_scratch, stream);
-  }
-  ts_set_error("bad rows dtype %d", in_dtype);
-  return TS_ERR_INVALID;
+  if (normalize) TS_CHECK(ts_launch_row_den(rows, in_dtype, n, L.dim, den_scratch, stream));
+  return ts_typed_rows(rows, in_dtype, [&](auto* r) -> int {
+    typedef typename TsPointee<decltype(r)>::type TIN;
+    TsRelayoutGeom g;
+    TS_CHECK(ts_relayout_geom(L.dim, L.kg, r, sizeof(TIN), row0, n, g));
+    hipLaunchKernelGGL(relayout_fp8_kernel<TIN>, dim3(g.blocks), dim3(256), 0, stream, r, n, L.dim, row0, g.blk_first,
+                       g.nwave, tiled, L.kg, fp8_pow2(L.fp8_scale_log2),
+                       normalize ? den_scratch : (const float*)nullptr, g.vec);
+    TS_HIP(hipGetLastError());
+    return TS_OK;
+  });
 }
 
 // thread per (row, 16-byte unit): the decoded values e4m3 * 2^-s (exact in f32)
@@ -286,14 +235,10 @@ __global__ void reconstruct_fp8_kernel(const uint4* tiled, int64_t row0, int64_t
 int ts_launch_reconstruct_fp8(const TsLayout& L, const uint4* tiled, int64_t row0, int64_t n, float* out,
                               hipStream_t stream) {
   if (n <= 0) return TS_OK;
-  const int64_t total = n * L.kg * 2;
-  const int64_t blocks = (total + 255) / 256;
-  if (blocks > 0x7fffffffLL) {
-    ts_set_error("reconstruct: range too large");
-    return TS_ERR_INVALID;
-  }
-  hipLaunchKernelGGL(reconstruct_fp8_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, tiled, row0, n, L.dim,
-                     L.kg, fp8_pow2(-L.fp8_scale_log2), out);
+  unsigned blocks;
+  TS_CHECK(ts_reconstruct_blocks(n, L.kg, blocks));
+  hipLaunchKernelGGL(reconstruct_fp8_kernel, dim3(blocks), dim3(256), 0, stream, tiled, row0, n, L.dim, L.kg,
+                     fp8_pow2(-L.fp8_scale_log2), out);
   TS_HIP(hipGetLastError());
   return TS_OK;
 }

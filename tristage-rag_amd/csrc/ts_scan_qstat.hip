@@ -402,8 +402,8 @@ int ts_scan_qstat_groups(const TsLayout& L) {
 uint32_t ts_scan_qstat_stage_cap(const TsLayout& L) {
   if (qstat_nwin(L) == 0) return 0;
   const size_t fixed = (size_t)qstat_depth(L) * TS_QSTAT_WINDOW + sizeof(StageQstatHdr);
-  if (fixed + 8 * (size_t)TS_QSTAT_MIN_STAGE > 160 * 1024) return 0;
-  return (uint32_t)((160 * 1024 - fixed) / 8);
+  if (fixed + 8 * (size_t)TS_QSTAT_MIN_STAGE > TS_LDS_BYTES) return 0;
+  return (uint32_t)((TS_LDS_BYTES - fixed) / 8);
 }
 
 bool ts_scan_qstat_fits(int64_t nblk, int num_cus) {
